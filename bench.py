@@ -1,9 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the MI355X sphere-tracing render path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 (N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`,
 one rank per GPU, RCCL through torch.distributed.)
+
+A plain run sets up, warms up, times the K steps and prints the result line; `--full` adds everything marked [full]
+below, each taking runs of its own after the timed region.  `--dump-outputs DIR` (N = 1) writes the last timed frame's
+buffers and diagnostics to DIR/*.npy (a seeded sample of 2^20 pixels for larger frames), so that two builds can be
+compared output for output.
 
 A step = one frame of BASELINE.json's metric workload (C3: Dense Sphere Grid, 125 spheres,
 3840x2160, sphere tracing + BVH, iteration-heatmap shader): render + fused shade into
@@ -21,22 +26,23 @@ overlaps the following frames.  Every frame is still rendered, shaded and reduce
 
 Rank 0 prints ONE JSON line (contract in the task statement).  What each number is:
   value / ms_per_step   K frames with S frames in flight / wall time of the timed region (max over ranks)
-  value_serial          the same frames strictly one after the other (S = 1), timed right after the timed region
+  value_serial          [full] the same frames strictly one after the other (S = 1), timed right after the timed region
   setup_frames          untimed frames run BEFORE the W warm-up frames (one per stream: a stream's first launch creates
                         its hardware queue); 0 when W >= S
-  roofline              the render kernel ALONE: achieved = algorithmic bytes per launch / kernel_ms, where kernel_ms
+  roofline              [full] the render kernel ALONE: achieved = algorithmic bytes per launch / kernel_ms, where kernel_ms
                         is the mean duration of serial launches (HIP events on the launch stream); frac = achieved /
-                        peak.  The overlapped figure (bytes x launches / wall time) is `achieved_in_flight`.
+                        peak.  The overlapped figure (bytes x launches / wall time) is `achieved_in_flight`.  Without
+                        --full only the timed region's launches are measured (kernel_ms = their mean duration).
                         traffic = FETCH_SIZE + WRITE_SIZE per launch and valu = the instruction mix priced with the
                         measured issue costs, both from profiles/r03/pmc_<workload>.json -- used only if that file was
                         measured on the kernel sources now in the tree (source hash) with the options of this run.
-  frames_verified       after the timed region every buffer set that was in flight (the last frame rendered into each of
+  frames_verified       [full] after the timed region every buffer set that was in flight (the last frame rendered into each of
                         the S sets, with the in-flight options and the tail-ramp values of the timed burst) is hashed
                         (SHA-256, all five buffers) against tests/golden/golden.json; the count of sets that match.  A
                         mismatch makes the run fail.
   host_enqueue_ms       host time this rank spent enqueueing one frame (render, gather, fan-in calls), mean over the
                         timed region; at N > 1 one value per rank
-  cpu_baseline          the reference's policy on this box's host cores: oracle/rm_oracle.js (the JS restatement; the
+  cpu_baseline          [full] the reference's policy on this box's host cores: oracle/rm_oracle.js (the JS restatement; the
                         reference itself cannot run here) on node worker_threads, N = max(1, min(4, cores - 1)) workers,
                         contiguous ceil(H/N)-row tiles, whole frames after a warm-up (main.ts:318,444-449), plus the C
                         port on all cores.  The only leg that loads oracle/.
@@ -59,6 +65,8 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0   # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 ALG_BYTES_PER_PIXEL = 12  # depth 1 + normal 3 + sdfEval 2 + iters 2 + RGBA 4, ~0 read
 PROFILE_DIR = os.path.join(ROOT, "profiles", "r03")
+DUMP_MAX_PIXELS = 1 << 20  # --dump-outputs: 10 values per pixel in float32, ~40 MB at most
+DUMP_SEED = 0x5EED
 
 WORKLOADS = {
     "C2": dict(name="C2: Grid of Spheres (9), 1920x1080, sphere-tracing + BVH, Phong shader",
@@ -121,6 +129,30 @@ def load_pmc(workload, options):
         return None, "stale: %s was measured with options %s, this run uses %s" % (
             os.path.relpath(path, ROOT), pj.get("options"), options)
     return pj, os.path.relpath(path, ROOT)
+
+
+def dump_outputs(out_dir, bufs, diag, W, H):
+    """--dump-outputs: the five buffers of one frame as a caller of the render path receives them (per pixel: depth,
+    normal xyz, sdfEval, iterations, RGBA) and its diagnostics, one .npy file each.  A frame of more than DUMP_MAX_PIXELS
+    pixels is sampled: the same seeded pixel indices in every run (pixel_index.npy)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n_px = W * H
+    if n_px <= DUMP_MAX_PIXELS:
+        idx = np.arange(n_px, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_px, DUMP_MAX_PIXELS, replace=False))
+    sel = torch.from_numpy(idx).to(bufs["depth"].device)
+    u16 = lambda t: t[sel].cpu().numpy().view(np.uint16).astype(np.float32)  # noqa: E731  (uint16 counters in int16 storage)
+    arrays = {"pixel_index": idx.astype(np.float64),
+              "depth": bufs["depth"][sel].cpu().numpy().astype(np.float32),
+              "normal": bufs["normal"].view(n_px, 3)[sel].cpu().numpy().astype(np.float32),
+              "sdf_evals": u16(bufs["sdf"]), "iterations": u16(bufs["iters"]),
+              "rgba": bufs["rgba"].view(n_px, 4)[sel].cpu().numpy().astype(np.float32),
+              "diagnostics": np.array([diag[k] for k in ("total_sdf", "total_iters", "max_sdf", "min_sdf")], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def cpu_baseline_port(wl, frames=5):
@@ -234,7 +266,16 @@ def main():
     ap.add_argument("--frames-in-flight", type=int, default=12,
                     help="frames enqueued concurrently, each on its own HIP stream with its own buffers: the tail of a "
                          "frame's persistent kernel (its slowest rays) overlaps the next frames; 1 = strictly serial")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure as well: the golden check of the in-flight buffer sets, the "
+                         "launch alone and the serial frame rate (roofline), the PMC figures and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed region write what its last frame computed to DIR/<name>.npy (float32 / float64; "
+                         "frames larger than %d pixels: a fixed, seeded sample of pixels, listed in pixel_index.npy)"
+                         % DUMP_MAX_PIXELS)
     args = ap.parse_args()
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit("--dump-outputs: one GPU only")
 
     # stdout carries exactly one line, the JSON record: libraries that write to file descriptor 1 themselves (RCCL prints
     # a five-line version banner there when a process group starts) are sent to stderr until that line is printed
@@ -592,12 +633,14 @@ def main():
         except Exception as e:  # noqa: BLE001
             fail(e)
     kernel_in_flight = ctx.last_kernel()
+    if args.dump_outputs:  # before anything below renders into a buffer set again
+        dump_outputs(args.dump_outputs, sets[(frame_no[0] - 1) % S], ctx.decode_acc(last_acc[0]), W, H)
 
-    # The timed configuration checks itself: every buffer set that was in flight holds the last frame
-    # rendered into it -- with the in-flight options, and for the last sets the tail-ramp values -- and all five buffers of
-    # every set must hash to the committed golden fixtures of this workload (C = JS oracle agreement, tests/golden/).
+    # With --full: the timed configuration checks itself: every buffer set that was in flight holds the last
+    # frame rendered into it -- with the in-flight options, and for the last sets the tail-ramp values -- and all five buffers
+    # of every set must hash to the committed golden fixtures of this workload (C = JS oracle agreement, tests/golden/).
     frames_verified, verify_note = None, None
-    if world == 1 and not args.analytics_sweep and not args.no_verify and "golden" in wl:
+    if world == 1 and args.full and not args.analytics_sweep and not args.no_verify and "golden" in wl:
         with open(os.path.join(ROOT, "tests", "golden", "golden.json")) as f:
             gold = json.load(f)[wl["golden"]]["sha256"]
         used = min(S, frame_no[0])
@@ -634,9 +677,10 @@ def main():
     bytes_per_launch = ALG_BYTES_PER_PIXEL * px_per_launch
 
     # The launch running ALONE (library defaults, serial, HIP events around each launch) and the strictly serial frame
-    # rate (render + reduce back to back on one stream), both right after the timed region.  N = 1 only.
+    # rate (render + reduce back to back on one stream), both right after the timed region.  N = 1 and --full only.
     kern_ms, value_serial, kernel_alone, kern_ms_cold = kern_ms_in_flight, None, kernel_in_flight, None
-    if world == 1 and not args.analytics_sweep:
+    alone = world == 1 and args.full and not args.analytics_sweep
+    if alone:
         b = sets[0]
         apply_opts(False)
         ser = []
@@ -682,9 +726,9 @@ def main():
 
     # HBM traffic and the VALU mix of the dominant kernel: PMC counters cannot be read from inside this process; the
     # per-launch figures come from profiles/r03/pmc_<workload>.json, which scripts/profile_r02.sh measured with rocprofv3
-    # on serial launches (library defaults) -- used only if measured on the sources now in the tree, N = 1.
+    # on serial launches (library defaults) -- used only if measured on the sources now in the tree, N = 1, --full.
     traffic, valu, pmc_note = None, None, None
-    if world == 1:
+    if world == 1 and args.full:
         pj, pmc_note = load_pmc(args.workload, user_opts)
         if pj:
             traffic = pj.get("traffic_bytes")
@@ -722,7 +766,7 @@ def main():
                                                       "after the timed region; by default (option lpt) a launch hands out its work "
                                                       "items longest-first using the item costs the previous launch recorded -- "
                                                       "kernel_ms_first_launch is the launch without such costs"
-                                                      if world == 1 and not args.analytics_sweep else "the timed region's launches"),
+                                                      if alone else "the timed region's launches"),
                          "achieved_in_flight": achieved_in_flight, "frac_in_flight": achieved_in_flight / HBM_PEAK_GBPS,
                          "kernel_in_flight": kernel_in_flight, "kernel_ms_in_flight": kern_ms_in_flight,
                          "frames_in_flight": S, "in_flight_options": {k: v for k, (v, _) in in_flight_opts.items()},
@@ -736,7 +780,7 @@ def main():
         }
         if root_balance:
             out["config"]["root_balance"] = root_balance
-        if world > 1:
+        if world > 1 and args.full:
             # outside the timed region: the gathered, reassembled frame must equal this frame
             # rendered whole on rank 0's GPU, byte for byte
             full = {"rgba": u8(4 * W * H), "sdf": u8(2 * W * H), "iters": u8(2 * W * H)}
@@ -764,7 +808,7 @@ def main():
                 {"yaw": round(y, 6), "avg_sdf_calls": ctx.decode_acc(a)["total_sdf"] / (W * H),
                  "avg_iterations": ctx.decode_acc(a)["total_iters"] / (W * H), "max_sdf_calls": ctx.decode_acc(a)["max_sdf"],
                  ("frame_ms" if S == 1 else "frame_ms_overlapped"): e0.elapsed_time(e1)} for (y, a), (e0, e1) in zip(series, ev_pairs)]
-        if world == 1 and not args.no_cpu_baseline and not args.analytics_sweep:
+        if world == 1 and args.full and not args.no_cpu_baseline and not args.analytics_sweep:
             out["cpu_baseline"] = cpu_baseline_port(wl)
             js = cpu_baseline_js_pool(wl)
             if js:

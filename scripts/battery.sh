@@ -28,7 +28,7 @@ make -s -C cpu_raymarcher_amd/csrc asm > gpurun_out/asm.log 2>&1 && python scrip
 tail -3 gpurun_out/price_valu.log
 line() {  # name, bench args...
   local name=$1; shift
-  timeout -k 10 400 python bench.py "$@" > $P/bench_$name.json 2> $O/bench_$name.err || echo "bench $name failed"
+  timeout -k 10 400 python bench.py --full "$@" > $P/bench_$name.json 2> $O/bench_$name.err || echo "bench $name failed"
   python - $P/bench_$name.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

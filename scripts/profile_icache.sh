@@ -5,7 +5,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/prof_icache
 rm -rf $OUT && mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --output-format csv -d $OUT/pmc -- python3 $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --frames-in-flight 1 > $OUT/run.log 2>&1 || { tail -5 $OUT/run.log; exit 1; }
+rocprofv3 --pmc SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY --output-format csv -d $OUT/pmc -- python3 $R/bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --frames-in-flight 1 > $OUT/run.log 2>&1 || { tail -5 $OUT/run.log; exit 1; }
 python3 - "$OUT" <<'PY'
 import csv, glob, sys, collections
 agg = collections.defaultdict(lambda: [0.0, 0])

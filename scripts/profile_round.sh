@@ -12,7 +12,7 @@ export RM_ROUND=$RND
 OUT=$R/gpurun_out/prof_${RND}_$WL
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--workload $WL --frames-in-flight 1 --steps 6 --warmup 2 --no-cpu-baseline --no-verify $@"
+ARGS="--full --workload $WL --frames-in-flight 1 --steps 6 --warmup 2 --no-cpu-baseline --no-verify $@"
 echo "$ARGS" > $OUT/bench_args.txt
 run() {  # name, rocprofv3 args...
   local name=$1; shift

@@ -11,7 +11,10 @@ traversal order, the interval state machine, the octree descent and skip rule, t
 marchers' step rules, shading, diagnostics) produces the same bytes as the reference's own statements do.
 
 Nothing from the reference is written anywhere: stdout carries digests and OK / MISMATCH lines only.
-usage: python scripts/ref_crosscheck.py [--quick] [--report profiles/r02/ref_crosscheck.txt]"""
+--record FILE stores what the reference flow produced (digests and counter sums, nothing else) for the configurations run
+and for STRIPPER_CASES; --recorded FILE compares the oracle with such a recording instead of running the reference flow, so
+the check needs neither node nor the reference sources (tests/golden/ref_crosscheck.json, tests/test_ref_crosscheck.py).
+usage: python scripts/ref_crosscheck.py [--quick] [--report profiles/r02/ref_crosscheck.txt] [--record FILE | --recorded FILE]"""
 import argparse
 import hashlib
 import json
@@ -25,6 +28,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 REF = "/root/reference/src"
 RUN = os.path.join(ROOT, "scripts", "ref_crosscheck", "run.js")
+# one small frame per marcher / shader pair: every module of the render path must survive the type stripper
+STRIPPER_CASES = [("%s/%s" % (alg, shader), dict(preset=9, accel="Octree", width=24, height=16, algorithm=alg, shader=shader))
+                  for alg, shader in (("fixed-step", "phong"), ("adaptive-step", "sdf-heatmap"),
+                                      ("adaptive-step-v2", "iteration-heatmap"), ("adaptive-step-v3", "normal"))]
 
 
 def reference_flow(cfg, timeout=1800):
@@ -82,21 +89,37 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--report")
+    ap.add_argument("--record", help="write the reference flow's results to this JSON file")
+    ap.add_argument("--recorded", help="take the reference flow's results from this JSON file instead of running it")
     args = ap.parse_args()
-    if not os.path.isdir(REF) or shutil.which("node") is None:
+    recorded = None
+    if args.recorded:
+        with open(args.recorded) as f:
+            recorded = json.load(f)["cases"]
+    elif not os.path.isdir(REF) or shutil.which("node") is None:
         print("reference sources or node not present: nothing to cross-check")
         return 0
+    record = {"cases": {}, "stripper": {}}
     from oracle import oracle as O
     O.build()
     golden = json.load(open(os.path.join(ROOT, "tests", "golden", "golden.json")))
     lines, bad = [], 0
     for name, cfg, fixture in cases(args.quick):
-        try:
-            ref = reference_flow(cfg)
-        except subprocess.CalledProcessError as e:
-            lines.append("ERROR     %s: the reference flow did not run (exit %d)" % (name, e.returncode))
-            bad += 1
-            continue
+        if recorded is not None:
+            rec = recorded.get(name)
+            if rec is None or rec["config"] != cfg:
+                lines.append("ERROR     %s: not in the recording %s" % (name, args.recorded))
+                bad += 1
+                continue
+            ref = rec["reference"]
+        else:
+            try:
+                ref = reference_flow(cfg)
+            except subprocess.CalledProcessError as e:
+                lines.append("ERROR     %s: the reference flow did not run (exit %d)" % (name, e.returncode))
+                bad += 1
+                continue
+        record["cases"][name] = {"config": cfg, "reference": ref}
         orc = oracle_flow(O, cfg)
         keys = ["depth", "normal", "sdf", "iters", "rgba"]
         diff = [k for k in keys if ref["sha256"][k] != orc["sha256"][k]]
@@ -114,6 +137,12 @@ def main():
         print(lines[-1], flush=True)
     summary = "%d configurations, %d differ" % (len(lines), bad)
     print(summary)
+    if args.record:
+        for name, cfg in STRIPPER_CASES:
+            record["stripper"][name] = {"config": cfg, "reference": reference_flow(cfg, timeout=300)}
+        with open(args.record, "w") as f:
+            json.dump(record, f, indent=1, sort_keys=True)
+            f.write("\n")
     if args.report:
         with open(args.report, "w") as f:
             f.write("# scripts/ref_crosscheck.py: the reference's own control flow (type-stripped in memory, restated gl-matrix underneath) against\n"

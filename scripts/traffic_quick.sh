@@ -4,7 +4,7 @@ W=$1; shift
 R=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$R/gpurun_out/trq_$W; rm -rf $OUT; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-ARGS="--workload $W --frames-in-flight 1 --steps 6 --warmup 2 --no-cpu-baseline $@"
+ARGS="--full --workload $W --frames-in-flight 1 --steps 6 --warmup 2 --no-cpu-baseline $@"
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/p1 -- python3 $R/bench.py $ARGS > $OUT/p1.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $OUT/p2 -- python3 $R/bench.py $ARGS > $OUT/p2.log 2>&1
 python3 - $OUT $W <<'PY'

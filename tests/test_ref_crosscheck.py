@@ -1,37 +1,42 @@
-"""Build-container only (skipped wherever /root/reference or node is absent, e.g. on the GPU box): the reference's own
-TypeScript control flow -- read as text at run time, type syntax removed in memory, a restated gl-matrix underneath --
-must produce the oracle's bytes (scripts/ref_crosscheck.py).  Not a reference build; it does not pin parity
-(DESIGN.md 5), it guards the oracle's reading of bvh.ts / octree.ts / scene.ts / the marchers against misreadings."""
+"""The reference's own TypeScript control flow -- type syntax removed in memory, a restated gl-matrix underneath -- must
+produce the oracle's bytes (scripts/ref_crosscheck.py).  What that flow produced (SHA-256 of the five buffers and the
+counter sums per configuration, nothing else) is recorded in tests/golden/ref_crosscheck.json by
+`scripts/ref_crosscheck.py --quick --record tests/golden/ref_crosscheck.json`, so these tests need neither node nor the
+reference sources.  Not a reference build; it does not pin parity, it guards the oracle's reading of
+bvh.ts / octree.ts / scene.ts / the marchers against misreadings."""
+import importlib.util
+import json
 import os
-import shutil
 import subprocess
 import sys
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-pytestmark = pytest.mark.skipif(not os.path.isdir("/root/reference/src") or shutil.which("node") is None,
-                                reason="reference sources / node not present (build container only)")
+SCRIPT = os.path.join(ROOT, "scripts", "ref_crosscheck.py")
+RECORDED = os.path.join(ROOT, "tests", "golden", "ref_crosscheck.json")
 
 
 def test_reference_control_flow_matches_the_oracle():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "scripts", "ref_crosscheck.py"), "--quick"], stdout=subprocess.PIPE,
+    p = subprocess.run([sys.executable, SCRIPT, "--quick", "--recorded", RECORDED], stdout=subprocess.PIPE,
                        stderr=subprocess.STDOUT, timeout=1500)
     out = p.stdout.decode()
     assert p.returncode == 0, out
     assert "8 configurations, 0 differ" in out, out
 
 
-def test_type_stripper_leaves_no_type_syntax():
-    """Every module of the render path compiles after stripping (run.js exits 3 otherwise) for each marcher and shader."""
-    import json
-    import tempfile
-    for alg, shader in (("fixed-step", "phong"), ("adaptive-step", "sdf-heatmap"), ("adaptive-step-v2", "iteration-heatmap"),
-                        ("adaptive-step-v3", "normal")):
-        with tempfile.TemporaryDirectory() as td:
-            cfg = os.path.join(td, "c.json")
-            json.dump(dict(preset=9, accel="Octree", width=24, height=16, algorithm=alg, shader=shader), open(cfg, "w"))
-            out = subprocess.check_output(["node", os.path.join(ROOT, "scripts", "ref_crosscheck", "run.js"), "/root/reference/src", cfg],
-                                          timeout=300)
-            assert json.loads(out)["n_objects"] > 0
+def test_type_stripper_leaves_no_type_syntax(oracle):
+    """Every module of the render path compiled after stripping (run.js exits 3 otherwise) for each marcher and shader,
+    built the scene, and rendered what the oracle renders."""
+    spec = importlib.util.spec_from_file_location("ref_crosscheck", SCRIPT)
+    rc = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rc)
+    with open(RECORDED) as f:
+        recorded = json.load(f)["stripper"]
+    assert len(rc.STRIPPER_CASES) == 4
+    for name, cfg in rc.STRIPPER_CASES:
+        rec = recorded[name]
+        assert rec["config"] == cfg, name
+        ref = rec["reference"]
+        assert ref["n_objects"] > 0, name
+        orc = rc.oracle_flow(oracle, cfg)
+        assert orc["sha256"] == ref["sha256"], name
+        assert all(orc[k] == ref[k] for k in ("total_sdf", "total_iters", "max_sdf", "min_sdf")), name
