@@ -44,6 +44,11 @@ class rm_job(C.Structure):  # include/rm_raymarch.h: struct rm_job
                 ("overshoot_factor", C.c_double), ("step_size", C.c_double)]
 
 
+class rm_ray_query(C.Structure):  # include/rm_raymarch.h: struct rm_ray_query
+    _fields_ = [("algorithm", C.c_int32), ("normal", C.c_int32), ("time", C.c_double),
+                ("overshoot_factor", C.c_double), ("step_size", C.c_double)]
+
+
 class rm_scene_info(C.Structure):
     _fields_ = [("n_prims", C.c_int32), ("accel", C.c_int32), ("preset_index", C.c_int32),
                 ("bvh_nodes", C.c_int32), ("bvh_leaves", C.c_int32), ("bvh_depth", C.c_int32),
@@ -90,6 +95,9 @@ SIGNATURES = {
     "rm_scene_get_info": (C.c_int, [_VP, C.POINTER(rm_scene_info)]),
     "rm_camera_from_angles": (C.c_int, [C.c_double, C.c_double, _VP, _VP]),
     "rm_scene_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
+    "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),
     "rm_render_tile": (C.c_int, [_VP, C.POINTER(rm_job), _VP, _VP, _VP, _VP]),
     "rm_render_tile_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_render_stripes_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, C.c_int32, C.c_int32, C.c_int32,

@@ -162,6 +162,53 @@ class Context:
         N.check(self._h, N.lib().rm_scene_distance(self._h, _ptr(p), len(p), _ptr(dist), _ptr(cnt)))
         return dist, cnt
 
+    def ray_march(self, origins, directions, algorithm="sphere-tracer", normal=True, time=0.0, overshoot=None, step=None):
+        """Raymarcher.rayMarch (+ getNormal at hits when `normal`) for caller-supplied rays through the active scene
+        (rm_ray_march).  origins, directions: float32 [n, 3] (directions are used as given, not normalised).  Returns
+        (t float64[n], iters uint32[n], sdf_calls uint32[n], normal float32[n, 3]); counts are exact (the reference's
+        Uint16Array buffers hold them mod 65536).  numpy input -> the host entry (synchronous); torch CUDA tensors ->
+        rm_ray_march_device on torch's current stream, outputs allocated on the same device -- there iters and sdf_calls are
+        int32 tensors holding the u32 bits (torch's uint32 tensors support few operations; the counts stay below 2^31).  `algorithm`: a name of
+        ALGORITHMS or an rm_algorithm value; overshoot / step None mirror JS `undefined` (1.2 / 0.1)."""
+        q = N.rm_ray_query()
+        q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
+        q.normal = 1 if normal else 0
+        q.time = float(time)
+        q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
+        q.step_size = float(step) if step is not None else float("nan")
+        if _is_torch(origins) or _is_torch(directions):
+            import torch
+            if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
+                raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
+            self._same_device(dict(origins=origins, directions=directions))
+            if origins.device != directions.device:
+                raise ValueError("origins and directions are on different devices")
+            for name, b in (("origins", origins), ("directions", directions)):
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
+                    raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
+            n = origins.numel() // 3
+            if directions.numel() != 3 * n:
+                raise ValueError("origins and directions differ in length")
+            dev = origins.device
+            t = torch.empty(n, dtype=torch.float64, device=dev)
+            it = torch.empty(n, dtype=torch.int32, device=dev)  # the u32 counts as int32 tensors (same bits; counts stay < 2^31)
+            sdf = torch.empty(n, dtype=torch.int32, device=dev)
+            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
+            N.check(self._h, N.lib().rm_ray_march_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
+                                                         _ptr(sdf), _ptr(nrm), _current_stream_ptr()))
+            return t, it, sdf, nrm
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        n = len(o)
+        t = np.zeros(n, np.float64)
+        it = np.zeros(n, np.uint32)
+        sdf = np.zeros(n, np.uint32)
+        nrm = np.zeros((n, 3), np.float32)
+        N.check(self._h, N.lib().rm_ray_march(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm)))
+        return t, it, sdf, nrm
+
     # ---- render ---------------------------------------------------------------------
     def _attach_diag(self, diag):
         """rm_render_attach_diagnostics for the render call that follows: `diag` is a CUDA tensor of 32 bytes that
@@ -380,6 +427,19 @@ def camera_from_angles(pitch, yaw):
     if rc != N.RM_OK:
         raise N.RmError(rc, "rm_camera_from_angles")
     return rot, org
+
+
+def camera_rays(width, height, pitch, yaw, y_start=0, y_end=None):
+    """rm_camera_rays: the rays runRaymarcher casts for rows [y_start, y_end) of a width x height frame
+    (raymarcher.ts:61-88) -> (origin float32[3], directions float32[(y_end - y_start) * width, 3])."""
+    if y_end is None:
+        y_end = height
+    org = np.zeros(3, np.float32)
+    dirs = np.zeros((max(0, int(y_end) - int(y_start)) * max(0, int(width)), 3), np.float32)
+    rc = N.lib().rm_camera_rays(int(width), int(height), float(pitch), float(yaw), int(y_start), int(y_end), _ptr(org), _ptr(dirs))
+    if rc != N.RM_OK:
+        raise N.RmError(rc, "rm_camera_rays")
+    return org, dirs
 
 
 def deal_stripes(rows, stripe_rows, n_parts, weights=None):

@@ -775,6 +775,40 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
 
 int norm_shader(int s) { return (s >= RM_SHADE_NORMAL && s <= RM_SHADE_ITERATION_HEATMAP) ? s : RM_SHADE_NORMAL; }
 
+// The parameter block of a ray query: what a one-ray-per-lane render launch of the ACTIVE scene reads (fill_params with a job
+// that names that scene, so every knob applies as it does there), the query's marcher, step rules and time.  A query is pure:
+// unlike a render it leaves the scene's time (rm_scene_set_time, what rm_scene_distance uses) as it was.  No run-time
+// specialised kernel: cast_kernel is ahead-of-time only.
+int fill_query_params(rm_ctx *ctx, const rm_ray_query *q, RmRenderParams &p) {
+    const double scene_time = ctx->time;
+    rm_job job;
+    std::memset(&job, 0, sizeof job);
+    job.width = 1;
+    job.height = 1;
+    job.y_end = 1;
+    job.time = q->time;
+    const bool known = q->algorithm >= RM_ALG_SPHERE_TRACER && q->algorithm <= RM_ALG_ADAPTIVE_STEP_V3;
+    job.algorithm = known ? q->algorithm : RM_ALG_SPHERE_TRACER;  // raymarchWorker.ts:49-68: the default branch
+    job.scene_preset_index = ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset;
+    job.acceleration_structure = ctx->host.accel;
+    job.overshoot_factor = q->overshoot_factor;
+    job.step_size = q->step_size;
+    const int rc = fill_params(ctx, &job, p);
+    ctx->time = scene_time;  // (fill_params stores the job's time there: raymarcher.ts:58-59 belongs to runRaymarcher only)
+    p.rtc_function = nullptr;
+    return rc;
+}
+
+// the checks rm_ray_march and rm_ray_march_device share
+int check_query(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs) {
+    if (!q) return fail(ctx, RM_E_INVALID, "null query");
+    if (n < 0 || n > std::numeric_limits<int32_t>::max()) return fail(ctx, RM_E_INVALID, "ray count out of range");
+    if (n > 0 && (!origins || !dirs)) return fail(ctx, RM_E_INVALID, "null ray buffer");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU ray path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1299,6 +1333,86 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
     RM_HIP(ctx, hipMemcpyAsync(dist, base + o_dist, 8 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
     RM_HIP(ctx, hipMemcpyAsync(count, base + o_cnt, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
     RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return RM_OK;
+}
+
+int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
+                        void *d_sdf_calls, void *d_normal, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, d_origins, d_dirs);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_cast_sqrt : rm_launch_cast)(
+                    p, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, static_cast<double *>(d_t),
+                    static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls), static_cast<float *>(d_normal),
+                    static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int rm_ray_march(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
+                 uint32_t *sdf_calls, float *normal_xyz) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
+    if (rc || !n) return rc;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // through the scratch buffer in chunks of at most 4 M rays (52 B per ray: 208 MB), whatever the batch
+    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
+    const size_t c = static_cast<size_t>(chunk);
+    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
+                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), total = o_nrm + align_up(12 * c, 256);
+    rc = ensure_scratch(ctx, total);
+    if (rc) return rc;
+    char *base = static_cast<char *>(ctx->scratch);
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_cast_sqrt : rm_launch_cast)(
+                        p, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
+                        t ? reinterpret_cast<double *>(base + o_t) : nullptr, iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr,
+                        sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr, normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr,
+                        ctx->stream, &ctx->last_kernel));
+        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
+        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
+int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end, float *origin3, float *dirs_xyz) {
+    if (width < 0 || height <= 0 || y_start < 0 || y_end < y_start || y_end > height) return RM_E_INVALID;
+    if (!std::isfinite(pitch) || !std::isfinite(yaw) || !origin3) return RM_E_INVALID;
+    const int64_t npx = static_cast<int64_t>(y_end - y_start) * width;
+    if (npx > 0 && !dirs_xyz) return RM_E_INVALID;
+    float rot[9];
+    rmh::camera_from_angles(pitch, yaw, rot, origin3);
+    for (int32_t y = y_start; y < y_end; ++y) {
+        const double v = (static_cast<double>(y) / height - 0.5) * 2.0;  // raymarcher.ts:73
+        for (int32_t x = 0; x < width; ++x) {
+            const double u = (static_cast<double>(x) / width - 0.5) * 2.0;                        // :83
+            const double ax = static_cast<float>(u), ay = static_cast<float>(v), az = -1.0;       // :84 vec3.fromValues
+            const float dx = static_cast<float>(ax * rot[0] + ay * rot[3] + az * rot[6]);         // :87 vec3.transformMat3
+            const float dy = static_cast<float>(ax * rot[1] + ay * rot[4] + az * rot[7]);
+            const float dz = static_cast<float>(ax * rot[2] + ay * rot[5] + az * rot[8]);
+            double len = static_cast<double>(dx) * dx + static_cast<double>(dy) * dy + static_cast<double>(dz) * dz;  // :88 vec3.normalize
+            if (len > 0) len = 1 / std::sqrt(len);
+            float *o = dirs_xyz + 3 * (static_cast<int64_t>(y - y_start) * width + x);
+            o[0] = static_cast<float>(dx * len);
+            o[1] = static_cast<float>(dy * len);
+            o[2] = static_cast<float>(dz * len);
+        }
+    }
     return RM_OK;
 }
 

@@ -64,6 +64,13 @@ hipError_t rm_launch_distance(const RmRenderParams &p, const float *points, int6
 hipError_t rm_launch_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist,
                                    uint32_t *count, hipStream_t stream);
 
+// Raymarcher.rayMarch (+ getNormal when want_normal) for n caller-supplied rays (origins, dirs: f32[3n]); every output may be
+// null.  *kernel_name (optional) receives the instantiation that was launched (static string).
+hipError_t rm_launch_cast(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
+                          uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_cast_sqrt(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
+                               uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name);
+
 // v2: builds the longest-first item order of the next launch from the previous launch's recorded costs (rm_render_v2.hip)
 hipError_t rm_launch_lpt_sort(const uint8_t *cost_prev, uint16_t *perm, int stride, int tiles_x, int tiles_y, hipStream_t stream);
 

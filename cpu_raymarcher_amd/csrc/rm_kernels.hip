@@ -420,10 +420,10 @@ __device__ bool bvh_next_interval(const RmRenderParams &P, const Ray &r, const R
 
 // ------------------------------------------------------------------ the render kernel
 
+// raymarcher.ts:94-102: the normal at hitPosition = f32(o + d * depth), (0, 0, 0) when depth >= MAX_DIST; getNormal's four
+// evaluations are added to count.  Shared by the render kernels (normal_and_store) and the ray queries (cast_kernel).
 template <int ACCEL, int GEN>
-__device__ double normal_and_store(const RmRenderParams &P, const Ray &ray, double depth, uint32_t &count,
-                                   uint8_t nb[3]) {
-    // raymarcher.ts:94-105
+__device__ __forceinline__ Vec3f hit_normal(const RmRenderParams &P, const Ray &ray, double depth, uint32_t &count) {
     Vec3f hit;
     hit.x = to_f32(static_cast<double>(ray.o.x) + static_cast<double>(ray.d.x) * depth);
     hit.y = to_f32(static_cast<double>(ray.o.y) + static_cast<double>(ray.d.y) * depth);
@@ -448,9 +448,17 @@ __device__ double normal_and_store(const RmRenderParams &P, const Ray &ray, doub
         ny = to_f32(ny * len);
         nz = to_f32(nz * len);
     }
-    nb[0] = u8clamp((static_cast<double>(nx) + 1) * 0.5 * 255);
-    nb[1] = u8clamp((static_cast<double>(ny) + 1) * 0.5 * 255);
-    nb[2] = u8clamp((static_cast<double>(nz) + 1) * 0.5 * 255);
+    return Vec3f{nx, ny, nz};
+}
+
+template <int ACCEL, int GEN>
+__device__ double normal_and_store(const RmRenderParams &P, const Ray &ray, double depth, uint32_t &count,
+                                   uint8_t nb[3]) {
+    // raymarcher.ts:94-105
+    const Vec3f n = hit_normal<ACCEL, GEN>(P, ray, depth, count);
+    nb[0] = u8clamp((static_cast<double>(n.x) + 1) * 0.5 * 255);
+    nb[1] = u8clamp((static_cast<double>(n.y) + 1) * 0.5 * 255);
+    nb[2] = u8clamp((static_cast<double>(n.z) + 1) * 0.5 * 255);
     return depth;
 }
 
@@ -1147,6 +1155,37 @@ __global__ __launch_bounds__(256) void distance_kernel(const RmRenderParams P, c
     distance_body<ACCEL, GEN>(P, pts, n, dist, count);
 }
 
+// Raymarcher.rayMarch (+ getNormal) for caller-supplied rays (rm_ray_march): one ray per lane, in input order.  The march is
+// render_body's (ray_march / ray_march_other, same scene fields, the per-ray BVH hit-leaf list in dynamic LDS); only the ray
+// comes from memory instead of the camera.  Nothing here may assume one origin for all rays: the per-frame octree table of
+// render_kernel_oct, the v2 wave loop's origin-relative boxes and its bundle cull are not used.  The direction is taken as
+// given (rayMarch does not normalise it).  Counts are exact u32: the reference's Uint16Array holds them mod 65536.
+// (Ahead-of-time only: the run-time specialiser's build of this file does not carry it.)
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void cast_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                                   double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray ray;
+    ray.o = Vec3f{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
+    ray.d = Vec3f{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
+    ray.od[0] = static_cast<double>(ray.o.x);  // per lane here (the camera's kernels take it from the parameter block)
+    ray.od[1] = static_cast<double>(ray.o.y);
+    ray.od[2] = static_cast<double>(ray.o.z);
+    uint32_t count = 0, iters = 0;
+    const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters) : ray_march<ACCEL, GEN>(P, ray, count, iters);
+    Vec3f nrm{0.f, 0.f, 0.f};
+    if (want_normal) nrm = hit_normal<ACCEL, GEN>(P, ray, t, count);
+    if (t_out) t_out[i] = t;
+    if (iters_out) iters_out[i] = iters;
+    if (sdf_out) sdf_out[i] = count;
+    if (normal_out) {
+        normal_out[3 * i] = nrm.x;
+        normal_out[3 * i + 1] = nrm.y;
+        normal_out[3 * i + 2] = nrm.z;
+    }
+}
+
 #ifndef RM_LENGTH_SQRT
 __global__ __launch_bounds__(256) void hypot_kernel(const float *xyz, int64_t n, double *out) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -1354,6 +1393,42 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
     else if (p.general) { if (p.accel == 2) RM_DK(2, 1); else if (p.accel == 1) RM_DK(1, 1); else RM_DK(0, 1); }
     else { if (p.accel == 2) RM_DK(2, 0); else if (p.accel == 1) RM_DK(1, 0); else RM_DK(0, 0); }
 #undef RM_DK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_cast)(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
+                                          uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (n <= 0) return hipSuccess;
+    const int threads = 256;
+    const dim3 grid(static_cast<unsigned>((n + threads - 1) / threads)), block(threads);
+    // the LDS of the one-ray-per-lane render launch: expression programs' slots, then the per-ray hit-leaf lists
+    size_t shmem = p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    pl.v1_list_offset = -1;
+    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
+    if (p.accel == 2 && p.v1_lists && p.general < 2 && p.bvh_nodes < 65536 && shmem + list_bytes <= 64 * 1024) {
+        pl.v1_list_offset = static_cast<int32_t>((shmem + 15) & ~static_cast<size_t>(15));
+        shmem = static_cast<size_t>(pl.v1_list_offset) + list_bytes;
+    }
+    const int32_t wn = want_normal ? 1 : 0;
+#define RM_CK(A, O, G)                                                                                                 \
+    {                                                                                                                  \
+        hipLaunchKernelGGL((cast_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, t, iters, sdf, normal); \
+        if (kernel_name) *kernel_name = "cast_kernel<" #A ", " #O ", " #G ">" RM_LEN_TAG;                             \
+    }
+#define RM_CKA(O, G) { if (p.accel == 2) RM_CK(2, O, G) else if (p.accel == 1) RM_CK(1, O, G) else RM_CK(0, O, G) }
+#define RM_CKO(G) { if (p.algorithm == 0) RM_CKA(false, G) else RM_CKA(true, G) }
+    if (p.general == 3) RM_CKO(3)
+    else if (p.general == 2) RM_CKO(2)
+    else if (p.general) RM_CKO(1)
+    else RM_CKO(0)
+#undef RM_CKO
+#undef RM_CKA
+#undef RM_CK
     return hipGetLastError();
 }
 

@@ -57,6 +57,7 @@ class Scene:
         self.camera = Camera()
         self._uploaded = False
         self.currentPresetIndex = 0
+        self.time = 0.0  # Scene.updateTime's value (scene.ts:135-140): what rayMarch / getNormal march with
         self.loadPreset(0)  # scene.ts:28
 
     @property
@@ -87,6 +88,7 @@ class Scene:
 
     def updateTime(self, time):  # scene.ts:135-140
         self.ctx.scene_set_time(time)
+        self.time = float(time)
 
     @property
     def preset_for_job(self):
@@ -146,6 +148,43 @@ class Raymarcher:
         sh = N.lib().rm_shader_from_string(str(shader).encode())
         scene.ctx.render_tile(job, depthBuffer, normalBuffer, SDFevaluationBuffer, iterationsBuffer,
                               rgba=shadedBuffer, shader=sh, diag=diagnostics)
+        scene.time = float(time)  # raymarcher.ts:58-59 scene.updateTime(time)
+
+    def _ray_march(self, scene, origins, directions, normal):
+        scene._activate()
+        return scene.ctx.ray_march(origins, directions, self.algorithm, normal=normal, time=scene.time,
+                                   overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None))
+
+    def rayMarch(self, scene, rayOrigin, direction, idx, SDFevaluationBuffer, iterationsBuffer):
+        """raymarcher.ts:26-33 (the subclass's marcher) for one ray of any origin and direction (rm_ray_march): returns
+        the distance travelled and adds its Scene.getDistance and iteration counts at idx, wrapped as Uint16Array += wraps."""
+        t, it, sdf, _ = self._ray_march(scene, np.asarray(rayOrigin, np.float32).reshape(1, 3),
+                                        np.asarray(direction, np.float32).reshape(1, 3), False)
+        SDFevaluationBuffer[idx] = (int(SDFevaluationBuffer[idx]) + int(sdf[0])) & 0xFFFF
+        iterationsBuffer[idx] = (int(iterationsBuffer[idx]) + int(it[0])) & 0xFFFF
+        return float(t[0])
+
+    def getNormal(self, scene, position, idx, SDFevaluationBuffer):
+        """raymarcher.ts:123-135 from four Scene.getDistance evaluations (rm_scene_distance): the offsets stored to
+        Float32Arrays, the differences to the Float32Array n, vec3.normalize.  Adds the four counts at idx."""
+        scene._activate()
+        scene.ctx.scene_set_time(scene.time)
+        p = np.asarray(position, np.float32).reshape(3)
+        pts = np.repeat(p[None, :], 4, axis=0)
+        for a in range(3):  # vec3.fromValues(position[a] - 0.01, ...)
+            pts[a + 1, a] = np.float32(np.float64(p[a]) - 0.01)
+        dist, cnt = scene.ctx.scene_distance(pts)
+        SDFevaluationBuffer[idx] = (int(SDFevaluationBuffer[idx]) + int(cnt.sum())) & 0xFFFF
+        n = np.float32(dist[0] - dist[1:4])
+        ln = float(np.float64(n[0]) * n[0] + np.float64(n[1]) * n[1] + np.float64(n[2]) * n[2])
+        if ln > 0:
+            ln = 1 / math.sqrt(ln)
+        return np.array([np.float32(np.float64(v) * ln) for v in n], np.float32)
+
+    def rayMarchBatch(self, scene, origins, directions, normal=True):
+        """rayMarch (+ getNormal at hits) for a batch of rays in one call: Context.ray_march with this marcher, its
+        options and the scene's time -> (t, iters, sdf_calls, normal)."""
+        return self._ray_march(scene, origins, directions, normal)
 
 
 class SphereTracer(Raymarcher):  # cpu_algorithms/sphereTracer.ts

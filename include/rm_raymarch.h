@@ -213,6 +213,50 @@ RM_API int rm_camera_from_angles(double pitch, double yaw, float *rot9, float *o
 RM_API int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist,
                              uint32_t *count);
 
+/* ---- ray queries ------------------------------------------------------------------ */
+
+typedef struct rm_ray_query {
+    int32_t algorithm;        /* rm_algorithm; unknown -> sphere tracer (raymarchWorker.ts:49-68)          */
+    int32_t normal;           /* 1: getNormal at hits, its 4 evaluations counted (raymarcher.ts:94-102)     */
+    double  time;             /* Scene.updateTime (AnimatedTranslate) for this query; rm_scene_set_time's value is kept */
+    double  overshoot_factor; /* NaN = JS undefined -> 1.2 */
+    double  step_size;        /* NaN = JS undefined -> 0.1 */
+} rm_ray_query;
+
+/* Raymarcher.rayMarch (+ getNormal) for n caller-supplied rays through the ACTIVE scene (as rm_scene_distance), host
+ * buffers (synchronous).  The marchers of sphereTracer.ts:15-83, fixedStep.ts:21-94, adaptiveStep.ts:22-105,
+ * adaptiveStepV2.ts:22-124 and adaptiveStepV3.ts:22-137 with the scene's acceleration structure (BVH.onRayMarchStart /
+ * onRayMarchStep, bvh.ts:181-240; Octree.marchRay, octree.ts:250-294), exactly as a render marches its camera rays, for
+ * ray i = (origins_xyz[3i..3i+2], dirs_xyz[3i..3i+2]) as Float32Array vec3s.  The direction is used as given: rayMarch
+ * does not normalise it.  Per ray: t[i] = the value rayMarch returns (>= 10 = miss for the sphere tracer; FixedStep /
+ * AdaptiveStep return 10 unless they hit), iters[i] and sdf_calls[i] = the iteration and Scene.getDistance primitive
+ * counts, exact (the reference's Uint16Array buffers hold them mod 65536; with q->normal, sdf_calls includes getNormal's
+ * four evaluations), normal_xyz[3i..3i+2] = the normalised binary32 getNormal result at hitPosition = f32(o + d t)
+ * (raymarcher.ts:94-102,123-135), (0, 0, 0) for t >= 10 or without q->normal.  Every output may be NULL.
+ * RM_E_NO_DEVICE for a host-only context, RM_E_NO_SCENE before any scene, RM_E_INVALID for a null query, n < 0,
+ * n > INT32_MAX, null ray buffers with n > 0 or a non-finite origin or direction component; n == 0 is RM_OK.
+ * Knobs (rm_set_option) apply as for the one-ray-per-lane render and never change results; `length` selects the
+ * vec3.length form.  Scenes whose renders run a run-time specialised kernel are marched by the ahead-of-time kernels
+ * here (same values).  A ray query is not a render call: it neither consumes nor fires rm_render_attach_diagnostics.
+ * rm_last_kernel names the cast_kernel<...> instantiation.  Large batches go through the context's scratch buffer in
+ * chunks of 4 M rays. */
+RM_API int rm_ray_march(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz,
+                        double *t, uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz);
+
+/* Same with device pointers (origins, dirs f32[3n]; t f64[n]; iters, sdf_calls u32[n]; normal f32[3n]; each output may be
+ * NULL), asynchronous on `stream` (a hipStream_t passed as void*, NULL = default stream).  Non-finite input is the
+ * caller's responsibility: it is not checked, and every march loop still ends (they are bounded). */
+RM_API int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs,
+                               void *d_t, void *d_iters, void *d_sdf_calls, void *d_normal, void *stream);
+
+/* The rays runRaymarcher casts for rows [y_start, y_end) of a W x H frame (raymarcher.ts:61-88), host-only, no ctx:
+ * origin3 = the camera position (Camera.setAngles(pitch, yaw) + getPosition, camera.ts:58-69,81-88),
+ * dirs_xyz[3 * (local_row * W + x)] = the binary32 direction after vec3.fromValues(u, v, -1), transformMat3 and
+ * normalize.  Marched with rm_ray_march they give the pixels of that frame.  RM_E_INVALID unless W >= 0, H > 0,
+ * 0 <= y_start <= y_end <= H and the angles are finite. */
+RM_API int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end,
+                          float *origin3, float *dirs_xyz);
+
 /* ---- render -------------------------------------------------------------------- */
 
 /* Replaces the worker's onmessage (raymarchWorker.ts:33-92) = Raymarcher.runRaymarcher
