@@ -170,6 +170,17 @@ class Context:
         rm_ray_march_device on torch's current stream, outputs allocated on the same device -- there iters and sdf_calls are
         int32 tensors holding the u32 bits (torch's uint32 tensors support few operations; the counts stay below 2^31).  `algorithm`: a name of
         ALGORITHMS or an rm_algorithm value; overshoot / step None mirror JS `undefined` (1.2 / 0.1)."""
+        return self._rays(False, origins, directions, algorithm, normal, time, overshoot, step)
+
+    def pick(self, origins, directions, algorithm="sphere-tracer", normal=True, time=0.0, overshoot=None, step=None):
+        """ray_march plus the object each ray hit (rm_ray_pick): returns (t, iters, sdf_calls, normal, object), the first
+        four bit-identical to ray_march's, object int32[n] an index into the scene's objects in the order the scene was
+        built in (-1: none; the rule is in include/rm_raymarch.h).  numpy input -> the host entry; torch CUDA tensors ->
+        rm_ray_pick_device on torch's current stream (object an int32 tensor on the same device)."""
+        return self._rays(True, origins, directions, algorithm, normal, time, overshoot, step)
+
+    def _rays(self, pick, origins, directions, algorithm, normal, time, overshoot, step):
+        """ray_march (pick False) or pick (True)."""
         q = N.rm_ray_query()
         q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
         q.normal = 1 if normal else 0
@@ -194,9 +205,14 @@ class Context:
             it = torch.empty(n, dtype=torch.int32, device=dev)  # the u32 counts as int32 tensors (same bits; counts stay < 2^31)
             sdf = torch.empty(n, dtype=torch.int32, device=dev)
             nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            N.check(self._h, N.lib().rm_ray_march_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
-                                                         _ptr(sdf), _ptr(nrm), _current_stream_ptr()))
-            return t, it, sdf, nrm
+            if not pick:
+                N.check(self._h, N.lib().rm_ray_march_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
+                                                             _ptr(sdf), _ptr(nrm), _current_stream_ptr()))
+                return t, it, sdf, nrm
+            obj = torch.empty(n, dtype=torch.int32, device=dev)
+            N.check(self._h, N.lib().rm_ray_pick_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
+                                                        _ptr(sdf), _ptr(nrm), _ptr(obj), _current_stream_ptr()))
+            return t, it, sdf, nrm, obj
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         if len(o) != len(d):
@@ -206,8 +222,39 @@ class Context:
         it = np.zeros(n, np.uint32)
         sdf = np.zeros(n, np.uint32)
         nrm = np.zeros((n, 3), np.float32)
-        N.check(self._h, N.lib().rm_ray_march(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm)))
-        return t, it, sdf, nrm
+        if not pick:
+            N.check(self._h, N.lib().rm_ray_march(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm)))
+            return t, it, sdf, nrm
+        obj = np.zeros(n, np.int32)
+        N.check(self._h, N.lib().rm_ray_pick(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm), _ptr(obj)))
+        return t, it, sdf, nrm, obj
+
+    def object_ids(self, width, height, pitch=0.0, yaw=0.0, y_start=0, y_end=None, algorithm="sphere-tracer", time=0.0,
+                   device=False):
+        """The object under every pixel of rows [y_start, y_end) of a width x height frame of the active scene (a selection
+        mask or outline without a render kernel): the frame's camera rays (camera_rays) picked without normals ->
+        int32[(y_end - y_start) * width], tile-local rows, row-major, -1 where no object was hit.  device=True: the rays go
+        to rm_ray_pick_device as CUDA tensors of this context's device and the result is one."""
+        if y_end is None:
+            y_end = height
+        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
+        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
+        if not device:
+            return self.pick(o, dirs, algorithm, normal=False, time=time)[4]
+        import torch
+        dev = torch.device("cuda", self.device)
+        return self.pick(torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev), algorithm, normal=False, time=time)[4]
+
+    def scene_object(self, index):
+        """Object `index` of the active scene (rm_scene_object) as (nodes, root): nodes is a list of
+        (type, child_a, child_b, world_to_local float32[16], params float64[6]) in the format OracleScene.nodes() and
+        Scene.loadNodes use, operands before their user, the object's root last (root = len(nodes) - 1)."""
+        n = C.c_int32(0)
+        N.check(self._h, N.lib().rm_scene_object(self._h, int(index), None, 0, C.byref(n)))
+        arr = (N.rm_node * max(1, n.value))()
+        N.check(self._h, N.lib().rm_scene_object(self._h, int(index), arr, n.value, C.byref(n)))
+        return [(int(e.type), int(e.child_a), int(e.child_b), np.array(e.world_to_local, np.float32), np.array(e.params, np.float64))
+                for e in arr[:n.value]]
 
     # ---- render ---------------------------------------------------------------------
     def _attach_diag(self, diag):

@@ -7,9 +7,11 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <map>
 #include <unordered_map>
@@ -44,6 +46,7 @@ struct DeviceScene {
     uint32_t *oct_sub_hdr = nullptr;
     uint8_t *oct_sub_list = nullptr;
     uint16_t *bvh_leaves = nullptr;  // node indices of the non-empty BVH leaves, increasing (v2 bundle cull)
+    int32_t *slot_object = nullptr;  // HostScene::slot_object (null: device slots are object indices)
     int32_t bvh_leaf_count = 0;      // 0: no cull (no BVH, too many leaves, or a leaf box not inside its ancestors')
 };
 
@@ -422,6 +425,7 @@ void free_device_scene(rm_ctx *ctx) {
     (void)hipFree(d.oct_sub_hdr);
     (void)hipFree(d.oct_sub_list);
     (void)hipFree(d.bvh_leaves);
+    (void)hipFree(d.slot_object);
     d = DeviceScene();
 }
 
@@ -496,6 +500,7 @@ int upload_scene(rm_ctx *ctx) {
     if ((rc = upload_vec(ctx, ctx->host.oct_lut, &ctx->dev.oct_lut))) return rc;
     if ((rc = upload_vec(ctx, ctx->host.oct_sub_hdr, &ctx->dev.oct_sub_hdr))) return rc;
     if ((rc = upload_vec(ctx, ctx->host.oct_sub_list, &ctx->dev.oct_sub_list))) return rc;
+    if (!ctx->host.slot_object.empty() && (rc = upload_vec(ctx, ctx->host.slot_object, &ctx->dev.slot_object))) return rc;
     // Leaf table of the bundle cull (rm_render_v2.hip, bvh_prologue_cull).  The cull tests leaves directly, which
     // equals the reference's traversal only if a hit leaf implies hit ancestors: every box must lie inside its
     // parent's, bit for bit (the builder takes unions, so it does; verified here rather than assumed).
@@ -807,6 +812,70 @@ int check_query(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origi
     if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU ray path");
     if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
     return RM_OK;
+}
+
+// Object `index` of the active scene as an rm_scene_from_nodes forest (operands before their user, the object's root last),
+// from the description the scene was built from: the upload as it was given (spheres as sphere leaves at
+// SceneManager.getTransform of their centre), or the preset's objects as the reference holds them -- vec3 members
+// (Box.halfSize, Repetition.spacing, AnimatedTranslate.direction) as their Float32Array values, operators with the
+// Primitive.transform their constructors derive (wrappers: the operand's; unions: identity).  Unused operand indices are -1.
+void object_forest(const rm_ctx *ctx, int index, std::vector<rm_node> &out) {
+    out.clear();
+    auto leaf = [&](int type, const float *m, const double *params, int n_params) {
+        rm_node d;
+        std::memset(&d, 0, sizeof d);
+        d.type = type;
+        d.child_a = d.child_b = -1;
+        std::memcpy(d.world_to_local, m, sizeof d.world_to_local);
+        for (int k = 0; k < n_params; ++k) d.params[k] = params[k];
+        out.push_back(d);
+    };
+    auto sphere = [&](const float *c, double r) {
+        float m[16];
+        rmh::make_transform(c[0], c[1], c[2], nullptr, m);
+        leaf(RM_PRIM_SPHERE, m, &r, 1);
+    };
+    auto forest = [&](const std::vector<rmh::NodeDesc> &nodes, int root, bool as_reference) {
+        std::vector<std::array<float, 16>> T(nodes.size());  // Primitive.transform (rmh Forest::derive_transforms)
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            const rmh::NodeDesc &d = nodes[i];
+            if (d.type < 10 || !as_reference) std::memcpy(T[i].data(), d.m, sizeof d.m);
+            else if (d.type == 11 || d.type == 12) T[i] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+            else T[i] = T[d.a];
+        }
+        std::function<int(int)> emit = [&](int i) -> int {
+            const rmh::NodeDesc &d = nodes[i];
+            const bool binary = d.type == 11 || d.type == 12, op = d.type >= 10;
+            const int a = op ? emit(d.a) : -1, b = binary ? emit(d.b) : -1;
+            double p[6];
+            for (int k = 0; k < 6; ++k) p[k] = d.params[k];
+            if (as_reference && (d.type == 1 || d.type == 14 || d.type == 15))
+                for (int k = 0; k < 3; ++k) p[k] = static_cast<float>(p[k]);
+            leaf(d.type, T[i].data(), p, 6);
+            out.back().child_a = a;
+            out.back().child_b = b;
+            return static_cast<int>(out.size()) - 1;
+        };
+        emit(root);
+    };
+    if (ctx->scene_is_uploaded) {
+        if (ctx->up_program) return forest(ctx->up_nodes, ctx->up_roots[index], false);
+        if (ctx->up_general) {
+            const rmh::PrimDesc &d = ctx->up_prims[index];
+            return leaf(d.type, d.m, d.params, 3);
+        }
+        return sphere(&ctx->up_centers[3 * static_cast<size_t>(index)], ctx->up_radii[index]);
+    }
+    std::vector<rmh::PrimDesc> prims;  // the order ensure_scene builds presets in
+    if (rmh::preset_prims(ctx->scene_preset, prims)) {
+        rmh::PrimDesc d = prims[index];
+        if (d.type == RM_PRIM_BOX)
+            for (double &v : d.params) v = static_cast<float>(v);
+        return leaf(d.type, d.m, d.params, 3);
+    }
+    std::vector<rmh::NodeDesc> nodes;
+    std::vector<int> roots;
+    if (rmh::preset_nodes(ctx->scene_preset, nodes, roots)) forest(nodes, roots[index], true);
 }
 
 }  // namespace
@@ -1413,6 +1482,78 @@ int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int3
             o[2] = static_cast<float>(dz * len);
         }
     }
+    return RM_OK;
+}
+
+int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
+                       void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, d_origins, d_dirs);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_pick_sqrt : rm_launch_pick)(
+                    p, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, ctx->dev.slot_object,
+                    static_cast<double *>(d_t), static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls),
+                    static_cast<float *>(d_normal), static_cast<int32_t *>(d_object), static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
+                uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
+    if (rc || !n) return rc;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // through the scratch buffer in chunks of at most 4 M rays (56 B per ray: 224 MB), as rm_ray_march
+    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
+    const size_t c = static_cast<size_t>(chunk);
+    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
+                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), o_obj = o_nrm + align_up(12 * c, 256),
+                 total = o_obj + align_up(4 * c, 256);
+    rc = ensure_scratch(ctx, total);
+    if (rc) return rc;
+    char *base = static_cast<char *>(ctx->scratch);
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_pick_sqrt : rm_launch_pick)(
+                        p, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
+                        ctx->dev.slot_object, t ? reinterpret_cast<double *>(base + o_t) : nullptr,
+                        iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr, sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr,
+                        normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr, object ? reinterpret_cast<int32_t *>(base + o_obj) : nullptr,
+                        ctx->stream, &ctx->last_kernel));
+        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (object) RM_HIP(ctx, hipMemcpyAsync(object + at, base + o_obj, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
+int rm_scene_object(rm_ctx *ctx, int32_t index, rm_node *nodes, int32_t cap, int32_t *n_nodes) {
+    if (!ctx) return RM_E_INVALID;
+    if (n_nodes) *n_nodes = 0;
+    if (cap < 0 || (cap > 0 && !nodes)) return fail(ctx, RM_E_INVALID, "bad node buffer");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (index < 0 || index >= scene_n_prims(ctx)) return fail(ctx, RM_E_INVALID, "object index out of range");
+    std::vector<rm_node> tree;
+    object_forest(ctx, index, tree);
+    if (tree.empty()) return fail(ctx, RM_E_UNSUPPORTED, "the active scene keeps no description of its objects");
+    const int32_t need = static_cast<int32_t>(tree.size());
+    if (n_nodes) *n_nodes = need;
+    if (need <= cap) std::memcpy(nodes, tree.data(), tree.size() * sizeof(rm_node));
     return RM_OK;
 }
 

@@ -1186,6 +1186,126 @@ __global__ __launch_bounds__(256) void cast_kernel(const RmRenderParams P, const
     }
 }
 
+// ------------------------------------------------------------------ object picking (rm_ray_pick)
+
+// Primitive.sdf of device object `id`, bit-identical to the value the render's Scene.getDistance paths take for it (the
+// filtered loops and the leaf records evaluate the same expressions: sphere_sdf_fast, prim_sdf_general, program_sdf).
+template <int GEN>
+__device__ __forceinline__ double pick_sdf(const RmRenderParams &P, int id, const Vec3f &p) {
+    if (GEN >= 2) {  // one object at a time through the scalar cache: list_min's waterfall over the lanes' distinct ids
+        double d = 0.0;
+        for (bool done = false; !done;) {
+            const int u = __builtin_amdgcn_readfirstlane(id);
+            if (id == u) {
+                d = program_sdf<GEN == 3>(P.prog, P.obj_ranges[2 * u], P.obj_ranges[2 * u + 1], p, P.time, P.prog_slots);
+                done = true;
+            }
+        }
+        return d;
+    }
+    if (GEN == 1) return prim_sdf_general(P.prims[id], p);
+    return sphere_sdf_fast(P.spheres[id], P.radii[id], p);
+}
+
+// The candidates ids[0 .. n) (0 .. n-1 when ids is null) against the running minimum `best` and its object `obj`: the
+// minimum is Scene.getDistance's (start 10; Math.min, which propagates NaN for expression programs, v_min_f64 -- NaN
+// ignored -- for the finite-input primitive records), and obj is the LOWEST object index whose value equals it under IEEE
+// ==, or the lowest NaN one once the minimum is NaN.  Min is order independent, so the walk order does not matter.
+// slot_obj (sphere scenes under the BVH: spheres are stored in leaf order) maps a device slot to its object index.
+template <int GEN>
+__device__ void pick_list(const RmRenderParams &P, const int32_t *ids, int n, const int32_t *slot_obj, const Vec3f &p, double &best,
+                          int &obj) {
+    for (int k = 0; k < n; ++k) {
+        const int id = ids ? ids[k] : k;
+        const double v = pick_sdf<GEN>(P, id, p);
+        const int j = (GEN == 0 && slot_obj) ? slot_obj[id] : id;
+        if (GEN >= 2 && v != v) {
+            obj = (best != best && obj < j) ? obj : j;
+            best = v;
+        } else if (v < best) {
+            best = v;
+            obj = j;
+        } else if (v == best) {
+            obj = (obj >= 0 && obj < j) ? obj : j;
+        }
+    }
+}
+
+// The object a ray hit (include/rm_raymarch.h, rm_ray_pick): -1 for depth >= MAX_DIST, else the lowest-index candidate of
+// Scene.getDistance at hitPosition = f32(o + d * depth) (hit_normal's point) whose Primitive.sdf attains the distance.
+// The candidates are what getDistance evaluates there (scene.ts:144-190): the octree leaf's primitives (none for an empty
+// leaf, all of them outside the cube), the primitives of every BVH leaf whose box contains the point (plain skip-linked
+// walk; all of them when that set is empty), or all.  Not counted: the pick is no part of the reference's work.
+template <int ACCEL, int GEN>
+__device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ray, double depth, const int32_t *slot_obj) {
+    if (depth >= RM_MAX_DIST) return -1;
+    Vec3f hit;
+    hit.x = to_f32(static_cast<double>(ray.o.x) + static_cast<double>(ray.d.x) * depth);
+    hit.y = to_f32(static_cast<double>(ray.o.y) + static_cast<double>(ray.d.y) * depth);
+    hit.z = to_f32(static_cast<double>(ray.o.z) + static_cast<double>(ray.d.z) * depth);
+    double best = RM_MAX_DIST;
+    int obj = -1;
+    if (ACCEL == 1) {
+        const int node = oct_find(P, hit);
+        if (node < 0) pick_list<GEN>(P, nullptr, P.n_prims, slot_obj, hit, best, obj);
+        else {
+            const RmOctNode nd = P.oct[node];
+            if (nd.prim_count > 0) pick_list<GEN>(P, P.oct_prims + nd.prim_first, nd.prim_count, slot_obj, hit, best, obj);
+        }
+        return obj;
+    }
+    if (ACCEL == 2) {
+        int found = 0;
+        for (int i = 0; i < P.bvh_nodes;) {
+            const RmBvhNode node = P.bvh[i];
+            if (!box_contains(node.lo, node.hi, hit)) {
+                i = node.skip;
+                continue;
+            }
+            if (node.leaf < 0) {
+                i = i + 1;
+                continue;
+            }
+            const int first = node.leaf >> 8, cnt = node.leaf & 0xFF;
+            pick_list<GEN>(P, P.bvh_prims + first, cnt, slot_obj, hit, best, obj);
+            found += cnt;
+            i = node.skip;
+        }
+        if (found) return obj;
+    }
+    pick_list<GEN>(P, nullptr, P.n_prims, slot_obj, hit, best, obj);
+    return obj;
+}
+
+// cast_kernel plus the object each ray hit (rm_ray_pick).  t, iters, sdf_calls and the normal are cast_kernel's, bit for
+// bit: the same march, the same hit_normal, and the object pass adds nothing to the count.  (Ahead-of-time only.)
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void pick_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                                   const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out,
+                                                   float *normal_out, int32_t *obj_out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray ray;
+    ray.o = Vec3f{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
+    ray.d = Vec3f{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
+    ray.od[0] = static_cast<double>(ray.o.x);
+    ray.od[1] = static_cast<double>(ray.o.y);
+    ray.od[2] = static_cast<double>(ray.o.z);
+    uint32_t count = 0, iters = 0;
+    const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters) : ray_march<ACCEL, GEN>(P, ray, count, iters);
+    Vec3f nrm{0.f, 0.f, 0.f};
+    if (want_normal) nrm = hit_normal<ACCEL, GEN>(P, ray, t, count);
+    if (t_out) t_out[i] = t;
+    if (iters_out) iters_out[i] = iters;
+    if (sdf_out) sdf_out[i] = count;
+    if (normal_out) {
+        normal_out[3 * i] = nrm.x;
+        normal_out[3 * i + 1] = nrm.y;
+        normal_out[3 * i + 2] = nrm.z;
+    }
+    if (obj_out) obj_out[i] = hit_object<ACCEL, GEN>(P, ray, t, slot_obj);
+}
+
 #ifndef RM_LENGTH_SQRT
 __global__ __launch_bounds__(256) void hypot_kernel(const float *xyz, int64_t n, double *out) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -1429,6 +1549,44 @@ hipError_t RM_LEN_VARIANT(rm_launch_cast)(const RmRenderParams &p, const float *
 #undef RM_CKO
 #undef RM_CKA
 #undef RM_CK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_pick)(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal,
+                                          const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
+                                          hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (n <= 0) return hipSuccess;
+    const int threads = 256;
+    const dim3 grid(static_cast<unsigned>((n + threads - 1) / threads)), block(threads);
+    // the launch rm_launch_cast makes (same LDS layout, same parameter block), so the march is the same
+    size_t shmem = p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    pl.v1_list_offset = -1;
+    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
+    if (p.accel == 2 && p.v1_lists && p.general < 2 && p.bvh_nodes < 65536 && shmem + list_bytes <= 64 * 1024) {
+        pl.v1_list_offset = static_cast<int32_t>((shmem + 15) & ~static_cast<size_t>(15));
+        shmem = static_cast<size_t>(pl.v1_list_offset) + list_bytes;
+    }
+    const int32_t wn = want_normal ? 1 : 0;
+#define RM_PK(A, O, G)                                                                                                 \
+    {                                                                                                                  \
+        hipLaunchKernelGGL((pick_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, slot_obj, t, iters, sdf, \
+                           normal, object);                                                                            \
+        if (kernel_name) *kernel_name = "pick_kernel<" #A ", " #O ", " #G ">" RM_LEN_TAG;                             \
+    }
+#define RM_PKA(O, G) { if (p.accel == 2) RM_PK(2, O, G) else if (p.accel == 1) RM_PK(1, O, G) else RM_PK(0, O, G) }
+#define RM_PKO(G) { if (p.algorithm == 0) RM_PKA(false, G) else RM_PKA(true, G) }
+    if (p.general == 3) RM_PKO(3)
+    else if (p.general == 2) RM_PKO(2)
+    else if (p.general) RM_PKO(1)
+    else RM_PKO(0)
+#undef RM_PKO
+#undef RM_PKA
+#undef RM_PK
     return hipGetLastError();
 }
 

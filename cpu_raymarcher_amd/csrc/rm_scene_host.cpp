@@ -600,7 +600,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
     if (s.accel == 2 && s.bvh_prims.size() == size_t(n) && n > 0) {
         std::vector<RmSphere> sp(n);
         std::vector<double> rd(n);
-        std::vector<int32_t> pos(n, -1);
+        std::vector<int32_t> pos(n, -1), obj(n);
         bool perm = true;
         for (int k = 0; k < n; ++k) {
             const int id = s.bvh_prims[k];
@@ -609,6 +609,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
                 break;
             }
             pos[id] = k;
+            obj[k] = id;
             sp[k] = s.spheres[id];
             rd[k] = s.radii[id];
         }
@@ -618,6 +619,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
             std::iota(s.bvh_prims.begin(), s.bvh_prims.end(), 0);
             for (uint16_t &e : s.nn_list) e = static_cast<uint16_t>(pos[e]);
             s.leaf_order = true;
+            s.slot_object.swap(obj);
         }
     }
     return true;

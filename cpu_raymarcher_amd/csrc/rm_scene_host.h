@@ -49,6 +49,7 @@ struct HostScene {
     std::vector<RmPrim> prims;
     std::vector<float> world_pos; // Primitive.getWorldPosition() per primitive (BVH sort key)
     bool leaf_order = false;      // BVH sphere scenes: spheres / radii are stored in leaf order, bvh_prims is 0..n-1
+    std::vector<int32_t> slot_object;  // with leaf_order: device slot -> object index (the sphere's place in the input list)
     std::vector<RmSphere> spheres;
     std::vector<double> radii;
     std::vector<float> prim_lo, prim_hi;  // padded AABBs, 3 floats per primitive

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .context import Context, _is_torch, partition_rows
+from .context import Context, _is_torch, camera_rays, partition_rows
 
 ALGORITHMS = ("sphere-tracer", "fixed-step", "adaptive-step", "adaptive-step-v2", "adaptive-step-v3")
 SHADERS = ("normal", "phong", "sdf-heatmap", "iteration-heatmap")
@@ -109,6 +109,22 @@ class Scene:
         self._activate()
         return self.ctx.scene_info()
 
+    def getObject(self, i):
+        """Scene.objectSDFs[i] as an expression tree (rm_scene_object): [(type, child_a, child_b, world_to_local, params)],
+        operands first, the object's root last -- what loadNodes takes back (as nodes, roots=[len(nodes) - 1])."""
+        self._activate()
+        return self.ctx.scene_object(i)
+
+    def objectAt(self, x, y, width, height, algorithm="sphere-tracer"):
+        """Index of the object under pixel (x, y) of a width x height frame from this scene's camera at its time
+        (runRaymarcher's ray for that pixel, raymarcher.ts:73,83-88, picked with `algorithm`); -1 when the ray hits nothing."""
+        if not (0 <= int(x) < int(width) and 0 <= int(y) < int(height)):
+            raise ValueError("pixel (%d, %d) is outside the %d x %d frame" % (x, y, width, height))
+        self._activate()
+        org, dirs = camera_rays(int(width), int(height), self.camera.pitch, self.camera.yaw, int(y), int(y) + 1)
+        d = dirs[int(x):int(x) + 1]
+        return int(self.ctx.pick(org.reshape(1, 3), d, algorithm, normal=False, time=self.time)[4][0])
+
     def _activate(self):
         if self._uploaded:
             return  # rm_scene_from_spheres already made it active
@@ -185,6 +201,13 @@ class Raymarcher:
         """rayMarch (+ getNormal at hits) for a batch of rays in one call: Context.ray_march with this marcher, its
         options and the scene's time -> (t, iters, sdf_calls, normal)."""
         return self._ray_march(scene, origins, directions, normal)
+
+    def pickBatch(self, scene, origins, directions, normal=True):
+        """rayMarchBatch plus the object each ray hit (Context.pick with this marcher, its options and the scene's time)
+        -> (t, iters, sdf_calls, normal, object)."""
+        scene._activate()
+        return scene.ctx.pick(origins, directions, self.algorithm, normal=normal, time=scene.time,
+                              overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None))
 
 
 class SphereTracer(Raymarcher):  # cpu_algorithms/sphereTracer.ts

@@ -257,6 +257,42 @@ RM_API int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, co
 RM_API int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end,
                           float *origin3, float *dirs_xyz);
 
+/* ---- picking and read-back of a scene's objects ------------------------------------- */
+
+/* rm_ray_march plus the object each ray hit: the same arguments, the same checks and return codes, and t, iters,
+ * sdf_calls, normal_xyz bit-identical to what rm_ray_march returns for the same rays and query.  object[i] is an index
+ * into the scene's objects (Scene.objectSDFs, scene.ts:16,43) in the order the scene was built in: the order of
+ * sceneManager.ts for a preset, the array index for rm_scene_from_spheres / rm_scene_from_prims, the index into roots[]
+ * for rm_scene_from_nodes -- never a device slot (a BVH stores a sphere list in leaf order).  The rule:
+ *   - t[i] >= 10 (getMaxDistance, the rule raymarcher.ts:98 skips the normal by): -1, nothing is evaluated;
+ *   - else p = hitPosition = f32(o + d t) (vec3.scaleAndAdd, raymarcher.ts:94-95; getNormal's point) and
+ *     D = Scene.getDistance(p).  The candidates are exactly the objects getDistance evaluates at p (scene.ts:144-190):
+ *     Octree: the primitives of the leaf findNode(p) returns (none for an empty leaf; every object outside the cube);
+ *     BVH: getPrimitivesAt(p), every object when that set is empty (scene.ts:173); None: every object.  object[i] is the
+ *     lowest index among the candidates whose primitive.sdf(p) == D (IEEE ==); when D is NaN, the lowest-index candidate
+ *     whose sdf is NaN; -1 when no candidate matches (D from an empty octree leaf's minDistance * 0.99, or the start
+ *     value 10).
+ * The pick is no part of the reference's work: it adds nothing to sdf_calls.  Every output may be NULL.  A pick neither
+ * consumes nor fires rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone; rm_last_kernel names the
+ * pick_kernel<...> instantiation.  Host buffers, synchronous, chunked through the context's scratch buffer. */
+RM_API int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz,
+                       double *t, uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, int32_t *object);
+
+/* Same with device pointers (object: i32[n]), asynchronous on `stream`, as rm_ray_march_device. */
+RM_API int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs,
+                              void *d_t, void *d_iters, void *d_sdf_calls, void *d_normal, void *d_object, void *stream);
+
+/* Reads back object `index` of the active scene as an expression tree in the form rm_scene_from_nodes takes: operands
+ * before their user, the object's root last.  A sphere, box or torus of a list scene is one leaf node (its world_to_local
+ * and params; a sphere of rm_scene_from_spheres at rm_make_transform of its centre).  An uploaded scene comes back as it
+ * was given, in upload order (never in a BVH's leaf order); a preset's objects come back as the reference holds them:
+ * Box.halfSize, Repetition.spacing and AnimatedTranslate.direction as their binary32 values, operators with the
+ * Primitive.transform their constructors derive (Round / Twist / Repetition / AnimatedTranslate: the operand's; the smooth
+ * unions: identity).  Operand indices a node does not use are -1.  *n_nodes (may be NULL) always receives the node count;
+ * the nodes are written only if cap >= that count, else nothing is (RM_OK either way).  RM_E_NO_SCENE before any scene,
+ * RM_E_INVALID for an index out of range, cap < 0 or a null buffer with cap > 0.  Works on a host-only context. */
+RM_API int rm_scene_object(rm_ctx *ctx, int32_t index, rm_node *nodes, int32_t cap, int32_t *n_nodes);
+
 /* ---- render -------------------------------------------------------------------- */
 
 /* Replaces the worker's onmessage (raymarchWorker.ts:33-92) = Raymarcher.runRaymarcher

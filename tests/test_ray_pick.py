@@ -1,0 +1,551 @@
+"""Object picking (rm_ray_pick / rm_ray_pick_device; Context.pick, object_ids) and read-back of a scene's objects
+(rm_scene_object; Context.scene_object, the host mirror's Scene.getObject / objectAt, Raymarcher.pickBatch).  CPU tests: the
+ABI contract on a host-only context, every preset's objects against the oracle's trees, upload round trips, and the build
+invariants of every pick_kernel instantiation.  GPU tests: the outputs a pick shares with rm_ray_march are bit-identical, the
+object ids agree with an independent check built from single-object scenes, sphere ids survive the BVH's leaf order,
+object_ids is the per-pixel pick, a pick has no side effects, and the CRUD loop pick -> read back -> edit -> re-upload."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+ACCELS = ("None", "Octree", "BVH")
+ALGS = ("sphere-tracer", "fixed-step", "adaptive-step", "adaptive-step-v2", "adaptive-step-v3")
+ANGLES = ((0.0, 0.0), (0.3, 0.7), (-1.2, 2.5))
+ACCEL_ENUM = {"None": 0, "Octree": 1, "BVH": 2}
+
+
+def tree(nodes, i):
+    """The subtree of node i, compared bit for bit: type, matrix and parameter bytes, then the operands."""
+    t, a, b, m, p = nodes[i]
+    return (int(t), np.asarray(m, np.float32).tobytes(), np.asarray(p, np.float64).tobytes(),
+            tree(nodes, a) if a >= 0 else None, tree(nodes, b) if b >= 0 else None)
+
+
+def object_tree(obj):
+    assert obj, "empty object"
+    return tree(obj, len(obj) - 1)
+
+
+# ----------------------------------------------------------------------------------------------------- CPU: ABI contract
+
+def test_host_only_context_refuses_to_pick(rm):
+    ctx = rm.Context(None)
+    ctx.scene_from_preset(3, 2)
+    with pytest.raises(rm.RmError) as e:
+        ctx.pick(np.zeros((4, 3), np.float32), np.ones((4, 3), np.float32))
+    assert e.value.code == rm._native.RM_E_NO_DEVICE
+
+
+def test_bad_pick_arguments_are_invalid(rm):
+    N = rm._native
+    L = N.lib()
+    ctx = rm.Context(None)
+    q = N.rm_ray_query()
+    o = np.zeros((2, 3), np.float32)
+    d = np.ones((2, 3), np.float32)
+    obj = np.zeros(2, np.int32)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    assert L.rm_ray_pick(ctx._h, None, 2, vp(o), vp(d), None, None, None, None, vp(obj)) == N.RM_E_INVALID  # null query
+    assert L.rm_ray_pick(ctx._h, C.byref(q), -1, vp(o), vp(d), None, None, None, None, vp(obj)) == N.RM_E_INVALID
+    assert L.rm_ray_pick(ctx._h, C.byref(q), 2, None, vp(d), None, None, None, None, vp(obj)) == N.RM_E_INVALID
+    assert L.rm_ray_pick(ctx._h, C.byref(q), 2, vp(o), None, None, None, None, None, vp(obj)) == N.RM_E_INVALID
+    assert L.rm_ray_pick(ctx._h, C.byref(q), 2 ** 31, vp(o), vp(d), None, None, None, None, vp(obj)) == N.RM_E_INVALID
+    assert L.rm_ray_pick(None, C.byref(q), 2, vp(o), vp(d), None, None, None, None, vp(obj)) == N.RM_E_INVALID
+    assert L.rm_ray_pick_device(ctx._h, None, 2, vp(o), vp(d), None, None, None, None, None, None) == N.RM_E_INVALID
+    assert L.rm_ray_pick_device(ctx._h, C.byref(q), -5, vp(o), vp(d), None, None, None, None, None, None) == N.RM_E_INVALID
+    assert L.rm_ray_pick_device(ctx._h, C.byref(q), 2, None, None, None, None, None, None, None, None) == N.RM_E_INVALID
+    # well-formed arguments on a host-only context: no device
+    assert L.rm_ray_pick(ctx._h, C.byref(q), 2, vp(o), vp(d), None, None, None, None, vp(obj)) == N.RM_E_NO_DEVICE
+    assert L.rm_ray_pick_device(ctx._h, C.byref(q), 2, vp(o), vp(d), None, None, None, None, None, None) == N.RM_E_NO_DEVICE
+
+
+def test_scene_object_before_any_scene_and_out_of_range(rm):
+    N = rm._native
+    L = N.lib()
+    ctx = rm.Context(None)
+    n = C.c_int32(-7)
+    assert L.rm_scene_object(ctx._h, 0, None, 0, C.byref(n)) == N.RM_E_NO_SCENE
+    assert L.rm_scene_object(None, 0, None, 0, C.byref(n)) == N.RM_E_INVALID
+    ctx.scene_from_preset(2, 0)  # nine spheres
+    for bad in (-1, 9, 2 ** 31 - 1):
+        assert L.rm_scene_object(ctx._h, bad, None, 0, C.byref(n)) == N.RM_E_INVALID, bad
+    assert L.rm_scene_object(ctx._h, 0, None, -1, C.byref(n)) == N.RM_E_INVALID
+    assert L.rm_scene_object(ctx._h, 0, None, 4, C.byref(n)) == N.RM_E_INVALID  # null buffer with room claimed
+    assert L.rm_scene_object(ctx._h, 8, None, 0, C.byref(n)) == N.RM_OK and n.value == 1
+    assert L.rm_scene_object(ctx._h, 8, None, 0, None) == N.RM_OK  # the count pointer may be NULL
+
+
+def test_a_too_small_cap_writes_nothing_and_reports_the_count(rm):
+    N = rm._native
+    L = N.lib()
+    ctx = rm.Context(None)
+    ctx.scene_from_preset(17, 1)  # "Chicken": one object of ten boxes under nine smooth unions
+    n = C.c_int32(0)
+    assert L.rm_scene_object(ctx._h, 0, None, 0, C.byref(n)) == N.RM_OK
+    assert n.value == 19
+    arr = (N.rm_node * 19)()
+    for e in arr:
+        e.type, e.params[0] = 77, 1.25
+    n.value = 0
+    assert L.rm_scene_object(ctx._h, 0, arr, 18, C.byref(n)) == N.RM_OK and n.value == 19
+    assert all(e.type == 77 and e.params[0] == 1.25 for e in arr), "a buffer one node short was written"
+    assert L.rm_scene_object(ctx._h, 0, arr, 19, C.byref(n)) == N.RM_OK and n.value == 19
+    assert arr[18].type == 11 and arr[18].child_a >= 0 and arr[18].child_b >= 0
+
+
+@pytest.mark.parametrize("accel", ACCELS)
+def test_every_preset_reads_back_as_the_oracle_holds_it(rm, oracle, accel):
+    ctx = rm.Context(None)
+    for p in range(19):
+        ctx.scene_from_preset(p, ACCEL_ENUM[accel])
+        nodes, roots = oracle.OracleScene(preset=p, accel=accel).nodes()
+        assert ctx.scene_info()["n_prims"] == len(roots), p
+        for j, r in enumerate(roots):
+            got = ctx.scene_object(j)
+            assert object_tree(got) == tree(nodes, r), (p, j)
+            # operands before their user, the root last
+            assert all(a < i and b < i for i, (_, a, b, _, _) in enumerate(got)), (p, j)
+
+
+def test_an_uploaded_sphere_list_comes_back_in_upload_order_under_every_accel(rm):
+    rng = np.random.default_rng(11)
+    c = rng.uniform(-2, 2, (40, 3)).astype(np.float32)
+    r = rng.uniform(0.05, 0.3, 40)
+    ctx = rm.Context(None)
+    for accel in (2, 1, 0):
+        ctx.scene_from_spheres(c, r, accel)
+        for j in range(40):
+            got = ctx.scene_object(j)
+            assert len(got) == 1
+            t, a, b, m, par = got[0]
+            want_m = np.zeros(16, np.float32)
+            assert rm._native.lib().rm_make_transform(float(c[j, 0]), float(c[j, 1]), float(c[j, 2]), None,
+                                                      want_m.ctypes.data_as(C.c_void_p)) == 0
+            assert (t, a, b) == (0, -1, -1) and m.tobytes() == want_m.tobytes(), (accel, j)
+            assert par[0] == r[j] and not par[1:].any(), (accel, j)
+
+
+def test_prim_lists_and_forests_come_back_as_given(rm, oracle):
+    ctx = rm.Context(None)
+    rng = np.random.default_rng(4)
+    given = []
+    for k in range(12):
+        m = np.zeros(16, np.float32)
+        rot = rng.uniform(-3, 3, 3).astype(np.float32)
+        rm._native.lib().rm_make_transform(*[float(v) for v in rng.uniform(-2, 2, 3)], rot.ctypes.data_as(C.c_void_p),
+                                           m.ctypes.data_as(C.c_void_p))
+        par = [0.3 + 0.01 * k, 0.1, 0.2] if k % 3 == 1 else [0.4 + 0.01 * k, 0.05 * (k % 3), 0.0]
+        given.append((k % 3, m, par))
+    for accel in (0, 1, 2):
+        ctx.scene_from_prims(given, accel)
+        for j, (t, m, par) in enumerate(given):
+            got = ctx.scene_object(j)
+            assert len(got) == 1 and got[0][0] == t and got[0][1:3] == (-1, -1), (accel, j)
+            assert got[0][3].tobytes() == m.tobytes() and got[0][4].tobytes() == np.array(par + [0, 0, 0], np.float64).tobytes()
+    # a forest: the roots of two presets side by side, uploaded, read back tree by tree
+    n1, r1 = oracle.OracleScene(preset=18, accel="None").nodes()
+    n2, r2 = oracle.OracleScene(preset=11, accel="None").nodes()
+    nodes = list(n1) + [(t, a + len(n1) if a >= 0 else -1, b + len(n1) if b >= 0 else -1, m, p) for t, a, b, m, p in n2]
+    roots = list(r1) + [r + len(n1) for r in r2]
+    for accel in (0, 1, 2):
+        ctx.scene_from_nodes(nodes, roots, accel)
+        assert ctx.scene_info()["n_prims"] == 3
+        for j, r in enumerate(roots):
+            assert object_tree(ctx.scene_object(j)) == tree(nodes, r), (accel, j)
+
+
+# ------------------------------------------------------------------------------------------------- CPU: build invariants
+
+def _pick_usage(extra):
+    from test_build_invariants import resource_usage
+    usage = resource_usage(extra, "rm_kernels.hip")
+    return {n: r for n, r in usage.items() if n.startswith("void pick_kernel<")}
+
+
+@pytest.mark.parametrize("extra", [(), ("-DRM_LENGTH_SQRT",)])
+def test_pick_kernels_spill_nothing(extra):
+    from test_build_invariants import HIPCC
+    import shutil
+    if not os.path.exists(HIPCC) or shutil.which("c++filt") is None:
+        pytest.skip("hipcc / c++filt not present")
+    kernels = _pick_usage(extra)
+    assert len(kernels) == 24, sorted(kernels)
+    for name, r in kernels.items():
+        gen = int(name.split("<")[1].split(">")[0].split(",")[-1])
+        assert r["VGPRs Spill"] == 0, (name, r)
+        if gen <= 1:
+            assert r["ScratchSize [bytes/lane]"] == 0, (name, r)
+        else:
+            assert r["ScratchSize [bytes/lane]"] <= 800, (name, r)
+
+
+@pytest.mark.parametrize("extra", [(), ("-DRM_LENGTH_SQRT",)])
+def test_pick_kernels_have_no_spill_ahead_of_an_exec_restore(extra):
+    from test_build_invariants import HIPCC, listing, spill_code_ahead_of_exec_restore
+    if not os.path.exists(HIPCC):
+        pytest.skip("hipcc not present")
+    lines = listing("rm_kernels.hip", extra)
+    spans, cur = [], None
+    for n, t in enumerate(lines):
+        if t.startswith("_Z") and t.split(";")[0].rstrip().endswith(":"):  # a function's label
+            cur = [n, len(lines)] if "11pick_kernel" in t else None
+            if cur:
+                spans.append(cur)
+        elif cur is not None and t.strip().startswith(".Lfunc_end"):
+            cur[1] = n
+            cur = None
+    assert len(spans) == 24, len(spans)
+    for a, b in spans:
+        assert not spill_code_ahead_of_exec_restore(lines[a:b]), lines[a]
+
+
+# ------------------------------------------------------------------------------------------------------------ GPU tests
+
+@pytest.fixture(scope="module")
+def pctx(rm):
+    """A context of its own: options set here never leak into other test modules."""
+    return rm.Context(0)
+
+
+@pytest.fixture(scope="module")
+def octx(rm):
+    """The single-object scenes of the independent check: interpreter only (no run-time compile per object)."""
+    c = rm.Context(0)
+    c.set_option("specialise", 0)
+    return c
+
+
+def _scene(rm, ctx, preset, accel):
+    sc = rm.Scene(accel, ctx=ctx)
+    sc.loadPreset(preset)
+    return sc
+
+
+def _camera(rm, W, H, ang):
+    org, dirs = rm.camera_rays(W, H, *ang)
+    return np.ascontiguousarray(np.broadcast_to(org, dirs.shape)), dirs
+
+
+def _same_bits(a, b):
+    return np.ascontiguousarray(a).view(np.uint8).tobytes() == np.ascontiguousarray(b).view(np.uint8).tobytes()
+
+
+def _assert_shared(got, want, what):
+    for g, w, name in zip(got[:4], want, ("t", "iters", "sdf", "normal")):
+        assert _same_bits(g, w), (what, name)
+
+
+def hit_points(o, d, t):
+    """hitPosition = f32(o + d t) (vec3.scaleAndAdd), in binary64 then rounded once, as the kernel forms it."""
+    return (o.astype(np.float64) + d.astype(np.float64) * t[:, None]).astype(np.float32)
+
+
+def single_object_values(ctx, octx, points, n_objects, time=0.0, objects=None):
+    """v[j, i] = Primitive.sdf of object j at points[i], from a scene of that object alone (read back with rm_scene_object,
+    uploaded with rm_scene_from_nodes, accel None) and rm_scene_distance -- no pick_kernel involved."""
+    js = range(n_objects) if objects is None else objects
+    out = {}
+    forests = {j: ctx.scene_object(j) for j in js}
+    for j, nodes in forests.items():
+        octx.scene_from_nodes(nodes, [len(nodes) - 1], 0)
+        octx.scene_set_time(time)
+        out[j] = octx.scene_distance(points)[0]
+    return out
+
+
+def expected_ids(D, v, n_objects):
+    """The lowest j with v_j == D, or with both NaN; else -1."""
+    want = np.full(len(D), -1, np.int64)
+    for j in reversed(range(n_objects)):
+        match = (v[j] == D) | (np.isnan(v[j]) & np.isnan(D))
+        want[match] = j
+    return want
+
+
+@pytest.mark.gpu
+def test_fixture_rays_share_every_output_with_ray_march(rm, pctx):
+    """The 60 rays of tests/golden/ray_queries.npz under each of its configurations (those pinned to the reference there)."""
+    import json
+    from cpu_raymarcher_amd.synthetic import synthetic_spheres
+    f = dict(np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ray_queries.npz")))
+    o, d = f["origins"], f["directions"]
+    for k, cfg in enumerate(json.loads(str(f["configs"]))):
+        sc = rm.Scene(cfg["accel"], ctx=pctx)
+        if "synthetic" in cfg:
+            sp = synthetic_spheres(cfg["synthetic"])
+            sc.loadSpheres(sp[:, :3], sp[:, 3])
+        else:
+            sc.loadPreset(cfg["preset"])
+        kw = dict(normal=True, time=cfg.get("time", 0.0), overshoot=cfg.get("overshootFactor"), step=cfg.get("stepSize"))
+        want = pctx.ray_march(o, d, cfg["algorithm"], **kw)
+        got = pctx.pick(o, d, cfg["algorithm"], **kw)
+        _assert_shared(got, want, cfg)
+        assert pctx.last_kernel().startswith("pick_kernel<")
+        assert (got[4][got[0] >= 10] == -1).all(), cfg
+        assert np.array_equal(got[0].view(np.uint64), f["t_bits"][k]), cfg  # (pinned to the reference's rayMarch)
+
+
+PRESETS = (0, 2, 3, 5, 9, 10, 13, 15, 17)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("accel", ACCELS)
+@pytest.mark.parametrize("preset", PRESETS)
+def test_camera_rays_share_every_output_with_ray_march(rm, pctx, preset, accel):
+    W, H = 64, 48
+    _scene(rm, pctx, preset, accel)
+    for ang in ANGLES:
+        o, d = _camera(rm, W, H, ang)
+        for alg in ALGS:
+            _assert_shared(pctx.pick(o, d, alg), pctx.ray_march(o, d, alg), (preset, accel, ang, alg))
+    # without normals too
+    o, d = _camera(rm, W, H, ANGLES[1])
+    _assert_shared(pctx.pick(o, d, normal=False), pctx.ray_march(o, d, normal=False), (preset, accel, "no normal"))
+
+
+def _check_object_ids(rm, pctx, octx, preset):
+    """For every hit: D = Scene.getDistance(p) (rm_scene_distance, pinned against the oracle elsewhere), v_j from a scene of
+    object j alone; the expected id is the lowest j with v_j == D (or both NaN), else -1.  Returns (hits, rays, ids)."""
+    W, H = 64, 48
+    time = 1.75 if preset == 12 else 0.0  # the animated preset: the query's time is also the single-object scenes' time
+    cases = []
+    for accel in ACCELS:
+        _scene(rm, pctx, preset, accel)
+        n_obj = pctx.scene_info()["n_prims"]
+        for alg in ("sphere-tracer", "adaptive-step-v3"):
+            for ang in ANGLES:
+                o, d = _camera(rm, W, H, ang)
+                t, _, _, _, obj = pctx.pick(o, d, alg, normal=False, time=time)
+                hit = t < 10
+                assert (obj[~hit] == -1).all(), (preset, accel, alg, ang)
+                p = hit_points(o[hit], d[hit], t[hit])
+                pctx.scene_set_time(time)
+                D, _ = pctx.scene_distance(p)
+                cases.append((accel, alg, ang, hit, p, D, obj[hit]))
+    allp = np.concatenate([c[4] for c in cases])
+    v = single_object_values(pctx, octx, allp, n_obj, time)
+    at = 0
+    ids = set()
+    for accel, alg, ang, hit, p, D, got in cases:
+        vj = {j: v[j][at:at + len(p)] for j in v}
+        at += len(p)
+        want = expected_ids(D, vj, n_obj)
+        bad = got != want
+        assert not bad.any(), (preset, accel, alg, ang, np.nonzero(bad)[0][:8], got[bad][:8], want[bad][:8])
+        ids |= set(got.tolist())
+    return sum(int(c[3].sum()) for c in cases), sum(len(c[3]) for c in cases), ids - {-1}
+
+
+@pytest.mark.gpu
+def test_object_ids_agree_with_single_object_scenes(rm, pctx, octx):
+    """Nine presets and the animated one, three accels, two marchers, three angles.  Not vacuous: a fifth of all rays hit,
+    and the Dense Sphere Grid shows at least ten distinct objects."""
+    hits = rays = 0
+    for preset in PRESETS + (12,):
+        h, n, ids = _check_object_ids(rm, pctx, octx, preset)
+        assert h > 0, preset
+        hits, rays = hits + h, rays + n
+        if preset == 3:
+            assert len(ids) >= 10, ids
+    assert hits >= 0.2 * rays, (hits, rays)
+
+
+@pytest.mark.gpu
+def test_large_octree_scene_ids_attain_the_distance(rm, pctx, octx):
+    from cpu_raymarcher_amd.synthetic import synthetic_spheres
+    from test_ray_queries import random_rays
+    sp = synthetic_spheres(10000)
+    sc = rm.Scene("Octree", ctx=pctx)
+    sc.loadSpheres(sp[:, :3], sp[:, 3])
+    o, d = random_rays(4096, seed=21)
+    o = (o * np.float32(0.3)).astype(np.float32)  # most origins near the cluster: many hits
+    for alg in ("sphere-tracer", "adaptive-step-v2"):
+        t, _, _, _, obj = pctx.pick(o, d, alg)
+        hit = t < 10
+        assert hit.mean() > 0.2 and (obj[~hit] == -1).all()
+        p = hit_points(o[hit], d[hit], t[hit])
+        pctx.scene_set_time(0.0)
+        D, cnt = pctx.scene_distance(p)
+        k = obj[hit]
+        ks = sorted(set(k.tolist()) - {-1})
+        assert len(ks) > 50
+        v = single_object_values(pctx, octx, p, None, objects=ks)
+        for j in ks:
+            sel = k == j
+            assert np.array_equal(v[j][sel], D[sel]), j
+        if alg == "sphere-tracer":
+            near = (D < 0.001) & (cnt > 0)  # cnt == 0: an empty leaf, no candidates
+            assert near.mean() > 0.5 and (k[near] >= 0).all()
+
+
+@pytest.mark.gpu
+def test_shuffled_spheres_under_the_bvh_keep_their_upload_index(rm, pctx):
+    """Isolated spheres on a 12 x 12 grid, uploaded in a shuffled order (the BVH stores them in leaf order): a ray straight
+    down onto each centre returns that sphere's index in the upload."""
+    xs, ys = np.meshgrid(np.arange(12) - 5.5, np.arange(12) - 5.5, indexing="ij")
+    centres = np.stack([xs.ravel() * 0.7, ys.ravel() * 0.7, np.zeros(144)], axis=1).astype(np.float32)
+    perm = np.random.default_rng(8).permutation(144)
+    centres = centres[perm]
+    radii = np.full(144, 0.2)
+    o = (centres + np.array([0, 0, 3], np.float32)).astype(np.float32)
+    d = np.tile(np.array([[0, 0, -1]], np.float32), (144, 1))
+    for accel in ("BVH", "Octree", "None"):
+        sc = rm.Scene(accel, ctx=pctx)
+        sc.loadSpheres(centres, radii)
+        if accel == "BVH":
+            assert pctx.scene_info()["bvh_leaves"] > 1
+        t, _, _, _, obj = pctx.pick(o, d)
+        assert (t < 10).all(), accel
+        assert np.array_equal(obj, np.arange(144)), (accel, obj[:16])
+        for j in (0, 77, 143):  # and the read-back names the same sphere
+            assert np.array_equal(sc.getObject(j)[0][3][12:15], -centres[j])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("preset,accel", [(3, "BVH"), (3, "Octree"), (17, "None"), (9, "BVH")])
+def test_object_ids_is_the_per_pixel_pick(rm, pctx, preset, accel):
+    import torch
+    W, H, ang = 80, 60, (0.3, 0.7)
+    _scene(rm, pctx, preset, accel)
+    ids = pctx.object_ids(W, H, *ang)
+    assert ids.dtype == np.int32 and ids.shape == (W * H,)
+    o, d = _camera(rm, W, H, ang)
+    t, _, _, _, obj = pctx.pick(o, d)
+    assert np.array_equal(ids, obj)
+    hit = t < 10
+    assert (ids[~hit] == -1).all() and (ids[hit] >= 0).mean() > 0.9
+    rule = hit & (ids < 0)  # -1 by rule: no candidate attains D (an empty octree leaf, or D still the start value 10)
+    if rule.any():
+        D, cnt = pctx.scene_distance(hit_points(o[rule], d[rule], t[rule]))
+        assert ((cnt == 0) | (D >= 10)).all()
+    rows = pctx.object_ids(W, H, *ang, y_start=13, y_end=41)
+    assert np.array_equal(rows, ids[13 * W:41 * W])
+    dev = pctx.object_ids(W, H, *ang, device=True)
+    torch.cuda.synchronize()
+    assert dev.is_cuda and np.array_equal(dev.cpu().numpy(), ids)
+    # the host mirror: objectAt for a few pixels, pickBatch for all
+    sc = _scene(rm, pctx, preset, accel)
+    sc.camera.setAngles(*ang)
+    for x, y in ((0, 0), (W // 2, H // 2), (17, 45), (W - 1, H - 1)):
+        assert sc.objectAt(x, y, W, H) == ids[y * W + x], (x, y)
+    pb = rm.SphereTracer().pickBatch(sc, o, d)
+    assert np.array_equal(pb[4], ids) and _same_bits(pb[0], t)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("preset,accel", [(3, "BVH"), (3, "Octree"), (2, "BVH"), (17, "BVH")])
+def test_knobs_change_no_bit_of_a_pick(rm, pctx, preset, accel):
+    from test_ray_queries import random_rays
+    _scene(rm, pctx, preset, accel)
+    o, d = random_rays(30000, seed=9)
+    co, cd = _camera(rm, 80, 60, (0.3, 0.7))
+    o, d = np.concatenate([o, co]), np.concatenate([d, cd])
+    base = pctx.pick(o, d)
+    for key in ("filter", "v1_lists", "grid", "lut", "recs", "sub", "specialise"):
+        old = pctx.get_option(key)
+        for v in (0, 1):
+            pctx.set_option(key, v)
+            _scene(rm, pctx, preset, accel)
+            got = pctx.pick(o, d)
+            assert all(_same_bits(x, y) for x, y in zip(got, base)), (key, v)
+        pctx.set_option(key, old)
+
+
+@pytest.mark.gpu
+def test_a_pick_leaves_armed_diagnostics_and_the_scene_time_alone(rm, pctx):
+    import torch
+    from test_ray_queries import random_rays
+    W, H = 64, 48
+    sc = _scene(rm, pctx, 3, "BVH")
+    sc.camera.setAngles(0.2, 0.5)
+    acc = torch.full((4,), -1, dtype=torch.int64, device="cuda")
+    pctx._attach_diag(acc)
+    o, d = random_rays(1000)
+    pctx.pick(o, d)
+    pctx.pick(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
+    pctx.object_ids(W, H, 0.2, 0.5, device=True)
+    torch.cuda.synchronize()
+    assert torch.equal(acc, torch.full((4,), -1, dtype=torch.int64, device="cuda")), "the pick fired the diagnostics"
+    bufs = [torch.zeros(W * H, dtype=torch.uint8, device="cuda"), torch.zeros(3 * W * H, dtype=torch.uint8, device="cuda"),
+            torch.zeros(W * H, dtype=torch.int16, device="cuda"), torch.zeros(W * H, dtype=torch.int16, device="cuda")]
+    rm.SphereTracer().runRaymarcher(sc, *bufs, W, H, 0.0)
+    torch.cuda.synchronize()
+    got = pctx.decode_acc(acc)
+    s = bufs[2].cpu().numpy().view(np.uint16).astype(np.int64)
+    i = bufs[3].cpu().numpy().view(np.uint16).astype(np.int64)
+    assert got == {"total_sdf": int(s.sum()), "total_iters": int(i.sum()), "max_sdf": int(s.max()), "min_sdf": int(s.min())}
+    sc = _scene(rm, pctx, 12, "None")
+    sc.updateTime(0.5)
+    pts = np.array([[0.3, 0.2, -0.1], [1.0, 0.0, 0.0]], np.float32)
+    before = pctx.scene_distance(pts)
+    pctx.pick(pts, np.ones_like(pts), time=3.25)
+    after = pctx.scene_distance(pts)
+    assert _same_bits(before[0], after[0]) and _same_bits(before[1], after[1])
+
+
+@pytest.mark.gpu
+def test_device_pick_equals_host_pick(rm, pctx):
+    import torch
+    from test_ray_queries import random_rays
+    s = torch.cuda.Stream()
+    for preset, accel in ((3, "BVH"), (10, "Octree")):
+        _scene(rm, pctx, preset, accel)
+        for n in (1, 257, 5000):
+            o, d = random_rays(n, seed=n)
+            want = pctx.pick(o, d)
+            with torch.cuda.stream(s):
+                got = pctx.pick(torch.from_numpy(o).cuda(), torch.from_numpy(d).cuda())
+            s.synchronize()
+            for g, w, name in zip(got, want, ("t", "iters", "sdf", "normal", "object")):
+                assert _same_bits(g.cpu().numpy(), w), (preset, accel, n, name)
+
+
+@pytest.mark.gpu
+def test_crud_loop_pick_read_back_edit_reupload(rm, oracle, pctx):
+    """Pick the centre pixel of preset 3 under the BVH, read every object back, drop the one picked, upload the rest: the
+    same ray no longer returns that object.  The unedited read-back renders as the oracle renders the preset."""
+    W, H, ang = 64, 48, (0.3, 0.7)
+    sc = _scene(rm, pctx, 3, "BVH")
+    sc.camera.setAngles(*ang)
+    k = sc.objectAt(W // 2, H // 2, W, H)
+    assert k >= 0
+    n = pctx.scene_info()["n_prims"]
+    objs = [sc.getObject(j) for j in range(n)]
+    removed = object_tree(objs[k])
+
+    def forest(objects):
+        nodes, roots = [], []
+        for ob in objects:
+            base = len(nodes)
+            nodes += [(t, a + base if a >= 0 else -1, b + base if b >= 0 else -1, m, p) for t, a, b, m, p in ob]
+            roots.append(len(nodes) - 1)
+        return nodes, roots
+
+    org, dirs = rm.camera_rays(W, H, *ang, y_start=H // 2, y_end=H // 2 + 1)
+    ray_o, ray_d = org.reshape(1, 3), dirs[W // 2:W // 2 + 1]
+    sc.loadNodes(*forest(objs[:k] + objs[k + 1:]))
+    t, _, _, _, obj = pctx.pick(ray_o, ray_d)
+    if obj[0] >= 0:
+        assert object_tree(sc.getObject(int(obj[0]))) != removed
+    assert pctx.scene_info()["n_prims"] == n - 1
+    # the unedited read-back, rendered under every accel, for two presets
+    for preset in (3, 9):
+        src = _scene(rm, pctx, preset, "None")
+        objs = [src.getObject(j) for j in range(pctx.scene_info()["n_prims"])]
+        nodes, roots = forest(objs)
+        for accel in ACCELS:
+            ref = oracle.OracleScene(preset=preset, accel=accel)
+            ref.set_angles(*ang)
+            want = ref.render(W, H)
+            s2 = rm.Scene(accel, ctx=pctx)
+            s2.loadNodes(nodes, roots)
+            s2.camera.setAngles(*ang)
+            bufs = (np.zeros(W * H, np.uint8), np.zeros(3 * W * H, np.uint8), np.zeros(W * H, np.uint16), np.zeros(W * H, np.uint16))
+            rm.SphereTracer().runRaymarcher(s2, *bufs, W, H, 0.0)
+            for g, w, name in zip(bufs, want, ("depth", "normal", "sdf", "iters")):
+                assert np.array_equal(g, w), (preset, accel, name)
