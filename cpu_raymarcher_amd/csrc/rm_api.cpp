@@ -783,7 +783,7 @@ int norm_shader(int s) { return (s >= RM_SHADE_NORMAL && s <= RM_SHADE_ITERATION
 // The parameter block of a ray query: what a one-ray-per-lane render launch of the ACTIVE scene reads (fill_params with a job
 // that names that scene, so every knob applies as it does there), the query's marcher, step rules and time.  A query is pure:
 // unlike a render it leaves the scene's time (rm_scene_set_time, what rm_scene_distance uses) as it was.  No run-time
-// specialised kernel: cast_kernel is ahead-of-time only.
+// specialised kernel: cast_kernel and pick_kernel are ahead-of-time only.
 int fill_query_params(rm_ctx *ctx, const rm_ray_query *q, RmRenderParams &p) {
     const double scene_time = ctx->time;
     rm_job job;
@@ -804,13 +804,72 @@ int fill_query_params(rm_ctx *ctx, const rm_ray_query *q, RmRenderParams &p) {
     return rc;
 }
 
-// the checks rm_ray_march and rm_ray_march_device share
+// the checks every ray query makes
 int check_query(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs) {
     if (!q) return fail(ctx, RM_E_INVALID, "null query");
     if (n < 0 || n > std::numeric_limits<int32_t>::max()) return fail(ctx, RM_E_INVALID, "ray count out of range");
     if (n > 0 && (!origins || !dirs)) return fail(ctx, RM_E_INVALID, "null ray buffer");
     if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU ray path");
     if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
+// rm_ray_march_device (pick false: cast_kernel, d_object unused) and rm_ray_pick_device (pick true: pick_kernel)
+int ray_query_device(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
+                     void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, d_origins, d_dirs);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_query_sqrt : rm_launch_query)(
+                    p, pick, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, ctx->dev.slot_object,
+                    static_cast<double *>(d_t), static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls),
+                    static_cast<float *>(d_normal), static_cast<int32_t *>(d_object), static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+// rm_ray_march (pick false) and rm_ray_pick (pick true): host buffers, synchronous
+int ray_query_host(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
+                   uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
+    if (rc || !n) return rc;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // through the scratch buffer in chunks of at most 4 M rays (52 B per ray: 208 MB; a pick's objects 4 B more: 224 MB), whatever the batch
+    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
+    const size_t c = static_cast<size_t>(chunk);
+    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
+                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), o_obj = o_nrm + align_up(12 * c, 256),
+                 total = o_obj + (pick ? align_up(4 * c, 256) : 0);
+    rc = ensure_scratch(ctx, total);
+    if (rc) return rc;
+    char *base = static_cast<char *>(ctx->scratch);
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_query_sqrt : rm_launch_query)(
+                        p, pick, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
+                        ctx->dev.slot_object, t ? reinterpret_cast<double *>(base + o_t) : nullptr,
+                        iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr, sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr,
+                        normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr, object ? reinterpret_cast<int32_t *>(base + o_obj) : nullptr,
+                        ctx->stream, &ctx->last_kernel));
+        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
+        if (object) RM_HIP(ctx, hipMemcpyAsync(object + at, base + o_obj, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
+        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
+    }
     return RM_OK;
 }
 
@@ -1407,56 +1466,12 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
 
 int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                         void *d_sdf_calls, void *d_normal, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, d_origins, d_dirs);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_cast_sqrt : rm_launch_cast)(
-                    p, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, static_cast<double *>(d_t),
-                    static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls), static_cast<float *>(d_normal),
-                    static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
+    return ray_query_device(ctx, false, q, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, nullptr, stream);
 }
 
 int rm_ray_march(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                  uint32_t *sdf_calls, float *normal_xyz) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
-    if (rc || !n) return rc;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // through the scratch buffer in chunks of at most 4 M rays (52 B per ray: 208 MB), whatever the batch
-    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
-    const size_t c = static_cast<size_t>(chunk);
-    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
-                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), total = o_nrm + align_up(12 * c, 256);
-    rc = ensure_scratch(ctx, total);
-    if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_cast_sqrt : rm_launch_cast)(
-                        p, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
-                        t ? reinterpret_cast<double *>(base + o_t) : nullptr, iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr,
-                        sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr, normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr,
-                        ctx->stream, &ctx->last_kernel));
-        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return ray_query_host(ctx, false, q, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, nullptr);
 }
 
 int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end, float *origin3, float *dirs_xyz) {
@@ -1487,59 +1502,12 @@ int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int3
 
 int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                        void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, d_origins, d_dirs);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_pick_sqrt : rm_launch_pick)(
-                    p, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, ctx->dev.slot_object,
-                    static_cast<double *>(d_t), static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls),
-                    static_cast<float *>(d_normal), static_cast<int32_t *>(d_object), static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
+    return ray_query_device(ctx, true, q, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, d_object, stream);
 }
 
 int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                 uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
-    if (rc || !n) return rc;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // through the scratch buffer in chunks of at most 4 M rays (56 B per ray: 224 MB), as rm_ray_march
-    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
-    const size_t c = static_cast<size_t>(chunk);
-    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
-                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), o_obj = o_nrm + align_up(12 * c, 256),
-                 total = o_obj + align_up(4 * c, 256);
-    rc = ensure_scratch(ctx, total);
-    if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_pick_sqrt : rm_launch_pick)(
-                        p, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
-                        ctx->dev.slot_object, t ? reinterpret_cast<double *>(base + o_t) : nullptr,
-                        iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr, sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr,
-                        normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr, object ? reinterpret_cast<int32_t *>(base + o_obj) : nullptr,
-                        ctx->stream, &ctx->last_kernel));
-        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (object) RM_HIP(ctx, hipMemcpyAsync(object + at, base + o_obj, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return ray_query_host(ctx, true, q, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, object);
 }
 
 int rm_scene_object(rm_ctx *ctx, int32_t index, rm_node *nodes, int32_t cap, int32_t *n_nodes) {

@@ -64,21 +64,17 @@ hipError_t rm_launch_distance(const RmRenderParams &p, const float *points, int6
 hipError_t rm_launch_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist,
                                    uint32_t *count, hipStream_t stream);
 
-// Raymarcher.rayMarch (+ getNormal when want_normal) for n caller-supplied rays (origins, dirs: f32[3n]); every output may be
-// null.  *kernel_name (optional) receives the instantiation that was launched (static string).
-hipError_t rm_launch_cast(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
-                          uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_cast_sqrt(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
-                               uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name);
-
-// rm_launch_cast plus the object each ray hit (object: i32[n], -1 = none; rm_ray_pick).  slot_obj: device sphere slot ->
-// object index (sphere scenes stored in BVH leaf order), null when the two agree.  Every output may be null.
-hipError_t rm_launch_pick(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                          const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                          hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_pick_sqrt(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                               const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                               hipStream_t stream, const char **kernel_name);
+// Ray queries (rm_ray_march, rm_ray_pick): Raymarcher.rayMarch (+ getNormal when want_normal) for n caller-supplied rays
+// (origins, dirs: f32[3n]).  pick launches pick_kernel, which also writes the object each ray hit (object: i32[n], -1 =
+// none), else cast_kernel, which reads neither slot_obj nor object.  slot_obj: device sphere slot -> object index (sphere
+// scenes stored in BVH leaf order), null when the two agree.  Every output may be null.  *kernel_name (optional) receives
+// the instantiation that was launched (static string).
+hipError_t rm_launch_query(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
+                           const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
+                           hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_query_sqrt(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
+                                const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
+                                hipStream_t stream, const char **kernel_name);
 
 // v2: builds the longest-first item order of the next launch from the previous launch's recorded costs (rm_render_v2.hip)
 hipError_t rm_launch_lpt_sort(const uint8_t *cost_prev, uint16_t *perm, int stride, int tiles_x, int tiles_y, hipStream_t stream);

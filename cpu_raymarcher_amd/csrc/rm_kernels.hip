@@ -1155,37 +1155,6 @@ __global__ __launch_bounds__(256) void distance_kernel(const RmRenderParams P, c
     distance_body<ACCEL, GEN>(P, pts, n, dist, count);
 }
 
-// Raymarcher.rayMarch (+ getNormal) for caller-supplied rays (rm_ray_march): one ray per lane, in input order.  The march is
-// render_body's (ray_march / ray_march_other, same scene fields, the per-ray BVH hit-leaf list in dynamic LDS); only the ray
-// comes from memory instead of the camera.  Nothing here may assume one origin for all rays: the per-frame octree table of
-// render_kernel_oct, the v2 wave loop's origin-relative boxes and its bundle cull are not used.  The direction is taken as
-// given (rayMarch does not normalise it).  Counts are exact u32: the reference's Uint16Array holds them mod 65536.
-// (Ahead-of-time only: the run-time specialiser's build of this file does not carry it.)
-template <int ACCEL, bool OTHER, int GEN>
-__global__ __launch_bounds__(256) void cast_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
-                                                   double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    Ray ray;
-    ray.o = Vec3f{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
-    ray.d = Vec3f{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
-    ray.od[0] = static_cast<double>(ray.o.x);  // per lane here (the camera's kernels take it from the parameter block)
-    ray.od[1] = static_cast<double>(ray.o.y);
-    ray.od[2] = static_cast<double>(ray.o.z);
-    uint32_t count = 0, iters = 0;
-    const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters) : ray_march<ACCEL, GEN>(P, ray, count, iters);
-    Vec3f nrm{0.f, 0.f, 0.f};
-    if (want_normal) nrm = hit_normal<ACCEL, GEN>(P, ray, t, count);
-    if (t_out) t_out[i] = t;
-    if (iters_out) iters_out[i] = iters;
-    if (sdf_out) sdf_out[i] = count;
-    if (normal_out) {
-        normal_out[3 * i] = nrm.x;
-        normal_out[3 * i + 1] = nrm.y;
-        normal_out[3 * i + 2] = nrm.z;
-    }
-}
-
 // ------------------------------------------------------------------ object picking (rm_ray_pick)
 
 // Primitive.sdf of device object `id`, bit-identical to the value the render's Scene.getDistance paths take for it (the
@@ -1277,18 +1246,25 @@ __device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ra
     return obj;
 }
 
-// cast_kernel plus the object each ray hit (rm_ray_pick).  t, iters, sdf_calls and the normal are cast_kernel's, bit for
-// bit: the same march, the same hit_normal, and the object pass adds nothing to the count.  (Ahead-of-time only.)
-template <int ACCEL, bool OTHER, int GEN>
-__global__ __launch_bounds__(256) void pick_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
-                                                   const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out,
-                                                   float *normal_out, int32_t *obj_out) {
+// ------------------------------------------------------------------ ray queries (rm_ray_march, rm_ray_pick)
+
+// Raymarcher.rayMarch (+ getNormal) for caller-supplied rays: one ray per lane, in input order.  The march is render_body's
+// (ray_march / ray_march_other, same scene fields, the per-ray BVH hit-leaf list in dynamic LDS); only the ray comes from
+// memory instead of the camera.  Nothing here may assume one origin for all rays: the per-frame octree table of
+// render_kernel_oct, the v2 wave loop's origin-relative boxes and its bundle cull are not used.  The direction is taken as
+// given (rayMarch does not normalise it).  Counts are exact u32: the reference's Uint16Array holds them mod 65536.
+// PICK adds the object each ray hit; t, iters, sdf_calls and the normal do not depend on it (the object pass adds nothing to
+// the count).  (Ahead-of-time only: the run-time specialiser's build of this file does not carry the ray queries.)
+template <int ACCEL, bool OTHER, int GEN, bool PICK>
+__device__ __forceinline__ void query_body(const RmRenderParams &P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                           const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out,
+                                           int32_t *obj_out) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
     Ray ray;
     ray.o = Vec3f{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
     ray.d = Vec3f{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
-    ray.od[0] = static_cast<double>(ray.o.x);
+    ray.od[0] = static_cast<double>(ray.o.x);  // per lane here (the camera's kernels take it from the parameter block)
     ray.od[1] = static_cast<double>(ray.o.y);
     ray.od[2] = static_cast<double>(ray.o.z);
     uint32_t count = 0, iters = 0;
@@ -1303,7 +1279,22 @@ __global__ __launch_bounds__(256) void pick_kernel(const RmRenderParams P, const
         normal_out[3 * i + 1] = nrm.y;
         normal_out[3 * i + 2] = nrm.z;
     }
-    if (obj_out) obj_out[i] = hit_object<ACCEL, GEN>(P, ray, t, slot_obj);
+    if constexpr (PICK) {
+        if (obj_out) obj_out[i] = hit_object<ACCEL, GEN>(P, ray, t, slot_obj);
+    }
+}
+
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void cast_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                                   double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out) {
+    query_body<ACCEL, OTHER, GEN, false>(P, origins, dirs, n, want_normal, nullptr, t_out, iters_out, sdf_out, normal_out, nullptr);
+}
+
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void pick_kernel(const RmRenderParams P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                                   const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out,
+                                                   float *normal_out, int32_t *obj_out) {
+    query_body<ACCEL, OTHER, GEN, true>(P, origins, dirs, n, want_normal, slot_obj, t_out, iters_out, sdf_out, normal_out, obj_out);
 }
 
 #ifndef RM_LENGTH_SQRT
@@ -1398,6 +1389,31 @@ hipError_t rm_launch_fastdiv_selftest(uint64_t seed, int64_t n, unsigned long lo
 
 // ---------------------------------------------------------------------- launchers
 
+namespace {
+// The dynamic LDS of a one-ray-per-lane launch of `threads` lanes: the expression programs' position slots and pending
+// values (rm_program.h), then, 16-byte aligned behind them, the per-ray BVH hit-leaf lists (v1_lists_begin reads
+// v1_list_offset; -1: no lists) -- where the caller wants them, the scene has them and they fit.
+struct V1Lds {
+    size_t bytes;
+    int32_t v1_list_offset;
+};
+V1Lds v1_lds_layout(const RmRenderParams &p, int threads, bool lists) {
+    V1Lds l{p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0, -1};
+    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
+    if (lists && p.accel == 2 && p.v1_lists && p.general < 2 && p.bvh_nodes < 65536 && l.bytes + list_bytes <= 64 * 1024) {
+        l.v1_list_offset = static_cast<int32_t>((l.bytes + 15) & ~static_cast<size_t>(15));
+        l.bytes = static_cast<size_t>(l.v1_list_offset) + list_bytes;
+    }
+    return l;
+}
+}  // namespace
+
+// RM_DISPATCH(K): K(ACCEL, OTHER, GEN) for the instantiation the parameter block `p` in scope selects (accel, algorithm, general).
+#define RM_DISPATCH_A(K, O, G) { if (p.accel == 2) K(2, O, G) else if (p.accel == 1) K(1, O, G) else K(0, O, G) }
+#define RM_DISPATCH_O(K, G) { if (p.algorithm == 0) RM_DISPATCH_A(K, false, G) else RM_DISPATCH_A(K, true, G) }
+#define RM_DISPATCH(K) { if (p.general == 3) RM_DISPATCH_O(K, 3) else if (p.general == 2) RM_DISPATCH_O(K, 2) else if (p.general) RM_DISPATCH_O(K, 1) else RM_DISPATCH_O(K, 0) }
+#define RM_KERNEL_NAME(kernel, A, O, G) #kernel "<" #A ", " #O ", " #G ">" RM_LEN_TAG
+
 hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t stream, const char **kernel_name) {
     const int rows = p.local_rows;
     if (kernel_name) *kernel_name = "";
@@ -1409,27 +1425,21 @@ hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t
     const int tiles_x = (p.width + tw - 1) / tw;
     const int tiles_y = (rows + wpw * th - 1) / (wpw * th);
     const dim3 grid((static_cast<unsigned>(tiles_x) * static_cast<unsigned>(tiles_y) + 63u) & ~63u), block(static_cast<unsigned>(threads));  // v1_tile_of_block
-    // expression programs keep their position slots and pending values in LDS (rm_program.h)
-    size_t shmem = p.general >= 2 && !p.rtc_function ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0;
+    const V1Lds lds = p.rtc_function ? V1Lds{0, -1} : v1_lds_layout(p, threads, true);
+    const size_t shmem = lds.bytes;
     RmRenderParams pl = p;
-    pl.v1_list_offset = -1;
-    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
-    if (p.accel == 2 && p.v1_lists && p.general < 2 && !p.rtc_function && p.bvh_nodes < 65536 && shmem + list_bytes <= 64 * 1024) {
-        pl.v1_list_offset = static_cast<int32_t>((shmem + 15) & ~static_cast<size_t>(15));  // per-ray hit-leaf lists behind the program slots
-        shmem = static_cast<size_t>(pl.v1_list_offset) + list_bytes;
-    }
+    pl.v1_list_offset = lds.v1_list_offset;
     if (p.rtc_function) {  // this scene's run-time specialised kernel (rm_rtc.h): same grid, nothing in LDS (set by the API layer for these launches only)
         size_t bytes = sizeof pl;
         void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &pl, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(const_cast<void *>(p.rtc_function)), grid.x, 1, 1, block.x, 1, 1, 0, stream, nullptr,
                                      extra);
     }
-#define RM_V1(A, O, G)                                                                       \
-    {                                                                                        \
-        hipLaunchKernelGGL((render_kernel<A, O, G>), grid, block, shmem, stream, pl);         \
-        if (kernel_name) *kernel_name = "render_kernel<" #A ", " #O ", " #G ">" RM_LEN_TAG;  \
+#define RM_V1(A, O, G)                                                               \
+    {                                                                                \
+        hipLaunchKernelGGL((render_kernel<A, O, G>), grid, block, shmem, stream, pl); \
+        if (kernel_name) *kernel_name = RM_KERNEL_NAME(render_kernel, A, O, G);      \
     }
-#define RM_V1A(O, G) { if (p.accel == 2) RM_V1(2, O, G) else if (p.accel == 1) RM_V1(1, O, G) else RM_V1(0, O, G) }
     if (p.accel == 1 && p.general == 0 && p.algorithm == 0 && p.oct_lean && p.oct_frame && p.oct_lut && p.oct_recs && p.filter && p.oct_nodes < (1 << 24) &&
         p.oct_prim_count < (1 << 26)) {  // 32-bit byte offsets into the node and record tables
         // one wave per workgroup, 8 x 8 pixels: wave slots refill one by one (four-wave workgroups wait for a free slot on every
@@ -1439,16 +1449,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t
         hipLaunchKernelGGL(render_kernel_oct, dim3((static_cast<unsigned>((p.width + 7) / 8) * static_cast<unsigned>(ty) + 63u) & ~63u), dim3(64), 0, stream,
                            pl);  // the lean octree sphere tracer (finite camera: rm_api.cpp)
         if (kernel_name) *kernel_name = "render_kernel_oct" RM_LEN_TAG;
-    } else if (p.general == 3) {
-        if (p.algorithm == 0) RM_V1A(false, 3) else RM_V1A(true, 3)
-    } else if (p.general == 2) {
-        if (p.algorithm == 0) RM_V1A(false, 2) else RM_V1A(true, 2)
-    } else if (p.general) {
-        if (p.algorithm == 0) RM_V1A(false, 1) else RM_V1A(true, 1)
-    } else {
-        if (p.algorithm == 0) RM_V1A(false, 0) else RM_V1A(true, 0)
-    }
-#undef RM_V1A
+    } else RM_DISPATCH(RM_V1)
 #undef RM_V1
     return hipGetLastError();
 }
@@ -1493,7 +1494,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
                               hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
-    const size_t shmem = p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * 256 : 0;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // (a point has no ray: no hit-leaf lists)
     if (p.rtc_function) {  // rm_rtc_distance(RmRenderParams, const float *, int64_t, double *, uint32_t *)
         struct Args {
             RmRenderParams p;
@@ -1507,86 +1508,40 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
         void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
         return hipModuleLaunchKernel(reinterpret_cast<hipFunction_t>(const_cast<void *>(p.rtc_function)), grid.x, 1, 1, 256, 1, 1, 0, stream, nullptr, extra);
     }
-#define RM_DK(A, G) hipLaunchKernelGGL((distance_kernel<A, G>), grid, block, shmem, stream, p, points, n, dist, count)
-    if (p.general == 3) { if (p.accel == 2) RM_DK(2, 3); else if (p.accel == 1) RM_DK(1, 3); else RM_DK(0, 3); }
-    else if (p.general == 2) { if (p.accel == 2) RM_DK(2, 2); else if (p.accel == 1) RM_DK(1, 2); else RM_DK(0, 2); }
-    else if (p.general) { if (p.accel == 2) RM_DK(2, 1); else if (p.accel == 1) RM_DK(1, 1); else RM_DK(0, 1); }
-    else { if (p.accel == 2) RM_DK(2, 0); else if (p.accel == 1) RM_DK(1, 0); else RM_DK(0, 0); }
+#define RM_DK(A, O, G) { hipLaunchKernelGGL((distance_kernel<A, G>), grid, block, shmem, stream, p, points, n, dist, count); }
+    RM_DISPATCH(RM_DK)
 #undef RM_DK
     return hipGetLastError();
 }
 
-hipError_t RM_LEN_VARIANT(rm_launch_cast)(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal, double *t,
-                                          uint32_t *iters, uint32_t *sdf, float *normal, hipStream_t stream, const char **kernel_name) {
+hipError_t RM_LEN_VARIANT(rm_launch_query)(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
+                                           const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
+                                           hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "";
     if (n <= 0) return hipSuccess;
     const int threads = 256;
     const dim3 grid(static_cast<unsigned>((n + threads - 1) / threads)), block(threads);
-    // the LDS of the one-ray-per-lane render launch: expression programs' slots, then the per-ray hit-leaf lists
-    size_t shmem = p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0;
+    const V1Lds lds = v1_lds_layout(p, threads, true);  // the LDS of the one-ray-per-lane render launch, so the march is the same
+    const size_t shmem = lds.bytes;
     RmRenderParams pl = p;
     pl.rtc_function = nullptr;
     pl.diag_block = nullptr;
     pl.diag_out = nullptr;
-    pl.v1_list_offset = -1;
-    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
-    if (p.accel == 2 && p.v1_lists && p.general < 2 && p.bvh_nodes < 65536 && shmem + list_bytes <= 64 * 1024) {
-        pl.v1_list_offset = static_cast<int32_t>((shmem + 15) & ~static_cast<size_t>(15));
-        shmem = static_cast<size_t>(pl.v1_list_offset) + list_bytes;
-    }
+    pl.v1_list_offset = lds.v1_list_offset;
     const int32_t wn = want_normal ? 1 : 0;
-#define RM_CK(A, O, G)                                                                                                 \
-    {                                                                                                                  \
-        hipLaunchKernelGGL((cast_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, t, iters, sdf, normal); \
-        if (kernel_name) *kernel_name = "cast_kernel<" #A ", " #O ", " #G ">" RM_LEN_TAG;                             \
+#define RM_QK(A, O, G)                                                                                                                \
+    {                                                                                                                                 \
+        if (pick) {                                                                                                                   \
+            hipLaunchKernelGGL((pick_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, slot_obj, t, iters, sdf, \
+                               normal, object);                                                                                       \
+            if (kernel_name) *kernel_name = RM_KERNEL_NAME(pick_kernel, A, O, G);                                                     \
+        } else {                                                                                                                      \
+            hipLaunchKernelGGL((cast_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, t, iters, sdf, normal);  \
+            if (kernel_name) *kernel_name = RM_KERNEL_NAME(cast_kernel, A, O, G);                                                     \
+        }                                                                                                                             \
     }
-#define RM_CKA(O, G) { if (p.accel == 2) RM_CK(2, O, G) else if (p.accel == 1) RM_CK(1, O, G) else RM_CK(0, O, G) }
-#define RM_CKO(G) { if (p.algorithm == 0) RM_CKA(false, G) else RM_CKA(true, G) }
-    if (p.general == 3) RM_CKO(3)
-    else if (p.general == 2) RM_CKO(2)
-    else if (p.general) RM_CKO(1)
-    else RM_CKO(0)
-#undef RM_CKO
-#undef RM_CKA
-#undef RM_CK
-    return hipGetLastError();
-}
-
-hipError_t RM_LEN_VARIANT(rm_launch_pick)(const RmRenderParams &p, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                                          const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                                          hipStream_t stream, const char **kernel_name) {
-    if (kernel_name) *kernel_name = "";
-    if (n <= 0) return hipSuccess;
-    const int threads = 256;
-    const dim3 grid(static_cast<unsigned>((n + threads - 1) / threads)), block(threads);
-    // the launch rm_launch_cast makes (same LDS layout, same parameter block), so the march is the same
-    size_t shmem = p.general >= 2 ? (static_cast<size_t>(p.prog_slots) * 12 + static_cast<size_t>(p.prog_vals) * 8) * threads : 0;
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
-    pl.v1_list_offset = -1;
-    const size_t list_bytes = static_cast<size_t>(2) * RM_V1_LIST_CAP * threads;
-    if (p.accel == 2 && p.v1_lists && p.general < 2 && p.bvh_nodes < 65536 && shmem + list_bytes <= 64 * 1024) {
-        pl.v1_list_offset = static_cast<int32_t>((shmem + 15) & ~static_cast<size_t>(15));
-        shmem = static_cast<size_t>(pl.v1_list_offset) + list_bytes;
-    }
-    const int32_t wn = want_normal ? 1 : 0;
-#define RM_PK(A, O, G)                                                                                                 \
-    {                                                                                                                  \
-        hipLaunchKernelGGL((pick_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, slot_obj, t, iters, sdf, \
-                           normal, object);                                                                            \
-        if (kernel_name) *kernel_name = "pick_kernel<" #A ", " #O ", " #G ">" RM_LEN_TAG;                             \
-    }
-#define RM_PKA(O, G) { if (p.accel == 2) RM_PK(2, O, G) else if (p.accel == 1) RM_PK(1, O, G) else RM_PK(0, O, G) }
-#define RM_PKO(G) { if (p.algorithm == 0) RM_PKA(false, G) else RM_PKA(true, G) }
-    if (p.general == 3) RM_PKO(3)
-    else if (p.general == 2) RM_PKO(2)
-    else if (p.general) RM_PKO(1)
-    else RM_PKO(0)
-#undef RM_PKO
-#undef RM_PKA
-#undef RM_PK
+    RM_DISPATCH(RM_QK)
+#undef RM_QK
     return hipGetLastError();
 }
 

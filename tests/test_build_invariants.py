@@ -4,10 +4,12 @@ SIMD and rendered wrong pixels, non-deterministically.  Round 3: EVERY v2 instan
 80 VGPRs -- six waves per SIMD -- without a spilled VGPR and without scratch, and so do the sphere / primitive
 instantiations of the one-ray-per-lane kernel (the expression-program ones, GEN = 2 / 3, keep their interpreter's stack:
 listed here with their bound, so that a change that makes it grow shows up)."""
+import functools
 import os
 import re
 import shutil
 import subprocess
+import tempfile
 
 import pytest
 
@@ -18,12 +20,21 @@ HIPCC = "/opt/rocm/bin/hipcc"
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC) or shutil.which("c++filt") is None, reason="hipcc / c++filt not present")
 
 
+@functools.lru_cache(maxsize=None)
+def compiled(source, extra=()):
+    """(remarks, listing lines) of one device compile of `source`, once per process for every (source, extra): the flags of
+    csrc/Makefile (DEVFLAGS included: the inliner's basic-block limit decides what is inlined)."""
+    with tempfile.TemporaryDirectory() as tmp:
+        out = os.path.join(tmp, "listing.s")
+        remarks = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-S",
+                                  "--cuda-device-only", "-mllvm", "-amdgpu-inline-max-bb=100000", "-Rpass-analysis=kernel-resource-usage",
+                                  "-o", out, os.path.join(CSRC, source), *extra],
+                                 stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900, check=True).stdout.decode()
+        return remarks, open(out).read().split("\n")
+
+
 def resource_usage(extra=(), source="rm_render_v2.hip"):
-    # the flags of csrc/Makefile (DEVFLAGS included: the inliner's basic-block limit decides what is inlined)
-    out = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only",
-                          "-mllvm", "-amdgpu-inline-max-bb=100000",
-                          "-Rpass-analysis=kernel-resource-usage", "-o", os.devnull, os.path.join(CSRC, source), *extra],
-                         stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=900).stdout.decode()
+    out = compiled(source, tuple(extra))[0]
     rows, cur = [], None
     for line in out.split("\n"):
         m = re.search(r"Function Name: (\S+)", line)
@@ -37,6 +48,17 @@ def resource_usage(extra=(), source="rm_render_v2.hip"):
                 cur[key] = int(m.group(1))
     names = subprocess.check_output(["c++filt"] + [r["name"] for r in rows]).decode().split("\n")
     return {n.replace("(anonymous namespace)::", ""): r for n, r in zip(names, rows)}
+
+
+def assert_no_vgpr_spill(kernels, gen23_scratch=None):
+    """No instantiation <..., GEN> spills a VGPR; GEN 0 / 1 use no scratch, GEN 2 / 3 at most gen23_scratch B/lane (None: unbounded)."""
+    for name, r in kernels.items():
+        gen = int(name.split("<")[1].split(">")[0].split(",")[-1])
+        assert r["VGPRs Spill"] == 0, (name, r)
+        if gen <= 1:
+            assert r["ScratchSize [bytes/lane]"] == 0, (name, r)
+        elif gen23_scratch is not None:
+            assert r["ScratchSize [bytes/lane]"] <= gen23_scratch, (name, r)
 
 
 def test_makefile_uses_the_flags_checked_here():
@@ -62,13 +84,7 @@ def test_one_ray_per_lane_kernels_spill_no_vgpr(extra):
     usage = resource_usage(extra, "rm_kernels.hip")
     kernels = {n: r for n, r in usage.items() if n.startswith(("void render_kernel<", "void distance_kernel<"))}
     assert len(kernels) >= 24 + 12, sorted(usage)
-    for name, r in kernels.items():
-        gen = int(name.split("<")[1].split(">")[0].split(",")[-1])
-        assert r["VGPRs Spill"] == 0, (name, r)
-        if gen <= 1:
-            assert r["ScratchSize [bytes/lane]"] == 0, (name, r)
-        else:
-            assert r["ScratchSize [bytes/lane]"] <= 800, (name, r)
+    assert_no_vgpr_spill(kernels, 800)
 
 
 @pytest.mark.parametrize("extra", [(), ("-DRM_LENGTH_SQRT",)])
@@ -82,14 +98,21 @@ def test_lean_octree_kernel_keeps_eight_waves_without_spills(extra):
 
 
 def listing(source, extra=()):
-    out = os.path.join("/tmp", "rm_inv_%d_%s.s" % (os.getpid(), os.path.basename(source)))
-    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-S", "--cuda-device-only",
-                    "-mllvm", "-amdgpu-inline-max-bb=100000", "-o", out, os.path.join(CSRC, source), *extra],
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=900, check=True)
-    try:
-        return open(out).read().split("\n")
-    finally:
-        os.remove(out)
+    return compiled(source, tuple(extra))[1]
+
+
+def kernel_spans(lines, mangled):
+    """[first, end) line ranges of the listing's functions whose label contains `mangled` (e.g. 11cast_kernel)."""
+    spans, cur = [], None
+    for n, t in enumerate(lines):
+        if t.startswith("_Z") and t.split(";")[0].rstrip().endswith(":"):  # a function's label
+            cur = [n, len(lines)] if mangled in t else None
+            if cur:
+                spans.append(cur)
+        elif cur is not None and t.strip().startswith(".Lfunc_end"):
+            cur[1] = n
+            cur = None
+    return spans
 
 
 def spill_code_ahead_of_exec_restore(lines):

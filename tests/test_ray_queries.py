@@ -121,36 +121,23 @@ def test_camera_rays_rejects_bad_frames(rm):
 
 @pytest.mark.parametrize("extra", [(), ("-DRM_LENGTH_SQRT",)])
 def test_cast_kernels_spill_nothing(extra):
-    from test_build_invariants import HIPCC, resource_usage
+    from test_build_invariants import HIPCC, assert_no_vgpr_spill, resource_usage
     import shutil
     if not os.path.exists(HIPCC) or shutil.which("c++filt") is None:
         pytest.skip("hipcc / c++filt not present")
     usage = resource_usage(extra, "rm_kernels.hip")
     kernels = {n: r for n, r in usage.items() if n.startswith("void cast_kernel<")}
     assert len(kernels) == 24, sorted(kernels)
-    for name, r in kernels.items():
-        gen = int(name.split("<")[1].split(">")[0].split(",")[-1])
-        assert r["VGPRs Spill"] == 0, (name, r)
-        if gen <= 1:
-            assert r["ScratchSize [bytes/lane]"] == 0, (name, r)
+    assert_no_vgpr_spill(kernels)
 
 
 @pytest.mark.parametrize("extra", [(), ("-DRM_LENGTH_SQRT",)])
 def test_cast_kernels_have_no_spill_ahead_of_an_exec_restore(extra):
-    from test_build_invariants import HIPCC, listing, spill_code_ahead_of_exec_restore
+    from test_build_invariants import HIPCC, kernel_spans, listing, spill_code_ahead_of_exec_restore
     if not os.path.exists(HIPCC):
         pytest.skip("hipcc not present")
     lines = listing("rm_kernels.hip", extra)
-    # the functions of the listing that belong to cast_kernel instantiations (mangled: 11cast_kernel)
-    spans, cur = [], None
-    for n, t in enumerate(lines):
-        if t.startswith("_Z") and t.split(";")[0].rstrip().endswith(":"):  # a function's label
-            cur = [n, len(lines)] if "11cast_kernel" in t else None
-            if cur:
-                spans.append(cur)
-        elif cur is not None and t.strip().startswith(".Lfunc_end"):
-            cur[1] = n
-            cur = None
+    spans = kernel_spans(lines, "11cast_kernel")
     assert len(spans) == 24, len(spans)
     for a, b in spans:
         assert not spill_code_ahead_of_exec_restore(lines[a:b]), lines[a]
