@@ -54,7 +54,7 @@ class rm_scene_info(C.Structure):
                 ("bvh_nodes", C.c_int32), ("bvh_leaves", C.c_int32), ("bvh_depth", C.c_int32),
                 ("oct_nodes", C.c_int32), ("oct_leaves", C.c_int32), ("oct_empty_leaves", C.c_int32),
                 ("oct_max_leaf_prims", C.c_int32), ("root_min", C.c_float * 3), ("root_max", C.c_float * 3),
-                ("nodes_in_lds", C.c_int32), ("reserved", C.c_int32)]
+                ("nodes_in_lds", C.c_int32), ("program", C.c_int32)]
 
 
 class rm_node(C.Structure):  # include/rm_raymarch.h: struct rm_node

@@ -152,6 +152,8 @@ class Context:
         d = {k: getattr(info, k) for k, _ in info._fields_ if k not in ("root_min", "root_max", "reserved")}
         d["root_min"] = [float(v) for v in info.root_min]
         d["root_max"] = [float(v) for v in info.root_max]
+        # expression forests: what the interpreter's program needs (0 for the other scene kinds)
+        d["prog_slots"], d["prog_vals"], d["prog_instructions"] = info.program & 0xFF, (info.program >> 8) & 0xFF, info.program >> 16
         return d
 
     def scene_distance(self, points):
@@ -348,12 +350,16 @@ class Context:
         N.check(self._h, N.lib().rm_rtc_source(self._h, buf, len(buf), None))
         return buf.value.decode()
 
-    def rtc_compile_check(self, accel=0, other=False):
+    def rtc_compile_check(self, accel=0, other=False, refused_ok=False):
         """Compiles the active scene's specialised kernel for gfx950 without loading it (no GPU needed).
-        Returns (compiler log with the resource-usage remarks, seconds)."""
+        Returns (compiler log with the resource-usage remarks, seconds).  A kernel that spills a VGPR is refused, as a
+        render would refuse it (the interpreter kernel then serves the scene): RuntimeError, or with refused_ok the
+        log -- it then starts with "refused:"."""
         buf = C.create_string_buffer(1 << 16)
         secs = C.c_double(0)
         rc = N.lib().rm_rtc_compile_check(self._h, int(accel), int(bool(other)), buf, len(buf), C.byref(secs))
+        if rc == N.RM_E_UNSUPPORTED and refused_ok and buf.value.startswith(b"refused:"):
+            return buf.value.decode(), secs.value
         if rc != 0:
             raise RuntimeError("rm_rtc_compile_check: %s\n%s" % (N.lib().rm_last_error(self._h).decode(), buf.value.decode()))
         return buf.value.decode(), secs.value

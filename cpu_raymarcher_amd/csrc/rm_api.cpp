@@ -141,7 +141,8 @@ struct rm_ctx {
     // Expression forests: the scene's programs compiled into the one-ray-per-lane kernels at run time (rm_rtc.h; option
     // `specialise`, default on).  One kernel per (acceleration structure, marcher family, vec3.length form) the scene is
     // rendered with, compiled at its first launch (1.5 - 3 s, synchronous) and kept until the scene is replaced.  A compile
-    // that fails is remembered with its log (rm_rtc_status) and the interpreter of rm_program.h serves the scene.
+    // that fails, or whose kernel spills a VGPR (refused: rm_rtc.h), is remembered with its log (rm_rtc_status) and the
+    // interpreter of rm_program.h serves the scene.
     int64_t opt_specialise = 1;
     // sphere lists of fewer spheres than this run in the one-ray-per-lane kernels as the scene's own code (C2, nine spheres at
     // 1080p: 0.22 ms alone against 0.32 in the v2 wave loop, 8 780 against 8 340 frames/s in flight); without hiprtc the rule is < 8
@@ -1135,6 +1136,7 @@ int rm_scene_get_info(const rm_ctx *ctx, rm_scene_info *out) {
     std::memcpy(out->root_min, h.root_min, sizeof h.root_min);
     std::memcpy(out->root_max, h.root_max, sizeof h.root_max);
     out->nodes_in_lds = static_cast<int32_t>(ctx->opt_lds);
+    if (h.program) out->program = h.prog_slots | (h.prog_vals << 8) | (static_cast<int32_t>(h.prog.size()) << 16);
     return RM_OK;
 }
 
@@ -1655,10 +1657,12 @@ int rm_rtc_compile_check(rm_ctx *ctx, int32_t accel, int32_t other, char *log, i
     if (!ctx->have_scene || ctx->rtc_src.empty()) return fail(ctx, RM_E_NO_SCENE, "the active scene has no specialised source");
     rmrtc::Kernel k;
     std::string text;
-    const bool ok = rmrtc::compile(ctx->rtc_src, norm_accel(accel), other != 0, ctx->opt_length != 0, false, true, k, text);
+    const bool ok = rmrtc::compile(ctx->rtc_src, norm_accel(accel), other != 0, ctx->opt_length != 0, false, k, text);
     if (seconds) *seconds = k.compile_seconds;
     copy_text(text, log, cap, nullptr);
-    return ok ? RM_OK : fail(ctx, RM_E_INVALID, "hiprtc: the specialised kernel did not compile (see the log)");
+    if (ok) return RM_OK;
+    if (text.compare(0, 8, "refused:") == 0) return fail(ctx, RM_E_UNSUPPORTED, "hiprtc: the specialised kernel spills and would not be loaded (see the log)");
+    return fail(ctx, RM_E_INVALID, "hiprtc: the specialised kernel did not compile (see the log)");
 }
 
 int rm_rtc_status(rm_ctx *ctx, int32_t *compiled, int32_t *failed, char *log, int64_t cap) {

@@ -504,8 +504,8 @@ struct Unit {
     const char *render_fn;    // kernel to look up (out.render)
     const char *distance_fn;  // second kernel (out.distance) or null
     std::string display;      // what rm_last_kernel reports
-    bool no_spills;           // refuse a kernel that spills VGPRs or uses scratch (the v2 wave loop: the ahead-of-time build holds that line, and
-                              // hipcc 7.2 can place a spill ahead of an EXEC restore: profiles/r03/spill_exec_hazard.txt)
+    bool no_scratch;          // refuse a kernel that uses scratch at all (the v2 wave loop: the ahead-of-time build holds that line); scene kernels
+                              // may carry scratch (the fdlibm tables of rm_jsmath.h), never a spilled VGPR
 };
 
 // the value behind "<key>: N" of the resource-usage remarks of function `fn` (-1: not found)
@@ -518,7 +518,7 @@ long remark_of(const std::string &log, const char *fn, const char *key) {
     return std::strtol(log.c_str() + at + std::strlen(key) + 2, nullptr, 10);
 }
 
-bool compile_unit(const Unit &u, bool load_module, bool want_remarks, Kernel &out, std::string &log) {
+bool compile_unit(const Unit &u, bool load_module, Kernel &out, std::string &log) {
     Rtc &r = rtc();
     if (!r.lib) {
         log = r.why;
@@ -549,7 +549,8 @@ bool compile_unit(const Unit &u, bool load_module, bool want_remarks, Kernel &ou
     }
     // the flags of csrc/Makefile
     std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-inline-max-bb=100000"};
-    if (want_remarks || u.no_spills) opts.push_back("-Rpass-analysis=kernel-resource-usage");
+    // (always: every kernel compiled here is held to zero spilled VGPRs, see below)
+    opts.push_back("-Rpass-analysis=kernel-resource-usage");
     const auto t0 = std::chrono::steady_clock::now();
     const hiprtcResult res = r.compile(prog, static_cast<int>(opts.size()), opts.data());
     out.compile_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -563,11 +564,16 @@ bool compile_unit(const Unit &u, bool load_module, bool want_remarks, Kernel &ou
         if (log.empty()) log = "hiprtcCompileProgram failed";
         return false;
     }
-    if (u.no_spills) {
-        const long spills = remark_of(log, u.render_fn, "VGPRs Spill"), scratch = remark_of(log, u.render_fn, "ScratchSize [bytes/lane]");
-        if (spills != 0 || scratch != 0) {
+    // No kernel that spills a VGPR is loaded: hipcc 7.2 can place a folded spill ahead of an EXEC restore, which gives wrong,
+    // run-to-run varying pixels (profiles/r03/spill_exec_hazard.txt).  The ahead-of-time kernels are held to that line by the
+    // build's tests; a kernel compiled here is a function of the caller's scene, so the line is held here.  A remark that is
+    // missing (-1) refuses too: what cannot be inspected is not launched.
+    for (const char *fn : {u.render_fn, u.distance_fn}) {
+        if (!fn) continue;
+        const long spills = remark_of(log, fn, "VGPRs Spill"), scratch = remark_of(log, fn, "ScratchSize [bytes/lane]");
+        if (spills != 0 || (u.no_scratch && scratch != 0)) {
             r.destroy(&prog);
-            log = "refused: " + std::string(u.render_fn) + " spills " + std::to_string(spills) + " VGPRs, " + std::to_string(scratch) + " bytes of scratch per lane\n" + log;
+            log = "refused: " + std::string(fn) + " spills " + std::to_string(spills) + " VGPRs, " + std::to_string(scratch) + " bytes of scratch per lane\n" + log;
             return false;
         }
     }
@@ -576,7 +582,8 @@ bool compile_unit(const Unit &u, bool load_module, bool want_remarks, Kernel &ou
     std::vector<char> code(cs);
     r.code(prog, code.data());
     r.destroy(&prog);
-    out.name = u.display;
+    out.name = u.display;  // (set from here on: the compile and the spill rule are passed, what can still fail is the load)
+    out.log = log;
     if (!load_module) return true;
     hipModule_t mod = nullptr;
     hipFunction_t fr = nullptr, fd = nullptr;
@@ -608,8 +615,7 @@ std::string lit_of<double>(double v) { return lit_d(v); }
 
 }  // namespace
 
-bool compile(const std::string &scene_src, int accel, bool other, bool length_sqrt, bool load_module, bool want_remarks, Kernel &out,
-             std::string &log) {
+bool compile(const std::string &scene_src, int accel, bool other, bool length_sqrt, bool load_module, Kernel &out, std::string &log) {
     if (scene_src.empty()) {
         log = "no specialised source for this scene";
         return false;
@@ -623,8 +629,8 @@ bool compile(const std::string &scene_src, int accel, bool other, bool length_sq
     u.render_fn = "rm_rtc_render";
     u.distance_fn = "rm_rtc_distance";
     u.display = std::string("rm_rtc_render<") + std::to_string(accel) + ", " + (other ? "true" : "false") + ">" + (length_sqrt ? " [length=sqrt]" : "");
-    u.no_spills = false;
-    return compile_unit(u, load_module, want_remarks, out, log);
+    u.no_scratch = false;
+    return compile_unit(u, load_module, out, log);
 }
 
 // ---- the v2 wave loop with a launch configuration's parameters as literals (rm_v2_fields.h) -------------------------------------
@@ -670,8 +676,8 @@ bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool
     u.render_fn = "rm_rtc_render_v2";
     u.distance_fn = nullptr;
     u.display = "rm_rtc_render_v2";
-    u.no_spills = true;
-    return compile_unit(u, load_module, false, out, log);
+    u.no_scratch = true;
+    return compile_unit(u, load_module, out, log);
 }
 
 namespace {
@@ -694,7 +700,7 @@ std::string cache_key(int device, const std::string &scene_src, int accel, bool 
 }
 bool compile_any(const std::string &src, int accel, bool other, bool length_sqrt, Kernel &out, std::string &log) {
     if (accel & kV2Bit) return compile_v2(src, accel & 3, (accel >> 2) & 1, (accel >> 3) & 1, (accel >> 4) & 1, length_sqrt, true, out, log);
-    return compile(src, accel, other, length_sqrt, true, false, out, log);
+    return compile(src, accel, other, length_sqrt, true, out, log);
 }
 }  // namespace
 
@@ -707,10 +713,20 @@ bool compile_cached(int device, const std::string &scene_src, int accel, bool ot
     if (it != c.done.end()) {
         out = it->second;
         out.compile_seconds = 0;
+        log = out.log;
         if (cached) *cached = true;
         return true;
     }
-    if (!compile_any(scene_src, accel, other, length_sqrt, out, log)) return false;
+    auto f = c.failed.find(key);  // (a refused key or a compile error is not compiled again: the same source gives the same answer)
+    if (f != c.failed.end()) {
+        log = f->second;
+        return false;
+    }
+    if (!compile_any(scene_src, accel, other, length_sqrt, out, log)) {
+        // (out.name is set once the compile and the spill rule are passed: a module that then fails to LOAD is tried again)
+        if (out.name.empty() && c.failed.size() < static_cast<size_t>(kCacheEntries)) c.failed[key] = log;
+        return false;
+    }
     const bool keep = c.done.size() < static_cast<size_t>(kCacheEntries);
     if (keep) c.done.emplace(key, out);
     if (cached) *cached = keep;
@@ -726,6 +742,7 @@ int compile_async(int device, const std::string &scene_src, int accel, bool othe
         if (it != c.done.end()) {
             out = it->second;
             out.compile_seconds = 0;
+            log = out.log;
             return 1;
         }
         auto f = c.failed.find(key);

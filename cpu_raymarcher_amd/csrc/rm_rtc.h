@@ -22,6 +22,7 @@ struct Kernel {
     void *distance = nullptr;     // hipFunction_t of rm_rtc_distance(RmRenderParams, const float *, int64_t, double *, uint32_t *)
     std::string name;             // "rm_rtc_render<ACCEL, OTHER>" + length tag, as rm_last_kernel reports it
     double compile_seconds = 0;
+    std::string log;              // the compiler's log of this kernel's compile (resource-usage remarks): what the spill rule read
 };
 
 // Straight-line source of a scene's programs: defines rmd::rm_rtc_object_sdf(int obj, const Vec3f &p, double time).
@@ -40,9 +41,10 @@ bool available(std::string *why);
 
 // Compiles rm_kernels.hip for (accel, other, length) around scene_src.  With load_module the code object is loaded into the
 // current device's context and the kernel handles are looked up; without (a machine with no GPU: tests of the build) only the
-// compile is done.  *log receives hiprtc's log (resource-usage remarks included when want_remarks).
-bool compile(const std::string &scene_src, int accel, bool other, bool length_sqrt, bool load_module, bool want_remarks, Kernel &out,
-             std::string &log);
+// compile is done.  *log receives hiprtc's log with the resource-usage remarks.  A kernel that spills a VGPR in either
+// function is refused (false; the log starts with "refused: " and names the function and the count): scratch is allowed
+// (the fdlibm tables), a spill is not (profiles/r03/spill_exec_hazard.txt); the interpreter serves such a scene.
+bool compile(const std::string &scene_src, int accel, bool other, bool length_sqrt, bool load_module, Kernel &out, std::string &log);
 void release(Kernel &k);
 
 // The v2 wave loop (rm_render_v2.hip) compiled for ONE launch configuration: rm_v2_fix() assigns every configuration parameter
@@ -62,7 +64,10 @@ constexpr int kCacheEntries = 256;
 bool compile_cached(int device, const std::string &scene_src, int accel, bool other, bool length_sqrt, Kernel &out, std::string &log, bool *cached);
 // The same without waiting: 1 = the kernel is in the cache (out is set), 0 = a background thread is compiling it (started by
 // this call or an earlier one; the caller renders with its ahead-of-time kernels meanwhile -- same bytes), -1 = that compile
-// failed or the cache is full (log says which).
+// failed, was refused or the cache is full (log says which).  A compile error or a refusal is remembered per key by both
+// calls (the same source gives the same answer: not compiled again); compile_cached does not remember a module that
+// compiled and then failed to load (out of device memory, say), and tries that one again.  On a hit `log` is the log of
+// the compile that made the kernel.
 int compile_async(int device, const std::string &scene_src, int accel, bool other, bool length_sqrt, Kernel &out, std::string &log);
 
 }  // namespace rmrtc

@@ -102,7 +102,9 @@ typedef struct rm_scene_info {
     int32_t oct_nodes, oct_leaves, oct_empty_leaves, oct_max_leaf_prims;
     float   root_min[3], root_max[3];
     int32_t nodes_in_lds;    /* 1 when the flattened node table is staged in LDS */
-    int32_t reserved;
+    int32_t program;         /* expression forests: what the interpreter's program needs, position slots | pending values << 8 |
+                                instructions << 16 (accepted: up to 15 slots -- one fewer than RM_PROG_MAX_SLOTS, a node at
+                                slot s may write slot s + 1 --, up to 16 values, (slots * 12 + values * 8) * 256 <= 64 KiB); else 0 */
 } rm_scene_info;
 
 /* diagnostics of main.ts:528-548 */
@@ -418,8 +420,13 @@ RM_API int rm_debug_read_stamps(rm_ctx *ctx, uint64_t *out8);
  * interpreter serves the scene (same results: both call the same formula functions in the same order).
  *   rm_rtc_source         the generated source of the active scene (NUL-terminated, truncated to cap; *needed = full size)
  *   rm_rtc_compile_check  compiles it for (accel, other != 0: the marchers other than the sphere tracer) without loading the
- *                         result -- works on a host-only context; log receives the compiler's resource-usage remarks
- *   rm_rtc_status         kernels compiled / failed for the active scene and the most recent compile log (or why hiprtc is absent) */
+ *                         result -- works on a host-only context; log receives the compiler's resource-usage remarks.
+ *                         A kernel that spills a VGPR (in rm_rtc_render or rm_rtc_distance) is never loaded: a render would
+ *                         record the compile as failed and launch the interpreter kernel.  This call applies the same rule:
+ *                         it returns RM_E_UNSUPPORTED and the log starts with "refused: <function> spills N VGPRs" (the
+ *                         compiler's remarks follow); RM_E_INVALID is a compile error
+ *   rm_rtc_status         kernels compiled / failed for the active scene and the log of the compile behind the most recent kernel
+ *                         lookup -- also when the kernel or the refusal came from the process-wide cache (or why hiprtc is absent) */
 RM_API int rm_rtc_source(rm_ctx *ctx, char *out, int64_t cap, int64_t *needed);
 RM_API int rm_rtc_compile_check(rm_ctx *ctx, int32_t accel, int32_t other, char *log, int64_t cap, double *seconds);
 RM_API int rm_rtc_status(rm_ctx *ctx, int32_t *compiled, int32_t *failed, char *log, int64_t cap);
