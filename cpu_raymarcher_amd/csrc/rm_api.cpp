@@ -27,27 +27,31 @@
 
 namespace {
 
+// Every table of the device-resident scene, once: X(name, always) -- HostScene::name is uploaded to DeviceScene::name, a pointer
+// to the same element type.  `always` 0: an empty table stays a null pointer (slot_object: null says that device slots are
+// object indices).
+#define RM_SCENE_ARRAYS(X)                                                                                                        \
+    X(spheres, 1) X(radii, 1) X(bvh, 1) X(bvh_prims, 1) X(oct, 1) X(oct_prims, 1) X(pq_cells, 1) X(pq_list, 1) X(nn_cells, 1)      \
+    X(nn_list, 1) X(prims, 1) X(prog, 1) X(obj_ranges, 1) X(oct_recs, 1) X(oct_lut, 1) X(oct_sub_hdr, 1) X(oct_sub_list, 1)       \
+    X(slot_object, 0)
+
 struct DeviceScene {
-    RmSphere *spheres = nullptr;
-    double *radii = nullptr;
-    RmBvhNode *bvh = nullptr;
-    int32_t *bvh_prims = nullptr;
-    RmOctNode *oct = nullptr;
-    int32_t *oct_prims = nullptr;
-    uint32_t *pq_cells = nullptr;
-    uint16_t *pq_list = nullptr;
-    uint32_t *nn_cells = nullptr;
-    uint16_t *nn_list = nullptr;
-    RmPrim *prims = nullptr;
-    RmInstr *prog = nullptr;
-    int32_t *obj_ranges = nullptr;
-    RmSphereRec *oct_recs = nullptr;
-    int32_t *oct_lut = nullptr;
-    uint32_t *oct_sub_hdr = nullptr;
-    uint8_t *oct_sub_list = nullptr;
-    uint16_t *bvh_leaves = nullptr;  // node indices of the non-empty BVH leaves, increasing (v2 bundle cull)
-    int32_t *slot_object = nullptr;  // HostScene::slot_object (null: device slots are object indices)
+#define RM_X(name, always) decltype(rmh::HostScene::name)::value_type *name = nullptr;
+    RM_SCENE_ARRAYS(RM_X)
+#undef RM_X
+    uint16_t *bvh_leaves = nullptr;  // node indices of the non-empty BVH leaves, increasing (v2 bundle cull: cull_leaf_table)
     int32_t bvh_leaf_count = 0;      // 0: no cull (no BVH, too many leaves, or a leaf box not inside its ancestors')
+};
+
+// What a scene is built from, in one of the three shapes the builders of rm_scene_host.h take: an upload as it was given, or
+// a preset's objects.
+struct SceneDesc {
+    enum Kind { kSpheres, kPrims, kNodes } kind = kSpheres;
+    std::vector<float> centers;  // kSpheres: x, y, z per sphere ...
+    std::vector<double> radii;   // ... and its radius
+    std::vector<rmh::PrimDesc> prims;  // kPrims
+    std::vector<rmh::NodeDesc> nodes;  // kNodes: the forest ...
+    std::vector<int> roots;            // ... and its objects
 };
 
 }  // namespace
@@ -64,14 +68,8 @@ struct rm_ctx {
     rmh::HostScene host;
     DeviceScene dev;
 
-    bool have_uploaded = false;  // sphere list kept for accel changes by later jobs
-    std::vector<float> up_centers;
-    std::vector<double> up_radii;
-    std::vector<rmh::PrimDesc> up_prims;  // when the uploaded scene came from rm_scene_from_prims
-    bool up_general = false;
-    std::vector<rmh::NodeDesc> up_nodes;  // when it came from rm_scene_from_nodes
-    std::vector<int> up_roots;
-    bool up_program = false;
+    bool have_uploaded = false;
+    SceneDesc uploaded;  // the last rm_scene_from_spheres / _prims / _nodes upload, kept for accel changes by later jobs
     double time = 0.0;  // Scene.updateTime: the last job's time, or rm_scene_set_time
 
     void *scratch = nullptr;
@@ -80,7 +78,7 @@ struct rm_ctx {
     float light[3] = {0, 0, 0};
 
     int64_t opt_tile_w = 8;  // 8 x 8-pixel batches (a frame alone, round 3: 128-pixel items of 8 x 16: 1.09 ms; of 16 x 8: 1.17 ms)
-    bool tile_w_set = false;  // rm_set_option("tile_w") was called: the value then holds for every kernel (else v1 kernels use 8 x 8 wave tiles)
+    bool tile_w_set = false;  // the tile_w option was set: the value then holds for every kernel (else v1 kernels use 8 x 8 wave tiles)
     int64_t opt_filter = 1;
     int64_t opt_lds = 1;
     int64_t opt_kernel = 0;  // 0 = auto: v2 for BVH / no acceleration, v1 for the octree (its lean kernel for sphere scenes: opt_oct_lean) and small scenes
@@ -197,6 +195,17 @@ int hip_fail(rm_ctx *ctx, hipError_t e, const char *what) {
     return fail(ctx, RM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// A kernel compiled at run time (rm_rtc.h), as `specialise` says: 1 waits for the compile; 2 never waits -- the ahead-of-time
+// kernels render until the background compile has finished.  1: k is set; 0: still compiling; -1: failed or refused.  The
+// compiler's log goes to ctx->rtc_log either way.
+int obtain_kernel(rm_ctx *ctx, const std::string &src, int accel, bool other, bool length_sqrt, rmrtc::Kernel &k) {
+    if (ctx->opt_specialise == 2) return rmrtc::compile_async(ctx->device, src, accel, other, length_sqrt, k, ctx->rtc_log);
+    bool cached = false;
+    if (!rmrtc::compile_cached(ctx->device, src, accel, other, length_sqrt, k, ctx->rtc_log, &cached)) return -1;
+    if (!cached) ctx->rtc_owned.push_back(k);  // the process-wide cache is full: this context unloads the module with the scene
+    return 1;
+}
+
 // the kernels exist twice: vec3.length = Math.hypot, and = sqrt(x*x + y*y + z*z) (rm_kernels.h, option `length`)
 // the scene's specialised kernel for (accel, marcher family, length form), compiled on first use; nullptr: the interpreter serves
 const rmrtc::Kernel *specialised_kernel(rm_ctx *ctx, int accel, bool other) {
@@ -206,18 +215,9 @@ const rmrtc::Kernel *specialised_kernel(rm_ctx *ctx, int accel, bool other) {
     if (it != ctx->rtc_kernels.end()) return &it->second;
     if (ctx->rtc_failed.count(key)) return nullptr;
     rmrtc::Kernel k;
-    bool cached = false;
-    if (ctx->opt_specialise == 2) {  // never wait: the ahead-of-time kernels render until the background compile has finished
-        const int st = rmrtc::compile_async(ctx->device, ctx->rtc_src, accel, other, ctx->opt_length != 0, k, ctx->rtc_log);
-        if (st < 0) ctx->rtc_failed[key] = ctx->rtc_log;
-        if (st <= 0) return nullptr;
-        return &(ctx->rtc_kernels[key] = k);
-    }
-    if (!rmrtc::compile_cached(ctx->device, ctx->rtc_src, accel, other, ctx->opt_length != 0, k, ctx->rtc_log, &cached)) {
-        ctx->rtc_failed[key] = ctx->rtc_log;
-        return nullptr;
-    }
-    if (!cached) ctx->rtc_owned.push_back(k);  // the process-wide cache is full: this context unloads the module with the scene
+    const int st = obtain_kernel(ctx, ctx->rtc_src, accel, other, ctx->opt_length != 0, k);
+    if (st < 0) ctx->rtc_failed[key] = ctx->rtc_log;
+    if (st <= 0) return nullptr;
     return &(ctx->rtc_kernels[key] = k);
 }
 
@@ -233,19 +233,9 @@ const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur
     if (e.state == 0 && ++e.launches < ctx->opt_v2_after) return nullptr;
     // with the scene's counts as literals first; a kernel refused for spilling (small scenes: their loops unroll) once more without
     for (;;) {
-        const std::string src = rmrtc::v2_fixed_source(p, !e.lite);
-        bool failed = false;
-        if (ctx->opt_specialise == 2) {
-            const int st = rmrtc::compile_async(ctx->device, src, bits, false, length_sqrt, e.k, ctx->rtc_log);
-            e.state = st > 0 ? 1 : (st < 0 ? -1 : 2);
-            failed = st < 0;
-        } else {
-            bool cached = false;
-            failed = !rmrtc::compile_cached(ctx->device, src, bits, false, length_sqrt, e.k, ctx->rtc_log, &cached);
-            e.state = failed ? -1 : 1;
-            if (!failed && !cached) ctx->rtc_owned.push_back(e.k);
-        }
-        if (!failed || e.lite) break;
+        const int st = obtain_kernel(ctx, rmrtc::v2_fixed_source(p, !e.lite), bits, false, length_sqrt, e.k);
+        e.state = st > 0 ? 1 : (st < 0 ? -1 : 2);
+        if (st >= 0 || e.lite) break;
         e.lite = true;
         e.state = 0;
     }
@@ -254,7 +244,8 @@ const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur
 
 namespace {
 
-hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, hipStream_t stream) {
+// diag_out: the accumulator rm_render_attach_diagnostics attached to this call (render_device took it), or null
+hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *diag_out, hipStream_t stream) {
     RmRenderParams p = p_in;
 #if !defined(RM_STAMPS) && !defined(RM_COUNTS) && !defined(RM_STAMPS_LOG) && !defined(RM_STAMPS_CLAIM)  // (diagnostic builds keep their instrumented kernels)
     p.rtc_ctx = ctx;
@@ -342,10 +333,9 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, hipStream_t st
             p.lpt_perm_out = ctx->d_lpt_perm + slot * per_slot;
         }
     }
-    // Fused diagnostics (rm_render_attach_diagnostics; one-shot).  v2 launches always get an accumulator block: their last
+    // Fused diagnostics (rm_render_attach_diagnostics).  v2 launches always get an accumulator block: their last
     // wave also re-zeroes the launch's tile-queue heads.  A launch without pixels runs no kernel: neutral elements then.
-    p.diag_out = static_cast<RmDiagDevice *>(ctx->diag_next);
-    ctx->diag_next = nullptr;
+    p.diag_out = diag_out;
     p.diag_block = nullptr;
     const bool empty = p.local_rows <= 0 || p.width <= 0;
     const bool v2 = p.variant == 2 && p.algorithm == 0;
@@ -408,25 +398,10 @@ void free_device_scene(rm_ctx *ctx) {
     ctx->last_kernel = "";
     if (!ctx->has_device) return;
     DeviceScene &d = ctx->dev;
-    (void)hipFree(d.spheres);
-    (void)hipFree(d.radii);
-    (void)hipFree(d.bvh);
-    (void)hipFree(d.bvh_prims);
-    (void)hipFree(d.oct);
-    (void)hipFree(d.oct_prims);
-    (void)hipFree(d.pq_cells);
-    (void)hipFree(d.pq_list);
-    (void)hipFree(d.nn_cells);
-    (void)hipFree(d.nn_list);
-    (void)hipFree(d.prims);
-    (void)hipFree(d.prog);
-    (void)hipFree(d.obj_ranges);
-    (void)hipFree(d.oct_recs);
-    (void)hipFree(d.oct_lut);
-    (void)hipFree(d.oct_sub_hdr);
-    (void)hipFree(d.oct_sub_list);
+#define RM_X(name, always) (void)hipFree(d.name);
+    RM_SCENE_ARRAYS(RM_X)
+#undef RM_X
     (void)hipFree(d.bvh_leaves);
-    (void)hipFree(d.slot_object);
     d = DeviceScene();
 }
 
@@ -460,6 +435,34 @@ int upload_vec(rm_ctx *ctx, const std::vector<T> &v, T **out) {
     return RM_OK;
 }
 
+// Leaf table of the bundle cull (rm_render_v2.hip, bvh_prologue_cull): the node indices of the non-empty leaves, or none
+// when the cull cannot serve this tree.  The cull tests leaves directly, which equals the reference's traversal only if a
+// hit leaf implies hit ancestors: every box must lie inside its parent's, bit for bit (the builder takes unions, so it
+// does; verified here rather than assumed).
+std::vector<uint16_t> cull_leaf_table(const std::vector<RmBvhNode> &bvh) {
+    std::vector<uint16_t> leaves;
+    bool ok = !bvh.empty() && bvh.size() < 65536;
+    std::vector<int> parent(bvh.size(), -1);
+    for (size_t i = 0; ok && i < bvh.size(); ++i) {
+        if (bvh[i].leaf >= 0) continue;
+        for (size_t c = i + 1; c < static_cast<size_t>(bvh[i].skip) && c < bvh.size(); c = static_cast<size_t>(bvh[c].skip)) {
+            parent[c] = static_cast<int>(i);
+            if (bvh[c].skip <= static_cast<int>(c)) { ok = false; break; }
+        }
+    }
+    for (size_t i = 0; ok && i < bvh.size(); ++i) {
+        if (parent[i] >= 0)
+            for (int k = 0; k < 3; ++k)
+                if (!(bvh[i].lo[k] >= bvh[parent[i]].lo[k] && bvh[i].hi[k] <= bvh[parent[i]].hi[k])) ok = false;
+        for (int k = 0; k < 3; ++k)  // a negative radius gives lo > hi: the slab test then is not monotone in the box
+            if (!(bvh[i].lo[k] <= bvh[i].hi[k])) ok = false;
+        if (i > 0 && parent[i] < 0) ok = false;  // not reached through the skip links: unknown shape
+        if (bvh[i].leaf >= 0 && (bvh[i].leaf & 0xFF) > 0) leaves.push_back(static_cast<uint16_t>(i));
+    }
+    if (!ok || leaves.size() > 256) leaves.clear();
+    return leaves;
+}
+
 int upload_scene(rm_ctx *ctx) {
     // Scenes the one-ray-per-lane kernels serve and that are small enough to be code (rm_rtc.h): expression forests, and --
     // as one single-leaf object per primitive -- primitive lists (up to 32) and sphere lists of fewer than `rtc_spheres` (16)
@@ -484,102 +487,60 @@ int upload_scene(rm_ctx *ctx) {
     free_device_scene(ctx);
     ctx->scene_gen++;  // the octree frame tables of the old scene are stale
     int rc;
-    if ((rc = upload_vec(ctx, ctx->host.spheres, &ctx->dev.spheres))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.radii, &ctx->dev.radii))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.bvh, &ctx->dev.bvh))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.bvh_prims, &ctx->dev.bvh_prims))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct, &ctx->dev.oct))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct_prims, &ctx->dev.oct_prims))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.pq_cells, &ctx->dev.pq_cells))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.pq_list, &ctx->dev.pq_list))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.nn_cells, &ctx->dev.nn_cells))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.nn_list, &ctx->dev.nn_list))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.prims, &ctx->dev.prims))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.prog, &ctx->dev.prog))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.obj_ranges, &ctx->dev.obj_ranges))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct_recs, &ctx->dev.oct_recs))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct_lut, &ctx->dev.oct_lut))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct_sub_hdr, &ctx->dev.oct_sub_hdr))) return rc;
-    if ((rc = upload_vec(ctx, ctx->host.oct_sub_list, &ctx->dev.oct_sub_list))) return rc;
-    if (!ctx->host.slot_object.empty() && (rc = upload_vec(ctx, ctx->host.slot_object, &ctx->dev.slot_object))) return rc;
-    // Leaf table of the bundle cull (rm_render_v2.hip, bvh_prologue_cull).  The cull tests leaves directly, which
-    // equals the reference's traversal only if a hit leaf implies hit ancestors: every box must lie inside its
-    // parent's, bit for bit (the builder takes unions, so it does; verified here rather than assumed).
-    {
-        const auto &bvh = ctx->host.bvh;
-        std::vector<uint16_t> leaves;
-        bool ok = !bvh.empty() && bvh.size() < 65536;
-        std::vector<int> parent(bvh.size(), -1);
-        for (size_t i = 0; ok && i < bvh.size(); ++i) {
-            if (bvh[i].leaf >= 0) continue;
-            for (size_t c = i + 1; c < static_cast<size_t>(bvh[i].skip) && c < bvh.size(); c = static_cast<size_t>(bvh[c].skip)) {
-                parent[c] = static_cast<int>(i);
-                if (bvh[c].skip <= static_cast<int>(c)) { ok = false; break; }
-            }
-        }
-        for (size_t i = 0; ok && i < bvh.size(); ++i) {
-            if (parent[i] >= 0)
-                for (int k = 0; k < 3; ++k)
-                    if (!(bvh[i].lo[k] >= bvh[parent[i]].lo[k] && bvh[i].hi[k] <= bvh[parent[i]].hi[k])) ok = false;
-            for (int k = 0; k < 3; ++k)  // a negative radius gives lo > hi: the slab test then is not monotone in the box
-                if (!(bvh[i].lo[k] <= bvh[i].hi[k])) ok = false;
-            if (i > 0 && parent[i] < 0) ok = false;  // not reached through the skip links: unknown shape
-            if (bvh[i].leaf >= 0 && (bvh[i].leaf & 0xFF) > 0) leaves.push_back(static_cast<uint16_t>(i));
-        }
-        if (!ok || leaves.size() > 256) leaves.clear();
-        ctx->dev.bvh_leaf_count = static_cast<int32_t>(leaves.size());
-        if ((rc = upload_vec(ctx, leaves, &ctx->dev.bvh_leaves))) return rc;
+#define RM_X(name, always) \
+    if ((always || !ctx->host.name.empty()) && (rc = upload_vec(ctx, ctx->host.name, &ctx->dev.name))) return rc;
+    RM_SCENE_ARRAYS(RM_X)
+#undef RM_X
+    const std::vector<uint16_t> leaves = cull_leaf_table(ctx->host.bvh);
+    ctx->dev.bvh_leaf_count = static_cast<int32_t>(leaves.size());
+    return upload_vec(ctx, leaves, &ctx->dev.bvh_leaves);
+}
+
+int clamp_preset(int idx) { return idx < 0 ? 0 : (idx > rmh::kPresetCount - 1 ? rmh::kPresetCount - 1 : idx); }
+int norm_accel(int a) { return (a == RM_ACCEL_OCTREE || a == RM_ACCEL_BVH) ? a : RM_ACCEL_NONE; }
+
+int set_scene(rm_ctx *ctx, const SceneDesc &d, int accel, bool uploaded, int preset) {
+    std::string err;
+    rmh::HostScene hs;
+    rmh::set_length_mode(static_cast<int>(ctx->opt_length));
+    bool ok = false;
+    switch (d.kind) {
+        case SceneDesc::kSpheres: ok = rmh::build_scene(hs, d.centers.data(), d.radii.data(), static_cast<int>(d.radii.size()), accel, err); break;
+        case SceneDesc::kPrims: ok = rmh::build_scene_general(hs, d.prims.data(), static_cast<int>(d.prims.size()), accel, err); break;
+        case SceneDesc::kNodes:
+            ok = rmh::build_scene_nodes(hs, d.nodes.data(), static_cast<int>(d.nodes.size()), d.roots.data(), static_cast<int>(d.roots.size()), accel, err);
+            break;
     }
+    if (!ok) {
+        const bool unsupported = err.find("BVH leaf") != std::string::npos || (d.kind == SceneDesc::kNodes && err.find("RM_PROG_MAX") != std::string::npos);
+        return fail(ctx, unsupported ? RM_E_UNSUPPORTED : RM_E_INVALID, err);
+    }
+    hs.preset = preset;
+    ctx->host = std::move(hs);
+    ctx->have_scene = true;
+    ctx->scene_is_uploaded = uploaded;
+    ctx->scene_preset = preset;
+    return upload_scene(ctx);
+}
+
+// rm_scene_from_spheres / _prims / _nodes: the upload is remembered only once it has been built
+int set_uploaded_scene(rm_ctx *ctx, SceneDesc &&d, int32_t accel) {
+    const int rc = set_scene(ctx, d, norm_accel(accel), true, RM_SCENE_UPLOADED);
+    if (rc) return rc;
+    ctx->uploaded = std::move(d);
+    ctx->have_uploaded = true;
     return RM_OK;
 }
 
-int set_scene(rm_ctx *ctx, const float *centers, const double *radii, int n, int accel, bool uploaded, int preset) {
-    std::string err;
-    rmh::HostScene hs;
-    rmh::set_length_mode(static_cast<int>(ctx->opt_length));
-    if (!rmh::build_scene(hs, centers, radii, n, accel, err)) {
-        const bool unsupported = err.find("BVH leaf") != std::string::npos;
-        return fail(ctx, unsupported ? RM_E_UNSUPPORTED : RM_E_INVALID, err);
-    }
-    hs.preset = preset;
-    ctx->host = std::move(hs);
-    ctx->have_scene = true;
-    ctx->scene_is_uploaded = uploaded;
-    ctx->scene_preset = preset;
-    return upload_scene(ctx);
-}
-
-int set_scene_general(rm_ctx *ctx, const rmh::PrimDesc *prims, int n, int accel, bool uploaded, int preset) {
-    std::string err;
-    rmh::HostScene hs;
-    rmh::set_length_mode(static_cast<int>(ctx->opt_length));
-    if (!rmh::build_scene_general(hs, prims, n, accel, err)) {
-        const bool unsupported = err.find("BVH leaf") != std::string::npos;
-        return fail(ctx, unsupported ? RM_E_UNSUPPORTED : RM_E_INVALID, err);
-    }
-    hs.preset = preset;
-    ctx->host = std::move(hs);
-    ctx->have_scene = true;
-    ctx->scene_is_uploaded = uploaded;
-    ctx->scene_preset = preset;
-    return upload_scene(ctx);
-}
-
-int set_scene_nodes(rm_ctx *ctx, const rmh::NodeDesc *nodes, int n_nodes, const int *roots, int n_roots, int accel,
-                    bool uploaded, int preset) {
-    std::string err;
-    rmh::HostScene hs;
-    rmh::set_length_mode(static_cast<int>(ctx->opt_length));
-    if (!rmh::build_scene_nodes(hs, nodes, n_nodes, roots, n_roots, accel, err)) {
-        const bool unsupported = err.find("BVH leaf") != std::string::npos || err.find("RM_PROG_MAX") != std::string::npos;
-        return fail(ctx, unsupported ? RM_E_UNSUPPORTED : RM_E_INVALID, err);
-    }
-    hs.preset = preset;
-    ctx->host = std::move(hs);
-    ctx->have_scene = true;
-    ctx->scene_is_uploaded = uploaded;
-    ctx->scene_preset = preset;
-    return upload_scene(ctx);
+// a preset's objects as the builders take them: sphere presets as spheres, torus / box presets as general primitive records,
+// operator / Mandelbulb presets as expression forests
+bool preset_desc(int preset, SceneDesc &d) {
+    d.kind = SceneDesc::kSpheres;
+    if (rmh::preset_spheres(preset, d.centers, d.radii)) return true;
+    d.kind = SceneDesc::kPrims;
+    if (rmh::preset_prims(preset, d.prims)) return true;
+    d.kind = SceneDesc::kNodes;
+    return rmh::preset_nodes(preset, d.nodes, d.roots);
 }
 
 int scene_n_prims(const rm_ctx *ctx) {
@@ -587,8 +548,11 @@ int scene_n_prims(const rm_ctx *ctx) {
     return static_cast<int>(ctx->host.general ? ctx->host.prims.size() : ctx->host.spheres.size());
 }
 
-// which primitive representation the kernels read (RmRenderParams::general)
-void fill_scene_repr(const rm_ctx *ctx, RmRenderParams &p) {
+// The active scene as every kernel that evaluates it reads it (render, ray query and rm_scene_distance alike): which primitive
+// representation (RmRenderParams::general), the counts, the primitive tables and the two trees.  What only the render
+// kernels read -- grids, candidate lists, octree records -- is fill_params' business and stays null / zero elsewhere.
+void fill_scene_view(const rm_ctx *ctx, RmRenderParams &p) {
+    p.n_prims = scene_n_prims(ctx);
     p.general = ctx->host.general ? 1 : 0;
     if (ctx->host.program) {
         p.general = 2;
@@ -600,10 +564,18 @@ void fill_scene_repr(const rm_ctx *ctx, RmRenderParams &p) {
     p.obj_ranges = ctx->dev.obj_ranges;
     p.prog_slots = ctx->host.prog_slots;
     p.prog_vals = ctx->host.prog_vals;
+    p.accel = ctx->host.accel;
+    p.bvh_nodes = static_cast<int32_t>(ctx->host.bvh.size());
+    p.oct_nodes = static_cast<int32_t>(ctx->host.oct.size());
+    p.spheres = ctx->dev.spheres;
+    p.radii = ctx->dev.radii;
+    p.bvh = ctx->dev.bvh;
+    p.bvh_prims = ctx->dev.bvh_prims;
+    p.oct = ctx->dev.oct;
+    p.oct_prims = ctx->dev.oct_prims;
+    p.oct_lut = ctx->opt_lut ? ctx->dev.oct_lut : nullptr;
 }
 
-int clamp_preset(int idx) { return idx < 0 ? 0 : (idx > rmh::kPresetCount - 1 ? rmh::kPresetCount - 1 : idx); }
-int norm_accel(int a) { return (a == RM_ACCEL_OCTREE || a == RM_ACCEL_BVH) ? a : RM_ACCEL_NONE; }
 
 // makes the scene named by the job the active one (raymarchWorker.ts:37-38)
 int ensure_scene(rm_ctx *ctx, int32_t preset_index, int32_t accel_in) {
@@ -611,30 +583,13 @@ int ensure_scene(rm_ctx *ctx, int32_t preset_index, int32_t accel_in) {
     if (preset_index == RM_SCENE_UPLOADED) {
         if (!ctx->have_uploaded) return fail(ctx, RM_E_NO_SCENE, "no scene uploaded with rm_scene_from_spheres");
         if (ctx->have_scene && ctx->scene_is_uploaded && ctx->host.accel == accel) return RM_OK;
-        if (ctx->up_program)
-            return set_scene_nodes(ctx, ctx->up_nodes.data(), static_cast<int>(ctx->up_nodes.size()), ctx->up_roots.data(),
-                                   static_cast<int>(ctx->up_roots.size()), accel, true, RM_SCENE_UPLOADED);
-        if (ctx->up_general)
-            return set_scene_general(ctx, ctx->up_prims.data(), static_cast<int>(ctx->up_prims.size()), accel, true,
-                                     RM_SCENE_UPLOADED);
-        return set_scene(ctx, ctx->up_centers.data(), ctx->up_radii.data(), static_cast<int>(ctx->up_radii.size()),
-                         accel, true, RM_SCENE_UPLOADED);
+        return set_scene(ctx, ctx->uploaded, accel, true, RM_SCENE_UPLOADED);
     }
     const int preset = clamp_preset(preset_index);
     if (ctx->have_scene && !ctx->scene_is_uploaded && ctx->scene_preset == preset && ctx->host.accel == accel)
         return RM_OK;
-    std::vector<float> c;
-    std::vector<double> r;
-    if (rmh::preset_spheres(preset, c, r))
-        return set_scene(ctx, c.data(), r.data(), static_cast<int>(r.size()), accel, false, preset);
-    std::vector<rmh::PrimDesc> prims;  // torus / box presets: general primitive records
-    if (rmh::preset_prims(preset, prims))
-        return set_scene_general(ctx, prims.data(), static_cast<int>(prims.size()), accel, false, preset);
-    std::vector<rmh::NodeDesc> nodes;  // operator / Mandelbulb presets: expression programs
-    std::vector<int> roots;
-    if (rmh::preset_nodes(preset, nodes, roots))
-        return set_scene_nodes(ctx, nodes.data(), static_cast<int>(nodes.size()), roots.data(),
-                               static_cast<int>(roots.size()), accel, false, preset);
+    SceneDesc d;
+    if (preset_desc(preset, d)) return set_scene(ctx, d, accel, false, preset);
     return fail(ctx, RM_E_UNSUPPORTED, "scene preset " + std::to_string(preset) + " is not on the native path");
 }
 
@@ -682,14 +637,10 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
         p.origin_d[k] = p.origin[k];
         p.light_d[k] = p.light[k];
     }
-    p.n_prims = scene_n_prims(ctx);
-    fill_scene_repr(ctx, p);
+    fill_scene_view(ctx, p);
     if (!std::isfinite(job->time)) return fail(ctx, RM_E_INVALID, "non-finite time");
     ctx->time = job->time;  // raymarcher.ts:58-59 scene.updateTime(time)
     p.time = job->time;
-    p.accel = ctx->host.accel;
-    p.bvh_nodes = static_cast<int32_t>(ctx->host.bvh.size());
-    p.oct_nodes = static_cast<int32_t>(ctx->host.oct.size());
     p.tile_w = static_cast<int32_t>(ctx->opt_tile_w);
     p.nodes_in_lds = static_cast<int32_t>(ctx->opt_lds);
     p.filter = static_cast<int32_t>(ctx->opt_filter);
@@ -766,14 +717,7 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
         p.nn_dim[k] = ctx->host.nn_dim[k];
         p.nn_inv[k] = ctx->host.nn_inv[k];
     }
-    p.spheres = ctx->dev.spheres;
-    p.radii = ctx->dev.radii;
-    p.bvh = ctx->dev.bvh;
-    p.bvh_prims = ctx->dev.bvh_prims;
-    p.oct = ctx->dev.oct;
-    p.oct_prims = ctx->dev.oct_prims;
     p.oct_recs = ctx->opt_recs ? ctx->dev.oct_recs : nullptr;
-    p.oct_lut = ctx->opt_lut ? ctx->dev.oct_lut : nullptr;
     p.oct_sub_hdr = (ctx->opt_sub && ctx->opt_recs) ? ctx->dev.oct_sub_hdr : nullptr;
     p.oct_sub_list = ctx->dev.oct_sub_list;
     return RM_OK;
@@ -918,24 +862,85 @@ void object_forest(const rm_ctx *ctx, int index, std::vector<rm_node> &out) {
         };
         emit(root);
     };
-    if (ctx->scene_is_uploaded) {
-        if (ctx->up_program) return forest(ctx->up_nodes, ctx->up_roots[index], false);
-        if (ctx->up_general) {
-            const rmh::PrimDesc &d = ctx->up_prims[index];
-            return leaf(d.type, d.m, d.params, 3);
+    SceneDesc preset;
+    const bool as_reference = !ctx->scene_is_uploaded;
+    if (as_reference) {  // presets: as general primitive records where there are some (the sphere presets too), else as forests
+        preset.kind = SceneDesc::kPrims;
+        if (!rmh::preset_prims(ctx->scene_preset, preset.prims)) {
+            preset.kind = SceneDesc::kNodes;
+            if (!rmh::preset_nodes(ctx->scene_preset, preset.nodes, preset.roots)) return;
         }
-        return sphere(&ctx->up_centers[3 * static_cast<size_t>(index)], ctx->up_radii[index]);
     }
-    std::vector<rmh::PrimDesc> prims;  // the order ensure_scene builds presets in
-    if (rmh::preset_prims(ctx->scene_preset, prims)) {
-        rmh::PrimDesc d = prims[index];
-        if (d.type == RM_PRIM_BOX)
-            for (double &v : d.params) v = static_cast<float>(v);
-        return leaf(d.type, d.m, d.params, 3);
+    const SceneDesc &d = as_reference ? preset : ctx->uploaded;
+    switch (d.kind) {
+        case SceneDesc::kSpheres: return sphere(&d.centers[3 * static_cast<size_t>(index)], d.radii[index]);
+        case SceneDesc::kPrims: {
+            rmh::PrimDesc pd = d.prims[index];
+            if (as_reference && pd.type == RM_PRIM_BOX)
+                for (double &v : pd.params) v = static_cast<float>(v);
+            return leaf(pd.type, pd.m, pd.params, 3);
+        }
+        case SceneDesc::kNodes: return forest(d.nodes, d.roots[index], as_reference);
     }
-    std::vector<rmh::NodeDesc> nodes;
-    std::vector<int> roots;
-    if (rmh::preset_nodes(ctx->scene_preset, nodes, roots)) forest(nodes, roots[index], true);
+}
+
+// which rows of the job a render call renders: all of them, the stripes dealt round-robin to part `part` of `n_parts`
+// (packed in increasing y), or the listed stripes (packed in list order)
+struct Stripes {
+    enum Kind { kWhole, kPart, kList } kind = kWhole;
+    int32_t stripe_rows = 0, n_parts = 1, part = 0;
+    const int32_t *ids = nullptr;
+    int32_t n_ids = 0;
+};
+
+struct RenderBuffers {
+    void *depth, *normal, *sdf, *iters, *rgba;
+};
+
+// The render entry behind rm_render_tile_device, rm_render_stripes_device and rm_render_stripe_list_device.  The accumulator
+// of rm_render_attach_diagnostics is taken first, so every exit has consumed it (rm_raymarch.h: "whether it succeeds or
+// not"); it reaches the launch as an argument.  A call whose rows come to none goes the way of every launch without pixels.
+int render_device(rm_ctx *ctx, const rm_job *job, int32_t shader, const Stripes &s, const RenderBuffers &b, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    RmDiagDevice *diag = static_cast<RmDiagDevice *>(ctx->diag_next);
+    ctx->diag_next = nullptr;
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
+    int64_t mine = 0;  // rows of the stripes this call renders
+    if (s.kind != Stripes::kWhole && !job) return fail(ctx, RM_E_INVALID, "null job");
+    if (s.kind == Stripes::kPart) {
+        mine = rm_stripe_rows(job->y_start, job->y_end, s.stripe_rows, s.n_parts, s.part);
+        if (mine < 0) return fail(ctx, RM_E_INVALID, "bad stripe partition");
+    }
+    if (s.kind == Stripes::kList) {  // (refused before any scene work)
+        if (s.stripe_rows <= 0 || s.n_ids < 0 || (s.n_ids > 0 && !s.ids)) return fail(ctx, RM_E_INVALID, "bad stripe list");
+        const int64_t rows = job->y_end > job->y_start ? static_cast<int64_t>(job->y_end) - job->y_start : 0;
+        const int64_t total = (rows + s.stripe_rows - 1) / s.stripe_rows;
+        for (int k = 0; k < s.n_ids; ++k) {
+            if (s.ids[k] < 0 || s.ids[k] >= total || (k > 0 && s.ids[k] <= s.ids[k - 1]))
+                return fail(ctx, RM_E_INVALID, "stripe ids must be strictly increasing and inside the row range");
+            const int64_t a = static_cast<int64_t>(s.ids[k]) * s.stripe_rows, e = a + s.stripe_rows;
+            mine += (e < rows ? e : rows) - a;
+        }
+    }
+    RmRenderParams p;
+    int rc = fill_params(ctx, job, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (s.kind != Stripes::kWhole) {
+        p.local_rows = static_cast<int32_t>(mine);
+        p.stripe_rows = s.stripe_rows;
+        p.n_parts = s.n_parts;
+        p.part = s.part;
+    }
+    if (s.kind == Stripes::kList && mine > 0 && (rc = device_table(ctx, s.ids, static_cast<size_t>(s.n_ids), &p.stripe_ids))) return rc;
+    p.shader = norm_shader(shader);
+    p.depth = static_cast<uint8_t *>(b.depth);
+    p.normal = static_cast<uint8_t *>(b.normal);
+    p.sdf = static_cast<uint16_t *>(b.sdf);
+    p.iters = static_cast<uint16_t *>(b.iters);
+    p.rgba = static_cast<uint8_t *>(b.rgba);
+    RM_HIP(ctx, launch_render(ctx, p, diag, static_cast<hipStream_t>(stream)));
+    return RM_OK;
 }
 
 }  // namespace
@@ -1044,14 +1049,11 @@ int rm_scene_from_preset(rm_ctx *ctx, int32_t preset_index, int32_t accel) {
 int rm_scene_from_spheres(rm_ctx *ctx, const float *centers_xyz, const double *radii, int32_t n, int32_t accel) {
     if (!ctx) return RM_E_INVALID;
     if (n < 0 || (n > 0 && (!centers_xyz || !radii))) return fail(ctx, RM_E_INVALID, "bad sphere list");
-    int rc = set_scene(ctx, centers_xyz, radii, n, norm_accel(accel), true, RM_SCENE_UPLOADED);
-    if (rc) return rc;
-    ctx->up_centers.assign(centers_xyz, centers_xyz + 3 * static_cast<size_t>(n));
-    ctx->up_radii.assign(radii, radii + n);
-    ctx->up_general = false;
-    ctx->up_program = false;
-    ctx->have_uploaded = true;
-    return RM_OK;
+    SceneDesc d;
+    d.kind = SceneDesc::kSpheres;
+    if (n) d.centers.assign(centers_xyz, centers_xyz + 3 * static_cast<size_t>(n));
+    if (n) d.radii.assign(radii, radii + n);
+    return set_uploaded_scene(ctx, std::move(d), accel);
 }
 
 int rm_scene_from_nodes(rm_ctx *ctx, const rm_node *nodes, int32_t n_nodes, const int32_t *roots, int32_t n_roots,
@@ -1059,23 +1061,18 @@ int rm_scene_from_nodes(rm_ctx *ctx, const rm_node *nodes, int32_t n_nodes, cons
     if (!ctx) return RM_E_INVALID;
     if (n_nodes < 0 || n_roots < 0 || (n_nodes > 0 && !nodes) || (n_roots > 0 && !roots))
         return fail(ctx, RM_E_INVALID, "bad node list");
-    std::vector<rmh::NodeDesc> d(static_cast<size_t>(n_nodes));
+    SceneDesc d;
+    d.kind = SceneDesc::kNodes;
+    d.nodes.resize(static_cast<size_t>(n_nodes));
     for (int i = 0; i < n_nodes; ++i) {
-        d[i].type = nodes[i].type;
-        d[i].a = nodes[i].child_a;
-        d[i].b = nodes[i].child_b;
-        std::memcpy(d[i].m, nodes[i].world_to_local, sizeof d[i].m);
-        for (int k = 0; k < 6; ++k) d[i].params[k] = nodes[i].params[k];
+        d.nodes[i].type = nodes[i].type;
+        d.nodes[i].a = nodes[i].child_a;
+        d.nodes[i].b = nodes[i].child_b;
+        std::memcpy(d.nodes[i].m, nodes[i].world_to_local, sizeof d.nodes[i].m);
+        for (int k = 0; k < 6; ++k) d.nodes[i].params[k] = nodes[i].params[k];
     }
-    std::vector<int> r(roots, roots + n_roots);
-    int rc = set_scene_nodes(ctx, d.data(), n_nodes, r.data(), n_roots, norm_accel(accel), true, RM_SCENE_UPLOADED);
-    if (rc) return rc;
-    ctx->up_nodes = std::move(d);
-    ctx->up_roots = std::move(r);
-    ctx->up_program = true;
-    ctx->up_general = false;
-    ctx->have_uploaded = true;
-    return RM_OK;
+    if (n_roots) d.roots.assign(roots, roots + n_roots);
+    return set_uploaded_scene(ctx, std::move(d), accel);
 }
 
 int rm_scale_transform(float *m, double x, double y, double z) {
@@ -1094,19 +1091,15 @@ int rm_scene_set_time(rm_ctx *ctx, double time) {
 int rm_scene_from_prims(rm_ctx *ctx, const rm_prim *prims, int32_t n, int32_t accel) {
     if (!ctx) return RM_E_INVALID;
     if (n < 0 || (n > 0 && !prims)) return fail(ctx, RM_E_INVALID, "bad primitive list");
-    std::vector<rmh::PrimDesc> d(static_cast<size_t>(n));
+    SceneDesc d;
+    d.kind = SceneDesc::kPrims;
+    d.prims.resize(static_cast<size_t>(n));
     for (int i = 0; i < n; ++i) {
-        d[i].type = prims[i].type;
-        std::memcpy(d[i].m, prims[i].world_to_local, sizeof d[i].m);
-        for (int k = 0; k < 3; ++k) d[i].params[k] = prims[i].params[k];
+        d.prims[i].type = prims[i].type;
+        std::memcpy(d.prims[i].m, prims[i].world_to_local, sizeof d.prims[i].m);
+        for (int k = 0; k < 3; ++k) d.prims[i].params[k] = prims[i].params[k];
     }
-    int rc = set_scene_general(ctx, d.data(), n, norm_accel(accel), true, RM_SCENE_UPLOADED);
-    if (rc) return rc;
-    ctx->up_prims = std::move(d);
-    ctx->up_general = true;
-    ctx->up_program = false;
-    ctx->have_uploaded = true;
-    return RM_OK;
+    return set_uploaded_scene(ctx, std::move(d), accel);
 }
 
 int rm_make_transform(double x, double y, double z, const float *rotation_xyz, float *world_to_local16) {
@@ -1148,20 +1141,7 @@ int rm_camera_from_angles(double pitch, double yaw, float *rot9, float *origin3)
 
 int rm_render_tile_device(rm_ctx *ctx, const rm_job *job, int32_t shader, void *d_depth, void *d_normal, void *d_sdf,
                           void *d_iters, void *d_rgba, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
-    RmRenderParams p;
-    int rc = fill_params(ctx, job, p);
-    if (rc) return rc;
-    p.shader = norm_shader(shader);
-    p.depth = static_cast<uint8_t *>(d_depth);
-    p.normal = static_cast<uint8_t *>(d_normal);
-    p.sdf = static_cast<uint16_t *>(d_sdf);
-    p.iters = static_cast<uint16_t *>(d_iters);
-    p.rgba = static_cast<uint8_t *>(d_rgba);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, launch_render(ctx, p, static_cast<hipStream_t>(stream)));
-    return RM_OK;
+    return render_device(ctx, job, shader, Stripes(), {d_depth, d_normal, d_sdf, d_iters, d_rgba}, stream);
 }
 
 int rm_render_attach_diagnostics(rm_ctx *ctx, void *d_acc) {
@@ -1186,27 +1166,12 @@ int rm_stripe_rows(int32_t y_start, int32_t y_end, int32_t stripe_rows, int32_t 
 int rm_render_stripes_device(rm_ctx *ctx, const rm_job *job, int32_t shader, int32_t stripe_rows, int32_t n_parts,
                              int32_t part, void *d_depth, void *d_normal, void *d_sdf, void *d_iters, void *d_rgba,
                              void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
-    if (!job) return fail(ctx, RM_E_INVALID, "null job");
-    const int mine = rm_stripe_rows(job->y_start, job->y_end, stripe_rows, n_parts, part);
-    if (mine < 0) return fail(ctx, RM_E_INVALID, "bad stripe partition");
-    RmRenderParams p;
-    int rc = fill_params(ctx, job, p);
-    if (rc) return rc;
-    p.local_rows = mine;
-    p.stripe_rows = stripe_rows;
-    p.n_parts = n_parts;
-    p.part = part;
-    p.shader = norm_shader(shader);
-    p.depth = static_cast<uint8_t *>(d_depth);
-    p.normal = static_cast<uint8_t *>(d_normal);
-    p.sdf = static_cast<uint16_t *>(d_sdf);
-    p.iters = static_cast<uint16_t *>(d_iters);
-    p.rgba = static_cast<uint8_t *>(d_rgba);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, launch_render(ctx, p, static_cast<hipStream_t>(stream)));
-    return RM_OK;
+    Stripes s;
+    s.kind = Stripes::kPart;
+    s.stripe_rows = stripe_rows;
+    s.n_parts = n_parts;
+    s.part = part;
+    return render_device(ctx, job, shader, s, {d_depth, d_normal, d_sdf, d_iters, d_rgba}, stream);
 }
 
 int rm_deal_stripes(int32_t rows, int32_t stripe_rows, int32_t n_parts, const int32_t *weights, int32_t *owner) {
@@ -1236,37 +1201,12 @@ int rm_deal_stripes(int32_t rows, int32_t stripe_rows, int32_t n_parts, const in
 int rm_render_stripe_list_device(rm_ctx *ctx, const rm_job *job, int32_t shader, int32_t stripe_rows, const int32_t *stripe_ids,
                                  int32_t n_stripes, void *d_depth, void *d_normal, void *d_sdf, void *d_iters, void *d_rgba,
                                  void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
-    if (!job) return fail(ctx, RM_E_INVALID, "null job");
-    if (stripe_rows <= 0 || n_stripes < 0 || (n_stripes > 0 && !stripe_ids)) return fail(ctx, RM_E_INVALID, "bad stripe list");
-    const int64_t rows = job->y_end > job->y_start ? static_cast<int64_t>(job->y_end) - job->y_start : 0;
-    const int64_t total = (rows + stripe_rows - 1) / stripe_rows;
-    int64_t mine = 0;
-    for (int k = 0; k < n_stripes; ++k) {
-        if (stripe_ids[k] < 0 || stripe_ids[k] >= total || (k > 0 && stripe_ids[k] <= stripe_ids[k - 1]))
-            return fail(ctx, RM_E_INVALID, "stripe ids must be strictly increasing and inside the row range");
-        const int64_t a = static_cast<int64_t>(stripe_ids[k]) * stripe_rows, b = a + stripe_rows;
-        mine += (b < rows ? b : rows) - a;
-    }
-    RmRenderParams p;
-    int rc = fill_params(ctx, job, p);
-    if (rc) return rc;
-    if (mine == 0) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if ((rc = device_table(ctx, stripe_ids, static_cast<size_t>(n_stripes), &p.stripe_ids))) return rc;
-    p.local_rows = static_cast<int32_t>(mine);
-    p.stripe_rows = stripe_rows;
-    p.n_parts = 1;
-    p.part = 0;
-    p.shader = norm_shader(shader);
-    p.depth = static_cast<uint8_t *>(d_depth);
-    p.normal = static_cast<uint8_t *>(d_normal);
-    p.sdf = static_cast<uint16_t *>(d_sdf);
-    p.iters = static_cast<uint16_t *>(d_iters);
-    p.rgba = static_cast<uint8_t *>(d_rgba);
-    RM_HIP(ctx, launch_render(ctx, p, static_cast<hipStream_t>(stream)));
-    return RM_OK;
+    Stripes s;
+    s.kind = Stripes::kList;
+    s.stripe_rows = stripe_rows;
+    s.ids = stripe_ids;
+    s.n_ids = n_stripes;
+    return render_device(ctx, job, shader, s, {d_depth, d_normal, d_sdf, d_iters, d_rgba}, stream);
 }
 
 int rm_assemble_frame_device(rm_ctx *ctx, const void *d_gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
@@ -1437,21 +1377,10 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
     char *base = static_cast<char *>(ctx->scratch);
     RmRenderParams p;
     std::memset(&p, 0, sizeof p);
-    p.n_prims = scene_n_prims(ctx);
-    fill_scene_repr(ctx, p);
+    fill_scene_view(ctx, p);
     p.time = ctx->time;
-    p.accel = ctx->host.accel;
-    p.bvh_nodes = static_cast<int32_t>(ctx->host.bvh.size());
-    p.oct_nodes = static_cast<int32_t>(ctx->host.oct.size());
     p.filter = static_cast<int32_t>(ctx->opt_filter);
     p.tile_w = 8;
-    p.spheres = ctx->dev.spheres;
-    p.radii = ctx->dev.radii;
-    p.bvh = ctx->dev.bvh;
-    p.bvh_prims = ctx->dev.bvh_prims;
-    p.oct = ctx->dev.oct;
-    p.oct_prims = ctx->dev.oct_prims;
-    p.oct_lut = ctx->opt_lut ? ctx->dev.oct_lut : nullptr;
     {
         const rmrtc::Kernel *special = specialised_kernel(ctx, p.accel, false);
         p.rtc_function = special ? special->distance : nullptr;
@@ -1702,199 +1631,91 @@ int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32) {
     return RM_OK;
 }
 
+// Every option once: its key, its member of rm_ctx (the defaults and what they were measured against are there; fill_params
+// reads the members), the values it takes and what rm_last_error says of any other.
+enum OptionKind {
+    kSwitch,       // 0 | 1: any non-zero value is 1
+    kRange,        // v[0] .. v[1], inclusive
+    kZeroOrRange,  // 0, or v[0] .. v[1]
+    kSet,          // one of v[0 .. 3] (shorter sets repeat their last member)
+};
+struct OptionRow {
+    const char *key;
+    int64_t rm_ctx::*member;
+    OptionKind kind;
+    int64_t v[4];
+    const char *error;
+};
+static const OptionRow kOptions[] = {
+    {"tile_w", &rm_ctx::opt_tile_w, kSet, {8, 16, 32, 64}, "tile_w must be 8, 16, 32 or 64"},
+    {"filter", &rm_ctx::opt_filter, kSwitch, {}, nullptr},
+    {"nodes_in_lds", &rm_ctx::opt_lds, kSwitch, {}, nullptr},
+    {"kernel", &rm_ctx::opt_kernel, kRange, {0, 2}, "kernel must be 0 (auto), 1 or 2"},
+    {"list_cap", &rm_ctx::opt_list_cap, kRange, {1, 64}, "list_cap must be in [1, 64]"},
+    {"coop", &rm_ctx::opt_coop, kSwitch, {}, nullptr},
+    {"recs", &rm_ctx::opt_recs, kSwitch, {}, nullptr},
+    {"lut", &rm_ctx::opt_lut, kSwitch, {}, nullptr},
+    {"uniform", &rm_ctx::opt_uniform, kSwitch, {}, nullptr},
+    {"lds_kb", &rm_ctx::opt_lds_kb, kZeroOrRange, {16, 64}, "lds_kb must be 0 (auto) or in [16, 64]"},
+    {"multi_step", &rm_ctx::opt_multi_step, kSwitch, {}, nullptr},
+    {"item_wide", &rm_ctx::opt_item_wide, kSwitch, {}, nullptr},
+    {"prune", &rm_ctx::opt_prune, kSwitch, {}, nullptr},
+    {"rtc_spheres", &rm_ctx::opt_rtc_spheres, kRange, {0, 33}, "rtc_spheres must be 0..33"},
+    {"specialise_v2_after", &rm_ctx::opt_v2_after, kRange, {0, 1000000}, "specialise_v2_after must be 0 (never) .. 1000000 launches"},
+    {"specialise", &rm_ctx::opt_specialise, kRange, {0, 2}, "specialise must be 0, 1 or 2"},
+    {"lds_fill", &rm_ctx::opt_lds_fill, kSwitch, {}, nullptr},
+    {"cull", &rm_ctx::opt_cull, kSwitch, {}, nullptr},
+    {"rel", &rm_ctx::opt_rel, kSwitch, {}, nullptr},
+    {"static", &rm_ctx::opt_static, kRange, {0, 95}, "static must be in [0, 95] percent"},  // stored, ignored (rm_ctx)
+    {"sub", &rm_ctx::opt_sub, kSwitch, {}, nullptr},
+    {"refill", &rm_ctx::opt_refill, kRange, {1, 64}, "refill must be in [1, 64]"},
+    {"item_px", &rm_ctx::opt_item_px, kSet, {64, 128, 256, 256}, "item_px must be 64, 128 or 256"},
+    {"hw_xcd", &rm_ctx::opt_hw_xcd, kSwitch, {}, nullptr},
+    {"grid", &rm_ctx::opt_grid, kSwitch, {}, nullptr},
+    {"nn", &rm_ctx::opt_nn, kRange, {0, 2}, "nn must be 0 (off), 1 (on) or 2 (auto)"},
+    {"blocks_per_cu", &rm_ctx::opt_blocks_per_cu, kRange, {1, 8}, "blocks_per_cu must be in [1, 8]"},
+    {"v1_lists", &rm_ctx::opt_v1_lists, kSwitch, {}, nullptr},
+    {"v1_block", &rm_ctx::opt_v1_block, kSet, {64, 128, 256, 256}, "v1_block must be 64, 128 or 256"},
+    {"oct_lean", &rm_ctx::opt_oct_lean, kSwitch, {}, nullptr},
+    {"lpt", &rm_ctx::opt_lpt, kSwitch, {}, nullptr},
+    {"n0_batch", &rm_ctx::opt_n0_batch, kRange, {1, 64}, "n0_batch must be in [1, 64]"},
+    {"length", &rm_ctx::opt_length, kRange, {0, 1}, "length must be 0 (Math.hypot) or 1 (Math.sqrt)"},  // part of the numeric contract, not a measurement knob (rm_raymarch.h)
+};
+
+static const OptionRow *find_option(const char *key) {
+    for (const OptionRow &o : kOptions)
+        if (!std::strcmp(key, o.key)) return &o;
+    return nullptr;
+}
+
 int rm_set_option(rm_ctx *ctx, const char *key, int64_t value) {
     if (!ctx || !key) return RM_E_INVALID;
-    if (!std::strcmp(key, "tile_w")) {
-        if (value != 8 && value != 16 && value != 32 && value != 64) return fail(ctx, RM_E_INVALID, "tile_w must be 8, 16, 32 or 64");
-        ctx->opt_tile_w = value;
-        ctx->tile_w_set = true;
-        return RM_OK;
+    const OptionRow *o = find_option(key);
+    if (!o) return fail(ctx, RM_E_INVALID, std::string("unknown option ") + key);
+    bool ok = true;
+    switch (o->kind) {
+        case kSwitch: value = value ? 1 : 0; break;
+        case kRange: ok = value >= o->v[0] && value <= o->v[1]; break;
+        case kZeroOrRange: ok = value == 0 || (value >= o->v[0] && value <= o->v[1]); break;
+        case kSet: ok = std::find(std::begin(o->v), std::end(o->v), value) != std::end(o->v); break;
     }
-    if (!std::strcmp(key, "filter")) {
-        ctx->opt_filter = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "nodes_in_lds")) {
-        ctx->opt_lds = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "kernel")) {
-        if (value < 0 || value > 2) return fail(ctx, RM_E_INVALID, "kernel must be 0 (auto), 1 or 2");
-        ctx->opt_kernel = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "list_cap")) {
-        if (value < 1 || value > 64) return fail(ctx, RM_E_INVALID, "list_cap must be in [1, 64]");
-        ctx->opt_list_cap = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "coop")) {
-        ctx->opt_coop = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "recs")) {
-        ctx->opt_recs = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "lut")) {
-        ctx->opt_lut = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "uniform")) {
-        ctx->opt_uniform = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "lds_kb")) {
-        if (value != 0 && (value < 16 || value > 64)) return fail(ctx, RM_E_INVALID, "lds_kb must be 0 (auto) or in [16, 64]");
-        ctx->opt_lds_kb = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "multi_step")) {
-        ctx->opt_multi_step = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "item_wide")) {
-        ctx->opt_item_wide = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "prune")) {
-        ctx->opt_prune = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "rtc_spheres")) {
-        if (value < 0 || value > 33) return fail(ctx, RM_E_INVALID, "rtc_spheres must be 0..33");
-        ctx->opt_rtc_spheres = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "specialise_v2_after")) {
-        if (value < 0 || value > 1000000) return fail(ctx, RM_E_INVALID, "specialise_v2_after must be 0 (never) .. 1000000 launches");
-        ctx->opt_v2_after = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "specialise")) {
-        if (value < 0 || value > 2) return fail(ctx, RM_E_INVALID, "specialise must be 0, 1 or 2");
-        ctx->opt_specialise = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "lds_fill")) {
-        ctx->opt_lds_fill = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "cull")) {
-        ctx->opt_cull = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "rel")) {
-        ctx->opt_rel = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "static")) {
-        if (value < 0 || value > 95) return fail(ctx, RM_E_INVALID, "static must be in [0, 95] percent");
-        ctx->opt_static = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "sub")) {
-        ctx->opt_sub = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "refill")) {
-        if (value < 1 || value > 64) return fail(ctx, RM_E_INVALID, "refill must be in [1, 64]");
-        ctx->opt_refill = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "item_px")) {
-        if (value != 64 && value != 128 && value != 256) return fail(ctx, RM_E_INVALID, "item_px must be 64, 128 or 256");
-        ctx->opt_item_px = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "hw_xcd")) {
-        ctx->opt_hw_xcd = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "grid")) {
-        ctx->opt_grid = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "nn")) {
-        if (value < 0 || value > 2) return fail(ctx, RM_E_INVALID, "nn must be 0 (off), 1 (on) or 2 (auto)");
-        ctx->opt_nn = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "blocks_per_cu")) {
-        if (value < 1 || value > 8) return fail(ctx, RM_E_INVALID, "blocks_per_cu must be in [1, 8]");
-        ctx->opt_blocks_per_cu = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "v1_lists")) {
-        ctx->opt_v1_lists = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "v1_block")) {
-        if (value != 64 && value != 128 && value != 256) return fail(ctx, RM_E_INVALID, "v1_block must be 64, 128 or 256");
-        ctx->opt_v1_block = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "oct_lean")) {
-        ctx->opt_oct_lean = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "lpt")) {
-        ctx->opt_lpt = value ? 1 : 0;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "n0_batch")) {
-        if (value < 1 || value > 64) return fail(ctx, RM_E_INVALID, "n0_batch must be in [1, 64]");
-        ctx->opt_n0_batch = value;
-        return RM_OK;
-    }
-    if (!std::strcmp(key, "length")) {  // part of the numeric contract, not a measurement knob (rm_raymarch.h)
-        if (value != 0 && value != 1) return fail(ctx, RM_E_INVALID, "length must be 0 (Math.hypot) or 1 (Math.sqrt)");
-        if (ctx->opt_length == value) return RM_OK;
-        ctx->opt_length = value;
-        if (!ctx->have_scene) return RM_OK;
+    if (!ok) return fail(ctx, RM_E_INVALID, o->error);
+    const bool changed = ctx->*(o->member) != value;
+    ctx->*(o->member) = value;
+    if (o->member == &rm_ctx::opt_tile_w) ctx->tile_w_set = true;
+    if (o->member == &rm_ctx::opt_length && changed && ctx->have_scene) {
         // bounding radii of boxes and smooth unions use vec3.length / vec3.distance too: rebuild the active scene
         ctx->have_scene = false;
         return ensure_scene(ctx, ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset, ctx->host.accel);
     }
-    return fail(ctx, RM_E_INVALID, std::string("unknown option ") + key);
+    return RM_OK;
 }
 
 int rm_get_option(const rm_ctx *ctx, const char *key, int64_t *value) {
     if (!ctx || !key || !value) return RM_E_INVALID;
-    if (!std::strcmp(key, "tile_w")) *value = ctx->opt_tile_w;
-    else if (!std::strcmp(key, "filter")) *value = ctx->opt_filter;
-    else if (!std::strcmp(key, "nodes_in_lds")) *value = ctx->opt_lds;
-    else if (!std::strcmp(key, "kernel")) *value = ctx->opt_kernel;
-    else if (!std::strcmp(key, "list_cap")) *value = ctx->opt_list_cap;
-    else if (!std::strcmp(key, "coop")) *value = ctx->opt_coop;
-    else if (!std::strcmp(key, "grid")) *value = ctx->opt_grid;
-    else if (!std::strcmp(key, "nn")) *value = ctx->opt_nn;
-    else if (!std::strcmp(key, "refill")) *value = ctx->opt_refill;
-    else if (!std::strcmp(key, "recs")) *value = ctx->opt_recs;
-    else if (!std::strcmp(key, "lut")) *value = ctx->opt_lut;
-    else if (!std::strcmp(key, "sub")) *value = ctx->opt_sub;
-    else if (!std::strcmp(key, "static")) *value = ctx->opt_static;
-    else if (!std::strcmp(key, "uniform")) *value = ctx->opt_uniform;
-    else if (!std::strcmp(key, "rel")) *value = ctx->opt_rel;
-    else if (!std::strcmp(key, "cull")) *value = ctx->opt_cull;
-    else if (!std::strcmp(key, "lds_kb")) *value = ctx->opt_lds_kb;
-    else if (!std::strcmp(key, "lds_fill")) *value = ctx->opt_lds_fill;
-    else if (!std::strcmp(key, "specialise")) *value = ctx->opt_specialise;
-    else if (!std::strcmp(key, "specialise_v2_after")) *value = ctx->opt_v2_after;
-    else if (!std::strcmp(key, "rtc_spheres")) *value = ctx->opt_rtc_spheres;
-    else if (!std::strcmp(key, "prune")) *value = ctx->opt_prune;
-    else if (!std::strcmp(key, "item_wide")) *value = ctx->opt_item_wide;
-    else if (!std::strcmp(key, "multi_step")) *value = ctx->opt_multi_step;
-    else if (!std::strcmp(key, "hw_xcd")) *value = ctx->opt_hw_xcd;
-    else if (!std::strcmp(key, "item_px")) *value = ctx->opt_item_px;
-    else if (!std::strcmp(key, "blocks_per_cu")) *value = ctx->opt_blocks_per_cu;
-    else if (!std::strcmp(key, "length")) *value = ctx->opt_length;
-    else if (!std::strcmp(key, "n0_batch")) *value = ctx->opt_n0_batch;
-    else if (!std::strcmp(key, "lpt")) *value = ctx->opt_lpt;
-    else if (!std::strcmp(key, "v1_lists")) *value = ctx->opt_v1_lists;
-    else if (!std::strcmp(key, "oct_lean")) *value = ctx->opt_oct_lean;
-    else if (!std::strcmp(key, "v1_block")) *value = ctx->opt_v1_block;
-    else return RM_E_INVALID;
+    const OptionRow *o = find_option(key);
+    if (!o) return RM_E_INVALID;
+    *value = ctx->*(o->member);
     return RM_OK;
 }
 

@@ -702,6 +702,23 @@ bool compile_any(const std::string &src, int accel, bool other, bool length_sqrt
     if (accel & kV2Bit) return compile_v2(src, accel & 3, (accel >> 2) & 1, (accel >> 3) & 1, (accel >> 4) & 1, length_sqrt, true, out, log);
     return compile(src, accel, other, length_sqrt, true, out, log);
 }
+// What the cache knows of `key` (the caller holds c.mu): 1 = the kernel (out, and its compile's log), -1 = that its compile
+// failed or was refused (that log: the same source gives the same answer, so it is not compiled again), 0 = nothing.
+int lookup(Cache &c, const std::string &key, Kernel &out, std::string &log) {
+    auto it = c.done.find(key);
+    if (it != c.done.end()) {
+        out = it->second;
+        out.compile_seconds = 0;
+        log = out.log;
+        return 1;
+    }
+    auto f = c.failed.find(key);
+    if (f != c.failed.end()) {
+        log = f->second;
+        return -1;
+    }
+    return 0;
+}
 }  // namespace
 
 bool compile_cached(int device, const std::string &scene_src, int accel, bool other, bool length_sqrt, Kernel &out, std::string &log, bool *cached) {
@@ -709,18 +726,10 @@ bool compile_cached(int device, const std::string &scene_src, int accel, bool ot
     const std::string key = cache_key(device, scene_src, accel, other, length_sqrt);
     std::lock_guard<std::mutex> lock(c.mu);  // (a compile in the background of the same key finishes first: it holds no lock while compiling,
                                              //  so this call may compile a second copy; the first one stored wins)
-    auto it = c.done.find(key);
-    if (it != c.done.end()) {
-        out = it->second;
-        out.compile_seconds = 0;
-        log = out.log;
-        if (cached) *cached = true;
-        return true;
-    }
-    auto f = c.failed.find(key);  // (a refused key or a compile error is not compiled again: the same source gives the same answer)
-    if (f != c.failed.end()) {
-        log = f->second;
-        return false;
+    // (this lock is held across the compile below; that, the duplicate module and a compile at process exit: ADVICE.md, low)
+    if (const int known = lookup(c, key, out, log)) {
+        if (cached) *cached = known > 0;
+        return known > 0;
     }
     if (!compile_any(scene_src, accel, other, length_sqrt, out, log)) {
         // (out.name is set once the compile and the spill rule are passed: a module that then fails to LOAD is tried again)
@@ -738,18 +747,7 @@ int compile_async(int device, const std::string &scene_src, int accel, bool othe
     const std::string key = cache_key(device, scene_src, accel, other, length_sqrt);
     {
         std::lock_guard<std::mutex> lock(c.mu);
-        auto it = c.done.find(key);
-        if (it != c.done.end()) {
-            out = it->second;
-            out.compile_seconds = 0;
-            log = out.log;
-            return 1;
-        }
-        auto f = c.failed.find(key);
-        if (f != c.failed.end()) {
-            log = f->second;
-            return -1;
-        }
+        if (const int known = lookup(c, key, out, log)) return known;
         if (c.running.count(key)) return 0;
         if (c.done.size() >= static_cast<size_t>(kCacheEntries)) {
             log = "the kernel cache is full";

@@ -601,6 +601,96 @@ def test_fused_diagnostics_of_stripes_and_frames_in_flight(rm, oracle):
     ctx.close()
 
 
+def _diag_frame_case(rm, preset, accel):
+    """A context, scene and job for the 64 x 16 frame of the two tests below: one 64-pixel batch wide, two 8 x 8 tiles high
+    (smaller, the v2 wave loop and the one-ray-per-lane kernels stop being distinguishable launches)."""
+    from cpu_raymarcher_amd import host
+    ctx = rm.Context(0)
+    ctx.set_option("specialise_v2_after", 0)  # (these tests repeat one configuration: no compile for it on the way)
+    sc = rm.Scene(accel, ctx=ctx)
+    sc.loadPreset(preset)
+    sc.camera.setAngles(0.2, 0.5)
+    return ctx, host._job(sc, 64, 16, 0.0, 0, 16, "sphere-tracer", None, None)
+
+
+def _diag_frame_render(ctx, job, dev):
+    import torch
+    bufs = [torch.zeros(64 * 16 * b, dtype=torch.uint8, device=dev) for b in (1, 3, 2, 2, 4)]  # depth, normal, sdf, iters, rgba
+    ctx.render_tile(job, *bufs[:4], rgba=bufs[4], shader=2)
+    torch.cuda.synchronize()
+    return [b.cpu().numpy() for b in bufs]
+
+
+@pytest.mark.parametrize("preset,accel,kernel", [(3, "BVH", "render_kernel_v2"), (3, "Octree", "render_kernel_oct")])
+def test_a_failed_render_consumes_the_attached_accumulator(rm, preset, accel, kernel):
+    """rm_render_attach_diagnostics is "consumed by the next render call whether it succeeds or not": a render entry that
+    refuses its arguments on the host (before any launch) must not leave the accumulator attached for the next, unrelated
+    render, which would write 32 bytes to memory the caller may have freed.  Every failing call below is followed by a
+    successful render without diagnostics: the accumulator keeps its sentinel and the frame equals a fresh context's."""
+    import ctypes as C
+    import copy
+    import torch
+    from cpu_raymarcher_amd import _native as N
+    from cpu_raymarcher_amd.context import _ptr, _current_stream_ptr
+    dev = torch.device("cuda:0")
+    fresh, job = _diag_frame_case(rm, preset, accel)
+    want = _diag_frame_render(fresh, job, dev)
+    assert kernel in fresh.last_kernel(), fresh.last_kernel()  # the wave loop, and a one-ray-per-lane kernel on the octree
+    fresh.close()
+    assert want[2].any() and want[4].any()
+    ctx, job = _diag_frame_case(rm, preset, accel)
+    d, nr, s16, i16 = [torch.zeros(64 * 16 * b, dtype=torch.uint8, device=dev) for b in (1, 3, 2, 2)]
+
+    def no_rows():
+        j = copy.copy(job)
+        j.height = 0
+        ctx.render_tile(j, d, nr, s16, i16, diag=acc)
+
+    def yaw_not_finite():
+        j = copy.copy(job)
+        j.camera_yaw = float("inf")
+        ctx.render_tile(j, d, nr, s16, i16, diag=acc)
+
+    def part_outside_the_partition():  # straight to the C entry: Context.render_stripes checks the partition itself
+        ctx._attach_diag(acc)
+        N.check(ctx._h, N.lib().rm_render_stripes_device(ctx._h, C.byref(job), 0, 8, 2, 2, _ptr(d), _ptr(nr), _ptr(s16), _ptr(i16), None,
+                                                        _current_stream_ptr()))
+
+    def descending_stripe_ids():
+        ctx.render_stripe_list(job, 8, [1, 0], d, nr, s16, i16, diag=acc)
+
+    sentinel = 0x5A5A5A5A5A5A5A5A
+    for failing in (no_rows, yaw_not_finite, part_outside_the_partition, descending_stripe_ids):
+        acc = torch.full((4,), sentinel, dtype=torch.int64, device=dev)
+        with pytest.raises(rm.RmError) as e:
+            failing()
+        assert e.value.code == N.RM_E_INVALID, failing.__name__
+        got = _diag_frame_render(ctx, job, dev)
+        assert acc.cpu().tolist() == [sentinel] * 4, "%s left the accumulator attached: %s" % (failing.__name__, ctx.decode_acc(acc))
+        for name, g, w in zip(NAMES + ("rgba",), got, want):
+            assert np.array_equal(g, w), (failing.__name__, name)
+    ctx.close()
+
+
+def test_a_stripe_list_without_rows_writes_the_neutral_elements(rm):
+    """A stripe list that names no stripe (a rank that was dealt none) renders no pixel: like the other render entries it
+    then writes the neutral elements to an attached accumulator (sums 0, max 0, min UINT32_MAX), runs no kernel, and
+    has consumed the accumulator."""
+    import torch
+    dev = torch.device("cuda:0")
+    ctx, job = _diag_frame_case(rm, 3, "BVH")
+    one = [torch.zeros(4, dtype=torch.uint8, device=dev) for _ in range(4)]
+    acc = torch.full((4,), -1, dtype=torch.int64, device=dev)
+    ctx.render_stripe_list(job, 8, [], *one, diag=acc)
+    torch.cuda.synchronize()
+    neutral = {"total_sdf": 0, "total_iters": 0, "max_sdf": 0, "min_sdf": 0xFFFFFFFF}
+    assert ctx.decode_acc(acc) == neutral
+    assert all(not b.any() for b in one)
+    _diag_frame_render(ctx, job, dev)
+    assert ctx.decode_acc(acc) == neutral
+    ctx.close()
+
+
 def test_empty_scene_and_bad_inputs(rm, gpu_ctx, oracle):
     empty = np.zeros((0, 4))
     for accel in ("None", "BVH", "Octree"):

@@ -171,3 +171,158 @@ def test_synthetic_scene_definitions_agree_with_the_oracles_copy(rm, oracle):
     want = oracle.OracleScene(accel="None", prims=oracle.synthetic_mixed_prims(12)).prims()
     for (t, m, par), (wt, wm, wpar) in zip(triples, want):
         assert t == wt and np.array_equal(m, wm) and list(par) == list(wpar[:len(par)])
+
+
+def _switch(default):  # 0 | 1: any non-zero value is 1
+    return dict(default=default, accepted=[(0, 0), (1, 1), (7, 1), (-1, 1), (0, 0)], rejected=[])
+
+
+def _range(default, lo, hi):  # inclusive range
+    return dict(default=default, accepted=[(lo, lo), (hi, hi), ((lo + hi) // 2, (lo + hi) // 2)], rejected=[lo - 1, hi + 1, -(1 << 40), 1 << 40])
+
+
+def _set(default, values, between):  # a short explicit value set
+    return dict(default=default, accepted=[(v, v) for v in values], rejected=[min(values) - 1, max(values) + 1, 0, -min(values)] + between)
+
+
+# one row per key of include/rm_raymarch.h's option list: default, (probe, value stored) pairs, rejected probes
+OPTION_CONTRACT = {
+    "tile_w": _set(8, [8, 16, 32, 64], [12, 24, 48]),
+    "filter": _switch(1),
+    "nodes_in_lds": _switch(1),
+    "kernel": _range(0, 0, 2),
+    "list_cap": _range(32, 1, 64),
+    "coop": _switch(1),
+    "grid": _switch(1),
+    "nn": _range(2, 0, 2),
+    "recs": _switch(1),
+    "lut": _switch(1),
+    "sub": _switch(1),
+    "blocks_per_cu": _range(6, 1, 8),
+    "refill": _range(64, 1, 64),
+    "hw_xcd": _switch(1),
+    "item_px": _set(128, [64, 128, 256], [96, 192]),
+    "static": _range(0, 0, 95),  # accepted, stored, ignored
+    "uniform": _switch(1),
+    "rel": _switch(1),
+    "cull": _switch(1),
+    "lds_kb": dict(default=0, accepted=[(16, 16), (64, 64), (32, 32), (0, 0), (40, 40)], rejected=[-1, 1, 8, 15, 65, 1 << 40]),  # 0 or a range
+    "n0_batch": _range(64, 1, 64),
+    "lpt": _switch(1),
+    "multi_step": _switch(1),
+    "lds_fill": _switch(0),
+    "item_wide": _switch(0),
+    "specialise": _range(1, 0, 2),
+    "specialise_v2_after": _range(3, 0, 1000000),
+    "rtc_spheres": _range(16, 0, 33),
+    "prune": _switch(1),
+    "v1_lists": _switch(1),
+    "v1_block": _set(64, [64, 128, 256], [96, 192]),
+    "oct_lean": _switch(1),
+    "length": dict(default=0, accepted=[(1, 1), (0, 0)], rejected=[-1, 2, 7]),  # strictly 0 or 1: part of the numeric contract
+}
+
+
+def test_every_option_keeps_its_contract(rm):
+    """Every key of rm_set_option / rm_get_option (include/rm_raymarch.h lists 33): its default, the values it takes and
+    how they are stored, the values it refuses -- those just outside every range and between the members of every set --
+    which leave the stored value alone and an error text behind; unknown keys fail both ways."""
+    from cpu_raymarcher_amd import _native as N
+    assert len(OPTION_CONTRACT) == 33
+    ctx = rm.Context(None)
+    last = {key: row["default"] for key, row in OPTION_CONTRACT.items()}
+    assert {key: ctx.get_option(key) for key in OPTION_CONTRACT} == last
+    for key, row in OPTION_CONTRACT.items():
+        for probe, stored in row["accepted"]:
+            ctx.set_option(key, probe)
+            assert ctx.get_option(key) == stored, (key, probe)
+            for bad in row["rejected"]:
+                with pytest.raises(rm.RmError) as e:
+                    ctx.set_option(key, bad)
+                assert e.value.code == N.RM_E_INVALID, (key, bad)
+                assert N.lib().rm_last_error(ctx._h).decode() != "", (key, bad)
+                assert ctx.get_option(key) == stored, (key, bad)
+        last[key] = row["accepted"][-1][1]
+        assert {k: ctx.get_option(k) for k in OPTION_CONTRACT} == last, key  # no key writes another's value
+    for key in ("", "no_such_option", "tile_w ", "Tile_w", "opt_tile_w"):
+        with pytest.raises(rm.RmError):
+            ctx.set_option(key, 1)
+        with pytest.raises(rm.RmError):
+            ctx.get_option(key)
+    ctx.close()
+    # `length` rebuilds the active scene (no device needed): with no scene, with a preset, after a sphere upload
+    ctx = rm.Context(None)
+    for scene in (None, "preset", "spheres"):
+        if scene == "preset":
+            ctx.scene_from_preset(9, 2)
+        elif scene == "spheres":
+            ctx.scene_from_spheres(np.float32([[0, 0, 0], [1, 0.5, 0], [0, 1, 0.25]]), [0.5, 0.25, 0.125], 1)
+        before = ctx.scene_info() if scene else None
+        for v in (1, 1, 0, 0):
+            ctx.set_option("length", v)
+            assert ctx.get_option("length") == v
+            if scene:
+                assert ctx.scene_info() == before, (scene, v)  # same scene, same structure: the two forms differ by an ulp
+                assert len(ctx.scene_object(0)) == 1
+    ctx.close()
+
+
+def test_uploads_of_every_kind_replace_one_another(rm):
+    """rm_scene_from_spheres / _prims / _nodes keep one description of the upload: each call replaces the one before,
+    whatever its kind (rm_scene_object reads it back), a refused upload replaces nothing, and the remembered upload is
+    what a rebuild builds from (the `length` option rebuilds the active scene)."""
+    ctx = rm.Context(None)
+    ident = np.eye(4, dtype=np.float32).ravel()
+    centers, radii = np.float32([[0.5, 0, 0], [0, 0.25, 0], [0, 0, -0.75]]), [0.5, 0.25, 0.125]
+    box = rm.make_transform(0.25, -0.5, 0.125, [0.1, 0.2, 0.3])
+    prims = [(1, box, [0.5, 0.25, 0.125]), (2, ident, [0.5, 0.125])]
+    nodes = [(0, -1, -1, rm.make_transform(0.25, 0, 0), [0.5]), (1, -1, -1, ident, [0.25, 0.5, 0.125]), (11, 0, 1, None, [0.0625])]
+
+    def sphere_0(c, r):
+        (t, a, b, m, par), = ctx.scene_object(0)
+        assert (t, a, b) == (0, -1, -1) and np.array_equal(m, rm.make_transform(*[float(v) for v in c])) and par[0] == r
+
+    def prim_0():
+        (t, a, b, m, par), = ctx.scene_object(0)
+        assert (t, a, b) == (1, -1, -1) and np.array_equal(m, box) and list(par[:3]) == [0.5, 0.25, 0.125]
+
+    def forest_0():
+        got = ctx.scene_object(0)
+        assert [(t, a, b) for t, a, b, _, _ in got] == [(0, -1, -1), (1, -1, -1), (11, 0, 1)]
+        assert np.array_equal(got[0][3], nodes[0][3]) and got[0][4][0] == 0.5 and got[2][4][0] == 0.0625
+
+    def rebuilt(check):  # the active scene built again from the remembered upload
+        for v in (1, 0):
+            ctx.set_option("length", v)
+            check()
+
+    ctx.scene_from_spheres(centers, radii, 2)
+    assert ctx.scene_info()["n_prims"] == 3
+    sphere_0(centers[0], 0.5)
+    ctx.scene_from_prims(prims, 2)
+    assert ctx.scene_info()["n_prims"] == 2
+    prim_0()
+    rebuilt(prim_0)
+    ctx.scene_from_nodes(nodes, [2], 1)
+    assert ctx.scene_info()["n_prims"] == 1 and ctx.scene_info()["prog_instructions"] > 0
+    forest_0()
+    # refused uploads of every kind: the forest stays the active scene and the remembered upload
+    with pytest.raises(rm.RmError):
+        ctx.scene_from_spheres(np.float32([[0, float("nan"), 0]]), [1.0], 1)
+    with pytest.raises(rm.RmError):
+        ctx.scene_from_prims([(7, ident, [0.5])], 1)
+    with pytest.raises(rm.RmError):
+        ctx.scene_from_nodes([(42, -1, -1, ident, [0.5])], [0], 1)
+    assert ctx.scene_info()["n_prims"] == 1
+    forest_0()
+    rebuilt(forest_0)
+    assert ctx.scene_info()["prog_instructions"] > 0
+    ctx.scene_from_spheres(centers[1:], radii[1:], 0)
+    assert ctx.scene_info()["n_prims"] == 2 and ctx.scene_info()["prog_instructions"] == 0
+    sphere_0(centers[1], 0.25)
+    rebuilt(lambda: sphere_0(centers[1], 0.25))
+    ctx.scene_from_preset(3, 2)  # a preset in between does not forget the upload ...
+    assert ctx.scene_info()["n_prims"] > 2 and len(ctx.scene_object(0)) == 1
+    ctx.scene_from_prims(prims, 0)
+    prim_0()
+    ctx.close()
