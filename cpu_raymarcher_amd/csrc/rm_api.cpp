@@ -54,6 +54,178 @@ struct SceneDesc {
     std::vector<int> roots;            // ... and its objects
 };
 
+// The three rings of launch_render.  Per-launch control slots: the 64 queue heads of a v2 launch, 256 bytes apart (rm_render_v2.hip RM_QUEUES, RM_QSTRIDE), and the
+// accumulator block of the fused diagnostics (rm_diag.h).  Zeroed once, in init; every launch's last wave leaves its slots
+// zeroed.  A launch owns what it took until kLaunches - 1 later launches have taken theirs (frames in flight on several streams).
+struct LaunchSlots {
+    static constexpr unsigned kLaunches = 1024, kHeads = 64, kHeadWords = 64;
+    unsigned int *heads = nullptr;  // [kLaunches][kHeads][kHeadWords]
+    RmDiagBlock *blocks = nullptr;  // [kLaunches]
+    unsigned int head_slot = 0, block_slot = 0;
+
+    hipError_t init() {
+        const size_t head_bytes = sizeof(unsigned int) * kLaunches * kHeads * kHeadWords, block_bytes = sizeof(RmDiagBlock) * kLaunches;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&heads), head_bytes);
+        if (e == hipSuccess) e = hipMemset(heads, 0, head_bytes);
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&blocks), block_bytes);
+        return e == hipSuccess ? hipMemset(blocks, 0, block_bytes) : e;
+    }
+    void release() {
+        (void)hipFree(heads);
+        (void)hipFree(blocks);
+    }
+    unsigned int *take_heads() { return heads ? heads + static_cast<size_t>(kHeads) * kHeadWords * (head_slot++ % kLaunches) : nullptr; }
+    RmDiagBlock *take_block() { return blocks ? blocks + block_slot++ % kLaunches : nullptr; }
+};
+
+// The LPT ring (option `lpt`; rm_render_v2.hip, lpt_sort_kernel): a v2 launch sorts its items longest-first from the costs the
+// previous launch recorded, into a permutation of its own, and records its own costs; one slot per launch in flight.
+//  - The buffers are allocated at the first acquire; both exist or neither does (launches then keep their queues' order).
+//  - The costs are per item of THIS tiling of THIS row set: cost_prev is given only when the previous launch had the same
+//    geometry key; any change restarts the feedback (costs read as zero).
+//  - A slot is reused once the launch that owned it is over: acquire waits for the event launched() recorded (16 launches ago).
+//  - acquire advances the launch counter whether or not the launch then succeeds.
+struct LptRing {
+    static constexpr int kSlots = 16;
+    static constexpr int kQueues = 64;    // rm_render_v2.hip RM_QUEUES
+    static constexpr int kStride = 4096;  // items per queue; larger frames render without LPT
+    static constexpr size_t kPerSlot = static_cast<size_t>(kQueues) * kStride;
+    uint8_t *cost = nullptr;   // [kSlots][kPerSlot]
+    uint16_t *perm = nullptr;  // [kSlots][kPerSlot]
+    unsigned int launches = 0;
+    long long geometry = -1;
+    hipEvent_t done[kSlots] = {};
+
+    unsigned last() const { return (launches + kSlots - 1) % kSlots; }  // the slot the last launch took
+    const uint8_t *last_costs() const { return cost && launches ? cost + last() * kPerSlot : nullptr; }  // rm_debug_read_lpt_costs
+
+    // the launch geometry of p -> p.lpt_cost_prev, lpt_cost_out, lpt_perm_out, lpt_stride (left null / zero without buffers)
+    void acquire(RmRenderParams &p) {
+        if (!cost && (hipMalloc(reinterpret_cast<void **>(&cost), kSlots * kPerSlot) != hipSuccess ||
+                      hipMalloc(reinterpret_cast<void **>(&perm), kSlots * kPerSlot * sizeof(uint16_t)) != hipSuccess)) {
+            (void)hipFree(cost);
+            cost = nullptr;
+            perm = nullptr;
+        }
+        if (!cost) return;
+        const long long geom = ((static_cast<long long>(p.width) * 65536 + p.local_rows) * 1024 + p.tile_w) * 1024 + p.item_px + (p.item_wide ? 512 : 0) +
+                               (p.stripe_rows ? (1ll << 62) + p.part * 131 + p.n_parts : 0) + p.y_start * 7919ll;
+        const unsigned slot = launches % kSlots, prev = last();
+        const bool have_prev = launches > 0 && geom == geometry;
+        geometry = geom;
+        launches++;
+        if (done[slot]) (void)hipEventSynchronize(done[slot]);
+        p.lpt_stride = kStride;
+        p.lpt_cost_prev = have_prev ? cost + prev * kPerSlot : nullptr;
+        p.lpt_cost_out = cost + slot * kPerSlot;
+        p.lpt_perm_out = perm + slot * kPerSlot;
+    }
+    void launched(hipStream_t stream) {  // behind a launch that succeeded with the slot of acquire
+        hipEvent_t &ev = done[last()];
+        if (!ev) (void)hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+        if (ev) (void)hipEventRecord(ev, stream);
+    }
+    void release() {
+        (void)hipFree(cost);
+        (void)hipFree(perm);
+        for (hipEvent_t ev : done)
+            if (ev) (void)hipEventDestroy(ev);
+    }
+};
+
+// The octree camera-table ring (render_kernel_oct): the octree relative to a camera position (RmOctFrameNode), one table per
+// position, shared by every launch with that position (frames in flight with one camera build it once) and rewritten only
+// when the ring comes round.
+//  - acquire tries the current table first, then all kSlots.  A table matches when it is valid, of this scene generation,
+//    and its three origin doubles are equal.
+//  - A table found may still be under construction on the stream that first saw the position: a launch on another stream
+//    that has not read it before (one that has is ordered behind the builder already) waits for the `built` event; without
+//    an event, or if the wait fails, it synchronises the builder's stream.  (the `users` events only made the
+//    next WRITER wait for the readers, never a reader for the writer.)
+//  - A new position takes slot next++ % kSlots: every reader event of the slot is waited for and destroyed and `users`
+//    cleared (it lists the readers of THIS table).  The memory is reallocated only when the node count grew.  The table is
+//    built on the launch's stream with `built` recorded right behind it; failing that the stream is synchronised.
+//  - A failed allocation or table launch yields null: the launcher then takes render_kernel<1, false, 0>.
+//  - read_by, behind the render launch whether or not it succeeded, records the stream's reader event: whoever rewrites the
+//    table waits for this launch.  No event to be had: the stream is synchronised.
+struct OctTableRing {
+    struct Table {
+        double origin[3] = {0, 0, 0};
+        unsigned long long gen = 0;
+        bool valid = false;
+        RmOctFrameNode *dev = nullptr;
+        size_t nodes = 0;
+        std::vector<std::pair<hipStream_t, hipEvent_t>> users;
+        hipStream_t builder = nullptr;  // the stream oct_frame_table_kernel ran on
+        hipEvent_t built = nullptr;
+    };
+    static constexpr int kSlots = 32;
+    Table slots[kSlots];
+    unsigned next = 0;
+    int cur = -1;
+
+    Table *acquire(unsigned long long gen, const RmOctNode *oct, int32_t oct_nodes, const double origin[3], hipStream_t stream) {
+        auto matches = [&](const Table &t) {
+            return t.valid && t.gen == gen && t.origin[0] == origin[0] && t.origin[1] == origin[1] && t.origin[2] == origin[2];
+        };
+        Table *found = cur >= 0 && matches(slots[cur]) ? &slots[cur] : nullptr;
+        for (int k = 0; !found && k < kSlots; ++k)
+            if (matches(slots[k])) {
+                found = &slots[k];
+                cur = k;
+            }
+        if (found) {
+            bool seen = found->builder == stream;
+            for (auto &u : found->users) seen = seen || u.first == stream;
+            if (!seen && (!found->built || hipStreamWaitEvent(stream, found->built, 0) != hipSuccess)) (void)hipStreamSynchronize(found->builder);
+            return found;
+        }
+        const int k = static_cast<int>(next++ % kSlots);
+        Table &t = slots[k];
+        for (auto &u : t.users) {
+            (void)hipEventSynchronize(u.second);
+            (void)hipEventDestroy(u.second);
+        }
+        t.users.clear();
+        t.valid = false;
+        const size_t n = static_cast<size_t>(oct_nodes);
+        if (t.nodes < n) {
+            (void)hipFree(t.dev);
+            t.dev = nullptr;
+            t.nodes = 0;
+            if (hipMalloc(reinterpret_cast<void **>(&t.dev), n * sizeof(RmOctFrameNode)) == hipSuccess) t.nodes = n;
+            else (void)hipGetLastError();
+        }
+        if (!t.dev || rm_launch_oct_frame_table(oct, oct_nodes, origin, t.dev, stream) != hipSuccess) return nullptr;
+        for (int a = 0; a < 3; ++a) t.origin[a] = origin[a];
+        t.gen = gen;
+        t.valid = true;
+        t.builder = stream;
+        if (!t.built && hipEventCreateWithFlags(&t.built, hipEventDisableTiming) != hipSuccess) t.built = nullptr;
+        if (!t.built || hipEventRecord(t.built, stream) != hipSuccess) (void)hipStreamSynchronize(stream);
+        cur = k;
+        return &t;
+    }
+    static void read_by(Table &t, hipStream_t stream) {
+        hipEvent_t ev = nullptr;
+        for (auto &u : t.users)
+            if (u.first == stream) ev = u.second;
+        if (!ev) {
+            if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess) t.users.emplace_back(stream, ev);
+            else ev = nullptr;
+        }
+        if (ev) (void)hipEventRecord(ev, stream);
+        else (void)hipStreamSynchronize(stream);
+    }
+    void release() {
+        for (Table &t : slots) {
+            (void)hipFree(t.dev);
+            for (auto &u : t.users) (void)hipEventDestroy(u.second);
+            if (t.built) (void)hipEventDestroy(t.built);
+        }
+    }
+};
+
 }  // namespace
 
 struct rm_ctx {
@@ -105,33 +277,9 @@ struct rm_ctx {
     int64_t opt_v1_block = 64;  // v1 kernels: threads per workgroup (one wave: wave slots refill one by one)
     int64_t opt_oct_lean = 1;  // octree, sphere scenes, sphere tracer: render_kernel_oct (rm_kernels.hip) instead of render_kernel<1, false, 0>
     int64_t opt_lpt = 1;  // v2: longest-first item order from the previous frame's item durations (shortens the tail of a frame that runs alone: 1.13 -> 1.08 ms)
-    // LPT buffers: a ring of slots, one per launch in flight (a launch sorts from the previous launch's costs into its own
-    // permutation and records its own costs); geometry changes restart the feedback
-    static constexpr int kLptSlots = 16;
-    static constexpr int kLptQueues = 64;     // rm_render_v2.hip RM_QUEUES
-    static constexpr int kLptStride = 4096;   // items per queue; larger frames render without LPT
-    uint8_t *d_lpt_cost = nullptr;    // [kLptSlots][kLptQueues * kLptStride]
-    uint16_t *d_lpt_perm = nullptr;   // [kLptSlots][kLptQueues * kLptStride]
-    unsigned int lpt_launch = 0;
-    long long lpt_geometry = -1;
-    hipEvent_t lpt_done[16] = {};  // recorded after the launch that owns the slot: a slot is reused only once that launch is over
-    // render_kernel_oct: the octree relative to a camera position (RmOctFrameNode), one table per position in a ring.  A table is
-    // shared by every launch with that position (frames in flight with one camera build it once) and rewritten only when the
-    // ring comes round, after every launch that read it has finished (one event per stream that used it).
-    struct OctFrameSlot {
-        double origin[3] = {0, 0, 0};
-        unsigned long long gen = 0;
-        bool valid = false;
-        RmOctFrameNode *dev = nullptr;
-        size_t nodes = 0;
-        std::vector<std::pair<hipStream_t, hipEvent_t>> users;
-        hipStream_t builder = nullptr;  // the stream oct_frame_table_kernel ran on ...
-        hipEvent_t built = nullptr;     // ... and the event recorded right behind it: a launch on ANY OTHER stream waits for it
-    };
-    static constexpr int kOctFrameSlots = 32;
-    OctFrameSlot oct_frames[kOctFrameSlots];
-    unsigned oct_frame_next = 0;
-    int oct_frame_cur = -1;
+    LaunchSlots slots;        // the three rings of launch_render (above)
+    LptRing lpt;
+    OctTableRing oct_tables;
     unsigned long long scene_gen = 0;  // bumped by every upload_scene
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
@@ -171,15 +319,7 @@ struct rm_ctx {
     };
     std::vector<DevTable> tables;
     int64_t opt_item_px = 128;  // two 64-pixel batches per queue claim: 7-10 % faster than 64 at the end of round 1, 256 loses
-    unsigned int *d_counters = nullptr;  // ring of 1024 x 64 queue heads, 256 bytes apart (rm_render_v2.hip RM_QSTRIDE): a launch owns its slot until 1023 later launches
-                                         // have been enqueued (frames in flight on several streams each need their own)
-    unsigned int counter_slot = 0;
-    // Fused diagnostics (rm_diag.h): a ring of accumulator blocks, one per launch in flight like the queue heads above;
-    // zeroed once here, left zeroed by every launch's last wave.  diag_next: rm_render_attach_diagnostics, one-shot.
-    static constexpr unsigned kDiagBlocks = 1024;
-    RmDiagBlock *d_diag_blocks = nullptr;
-    unsigned int diag_slot = 0;
-    void *diag_next = nullptr;
+    void *diag_next = nullptr;  // rm_render_attach_diagnostics, one-shot
     unsigned long long *d_stamps = nullptr;  // diagnostic build only
     int num_cus = 256;
 };
@@ -250,95 +390,19 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
 #if !defined(RM_STAMPS) && !defined(RM_COUNTS) && !defined(RM_STAMPS_LOG) && !defined(RM_STAMPS_CLAIM)  // (diagnostic builds keep their instrumented kernels)
     p.rtc_ctx = ctx;
 #endif
+    const bool empty = p.local_rows <= 0 || p.width <= 0;  // a launch without pixels runs no kernel
+    const bool v2 = p.variant == 2 && p.algorithm == 0;
     // every launch of the one-ray-per-lane kernels (not the v2 wave loop, not the lean octree kernel) takes the scene's own kernel if it has one
     const bool lean_oct = p.accel == 1 && p.oct_lean && !p.general && p.algorithm == 0 && p.oct_lut && p.oct_recs && p.filter;
-    const rmrtc::Kernel *special = (p.variant == 2 && p.algorithm == 0) || lean_oct ? nullptr : specialised_kernel(ctx, p.accel, p.algorithm != 0);
+    const rmrtc::Kernel *special = v2 || lean_oct ? nullptr : specialised_kernel(ctx, p.accel, p.algorithm != 0);
     p.rtc_function = special ? special->render : nullptr;
-    rm_ctx::OctFrameSlot *oct_slot = nullptr;
-    if (lean_oct) {
-        const size_t n = static_cast<size_t>(p.oct_nodes);
-        auto matches = [&](const rm_ctx::OctFrameSlot &sl) {
-            return sl.valid && sl.gen == ctx->scene_gen && sl.origin[0] == p.origin_d[0] && sl.origin[1] == p.origin_d[1] && sl.origin[2] == p.origin_d[2];
-        };
-        if (ctx->oct_frame_cur >= 0 && matches(ctx->oct_frames[ctx->oct_frame_cur])) oct_slot = &ctx->oct_frames[ctx->oct_frame_cur];
-        for (int k = 0; !oct_slot && k < rm_ctx::kOctFrameSlots; ++k)
-            if (matches(ctx->oct_frames[k])) {
-                oct_slot = &ctx->oct_frames[k];
-                ctx->oct_frame_cur = k;
-            }
-        // A table found here may still be under construction on the stream that first saw this camera position (frames
-        // in flight share one table): a reader on another stream orders itself behind the builder (the `users`
-        // events only made the next WRITER wait for the readers, never a reader for the writer).
-        bool seen = false;  // a stream that has read this table before is already ordered behind the builder
-        if (oct_slot)
-            for (auto &u : oct_slot->users) seen = seen || u.first == stream;
-        if (oct_slot && oct_slot->builder != stream && !seen) {
-            if (oct_slot->built) {
-                if (hipStreamWaitEvent(stream, oct_slot->built, 0) != hipSuccess) (void)hipStreamSynchronize(oct_slot->builder);
-            } else {
-                (void)hipStreamSynchronize(oct_slot->builder);  // no event could be created when it was built
-            }
-        }
-        if (!oct_slot) {  // a new camera position: the oldest table is rewritten once its readers are done
-            const int k = static_cast<int>(ctx->oct_frame_next++ % rm_ctx::kOctFrameSlots);
-            rm_ctx::OctFrameSlot &sl = ctx->oct_frames[k];
-            for (auto &u : sl.users) {
-                (void)hipEventSynchronize(u.second);
-                (void)hipEventDestroy(u.second);
-            }
-            sl.users.clear();  // `seen` above is about THIS table, not the one the slot held before
-            sl.valid = false;
-            if (sl.nodes < n) {
-                (void)hipFree(sl.dev);
-                sl.dev = nullptr;
-                sl.nodes = 0;
-                if (hipMalloc(reinterpret_cast<void **>(&sl.dev), n * sizeof(RmOctFrameNode)) == hipSuccess) sl.nodes = n;
-                else (void)hipGetLastError();
-            }
-            if (sl.dev && rm_launch_oct_frame_table(p.oct, p.oct_nodes, p.origin_d, sl.dev, stream) == hipSuccess) {
-                for (int a = 0; a < 3; ++a) sl.origin[a] = p.origin_d[a];
-                sl.gen = ctx->scene_gen;
-                sl.valid = true;
-                sl.builder = stream;
-                if (!sl.built && hipEventCreateWithFlags(&sl.built, hipEventDisableTiming) != hipSuccess) sl.built = nullptr;
-                if (!sl.built || hipEventRecord(sl.built, stream) != hipSuccess) (void)hipStreamSynchronize(stream);  // built before anyone else can look
-                oct_slot = &sl;
-                ctx->oct_frame_cur = k;
-            }
-        }
-        p.oct_frame = oct_slot ? oct_slot->dev : nullptr;  // null: the launcher takes render_kernel<1, false, 0>
-    }
-    if (ctx->opt_lpt && p.variant == 2 && p.algorithm == 0) {  // longest-first item order (rm_render_v2.hip, lpt_sort_kernel)
-        const size_t per_slot = static_cast<size_t>(rm_ctx::kLptQueues) * rm_ctx::kLptStride;
-        if (!ctx->d_lpt_cost) {
-            if (hipMalloc(reinterpret_cast<void **>(&ctx->d_lpt_cost), rm_ctx::kLptSlots * per_slot) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void **>(&ctx->d_lpt_perm), rm_ctx::kLptSlots * per_slot * sizeof(uint16_t)) != hipSuccess) {
-                (void)hipFree(ctx->d_lpt_cost);
-                ctx->d_lpt_cost = nullptr;
-                ctx->d_lpt_perm = nullptr;
-            }
-        }
-        if (ctx->d_lpt_cost) {
-            // the costs are per item of THIS tiling of THIS row set: any change restarts the feedback (costs read as zero)
-            const long long geom = ((static_cast<long long>(p.width) * 65536 + p.local_rows) * 1024 + p.tile_w) * 1024 + p.item_px + (p.item_wide ? 512 : 0) +
-                                   (p.stripe_rows ? (1ll << 62) + p.part * 131 + p.n_parts : 0) + p.y_start * 7919ll;
-            const unsigned slot = ctx->lpt_launch % rm_ctx::kLptSlots, prev = (ctx->lpt_launch + rm_ctx::kLptSlots - 1) % rm_ctx::kLptSlots;
-            const bool have_prev = ctx->lpt_launch > 0 && geom == ctx->lpt_geometry;
-            ctx->lpt_geometry = geom;
-            ctx->lpt_launch++;
-            if (ctx->lpt_done[slot]) (void)hipEventSynchronize(ctx->lpt_done[slot]);  // 16 launches ago: normally long finished
-            p.lpt_stride = rm_ctx::kLptStride;
-            p.lpt_cost_prev = have_prev ? ctx->d_lpt_cost + prev * per_slot : nullptr;
-            p.lpt_cost_out = ctx->d_lpt_cost + slot * per_slot;
-            p.lpt_perm_out = ctx->d_lpt_perm + slot * per_slot;
-        }
-    }
+    OctTableRing::Table *oct_table = lean_oct ? ctx->oct_tables.acquire(ctx->scene_gen, p.oct, p.oct_nodes, p.origin_d, stream) : nullptr;
+    p.oct_frame = oct_table ? oct_table->dev : nullptr;  // null: the launcher takes render_kernel<1, false, 0>
+    if (ctx->opt_lpt && v2) ctx->lpt.acquire(p);  // longest-first item order
+    if (v2 && !empty) p.tile_counters = ctx->slots.take_heads();
     // Fused diagnostics (rm_render_attach_diagnostics).  v2 launches always get an accumulator block: their last
-    // wave also re-zeroes the launch's tile-queue heads.  A launch without pixels runs no kernel: neutral elements then.
+    // wave also re-zeroes the launch's queue heads.  A launch without pixels writes the neutral elements.
     p.diag_out = diag_out;
-    p.diag_block = nullptr;
-    const bool empty = p.local_rows <= 0 || p.width <= 0;
-    const bool v2 = p.variant == 2 && p.algorithm == 0;
     // The one-ray-per-lane kernels run one-wave workgroups: 129 600 waves per 4K frame, each of which would end with five
     // device-scope atomics and a wait for four of them.  Measured (round 3, frames in flight): Pyramid of Boxes 1 348 frames/s
     // with that epilogue against 1 561 with the two reduction launches over the stored counters, C5 493 against 512.  So
@@ -349,8 +413,7 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
         reduce_after = p.diag_out;
         p.diag_out = nullptr;
     }
-    if (!empty && ctx->d_diag_blocks && (p.diag_out || v2))
-        p.diag_block = ctx->d_diag_blocks + (ctx->diag_slot++ % rm_ctx::kDiagBlocks);
+    p.diag_block = !empty && (p.diag_out || v2) ? ctx->slots.take_block() : nullptr;
     if (p.diag_out && empty) {
         const hipError_t ei = rm_launch_reduce_init(p.diag_out, stream);
         if (ei != hipSuccess) return ei;
@@ -361,25 +424,8 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
         e = rm_launch_reduce_init(reduce_after, stream);
         if (e == hipSuccess) e = rm_launch_reduce(p.sdf, p.iters, static_cast<int64_t>(p.local_rows) * p.width, reduce_after, stream);
     }
-    if (oct_slot) {  // this stream now reads the table: whoever rewrites it waits for this launch
-        hipEvent_t *ev = nullptr;
-        for (auto &u : oct_slot->users)
-            if (u.first == stream) ev = &u.second;
-        if (!ev) {
-            hipEvent_t fresh = nullptr;
-            if (hipEventCreateWithFlags(&fresh, hipEventDisableTiming) == hipSuccess) {
-                oct_slot->users.emplace_back(stream, fresh);
-                ev = &oct_slot->users.back().second;
-            }
-        }
-        if (ev) (void)hipEventRecord(*ev, stream);
-        else (void)hipStreamSynchronize(stream);  // no event to be had: the table must not outlive its reader unseen
-    }
-    if (e == hipSuccess && p.lpt_perm_out) {
-        const unsigned slot = (ctx->lpt_launch + rm_ctx::kLptSlots - 1) % rm_ctx::kLptSlots;
-        if (!ctx->lpt_done[slot]) (void)hipEventCreateWithFlags(&ctx->lpt_done[slot], hipEventDisableTiming);
-        if (ctx->lpt_done[slot]) (void)hipEventRecord(ctx->lpt_done[slot], stream);
-    }
+    if (oct_table) OctTableRing::read_by(*oct_table, stream);
+    if (e == hipSuccess && p.lpt_perm_out) ctx->lpt.launched(stream);
     return e;
 }
 
@@ -387,6 +433,15 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
     do {                                                        \
         hipError_t e_ = (call);                                 \
         if (e_ != hipSuccess) return hip_fail(ctx, e_, #call); \
+    } while (0)
+
+// The preamble of an entry that needs a device: a null context is RM_E_INVALID (there is no context to leave a text in), a
+// host-only one RM_E_NO_DEVICE with `text`.  hipSetDevice is not part of it: in all but the rm_debug_read_* entries argument
+// checks stand between the two, and the order of checks is behaviour.
+#define RM_NEED_DEVICE(ctx, text)                                             \
+    do {                                                                      \
+        if (!(ctx)) return RM_E_INVALID;                                      \
+        if (!(ctx)->has_device) return fail(ctx, RM_E_NO_DEVICE, text);       \
     } while (0)
 
 void free_device_scene(rm_ctx *ctx) {
@@ -593,20 +648,40 @@ int ensure_scene(rm_ctx *ctx, int32_t preset_index, int32_t accel_in) {
     return fail(ctx, RM_E_UNSUPPORTED, "scene preset " + std::to_string(preset) + " is not on the native path");
 }
 
-int ensure_scratch(rm_ctx *ctx, size_t bytes) {
-    if (bytes <= ctx->scratch_bytes) return RM_OK;
-    if (ctx->scratch) {
-        RM_HIP(ctx, hipDeviceSynchronize());
-        (void)hipFree(ctx->scratch);
-        ctx->scratch = nullptr;
-        ctx->scratch_bytes = 0;
-    }
-    RM_HIP(ctx, hipMalloc(&ctx->scratch, bytes));
-    ctx->scratch_bytes = bytes;
-    return RM_OK;
-}
-
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// Staging of one call's host buffers through the context's scratch buffer, on the context's stream.  region() lays the
+// regions out in the order they are named, each 256-byte aligned, and returns their offsets; reserve() grows the scratch
+// once to hold them all (it never shrinks, and the device is synchronised before an old buffer is freed) and asks for 256
+// bytes at least, so at() is a device pointer even when every region is empty.  in / zero / out are enqueued.
+struct Staging {
+    rm_ctx *ctx;
+    size_t total = 0;
+    size_t region(size_t bytes) {
+        const size_t offset = total;
+        total += align_up(bytes, 256);
+        return offset;
+    }
+    int reserve() const {
+        const size_t bytes = total ? total : 256;
+        if (bytes <= ctx->scratch_bytes) return RM_OK;
+        if (ctx->scratch) {
+            RM_HIP(ctx, hipDeviceSynchronize());
+            (void)hipFree(ctx->scratch);
+            ctx->scratch = nullptr;
+            ctx->scratch_bytes = 0;
+        }
+        RM_HIP(ctx, hipMalloc(&ctx->scratch, bytes));
+        ctx->scratch_bytes = bytes;
+        return RM_OK;
+    }
+    template <typename T>
+    T *at(size_t offset) const { return reinterpret_cast<T *>(static_cast<char *>(ctx->scratch) + offset); }
+    hipError_t in(size_t offset, const void *host, size_t bytes) const { return hipMemcpyAsync(at<char>(offset), host, bytes, hipMemcpyHostToDevice, ctx->stream); }
+    hipError_t zero(size_t offset, size_t bytes) const { return hipMemsetAsync(at<char>(offset), 0, bytes, ctx->stream); }
+    hipError_t out(void *host, size_t offset, size_t bytes) const { return hipMemcpyAsync(host, at<char>(offset), bytes, hipMemcpyDeviceToHost, ctx->stream); }
+    hipError_t sync() const { return hipStreamSynchronize(ctx->stream); }
+};
 
 int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     if (!job) return fail(ctx, RM_E_INVALID, "null job");
@@ -668,7 +743,6 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.refill_threshold = static_cast<int32_t>(ctx->opt_refill);
     p.hw_xcd = static_cast<int32_t>(ctx->opt_hw_xcd);
     p.item_px = static_cast<int32_t>(ctx->opt_item_px);
-    p.tile_counters = ctx->d_counters ? ctx->d_counters + 64 * 64 * (ctx->counter_slot++ % 1024) : nullptr;
     p.stamps = ctx->d_stamps;
     for (int k = 0; k < 3; ++k) {
         p.pq_dim[k] = ctx->host.pq_dim[k];
@@ -720,6 +794,23 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.oct_recs = ctx->opt_recs ? ctx->dev.oct_recs : nullptr;
     p.oct_sub_hdr = (ctx->opt_sub && ctx->opt_recs) ? ctx->dev.oct_sub_hdr : nullptr;
     p.oct_sub_list = ctx->dev.oct_sub_list;
+    return RM_OK;
+}
+
+// rm_selftest_fastdiv and rm_selftest_recip: a kernel counts mismatches into one zeroed word of the scratch, read back alone
+template <typename Launch>
+int read_mismatches(rm_ctx *ctx, Launch launch, uint64_t *mismatches) {
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const size_t o = st.region(sizeof(unsigned long long));
+    const int rc = st.reserve();
+    if (rc) return rc;
+    RM_HIP(ctx, st.zero(o, sizeof(unsigned long long)));
+    RM_HIP(ctx, launch(st.at<unsigned long long>(o)));
+    unsigned long long h = 0;
+    RM_HIP(ctx, st.out(&h, o, sizeof h));
+    RM_HIP(ctx, st.sync());
+    *mismatches = h;
     return RM_OK;
 }
 
@@ -791,29 +882,25 @@ int ray_query_host(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, con
     // through the scratch buffer in chunks of at most 4 M rays (52 B per ray: 208 MB; a pick's objects 4 B more: 224 MB), whatever the batch
     const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
     const size_t c = static_cast<size_t>(chunk);
-    const size_t o_dirs = align_up(12 * c, 256), o_t = o_dirs + align_up(12 * c, 256), o_it = o_t + align_up(8 * c, 256),
-                 o_sdf = o_it + align_up(4 * c, 256), o_nrm = o_sdf + align_up(4 * c, 256), o_obj = o_nrm + align_up(12 * c, 256),
-                 total = o_obj + (pick ? align_up(4 * c, 256) : 0);
-    rc = ensure_scratch(ctx, total);
-    if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
+    Staging st{ctx};
+    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_t = st.region(8 * c), o_it = st.region(4 * c), o_sdf = st.region(4 * c),
+                 o_nrm = st.region(12 * c), o_obj = st.region(pick ? 4 * c : 0);
+    if ((rc = st.reserve())) return rc;
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
         const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, hipMemcpyAsync(base, origins_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(base + o_dirs, dirs_xyz + 3 * at, 12 * k, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
+        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
         RM_HIP(ctx, (ctx->opt_length ? rm_launch_query_sqrt : rm_launch_query)(
-                        p, pick, reinterpret_cast<const float *>(base), reinterpret_cast<const float *>(base + o_dirs), m, q->normal != 0,
-                        ctx->dev.slot_object, t ? reinterpret_cast<double *>(base + o_t) : nullptr,
-                        iters ? reinterpret_cast<uint32_t *>(base + o_it) : nullptr, sdf_calls ? reinterpret_cast<uint32_t *>(base + o_sdf) : nullptr,
-                        normal_xyz ? reinterpret_cast<float *>(base + o_nrm) : nullptr, object ? reinterpret_cast<int32_t *>(base + o_obj) : nullptr,
-                        ctx->stream, &ctx->last_kernel));
-        if (t) RM_HIP(ctx, hipMemcpyAsync(t + at, base + o_t, 8 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (iters) RM_HIP(ctx, hipMemcpyAsync(iters + at, base + o_it, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (sdf_calls) RM_HIP(ctx, hipMemcpyAsync(sdf_calls + at, base + o_sdf, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (normal_xyz) RM_HIP(ctx, hipMemcpyAsync(normal_xyz + 3 * at, base + o_nrm, 12 * k, hipMemcpyDeviceToHost, ctx->stream));
-        if (object) RM_HIP(ctx, hipMemcpyAsync(object + at, base + o_obj, 4 * k, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipStreamSynchronize(ctx->stream));  // the next chunk reuses the scratch
+                        p, pick, st.at<const float>(o_org), st.at<const float>(o_dirs), m, q->normal != 0, ctx->dev.slot_object,
+                        t ? st.at<double>(o_t) : nullptr, iters ? st.at<uint32_t>(o_it) : nullptr, sdf_calls ? st.at<uint32_t>(o_sdf) : nullptr,
+                        normal_xyz ? st.at<float>(o_nrm) : nullptr, object ? st.at<int32_t>(o_obj) : nullptr, ctx->stream, &ctx->last_kernel));
+        if (t) RM_HIP(ctx, st.out(t + at, o_t, 8 * k));
+        if (iters) RM_HIP(ctx, st.out(iters + at, o_it, 4 * k));
+        if (sdf_calls) RM_HIP(ctx, st.out(sdf_calls + at, o_sdf, 4 * k));
+        if (normal_xyz) RM_HIP(ctx, st.out(normal_xyz + 3 * at, o_nrm, 12 * k));
+        if (object) RM_HIP(ctx, st.out(object + at, o_obj, 4 * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
     }
     return RM_OK;
 }
@@ -965,10 +1052,7 @@ int rm_create(int device, rm_ctx **out) {
         e = hipSetDevice(device);
         if (e == hipSuccess) e = hipStreamCreate(&ctx->stream);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->d_diag), sizeof(RmDiagDevice));
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->d_counters), 1024 * 64 * 64 * sizeof(unsigned int));
-        if (e == hipSuccess) e = hipMemset(ctx->d_counters, 0, 1024 * 64 * 64 * sizeof(unsigned int));  // every launch leaves its heads zeroed (rm_diag.h)
-        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->d_diag_blocks), rm_ctx::kDiagBlocks * sizeof(RmDiagBlock));
-        if (e == hipSuccess) e = hipMemset(ctx->d_diag_blocks, 0, rm_ctx::kDiagBlocks * sizeof(RmDiagBlock));
+        if (e == hipSuccess) e = ctx->slots.init();
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&ctx->d_stamps), (40 + 3 * 8192 + 2048 * 48) * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMemset(ctx->d_stamps, 0, (40 + 3 * 8192 + 2048 * 48) * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMemset(ctx->d_stamps + 6, 0xFF, sizeof(unsigned long long));
@@ -994,19 +1078,11 @@ void rm_destroy(rm_ctx *ctx) {
         free_device_scene(ctx);
         (void)hipFree(ctx->scratch);
         (void)hipFree(ctx->d_diag);
-        (void)hipFree(ctx->d_counters);
-        (void)hipFree(ctx->d_diag_blocks);
         (void)hipFree(ctx->d_stamps);
         for (auto &t : ctx->tables) (void)hipFree(t.dev);
-        (void)hipFree(ctx->d_lpt_cost);
-        (void)hipFree(ctx->d_lpt_perm);
-        for (hipEvent_t ev : ctx->lpt_done)
-            if (ev) (void)hipEventDestroy(ev);
-        for (auto &sl : ctx->oct_frames) {
-            (void)hipFree(sl.dev);
-            for (auto &u : sl.users) (void)hipEventDestroy(u.second);
-            if (sl.built) (void)hipEventDestroy(sl.built);
-        }
+        ctx->slots.release();
+        ctx->lpt.release();
+        ctx->oct_tables.release();
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -1145,8 +1221,7 @@ int rm_render_tile_device(rm_ctx *ctx, const rm_job *job, int32_t shader, void *
 }
 
 int rm_render_attach_diagnostics(rm_ctx *ctx, void *d_acc) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (d_acc && (reinterpret_cast<uintptr_t>(d_acc) & 7)) return fail(ctx, RM_E_INVALID, "the accumulator must be 8-byte aligned");
     ctx->diag_next = d_acc;
     return RM_OK;
@@ -1212,8 +1287,7 @@ int rm_render_stripe_list_device(rm_ctx *ctx, const rm_job *job, int32_t shader,
 int rm_assemble_frame_device(rm_ctx *ctx, const void *d_gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
                              int32_t height, int32_t stripe_rows, const int32_t *owner, int32_t n_stripes, int32_t world,
                              void *d_frame, int64_t acc_offset, void *d_acc, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (!d_gathered || !d_frame || !owner) return fail(ctx, RM_E_INVALID, "null buffer");
     if (row_bytes <= 0 || height < 0 || stripe_rows <= 0 || world <= 0 || world > 65535 || rank_stride < 0 || section_offset < 0)
         return fail(ctx, RM_E_INVALID, "bad frame geometry");
@@ -1238,35 +1312,32 @@ int rm_assemble_frame_device(rm_ctx *ctx, const void *d_gathered, int64_t rank_s
 }
 
 int rm_render_tile(rm_ctx *ctx, const rm_job *job, uint8_t *depth, uint8_t *normal, uint16_t *sdf, uint16_t *iters) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
+    RM_NEED_DEVICE(ctx, "host-only context: there is no CPU render path");
     if (!job) return fail(ctx, RM_E_INVALID, "null job");
     if (!depth || !normal || !sdf || !iters) return fail(ctx, RM_E_INVALID, "null output buffer");
     const int64_t rows = job->y_end > job->y_start ? static_cast<int64_t>(job->y_end) - job->y_start : 0;
     const size_t npx = static_cast<size_t>(rows) * static_cast<size_t>(job->width > 0 ? job->width : 0);
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_depth = 0, o_normal = align_up(npx, 256), o_sdf = o_normal + align_up(3 * npx, 256),
-                 o_iters = o_sdf + align_up(2 * npx, 256), total = o_iters + align_up(2 * npx, 256);
-    int rc = ensure_scratch(ctx, total ? total : 256);
+    Staging st{ctx};
+    const size_t o_depth = st.region(npx), o_normal = st.region(3 * npx), o_sdf = st.region(2 * npx), o_iters = st.region(2 * npx);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    rc = rm_render_tile_device(ctx, job, RM_SHADE_NORMAL, base + o_depth, base + o_normal, base + o_sdf,
-                               base + o_iters, nullptr, ctx->stream);
+    rc = rm_render_tile_device(ctx, job, RM_SHADE_NORMAL, st.at<void>(o_depth), st.at<void>(o_normal), st.at<void>(o_sdf), st.at<void>(o_iters), nullptr,
+                               ctx->stream);
     if (rc) return rc;
     if (npx) {
-        RM_HIP(ctx, hipMemcpyAsync(depth, base + o_depth, npx, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(normal, base + o_normal, 3 * npx, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(sdf, base + o_sdf, 2 * npx, hipMemcpyDeviceToHost, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(iters, base + o_iters, 2 * npx, hipMemcpyDeviceToHost, ctx->stream));
+        RM_HIP(ctx, st.out(depth, o_depth, npx));
+        RM_HIP(ctx, st.out(normal, o_normal, 3 * npx));
+        RM_HIP(ctx, st.out(sdf, o_sdf, 2 * npx));
+        RM_HIP(ctx, st.out(iters, o_iters, 2 * npx));
     }
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
 int rm_shade_device(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, const void *d_depth,
                     const void *d_normal, const void *d_sdf, const void *d_iters, void *d_rgba, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (width < 0 || height < 0) return fail(ctx, RM_E_INVALID, "negative size");
     if (!d_depth || !d_normal || !d_sdf || !d_iters || !d_rgba) return fail(ctx, RM_E_INVALID, "null buffer");
     RM_HIP(ctx, hipSetDevice(ctx->device));
@@ -1279,35 +1350,33 @@ int rm_shade_device(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, 
 
 int rm_shade(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, const uint8_t *depth, const uint8_t *normal,
              const uint16_t *sdf, const uint16_t *iters, uint8_t *rgba) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (width < 0 || height < 0) return fail(ctx, RM_E_INVALID, "negative size");
     if (!depth || !normal || !sdf || !iters || !rgba) return fail(ctx, RM_E_INVALID, "null buffer");
     const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(height);
     if (!npx) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_depth = 0, o_normal = align_up(npx, 256), o_sdf = o_normal + align_up(3 * npx, 256),
-                 o_iters = o_sdf + align_up(2 * npx, 256), o_rgba = o_iters + align_up(2 * npx, 256),
-                 total = o_rgba + align_up(4 * npx, 256);
-    int rc = ensure_scratch(ctx, total);
+    Staging st{ctx};
+    const size_t o_depth = st.region(npx), o_normal = st.region(3 * npx), o_sdf = st.region(2 * npx), o_iters = st.region(2 * npx),
+                 o_rgba = st.region(4 * npx);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    RM_HIP(ctx, hipMemcpyAsync(base + o_depth, depth, npx, hipMemcpyHostToDevice, ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(base + o_normal, normal, 3 * npx, hipMemcpyHostToDevice, ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(base + o_sdf, sdf, 2 * npx, hipMemcpyHostToDevice, ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(base + o_iters, iters, 2 * npx, hipMemcpyHostToDevice, ctx->stream));
-    rc = rm_shade_device(ctx, shader, width, height, base + o_depth, base + o_normal, base + o_sdf, base + o_iters,
-                         base + o_rgba, ctx->stream);
+    RM_HIP(ctx, st.in(o_depth, depth, npx));
+    RM_HIP(ctx, st.in(o_normal, normal, 3 * npx));
+    RM_HIP(ctx, st.in(o_sdf, sdf, 2 * npx));
+    RM_HIP(ctx, st.in(o_iters, iters, 2 * npx));
+    rc = rm_shade_device(ctx, shader, width, height, st.at<void>(o_depth), st.at<void>(o_normal), st.at<void>(o_sdf), st.at<void>(o_iters),
+                         st.at<void>(o_rgba), ctx->stream);
     if (rc) return rc;
-    RM_HIP(ctx, hipMemcpyAsync(rgba, base + o_rgba, 4 * npx, hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * npx));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
 int rm_reduce_counters_enqueue(rm_ctx *ctx, const void *d_sdf, const void *d_iters, int64_t n, void *d_acc,
                                void *stream) {
-    if (!ctx || !d_acc) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!d_acc) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (n < 0 || (n > 0 && (!d_sdf || !d_iters))) return fail(ctx, RM_E_INVALID, "bad buffers");
     RM_HIP(ctx, hipSetDevice(ctx->device));
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1319,8 +1388,8 @@ int rm_reduce_counters_enqueue(rm_ctx *ctx, const void *d_sdf, const void *d_ite
 
 int rm_reduce_counters_device(rm_ctx *ctx, const void *d_sdf, const void *d_iters, int64_t n, rm_diagnostics *out,
                               void *stream) {
-    if (!ctx || !out) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!out) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     hipStream_t st = static_cast<hipStream_t>(stream);
     int rc0 = rm_reduce_counters_enqueue(ctx, d_sdf, d_iters, n, ctx->d_diag, stream);
     if (rc0) return rc0;
@@ -1336,20 +1405,20 @@ int rm_reduce_counters_device(rm_ctx *ctx, const void *d_sdf, const void *d_iter
 }
 
 int rm_reduce_counters(rm_ctx *ctx, const uint16_t *sdf, const uint16_t *iters, int64_t n, rm_diagnostics *out) {
-    if (!ctx || !out) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!out) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (n < 0 || (n > 0 && (!sdf || !iters))) return fail(ctx, RM_E_INVALID, "bad buffers");
     RM_HIP(ctx, hipSetDevice(ctx->device));
     const size_t bytes = 2 * static_cast<size_t>(n);
-    const size_t o_iters = align_up(bytes, 256);
-    int rc = ensure_scratch(ctx, o_iters + align_up(bytes, 256) + 256);
+    Staging st{ctx};
+    const size_t o_sdf = st.region(bytes), o_iters = st.region(bytes);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
     if (n) {
-        RM_HIP(ctx, hipMemcpyAsync(base, sdf, bytes, hipMemcpyHostToDevice, ctx->stream));
-        RM_HIP(ctx, hipMemcpyAsync(base + o_iters, iters, bytes, hipMemcpyHostToDevice, ctx->stream));
+        RM_HIP(ctx, st.in(o_sdf, sdf, bytes));
+        RM_HIP(ctx, st.in(o_iters, iters, bytes));
     }
-    return rm_reduce_counters_device(ctx, base, base + o_iters, n, out, ctx->stream);
+    return rm_reduce_counters_device(ctx, st.at<void>(o_sdf), st.at<void>(o_iters), n, out, ctx->stream);  // (synchronises)
 }
 
 int rm_partition_rows(int32_t height, int32_t n_workers, int32_t i, int32_t *y_start, int32_t *y_end) {
@@ -1363,18 +1432,18 @@ int rm_partition_rows(int32_t height, int32_t n_workers, int32_t i, int32_t *y_s
 }
 
 int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
     if (n < 0 || (n > 0 && (!points_xyz || !dist || !count))) return fail(ctx, RM_E_INVALID, "bad buffers");
     if (!n) return RM_OK;
     for (int64_t i = 0; i < 3 * n; ++i)
         if (!std::isfinite(points_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_dist = align_up(12 * static_cast<size_t>(n), 256), o_cnt = o_dist + align_up(8 * static_cast<size_t>(n), 256);
-    int rc = ensure_scratch(ctx, o_cnt + align_up(4 * static_cast<size_t>(n), 256));
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_pts = st.region(12 * k), o_dist = st.region(8 * k), o_cnt = st.region(4 * k);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
     RmRenderParams p;
     std::memset(&p, 0, sizeof p);
     fill_scene_view(ctx, p);
@@ -1385,13 +1454,12 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
         const rmrtc::Kernel *special = specialised_kernel(ctx, p.accel, false);
         p.rtc_function = special ? special->distance : nullptr;
     }
-    RM_HIP(ctx, hipMemcpyAsync(base, points_xyz, 12 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_distance_sqrt : rm_launch_distance)(
-                    p, reinterpret_cast<const float *>(base), n, reinterpret_cast<double *>(base + o_dist),
-                    reinterpret_cast<uint32_t *>(base + o_cnt), ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(dist, base + o_dist, 8 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(count, base + o_cnt, 4 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, st.in(o_pts, points_xyz, 12 * k));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_distance_sqrt : rm_launch_distance)(p, st.at<const float>(o_pts), n, st.at<double>(o_dist),
+                                                                                  st.at<uint32_t>(o_cnt), ctx->stream));
+    RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
+    RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
@@ -1457,112 +1525,81 @@ int rm_scene_object(rm_ctx *ctx, int32_t index, rm_node *nodes, int32_t cap, int
 }
 
 int rm_selftest_hypot(rm_ctx *ctx, const float *xyz, int64_t n, double *out) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (n < 0 || (n > 0 && (!xyz || !out))) return fail(ctx, RM_E_INVALID, "bad buffers");
     if (!n) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t o_out = align_up(12 * static_cast<size_t>(n), 256);
-    int rc = ensure_scratch(ctx, o_out + 8 * static_cast<size_t>(n));
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_xyz = st.region(12 * k), o_out = st.region(8 * k);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    RM_HIP(ctx, hipMemcpyAsync(base, xyz, 12 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    RM_HIP(ctx, rm_launch_hypot(reinterpret_cast<const float *>(base), n, reinterpret_cast<double *>(base + o_out),
-                                ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(out, base + o_out, 8 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, st.in(o_xyz, xyz, 12 * k));
+    RM_HIP(ctx, rm_launch_hypot(st.at<const float>(o_xyz), n, st.at<double>(o_out), ctx->stream));
+    RM_HIP(ctx, st.out(out, o_out, 8 * k));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
 int rm_selftest_jsmath(rm_ctx *ctx, int32_t fn, const double *a, const double *b, int64_t n, double *out) {
-    if (!ctx) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (n < 0 || fn < 0 || fn > 7 || (n > 0 && (!a || !out))) return fail(ctx, RM_E_INVALID, "bad buffers");
     if (!n) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t stride = align_up(8 * static_cast<size_t>(n), 256);
-    int rc = ensure_scratch(ctx, 3 * stride);
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_a = st.region(8 * k), o_b = st.region(8 * k), o_out = st.region(8 * k);
+    int rc = st.reserve();
     if (rc) return rc;
-    char *base = static_cast<char *>(ctx->scratch);
-    RM_HIP(ctx, hipMemcpyAsync(base, a, 8 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    if (b) {
-        RM_HIP(ctx, hipMemcpyAsync(base + stride, b, 8 * static_cast<size_t>(n), hipMemcpyHostToDevice, ctx->stream));
-    } else {
-        RM_HIP(ctx, hipMemsetAsync(base + stride, 0, 8 * static_cast<size_t>(n), ctx->stream));
-    }
-    RM_HIP(ctx, rm_launch_jsmath(fn, reinterpret_cast<const double *>(base), reinterpret_cast<const double *>(base + stride),
-                                 n, reinterpret_cast<double *>(base + 2 * stride), ctx->stream));
-    RM_HIP(ctx, hipMemcpyAsync(out, base + 2 * stride, 8 * static_cast<size_t>(n), hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    RM_HIP(ctx, st.in(o_a, a, 8 * k));
+    if (b) RM_HIP(ctx, st.in(o_b, b, 8 * k));
+    else RM_HIP(ctx, st.zero(o_b, 8 * k));  // no second operand: zeros
+    RM_HIP(ctx, rm_launch_jsmath(fn, st.at<const double>(o_a), st.at<const double>(o_b), n, st.at<double>(o_out), ctx->stream));
+    RM_HIP(ctx, st.out(out, o_out, 8 * k));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
 int rm_selftest_fastdiv(rm_ctx *ctx, uint64_t seed, int64_t n, uint64_t *mismatches) {
-    if (!ctx || !mismatches) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!mismatches) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (n < 0) return fail(ctx, RM_E_INVALID, "negative count");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_scratch(ctx, 256);
-    if (rc) return rc;
-    unsigned long long *d = static_cast<unsigned long long *>(ctx->scratch);
-    RM_HIP(ctx, hipMemsetAsync(d, 0, sizeof *d, ctx->stream));
-    RM_HIP(ctx, rm_launch_fastdiv_selftest(seed, n, d, ctx->stream));
-    unsigned long long h = 0;
-    RM_HIP(ctx, hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *mismatches = h;
-    return RM_OK;
+    return read_mismatches(ctx, [&](unsigned long long *d) { return rm_launch_fastdiv_selftest(seed, n, d, ctx->stream); }, mismatches);
 }
 
 int rm_selftest_recip(rm_ctx *ctx, int mode, uint64_t *mismatches) {
-    if (!ctx || !mismatches) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!mismatches) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     if (mode != 0 && mode != 1) return fail(ctx, RM_E_INVALID, "mode must be 0 or 1");
+    return read_mismatches(ctx, [&](unsigned long long *d) { return rm_launch_recip_selftest(mode, d, ctx->stream); }, mismatches);
+}
+
+// The rm_debug_read_* entries of the diagnostic builds (-DRM_STAMPS, -DRM_COUNTS, ...): `bytes` of ctx->d_stamps from word
+// `first` on, read behind everything enqueued and zeroed for the next launch.
+static int read_stamps(rm_ctx *ctx, void *out, size_t first, size_t bytes) {
+    if (!out) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_scratch(ctx, 256);
-    if (rc) return rc;
-    unsigned long long *d = static_cast<unsigned long long *>(ctx->scratch);
-    RM_HIP(ctx, hipMemsetAsync(d, 0, sizeof *d, ctx->stream));
-    RM_HIP(ctx, rm_launch_recip_selftest(mode, d, ctx->stream));
-    unsigned long long h = 0;
-    RM_HIP(ctx, hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, ctx->stream));
-    RM_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *mismatches = h;
+    RM_HIP(ctx, hipDeviceSynchronize());
+    RM_HIP(ctx, hipMemcpy(out, ctx->d_stamps + first, bytes, hipMemcpyDeviceToHost));
+    RM_HIP(ctx, hipMemset(ctx->d_stamps + first, 0, bytes));
     return RM_OK;
 }
 
 int rm_debug_read_stamps(rm_ctx *ctx, uint64_t *out8) {
-    if (!ctx || !out8) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, hipDeviceSynchronize());
-    RM_HIP(ctx, hipMemcpy(out8, ctx->d_stamps, 8 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    RM_HIP(ctx, hipMemset(ctx->d_stamps, 0, 8 * sizeof(uint64_t)));
+    const int rc = read_stamps(ctx, out8, 0, 8 * sizeof(uint64_t));
+    if (rc) return rc;
     RM_HIP(ctx, hipMemset(ctx->d_stamps + 6, 0xFF, sizeof(uint64_t)));  // slot 6: minimum start time of the next launch's waves
     return RM_OK;
 }
 
 // -DRM_STAMPS builds: start / end time (s_memrealtime, 100 MHz) of the first 8192 waves of the last v2 launch
-int rm_debug_read_wave_times(rm_ctx *ctx, uint64_t *out16384) {
-    if (!ctx || !out16384) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, hipDeviceSynchronize());
-    RM_HIP(ctx, hipMemcpy(out16384, ctx->d_stamps + 40, 3 * 8192 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    RM_HIP(ctx, hipMemset(ctx->d_stamps + 40, 0, 3 * 8192 * sizeof(uint64_t)));
-    return RM_OK;
-}
+int rm_debug_read_wave_times(rm_ctx *ctx, uint64_t *out16384) { return read_stamps(ctx, out16384, 40, 3 * 8192 * sizeof(uint64_t)); }
 
 // -DRM_STAMPS -DRM_STAMPS_LOG builds: the low 32 bits of s_memrealtime at the start of the first 96 batches of the first 2048 waves
-int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608) {
-    if (!ctx || !out196608) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, hipDeviceSynchronize());
-    RM_HIP(ctx, hipMemcpy(out196608, ctx->d_stamps + 40 + 3 * 8192, 2048 * 96 * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    RM_HIP(ctx, hipMemset(ctx->d_stamps + 40 + 3 * 8192, 0, 2048 * 96 * sizeof(uint32_t)));
-    return RM_OK;
-}
+int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608) { return read_stamps(ctx, out196608, 40 + 3 * 8192, 2048 * 96 * sizeof(uint32_t)); }
+
+int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32) { return read_stamps(ctx, out32, 8, 32 * sizeof(uint64_t)); }
 
 // ---- run-time specialisation of expression forests (rm_rtc.h) -------------------------------------------------------------
 static int copy_text(const std::string &t, char *out, int64_t cap, int64_t *needed) {
@@ -1608,26 +1645,15 @@ int rm_rtc_status(rm_ctx *ctx, int32_t *compiled, int32_t *failed, char *log, in
     return copy_text(ctx->rtc_log, log, cap, nullptr);
 }
 
-// the item costs (durations in units of 2.56 us, one byte per item, 64 queues x kLptStride slots) the LAST v2 launch recorded
+// the item costs (durations in units of 2.56 us, one byte per item, 64 queues x LptRing::kStride slots) the LAST v2 launch recorded
 int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n) {
-    if (!ctx || !out) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
-    const size_t per_slot = static_cast<size_t>(rm_ctx::kLptQueues) * rm_ctx::kLptStride;
-    if (!ctx->d_lpt_cost || ctx->lpt_launch == 0 || n < 0 || static_cast<size_t>(n) > per_slot) return fail(ctx, RM_E_INVALID, "no costs recorded");
+    if (!out) return RM_E_INVALID;
+    RM_NEED_DEVICE(ctx, "host-only context");
+    const uint8_t *costs = ctx->lpt.last_costs();
+    if (!costs || n < 0 || static_cast<size_t>(n) > LptRing::kPerSlot) return fail(ctx, RM_E_INVALID, "no costs recorded");
     RM_HIP(ctx, hipSetDevice(ctx->device));
     RM_HIP(ctx, hipDeviceSynchronize());
-    const unsigned slot = (ctx->lpt_launch + rm_ctx::kLptSlots - 1) % rm_ctx::kLptSlots;
-    RM_HIP(ctx, hipMemcpy(out, ctx->d_lpt_cost + slot * per_slot, static_cast<size_t>(n), hipMemcpyDeviceToHost));
-    return RM_OK;
-}
-
-int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32) {
-    if (!ctx || !out32) return RM_E_INVALID;
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, hipDeviceSynchronize());
-    RM_HIP(ctx, hipMemcpy(out32, ctx->d_stamps + 8, 32 * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    RM_HIP(ctx, hipMemset(ctx->d_stamps + 8, 0, 32 * sizeof(uint64_t)));
+    RM_HIP(ctx, hipMemcpy(out, costs, static_cast<size_t>(n), hipMemcpyDeviceToHost));
     return RM_OK;
 }
 

@@ -1424,3 +1424,62 @@ def test_longest_first_item_order_is_only_an_order(rm, oracle):
         for name in b:
             assert torch.equal(b[name], sets[k][name]), (k, name)
     ctx.close()
+
+
+def test_host_entries_stage_through_one_scratch(rm, oracle):
+    """The entries that take host buffers stage them through one scratch buffer of the context.  On a fresh context
+    (preset 0, no acceleration) they run in an order that makes the scratch grow (256 bytes, 24 KB for 1 000 points, 36 KB for
+    the shade of a 64 x 48 tile), be reused while far too large (down to 3 points) and grow again (55 KB for 1 000 rays),
+    each result against the oracle -- ray queries against the device entry on the same rays.  Then a pick of (1 << 22) + 77 rays, the smallest count that crosses the 4 M-ray chunk seam
+    of the host ray entries: all five outputs bit for bit over the whole range, so the ray at index 1 << 22 and the 77
+    behind it are covered."""
+    import ctypes
+    import torch
+    from test_ray_queries import random_rays
+    ctx = rm.Context(0)
+    dev = torch.device("cuda:0")
+    L = oracle.lib()
+    L.ro_jsmath_eval.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3 + [ctypes.c_long]
+    osc = oracle.OracleScene(preset=0, accel="None")
+    rng = np.random.default_rng(17)
+
+    def distances(pts):
+        sc = rm.Scene("None", ctx=ctx)
+        sc.loadPreset(0)
+        d, c = sc.getDistances(pts)
+        for k in range(len(pts)):
+            assert (d[k], c[k]) == osc.distance(pts[k]), k
+
+    def picks(n, seed):
+        o, d = random_rays(n, seed=seed)
+        want = ctx.pick(torch.from_numpy(o).to(dev), torch.from_numpy(d).to(dev))
+        torch.cuda.synchronize()
+        got = ctx.pick(o, d)
+        for g, w, name in zip(got, want, ("t", "iters", "sdf", "normal", "object")):
+            assert np.array_equal(np.ascontiguousarray(g).view(np.uint8).ravel(), w.cpu().numpy().view(np.uint8).ravel()), (n, name)
+
+    assert ctx.selftest_fastdiv(0x1234, 1000) == 0
+    distances(rng.uniform(-2, 2, (1000, 3)).astype(np.float32))
+    W, H = 64, 48
+    sc = rm.Scene("None", ctx=ctx)
+    sc.loadPreset(0)
+    bufs = (np.zeros(W * H, np.uint8), np.zeros(3 * W * H, np.uint8), np.zeros(W * H, np.uint16), np.zeros(W * H, np.uint16))
+    rgba = np.zeros(4 * W * H, np.uint8)
+    rm.SphereTracer().runRaymarcher(sc, *bufs, W, H, 0.0, shadedBuffer=rgba, shader="iteration-heatmap")
+    want = cpu_render(oracle, 0, "None", W, H)
+    assert_same(bufs, want, "host tile")
+    assert np.array_equal(rgba, oracle.shade("iteration-heatmap", *want, W, H))
+    red = ctx.reduce_counters(bufs[2], bufs[3])
+    wd = _oracle_diag(want)
+    assert {k: red[k] for k in wd} == wd and red["total_pixels"] == W * H
+    a, b = rng.normal(0, 1, 1000) * 10.0 ** rng.integers(-5, 5, 1000), rng.normal(0, 1, 1000) * 10.0 ** rng.integers(-5, 5, 1000)
+    for fn, bb in ((7, None), (2, b)):  # Math.atan(a): b absent, read as zeros; Math.atan2(a, b)
+        ob, wj = (np.zeros_like(a) if bb is None else bb), np.zeros_like(a)
+        L.ro_jsmath_eval(fn, a.ctypes.data, ob.ctypes.data, wj.ctypes.data, len(a))
+        assert np.array_equal(ctx.selftest_jsmath(fn, a, bb).view(np.uint64), wj.view(np.uint64)), fn
+    xyz = (rng.standard_normal((1000, 3)) * 3).astype(np.float32)
+    assert np.array_equal(ctx.selftest_hypot(xyz), np.array([L.ro_hypot3(float(x), float(y), float(z)) for x, y, z in xyz]))
+    distances(rng.uniform(-2, 2, (3, 3)).astype(np.float32))
+    picks(1000, 7)
+    picks((1 << 22) + 77, 9)
+    ctx.close()

@@ -326,3 +326,77 @@ def test_uploads_of_every_kind_replace_one_another(rm):
     ctx.scene_from_prims(prims, 0)
     prim_0()
     ctx.close()
+
+
+def test_device_entries_keep_their_order_of_refusals(rm):
+    """Every exported entry that needs a device, called through ctypes (no Python-side validation in the way): the code of
+    a null context; the code and rm_last_error text of a host-only context with otherwise valid arguments; and which
+    refusal wins when one argument is bad as well.  The order of the checks and the texts are behaviour: some entries
+    look at an argument before the device (the accumulator of rm_reduce_counters_enqueue, the query, count and buffers of
+    a ray query), the others at the device first.  Every call is refused before any copy, so no pointer is dereferenced."""
+    from cpu_raymarcher_amd import _native as N
+    L = N.lib()
+    ctx = rm.Context(None)
+    ctx.scene_from_preset(0, 0)
+    buf = np.zeros(4096, np.uint8)
+    p = buf.ctypes.data_as(C.c_void_p)
+    odd = buf[1:].ctypes.data_as(C.c_void_p)  # inside the same buffer, not 8-byte aligned
+    ids = np.zeros(1, np.int32).ctypes.data_as(C.c_void_p)
+    job = N.rm_job(width=4, height=4, y_end=4)
+    J, Q = C.byref(job), C.byref(N.rm_ray_query())
+    D, U = C.byref(N.rm_diagnostics()), C.byref(C.c_uint64(0))
+    INVALID, NO_DEVICE = N.RM_E_INVALID, N.RM_E_NO_DEVICE
+    HOST, RENDER, RAY = "host-only context", "host-only context: there is no CPU render path", "host-only context: there is no CPU ray path"
+    KEPT = "unknown option no_such_option"  # the text a refused rm_set_option leaves before every call: the entry set none
+    five = (p, p, p, p, p)
+
+    def rays(device, pick):  # rm_ray_march / _device, rm_ray_pick / _device: the arguments behind (query, n, origins, dirs)
+        tail = (p, p, p, p) + ((p,) if pick else ()) + ((None,) if device else ())
+        return ((Q, 2, p, p) + tail, RAY,
+                [((None, 2, p, p) + tail, INVALID, "null query"), ((Q, -1, p, p) + tail, INVALID, "ray count out of range"),
+                 ((Q, 1 << 31, p, p) + tail, INVALID, "ray count out of range"), ((Q, 2, None, p) + tail, INVALID, "null ray buffer"),
+                 ((Q, 2, p, None) + tail, INVALID, "null ray buffer"), ((None, -1, None, None) + tail, INVALID, "null query")])
+
+    # entry: (valid arguments behind the context, text of the host-only refusal, [(arguments with one bad, code, text)])
+    table = {
+        "rm_render_tile_device": ((J, 0) + five + (None,), RENDER, [((None, 0) + five + (None,), NO_DEVICE, RENDER)]),
+        "rm_render_stripes_device": ((J, 0, 16, 2, 0) + five + (None,), RENDER,
+                                     [((None, 0, 16, 2, 0) + five + (None,), NO_DEVICE, RENDER), ((J, 0, 16, 0, 0) + five + (None,), NO_DEVICE, RENDER)]),
+        "rm_render_stripe_list_device": ((J, 0, 16, ids, 1) + five + (None,), RENDER,
+                                         [((None, 0, 16, ids, 1) + five + (None,), NO_DEVICE, RENDER), ((J, 0, 0, None, 1) + five + (None,), NO_DEVICE, RENDER)]),
+        "rm_render_tile": ((J, p, p, p, p), RENDER, [((None, p, p, p, p), NO_DEVICE, RENDER), ((J, None, p, p, p), NO_DEVICE, RENDER)]),
+        "rm_render_attach_diagnostics": ((p,), HOST, [((odd,), NO_DEVICE, HOST)]),
+        "rm_assemble_frame_device": ((p, 64, 0, 16, 4, 4, ids, 1, 1, p, -1, None, None), HOST,
+                                     [((None, 64, 0, 16, 4, 4, ids, 1, 1, p, -1, None, None), NO_DEVICE, HOST),
+                                      ((p, 64, 0, 16, 4, 4, ids, 1, 0, p, -1, None, None), NO_DEVICE, HOST)]),
+        "rm_shade": ((0, 4, 4) + five, HOST, [((0, -4, 4) + five, NO_DEVICE, HOST), ((0, 4, 4, None, p, p, p, p), NO_DEVICE, HOST)]),
+        "rm_shade_device": ((0, 4, 4) + five + (None,), HOST,
+                            [((0, 4, -4) + five + (None,), NO_DEVICE, HOST), ((0, 4, 4, p, p, p, p, None, None), NO_DEVICE, HOST)]),
+        "rm_reduce_counters_enqueue": ((p, p, 16, p, None), HOST, [((p, p, 16, None, None), INVALID, KEPT), ((p, p, -1, p, None), NO_DEVICE, HOST),
+                                                                    ((None, p, 16, p, None), NO_DEVICE, HOST)]),
+        "rm_reduce_counters_device": ((p, p, 16, D, None), HOST, [((p, p, 16, None, None), INVALID, KEPT), ((p, p, -1, D, None), NO_DEVICE, HOST)]),
+        "rm_reduce_counters": ((p, p, 16, D), HOST, [((p, p, 16, None), INVALID, KEPT), ((p, None, 16, D), NO_DEVICE, HOST), ((p, p, -1, D), NO_DEVICE, HOST)]),
+        "rm_scene_distance": ((p, 4, p, p), HOST, [((p, -1, p, p), NO_DEVICE, HOST), ((None, 4, p, p), NO_DEVICE, HOST)]),
+        "rm_ray_march": rays(False, False),
+        "rm_ray_march_device": rays(True, False),
+        "rm_ray_pick": rays(False, True),
+        "rm_ray_pick_device": rays(True, True),
+        "rm_selftest_hypot": ((p, 4, p), HOST, [((p, -1, p), NO_DEVICE, HOST), ((None, 4, p), NO_DEVICE, HOST)]),
+        "rm_selftest_jsmath": ((0, p, p, 4, p), HOST, [((9, p, p, 4, p), NO_DEVICE, HOST), ((0, None, p, 4, p), NO_DEVICE, HOST)]),
+        "rm_selftest_fastdiv": ((1, 4, U), HOST, [((1, 4, None), INVALID, KEPT), ((1, -4, U), NO_DEVICE, HOST)]),
+        "rm_selftest_recip": ((0, p), HOST, [((0, None), INVALID, KEPT), ((2, p), NO_DEVICE, HOST)]),
+        "rm_debug_read_stamps": ((p,), HOST, [((None,), INVALID, KEPT)]),
+        "rm_debug_read_wave_times": ((p,), HOST, [((None,), INVALID, KEPT)]),
+        "rm_debug_read_batch_log": ((p,), HOST, [((None,), INVALID, KEPT)]),
+        "rm_debug_read_counts": ((p,), HOST, [((None,), INVALID, KEPT)]),
+        "rm_debug_read_lpt_costs": ((p, 16), HOST, [((None, 16), INVALID, KEPT), ((p, -1), NO_DEVICE, HOST)]),
+    }
+    assert len(table) == 25 and set(table) <= set(N.SIGNATURES)
+    for name, (good, text, bad) in table.items():
+        fn = getattr(L, name)
+        assert fn(None, *good) == INVALID, name  # a null context: no context to leave a text in
+        for args, code, want in [(good, NO_DEVICE, text)] + bad:
+            assert L.rm_set_option(ctx._h, b"no_such_option", 1) == INVALID
+            assert fn(ctx._h, *args) == code, (name, args)
+            assert L.rm_last_error(ctx._h).decode() == want, (name, args)
+    ctx.close()
