@@ -49,6 +49,10 @@ class rm_ray_query(C.Structure):  # include/rm_raymarch.h: struct rm_ray_query
                 ("overshoot_factor", C.c_double), ("step_size", C.c_double)]
 
 
+class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
+    _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
+
+
 class rm_scene_info(C.Structure):
     _fields_ = [("n_prims", C.c_int32), ("accel", C.c_int32), ("preset_index", C.c_int32),
                 ("bvh_nodes", C.c_int32), ("bvh_leaves", C.c_int32), ("bvh_depth", C.c_int32),
@@ -103,6 +107,8 @@ SIGNATURES = {
     "rm_scene_object": (C.c_int, [_VP, C.c_int32, C.POINTER(rm_node), C.c_int32, C.POINTER(C.c_int32)]),
     "rm_render_tile": (C.c_int, [_VP, C.POINTER(rm_job), _VP, _VP, _VP, _VP]),
     "rm_render_tile_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_render_frames_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_sweep_views": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _VP]),
     "rm_render_stripes_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_stripe_rows": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),

@@ -291,6 +291,26 @@ class Context:
             rows = max(0, job.y_end - job.y_start)
             self.shade(shader, job.width, rows, depth, normal, sdf, iters, rgba)
 
+    def render_frames(self, job, views, depth, normal, sdf, iters, rgba=None, shader=0, diag=None):
+        """len(views) frames of one scene in one launch (rm_render_frames_device) on torch's current stream.  `job` gives what
+        the frames share (its own camera and time are ignored); `views` is a sequence of (pitch, yaw, time) or an (n, 3)
+        float64 array (sweep_views).  depth / normal / sdf / iters / rgba: CUDA tensors that hold the n frames one behind the
+        other (frame k at pixel k * width * rows), or None; `diag`: None or a CUDA tensor of 32 * n bytes that receives one
+        accumulator per frame (decode_accs)."""
+        v = np.ascontiguousarray(views, dtype=np.float64).reshape(-1, 3)
+        n = len(v)
+        npx = max(0, job.y_end - job.y_start) * max(0, job.width)
+        bufs = dict(depth=depth, normal=normal, sdf=sdf, iters=iters, rgba=rgba)
+        _check_buffers(npx * n, bufs, need_device=True)
+        self._same_device(bufs)
+        if diag is not None:
+            if not (_is_torch(diag) and diag.is_cuda and diag.is_contiguous() and diag.numel() * diag.element_size() >= 32 * n):
+                raise ValueError("diag must be a contiguous CUDA tensor of 32 bytes per view")
+            self._same_device(dict(diag=diag))
+        N.check(self._h, N.lib().rm_render_frames_device(
+            self._h, C.byref(job), int(shader), _ptr(v), n, _ptr(depth), _ptr(normal), _ptr(sdf), _ptr(iters), _ptr(rgba),
+            _ptr(diag), _current_stream_ptr() if self.device >= 0 else None))  # (a host-only context: RM_E_NO_DEVICE from the library)
+
     def _same_device(self, bufs):
         for name, b in bufs.items():
             if b is not None and _is_torch(b) and b.is_cuda and b.device.index != self.device:
@@ -426,6 +446,13 @@ class Context:
         return {"total_sdf": v[0], "total_iters": v[1], "max_sdf": v[2] & 0xFFFFFFFF,
                 "min_sdf": (v[2] >> 32) & 0xFFFFFFFF}
 
+    @staticmethod
+    def decode_accs(acc):
+        """decode_acc for a batch: one dict per 32-byte accumulator of `acc` (render_frames' diag)."""
+        v = acc.cpu().contiguous().view(-1).numpy().view(np.uint64).reshape(-1, 4)
+        return [{"total_sdf": int(r[0]), "total_iters": int(r[1]), "max_sdf": int(r[2]) & 0xFFFFFFFF, "min_sdf": int(r[2]) >> 32}
+                for r in v]
+
     def selftest_hypot(self, xyz):
         a = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(len(a), np.float64)
@@ -480,6 +507,17 @@ def camera_from_angles(pitch, yaw):
     if rc != N.RM_OK:
         raise N.RmError(rc, "rm_camera_from_angles")
     return rot, org
+
+
+def sweep_views(pitch, yaw, d_pitch, d_yaw, time0=0.0, d_time=0.0, n=1):
+    """rm_sweep_views: the (pitch, yaw, time) of Camera.setAngles(pitch, yaw) followed by n - 1 calls of
+    Camera.rotateCamera(d_pitch, d_yaw) (camera.ts:26-31,58-62), time0 + k * d_time -> float64 (n, 3), what
+    Context.render_frames takes as views."""
+    out = np.zeros((max(0, int(n)), 3), np.float64)
+    rc = N.lib().rm_sweep_views(float(pitch), float(yaw), float(d_pitch), float(d_yaw), float(time0), float(d_time), int(n), _ptr(out))
+    if rc != N.RM_OK:
+        raise N.RmError(rc, "rm_sweep_views")
+    return out
 
 
 def camera_rays(width, height, pitch, yaw, y_start=0, y_end=None):

@@ -78,6 +78,85 @@ struct LaunchSlots {
     RmDiagBlock *take_block() { return blocks ? blocks + block_slot++ % kLaunches : nullptr; }
 };
 
+// The ring of rm_render_frames_device: per frame of a call one RmFrameView (the frame's camera and time; written by the host
+// into a pinned mirror and copied on the call's stream) and one RmFrameDiagBlock (rm_diag.h; zeroed when allocated, left zeroed
+// by the last wave of its frame).
+//  - A call takes n consecutive entries, from the start again when the end is too near, and records an event behind its
+//    launch (launched).  The entries stay that call's -- mirror, table and blocks alike -- until the event has completed:
+//    take() waits for the event of every earlier call whose entries overlap the ones it hands out, whatever stream that call
+//    ran on, so neither the host (writing the mirror) nor a later launch (adding into the blocks) meets a call in flight.  A
+//    call without an event (none to be had, or its launch failed) has its stream synchronised instead.
+//  - Batches of up to half the ring therefore never wait for the call just before them; larger ones do.
+//  - Allocated at the first call, kFrames entries (5 MB).  A call of more frames replaces the ring by one that holds exactly
+//    it: the device is synchronised first (nothing in flight reads the old ring), so that one call is not asynchronous.
+struct FrameRing {
+    static constexpr size_t kFrames = 4096;
+    struct Claim {
+        size_t first, n;
+        hipEvent_t done;
+    };
+    RmFrameView *host = nullptr, *dev = nullptr;
+    RmFrameDiagBlock *blocks = nullptr;
+    size_t cap = 0, next = 0;
+    std::vector<Claim> claims;  // calls whose event has not been waited for yet
+
+    void retire_all() {  // (the device is idle)
+        for (Claim &c : claims) (void)hipEventDestroy(c.done);
+        claims.clear();
+    }
+    void release() {
+        retire_all();
+        (void)hipHostFree(host);
+        (void)hipFree(dev);
+        (void)hipFree(blocks);
+        host = dev = nullptr;
+        blocks = nullptr;
+        cap = next = 0;
+    }
+    // first entry of n consecutive ones that no call in flight owns
+    hipError_t take(size_t n, size_t *first) {
+        if (n > cap) {
+            hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) return e;
+            release();
+            const size_t want = n > kFrames ? n : kFrames;
+            e = hipHostMalloc(reinterpret_cast<void **>(&host), want * sizeof(RmFrameView), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dev), want * sizeof(RmFrameView));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&blocks), want * sizeof(RmFrameDiagBlock));
+            if (e == hipSuccess) e = hipMemset(blocks, 0, want * sizeof(RmFrameDiagBlock));
+            if (e != hipSuccess) {
+                release();
+                return e;
+            }
+            cap = want;
+        }
+        if (next + n > cap) next = 0;
+        const size_t lo = next, hi = next + n;
+        for (size_t k = 0; k < claims.size();) {
+            const Claim c = claims[k];
+            if (c.first < hi && lo < c.first + c.n) {
+                const hipError_t e = hipEventSynchronize(c.done);
+                if (e != hipSuccess) return e;
+                (void)hipEventDestroy(c.done);
+                claims.erase(claims.begin() + static_cast<std::ptrdiff_t>(k));
+            } else ++k;
+        }
+        *first = lo;
+        next = hi;
+        return hipSuccess;
+    }
+    // behind the launch (or the failed attempt) that uses the entries of the last take
+    void launched(size_t first, size_t n, hipStream_t stream) {
+        hipEvent_t ev = nullptr;
+        if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) == hipSuccess && hipEventRecord(ev, stream) == hipSuccess) {
+            claims.push_back(Claim{first, n, ev});
+            return;
+        }
+        if (ev) (void)hipEventDestroy(ev);
+        (void)hipStreamSynchronize(stream);
+    }
+};
+
 // The LPT ring (option `lpt`; rm_render_v2.hip, lpt_sort_kernel): a v2 launch sorts its items longest-first from the costs the
 // previous launch recorded, into a permutation of its own, and records its own costs; one slot per launch in flight.
 //  - The buffers are allocated at the first acquire; both exist or neither does (launches then keep their queues' order).
@@ -280,6 +359,7 @@ struct rm_ctx {
     LaunchSlots slots;        // the three rings of launch_render (above)
     LptRing lpt;
     OctTableRing oct_tables;
+    FrameRing frames;         // rm_render_frames_device
     unsigned long long scene_gen = 0;  // bumped by every upload_scene
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
@@ -1083,6 +1163,7 @@ void rm_destroy(rm_ctx *ctx) {
         ctx->slots.release();
         ctx->lpt.release();
         ctx->oct_tables.release();
+        ctx->frames.release();
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -1218,6 +1299,79 @@ int rm_camera_from_angles(double pitch, double yaw, float *rot9, float *origin3)
 int rm_render_tile_device(rm_ctx *ctx, const rm_job *job, int32_t shader, void *d_depth, void *d_normal, void *d_sdf,
                           void *d_iters, void *d_rgba, void *stream) {
     return render_device(ctx, job, shader, Stripes(), {d_depth, d_normal, d_sdf, d_iters, d_rgba}, stream);
+}
+
+int rm_render_frames_device(rm_ctx *ctx, const rm_job *job, int32_t shader, const rm_view *views, int32_t n_views, void *d_depth,
+                            void *d_normal, void *d_sdf, void *d_iters, void *d_rgba, void *d_acc, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    if (!job) return fail(ctx, RM_E_INVALID, "null job");
+    if (n_views < 0 || n_views > 65535) return fail(ctx, RM_E_INVALID, "n_views must be in [0, 65535] (one grid dimension)");
+    if (n_views > 0 && !views) return fail(ctx, RM_E_INVALID, "null views");
+    for (int32_t k = 0; k < n_views; ++k)
+        if (!std::isfinite(views[k].camera_pitch) || !std::isfinite(views[k].camera_yaw) || !std::isfinite(views[k].time))
+            return fail(ctx, RM_E_INVALID, "non-finite angle or time in view " + std::to_string(k));
+    if (d_acc && (reinterpret_cast<uintptr_t>(d_acc) & 7)) return fail(ctx, RM_E_INVALID, "the accumulators must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU render path");
+    // everything the frames share, defaulted and clamped as for rm_render_tile_device; the job's own camera and time are not read
+    rm_job shared = *job;
+    shared.camera_pitch = shared.camera_yaw = shared.time = 0.0;
+    const double scene_time = ctx->time;
+    RmRenderParams p;
+    const int rc = fill_params(ctx, &shared, p);
+    ctx->time = scene_time;  // (fill_params stores the job's time there; this entry leaves rm_scene_set_time's value alone)
+    if (rc) return rc;
+    if (n_views == 0) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    p.variant = 1;  // the ahead-of-time one-ray-per-lane kernels, 8 x 8 wave tiles unless tile_w was set (fill_params)
+    if (!ctx->tile_w_set) p.tile_w = 8;
+    p.shader = norm_shader(shader);
+    p.depth = static_cast<uint8_t *>(d_depth);
+    p.normal = static_cast<uint8_t *>(d_normal);
+    p.sdf = static_cast<uint16_t *>(d_sdf);
+    p.iters = static_cast<uint16_t *>(d_iters);
+    p.rgba = static_cast<uint8_t *>(d_rgba);
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const bool empty = p.local_rows <= 0 || p.width <= 0;
+    const RmFrameView *d_views = nullptr;
+    RmFrameDiagBlock *blocks = nullptr;
+    size_t first = 0;
+    if (!empty) {
+        RM_HIP(ctx, ctx->frames.take(static_cast<size_t>(n_views), &first));
+        RmFrameView *h = ctx->frames.host + first;
+        for (int32_t k = 0; k < n_views; ++k) {
+            rmh::camera_from_angles(views[k].camera_pitch, views[k].camera_yaw, h[k].rot, h[k].origin);
+            for (int a = 0; a < 3; ++a) h[k].origin_d[a] = h[k].origin[a];
+            h[k].time = views[k].time;
+        }
+        d_views = ctx->frames.dev + first;
+        blocks = d_acc ? ctx->frames.blocks + first : nullptr;
+    }
+    hipError_t e = empty ? hipSuccess
+                         : hipMemcpyAsync(ctx->frames.dev + first, ctx->frames.host + first, static_cast<size_t>(n_views) * sizeof(RmFrameView),
+                                          hipMemcpyHostToDevice, hs);
+    if (e == hipSuccess)
+        e = (ctx->opt_length ? rm_launch_frames_sqrt : rm_launch_frames)(p, d_views, n_views, blocks, static_cast<RmDiagDevice *>(d_acc), hs,
+                                                                         &ctx->last_kernel);
+    if (!empty) ctx->frames.launched(first, static_cast<size_t>(n_views), hs);  // (also behind a failed attempt: the copy may be queued)
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_render_frames_device");
+    return RM_OK;
+}
+
+int rm_sweep_views(double pitch, double yaw, double d_pitch, double d_yaw, double time0, double d_time, int32_t n, rm_view *views) {
+    if (!std::isfinite(pitch) || !std::isfinite(yaw) || !std::isfinite(d_pitch) || !std::isfinite(d_yaw) || !std::isfinite(time0) ||
+        !std::isfinite(d_time) || n < 0 || (n > 0 && !views))
+        return RM_E_INVALID;
+    double p = rmh::clamp_pitch(pitch), y = yaw;  // Camera.setAngles (camera.ts:58-62)
+    for (int32_t k = 0; k < n; ++k) {
+        if (k) {  // Camera.rotateCamera (camera.ts:26-31)
+            p = rmh::clamp_pitch(p + d_pitch);
+            y += d_yaw;
+        }
+        views[k].camera_pitch = p;
+        views[k].camera_yaw = y;
+        views[k].time = time0 + static_cast<double>(k) * d_time;
+    }
+    return RM_OK;
 }
 
 int rm_render_attach_diagnostics(rm_ctx *ctx, void *d_acc) {

@@ -14,6 +14,12 @@
 // flushed, so they are performed (at device scope: every XCD sees them) before the count can reach its target; there is
 // no fence, whose release half would write back every dirty line of the XCD's L2 -- the pixel stores.  The last wave
 // reads the slots with device-scope atomic loads.  min is kept as max(0xFFFFFFFF - sdfEval): all accumulators start at 0.
+//
+// A launch that renders many frames (frames_kernel, rm_kernels.hip) has one result per FRAME: every frame owns a block of
+// its own, RmFrameDiagBlock -- the same scheme with RM_FRAME_DIAG_SLOTS slots (a small frame is a few hundred waves; 1 152
+// bytes per frame, so thousands of frames stay in the megabytes) and its own completion count, so the last wave OF A FRAME
+// writes that frame's 32 bytes and re-zeroes that frame's block.  The waves of a frame touch no other frame's block, so the
+// ordering argument above holds per frame unchanged.
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime.h>
@@ -34,12 +40,23 @@ struct RmDiagBlock {
     unsigned int pad[31];
 };
 
+#define RM_FRAME_DIAG_SLOTS 8
+struct RmFrameDiagBlock {
+    RmDiagSlot slot[RM_FRAME_DIAG_SLOTS];
+    unsigned int slots_done;
+    unsigned int pad[31];
+};
+
 namespace rmd {
+
+template <typename BLK>
+constexpr unsigned int diag_slots() { return static_cast<unsigned int>(sizeof(BLK::slot) / sizeof(RmDiagSlot)); }
 
 // The launch's last wave (all 64 lanes): every slot is complete.  Lanes read slots lane, lane + 64, ..., zero them, and a
 // wave reduction gives the result.  Out of line: it runs once per launch, and inlined into the render kernels its
 // unrolled loads raised their register need (40 spilled VGPRs in the headline instantiation).
-__device__ __forceinline__ void diag_finalise_body(RmDiagBlock *blk, RmDiagDevice *out, unsigned int *tile_counters, unsigned int nslots) {
+template <typename BLK>
+__device__ __forceinline__ void diag_finalise_body(BLK *blk, RmDiagDevice *out, unsigned int *tile_counters, unsigned int nslots) {
     const unsigned int lane = __lane_id();
     unsigned long long ts = 0, ti = 0;
     unsigned int mxa = 0, mia = 0;
@@ -77,7 +94,8 @@ __device__ __forceinline__ void diag_finalise_body(RmDiagBlock *blk, RmDiagDevic
     if (tile_counters) __hip_atomic_store(&tile_counters[lane * 64u], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // the v2 kernels' 64 queue heads, 256 bytes apart (RM_QSTRIDE)
 }
 
-__device__ __attribute__((noinline)) static void diag_finalise(RmDiagBlock *blk, RmDiagDevice *out, unsigned int *tile_counters,
+template <typename BLK>
+__device__ __attribute__((noinline)) static void diag_finalise(BLK *blk, RmDiagDevice *out, unsigned int *tile_counters,
                                                                unsigned int nslots) {
     diag_finalise_body(blk, out, tile_counters, nslots);
 }
@@ -86,13 +104,14 @@ __device__ __attribute__((noinline)) static void diag_finalise(RmDiagBlock *blk,
 // would need a stack frame.
 // Called by EVERY lane of EVERY wave of the launch, all 64 lanes active, exactly once; (sdf, iters, mx, mn_inv) are the
 // wave's totals (wave-uniform), `unit` numbers the launch's waves 0 .. units - 1.
-template <bool FINAL_INLINE = false>
-__device__ __forceinline__ void diag_flush_wave(RmDiagBlock *blk, RmDiagDevice *out, unsigned int *tile_counters,
+template <bool FINAL_INLINE = false, typename BLK = RmDiagBlock>
+__device__ __forceinline__ void diag_flush_wave(BLK *blk, RmDiagDevice *out, unsigned int *tile_counters,
                                                 unsigned long long sdf, unsigned long long iters, unsigned int mx,
                                                 unsigned int mn_inv, unsigned int unit, unsigned int units, int lane) {
-    const unsigned int s = unit % RM_DIAG_SLOTS;
-    const unsigned int expected = units / RM_DIAG_SLOTS + (s < units % RM_DIAG_SLOTS ? 1u : 0u);
-    const unsigned int nslots = units < RM_DIAG_SLOTS ? units : static_cast<unsigned int>(RM_DIAG_SLOTS);
+    constexpr unsigned int SLOTS = diag_slots<BLK>();
+    const unsigned int s = unit % SLOTS;
+    const unsigned int expected = units / SLOTS + (s < units % SLOTS ? 1u : 0u);
+    const unsigned int nslots = units < SLOTS ? units : SLOTS;
     RmDiagSlot *sl = &blk->slot[s];
     unsigned int last = 0;
     if (lane == 0) {

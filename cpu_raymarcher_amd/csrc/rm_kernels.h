@@ -76,6 +76,15 @@ hipError_t rm_launch_query_sqrt(const RmRenderParams &p, bool pick, const float 
                                 const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
                                 hipStream_t stream, const char **kernel_name);
 
+// rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
+// origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics
+// (acc non-null) accumulated in blocks[k] (zero before and after the launch) and written to acc[k].  One launch of
+// frames_kernel; frames without a pixel: the neutral elements to acc[0 .. n_views).
+hipError_t rm_launch_frames(const RmRenderParams &p, const RmFrameView *views, int32_t n_views, RmFrameDiagBlock *blocks, RmDiagDevice *acc,
+                            hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_frames_sqrt(const RmRenderParams &p, const RmFrameView *views, int32_t n_views, RmFrameDiagBlock *blocks, RmDiagDevice *acc,
+                                 hipStream_t stream, const char **kernel_name);
+
 // v2: builds the longest-first item order of the next launch from the previous launch's recorded costs (rm_render_v2.hip)
 hipError_t rm_launch_lpt_sort(const uint8_t *cost_prev, uint16_t *perm, int stride, int tiles_x, int tiles_y, hipStream_t stream);
 

@@ -58,7 +58,10 @@ using namespace rmd;
 // lanes on one address would be 64 serial read-modify-writes) and flushed by the wave.  Reached by EVERY lane of every wave
 // of the launch (no early return above it), all 64 lanes active.  Out of line, plain arguments: the lean octree kernel
 // lives on exactly 64 VGPRs, and inlined this epilogue cost it two spills.
-__device__ __attribute__((noinline)) static void v1_diag_flush(RmDiagBlock *blk, RmDiagDevice *out, bool has_pixel, uint32_t c16, uint32_t i16) {
+// BLK: the launch's block (RmDiagBlock) or, in a launch of many frames, the block of this workgroup's frame (RmFrameDiagBlock):
+// the waves are numbered within blockIdx.x either way -- frames_kernel numbers the frame in blockIdx.y.
+template <typename BLK>
+__device__ __attribute__((noinline)) static void v1_diag_flush(BLK *blk, RmDiagDevice *out, bool has_pixel, uint32_t c16, uint32_t i16) {
     __shared__ unsigned int v1_diag_s[4][4][8];
     const int lane = static_cast<int>(__lane_id());
     const int wave = __builtin_amdgcn_readfirstlane(static_cast<int>(threadIdx.x >> 6));
@@ -82,8 +85,9 @@ __device__ __attribute__((noinline)) static void v1_diag_flush(RmDiagBlock *blk,
     const unsigned int wpw = blockDim.x >> 6;
     diag_flush_wave<true>(blk, out, nullptr, ts, ti, mx, mi, blockIdx.x * wpw + static_cast<unsigned int>(wave), gridDim.x * wpw, lane);
 }
-__device__ __forceinline__ void v1_diag_epilogue(const RmRenderParams &P, bool has_pixel, uint32_t c16, uint32_t i16) {
-    if (P.diag_block) v1_diag_flush(P.diag_block, P.diag_out, has_pixel, c16, i16);
+template <typename BLK>
+__device__ __forceinline__ void v1_diag_epilogue(BLK *blk, RmDiagDevice *out, bool has_pixel, uint32_t c16, uint32_t i16) {
+    if (blk) v1_diag_flush(blk, out, has_pixel, c16, i16);
 }
 
 // ------------------------------------------------------------------ Scene.getDistance
@@ -940,13 +944,14 @@ __global__ __launch_bounds__(64, 8) void render_kernel_oct(const RmRenderParams 
         }
     }
     if (in_frame) store_pixel(P, static_cast<size_t>(row) * P.width + x, t, nx, ny, nz, counters >> 16, counters & 0xFFFFu);
-    v1_diag_epilogue(P, in_frame, counters >> 16, counters & 0xFFFFu);
+    v1_diag_epilogue(P.diag_block, P.diag_out, in_frame, counters >> 16, counters & 0xFFFFu);
 }
 
 #endif  // !RM_RTC
 
-template <int ACCEL, bool OTHER, int GEN>
-__device__ __forceinline__ void render_body(const RmRenderParams &P) {
+// diag: where the diagnostics of this workgroup's pixels are accumulated (null: nowhere), result to P.diag_out
+template <int ACCEL, bool OTHER, int GEN, typename BLK>
+__device__ __forceinline__ void render_body(const RmRenderParams &P, BLK *diag) {
     // wave tile: tile_w x (64 / tile_w); the waves of a workgroup (blockDim / 64: option `v1_block`) stacked vertically
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int tw = P.tile_w, th = 64 / tw;
@@ -1004,7 +1009,7 @@ __device__ __forceinline__ void render_body(const RmRenderParams &P) {
     if (P.iters) P.iters[idx] = i16;
     if (P.rgba) reinterpret_cast<uchar4 *>(P.rgba)[idx] = shade_pixel(P.shader, db, nb[0], nb[1], nb[2], c16, i16, P.light_d);
     }
-    v1_diag_epilogue(P, in_frame, c16, i16);
+    v1_diag_epilogue(diag, P.diag_out, in_frame, c16, i16);
 }
 
 template <int ACCEL, int GEN>
@@ -1019,14 +1024,53 @@ __device__ __forceinline__ void distance_body(const RmRenderParams &P, const flo
 
 #ifdef RM_RTC
 }  // namespace
-extern "C" __global__ __launch_bounds__(256) void rm_rtc_render(const RmRenderParams P) { render_body<RM_RTC_ACCEL, RM_RTC_OTHER != 0, 4>(P); }
+extern "C" __global__ __launch_bounds__(256) void rm_rtc_render(const RmRenderParams P) { render_body<RM_RTC_ACCEL, RM_RTC_OTHER != 0, 4>(P, P.diag_block); }
 extern "C" __global__ __launch_bounds__(256) void rm_rtc_distance(const RmRenderParams P, const float *pts, int64_t n, double *dist, uint32_t *count) {
     distance_body<RM_RTC_ACCEL, 4>(P, pts, n, dist, count);
 }
 #else
 template <int ACCEL, bool OTHER, int GEN>
 __global__ __launch_bounds__(256) void render_kernel(const RmRenderParams P) {
-    render_body<ACCEL, OTHER, GEN>(P);
+    render_body<ACCEL, OTHER, GEN>(P, P.diag_block);
+}
+
+// ------------------------------------------------------------------ many frames of one scene in one launch
+//
+// rm_render_frames_device: blockIdx.y numbers the frame, blockIdx.x the frame's tiles exactly as render_kernel's does.  What a
+// frame has of its own -- camera, time, where its pixels and its diagnostics go -- is taken from views[blockIdx.y] and written
+// over a copy of the parameter block; everything else is the launch's.  blockIdx.y is the same for every lane, the table is
+// read before the kernel stores anything and each word passes through readfirstlane, so the frame's state lives in scalar
+// registers like the parameter block it replaces (no per-lane camera loads; the copy itself dissolves into registers).
+__device__ __forceinline__ float frame_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
+__device__ __forceinline__ double frame_uniform(double v) {
+    const long long b = __double_as_longlong(v);
+    const unsigned int lo = static_cast<unsigned int>(__builtin_amdgcn_readfirstlane(static_cast<int>(b)));
+    const unsigned int hi = static_cast<unsigned int>(__builtin_amdgcn_readfirstlane(static_cast<int>(b >> 32)));
+    return __longlong_as_double(static_cast<long long>((static_cast<unsigned long long>(hi) << 32) | lo));
+}
+
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void frames_kernel(const RmRenderParams P, const RmFrameView *__restrict__ views, RmFrameDiagBlock *blocks,
+                                                     RmDiagDevice *acc) {
+    const unsigned int f = blockIdx.y;
+    const RmFrameView *V = views + f;
+    RmRenderParams Q = P;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) Q.rot[k] = frame_uniform(V->rot[k]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        Q.origin[k] = frame_uniform(V->origin[k]);
+        Q.origin_d[k] = frame_uniform(V->origin_d[k]);
+    }
+    Q.time = frame_uniform(V->time);
+    const size_t first = static_cast<size_t>(f) * (static_cast<size_t>(P.width) * static_cast<size_t>(P.local_rows));  // the frame's first pixel
+    if (P.depth) Q.depth = P.depth + first;
+    if (P.normal) Q.normal = P.normal + 3 * first;
+    if (P.sdf) Q.sdf = P.sdf + first;
+    if (P.iters) Q.iters = P.iters + first;
+    if (P.rgba) Q.rgba = P.rgba + 4 * first;
+    Q.diag_out = acc ? acc + f : nullptr;
+    render_body<ACCEL, OTHER, GEN>(Q, blocks ? blocks + f : nullptr);
 }
 
 #ifndef RM_LENGTH_SQRT  // scene-independent kernels exist once (this file is compiled a second time with -DRM_LENGTH_SQRT)
@@ -1147,6 +1191,16 @@ __global__ void reduce_init_kernel(RmDiagDevice *acc) {
     acc->pad = 0;
 }
 
+// rm_render_frames_device for frames without a pixel: the neutral elements for all n accumulators (there is no render launch)
+__global__ __launch_bounds__(256) void frames_neutral_kernel(RmDiagDevice *acc, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    acc[i].total_sdf = 0;
+    acc[i].total_iters = 0;
+    acc[i].max_sdf = 0;
+    acc[i].min_sdf = 0xFFFFFFFFu;
+    acc[i].pad = 0;
+}
 #endif  // !RM_LENGTH_SQRT
 
 template <int ACCEL, int GEN>
@@ -1451,6 +1505,46 @@ hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t
         if (kernel_name) *kernel_name = "render_kernel_oct" RM_LEN_TAG;
     } else RM_DISPATCH(RM_V1)
 #undef RM_V1
+    return hipGetLastError();
+}
+
+// n_views frames of rows [y_start, y_end) in one launch: the grid of a one-ray-per-lane render launch (tile_w, v1_block) in x, the
+// frame in y (n_views <= 65535).  Ahead-of-time kernels only, the general ones (no lean octree kernel: its table is per camera).
+hipError_t RM_LEN_VARIANT(rm_launch_frames)(const RmRenderParams &p, const RmFrameView *views, int32_t n_views, RmFrameDiagBlock *blocks,
+                                            RmDiagDevice *acc, hipStream_t stream, const char **kernel_name) {
+    const int rows = p.local_rows;
+    if (kernel_name) *kernel_name = "";
+    if (n_views <= 0) return hipSuccess;
+    if (rows <= 0 || p.width <= 0) {
+#ifdef RM_LENGTH_SQRT
+        return rm_launch_frames(p, views, n_views, blocks, acc, stream, kernel_name);
+#else
+        if (acc) hipLaunchKernelGGL(frames_neutral_kernel, dim3(static_cast<unsigned>((n_views + 255) / 256)), dim3(256), 0, stream, acc, n_views);
+        return hipGetLastError();
+#endif
+    }
+    const int tw = p.tile_w, th = 64 / tw;
+    const int wpw = p.v1_block >= 256 ? 4 : (p.v1_block >= 128 ? 2 : 1);
+    const int threads = 64 * wpw;
+    const int tiles_x = (p.width + tw - 1) / tw;
+    const int tiles_y = (rows + wpw * th - 1) / (wpw * th);
+    const dim3 grid((static_cast<unsigned>(tiles_x) * static_cast<unsigned>(tiles_y) + 63u) & ~63u, static_cast<unsigned>(n_views)),
+        block(static_cast<unsigned>(threads));  // x: v1_tile_of_block
+    const V1Lds lds = v1_lds_layout(p, threads, true);
+    const size_t shmem = lds.bytes;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.oct_frame = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    pl.v1_list_offset = lds.v1_list_offset;
+#define RM_FK(A, O, G)                                                                                   \
+    {                                                                                                    \
+        hipLaunchKernelGGL((frames_kernel<A, O, G>), grid, block, shmem, stream, pl, views, blocks, acc); \
+        if (kernel_name) *kernel_name = RM_KERNEL_NAME(frames_kernel, A, O, G);                          \
+    }
+    RM_DISPATCH(RM_FK)
+#undef RM_FK
     return hipGetLastError();
 }
 

@@ -1209,9 +1209,13 @@ bool leaf_objects(const HostScene &s, std::vector<RmInstr> &prog, std::vector<in
     return true;
 }
 
-void camera_from_angles(double pitch, double yaw, float rot9[9], float origin3[3]) {
+double clamp_pitch(double pitch) {
     const double half_pi = 3.141592653589793 / 2;
-    const double p = js_min2(js_max2(pitch, -half_pi), half_pi);  // camera.ts:59
+    return js_min2(js_max2(pitch, -half_pi), half_pi);
+}
+
+void camera_from_angles(double pitch, double yaw, float rot9[9], float origin3[3]) {
+    const double p = clamp_pitch(pitch);  // camera.ts:59
     const Mat4 orbit = rotate_x(rotate_y(Mat4::identity(), yaw), p);  // camera.ts:83-84
     const float back[3] = {0.0f, 0.0f, 3.0f};                       // camera.ts:13,86
     const Mat4 cam = translate(orbit, back);

@@ -129,6 +129,8 @@ void scale_transform(float m[16], double x, double y, double z);
 
 // camera.ts:58-69,81-88 + raymarcher.ts:62-67
 void camera_from_angles(double pitch, double yaw, float rot9[9], float origin3[3]);
+// Math.min(Math.max(pitch, -Math.PI / 2), Math.PI / 2) (camera.ts:29,59) for a finite pitch
+double clamp_pitch(double pitch);
 
 // phongModel.ts:15-16
 void phong_light_dir(float out[3]);

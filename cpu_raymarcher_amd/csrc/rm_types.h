@@ -115,7 +115,17 @@ struct RmInstr {
 #define RM_EPSILON 0.001
 
 struct RmDiagBlock;   // rm_diag.h
+struct RmFrameDiagBlock;
 struct RmDiagDevice;  // rm_kernels.h
+
+// What one frame of a launch of many frames (frames_kernel) has of its own: RmRenderParams::rot, origin, origin_d and time of
+// that frame, built on the host like the parameter block's (80 bytes; read with scalar loads).
+struct RmFrameView {
+    float rot[9];
+    float origin[3];
+    double origin_d[3];
+    double time;
+};
 
 // Kernel parameters (passed by value).
 struct RmRenderParams {

@@ -311,6 +311,56 @@ RM_API int rm_render_tile_device(rm_ctx *ctx, const rm_job *job, int32_t shader,
                                  void *d_normal, void *d_sdf, void *d_iters, void *d_rgba,
                                  void *stream);
 
+/* ---- many frames of one scene in one launch ----------------------------------------- */
+
+/* What one frame of rm_render_frames_device has of its own: Job.camera.pitch / .yaw and Job.time. */
+typedef struct rm_view { double camera_pitch, camera_yaw, time; } rm_view;
+
+/* n_views frames of ONE scene in ONE launch: a yaw sweep with its metric series (main.ts:438-441,550-566), an animated
+ * scene over time, an orbit of thumbnails -- consumers of a sequence of small frames, which rendered one call at a time pay a
+ * launch, a parameter block and a host round trip per frame and cannot fill the GPU (a 256 x 256 frame is 1 024 waves).
+ *   job     everything the frames share -- width, height, rows [y_start, y_end), algorithm, scene / preset, acceleration
+ *           structure, overshoot, step size -- defaulted, clamped and checked exactly as rm_render_tile_device does.  Its own
+ *           camera_pitch, camera_yaw and time are ignored.
+ *   views   host memory, copied: views[k] gives frame k its pitch (clamped per view, camera.ts:59), yaw and time.  The cameras
+ *           are built on the host by the code behind rm_camera_from_angles.
+ * Frame k is bit for bit what rm_render_tile_device writes for the same job with views[k]'s three fields; with
+ * h = max(0, y_end - y_start) it occupies elements [k * W * h, (k + 1) * W * h) of each buffer (x3 normal, x4 rgba).  Each of
+ * the five pixel buffers may be NULL; with d_rgba the shader is fused and still sees the G-buffers.
+ *   d_acc   NULL, or n_views accumulators of 32 bytes (the layout of rm_reduce_counters_enqueue, 8-byte aligned): entry k
+ *           receives what rm_render_attach_diagnostics would leave for frame k -- sum / max / min of the stored sdfEval values
+ *           and the sum of the stored iteration values, Uint16Array wrap included -- written by the render launch itself (every
+ *           frame has its own accumulator slots and completion count, the last wave of a frame writes its entry): no
+ *           initialising launch, no second pass, no memset.  With all five pixel buffers NULL the call writes the metric
+ *           series and nothing else.  Frames without a pixel (h == 0 or W == 0): the neutral elements to every entry.
+ * Calls in flight: the per-frame view records and accumulator slots come from a ring in the context (4 096 frames) and stay a
+ * call's own until its launch is over; a call that would reuse entries of an earlier call, on whatever stream, first waits on
+ * the host for that call (batches of up to 2 048 frames never wait for the call just before them).  The first call with more
+ * than 4 096 views, and every later call with more than any before, replaces the ring: the device is synchronised, so THAT
+ * call is not asynchronous.
+ * Cost of d_acc: every wave of a frame ends with five device-scope atomics into one of the frame's 8 slots.  Sized for small
+ * frames (a 256 x 256 frame: 128 flushes per slot); a 4K frame has 16 200 per slot, which serialise on the slot's cache line
+ * (about a millisecond per frame): pass d_acc = NULL there, or use the single-frame entries.
+ * Not one of the render entries: it neither consumes nor fires rm_render_attach_diagnostics and leaves
+ * rm_scene_set_time's value alone.  Asynchronous on `stream` like the other device entries; rm_last_kernel names the
+ * frames_kernel<...> instantiation.  RM_E_INVALID for a null job, null views with n_views > 0, n_views < 0 or > 65535 (one
+ * grid dimension) or a non-finite angle or time -- checked before anything else; RM_E_NO_DEVICE on a host-only context;
+ * RM_E_NO_SCENE before any scene; n_views == 0 is RM_OK and launches nothing.
+ * Deliberately NOT used here: the v2 wave loop, the run-time compiled scene kernels, the lean octree kernel (its node table
+ * and the origin-relative boxes belong to ONE camera position) and striping.  Every scene is served by the ahead-of-time
+ * one-ray-per-lane kernels, which give the same bytes; options tile_w and v1_block apply.  Many small frames suit this
+ * entry; for 4K frames prefer single-frame calls in flight on several streams. */
+RM_API int rm_render_frames_device(rm_ctx *ctx, const rm_job *job, int32_t shader, const rm_view *views, int32_t n_views,
+                                   void *d_depth, void *d_normal, void *d_sdf, void *d_iters, void *d_rgba, void *d_acc,
+                                   void *stream);
+
+/* The views of a camera sweep, host-only, no ctx: views[0] = Camera.setAngles(pitch, yaw) (pitch clamped, camera.ts:58-62),
+ * views[k] = that state after k calls of Camera.rotateCamera(d_pitch, d_yaw) (camera.ts:26-31) -- sequential binary64
+ * additions (yaw_k = yaw_{k-1} + d_yaw, never k * d_yaw) with the pitch clamp at every step -- and time_k = time0 + k * d_time.
+ * RM_E_INVALID for a non-finite argument, n < 0 or null views with n > 0. */
+RM_API int rm_sweep_views(double pitch, double yaw, double d_pitch, double d_yaw, double time0, double d_time, int32_t n,
+                          rm_view *views);
+
 /* Multi-GPU sharding of one Job (replaces the contiguous ceil(H/N) split of main.ts:444-449
  * by a load-balanced one): the rows [y_start, y_end) are cut into stripes of `stripe_rows`
  * rows dealt round-robin over `n_parts`; this call renders, in ONE launch, the stripes of
