@@ -53,6 +53,21 @@ class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
 
+class rm_frame_set(C.Structure):  # include/rm_raymarch.h: struct rm_frame_set
+    _fields_ = [("depth", C.c_void_p), ("normal", C.c_void_p), ("sdf", C.c_void_p), ("iters", C.c_void_p)]
+
+
+class rm_compare_stats(C.Structure):  # include/rm_raymarch.h: struct rm_compare_stats
+    _fields_ = [(name, C.c_uint64) for name in (
+        "pixels", "sum_sdf_a", "sum_sdf_b", "sum_iters_a", "sum_iters_b", "sum_abs_depth", "surface_a", "surface_b",
+        "surface_only_a", "surface_only_b", "depth_differs", "normal_differs", "counters_differ", "b_cheaper", "a_cheaper")] + \
+        [("max_abs_depth", C.c_uint32), ("max_abs_normal", C.c_uint32)]
+
+
+# rm_compare_map by name
+COMPARE_MAPS = {"none": -1, "sdf": 0, "iters": 1, "depth": 2, "normal": 3, "surface": 4}
+
+
 class rm_scene_info(C.Structure):
     _fields_ = [("n_prims", C.c_int32), ("accel", C.c_int32), ("preset_index", C.c_int32),
                 ("bvh_nodes", C.c_int32), ("bvh_leaves", C.c_int32), ("bvh_depth", C.c_int32),
@@ -108,6 +123,10 @@ SIGNATURES = {
     "rm_render_tile": (C.c_int, [_VP, C.POINTER(rm_job), _VP, _VP, _VP, _VP]),
     "rm_render_tile_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_render_frames_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_compare_frames_device": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(rm_frame_set), C.POINTER(rm_frame_set),
+                                           C.c_int32, C.c_int32, _VP, _VP, _VP]),
+    "rm_compare_frames": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(rm_frame_set), C.POINTER(rm_frame_set),
+                                    C.c_int32, C.c_int32, _VP, _VP]),
     "rm_sweep_views": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _VP]),
     "rm_render_stripes_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            _VP, _VP, _VP, _VP, _VP, _VP]),

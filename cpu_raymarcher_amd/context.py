@@ -55,6 +55,30 @@ def _check_buffers(npx, bufs, need_device=None):
     return bool(on_dev)
 
 
+def _check_pixel_sets(npx, bufs, rgba, stats, stats_bytes):
+    """_check_buffers for compare_frames: bufs maps depth_a .. iters_b to buffers or None.  Returns True for device buffers."""
+    on_dev = None
+    for name, b in list(bufs.items()) + [("rgba", rgba)]:
+        if b is None:
+            continue
+        d = _check_buffers(npx, {name.split("_")[0]: b})
+        if on_dev is not None and on_dev != d:
+            raise ValueError("buffers must be all on the host or all on the device")
+        on_dev = d
+    if stats is not None:
+        d = bool(_is_torch(stats) and stats.is_cuda)
+        if not (_is_torch(stats) or isinstance(stats, np.ndarray)):
+            raise ValueError("stats must be a numpy array or a torch tensor")
+        contiguous = stats.is_contiguous() if _is_torch(stats) else stats.flags["C_CONTIGUOUS"]
+        nbytes = stats.numel() * stats.element_size() if _is_torch(stats) else stats.nbytes
+        if not contiguous or nbytes < stats_bytes:
+            raise ValueError("stats must be a contiguous buffer of 128 bytes per frame")
+        if on_dev is not None and on_dev != d:
+            raise ValueError("buffers must be all on the host or all on the device")
+        on_dev = d
+    return bool(on_dev)
+
+
 def _current_stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -310,6 +334,82 @@ class Context:
         N.check(self._h, N.lib().rm_render_frames_device(
             self._h, C.byref(job), int(shader), _ptr(v), n, _ptr(depth), _ptr(normal), _ptr(sdf), _ptr(iters), _ptr(rgba),
             _ptr(diag), _current_stream_ptr() if self.device >= 0 else None))  # (a host-only context: RM_E_NO_DEVICE from the library)
+
+    # ---- two renders of a view: difference image and statistics ------------------------
+    def compare_frames(self, a, b, rgba=None, map="sdf", gain=5, stats=None, width=0, rows=0, n_frames=1):
+        """B against A for n_frames frames of width x rows pixels (rm_compare_frames_device / rm_compare_frames).  a, b:
+        (depth, normal, sdf, iters), the n frames one behind the other as render_frames writes them; a pair may be None on
+        both sides (the fields derived from it are 0).  `map`: a name of COMPARE_MAPS ("none", "sdf", "iters", "depth",
+        "normal", "surface") or an rm_compare_map value -- the difference image written to `rgba` (4 bytes per pixel; None
+        only with "none"); `gain` 1 .. 255.  `stats`: None, or a buffer of 128 * n_frames bytes for one rm_compare_stats per
+        frame (decode_compare_stats).  torch CUDA tensors -> the device entry on torch's current stream (asynchronous); numpy
+        arrays -> the host entry (synchronous).  Neither rgba nor stats needs a pre-clear."""
+        if a is None or b is None:
+            a = b = None
+            sides = [None, None]
+        else:
+            if len(a) != 4 or len(b) != 4:
+                raise ValueError("a and b are (depth, normal, sdf, iters)")
+            sides = [N.rm_frame_set(*[getattr(_ptr(x), "value", None) for x in side]) for side in (a, b)]
+        m = N.COMPARE_MAPS[map] if isinstance(map, str) else int(map)
+        n = int(n_frames)
+        npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
+        bufs = {}
+        for side, tag in ((a, "_a"), (b, "_b")):
+            for name, x in zip(("depth", "normal", "sdf", "iters"), side or ()):
+                bufs[name + tag] = x
+        on_dev = _check_pixel_sets(npx, bufs, rgba, stats, 128 * max(0, n))
+        self._same_device(dict(bufs, rgba=rgba, stats=stats))
+        refs = [None if x is None else C.byref(x) for x in sides]
+        if on_dev:
+            N.check(self._h, N.lib().rm_compare_frames_device(self._h, int(width), int(rows), n, refs[0], refs[1], m, int(gain),
+                                                              _ptr(rgba), _ptr(stats), _current_stream_ptr()))
+        else:
+            N.check(self._h, N.lib().rm_compare_frames(self._h, int(width), int(rows), n, refs[0], refs[1], m, int(gain),
+                                                       _ptr(rgba), _ptr(stats)))
+
+    @staticmethod
+    def decode_compare_stats(buf):
+        """One dict per 128-byte rm_compare_stats record of `buf` (a CUDA tensor or a numpy array, compare_frames' stats)."""
+        raw = buf.cpu().contiguous().view(-1).numpy() if _is_torch(buf) else np.ascontiguousarray(buf).reshape(-1)
+        raw = raw.view(np.uint8)
+        out = []
+        for k in range(raw.size // 128):
+            rec = N.rm_compare_stats.from_buffer_copy(raw[128 * k:128 * (k + 1)].tobytes())
+            out.append({name: int(getattr(rec, name)) for name, _ in N.rm_compare_stats._fields_})
+        return out
+
+    def compare(self, job_a, job_b, views=None, shader=None, map="sdf", gain=5):
+        """Renders job_a and job_b into buffers of its own and compares them, B against A: returns (stats, rgba) -- a list of
+        one dict per frame and the difference image as a CUDA uint8 tensor [n, rows, width, 4].  `views` (as render_frames
+        takes them): that many frames per job through render_frames, else one frame through render_tile with each job's own
+        camera.  The jobs must agree in width, height, rows and scene; they may differ in algorithm, acceleration
+        structure, overshoot and step size.  `shader`: None, or the shading model the two renders also run -- the result is
+        then (stats, rgba, shaded_a, shaded_b)."""
+        import torch
+        for f in ("width", "height", "y_start", "y_end", "scene_preset_index"):
+            if getattr(job_a, f) != getattr(job_b, f):
+                raise ValueError("the jobs differ in %s" % f)
+        W, rows = max(0, job_a.width), max(0, job_a.y_end - job_a.y_start)
+        n = 1 if views is None else len(np.ascontiguousarray(views, dtype=np.float64).reshape(-1, 3))
+        dev, total = torch.device("cuda", self.device), W * rows * n
+        sets, shaded = [], []
+        for job in (job_a, job_b):
+            g = (torch.empty(total, dtype=torch.uint8, device=dev), torch.empty(3 * total, dtype=torch.uint8, device=dev),
+                 torch.empty(total, dtype=torch.int16, device=dev), torch.empty(total, dtype=torch.int16, device=dev))
+            img = None if shader is None else torch.empty(4 * total, dtype=torch.uint8, device=dev)
+            if views is None:
+                self.render_tile(job, *g, rgba=img, shader=shader or 0)
+            else:
+                self.render_frames(job, views, *g, rgba=img, shader=shader or 0)
+            sets.append(g)
+            shaded.append(img)
+        m = N.COMPARE_MAPS[map] if isinstance(map, str) else int(map)
+        rgba = None if m < 0 else torch.empty(4 * total, dtype=torch.uint8, device=dev)
+        stats = torch.empty(128 * n, dtype=torch.uint8, device=dev)
+        self.compare_frames(sets[0], sets[1], rgba=rgba, map=m, gain=gain, stats=stats, width=W, rows=rows, n_frames=n)
+        out = (self.decode_compare_stats(stats), None if rgba is None else rgba.view(n, rows, W, 4))
+        return out if shader is None else out + tuple(x.view(n, rows, W, 4) for x in shaded)
 
     def _same_device(self, bufs):
         for name, b in bufs.items():

@@ -78,58 +78,26 @@ struct LaunchSlots {
     RmDiagBlock *take_block() { return blocks ? blocks + block_slot++ % kLaunches : nullptr; }
 };
 
-// The ring of rm_render_frames_device: per frame of a call one RmFrameView (the frame's camera and time; written by the host
-// into a pinned mirror and copied on the call's stream) and one RmFrameDiagBlock (rm_diag.h; zeroed when allocated, left zeroed
-// by the last wave of its frame).
-//  - A call takes n consecutive entries, from the start again when the end is too near, and records an event behind its
-//    launch (launched).  The entries stay that call's -- mirror, table and blocks alike -- until the event has completed:
-//    take() waits for the event of every earlier call whose entries overlap the ones it hands out, whatever stream that call
-//    ran on, so neither the host (writing the mirror) nor a later launch (adding into the blocks) meets a call in flight.  A
-//    call without an event (none to be had, or its launch failed) has its stream synchronised instead.
-//  - Batches of up to half the ring therefore never wait for the call just before them; larger ones do.
-//  - Allocated at the first call, kFrames entries (5 MB).  A call of more frames replaces the ring by one that holds exactly
-//    it: the device is synchronised first (nothing in flight reads the old ring), so that one call is not asynchronous.
-struct FrameRing {
-    static constexpr size_t kFrames = 4096;
+// Who owns which entries of a ring that calls in flight share (FrameRing, CompareRing).  A call takes n consecutive entries, from
+// the start again when the end is too near, and records an event behind its launch (launched).  The entries stay that call's
+// until the event has completed: take() waits for the event of every earlier call whose entries overlap the ones it hands out,
+// whatever stream that call ran on.  A call without an event (none to be had, or its launch failed) has its stream
+// synchronised instead.  Batches of up to half the ring therefore never wait for the call just before them; larger ones do.
+struct RingClaims {
     struct Claim {
         size_t first, n;
         hipEvent_t done;
     };
-    RmFrameView *host = nullptr, *dev = nullptr;
-    RmFrameDiagBlock *blocks = nullptr;
-    size_t cap = 0, next = 0;
+    size_t next = 0;
     std::vector<Claim> claims;  // calls whose event has not been waited for yet
 
     void retire_all() {  // (the device is idle)
         for (Claim &c : claims) (void)hipEventDestroy(c.done);
         claims.clear();
+        next = 0;
     }
-    void release() {
-        retire_all();
-        (void)hipHostFree(host);
-        (void)hipFree(dev);
-        (void)hipFree(blocks);
-        host = dev = nullptr;
-        blocks = nullptr;
-        cap = next = 0;
-    }
-    // first entry of n consecutive ones that no call in flight owns
-    hipError_t take(size_t n, size_t *first) {
-        if (n > cap) {
-            hipError_t e = hipDeviceSynchronize();
-            if (e != hipSuccess) return e;
-            release();
-            const size_t want = n > kFrames ? n : kFrames;
-            e = hipHostMalloc(reinterpret_cast<void **>(&host), want * sizeof(RmFrameView), hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dev), want * sizeof(RmFrameView));
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&blocks), want * sizeof(RmFrameDiagBlock));
-            if (e == hipSuccess) e = hipMemset(blocks, 0, want * sizeof(RmFrameDiagBlock));
-            if (e != hipSuccess) {
-                release();
-                return e;
-            }
-            cap = want;
-        }
+    // first entry of n <= cap consecutive ones that no call in flight owns
+    hipError_t take(size_t n, size_t cap, size_t *first) {
         if (next + n > cap) next = 0;
         const size_t lo = next, hi = next + n;
         for (size_t k = 0; k < claims.size();) {
@@ -155,6 +123,85 @@ struct FrameRing {
         if (ev) (void)hipEventDestroy(ev);
         (void)hipStreamSynchronize(stream);
     }
+};
+
+// The ring of rm_render_frames_device: per frame of a call one RmFrameView (the frame's camera and time; written by the host
+// into a pinned mirror and copied on the call's stream) and one RmFrameDiagBlock (rm_diag.h; zeroed when allocated, left zeroed
+// by the last wave of its frame).
+//  - Entries are owned as RingClaims says -- mirror, table and blocks alike -- so neither the host (writing the mirror) nor a
+//    later launch (adding into the blocks) meets a call in flight.
+//  - Allocated at the first call, kFrames entries (5 MB).  A call of more frames replaces the ring by one that holds exactly
+//    it: the device is synchronised first (nothing in flight reads the old ring), so that one call is not asynchronous.
+struct FrameRing {
+    static constexpr size_t kFrames = 4096;
+    RmFrameView *host = nullptr, *dev = nullptr;
+    RmFrameDiagBlock *blocks = nullptr;
+    size_t cap = 0;
+    RingClaims owners;
+
+    void release() {
+        owners.retire_all();
+        (void)hipHostFree(host);
+        (void)hipFree(dev);
+        (void)hipFree(blocks);
+        host = dev = nullptr;
+        blocks = nullptr;
+        cap = 0;
+    }
+    hipError_t take(size_t n, size_t *first) {
+        if (n > cap) {
+            hipError_t e = hipDeviceSynchronize();
+            if (e != hipSuccess) return e;
+            release();
+            const size_t want = n > kFrames ? n : kFrames;
+            e = hipHostMalloc(reinterpret_cast<void **>(&host), want * sizeof(RmFrameView), hipHostMallocDefault);
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&dev), want * sizeof(RmFrameView));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&blocks), want * sizeof(RmFrameDiagBlock));
+            if (e == hipSuccess) e = hipMemset(blocks, 0, want * sizeof(RmFrameDiagBlock));
+            if (e != hipSuccess) {
+                release();
+                return e;
+            }
+            cap = want;
+        }
+        return owners.take(n, cap, first);
+    }
+    void launched(size_t first, size_t n, hipStream_t stream) { owners.launched(first, n, stream); }
+};
+
+// The ring of rm_compare_frames_device: what the workgroups of a frame hand to the one that writes the frame's record
+// (compare_kernel, rm_frame_ops.hip) -- one RmComparePartial per workgroup and, at the index of the frame's first workgroup, the
+// frame's ticket counter (zeroed when allocated, left at zero by the workgroup that took the last ticket; partial records are
+// overwritten whole, never cleared).  Only frames of more than one workgroup use it, and a launch has at most 2 048 workgroups
+// in such frames (rm_compare_blocks_per_frame): kEntries is never too small.  Allocated at the first call that needs it (544 KB);
+// entries are owned as RingClaims says.
+struct CompareRing {
+    static constexpr size_t kEntries = 4096;
+    RmComparePartial *partials = nullptr;
+    unsigned int *counters = nullptr;
+    RingClaims owners;
+
+    void release() {
+        owners.retire_all();
+        (void)hipFree(partials);
+        (void)hipFree(counters);
+        partials = nullptr;
+        counters = nullptr;
+    }
+    hipError_t take(size_t n, size_t *first) {
+        if (n > kEntries) return hipErrorInvalidValue;
+        if (!partials) {
+            hipError_t e = hipMalloc(reinterpret_cast<void **>(&partials), kEntries * sizeof(RmComparePartial));
+            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&counters), kEntries * sizeof(unsigned int));
+            if (e == hipSuccess) e = hipMemset(counters, 0, kEntries * sizeof(unsigned int));
+            if (e != hipSuccess) {
+                release();
+                return e;
+            }
+        }
+        return owners.take(n, kEntries, first);
+    }
+    void launched(size_t first, size_t n, hipStream_t stream) { owners.launched(first, n, stream); }
 };
 
 // The LPT ring (option `lpt`; rm_render_v2.hip, lpt_sort_kernel): a v2 launch sorts its items longest-first from the costs the
@@ -360,6 +407,7 @@ struct rm_ctx {
     LptRing lpt;
     OctTableRing oct_tables;
     FrameRing frames;         // rm_render_frames_device
+    CompareRing compare;      // rm_compare_frames_device
     unsigned long long scene_gen = 0;  // bumped by every upload_scene
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
@@ -1110,6 +1158,34 @@ int render_device(rm_ctx *ctx, const rm_job *job, int32_t shader, const Stripes 
     return RM_OK;
 }
 
+static_assert(sizeof(rm_compare_stats) == 128 && sizeof(RmCompareStats) == sizeof(rm_compare_stats) && sizeof(RmComparePartial) == 128,
+              "compare_kernel writes rm_compare_stats records");
+static_assert(RM_CMP_MAP_NONE == RM_CMP_NONE && RM_CMP_MAP_SDF == RM_CMP_SDF && RM_CMP_MAP_ITERS == RM_CMP_ITERS &&
+              RM_CMP_MAP_DEPTH == RM_CMP_DEPTH && RM_CMP_MAP_NORMAL == RM_CMP_NORMAL && RM_CMP_MAP_SURFACE == RM_CMP_SURFACE,
+              "compare_kernel's maps are rm_compare_map's");
+
+// the checks both forms of rm_compare_frames make, ahead of the device check (the order of checks is behaviour)
+int check_compare(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b, int32_t map,
+                  int32_t gain, const void *rgba, const void *stats) {
+    if (!a || !b) return fail(ctx, RM_E_INVALID, "null frame set");
+    if (width < 0 || rows < 0 || n_frames < 0) return fail(ctx, RM_E_INVALID, "negative size");
+    if (n_frames > 65535) return fail(ctx, RM_E_INVALID, "n_frames must be in [0, 65535] (one grid dimension)");
+    if (!a->depth != !b->depth || !a->normal != !b->normal || !a->sdf != !b->sdf || !a->iters != !b->iters)
+        return fail(ctx, RM_E_INVALID, "a buffer given on one side only");
+    if (map < RM_CMP_MAP_NONE || map > RM_CMP_MAP_SURFACE) return fail(ctx, RM_E_INVALID, "unknown map");
+    const void *of_map[] = {a->sdf, a->iters, a->depth, a->normal, a->normal};
+    if (map != RM_CMP_MAP_NONE) {
+        if (!of_map[map]) return fail(ctx, RM_E_INVALID, "the map's buffer is absent");
+        if (gain < 1 || gain > 255) return fail(ctx, RM_E_INVALID, "gain must be in [1, 255]");
+        if (!rgba) return fail(ctx, RM_E_INVALID, "a map needs an image buffer");
+    }
+    for (const void *p : {a->sdf, b->sdf, a->iters, b->iters})
+        if (reinterpret_cast<uintptr_t>(p) & 1) return fail(ctx, RM_E_INVALID, "the counters must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(stats) & 7) return fail(ctx, RM_E_INVALID, "the records must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU compare path");
+    return RM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1164,6 +1240,7 @@ void rm_destroy(rm_ctx *ctx) {
         ctx->lpt.release();
         ctx->oct_tables.release();
         ctx->frames.release();
+        ctx->compare.release();
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -1354,6 +1431,85 @@ int rm_render_frames_device(rm_ctx *ctx, const rm_job *job, int32_t shader, cons
                                                                          &ctx->last_kernel);
     if (!empty) ctx->frames.launched(first, static_cast<size_t>(n_views), hs);  // (also behind a failed attempt: the copy may be queued)
     if (e != hipSuccess) return hip_fail(ctx, e, "rm_render_frames_device");
+    return RM_OK;
+}
+
+int rm_compare_frames_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b,
+                             int32_t map, int32_t gain, void *d_rgba, void *d_stats, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_compare(ctx, width, rows, n_frames, a, b, map, gain, d_rgba, d_stats);
+    if (rc || n_frames == 0) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    const int64_t npx = static_cast<int64_t>(width) * rows;
+    if (npx == 0) {  // frames without a pixel: all-zero records, no image byte
+        if (d_stats) RM_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(rm_compare_stats) * static_cast<size_t>(n_frames), hs));
+        return RM_OK;
+    }
+    RmCompareArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.depth_a = static_cast<const uint8_t *>(a->depth);
+    args.depth_b = static_cast<const uint8_t *>(b->depth);
+    args.normal_a = static_cast<const uint8_t *>(a->normal);
+    args.normal_b = static_cast<const uint8_t *>(b->normal);
+    args.sdf_a = static_cast<const uint16_t *>(a->sdf);
+    args.sdf_b = static_cast<const uint16_t *>(b->sdf);
+    args.iters_a = static_cast<const uint16_t *>(a->iters);
+    args.iters_b = static_cast<const uint16_t *>(b->iters);
+    args.rgba = map == RM_CMP_MAP_NONE ? nullptr : static_cast<uint8_t *>(d_rgba);
+    args.stats = static_cast<RmCompareStats *>(d_stats);
+    args.npx = npx;
+    args.gain = static_cast<unsigned int>(map == RM_CMP_MAP_NONE ? 1 : gain);
+    const int32_t per_frame = rm_compare_blocks_per_frame(npx, n_frames);
+    // frames of several workgroups combine their partial records through the context's ring
+    const size_t entries = d_stats && per_frame > 1 ? static_cast<size_t>(per_frame) * static_cast<size_t>(n_frames) : 0;
+    size_t first = 0;
+    if (entries) {
+        RM_HIP(ctx, ctx->compare.take(entries, &first));
+        args.partials = ctx->compare.partials + first;
+        args.counters = ctx->compare.counters + first;
+    }
+    const hipError_t e = rm_launch_compare(args, map, n_frames, per_frame, hs, &ctx->last_kernel);
+    if (entries) ctx->compare.launched(first, entries, hs);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_compare_frames_device");
+    return RM_OK;
+}
+
+int rm_compare_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b, int32_t map,
+                      int32_t gain, uint8_t *rgba, rm_compare_stats *stats) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_compare(ctx, width, rows, n_frames, a, b, map, gain, rgba, stats);
+    if (rc) return rc;
+    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
+    if (!total) {
+        if (stats && n) std::memset(stats, 0, sizeof(rm_compare_stats) * n);
+        return RM_OK;
+    }
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const void *host[2][4] = {{a->depth, a->normal, a->sdf, a->iters}, {b->depth, b->normal, b->sdf, b->iters}};
+    const size_t bpp[4] = {1, 3, 2, 2};
+    size_t at[2][4];
+    for (int side = 0; side < 2; ++side)
+        for (int k = 0; k < 4; ++k) at[side][k] = st.region(host[side][k] ? bpp[k] * total : 0);
+    const bool image = map != RM_CMP_MAP_NONE;
+    const size_t o_rgba = st.region(image ? 4 * total : 0), o_stats = st.region(stats ? sizeof(rm_compare_stats) * n : 0);
+    if ((rc = st.reserve())) return rc;
+    rm_frame_set dev[2];
+    for (int side = 0; side < 2; ++side) {
+        const void *d[4];
+        for (int k = 0; k < 4; ++k) {
+            d[k] = host[side][k] ? st.at<void>(at[side][k]) : nullptr;
+            if (host[side][k]) RM_HIP(ctx, st.in(at[side][k], host[side][k], bpp[k] * total));
+        }
+        dev[side] = rm_frame_set{d[0], d[1], d[2], d[3]};
+    }
+    rc = rm_compare_frames_device(ctx, width, rows, n_frames, &dev[0], &dev[1], map, gain, image ? st.at<void>(o_rgba) : nullptr,
+                                  stats ? st.at<void>(o_stats) : nullptr, ctx->stream);
+    if (rc) return rc;
+    if (image) RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
+    if (stats) RM_HIP(ctx, st.out(stats, o_stats, sizeof(rm_compare_stats) * n));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 

@@ -64,6 +64,311 @@ __global__ __launch_bounds__(256) void assemble_kernel(const unsigned char *__re
     }
 }
 
+
+// ------------------------------------------------------------------ compare_kernel (rm_compare_frames_device)
+//
+// Two G-buffer sets of the same frames, B against A: the difference image of one of the four buffers (or of the G-buffer's
+// surface mask) and a 128-byte record of exact integer statistics per frame.  A per-pixel integer function plus a reduction:
+// HBM-bound (16 B read, 4 B written per pixel), so the shape is that of assemble_kernel and reduce_kernel --
+//   * blockIdx.y is the frame, blockIdx.x a share of its pixels; one launch for the whole batch;
+//   * a lane takes GROUPS of 16 consecutive pixels: 16 B of depth, 48 B of normal, 32 B of each counter per side -- sixteen
+//     16-byte loads in flight per lane -- and 64 B of image, stored as four 16-byte values;
+//   * frame k starts at element k * N of every buffer, so its slices are aligned differently per frame and per buffer.  The
+//     groups start `head` pixels into the frame (0 .. 15, the value that 16-byte aligns the most bytes per pixel: with
+//     16-byte aligned bases ALL slices, whatever k * N is); a slice that is still misaligned is read element by element into
+//     the same registers (the flags are the same for the whole workgroup: scalar branches).  The head and the tail behind the
+//     last whole group (at most 30 pixels) are taken one pixel per lane by the frame's first workgroup;
+//   * MAP and STATS are template parameters: they decide what is computed per pixel (and which buffers are read at all).
+//     An absent pair is a workgroup-uniform branch around its loads; its registers then hold a value that is equal on both
+//     sides and no surface ((128,128,128) for the normal), so every field derived from it comes out 0 without a test;
+//   * statistics: per lane in registers (sums of a group in 32 bits, folded into 64 bits per group), per wave by __shfl_down,
+//     per workgroup in LDS.  A frame of one workgroup writes its record directly.  Otherwise the workgroup's first lane
+//     stores the 16 words of a partial record of its own (write-through stores, nothing shared, no atomics on data), waits for
+//     them and takes a ticket from the frame's counter; the workgroup whose ticket is the last one acquires, adds up the
+//     frame's partial records with all its lanes, writes the record and leaves the counter at zero for its next user.
+//     Partial records are overwritten whole by their next user: nothing to clear.  All results are exact integers, so the
+//     order of summation does not matter.
+// A lane counts pixels in 32 bits: it sees at most N / (256 * workgroups of the frame) + 30 of them.
+
+constexpr int CMP_WORDS = 16, CMP_SUMS = 14;  // words [0, 14) of a partial record add, [14, 16) take the maximum
+enum { W_SDF_A, W_SDF_B, W_ITERS_A, W_ITERS_B, W_ABS_DEPTH, W_SURF_A, W_SURF_B, W_ONLY_A, W_ONLY_B, W_DEPTH_DIFF, W_NORMAL_DIFF,
+       W_COUNTERS_DIFF, W_B_CHEAPER, W_A_CHEAPER, W_MAX_DEPTH, W_MAX_NORMAL };
+
+struct CmpAcc {
+    unsigned long long sum[5];  // W_SDF_A .. W_ABS_DEPTH
+    unsigned int group[5];      // the same, of the group in hand
+    unsigned int cnt[9];        // W_SURF_A .. W_A_CHEAPER
+    unsigned int mx[2];
+};
+
+__device__ __forceinline__ unsigned int absdiff(unsigned int a, unsigned int b) { return a > b ? a - b : b - a; }
+
+// One pixel: the normals as 24 bits (R lowest), everything else as the stored value.  Returns the image's uchar4 as a word.
+template <int MAP, bool STATS>
+__device__ __forceinline__ unsigned int compare_pixel(CmpAcc &c, unsigned int da, unsigned int db, unsigned int na, unsigned int nb,
+                                                      unsigned int sa, unsigned int sb, unsigned int ia, unsigned int ib, unsigned int gain) {
+    const bool surf_a = na != 0x808080u, surf_b = nb != 0x808080u;  // raymarcher.ts:97-105
+    unsigned int dn = 0;
+    if (STATS || MAP == RM_CMP_NORMAL) {
+        dn = absdiff(na & 255u, nb & 255u);
+        const unsigned int g = absdiff((na >> 8) & 255u, (nb >> 8) & 255u), b = absdiff(na >> 16, nb >> 16);
+        dn = g > dn ? g : dn;
+        dn = b > dn ? b : dn;
+    }
+    if (STATS) {
+        const unsigned int dd = absdiff(da, db);
+        c.group[W_SDF_A] += sa;
+        c.group[W_SDF_B] += sb;
+        c.group[W_ITERS_A] += ia;
+        c.group[W_ITERS_B] += ib;
+        c.group[W_ABS_DEPTH] += dd;
+        c.cnt[W_SURF_A - W_SURF_A] += surf_a;
+        c.cnt[W_SURF_B - W_SURF_A] += surf_b;
+        c.cnt[W_ONLY_A - W_SURF_A] += surf_a && !surf_b;
+        c.cnt[W_ONLY_B - W_SURF_A] += surf_b && !surf_a;
+        c.cnt[W_DEPTH_DIFF - W_SURF_A] += da != db;
+        c.cnt[W_NORMAL_DIFF - W_SURF_A] += na != nb;
+        c.cnt[W_COUNTERS_DIFF - W_SURF_A] += sa != sb || ia != ib;
+        c.cnt[W_B_CHEAPER - W_SURF_A] += sb < sa;
+        c.cnt[W_A_CHEAPER - W_SURF_A] += sa < sb;
+        c.mx[0] = dd > c.mx[0] ? dd : c.mx[0];
+        c.mx[1] = dn > c.mx[1] ? dn : c.mx[1];
+    }
+    if (MAP == RM_CMP_NONE) return 0u;
+    if (MAP == RM_CMP_SURFACE) return 0xFF000000u | (surf_a && surf_b ? 0x606060u : surf_b ? 0xFFu : surf_a ? 0xFF00u : 0u);
+    if (MAP == RM_CMP_NORMAL) {
+        const unsigned int m = min(dn * gain, 255u);
+        return 0xFF000000u | m | (m << 8);
+    }
+    const unsigned int a = MAP == RM_CMP_SDF ? sa : MAP == RM_CMP_ITERS ? ia : da, b = MAP == RM_CMP_SDF ? sb : MAP == RM_CMP_ITERS ? ib : db;
+    const unsigned int m = min(absdiff(a, b) * gain, 255u);  // (65535 * 255 fits)
+    return 0xFF000000u | (b > a ? m : m << 8);               // red: B has or costs more; green: A; equal: m is 0
+}
+
+__device__ __forceinline__ void fold_group(CmpAcc &c) {
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        c.sum[k] += c.group[k];
+        c.group[k] = 0;
+    }
+}
+
+// NW words of one lane's share of a group: 16-byte loads, or element loads (E: the buffer's element type) into the same words
+template <int NW, typename E>
+__device__ __forceinline__ void load_group(const E *p, bool present, bool vec, unsigned int fill, unsigned int (&w)[NW]) {
+    if (!present) {
+#pragma unroll
+        for (int k = 0; k < NW; ++k) w[k] = fill;
+    } else if (vec) {
+        const uint4 *q = reinterpret_cast<const uint4 *>(p);
+#pragma unroll
+        for (int k = 0; k < NW / 4; ++k) {
+            const uint4 v = q[k];
+            w[4 * k] = v.x;
+            w[4 * k + 1] = v.y;
+            w[4 * k + 2] = v.z;
+            w[4 * k + 3] = v.w;
+        }
+    } else {
+        constexpr int PER = 4 / static_cast<int>(sizeof(E));
+#pragma unroll
+        for (int k = 0; k < NW; ++k) {
+            unsigned int x = 0;
+#pragma unroll
+            for (int j = 0; j < PER; ++j) x |= static_cast<unsigned int>(p[k * PER + j]) << (8 * static_cast<int>(sizeof(E)) * j);
+            w[k] = x;
+        }
+    }
+}
+
+// the 24 bits of pixel P (a constant after unrolling) of a group's 48 normal bytes
+template <int P>
+__device__ __forceinline__ unsigned int normal_of(const unsigned int (&w)[12]) {
+    constexpr int J = (3 * P) >> 2, SH = (3 * P) & 3;
+    if (SH <= 1) return (w[J] >> (8 * SH)) & 0xFFFFFFu;
+    return __builtin_amdgcn_alignbyte(w[J + 1 < 12 ? J + 1 : J], w[J], SH) & 0xFFFFFFu;  // (SH >= 2 never meets J == 11)
+}
+
+__device__ __forceinline__ void store_pixel(uint8_t *rgba, long long i, unsigned int px, bool whole) {
+    if (whole) {
+        reinterpret_cast<unsigned int *>(rgba)[i] = px;  // a whole uchar4
+    } else {  // an image that does not start on a 4-byte boundary
+#pragma unroll
+        for (int k = 0; k < 4; ++k) rgba[4 * i + k] = static_cast<uint8_t>(px >> (8 * k));
+    }
+}
+
+// sums and maxima of the workgroup's lanes -> v of thread 0
+__device__ __forceinline__ void cmp_combine(unsigned long long (&v)[CMP_WORDS], const unsigned long long (&o)[CMP_WORDS]) {
+#pragma unroll
+    for (int k = 0; k < CMP_WORDS; ++k) v[k] = k < CMP_SUMS ? v[k] + o[k] : (o[k] > v[k] ? o[k] : v[k]);
+}
+__device__ __forceinline__ void cmp_block_reduce(unsigned long long (&v)[CMP_WORDS]) {
+    __shared__ unsigned long long sh[4][CMP_WORDS];
+    for (int off = 32; off > 0; off >>= 1) {
+        unsigned long long o[CMP_WORDS];
+#pragma unroll
+        for (int k = 0; k < CMP_WORDS; ++k) o[k] = __shfl_down(v[k], off);
+        cmp_combine(v, o);
+    }
+    const int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < CMP_WORDS; ++k) sh[w][k] = v[k];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int j = 1; j < 4; ++j) cmp_combine(v, sh[j]);
+    }
+    __syncthreads();  // (sh is written again when the frame's last workgroup adds up the partial records)
+}
+
+__device__ __forceinline__ void cmp_write_record(RmCompareStats *out, long long npx, const unsigned long long (&v)[CMP_WORDS]) {
+    out->pixels = static_cast<unsigned long long>(npx);
+#pragma unroll
+    for (int k = 0; k < CMP_SUMS; ++k) out->sums[k] = v[k];
+    out->max_abs_depth = static_cast<unsigned int>(v[W_MAX_DEPTH]);
+    out->max_abs_normal = static_cast<unsigned int>(v[W_MAX_NORMAL]);
+}
+
+template <int MAP, bool STATS>
+__global__ __launch_bounds__(256) void compare_kernel(const RmCompareArgs A) {
+    constexpr bool NEED_D = STATS || MAP == RM_CMP_DEPTH, NEED_N = STATS || MAP == RM_CMP_NORMAL || MAP == RM_CMP_SURFACE,
+                   NEED_S = STATS || MAP == RM_CMP_SDF, NEED_I = STATS || MAP == RM_CMP_ITERS, IMAGE = MAP != RM_CMP_NONE;
+    const unsigned int f = blockIdx.y;
+    const long long N = A.npx, first = static_cast<long long>(f) * N;
+    const bool has_d = NEED_D && A.depth_a, has_n = NEED_N && A.normal_a, has_s = NEED_S && A.sdf_a, has_i = NEED_I && A.iters_a;
+    // the frame's slices (a pair that is absent or not needed: never dereferenced)
+    const uint8_t *da = has_d ? A.depth_a + first : nullptr, *db = has_d ? A.depth_b + first : nullptr;
+    const uint8_t *na = has_n ? A.normal_a + 3 * first : nullptr, *nb = has_n ? A.normal_b + 3 * first : nullptr;
+    const uint16_t *sa = has_s ? A.sdf_a + first : nullptr, *sb = has_s ? A.sdf_b + first : nullptr;
+    const uint16_t *ia = has_i ? A.iters_a + first : nullptr, *ib = has_i ? A.iters_b + first : nullptr;
+    uint8_t *rgba = IMAGE ? A.rgba + 4 * first : nullptr;
+    const bool whole = (reinterpret_cast<uintptr_t>(rgba) & 3) == 0;
+
+    // head: the first pixel of the groups, chosen to 16-byte align as many bytes per pixel as possible
+    const uintptr_t addr[9] = {reinterpret_cast<uintptr_t>(da), reinterpret_cast<uintptr_t>(db), reinterpret_cast<uintptr_t>(na),
+                               reinterpret_cast<uintptr_t>(nb), reinterpret_cast<uintptr_t>(sa), reinterpret_cast<uintptr_t>(sb),
+                               reinterpret_cast<uintptr_t>(ia), reinterpret_cast<uintptr_t>(ib), reinterpret_cast<uintptr_t>(rgba)};
+    const bool used[9] = {has_d, has_d, has_n, has_n, has_s, has_s, has_i, has_i, IMAGE};
+    constexpr unsigned int bpp[9] = {1, 1, 3, 3, 2, 2, 2, 2, 4};
+    unsigned int head = 0, best = 0;
+    for (unsigned int h = 0; h < 16; ++h) {
+        unsigned int score = 0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) score += used[k] && ((addr[k] + h * bpp[k]) & 15) == 0 ? bpp[k] : 0u;
+        if (score > best) {
+            best = score;
+            head = h;
+        }
+    }
+    if (head > N) head = static_cast<unsigned int>(N);
+    bool vec[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) vec[k] = ((addr[k] + head * bpp[k]) & 15) == 0;
+    const long long groups = (N - head) >> 4, tail0 = head + (groups << 4);
+
+    CmpAcc c;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        c.sum[k] = 0;
+        c.group[k] = 0;
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) c.cnt[k] = 0;
+    c.mx[0] = c.mx[1] = 0;
+
+    // head and tail: one pixel per lane of the frame's first workgroup (head + tail < 32)
+    if (blockIdx.x == 0) {
+        const long long t = threadIdx.x, i = t < head ? t : tail0 + (t - head);
+        if (i < N) {
+            const unsigned int pna = has_n ? na[3 * i] | na[3 * i + 1] << 8 | na[3 * i + 2] << 16 : 0x808080u;
+            const unsigned int pnb = has_n ? nb[3 * i] | nb[3 * i + 1] << 8 | nb[3 * i + 2] << 16 : 0x808080u;
+            const unsigned int px = compare_pixel<MAP, STATS>(c, has_d ? da[i] : 0u, has_d ? db[i] : 0u, pna, pnb, has_s ? sa[i] : 0u,
+                                                              has_s ? sb[i] : 0u, has_i ? ia[i] : 0u, has_i ? ib[i] : 0u, A.gain);
+            if (IMAGE) store_pixel(rgba, i, px, whole);
+        }
+        if (STATS) fold_group(c);
+    }
+
+    const long long step = static_cast<long long>(gridDim.x) * 256;
+    for (long long g = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; g < groups; g += step) {
+        const long long p0 = head + (g << 4);  // the group's first pixel
+        unsigned int wda[4], wdb[4], wna[12], wnb[12], wsa[8], wsb[8], wia[8], wib[8];
+        load_group(da + p0, has_d, vec[0], 0u, wda);
+        load_group(db + p0, has_d, vec[1], 0u, wdb);
+        load_group(na + 3 * p0, has_n, vec[2], 0x80808080u, wna);
+        load_group(nb + 3 * p0, has_n, vec[3], 0x80808080u, wnb);
+        load_group(sa + p0, has_s, vec[4], 0u, wsa);
+        load_group(sb + p0, has_s, vec[5], 0u, wsb);
+        load_group(ia + p0, has_i, vec[6], 0u, wia);
+        load_group(ib + p0, has_i, vec[7], 0u, wib);
+        unsigned int px[16];
+#define RM_CMP_PIXEL(P)                                                                                                              \
+    px[P] = compare_pixel<MAP, STATS>(c, (wda[(P) >> 2] >> (8 * ((P) & 3))) & 255u, (wdb[(P) >> 2] >> (8 * ((P) & 3))) & 255u,      \
+                                      normal_of<P>(wna), normal_of<P>(wnb), (wsa[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu,          \
+                                      (wsb[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu, (wia[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu, \
+                                      (wib[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu, A.gain);
+        RM_CMP_PIXEL(0) RM_CMP_PIXEL(1) RM_CMP_PIXEL(2) RM_CMP_PIXEL(3) RM_CMP_PIXEL(4) RM_CMP_PIXEL(5) RM_CMP_PIXEL(6) RM_CMP_PIXEL(7)
+        RM_CMP_PIXEL(8) RM_CMP_PIXEL(9) RM_CMP_PIXEL(10) RM_CMP_PIXEL(11) RM_CMP_PIXEL(12) RM_CMP_PIXEL(13) RM_CMP_PIXEL(14) RM_CMP_PIXEL(15)
+#undef RM_CMP_PIXEL
+        if (STATS) fold_group(c);
+        if (IMAGE) {
+            if (vec[8]) {
+                uint4 *out = reinterpret_cast<uint4 *>(rgba + 4 * p0);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) out[k] = make_uint4(px[4 * k], px[4 * k + 1], px[4 * k + 2], px[4 * k + 3]);
+            } else {
+#pragma unroll
+                for (int k = 0; k < 16; ++k) store_pixel(rgba, p0 + k, px[k], whole);
+            }
+        }
+    }
+
+    if (!STATS) return;
+    unsigned long long v[CMP_WORDS];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) v[k] = c.sum[k];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) v[5 + k] = c.cnt[k];
+    v[W_MAX_DEPTH] = c.mx[0];
+    v[W_MAX_NORMAL] = c.mx[1];
+    cmp_block_reduce(v);
+    if (gridDim.x == 1) {  // the frame's only workgroup
+        if (threadIdx.x == 0) cmp_write_record(A.stats + f, N, v);
+        return;
+    }
+    RmComparePartial *partials = A.partials + static_cast<size_t>(f) * gridDim.x;
+    unsigned int *counter = A.counters + static_cast<size_t>(f) * gridDim.x;
+    __shared__ unsigned int last;
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < CMP_WORDS; ++k) __hip_atomic_store(&partials[blockIdx.x].v[k], v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the partial record has left before the ticket is taken
+        const unsigned int ticket = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        last = ticket + 1u == gridDim.x;
+        if (ticket + 1u == gridDim.x) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // ... and the invalidate is over before the barrier lets the others load
+        }
+    }
+    __syncthreads();
+    if (!last) return;
+#pragma unroll
+    for (int k = 0; k < CMP_WORDS; ++k) v[k] = 0;
+    for (unsigned int b = threadIdx.x; b < gridDim.x; b += 256) {
+        unsigned long long o[CMP_WORDS];
+#pragma unroll
+        for (int k = 0; k < CMP_WORDS; ++k) o[k] = __hip_atomic_load(&partials[b].v[k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        cmp_combine(v, o);
+    }
+    cmp_block_reduce(v);
+    if (threadIdx.x == 0) {
+        cmp_write_record(A.stats + f, N, v);
+        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the counter's next user
+    }
+}
+
 }  // namespace
 
 hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
@@ -79,5 +384,43 @@ hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride
     hipLaunchKernelGGL(assemble_kernel, dim3(blocks), dim3(256), 0, stream, gathered, static_cast<long long>(rank_stride),
                        static_cast<long long>(section_offset), row_bytes, height, stripe_rows, stripe_src, n_stripes, frame,
                        static_cast<long long>(acc_offset), world, acc, chunks);
+    return hipGetLastError();
+}
+
+
+int32_t rm_compare_blocks_per_frame(int64_t npx, int32_t n_frames) {
+    // ~2048 workgroups per launch, at most 512 per frame (two per CU: all resident at the kernel's three waves per SIMD, and
+    // the frame's last workgroup adds up that many partial records), never more than the frame has groups for
+    const int64_t want = (npx / 16 + 255) / 256, share = n_frames > 0 ? 2048 / n_frames : 1;
+    const int64_t cap = share > 512 ? 512 : share;
+    return static_cast<int32_t>(want < 1 || cap < 1 ? 1 : want < cap ? want : cap);
+}
+
+hipError_t rm_launch_compare(const RmCompareArgs &a, int32_t map, int32_t n_frames, int32_t blocks_per_frame, hipStream_t stream,
+                             const char **kernel_name) {
+    const bool stats = a.stats != nullptr;
+    if (n_frames <= 0 || a.npx <= 0 || (map == RM_CMP_NONE && !stats)) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(blocks_per_frame), static_cast<unsigned>(n_frames)), block(256);
+    const char *name = nullptr;
+#define RM_CMP_CASE(M)                                                                                \
+    case M:                                                                                           \
+        if (stats) {                                                                                  \
+            hipLaunchKernelGGL((compare_kernel<M, true>), grid, block, 0, stream, a);                 \
+            name = "compare_kernel<" #M ", true>";                                                    \
+        } else {                                                                                      \
+            hipLaunchKernelGGL((compare_kernel<M, false>), grid, block, 0, stream, a);                \
+            name = "compare_kernel<" #M ", false>";                                                   \
+        }                                                                                             \
+        break;
+    switch (map) {
+        RM_CMP_CASE(0) RM_CMP_CASE(1) RM_CMP_CASE(2) RM_CMP_CASE(3) RM_CMP_CASE(4)
+    case RM_CMP_NONE:
+        hipLaunchKernelGGL((compare_kernel<RM_CMP_NONE, true>), grid, block, 0, stream, a);
+        name = "compare_kernel<-1, true>";
+        break;
+    default: return hipErrorInvalidValue;
+    }
+#undef RM_CMP_CASE
+    if (kernel_name) *kernel_name = name;
     return hipGetLastError();
 }

@@ -28,6 +28,28 @@ struct RmDiagDevice {  // accumulator of rm_reduce_counters_device (32 bytes)
 #define RM_LEN_IS_SQRT false
 #endif
 
+// rm_compare_frames_device (rm_frame_ops.hip, compare_kernel).  The maps are rm_compare_map's values.
+enum { RM_CMP_NONE = -1, RM_CMP_SDF = 0, RM_CMP_ITERS = 1, RM_CMP_DEPTH = 2, RM_CMP_NORMAL = 3, RM_CMP_SURFACE = 4 };
+struct RmCompareStats {  // rm_compare_stats: sums = sum_sdf_a .. a_cheaper in the order of the header
+    unsigned long long pixels;
+    unsigned long long sums[14];
+    unsigned int max_abs_depth, max_abs_normal;
+};
+struct RmComparePartial {  // what one workgroup of a frame contributes: the 14 sums, then the two maxima
+    unsigned long long v[16];
+};
+struct RmCompareArgs {
+    const uint8_t *depth_a, *depth_b, *normal_a, *normal_b;  // a pair is present or absent on both sides
+    const uint16_t *sdf_a, *sdf_b, *iters_a, *iters_b;
+    uint8_t *rgba;               // null exactly when the map is RM_CMP_NONE
+    RmCompareStats *stats;       // one record per frame, or null
+    RmComparePartial *partials;  // [n_frames][blocks_per_frame], and ...
+    unsigned int *counters;      // ... the frame's ticket counter at [frame * blocks_per_frame], zero before and after the launch;
+                                 // both unused (may be null) with one workgroup per frame or without stats
+    long long npx;               // pixels of a frame
+    unsigned int gain;
+};
+
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
 // instantiation that was launched (static string).
@@ -93,6 +115,13 @@ hipError_t rm_launch_lpt_sort(const uint8_t *cost_prev, uint16_t *perm, int stri
 hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
                               int32_t height, int32_t stripe_rows, const int32_t *stripe_src, int32_t n_stripes,
                               unsigned char *frame, int64_t acc_offset, int32_t world, RmDiagDevice *acc, hipStream_t stream);
+
+// rm_compare_frames_device: ONE launch of compare_kernel<map, stats> over n_frames frames of a.npx pixels, blocks_per_frame
+// workgroups each (rm_compare_blocks_per_frame: what the caller sizes a.partials and a.counters by).  Launches nothing when
+// there is no pixel, no frame, or neither an image nor statistics to write.
+int32_t rm_compare_blocks_per_frame(int64_t npx, int32_t n_frames);
+hipError_t rm_launch_compare(const RmCompareArgs &a, int32_t map, int32_t n_frames, int32_t blocks_per_frame, hipStream_t stream,
+                             const char **kernel_name);
 
 hipError_t rm_launch_hypot(const float *xyz, int64_t n, double *out, hipStream_t stream);
 // rm_jsmath.h on the device: fn 0 sin, 1 cos, 2 atan2, 3 asin, 4 log, 5 pow, 6 round, 7 atan

@@ -361,6 +361,62 @@ RM_API int rm_render_frames_device(rm_ctx *ctx, const rm_job *job, int32_t shade
 RM_API int rm_sweep_views(double pitch, double yaw, double d_pitch, double d_yaw, double time0, double d_time, int32_t n,
                           rm_view *views);
 
+/* ---- two renders of a view: difference image and statistics --------------------------- */
+
+/* The reference's README plans "more detailed diagnostic data including comparing different algorithms"; today its user compares
+ * two marchers or acceleration structures by eye, switching between the two heatmap shaders.  This entry compares two G-buffer
+ * sets of the same frames on the device -- two calls of rm_render_tile_device / rm_render_frames_device that differ in algorithm,
+ * acceleration structure, overshoot or step size, a scene before and after an edit, or the host's own CPU result against this
+ * library's -- and needs no scene. */
+typedef enum rm_compare_map {
+    RM_CMP_MAP_NONE = -1,   /* statistics only */
+    RM_CMP_MAP_SDF = 0, RM_CMP_MAP_ITERS = 1, RM_CMP_MAP_DEPTH = 2, RM_CMP_MAP_NORMAL = 3, RM_CMP_MAP_SURFACE = 4
+} rm_compare_map;
+
+typedef struct rm_frame_set { const void *depth, *normal, *sdf, *iters; } rm_frame_set;   /* layouts of the header's top comment */
+
+/* "Surface" is the G-buffer's own notion: raymarcher.ts:97-105 stores the normal bytes (128,128,128) exactly when the normal is
+ * the zero vector -- on a miss (depth >= MAX_DIST, where getNormal is skipped) or where the gradient is zero.  The depth byte
+ * cannot tell a hit from a miss: t in [9.5, 10) rounds to the same 10 a miss stores. */
+typedef struct rm_compare_stats {        /* 128 bytes, one per frame, everything B against A */
+    uint64_t pixels;
+    uint64_t sum_sdf_a, sum_sdf_b, sum_iters_a, sum_iters_b;   /* stored u16 values, as main.ts:534-543 sums them */
+    uint64_t sum_abs_depth;                                    /* sum |depthB - depthA| */
+    uint64_t surface_a, surface_b;                             /* pixels whose normal bytes are not (128,128,128) */
+    uint64_t surface_only_a, surface_only_b;
+    uint64_t depth_differs, normal_differs, counters_differ;   /* counters: sdf or iters differ */
+    uint64_t b_cheaper, a_cheaper;                             /* sdfB < sdfA, sdfA < sdfB */
+    uint32_t max_abs_depth, max_abs_normal;                    /* normal: max over pixels and the three channels */
+} rm_compare_stats;
+
+/* n_frames frames of width x rows pixels, device pointers, ONE launch, asynchronous on `stream` like the other device entries.
+ * Frame k occupies elements [k * W * rows, (k + 1) * W * rows) of every buffer (x3 normal, x4 rgba): the layout
+ * rm_render_frames_device writes; n_frames = 1 is a single tile.  Each of the four pairs (depth, normal, sdf, iters) may be
+ * absent -- NULL in a AND in b -- and every field derived from an absent pair is 0 (pixels is always W * rows).
+ *   map, gain  the difference image, pure integer, alpha 255.  SDF, ITERS, DEPTH: d = B - A of that buffer, m = min(|d| * gain, 255):
+ *              d > 0 (m, 0, 0), d < 0 (0, m, 0), d == 0 (0, 0, 0) -- red: B has or costs more (the reference's heatmaps are red and
+ *              green too, and use 5).  NORMAL: m from the largest absolute channel difference, (m, m, 0).  SURFACE: on both sides
+ *              (96, 96, 96), on neither (0, 0, 0), only B (255, 0, 0), only A (0, 255, 0); gain is not used.  gain is 1 .. 255.
+ *   d_rgba     W * rows * n_frames * 4 bytes, written as whole pixels; NULL only with RM_CMP_MAP_NONE
+ *   d_stats    NULL, or n_frames records (8-byte aligned), each written completely by the launch: neither d_rgba nor d_stats
+ *              needs a pre-clear, there is no initialising launch.  Exact integers: the same record whatever the launch shape.
+ * width == 0, rows == 0 or n_frames == 0 is RM_OK: every one of the n_frames records is all zero, no image byte is written.
+ * RM_E_INVALID -- checked before anything else -- for a null a or b, a negative size, n_frames > 65535 (one grid dimension), a
+ * pair given on one side only, a map outside the enum or whose pair is absent, and with a map other than NONE a gain outside
+ * 1 .. 255 or a null d_rgba; also for an sdf / iters pointer that is not 2-byte or a d_stats that is not 8-byte aligned.
+ * RM_E_NO_DEVICE on a host-only context; never RM_E_NO_SCENE.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics.  rm_last_kernel names the compare_kernel<map, stats> instantiation.
+ * Calls in flight: a frame of more than one workgroup (above 4 096 pixels) combines per-workgroup partial records through a ring
+ * in the context (4 096 records); a call owns its entries until its launch is over, on whatever stream it ran, and a call that
+ * would reuse them waits on the host for it first -- the rule of rm_render_frames_device's ring.  No call needs more than half of it. */
+RM_API int rm_compare_frames_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames,
+                                    const rm_frame_set *a, const rm_frame_set *b,
+                                    int32_t map, int32_t gain, void *d_rgba, void *d_stats, void *stream);
+/* Same with host buffers (synchronous), staged through the context's scratch buffer. */
+RM_API int rm_compare_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames,
+                             const rm_frame_set *a, const rm_frame_set *b,
+                             int32_t map, int32_t gain, uint8_t *rgba, rm_compare_stats *stats);
+
 /* Multi-GPU sharding of one Job (replaces the contiguous ceil(H/N) split of main.ts:444-449
  * by a load-balanced one): the rows [y_start, y_end) are cut into stripes of `stripe_rows`
  * rows dealt round-robin over `n_parts`; this call renders, in ONE launch, the stripes of

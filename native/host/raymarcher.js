@@ -108,5 +108,33 @@ function diagnostics(SDFevaluationBuffer, iterationsBuffer) { // main.ts:528-548
   return d;
 }
 
+// Two G-buffer sets of the same frames, B against A (rm_compare_frames): the analytics the reference's README plans
+// ("comparing different algorithms").  Sets are {depth, normal, sdfEval, iters} as onmessage returns them (a buffer may be
+// absent on both sides); nFrames frames lie one behind the other.
+const COMPARE_MAPS = { none: -1, sdf: 0, iters: 1, depth: 2, normal: 3, surface: 4 };
+const COMPARE_FIELDS = ['pixels', 'sumSdfA', 'sumSdfB', 'sumItersA', 'sumItersB', 'sumAbsDepth', 'surfaceA', 'surfaceB',
+  'surfaceOnlyA', 'surfaceOnlyB', 'depthDiffers', 'normalDiffers', 'countersDiffer', 'bCheaper', 'aCheaper'];
+class FrameComparison {
+  constructor(map = 'sdf', gain = 5) { this.map = map; this.gain = gain; }
+  // -> { stats: one object per frame, rgba: Uint8ClampedArray | null }
+  compareFrames(a, b, width, rows, nFrames = 1) {
+    ensure();
+    const map = typeof this.map === 'number' ? this.map : COMPARE_MAPS[this.map];
+    const rgba = map === -1 ? null : new Uint8ClampedArray(width * rows * nFrames * 4);
+    const raw = new Uint8Array(128 * nFrames);
+    check(native.compareFrames(a, b, width, rows, nFrames, map, this.gain, rgba, raw));
+    const view = new DataView(raw.buffer);
+    const stats = [];
+    for (let k = 0; k < nFrames; k++) {
+      const s = {};
+      COMPARE_FIELDS.forEach((name, i) => { s[name] = Number(view.getBigUint64(128 * k + 8 * i, true)); });
+      s.maxAbsDepth = view.getUint32(128 * k + 120, true);
+      s.maxAbsNormal = view.getUint32(128 * k + 124, true);
+      stats.push(s);
+    }
+    return { stats, rgba };
+  }
+}
+
 module.exports = { Camera, Scene, Raymarcher, SphereTracer, FixedStep, AdaptiveStep, AdaptiveStepV2, AdaptiveStepV3,
-  ShadingModel, createShadingModelFromValue, onmessage, diagnostics, native };
+  ShadingModel, createShadingModelFromValue, onmessage, diagnostics, FrameComparison, native };

@@ -101,7 +101,9 @@ void *typed(napi_env env, napi_value v, size_t *bytes) {
     void *data = nullptr;
     napi_value ab;
     if (napi_get_typedarray_info(env, v, &t, &len, &data, &ab, &off) != napi_ok) return nullptr;
-    const size_t esz = (t == napi_uint16_array || t == napi_int16_array) ? 2 : (t == napi_uint8_array || t == napi_uint8_clamped_array || t == napi_int8_array) ? 1 : 4;
+    const size_t esz = (t == napi_uint16_array || t == napi_int16_array) ? 2
+                       : (t == napi_uint8_array || t == napi_uint8_clamped_array || t == napi_int8_array) ? 1
+                       : (t == napi_float64_array || t == napi_bigint64_array || t == napi_biguint64_array) ? 8 : 4;
     *bytes = len * esz;
     return data;
 }
@@ -202,6 +204,41 @@ napi_value Diagnostics(napi_env env, napi_callback_info info) {
     return out;
 }
 
+// compareFrames(a, b, width, rows, nFrames, map, gain, rgba, stats) -> status   (rm_compare_frames, host buffers)
+// a, b: {depth, normal, sdfEval, iters}, each a typed array or absent on both sides; map: rm_compare_map; rgba:
+// Uint8ClampedArray or null (map -1); stats: null or a typed array of 128 bytes per frame that receives the rm_compare_stats records
+napi_value CompareFrames(napi_env env, napi_callback_info info) {
+    size_t argc = 9;
+    napi_value a[9];
+    napi_get_cb_info(env, info, &argc, a, nullptr, nullptr);
+    Addon *ad = addon_of(env);
+    rm_ctx *g_ctx = ad ? ad->ctx : nullptr;
+    if (!g_ctx || argc < 9) return make_int(env, RM_E_INVALID);
+    int32_t v[5] = {0, 0, 0, 0, 0};  // width, rows, nFrames, map, gain
+    for (int i = 0; i < 5; ++i) napi_get_value_int32(env, a[2 + i], &v[i]);
+    const size_t n = v[2] > 0 ? static_cast<size_t>(v[2]) : 0;
+    const size_t total = static_cast<size_t>(v[0] > 0 ? v[0] : 0) * static_cast<size_t>(v[1] > 0 ? v[1] : 0) * n;
+    static const char *const names[4] = {"depth", "normal", "sdfEval", "iters"};
+    const size_t bpp[4] = {1, 3, 2, 2};
+    rm_frame_set sets[2];
+    for (int side = 0; side < 2; ++side) {
+        napi_valuetype t;
+        if (napi_typeof(env, a[side], &t) != napi_ok || t != napi_object) return make_int(env, RM_E_INVALID);
+        const void *p[4];
+        for (int k = 0; k < 4; ++k) {
+            size_t bytes = 0;
+            p[k] = typed(env, obj_prop(env, a[side], names[k]), &bytes);
+            if (p[k] && bytes < bpp[k] * total) return make_int(env, RM_E_INVALID);
+        }
+        sets[side] = rm_frame_set{p[0], p[1], p[2], p[3]};
+    }
+    size_t rgba_bytes = 0, stats_bytes = 0;
+    uint8_t *rgba = static_cast<uint8_t *>(typed(env, a[7], &rgba_bytes));
+    void *stats = typed(env, a[8], &stats_bytes);
+    if ((rgba && rgba_bytes < 4 * total) || (stats && stats_bytes < sizeof(rm_compare_stats) * n)) return make_int(env, RM_E_INVALID);
+    return make_int(env, rm_compare_frames(g_ctx, v[0], v[1], v[2], &sets[0], &sets[1], v[3], v[4], rgba, static_cast<rm_compare_stats *>(stats)));
+}
+
 napi_value LastError(napi_env env, napi_callback_info) {
     napi_value out;
     Addon *ad = addon_of(env);
@@ -226,6 +263,9 @@ napi_value Init(napi_env env, napi_value exports) {
         {"diagnostics", nullptr, Diagnostics, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"lastError", nullptr, LastError, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
         {"version", nullptr, Version, nullptr, nullptr, nullptr, napi_enumerable, nullptr},
+        // (not enumerable: Object.keys of the addon stays the worker's surface of raymarchWorker.ts; hosts reach it through
+        // FrameComparison of native/host/raymarcher.js)
+        {"compareFrames", nullptr, CompareFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;
