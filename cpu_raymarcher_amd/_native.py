@@ -67,6 +67,21 @@ class rm_compare_stats(C.Structure):  # include/rm_raymarch.h: struct rm_compare
 # rm_compare_map by name
 COMPARE_MAPS = {"none": -1, "sdf": 0, "iters": 1, "depth": 2, "normal": 3, "surface": 4}
 
+RM_HIST_BINS = 256
+
+
+class rm_counter_hist(C.Structure):  # include/rm_raymarch.h: struct rm_counter_hist
+    _fields_ = [("pixels", C.c_uint64), ("sum", C.c_uint64), ("min", C.c_uint32), ("max", C.c_uint32), ("range_lo", C.c_uint32),
+                ("range_hi", C.c_uint32), ("shift", C.c_uint32), ("reserved", C.c_uint32), ("bins", C.c_uint32 * RM_HIST_BINS)]
+
+
+class rm_frame_hist(C.Structure):  # include/rm_raymarch.h: struct rm_frame_hist
+    _fields_ = [("sdf", rm_counter_hist), ("iters", rm_counter_hist)]
+
+
+# rm_hist_mask by name
+HIST_MASKS = {"all": 0, "surface": 1, "background": 2}
+
 
 class rm_scene_info(C.Structure):
     _fields_ = [("n_prims", C.c_int32), ("accel", C.c_int32), ("preset_index", C.c_int32),
@@ -127,6 +142,11 @@ SIGNATURES = {
                                            C.c_int32, C.c_int32, _VP, _VP, _VP]),
     "rm_compare_frames": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.POINTER(rm_frame_set), C.POINTER(rm_frame_set),
                                     C.c_int32, C.c_int32, _VP, _VP]),
+    "rm_counter_hist_device": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         _VP, _VP]),
+    "rm_counter_hist": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP]),
+    "rm_shade_ranged_device": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, C.c_uint32, _VP, _VP]),
+    "rm_shade_ranged": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, C.c_uint32, C.c_uint32, _VP]),
     "rm_sweep_views": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int32, _VP]),
     "rm_render_stripes_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                            _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -79,6 +79,37 @@ def _check_pixel_sets(npx, bufs, rgba, stats, stats_bytes):
     return bool(on_dev)
 
 
+def _check_records(hist, n_frames, on_dev):
+    """A buffer of one rm_frame_hist (2 128 bytes) per frame, on the side the pixel buffers are on (on_dev None: either)."""
+    if not (_is_torch(hist) or isinstance(hist, np.ndarray)):
+        raise ValueError("hist must be a numpy array or a torch tensor")
+    d = bool(_is_torch(hist) and hist.is_cuda)
+    contiguous = hist.is_contiguous() if _is_torch(hist) else hist.flags["C_CONTIGUOUS"]
+    nbytes = hist.numel() * hist.element_size() if _is_torch(hist) else hist.nbytes
+    if not contiguous or nbytes < 2128 * max(0, n_frames):
+        raise ValueError("hist must be a contiguous buffer of 2128 bytes per frame")
+    if on_dev is not None and on_dev != d:
+        raise ValueError("buffers must be all on the host or all on the device")
+    return d
+
+
+def percentile(record, permille):
+    """The header's percentile rule on a decoded record (an entry of Context.decode_hists(...)[k]["sdf" | "iters"]): any further
+    percentile from one read-back.  permille 0 .. 1000 -> (lo, hi), the value range of the bin that holds the pixel of rank
+    floor(permille * (pixels - 1) / 1000), clipped to [min, max] as range_lo and range_hi are; (0, 0) without pixels.  With shift
+    0 and values below 255 lo == hi is the exact nearest-rank percentile."""
+    p = int(permille)
+    if not 0 <= p <= 1000:
+        raise ValueError("permille must be in [0, 1000]")
+    M = int(record["pixels"])
+    if M == 0:
+        return 0, 0
+    r = p * (M - 1) // 1000
+    b = int(np.searchsorted(np.cumsum(np.asarray(record["bins"], dtype=np.uint64)), r, side="right"))
+    shift, mn, mx = int(record["shift"]), int(record["min"]), int(record["max"])
+    return max(mn, b << shift), (mx if b == 255 else min(mx, ((b + 1) << shift) - 1))
+
+
 def _current_stream_ptr():
     import torch
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -410,6 +441,82 @@ class Context:
         self.compare_frames(sets[0], sets[1], rgba=rgba, map=m, gain=gain, stats=stats, width=W, rows=rows, n_frames=n)
         out = (self.decode_compare_stats(stats), None if rgba is None else rgba.view(n, rows, W, 4))
         return out if shader is None else out + tuple(x.view(n, rows, W, 4) for x in shaded)
+
+    # ---- counter distributions per frame: histograms, percentiles, ranged heatmaps --------
+    def counter_hist(self, sdf, iters, normal=None, mask="all", bin_shift=0, percentiles=(0, 1000), hist=None, width=0, rows=0,
+                     n_frames=1):
+        """The histogram of each counter of each of n_frames frames of width x rows pixels (rm_counter_hist_device /
+        rm_counter_hist), the frames one behind the other as render_frames writes them.  sdf, iters: either may be None (its
+        records are zero), not both.  `mask`: a name of HIST_MASKS ("all", "surface", "background") or an rm_hist_mask value;
+        the last two need `normal`.  bin(v) = min(v >> bin_shift, 255); `percentiles`: the two permille values (lo, hi) behind
+        range_lo and range_hi.  `hist`: a buffer of 2128 * n_frames bytes for one rm_frame_hist per frame (decode_hists), or
+        None: one is allocated beside the counters.  Returns it.  torch CUDA tensors -> the device entry on torch's current
+        stream (asynchronous); numpy arrays -> the host entry (synchronous).  hist needs no pre-clear."""
+        m = N.HIST_MASKS[mask] if isinstance(mask, str) else int(mask)
+        n = int(n_frames)
+        npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
+        bufs = dict(sdf=sdf, iters=iters, normal=normal)
+        on_dev = _check_buffers(npx, bufs)
+        some = next((b for b in bufs.values() if b is not None), None)
+        if some is None:
+            on_dev = None if hist is None else bool(_is_torch(hist) and hist.is_cuda)
+        if hist is None:
+            if on_dev:
+                import torch
+                hist = torch.empty(2128 * max(0, n), dtype=torch.uint8, device=some.device)
+            else:
+                hist = np.zeros(2128 * max(0, n), np.uint8)
+                on_dev = False
+        on_dev = _check_records(hist, n, on_dev)
+        self._same_device(dict(bufs, hist=hist))
+        lo, hi = (int(x) for x in percentiles)
+        if on_dev:
+            N.check(self._h, N.lib().rm_counter_hist_device(self._h, int(width), int(rows), n, _ptr(sdf), _ptr(iters), _ptr(normal), m,
+                                                            int(bin_shift), lo, hi, _ptr(hist), _current_stream_ptr()))
+        else:
+            N.check(self._h, N.lib().rm_counter_hist(self._h, int(width), int(rows), n, _ptr(sdf), _ptr(iters), _ptr(normal), m,
+                                                     int(bin_shift), lo, hi, _ptr(hist)))
+        return hist
+
+    @staticmethod
+    def decode_hists(buf):
+        """One {"sdf": {...}, "iters": {...}} per 2128-byte rm_frame_hist record of `buf` (a CUDA tensor or a numpy array,
+        counter_hist's hist): the fields of rm_counter_hist as ints, `bins` as a numpy uint32[256] array."""
+        raw = buf.cpu().contiguous().view(-1).numpy() if _is_torch(buf) else np.ascontiguousarray(buf).reshape(-1)
+        raw = raw.view(np.uint8)
+        out = []
+        for k in range(raw.size // 2128):
+            rec = N.rm_frame_hist.from_buffer_copy(raw[2128 * k:2128 * (k + 1)].tobytes())
+            frame = {}
+            for name in ("sdf", "iters"):
+                c = getattr(rec, name)
+                d = {f: int(getattr(c, f)) for f, _ in N.rm_counter_hist._fields_ if f != "bins"}
+                d["bins"] = np.frombuffer(bytes(c.bins), dtype=np.uint32).copy()
+                frame[name] = d
+            out.append(frame)
+        return out
+
+    def shade_ranged(self, counter, values, rgba, hist=None, lo=0, hi=0, width=0, rows=0, n_frames=1):
+        """The heatmap of one counter scaled to a range (rm_shade_ranged_device / rm_shade_ranged): s = 0 up to lo, 255 from hi,
+        (v - lo) * 255 // (hi - lo) between, coloured by the reference's red-green ramp; it never wraps.  `counter`: "sdf" / 0 or
+        "iters" / 1 -- what `values` holds.  `hist`: None (every frame uses lo, hi) or counter_hist's records: frame k then takes
+        range_lo, range_hi of its own record, read on the device -- no synchronisation is needed between the two calls.
+        torch CUDA tensors -> the device entry on torch's current stream; numpy arrays -> the host entry (synchronous)."""
+        c = {"sdf": 0, "iters": 1}[counter] if isinstance(counter, str) else int(counter)
+        n = int(n_frames)
+        npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
+        bufs = dict(sdf=values, rgba=rgba)
+        on_dev = _check_buffers(npx, bufs)
+        if hist is not None:
+            _check_records(hist, n, on_dev if (values is not None or rgba is not None) else None)
+        self._same_device(dict(bufs, hist=hist))
+        if on_dev:
+            N.check(self._h, N.lib().rm_shade_ranged_device(self._h, c, int(width), int(rows), n, _ptr(values), _ptr(hist), int(lo), int(hi),
+                                                            _ptr(rgba), _current_stream_ptr()))
+        else:
+            N.check(self._h, N.lib().rm_shade_ranged(self._h, c, int(width), int(rows), n, _ptr(values), _ptr(hist), int(lo), int(hi),
+                                                     _ptr(rgba)))
+        return rgba
 
     def _same_device(self, bufs):
         for name, b in bufs.items():

@@ -204,6 +204,36 @@ struct CompareRing {
     void launched(size_t first, size_t n, hipStream_t stream) { owners.launched(first, n, stream); }
 };
 
+// The ring of rm_counter_hist_device: per frame of more than one workgroup one RmHistScratch (2 096 bytes: the frame's scratch
+// histograms, sums, extremes and ticket counter; zeroed when allocated, left all zero by the workgroup that took the last ticket --
+// hist_kernel, rm_frame_ops.hip).  A launch has at most 2 048 workgroups in such frames (rm_compare_blocks_per_frame), so at most
+// 1 024 such frames: no call needs more than half of kEntries.  Allocated at the first call that needs it (4.2 MB); entries are
+// owned as RingClaims says.
+struct HistRing {
+    static constexpr size_t kEntries = 2048;
+    RmHistScratch *entries = nullptr;
+    RingClaims owners;
+
+    void release() {
+        owners.retire_all();
+        (void)hipFree(entries);
+        entries = nullptr;
+    }
+    hipError_t take(size_t n, size_t *first) {
+        if (n > kEntries) return hipErrorInvalidValue;
+        if (!entries) {
+            hipError_t e = hipMalloc(reinterpret_cast<void **>(&entries), kEntries * sizeof(RmHistScratch));
+            if (e == hipSuccess) e = hipMemset(entries, 0, kEntries * sizeof(RmHistScratch));
+            if (e != hipSuccess) {
+                release();
+                return e;
+            }
+        }
+        return owners.take(n, kEntries, first);
+    }
+    void launched(size_t first, size_t n, hipStream_t stream) { owners.launched(first, n, stream); }
+};
+
 // The LPT ring (option `lpt`; rm_render_v2.hip, lpt_sort_kernel): a v2 launch sorts its items longest-first from the costs the
 // previous launch recorded, into a permutation of its own, and records its own costs; one slot per launch in flight.
 //  - The buffers are allocated at the first acquire; both exist or neither does (launches then keep their queues' order).
@@ -408,6 +438,7 @@ struct rm_ctx {
     OctTableRing oct_tables;
     FrameRing frames;         // rm_render_frames_device
     CompareRing compare;      // rm_compare_frames_device
+    HistRing hists;           // rm_counter_hist_device
     unsigned long long scene_gen = 0;  // bumped by every upload_scene
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
@@ -1186,6 +1217,46 @@ int check_compare(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, co
     return RM_OK;
 }
 
+static_assert(sizeof(struct rm_counter_hist) == 1064 && sizeof(rm_frame_hist) == 2128 && sizeof(RmCounterHist) == sizeof(struct rm_counter_hist) &&
+                  sizeof(RmFrameHist) == sizeof(rm_frame_hist) && RM_HIST_NBINS == RM_HIST_BINS && sizeof(RmHistScratch) == 2096,
+              "hist_kernel writes rm_frame_hist records");
+
+// what both forms of rm_counter_hist and of rm_shade_ranged check about the frames, ahead of the device check
+int check_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames) {
+    if (width < 0 || rows < 0 || n_frames < 0) return fail(ctx, RM_E_INVALID, "negative size");
+    if (static_cast<uint64_t>(width) * static_cast<uint64_t>(rows) > UINT32_MAX) return fail(ctx, RM_E_INVALID, "more than UINT32_MAX pixels per frame");
+    if (n_frames > 65535) return fail(ctx, RM_E_INVALID, "n_frames must be in [0, 65535] (one grid dimension)");
+    return RM_OK;
+}
+
+int check_hist(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *sdf, const void *iters, const void *normal, int32_t mask,
+               int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, const void *hist) {
+    if (!hist) return fail(ctx, RM_E_INVALID, "null records");
+    if (!sdf && !iters) return fail(ctx, RM_E_INVALID, "both counters are absent");
+    if (const int rc = check_frames(ctx, width, rows, n_frames)) return rc;
+    if (mask < RM_HIST_ALL || mask > RM_HIST_BACKGROUND) return fail(ctx, RM_E_INVALID, "unknown mask");
+    if (mask != RM_HIST_ALL && !normal) return fail(ctx, RM_E_INVALID, "the mask needs the normal buffer");
+    if (bin_shift < 0 || bin_shift > 8) return fail(ctx, RM_E_INVALID, "bin_shift must be in [0, 8]");
+    if (lo_permille < 0 || lo_permille > hi_permille || hi_permille > 1000) return fail(ctx, RM_E_INVALID, "need 0 <= lo_permille <= hi_permille <= 1000");
+    if ((reinterpret_cast<uintptr_t>(sdf) | reinterpret_cast<uintptr_t>(iters)) & 1) return fail(ctx, RM_E_INVALID, "the counters must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(hist) & 7) return fail(ctx, RM_E_INVALID, "the records must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU histogram path");
+    return RM_OK;
+}
+
+int check_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const void *values, const void *hist,
+                       uint32_t lo, uint32_t hi, const void *rgba) {
+    if (!rgba) return fail(ctx, RM_E_INVALID, "null image");
+    if (!values) return fail(ctx, RM_E_INVALID, "null counter buffer");
+    if (counter != 0 && counter != 1) return fail(ctx, RM_E_INVALID, "counter must be 0 (sdf) or 1 (iters)");
+    if (const int rc = check_frames(ctx, width, rows, n_frames)) return rc;
+    if (!hist && lo > hi) return fail(ctx, RM_E_INVALID, "lo > hi");
+    if (reinterpret_cast<uintptr_t>(values) & 1) return fail(ctx, RM_E_INVALID, "the counter must be 2-byte aligned");
+    if (reinterpret_cast<uintptr_t>(hist) & 7) return fail(ctx, RM_E_INVALID, "the records must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU shading path");
+    return RM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1241,6 +1312,7 @@ void rm_destroy(rm_ctx *ctx) {
         ctx->oct_tables.release();
         ctx->frames.release();
         ctx->compare.release();
+        ctx->hists.release();
         if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     }
     delete ctx;
@@ -1509,6 +1581,104 @@ int rm_compare_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames
     if (rc) return rc;
     if (image) RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
     if (stats) RM_HIP(ctx, st.out(stats, o_stats, sizeof(rm_compare_stats) * n));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_counter_hist_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *d_sdf, const void *d_iters,
+                           const void *d_normal, int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, void *d_hist,
+                           void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_hist(ctx, width, rows, n_frames, d_sdf, d_iters, d_normal, mask, bin_shift, lo_permille, hi_permille, d_hist);
+    if (rc || n_frames == 0) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t hs = static_cast<hipStream_t>(stream);
+    RmHistArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.sdf = static_cast<const uint16_t *>(d_sdf);
+    args.iters = static_cast<const uint16_t *>(d_iters);
+    args.normal = mask == RM_HIST_ALL ? nullptr : static_cast<const uint8_t *>(d_normal);
+    args.hist = static_cast<RmFrameHist *>(d_hist);
+    args.npx = static_cast<int64_t>(width) * rows;  // (0: one workgroup per frame writes the empty records)
+    args.shift = static_cast<unsigned int>(bin_shift);
+    args.lo_permille = static_cast<unsigned int>(lo_permille);
+    args.hi_permille = static_cast<unsigned int>(hi_permille);
+    args.want_surface = mask == RM_HIST_SURFACE;
+    const int32_t per_frame = rm_compare_blocks_per_frame(args.npx, n_frames);
+    // frames of several workgroups add into scratch entries of the context's ring
+    const size_t entries = per_frame > 1 ? static_cast<size_t>(n_frames) : 0;
+    size_t first = 0;
+    if (entries) {
+        RM_HIP(ctx, ctx->hists.take(entries, &first));
+        args.scratch = ctx->hists.entries + first;
+    }
+    const hipError_t e = rm_launch_hist(args, mask != RM_HIST_ALL, n_frames, per_frame, hs, &ctx->last_kernel);
+    if (entries) ctx->hists.launched(first, entries, hs);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_counter_hist_device");
+    return RM_OK;
+}
+
+int rm_counter_hist(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint16_t *sdf, const uint16_t *iters,
+                    const uint8_t *normal, int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, rm_frame_hist *hist) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_hist(ctx, width, rows, n_frames, sdf, iters, normal, mask, bin_shift, lo_permille, hi_permille, hist);
+    if (rc || n_frames == 0) return rc;
+    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const bool masked = mask != RM_HIST_ALL;
+    const size_t o_sdf = st.region(sdf ? 2 * total : 0), o_iters = st.region(iters ? 2 * total : 0), o_normal = st.region(masked ? 3 * total : 0),
+                 o_hist = st.region(sizeof(rm_frame_hist) * n);
+    if ((rc = st.reserve())) return rc;
+    if (sdf && total) RM_HIP(ctx, st.in(o_sdf, sdf, 2 * total));
+    if (iters && total) RM_HIP(ctx, st.in(o_iters, iters, 2 * total));
+    if (masked && total) RM_HIP(ctx, st.in(o_normal, normal, 3 * total));
+    rc = rm_counter_hist_device(ctx, width, rows, n_frames, sdf ? st.at<void>(o_sdf) : nullptr, iters ? st.at<void>(o_iters) : nullptr,
+                                masked ? st.at<void>(o_normal) : nullptr, mask, bin_shift, lo_permille, hi_permille, st.at<void>(o_hist), ctx->stream);
+    if (rc) return rc;
+    RM_HIP(ctx, st.out(hist, o_hist, sizeof(rm_frame_hist) * n));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_shade_ranged_device(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const void *d_counter,
+                           const void *d_hist, uint32_t lo, uint32_t hi, void *d_rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_ranged(ctx, counter, width, rows, n_frames, d_counter, d_hist, lo, hi, d_rgba);
+    if (rc) return rc;
+    RmShadeRangedArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.values = static_cast<const uint16_t *>(d_counter);
+    args.hist = static_cast<const RmFrameHist *>(d_hist);
+    args.rgba = static_cast<uint8_t *>(d_rgba);
+    args.npx = static_cast<int64_t>(width) * rows;
+    args.counter = static_cast<unsigned int>(counter);
+    args.lo = lo;
+    args.hi = hi;
+    if (n_frames == 0 || args.npx == 0) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = rm_launch_shade_ranged(args, n_frames, static_cast<hipStream_t>(stream), &ctx->last_kernel);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_ranged_device");
+    return RM_OK;
+}
+
+int rm_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const uint16_t *values,
+                    const rm_frame_hist *hist, uint32_t lo, uint32_t hi, uint8_t *rgba) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_shade_ranged(ctx, counter, width, rows, n_frames, values, hist, lo, hi, rgba);
+    if (rc) return rc;
+    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
+    if (!total) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const size_t o_val = st.region(2 * total), o_hist = st.region(hist ? sizeof(rm_frame_hist) * n : 0), o_rgba = st.region(4 * total);
+    if ((rc = st.reserve())) return rc;
+    RM_HIP(ctx, st.in(o_val, values, 2 * total));
+    if (hist) RM_HIP(ctx, st.in(o_hist, hist, sizeof(rm_frame_hist) * n));
+    rc = rm_shade_ranged_device(ctx, counter, width, rows, n_frames, st.at<void>(o_val), hist ? st.at<void>(o_hist) : nullptr, lo, hi,
+                                st.at<void>(o_rgba), ctx->stream);
+    if (rc) return rc;
+    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
     RM_HIP(ctx, st.sync());
     return RM_OK;
 }

@@ -369,6 +369,317 @@ __global__ __launch_bounds__(256) void compare_kernel(const RmCompareArgs A) {
     }
 }
 
+// ------------------------------------------------------------------ hist_kernel (rm_counter_hist_device)
+//
+// The distribution of the two counters of each frame: 256 bins of min(v >> shift, 255) per counter, with the sum, minimum and
+// maximum of the pixels the mask selects and two percentiles derived from the bins.  The shape is compare_kernel's: blockIdx.y
+// is the frame, blockIdx.x a share of its pixels, a lane takes GROUPS of 16 consecutive pixels (32 B of each counter, 48 B of
+// normal when the mask needs it) with the same head / tail and misaligned-slice handling.
+//   * bins: one LDS histogram per WAVE and counter (4 x 2 x 256 words), ds_add without a return value.  The data names the
+//     hazard: background pixels all carry one value, so most lanes of most waves of a rendered frame would add 1 at ONE LDS
+//     address, and same-address LDS atomics of a wave-instruction serialise.  So nothing is added per pixel: a lane keeps the
+//     run in hand (bin, length) per counter in registers, ACROSS its groups, and touches LDS only when the bin changes -- a
+//     lane that sees one value makes no LDS access until the end.  At the end the lanes whose run is in the bin of the wave's
+//     first lane add their lengths up by __shfl_down and the first lane makes ONE add for them (a constant frame: one add
+//     per wave and counter); the others add their own;
+//   * sum, min, max: per lane in registers (sums of a group in 32 bits, folded into 64 bits per group), per wave by
+//     __shfl_down, per workgroup in LDS, as cmp_block_reduce does;
+//   * across workgroups: a frame of one workgroup finishes from its LDS.  Otherwise every lane adds its non-zero bin of each
+//     counter to the frame's scratch histogram (RmHistScratch, agent-scope atomics executed at the memory side; sum by add,
+//     max and ~min by max, so all-zero is the neutral state), waits for them, and after the barrier the first lane takes a
+//     ticket; the workgroup with the last ticket acquires, reads the scratch with all its lanes, leaves it all zero for its
+//     next user and finishes.  Integer adds commute: the same bytes whatever the launch shape;
+//   * finishing a counter: 256 lanes, one bin each -- an inclusive prefix sum (__shfl_up in the wave, wave totals in LDS), M =
+//     the total, r = p (M - 1) / 1000, and the lane with exclusive <= r < inclusive is b_p.  The record is written whole.
+
+struct HistAcc {
+    unsigned int bin[2], cnt[2];  // the run in hand
+    unsigned int group[2], mn[2], mx[2];
+    unsigned long long sum[2];
+};
+
+__device__ __forceinline__ void hist_value(HistAcc &a, int c, unsigned int *h, unsigned int v, unsigned int shift) {
+    const unsigned int b = min(v >> shift, 255u);
+    if (b != a.bin[c]) {  // the run ends: its length goes to the wave's histogram (a first run of length 0 adds 0)
+        (void)__hip_atomic_fetch_add(&h[a.bin[c]], a.cnt[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        a.bin[c] = b;
+        a.cnt[c] = 0;
+    }
+    ++a.cnt[c];
+    a.group[c] += v;
+    a.mn[c] = min(a.mn[c], v);
+    a.mx[c] = max(a.mx[c], v);
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void hist_pixel(HistAcc &a, unsigned int *hs, unsigned int *hi, bool has_s, bool has_i, unsigned int n,
+                                           unsigned int s, unsigned int i, unsigned int shift, bool want_surface) {
+    if (MASKED && (n != 0x808080u) != want_surface) return;  // raymarcher.ts:97-105
+    if (has_s) hist_value(a, 0, hs, s, shift);
+    if (has_i) hist_value(a, 1, hi, i, shift);
+}
+
+template <bool MASKED>
+__global__ __launch_bounds__(256) void hist_kernel(const RmHistArgs A) {
+    __shared__ unsigned int bins[4][2][RM_HIST_NBINS];  // [wave][counter][bin]
+    __shared__ unsigned long long sh_sum[4][2];
+    __shared__ unsigned int sh_mm[4][4], sh_scan[4], sh_pick[2], sh_last;
+    const unsigned int f = blockIdx.y, t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const long long N = A.npx, first = static_cast<long long>(f) * N;
+    const bool has_s = A.sdf != nullptr, has_i = A.iters != nullptr, has_n = MASKED, want_surface = A.want_surface != 0;
+    const uint16_t *ps = has_s ? A.sdf + first : nullptr, *pi = has_i ? A.iters + first : nullptr;
+    const uint8_t *pn = has_n ? A.normal + 3 * first : nullptr;
+    for (unsigned int k = t; k < 4 * 2 * RM_HIST_NBINS; k += 256) (&bins[0][0][0])[k] = 0;
+    __syncthreads();
+
+    // head: the first pixel of the groups, chosen to 16-byte align as many bytes per pixel as possible (compare_kernel)
+    const uintptr_t addr[3] = {reinterpret_cast<uintptr_t>(ps), reinterpret_cast<uintptr_t>(pi), reinterpret_cast<uintptr_t>(pn)};
+    const bool used[3] = {has_s, has_i, has_n};
+    constexpr unsigned int bpp[3] = {2, 2, 3};
+    unsigned int head = 0, best = 0;
+    for (unsigned int h = 0; h < 16; ++h) {
+        unsigned int score = 0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) score += used[k] && ((addr[k] + h * bpp[k]) & 15) == 0 ? bpp[k] : 0u;
+        if (score > best) {
+            best = score;
+            head = h;
+        }
+    }
+    if (head > N) head = static_cast<unsigned int>(N);
+    bool vec[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) vec[k] = ((addr[k] + head * bpp[k]) & 15) == 0;
+    const long long groups = (N - head) >> 4, tail0 = head + (groups << 4);
+
+    HistAcc a;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        a.bin[c] = a.cnt[c] = a.group[c] = a.mx[c] = 0;
+        a.mn[c] = 0xFFFFFFFFu;
+        a.sum[c] = 0;
+    }
+    unsigned int *hs = bins[wave][0], *hi = bins[wave][1];
+
+    // head and tail: one pixel per lane of the frame's first workgroup (head + tail < 32)
+    if (blockIdx.x == 0) {
+        const long long i = t < head ? static_cast<long long>(t) : tail0 + (static_cast<long long>(t) - head);
+        if (i < N) {
+            const unsigned int n = has_n ? pn[3 * i] | pn[3 * i + 1] << 8 | pn[3 * i + 2] << 16 : 0x808080u;
+            hist_pixel<MASKED>(a, hs, hi, has_s, has_i, n, has_s ? ps[i] : 0u, has_i ? pi[i] : 0u, A.shift, want_surface);
+        }
+    }
+
+    const long long step = static_cast<long long>(gridDim.x) * 256;
+    for (long long g = static_cast<long long>(blockIdx.x) * 256 + t; g < groups; g += step) {
+        const long long p0 = head + (g << 4);  // the group's first pixel
+        unsigned int ws[8], wi[8], wn[12];
+        load_group(ps + p0, has_s, vec[0], 0u, ws);
+        load_group(pi + p0, has_i, vec[1], 0u, wi);
+        load_group(pn + 3 * p0, has_n, vec[2], 0x80808080u, wn);
+#define RM_HIST_PIXEL(P)                                                                                                          \
+    hist_pixel<MASKED>(a, hs, hi, has_s, has_i, normal_of<P>(wn), (ws[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu,                   \
+                       (wi[(P) >> 1] >> (16 * ((P) & 1))) & 0xFFFFu, A.shift, want_surface);
+        RM_HIST_PIXEL(0) RM_HIST_PIXEL(1) RM_HIST_PIXEL(2) RM_HIST_PIXEL(3) RM_HIST_PIXEL(4) RM_HIST_PIXEL(5) RM_HIST_PIXEL(6) RM_HIST_PIXEL(7)
+        RM_HIST_PIXEL(8) RM_HIST_PIXEL(9) RM_HIST_PIXEL(10) RM_HIST_PIXEL(11) RM_HIST_PIXEL(12) RM_HIST_PIXEL(13) RM_HIST_PIXEL(14) RM_HIST_PIXEL(15)
+#undef RM_HIST_PIXEL
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            a.sum[c] += a.group[c];
+            a.group[c] = 0;
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 2; ++c) a.sum[c] += a.group[c];  // (the head and tail pixels)
+
+    // the runs still in hand: the lanes in the bin of the wave's first lane as ONE add, the others on their own
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const unsigned int lead = __builtin_amdgcn_readfirstlane(a.bin[c]);
+        const bool same = a.bin[c] == lead;
+        unsigned int merged = same ? a.cnt[c] : 0u;
+        for (int off = 32; off > 0; off >>= 1) merged += __shfl_down(merged, off);
+        unsigned int *h = bins[wave][c];
+        if (lane == 0) (void)__hip_atomic_fetch_add(&h[lead], merged, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (!same && a.cnt[c]) (void)__hip_atomic_fetch_add(&h[a.bin[c]], a.cnt[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+
+    // sums, minima and maxima of the workgroup -> thread 0
+    for (int off = 32; off > 0; off >>= 1) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            a.sum[c] += __shfl_down(a.sum[c], off);
+            a.mn[c] = min(a.mn[c], static_cast<unsigned int>(__shfl_down(a.mn[c], off)));
+            a.mx[c] = max(a.mx[c], static_cast<unsigned int>(__shfl_down(a.mx[c], off)));
+        }
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            sh_sum[wave][c] = a.sum[c];
+            sh_mm[wave][c] = a.mn[c];
+            sh_mm[wave][2 + c] = a.mx[c];
+        }
+    }
+    __syncthreads();  // (also: every wave's histogram is complete)
+    if (t == 0) {
+        for (int w = 1; w < 4; ++w) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                a.sum[c] += sh_sum[w][c];
+                a.mn[c] = min(a.mn[c], sh_mm[w][c]);
+                a.mx[c] = max(a.mx[c], sh_mm[w][2 + c]);
+            }
+        }
+    }
+    unsigned int x[2];  // bin t of each counter
+#pragma unroll
+    for (int c = 0; c < 2; ++c) x[c] = bins[0][c][t] + bins[1][c][t] + bins[2][c][t] + bins[3][c][t];
+
+    if (gridDim.x > 1) {
+        RmHistScratch *S = A.scratch + f;
+#pragma unroll
+        for (int c = 0; c < 2; ++c)
+            if (x[c]) (void)__hip_atomic_fetch_add(&S->bins[c][t], x[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                (void)__hip_atomic_fetch_add(&S->sum[c], a.sum[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_max(&S->max[c], a.mx[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                (void)__hip_atomic_fetch_max(&S->inv_min[c], ~a.mn[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this lane's contributions have arrived ...
+        __syncthreads();                                  // ... and every lane's, before the ticket is taken
+        if (t == 0) {
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+            const unsigned int ticket = __hip_atomic_fetch_add(&S->ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            sh_last = ticket + 1u == gridDim.x;
+            if (ticket + 1u == gridDim.x) {
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // ... and the invalidate is over before the barrier lets the others load
+            }
+        }
+        __syncthreads();
+        if (!sh_last) return;
+#pragma unroll
+        for (int c = 0; c < 2; ++c) {
+            x[c] = __hip_atomic_load(&S->bins[c][t], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&S->bins[c][t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // all zero for the entry's next user
+        }
+        if (t == 0) {
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                a.sum[c] = __hip_atomic_load(&S->sum[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                a.mx[c] = __hip_atomic_load(&S->max[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                a.mn[c] = ~__hip_atomic_load(&S->inv_min[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&S->sum[c], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&S->max[c], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(&S->inv_min[c], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            __hip_atomic_store(&S->ticket, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+
+    // the frame's two records
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        RmCounterHist *rec = c ? &A.hist[f].iters : &A.hist[f].sdf;
+        unsigned int incl = x[c];
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned int y = __shfl_up(incl, off);
+            if (lane >= static_cast<unsigned int>(off)) incl += y;
+        }
+        if (lane == 63) sh_scan[wave] = incl;
+        if (t == 0) sh_pick[0] = sh_pick[1] = 0;
+        __syncthreads();
+        unsigned int M = 0;
+        for (unsigned int w = 0; w < 4; ++w) {
+            if (w < wave) incl += sh_scan[w];
+            M += sh_scan[w];
+        }
+        // b_p: the smallest b with bins[0] + .. + bins[b] > r
+        const unsigned long long span = M ? M - 1u : 0u;
+        const unsigned int r_lo = static_cast<unsigned int>(A.lo_permille * span / 1000u), r_hi = static_cast<unsigned int>(A.hi_permille * span / 1000u);
+        if (M && incl > r_lo && incl - x[c] <= r_lo) sh_pick[0] = t;
+        if (M && incl > r_hi && incl - x[c] <= r_hi) sh_pick[1] = t;
+        __syncthreads();
+        if (t == 0) {
+            const unsigned int mn = M ? a.mn[c] : 0u, mx = M ? a.mx[c] : 0u, b_lo = sh_pick[0], b_hi = sh_pick[1];
+            rec->pixels = M;
+            rec->sum = M ? a.sum[c] : 0ull;
+            rec->min = mn;
+            rec->max = mx;
+            rec->range_lo = M ? max(mn, b_lo << A.shift) : 0u;
+            rec->range_hi = !M ? 0u : b_hi == 255u ? mx : min(mx, ((b_hi + 1u) << A.shift) - 1u);
+            rec->shift = A.shift;
+            rec->reserved = 0;
+        }
+        rec->bins[t] = x[c];
+        __syncthreads();  // (sh_scan and sh_pick are written again for the second counter)
+    }
+}
+
+// ------------------------------------------------------------------ shade_ranged_kernel (rm_shade_ranged_device)
+//
+// The heatmap ramp of IterationHeatmap.ts:26-29 over a range instead of counter * 5 % 256: s = 0 up to lo, 255 from hi,
+// (v - lo) * 255 / (hi - lo) between.  One pass, 2 B read and 4 B written per pixel: a lane takes groups of 8 pixels (one 16-byte
+// load, two 16-byte stores) that start `head` pixels into the frame, where the counter slice is 16-byte aligned; an image slice
+// that is misaligned there is stored pixel by pixel; head and tail (< 16 pixels) go to the first lanes of the frame's first
+// workgroup.  lo and hi are the same for the whole workgroup: the kernel arguments, or two scalar loads from the frame's
+// record.  The division is by a workgroup-uniform d = hi - lo and of n = (v - lo) * 255 < 2^24: with d <= 2^L, k = 24 + L and
+// m = ceil(2^k / d) < 2^25 + 1, (n * m) >> k == n / d exactly (m d - 2^k < d <= 2^L, so n (m d - 2^k) < 2^k).
+__device__ __forceinline__ unsigned int ranged_pixel(unsigned int v, unsigned int lo, unsigned int hi, unsigned int m, unsigned int k) {
+    const unsigned int q = static_cast<unsigned int>((static_cast<unsigned long long>((v - lo) * 255u) * m) >> k);
+    const unsigned int s = v <= lo ? 0u : v >= hi ? 255u : q;
+    return 0xFF000000u | min(2u * s, 255u) | (min(512u - 2u * s, 255u) << 8);
+}
+
+__global__ __launch_bounds__(256) void shade_ranged_kernel(const RmShadeRangedArgs A) {
+    const unsigned int f = blockIdx.y, t = threadIdx.x;
+    const long long N = A.npx, first = static_cast<long long>(f) * N;
+    const uint16_t *val = A.values + first;
+    uint8_t *rgba = A.rgba + 4 * first;
+    unsigned int lo = A.lo, hi = A.hi;
+    if (A.hist) {
+        const RmCounterHist *rec = A.counter ? &A.hist[f].iters : &A.hist[f].sdf;
+        lo = rec->range_lo;
+        hi = rec->range_hi;
+    }
+    const unsigned int d = hi > lo ? hi - lo : 1u;
+    const unsigned int k = 24u + (d > 1u ? 32u - static_cast<unsigned int>(__builtin_clz(d - 1u)) : 0u);
+    const unsigned long long pow2 = 1ull << k;
+    unsigned int m = static_cast<unsigned int>(static_cast<double>(pow2) / static_cast<double>(d));  // ceil(2^k / d), made exact below
+    while (static_cast<unsigned long long>(m) * d < pow2) ++m;
+    while (m > 1u && static_cast<unsigned long long>(m - 1u) * d >= pow2) --m;
+
+    const bool whole = (reinterpret_cast<uintptr_t>(rgba) & 3) == 0;
+    unsigned int head = static_cast<unsigned int>(((16u - (reinterpret_cast<uintptr_t>(val) & 15u)) & 15u) >> 1);
+    if (head > N) head = static_cast<unsigned int>(N);
+    const bool vec_in = ((reinterpret_cast<uintptr_t>(val) + 2 * head) & 15) == 0, vec_out = ((reinterpret_cast<uintptr_t>(rgba) + 4 * head) & 15) == 0;
+    const long long groups = (N - head) >> 3, tail0 = head + (groups << 3);
+    if (blockIdx.x == 0) {
+        const long long i = t < head ? static_cast<long long>(t) : tail0 + (static_cast<long long>(t) - head);
+        if (i < N) store_pixel(rgba, i, ranged_pixel(val[i], lo, hi, m, k), whole);
+    }
+    const long long step = static_cast<long long>(gridDim.x) * 256;
+    for (long long g = static_cast<long long>(blockIdx.x) * 256 + t; g < groups; g += step) {
+        const long long p0 = head + (g << 3);
+        unsigned int w[4], px[8];
+        load_group(val + p0, true, vec_in, 0u, w);
+#pragma unroll
+        for (int p = 0; p < 8; ++p) px[p] = ranged_pixel((w[p >> 1] >> (16 * (p & 1))) & 0xFFFFu, lo, hi, m, k);
+        if (vec_out) {
+            uint4 *out = reinterpret_cast<uint4 *>(rgba + 4 * p0);
+            out[0] = make_uint4(px[0], px[1], px[2], px[3]);
+            out[1] = make_uint4(px[4], px[5], px[6], px[7]);
+        } else {
+#pragma unroll
+            for (int p = 0; p < 8; ++p) store_pixel(rgba, p0 + p, px[p], whole);
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
@@ -422,5 +733,31 @@ hipError_t rm_launch_compare(const RmCompareArgs &a, int32_t map, int32_t n_fram
     }
 #undef RM_CMP_CASE
     if (kernel_name) *kernel_name = name;
+    return hipGetLastError();
+}
+
+
+hipError_t rm_launch_hist(const RmHistArgs &a, bool masked, int32_t n_frames, int32_t blocks_per_frame, hipStream_t stream,
+                          const char **kernel_name) {
+    if (n_frames <= 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(blocks_per_frame), static_cast<unsigned>(n_frames)), block(256);
+    if (masked) hipLaunchKernelGGL((hist_kernel<true>), grid, block, 0, stream, a);
+    else hipLaunchKernelGGL((hist_kernel<false>), grid, block, 0, stream, a);
+    if (kernel_name) *kernel_name = masked ? "hist_kernel<true>" : "hist_kernel<false>";
+    return hipGetLastError();
+}
+
+int32_t rm_shade_ranged_blocks_per_frame(int64_t npx, int32_t n_frames) {
+    // ~4096 workgroups per launch, at most 2048 per frame (a lane of a 4K frame takes two groups), never more than the frame has groups for
+    const int64_t want = (npx / 8 + 255) / 256, share = n_frames > 0 ? 4096 / n_frames : 1;
+    const int64_t cap = share > 2048 ? 2048 : share;
+    return static_cast<int32_t>(want < 1 || cap < 1 ? 1 : want < cap ? want : cap);
+}
+
+hipError_t rm_launch_shade_ranged(const RmShadeRangedArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name) {
+    if (n_frames <= 0 || a.npx <= 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>(rm_shade_ranged_blocks_per_frame(a.npx, n_frames)), static_cast<unsigned>(n_frames)), block(256);
+    hipLaunchKernelGGL(shade_ranged_kernel, grid, block, 0, stream, a);
+    if (kernel_name) *kernel_name = "shade_ranged_kernel";
     return hipGetLastError();
 }

@@ -50,6 +50,39 @@ struct RmCompareArgs {
     unsigned int gain;
 };
 
+// rm_counter_hist_device / rm_shade_ranged_device (rm_frame_ops.hip, hist_kernel and shade_ranged_kernel).
+constexpr int RM_HIST_NBINS = 256;
+struct RmCounterHist {  // rm_counter_hist
+    unsigned long long pixels, sum;
+    unsigned int min, max, range_lo, range_hi, shift, reserved;
+    unsigned int bins[RM_HIST_NBINS];
+};
+struct RmFrameHist {  // rm_frame_hist
+    RmCounterHist sdf, iters;
+};
+struct RmHistScratch {  // what the workgroups of one frame add into (index 0 sdf, 1 iters); all zero before and after the launch
+    unsigned int bins[2][RM_HIST_NBINS];
+    unsigned long long sum[2];
+    unsigned int max[2], inv_min[2];  // inv_min: the maximum of ~v, so that zero is neutral
+    unsigned int ticket, pad[3];
+};
+struct RmHistArgs {
+    const uint16_t *sdf, *iters;  // either may be null
+    const uint8_t *normal;        // read by hist_kernel<true> only
+    RmFrameHist *hist;            // one per frame
+    RmHistScratch *scratch;       // one per frame; unused (may be null) with one workgroup per frame
+    long long npx;                // pixels of a frame
+    unsigned int shift, lo_permille, hi_permille;
+    unsigned int want_surface;    // hist_kernel<true>: 1 counts surface pixels, 0 background pixels
+};
+struct RmShadeRangedArgs {
+    const uint16_t *values;
+    const RmFrameHist *hist;  // null: lo and hi below for every frame
+    uint8_t *rgba;
+    long long npx;
+    unsigned int counter, lo, hi;  // counter: 0 takes hist[k].sdf, 1 hist[k].iters
+};
+
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
 // instantiation that was launched (static string).
@@ -122,6 +155,13 @@ hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride
 int32_t rm_compare_blocks_per_frame(int64_t npx, int32_t n_frames);
 hipError_t rm_launch_compare(const RmCompareArgs &a, int32_t map, int32_t n_frames, int32_t blocks_per_frame, hipStream_t stream,
                              const char **kernel_name);
+
+// rm_counter_hist_device: ONE launch of hist_kernel<masked> over n_frames frames of a.npx pixels (0 included), blocks_per_frame
+// workgroups each (rm_compare_blocks_per_frame: the same shape); a.scratch holds one entry per frame when blocks_per_frame > 1.
+hipError_t rm_launch_hist(const RmHistArgs &a, bool masked, int32_t n_frames, int32_t blocks_per_frame, hipStream_t stream,
+                          const char **kernel_name);
+// rm_shade_ranged_device: ONE launch of shade_ranged_kernel; nothing without a pixel or a frame.
+hipError_t rm_launch_shade_ranged(const RmShadeRangedArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name);
 
 hipError_t rm_launch_hypot(const float *xyz, int64_t n, double *out, hipStream_t stream);
 // rm_jsmath.h on the device: fn 0 sin, 1 cos, 2 atan2, 3 asin, 4 log, 5 pow, 6 round, 7 atan

@@ -22,7 +22,7 @@ from typing import Optional
 import numpy as np
 
 from . import _native as N
-from .context import Context, _is_torch, camera_rays, partition_rows
+from .context import Context, _is_torch, camera_rays, partition_rows, percentile  # noqa: F401
 
 ALGORITHMS = ("sphere-tracer", "fixed-step", "adaptive-step", "adaptive-step-v2", "adaptive-step-v3")
 SHADERS = ("normal", "phong", "sdf-heatmap", "iteration-heatmap")
@@ -280,6 +280,41 @@ class SDFHeatmap(ShadingModel):
 
 class IterationHeatmap(ShadingModel):
     name = "iteration-heatmap"
+
+
+class _RangedHeatmap(ShadingModel):
+    """Build-defined, beside the factory (createShadingModelFromValue keeps the reference's mapping): the heatmap of one
+    counter scaled from 0 to the hi_permille percentile of the frame's own histogram of that counter (Context.counter_hist,
+    then Context.shade_ranged from the same record, with no host round trip in between on device buffers), so it never wraps
+    as counter * 5 % 256 does.  `mask`, `bin_shift`: as counter_hist takes them.  After shade(), `hist` holds the frame's
+    record buffer (Context.decode_hists)."""
+    counter = "sdf"
+
+    def __init__(self, ctx: Optional[Context] = None, device=0, hi_permille=1000, mask="all", bin_shift=0):
+        super().__init__(ctx, device)
+        self.hi_permille, self.mask, self.bin_shift = int(hi_permille), mask, int(bin_shift)
+        self.hist = None
+
+    def shade(self, shadedBuffer, depthBuffer, normalBuffer, SDFevaluationBuffer, iterationsBuffer, width, height):
+        if self._ctx is None:
+            self._ctx = Context(self._device)
+        values = SDFevaluationBuffer if self.counter == "sdf" else iterationsBuffer
+        masked = self.mask not in ("all", 0)
+        self.hist = self._ctx.counter_hist(values if self.counter == "sdf" else None, values if self.counter == "iters" else None,
+                                           normal=normalBuffer if masked else None, mask=self.mask, bin_shift=self.bin_shift,
+                                           percentiles=(0, self.hi_permille), width=width, rows=height, n_frames=1)
+        self._ctx.shade_ranged(self.counter, values, shadedBuffer, hist=self.hist, width=width, rows=height, n_frames=1)
+        return shadedBuffer
+
+
+class RangedSDFHeatmap(_RangedHeatmap):
+    name = "ranged-sdf-heatmap"
+    counter = "sdf"
+
+
+class RangedIterationHeatmap(_RangedHeatmap):
+    name = "ranged-iteration-heatmap"
+    counter = "iters"
 
 
 def createShadingModelFromValue(selectedModel, ctx=None):  # main.ts:33-45

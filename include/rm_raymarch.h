@@ -417,6 +417,82 @@ RM_API int rm_compare_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n
                              const rm_frame_set *a, const rm_frame_set *b,
                              int32_t map, int32_t gain, uint8_t *rgba, rm_compare_stats *stats);
 
+/* ---- counter distributions per frame: histograms, percentiles, ranged heatmaps -------- */
+
+/* The reference's two heatmap shaders colour by counter * 5 % 256 (IterationHeatmap.ts:24, SDFHeatmap.ts:24) and its README
+ * warns that they "loop around": a pixel of 52 iterations looks like one of 1.  Its diagnostics are a sum, a maximum and a
+ * minimum (main.ts:528-548), which the background pixels of a frame swamp.  These entries give, on the device and for a batch of
+ * frames per launch, the histogram of each counter of each frame over all, the surface or the background pixels, two percentiles
+ * derived from it, and a heatmap scaled to a range -- the arguments' or those two percentiles' -- that never wraps.  Neither
+ * needs a scene. */
+#define RM_HIST_BINS 256
+typedef enum rm_hist_mask { RM_HIST_ALL = 0, RM_HIST_SURFACE = 1, RM_HIST_BACKGROUND = 2 } rm_hist_mask;
+
+struct rm_counter_hist {              /* 1064 bytes; named by its tag only: rm_counter_hist is also the host entry below */
+    uint64_t pixels;                  /* pixels the mask selects */
+    uint64_t sum;                     /* of their stored u16 values */
+    uint32_t min, max;                /* of their stored values; 0, 0 when pixels == 0 */
+    uint32_t range_lo, range_hi;      /* the two requested percentiles, rule below */
+    uint32_t shift, reserved;         /* the call's bin_shift; 0 */
+    uint32_t bins[RM_HIST_BINS];
+};
+typedef struct rm_frame_hist { struct rm_counter_hist sdf, iters; } rm_frame_hist;   /* 2128 bytes, one per frame */
+
+/* n_frames frames of width x rows pixels, device pointers, ONE launch, asynchronous on `stream`.  Frame k occupies elements
+ * [k * W * rows, (k + 1) * W * rows) of every buffer (x3 normal): the layout rm_render_frames_device writes and
+ * rm_compare_frames_device reads; n_frames = 1 is a single tile.
+ *   mask         RM_HIST_ALL: every pixel; d_normal may be NULL and is not read.  RM_HIST_SURFACE / RM_HIST_BACKGROUND: the pixels
+ *                whose normal bytes are not / are (128,128,128) -- "surface" as defined for rm_compare_stats; d_normal is needed.
+ *   bin_shift    0 .. 8: bin(v) = min(v >> bin_shift, 255).  Shift 8 covers every u16 value exactly; with smaller shifts the last
+ *                bin also holds everything above it.
+ *   d_sdf, d_iters  either may be NULL, not both; the record of an absent counter is all zero except `shift`.
+ *   lo_permille, hi_permille  0 <= lo <= hi <= 1000.  With M = pixels and a given p: r = floor(p * (M - 1) / 1000) in 64 bits, b_p
+ *                the smallest b with bins[0] + .. + bins[b] > r.  range_lo = max(min, b_lo << shift); range_hi = max when
+ *                b_hi == 255, else min(max, ((b_hi + 1) << shift) - 1).  M == 0: both 0.  range_lo <= range_hi always; with shift 0
+ *                and values below 255 they are the exact nearest-rank percentiles; 0 and 1000 give min and max.
+ *   d_hist       n_frames rm_frame_hist records (8-byte aligned), each written whole by the launch: no pre-clear, no
+ *                initialising launch, no memset on the caller's side.  Exact integers: the same bytes whatever the launch shape.
+ * width == 0, rows == 0 or n_frames == 0 is RM_OK: every one of the n_frames records is zero except `shift`.
+ * RM_E_INVALID -- checked before anything else -- for a null d_hist or both counters null; a negative size, W * rows > UINT32_MAX
+ * or n_frames > 65535 (one grid dimension); a mask outside the enum, or one other than ALL without d_normal; a shift or permille
+ * out of range; a counter pointer that is not 2-byte or a d_hist that is not 8-byte aligned.  RM_E_NO_DEVICE on a host-only
+ * context; never RM_E_NO_SCENE.  Not a render entry: it neither consumes nor fires rm_render_attach_diagnostics.  rm_last_kernel
+ * names the hist_kernel<masked> instantiation.
+ * Calls in flight: a frame of more than one workgroup (above 4 096 pixels) adds into a scratch entry of a ring in the context
+ * (2 048 entries of 2 096 bytes, one per such frame; a call takes at most 1 024, half of it); a call owns its entries until its
+ * launch is over, on whatever stream it ran, and only a call that would reuse the entries of a call still in flight waits on the
+ * host for it first -- the rule of rm_compare_frames_device's ring.  Frames of one workgroup use no entry. */
+RM_API int rm_counter_hist_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames,
+                                  const void *d_sdf, const void *d_iters, const void *d_normal,
+                                  int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille,
+                                  void *d_hist, void *stream);
+/* Same with host buffers (synchronous), staged through the context's scratch buffer. */
+RM_API int rm_counter_hist(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames,
+                           const uint16_t *sdf, const uint16_t *iters, const uint8_t *normal,
+                           int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille,
+                           rm_frame_hist *hist);
+
+/* The heatmap of one counter scaled to a range, ONE launch for n_frames frames (layout as above, x4 rgba), asynchronous on
+ * `stream`.  Per pixel value v: s = 0 if v <= lo, 255 if v >= hi, else (v - lo) * 255 / (hi - lo) by integer division; the colour
+ * is R = min(2s, 255), G = min(512 - 2s, 255), B = 0, A = 255 -- the ramp of IterationHeatmap.ts:26-29 with s in place of
+ * counter * 5 % 256, so lo = 0, hi = 51 reproduces the reference's heatmap wherever that one does not wrap.
+ *   counter      0: d_counter holds sdfEval, 1: iters (decides which record of a frame gives the range)
+ *   d_hist       NULL: every frame uses the arguments lo, hi (lo > hi is invalid).  Else n_frames rm_frame_hist records: frame k
+ *                takes range_lo, range_hi of d_hist[k].sdf or .iters, read ON THE DEVICE -- the launch may follow
+ *                rm_counter_hist_device on the same stream with no host synchronisation between them; lo and hi are ignored.
+ *   d_rgba       W * rows * n_frames * 4 bytes, written as whole pixels; no pre-clear.  Without a pixel or a frame no byte is written.
+ * RM_E_INVALID -- checked before anything else -- for a null d_rgba or d_counter, a counter other than 0 and 1, a negative size,
+ * W * rows > UINT32_MAX, n_frames > 65535, lo > hi without d_hist, a d_counter that is not 2-byte or a d_hist that is not 8-byte
+ * aligned.  RM_E_NO_DEVICE on a host-only context; never RM_E_NO_SCENE; not a render entry.  rm_last_kernel: shade_ranged_kernel.
+ * Uses no ring: no call waits. */
+RM_API int rm_shade_ranged_device(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames,
+                                  const void *d_counter, const void *d_hist, uint32_t lo, uint32_t hi,
+                                  void *d_rgba, void *stream);
+/* Same with host buffers (synchronous); hist is a host rm_frame_hist array or NULL. */
+RM_API int rm_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames,
+                           const uint16_t *values, const rm_frame_hist *hist, uint32_t lo, uint32_t hi,
+                           uint8_t *rgba);
+
 /* Multi-GPU sharding of one Job (replaces the contiguous ceil(H/N) split of main.ts:444-449
  * by a load-balanced one): the rows [y_start, y_end) are cut into stripes of `stripe_rows`
  * rows dealt round-robin over `n_parts`; this call renders, in ONE launch, the stripes of
