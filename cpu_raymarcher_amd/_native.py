@@ -129,6 +129,7 @@ SIGNATURES = {
     "rm_scene_get_info": (C.c_int, [_VP, C.POINTER(rm_scene_info)]),
     "rm_camera_from_angles": (C.c_int, [C.c_double, C.c_double, _VP, _VP]),
     "rm_scene_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
+    "rm_debug_wave_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

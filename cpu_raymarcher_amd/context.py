@@ -219,6 +219,14 @@ class Context:
         N.check(self._h, N.lib().rm_scene_distance(self._h, _ptr(p), len(p), _ptr(dist), _ptr(cnt)))
         return dist, cnt
 
+    def wave_distance(self, points):
+        """scene_distance through the v2 wave loop's distance function (rm_debug_wave_distance; BVH sphere scenes)."""
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        dist = np.zeros(len(p), np.float64)
+        cnt = np.zeros(len(p), np.uint32)
+        N.check(self._h, N.lib().rm_debug_wave_distance(self._h, _ptr(p), len(p), _ptr(dist), _ptr(cnt)))
+        return dist, cnt
+
     def ray_march(self, origins, directions, algorithm="sphere-tracer", normal=True, time=0.0, overshoot=None, step=None):
         """Raymarcher.rayMarch (+ getNormal at hits when `normal`) for caller-supplied rays through the active scene
         (rm_ray_march).  origins, directions: float32 [n, 3] (directions are used as given, not normalised).  Returns

@@ -33,7 +33,7 @@ namespace {
 #define RM_SCENE_ARRAYS(X)                                                                                                        \
     X(spheres, 1) X(radii, 1) X(bvh, 1) X(bvh_prims, 1) X(oct, 1) X(oct_prims, 1) X(pq_cells, 1) X(pq_list, 1) X(nn_cells, 1)      \
     X(nn_list, 1) X(prims, 1) X(prog, 1) X(obj_ranges, 1) X(oct_recs, 1) X(oct_lut, 1) X(oct_sub_hdr, 1) X(oct_sub_list, 1)       \
-    X(slot_object, 0)
+    X(slot_object, 0) X(ext_cells, 1) X(ext_list, 1)
 
 struct DeviceScene {
 #define RM_X(name, always) decltype(rmh::HostScene::name)::value_type *name = nullptr;
@@ -415,6 +415,7 @@ struct rm_ctx {
     int64_t opt_grid = 1;
     int64_t opt_nn = 2;  // per-cell nearest-candidate lists for the all-primitive fallback: 0 off, 1 on, 2 auto (scenes of
                          // <= 512 spheres, where the 48^3 candidate grid keeps the lists short: C3 2.65 -> 2.62 ms)
+    int64_t opt_ext = 1;  // the exterior candidate grid serves the all-primitive evaluations outside the BVH root box (rm_scene_host.cpp build_exterior_grid)
     int64_t opt_blocks_per_cu = 6;  // persistent workgroups per launch and CU: what the kernel's 80 VGPRs and 26 KB of LDS allow (a frame alone, round 3: 4: 1.42 ms, 6: 1.32, 7: 1.30)
     int64_t opt_lds_fill = 0;
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
@@ -763,8 +764,9 @@ int scene_n_prims(const rm_ctx *ctx) {
 }
 
 // The active scene as every kernel that evaluates it reads it (render, ray query and rm_scene_distance alike): which primitive
-// representation (RmRenderParams::general), the counts, the primitive tables and the two trees.  What only the render
-// kernels read -- grids, candidate lists, octree records -- is fill_params' business and stays null / zero elsewhere.
+// representation (RmRenderParams::general), the counts, the primitive tables and the two trees, and the exterior
+// candidate grid (option `ext`).  What only the render kernels read -- the leaf grid, its candidate lists, octree records -- is
+// fill_params' business and stays null / zero elsewhere.
 void fill_scene_view(const rm_ctx *ctx, RmRenderParams &p) {
     p.n_prims = scene_n_prims(ctx);
     p.general = ctx->host.general ? 1 : 0;
@@ -788,6 +790,16 @@ void fill_scene_view(const rm_ctx *ctx, RmRenderParams &p) {
     p.oct = ctx->dev.oct;
     p.oct_prims = ctx->dev.oct_prims;
     p.oct_lut = ctx->opt_lut ? ctx->dev.oct_lut : nullptr;
+    // the exterior candidate grid (points outside the BVH root box): read by the v2 wave loop and rm_debug_wave_distance only -- the
+    // one-ray-per-lane kernels (kernel = 1, rm_scene_distance, ray queries) ignore it and evaluate all N there
+    p.ext_cells = ctx->dev.ext_cells;
+    p.ext_list = ctx->dev.ext_list;
+    for (int k = 0; k < 3; ++k) {
+        p.ext_dim[k] = ctx->host.ext_dim[k];
+        p.ext_origin[k] = ctx->host.ext_origin[k];
+        p.ext_inv[k] = ctx->host.ext_inv[k];
+    }
+    p.use_ext = (ctx->opt_ext && ctx->host.accel == RM_ACCEL_BVH && !ctx->host.ext_cells.empty() && ctx->host.ext_dim[0] > 0) ? 1 : 0;
 }
 
 
@@ -1943,6 +1955,36 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
     return RM_OK;
 }
 
+int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
+    RM_NEED_DEVICE(ctx, "host-only context");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (n < 0 || (n > 0 && (!points_xyz || !dist || !count))) return fail(ctx, RM_E_INVALID, "bad buffers");
+    if (!n) return RM_OK;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(points_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
+    rm_ray_query q;
+    std::memset(&q, 0, sizeof q);
+    q.algorithm = RM_ALG_SPHERE_TRACER;
+    q.time = ctx->time;
+    q.overshoot_factor = q.step_size = std::numeric_limits<double>::quiet_NaN();
+    RmRenderParams p;
+    int rc = fill_query_params(ctx, &q, p);  // every option applies as it does to a render of the active scene
+    if (rc) return rc;
+    if (p.accel != RM_ACCEL_BVH || p.general || p.bvh_nodes <= 0) return fail(ctx, RM_E_UNSUPPORTED, "the wave loop's distance query serves BVH sphere scenes");
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_pts = st.region(12 * k), o_dist = st.region(8 * k), o_cnt = st.region(4 * k);
+    if ((rc = st.reserve())) return rc;
+    RM_HIP(ctx, st.in(o_pts, points_xyz, 12 * k));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_wave_distance_sqrt : rm_launch_wave_distance)(p, st.at<const float>(o_pts), n, st.at<double>(o_dist),
+                                                                                            st.at<uint32_t>(o_cnt), ctx->stream));
+    RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
+    RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
 int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                         void *d_sdf_calls, void *d_normal, void *stream) {
     return ray_query_device(ctx, false, q, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, nullptr, stream);
@@ -2179,6 +2221,7 @@ static const OptionRow kOptions[] = {
     {"hw_xcd", &rm_ctx::opt_hw_xcd, kSwitch, {}, nullptr},
     {"grid", &rm_ctx::opt_grid, kSwitch, {}, nullptr},
     {"nn", &rm_ctx::opt_nn, kRange, {0, 2}, "nn must be 0 (off), 1 (on) or 2 (auto)"},
+    {"ext", &rm_ctx::opt_ext, kSwitch, {}, nullptr},
     {"blocks_per_cu", &rm_ctx::opt_blocks_per_cu, kRange, {1, 8}, "blocks_per_cu must be in [1, 8]"},
     {"v1_lists", &rm_ctx::opt_v1_lists, kSwitch, {}, nullptr},
     {"v1_block", &rm_ctx::opt_v1_block, kSet, {64, 128, 256, 256}, "v1_block must be 64, 128 or 256"},

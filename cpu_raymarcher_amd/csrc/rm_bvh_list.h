@@ -25,6 +25,8 @@ struct SceneView {
     const uint16_t *pq_list;
     const uint32_t *nn_cells;
     const uint16_t *nn_list;
+    const uint32_t *ext_cells;  // exterior candidate grid (points outside the root box)
+    const uint16_t *ext_list;
     const double *rel;  // REL kernels: per BVH node {lo - origin, hi - origin} as doubles (LDS, built per launch)
     int n_prims, bvh_nodes;
 };

@@ -98,6 +98,10 @@ const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur
 hipError_t rm_launch_render_v2(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_render_v2_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
 
+// rm_debug_wave_distance: Scene.getDistance through the wave loop's bvh_distance_wave, one point per lane (BVH sphere scenes)
+hipError_t rm_launch_wave_distance(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);
+hipError_t rm_launch_wave_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);
+
 // the octree's node boxes relative to one camera position, for render_kernel_oct (rm_kernels.hip)
 hipError_t rm_launch_oct_frame_table(const RmOctNode *nodes, int n, const double origin[3], RmOctFrameNode *out, hipStream_t stream);
 

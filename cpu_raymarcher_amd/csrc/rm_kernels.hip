@@ -483,6 +483,8 @@ __device__ __forceinline__ SceneView v1_view(const RmRenderParams &P) {
     S.pq_list = P.pq_list;
     S.nn_cells = P.nn_cells;
     S.nn_list = P.nn_list;
+    S.ext_cells = nullptr;  // (the one-ray-per-lane kernels do not use the exterior candidate grid)
+    S.ext_list = nullptr;
     S.rel = nullptr;
     S.n_prims = P.n_prims;
     S.bvh_nodes = P.bvh_nodes;

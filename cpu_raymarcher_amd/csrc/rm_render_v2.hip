@@ -514,12 +514,34 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
             served = true;
         }
     }
+    // Points outside the root box (no leaf contains them, found == 0) through the exterior candidate grid: the
+    // cell's list holds every sphere that can attain the minimum somewhere in the cell, and feeds the same scan.  Beyond the
+    // grid, or in a cell without a list, the lane stays unserved and takes the all-N code below.
+    if (fallback && !served && P.use_ext) {
+        const float gx = (q.x - P.ext_origin[0]) * P.ext_inv[0], gy = (q.y - P.ext_origin[1]) * P.ext_inv[1], gz = (q.z - P.ext_origin[2]) * P.ext_inv[2];
+        const float lo = __builtin_fminf(__builtin_fminf(gx, gy), gz);
+        const bool inside = lo >= 0.f && gx < static_cast<float>(P.ext_dim[0]) && gy < static_cast<float>(P.ext_dim[1]) && gz < static_cast<float>(P.ext_dim[2]);
+        if (inside) {
+            const uint32_t cell = S.ext_cells[(static_cast<int>(gz) * P.ext_dim[1] + static_cast<int>(gy)) * P.ext_dim[0] + static_cast<int>(gx)];
+            const int ccnt = static_cast<int>(cell & 0xFFu);
+            if (ccnt != 255) {
+                const uint16_t *lst = S.ext_list + (cell >> 8);
+                for (int e = 0; e < ccnt; ++e) {
+                    const int id = lst[e];
+                    RM_CNT(9)
+                    scan_sphere<UR>(bs, S.spheres[id], id, q);
+                }
+                served = true;
+            }
+        }
+    }
     // Points no list serves (outside the root box: a ray that overshoots the grid after passing a sphere still takes one
     // step per remaining interval, each an evaluation of ALL primitives, scene.ts:173).  When many lanes of the wave hold
     // such a point -- whole batches do -- every lane feeds all N spheres into the SAME scan as the leaf candidates (twelve
     // instructions per sphere for one-radius scenes) and joins the one exact evaluation below; a few such lanes are
     // served one at a time by the whole wave afterwards (all_prims_wave).  Round 3: these rounds were 8 % of C3's VALU
-    // instructions with the separate estimate-and-evaluate loop.
+    // instructions with the separate estimate-and-evaluate loop.  Round 4: with the exterior grid only points beyond it, or of scenes
+    // without one, come here.
     if (fallback && !served) RM_CNT(13)
     {
         const unsigned long long unserved = __ballot(fallback && !served);
@@ -791,6 +813,8 @@ __device__ __forceinline__ SceneView scene_view(const RmRenderParams &C, unsigne
     S.pq_list = C.pq_list;
     S.nn_cells = C.nn_cells;
     S.nn_list = C.nn_list;
+    S.ext_cells = C.ext_cells;
+    S.ext_list = C.ext_list;
     S.rel = nullptr;
     S.n_prims = C.n_prims;
     S.bvh_nodes = C.bvh_nodes;
@@ -1503,6 +1527,26 @@ __global__ __launch_bounds__(256, RM_V2_WAVES) void render_kernel_v2(const RmRen
     render_v2_body<ACCEL, LDS, UR, REL>(P);
 }
 
+// Test entry (rm_debug_wave_distance): Scene.getDistance of a BVH sphere scene as the wave loop evaluates it -- bvh_distance_wave,
+// one point per lane, the tables read from global memory -- for a batch of points.  Lanes past the end take part without a point.
+template <bool UR>
+__global__ __launch_bounds__(256) void wave_distance_kernel(const RmRenderParams P, const float *pts, int64_t n, double *dist, uint32_t *count) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * 256 + threadIdx.x;
+    const bool need = i < n;
+    Vec3f q;
+    q.x = need ? pts[3 * i] : 0.f;
+    q.y = need ? pts[3 * i + 1] : 0.f;
+    q.z = need ? pts[3 * i + 2] : 0.f;
+    const SceneView S = scene_view<2, false, false>(P, nullptr);
+    uint32_t c = 0;
+    NormalAux aux;
+    const double d = bvh_distance_wave<UR>(P, S, need, q, c, static_cast<int>(threadIdx.x & 63), P.coop != 0, P.filter != 0, P.use_grid != 0, nullptr, &aux);
+    if (need) {
+        dist[i] = d;
+        count[i] = c;
+    }
+}
+
 size_t scene_lds_bytes(const RmRenderParams &p) {
     auto up = [](size_t v) { return (v + 15) & ~static_cast<size_t>(15); };
     size_t b = 0;
@@ -1582,6 +1626,15 @@ hipError_t rm_launch_lpt_sort(const uint8_t *cost_prev, uint16_t *perm, int stri
     return hipGetLastError();
 }
 #endif
+
+hipError_t RM_LEN_VARIANT(rm_launch_wave_distance)(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream) {
+    if (p.accel != 2 || p.general || p.bvh_nodes <= 0) return hipErrorInvalidValue;
+    if (n <= 0) return hipSuccess;
+    const dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
+    if (p.uniform_radius) hipLaunchKernelGGL(wave_distance_kernel<true>, grid, block, 0, stream, p, points, n, dist, count);
+    else hipLaunchKernelGGL(wave_distance_kernel<false>, grid, block, 0, stream, p, points, n, dist, count);
+    return hipGetLastError();
+}
 
 hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipStream_t stream, const char **kernel_name) {
     RmRenderParams p = p_in;

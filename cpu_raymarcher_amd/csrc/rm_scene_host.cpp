@@ -291,6 +291,100 @@ void build_point_query_grid(HostScene &s) {
             }
 }
 
+// Nearest-candidate lists for points OUTSIDE the root box.  A ray that has passed the scene still takes one march step per
+// remaining interval (bvh.ts:222-239, sphereTracer.ts:67), each at a point no leaf contains: scene.ts:173 evaluates every
+// primitive there.  The region is the root box grown to the cube |x_k| <= kExtReach (and by half a unit at least): the orbit
+// camera sits 3 from the origin (camera.ts:13) and looks at it with a half angle of acos(1 / sqrt 3) at the frame's corners,
+// an evaluation point has t <= 10, so it lies within sqrt(109 - 60 / sqrt 3) = 8.63 of the origin.  Points beyond the
+// region are not an error: the device evaluates all N for them, as it does without this grid.
+// The lists follow the rule of the interior grid above (same bounds, same 3 % growth, same margin), so the same argument
+// holds: whatever is not listed has lb_j > min_k ub_k >= min_k sdf_k(p) for every point p of the cell.  A cell whose grown
+// box lies inside the root box receives no exterior point and stays 255.
+// Refused (no grid): general scenes, fewer than 16 or more than 2048 spheres, a root box that covers the whole region.
+void build_exterior_grid(HostScene &s) {
+    const double kExtReach = 8.7;  // > sqrt(3^2 + 10^2 - 2 * 3 * 10 / sqrt 3): orbit radius 3 (camera_from_angles), MAX_DIST 10 (raymarcher.ts)
+    if (s.general || s.program || s.bvh.empty()) return;
+    const size_t n = s.spheres.size();
+    if (n < 16 || n > 2048) return;
+    int g = 32;
+    while (g > 8 && static_cast<unsigned long long>(g) * g * g * n > 40000000ull) g -= 4;
+    bool covered = true;
+    double w[3], lo3[3], hi3[3];
+    for (int k = 0; k < 3; ++k) {
+        covered = covered && double(s.root_min[k]) <= -kExtReach && double(s.root_max[k]) >= kExtReach;
+        lo3[k] = std::min(double(s.root_min[k]) - 0.5, -kExtReach);
+        hi3[k] = std::max(double(s.root_max[k]) + 0.5, kExtReach);
+        if (!std::isfinite(lo3[k]) || !std::isfinite(hi3[k]) || !(hi3[k] > lo3[k])) return;
+    }
+    if (covered) return;
+    for (int k = 0; k < 3; ++k) {
+        s.ext_origin[k] = static_cast<float>(lo3[k]);
+        s.ext_inv[k] = static_cast<float>(g / (hi3[k] - lo3[k]));
+        w[k] = 1.0 / double(s.ext_inv[k]);
+    }
+    s.ext_dim[0] = s.ext_dim[1] = s.ext_dim[2] = g;
+    s.ext_cells.assign(static_cast<size_t>(g) * g * g, 255);
+    const double margin = 1e-6;
+    std::vector<double> lb(n);
+    // the candidates of the box [lo, hi] among the spheres `from`, in their order
+    auto candidates = [&](const double lo[3], const double hi[3], const std::vector<uint16_t> &from, std::vector<uint16_t> &out) {
+        double U = 10.0;
+        for (size_t e = 0; e < from.size(); ++e) {
+            const size_t j = from[e];
+            const double c[3] = {s.spheres[j].cx, s.spheres[j].cy, s.spheres[j].cz};
+            double dmin2 = 0, dmax2 = 0;
+            for (int k = 0; k < 3; ++k) {
+                const double below = lo[k] - c[k], above = c[k] - hi[k];
+                const double dmin = below > 0 ? below : (above > 0 ? above : 0.0);
+                const double dmax = std::max(std::fabs(c[k] - lo[k]), std::fabs(c[k] - hi[k]));
+                dmin2 += dmin * dmin;
+                dmax2 += dmax * dmax;
+            }
+            lb[e] = std::sqrt(dmin2) - s.radii[j];
+            const double ub = std::sqrt(dmax2) - s.radii[j];
+            if (ub < U) U = ub;
+        }
+        out.clear();
+        for (size_t e = 0; e < from.size(); ++e)
+            if (lb[e] <= U + margin) out.push_back(from[e]);
+    };
+    // Two levels, for the build time (cells * n pairs otherwise: as long again as the rest of the scene build): blocks of 4^3
+    // cells first.  A cell's bounds lie between its block's (lb_j(block) <= lb_j(cell), ub_k(cell) <= ub_k(block)), so a
+    // candidate of the cell is a candidate of the block, the sphere with the smallest ub in the cell is one too, and the rule
+    // applied to the block's candidates gives the cell's list unchanged.
+    std::vector<uint16_t> all(n), block, cand;
+    std::iota(all.begin(), all.end(), static_cast<uint16_t>(0));
+    const int B = 4;  // (g is a multiple of 4)
+    for (int bz = 0; bz < g; bz += B)
+        for (int by = 0; by < g; by += B)
+            for (int bx = 0; bx < g; bx += B) {
+                const int b0[3] = {bx, by, bz};
+                double lo[3], hi[3];
+                for (int k = 0; k < 3; ++k) {
+                    lo[k] = double(s.ext_origin[k]) + (b0[k] - 0.03) * w[k];
+                    hi[k] = double(s.ext_origin[k]) + (b0[k] + B - 1 + 1.03) * w[k];
+                }
+                candidates(lo, hi, all, block);
+                for (int z = bz; z < bz + B; ++z)
+                    for (int y = by; y < by + B; ++y)
+                        for (int x = bx; x < bx + B; ++x) {
+                            const int ci[3] = {x, y, z};
+                            bool inside = true;
+                            for (int k = 0; k < 3; ++k) {  // 3 % slack: the device's binary32 cell coordinate is off by ~1e-5 cell
+                                lo[k] = double(s.ext_origin[k]) + (ci[k] - 0.03) * w[k];
+                                hi[k] = double(s.ext_origin[k]) + (ci[k] + 1.03) * w[k];
+                                inside = inside && lo[k] >= double(s.root_min[k]) && hi[k] <= double(s.root_max[k]);
+                            }
+                            if (inside) continue;  // stays 255
+                            candidates(lo, hi, block, cand);
+                            if (cand.size() >= 255 || s.ext_list.size() + cand.size() >= (1u << 24)) continue;  // stays 255
+                            const size_t c_idx = (static_cast<size_t>(z) * g + y) * g + x;
+                            s.ext_cells[c_idx] = static_cast<uint32_t>(s.ext_list.size() << 8) | static_cast<uint32_t>(cand.size());
+                            s.ext_list.insert(s.ext_list.end(), cand.begin(), cand.end());
+                        }
+            }
+}
+
 // ---- Octree (octree.ts:36-191) ----------------------------------------------------------
 
 struct OctBuilder {
@@ -468,6 +562,7 @@ static bool build_accel(HostScene &s, int n, std::string &err) {
         std::memcpy(s.root_min, root.lo, sizeof root.lo);
         std::memcpy(s.root_max, root.hi, sizeof root.hi);
         build_point_query_grid(s);  // the leaf grid only knows leaf boxes: it serves every primitive representation
+        build_exterior_grid(s);
     } else if (s.accel == 1) {
         Box root;  // scene.ts:81-85
         for (int k = 0; k < 3; ++k) {
@@ -618,6 +713,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
             s.radii.swap(rd);
             std::iota(s.bvh_prims.begin(), s.bvh_prims.end(), 0);
             for (uint16_t &e : s.nn_list) e = static_cast<uint16_t>(pos[e]);
+            for (uint16_t &e : s.ext_list) e = static_cast<uint16_t>(pos[e]);
             s.leaf_order = true;
             s.slot_object.swap(obj);
         }

@@ -69,6 +69,13 @@ struct HostScene {
     float nn_inv[3] = {0, 0, 0};
     std::vector<uint32_t> nn_cells;
     std::vector<uint16_t> nn_list;
+    // The same lists for points OUTSIDE the root box (a ray that overshoots the scene: no leaf contains the point, scene.ts:173
+    // evaluates every primitive): a coarse grid over the root box grown to where the orbit camera's rays can reach
+    // (build_exterior_grid).  Same encoding; cells that lie inside the root box stay 255.  ext_dim[0] == 0: no grid.
+    int ext_dim[3] = {0, 0, 0};
+    float ext_origin[3] = {0, 0, 0}, ext_inv[3] = {0, 0, 0};
+    std::vector<uint32_t> ext_cells;
+    std::vector<uint16_t> ext_list;
     std::vector<RmOctNode> oct;
     std::vector<int32_t> oct_prims;
     std::vector<RmSphereRec> oct_recs;  // oct_prims expanded to sphere records (sphere scenes)

@@ -204,6 +204,12 @@ struct RmRenderParams {
     int32_t leaf_order;  // BVH leaf lists are consecutive: leaf = spheres[first .. first+count), no id reads
     int32_t nn_dim[3];   // the nearest-candidate grid has its own (finer) resolution over the root box
     float nn_inv[3];
+    // exterior candidate grid (rm_scene_host.cpp build_exterior_grid): nearest-candidate lists for points outside the BVH root box
+    const uint32_t *ext_cells;
+    const uint16_t *ext_list;
+    int32_t ext_dim[3];  // cells per axis (0: no grid)
+    float ext_origin[3], ext_inv[3];
+    int32_t use_ext;     // option `ext` and the scene has the grid
     int32_t algorithm;   // rm_algorithm; 0 = sphere tracer, 1..4 the other marchers (v1 kernel)
     int32_t general;     // 0: RmSphere records; 1: RmPrim records (`prims`); 2: expression programs (`prog`); 3: programs with a Mandelbulb
     int32_t uniform_radius;  // v2: every sphere has the same radius (candidates are ranked by squared centre distance)

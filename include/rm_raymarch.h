@@ -212,6 +212,10 @@ RM_API int rm_camera_from_angles(double pitch, double yaw, float *rot9, float *o
 
 /* Scene.getDistance(position, counter) (scene.ts:144-190) for a batch of points, on the
  * device: dist[i] and count[i] (primitives evaluated) for points xyz f32[3n] (host). */
+/* Test entry: the same query for a BVH sphere scene through the distance function of the v2 wave loop (one point per lane, every
+ * option -- filter, grid, nn, ext, uniform, coop -- as in a render of the scene; csrc/rm_render_v2.hip bvh_distance_wave).  Same
+ * values and counts as rm_scene_distance, bit for bit; RM_E_UNSUPPORTED for any other scene. */
+RM_API int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count);
 RM_API int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist,
                              uint32_t *count);
 
@@ -633,6 +637,7 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *   filter 0|1 conservative binary32 bound before exact evaluations         coop 0|1 wave-cooperative all-primitive loop
  *   nodes_in_lds 0|1 scene tables staged in LDS (v2)                        list_cap 1..64 hit-leaf list entries per ray (v2)
  *   grid 0|1 leaf grid for BVH.getPrimitivesAt (v2)                         nn 0|1|2 nearest-candidate grid off|on|auto
+ *   ext 0|1       BVH (v2): all-primitive evaluations outside the root box scan the exterior candidate grid's cell list (default 1)
  *   recs, lut, sub 0|1 octree: leaf-ordered records, findNode cell table, sub-cell candidate lists
  *   blocks_per_cu 1..8, refill 1..64, hw_xcd 0|1, item_px 64|128|256       persistent-kernel scheduling (v2)
  *   static 0..95 percent of every tile queue assigned to the waves without atomics (v2; for overlapping frames)
