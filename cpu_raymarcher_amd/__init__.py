@@ -9,7 +9,8 @@ from ._native import RmError, RmUnsupported, RM_SCENE_UPLOADED
 
 _native.lib()  # raise now, not at first render, when the HIP library is missing
 
-from .context import Context, camera_from_angles, camera_rays, make_transform, partition_rows, percentile, scale_transform, sweep_views  # noqa: E402
+from .context import (Context, camera_from_angles, camera_rays, make_transform, partition_rows, percentile, phong_light,  # noqa: E402
+                      scale_transform, sweep_views)
 from .host import (ALGORITHMS, SHADERS, AdaptiveStep, AdaptiveStepV2, AdaptiveStepV3, Camera, FixedStep,  # noqa: E402
                    IterationHeatmap, Job, NormalModel, PhongModel, RangedIterationHeatmap, RangedSDFHeatmap, Raymarcher,
                    RaymarchWorker, Result, Scene,

@@ -49,6 +49,11 @@ class rm_ray_query(C.Structure):  # include/rm_raymarch.h: struct rm_ray_query
                 ("overshoot_factor", C.c_double), ("step_size", C.c_double)]
 
 
+class rm_light(C.Structure):  # include/rm_raymarch.h: struct rm_light
+    _fields_ = [("dir", C.c_float * 3), ("ao_samples", C.c_int32), ("bias", C.c_double), ("ao_step", C.c_double),
+                ("ao_strength", C.c_double)]
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -135,6 +140,13 @@ SIGNATURES = {
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),
     "rm_ray_pick": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_pick_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_ray_light": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.POINTER(rm_light), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                               _VP]),
+    "rm_ray_light_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.POINTER(rm_light), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
+                                      _VP, _VP, _VP]),
+    "rm_phong_light": (C.c_int, [_VP]),
+    "rm_shade_lit_device": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_shade_lit": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP]),
     "rm_scene_object": (C.c_int, [_VP, C.c_int32, C.POINTER(rm_node), C.c_int32, C.POINTER(C.c_int32)]),
     "rm_render_tile": (C.c_int, [_VP, C.POINTER(rm_job), _VP, _VP, _VP, _VP]),
     "rm_render_tile_device": (C.c_int, [_VP, C.POINTER(rm_job), C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),

@@ -310,6 +310,108 @@ class Context:
         dev = torch.device("cuda", self.device)
         return self.pick(torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev), algorithm, normal=False, time=time)[4]
 
+    def light(self, origins, directions, light_dir=None, bias=0.02, ao_samples=5, ao_step=0.05, ao_strength=1.0,
+              algorithm="sphere-tracer", time=0.0, overshoot=None, step=None):
+        """ray_march with normals plus two light terms at each hit, in one launch (rm_ray_light; the rule is in
+        include/rm_raymarch.h): returns (t, iters, sdf_calls, normal, lit, ao, iters2, sdf_calls2), the first four
+        bit-identical to ray_march(..., normal=True).  lit float32[n]: 0 where the surface faces away from `light_dir` or a
+        shadow ray from f32(p + n * bias) towards it, marched by the same marcher, hits something; else 1.  ao float32[n]:
+        1 - ao_strength * sum_k (k * ao_step - getDistance(p + n * k * ao_step)) / 2^(k-1) over ao_samples (0 .. 8) samples,
+        clamped to [0, 1].  iters2 / sdf_calls2: the shadow ray's iterations, and its SDF calls plus the samples'.  Misses
+        give lit = ao = 1.  light_dir None: phong_light(), the direction the Phong shader uses; it is taken as given, not
+        normalised.  The default bias must exceed the marchers' hit threshold of 0.001, or every shadow ray hits its own
+        surface at once; 0.02 is a choice that clears it on the presets, not a measured optimum.  numpy input -> the host
+        entry; torch CUDA tensors -> rm_ray_light_device on torch's current stream (counts as int32 tensors, as ray_march)."""
+        q = N.rm_ray_query()
+        q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
+        q.normal = 1
+        q.time = float(time)
+        q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
+        q.step_size = float(step) if step is not None else float("nan")
+        lt = N.rm_light()
+        lt.dir[:] = [float(v) for v in (phong_light() if light_dir is None else np.asarray(light_dir, np.float32).reshape(3))]
+        lt.ao_samples = int(ao_samples)
+        lt.bias, lt.ao_step, lt.ao_strength = float(bias), float(ao_step), float(ao_strength)
+        if _is_torch(origins) or _is_torch(directions):
+            import torch
+            if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
+                raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
+            self._same_device(dict(origins=origins, directions=directions))
+            for name, b in (("origins", origins), ("directions", directions)):
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
+                    raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
+            n = origins.numel() // 3
+            if directions.numel() != 3 * n:
+                raise ValueError("origins and directions differ in length")
+            dev = origins.device
+            out = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
+                   torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
+                   torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
+            N.check(self._h, N.lib().rm_ray_light_device(self._h, C.byref(q), C.byref(lt), n, _ptr(origins), _ptr(directions),
+                                                         *[_ptr(b) for b in out], _current_stream_ptr()))
+            return out
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        n = len(o)
+        out = (np.zeros(n, np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32),
+               np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
+        N.check(self._h, N.lib().rm_ray_light(self._h, C.byref(q), C.byref(lt), n, _ptr(o), _ptr(d), *[_ptr(b) for b in out]))
+        return out
+
+    def light_frame(self, width, height, pitch=0.0, yaw=0.0, y_start=0, y_end=None, light_dir=None, bias=0.02, ao_samples=5,
+                    ao_step=0.05, ao_strength=1.0, algorithm="sphere-tracer", time=0.0, device=False):
+        """The light terms under every pixel of rows [y_start, y_end) of a width x height frame of the active scene: the
+        frame's camera rays (camera_rays) through `light` -> (lit, ao), float32[(y_end - y_start) * width] each, tile-local
+        rows, row-major: what shade_lit takes beside the frame's depth and normal buffers.  device=True: the rays go to
+        rm_ray_light_device as CUDA tensors of this context's device and the results are tensors."""
+        if y_end is None:
+            y_end = height
+        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
+        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
+        kw = dict(light_dir=light_dir, bias=bias, ao_samples=ao_samples, ao_step=ao_step, ao_strength=ao_strength, algorithm=algorithm,
+                  time=time)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            o, dirs = torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev)
+        out = self.light(o, dirs, **kw)
+        return out[4], out[5]
+
+    def shade_lit(self, depth, normal, lit, ao, rgba, width=0, rows=0, n_frames=1):
+        """The Phong shade with the light terms of `light` / `light_frame` (rm_shade_lit_device / rm_shade_lit):
+        I = min((0.1 + diffuse * lit + specular * lit) * ao, 1); lit = ao = 1 gives the "phong" shader's bytes.  depth,
+        normal: a render's G-buffers; lit, ao: float32, one per pixel; n_frames frames of width x rows pixels, frame after
+        frame in every buffer.  torch CUDA tensors -> the device entry on torch's current stream; numpy arrays -> the host
+        entry (synchronous)."""
+        n = int(n_frames)
+        npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
+        on_dev = _check_buffers(npx, dict(depth=depth, normal=normal, rgba=rgba))
+        for name, b in (("lit", lit), ("ao", ao)):
+            if b is None:
+                continue
+            if _is_torch(b):
+                import torch
+                ok, dev, count = b.dtype == torch.float32 and b.is_contiguous(), b.is_cuda, b.numel()
+            elif isinstance(b, np.ndarray):
+                ok, dev, count = b.dtype == np.float32 and b.flags["C_CONTIGUOUS"], False, b.size
+            else:
+                raise ValueError("%s must be a numpy array or a torch tensor, not %s" % (name, type(b).__name__))
+            if not ok or count < npx:
+                raise ValueError("%s must be a contiguous float32 buffer of one element per pixel" % name)
+            if dev != on_dev and (depth is not None or normal is not None or rgba is not None):
+                raise ValueError("buffers must be all on the host or all on the device")
+        self._same_device(dict(depth=depth, normal=normal, lit=lit, ao=ao, rgba=rgba))
+        if on_dev:
+            N.check(self._h, N.lib().rm_shade_lit_device(self._h, int(width), int(rows), n, _ptr(depth), _ptr(normal), _ptr(lit), _ptr(ao),
+                                                         _ptr(rgba), _current_stream_ptr()))
+        else:
+            N.check(self._h, N.lib().rm_shade_lit(self._h, int(width), int(rows), n, _ptr(depth), _ptr(normal), _ptr(lit), _ptr(ao),
+                                                  _ptr(rgba)))
+        return rgba
+
     def scene_object(self, index):
         """Object `index` of the active scene (rm_scene_object) as (nodes, root): nodes is a list of
         (type, child_a, child_b, world_to_local float32[16], params float64[6]) in the format OracleScene.nodes() and
@@ -746,6 +848,16 @@ def camera_rays(width, height, pitch, yaw, y_start=0, y_end=None):
     if rc != N.RM_OK:
         raise N.RmError(rc, "rm_camera_rays")
     return org, dirs
+
+
+def phong_light():
+    """rm_phong_light: the binary32 light direction PhongModel normalises from (1, -1, 1.5) (phongModel.ts:15-16) ->
+    float32[3]; what the "phong" shader and Context.shade_lit shade with, and Context.light's default direction."""
+    out = np.zeros(3, np.float32)
+    rc = N.lib().rm_phong_light(_ptr(out))
+    if rc != N.RM_OK:
+        raise N.RmError(rc, "rm_phong_light")
+    return out
 
 
 def deal_stripes(rows, stripe_rows, n_parts, weights=None):

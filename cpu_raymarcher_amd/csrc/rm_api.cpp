@@ -1076,6 +1076,104 @@ int ray_query_host(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, con
     return RM_OK;
 }
 
+// what both forms of rm_ray_light check: the light (ahead of the device check, like every argument check), then check_query
+int check_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *origins, const void *dirs) {
+    if (!light) return fail(ctx, RM_E_INVALID, "null light");
+    for (int k = 0; k < 3; ++k)
+        if (!std::isfinite(light->dir[k])) return fail(ctx, RM_E_INVALID, "non-finite light direction");
+    if (light->ao_samples < 0 || light->ao_samples > 8) return fail(ctx, RM_E_INVALID, "ao_samples must be in [0, 8]");
+    if (!std::isfinite(light->bias) || light->bias < 0) return fail(ctx, RM_E_INVALID, "bias must be finite and >= 0");
+    if (!std::isfinite(light->ao_strength) || light->ao_strength < 0) return fail(ctx, RM_E_INVALID, "ao_strength must be finite and >= 0");
+    if (!std::isfinite(light->ao_step) || (light->ao_samples > 0 && !(light->ao_step > 0)))
+        return fail(ctx, RM_E_INVALID, "ao_step must be finite, and > 0 with occlusion samples");
+    return check_query(ctx, q, n, origins, dirs);
+}
+
+RmLightArgs light_args(const rm_light *light) {
+    RmLightArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.bias = light->bias;
+    a.ao_step = light->ao_step;
+    a.ao_strength = light->ao_strength;
+    std::memcpy(a.light, light->dir, sizeof a.light);
+    a.ao_samples = light->ao_samples;
+    return a;
+}
+
+int ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *d_origins, const void *d_dirs, void *d_t,
+                     void *d_iters, void *d_sdf_calls, void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_light(ctx, q, light, n, d_origins, d_dirs);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RmLightArgs a = light_args(light);
+    a.origins = static_cast<const float *>(d_origins);
+    a.dirs = static_cast<const float *>(d_dirs);
+    a.n = n;
+    a.t = static_cast<double *>(d_t);
+    a.iters = static_cast<uint32_t *>(d_iters);
+    a.sdf = static_cast<uint32_t *>(d_sdf_calls);
+    a.normal = static_cast<float *>(d_normal);
+    a.lit = static_cast<float *>(d_lit);
+    a.ao = static_cast<float *>(d_ao);
+    a.iters2 = static_cast<uint32_t *>(d_iters2);
+    a.sdf2 = static_cast<uint32_t *>(d_sdf_calls2);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_light_sqrt : rm_launch_light)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int ray_light_host(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
+                   uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_light(ctx, q, light, n, origins_xyz, dirs_xyz);
+    if (rc || !n) return rc;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // through the scratch buffer in chunks of at most 4 M rays, as ray_query_host (68 B per ray: 272 MB)
+    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
+    const size_t c = static_cast<size_t>(chunk);
+    Staging st{ctx};
+    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_t = st.region(8 * c), o_it = st.region(4 * c), o_sdf = st.region(4 * c),
+                 o_nrm = st.region(12 * c), o_lit = st.region(4 * c), o_ao = st.region(4 * c), o_it2 = st.region(4 * c), o_sdf2 = st.region(4 * c);
+    if ((rc = st.reserve())) return rc;
+    RmLightArgs a = light_args(light);
+    a.origins = st.at<const float>(o_org);
+    a.dirs = st.at<const float>(o_dirs);
+    a.t = t ? st.at<double>(o_t) : nullptr;
+    a.iters = iters ? st.at<uint32_t>(o_it) : nullptr;
+    a.sdf = sdf_calls ? st.at<uint32_t>(o_sdf) : nullptr;
+    a.normal = normal_xyz ? st.at<float>(o_nrm) : nullptr;
+    a.lit = lit ? st.at<float>(o_lit) : nullptr;
+    a.ao = ao ? st.at<float>(o_ao) : nullptr;
+    a.iters2 = iters2 ? st.at<uint32_t>(o_it2) : nullptr;
+    a.sdf2 = sdf_calls2 ? st.at<uint32_t>(o_sdf2) : nullptr;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
+        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
+        a.n = m;
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_light_sqrt : rm_launch_light)(p, a, ctx->stream, &ctx->last_kernel));
+        if (t) RM_HIP(ctx, st.out(t + at, o_t, 8 * k));
+        if (iters) RM_HIP(ctx, st.out(iters + at, o_it, 4 * k));
+        if (sdf_calls) RM_HIP(ctx, st.out(sdf_calls + at, o_sdf, 4 * k));
+        if (normal_xyz) RM_HIP(ctx, st.out(normal_xyz + 3 * at, o_nrm, 12 * k));
+        if (lit) RM_HIP(ctx, st.out(lit + at, o_lit, 4 * k));
+        if (ao) RM_HIP(ctx, st.out(ao + at, o_ao, 4 * k));
+        if (iters2) RM_HIP(ctx, st.out(iters2 + at, o_it2, 4 * k));
+        if (sdf_calls2) RM_HIP(ctx, st.out(sdf_calls2 + at, o_sdf2, 4 * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
 // Object `index` of the active scene as an rm_scene_from_nodes forest (operands before their user, the object's root last),
 // from the description the scene was built from: the upload as it was given (spheres as sphere leaves at
 // SceneManager.getTransform of their centre), or the preset's objects as the reference holds them -- vec3 members
@@ -1265,6 +1363,15 @@ int check_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows
     if (!hist && lo > hi) return fail(ctx, RM_E_INVALID, "lo > hi");
     if (reinterpret_cast<uintptr_t>(values) & 1) return fail(ctx, RM_E_INVALID, "the counter must be 2-byte aligned");
     if (reinterpret_cast<uintptr_t>(hist) & 7) return fail(ctx, RM_E_INVALID, "the records must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU shading path");
+    return RM_OK;
+}
+
+int check_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *depth, const void *normal, const void *lit,
+                    const void *ao, const void *rgba) {
+    if (!depth || !normal || !lit || !ao || !rgba) return fail(ctx, RM_E_INVALID, "null buffer");
+    if (const int rc = check_frames(ctx, width, rows, n_frames)) return rc;
+    if ((reinterpret_cast<uintptr_t>(lit) | reinterpret_cast<uintptr_t>(ao)) & 3) return fail(ctx, RM_E_INVALID, "lit and ao must be 4-byte aligned");
     if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU shading path");
     return RM_OK;
 }
@@ -1695,6 +1802,51 @@ int rm_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, i
     return RM_OK;
 }
 
+int rm_shade_lit_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *d_depth, const void *d_normal, const void *d_lit,
+                        const void *d_ao, void *d_rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_lit(ctx, width, rows, n_frames, d_depth, d_normal, d_lit, d_ao, d_rgba);
+    if (rc) return rc;
+    RmShadeLitArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.depth = static_cast<const uint8_t *>(d_depth);
+    args.normal = static_cast<const uint8_t *>(d_normal);
+    args.lit = static_cast<const float *>(d_lit);
+    args.ao = static_cast<const float *>(d_ao);
+    args.rgba = static_cast<uint8_t *>(d_rgba);
+    args.npx = static_cast<int64_t>(width) * rows;
+    for (int k = 0; k < 3; ++k) args.light[k] = ctx->light[k];
+    if (n_frames == 0 || args.npx == 0) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = rm_launch_shade_lit(args, n_frames, static_cast<hipStream_t>(stream), &ctx->last_kernel);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_lit_device");
+    return RM_OK;
+}
+
+int rm_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint8_t *depth, const uint8_t *normal, const float *lit,
+                 const float *ao, uint8_t *rgba) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_shade_lit(ctx, width, rows, n_frames, depth, normal, lit, ao, rgba);
+    if (rc) return rc;
+    const size_t total = static_cast<size_t>(width) * static_cast<size_t>(rows) * static_cast<size_t>(n_frames);
+    if (!total) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const size_t o_depth = st.region(total), o_normal = st.region(3 * total), o_lit = st.region(4 * total), o_ao = st.region(4 * total),
+                 o_rgba = st.region(4 * total);
+    if ((rc = st.reserve())) return rc;
+    RM_HIP(ctx, st.in(o_depth, depth, total));
+    RM_HIP(ctx, st.in(o_normal, normal, 3 * total));
+    RM_HIP(ctx, st.in(o_lit, lit, 4 * total));
+    RM_HIP(ctx, st.in(o_ao, ao, 4 * total));
+    rc = rm_shade_lit_device(ctx, width, rows, n_frames, st.at<void>(o_depth), st.at<void>(o_normal), st.at<void>(o_lit), st.at<void>(o_ao),
+                             st.at<void>(o_rgba), ctx->stream);
+    if (rc) return rc;
+    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
 int rm_sweep_views(double pitch, double yaw, double d_pitch, double d_yaw, double time0, double d_time, int32_t n, rm_view *views) {
     if (!std::isfinite(pitch) || !std::isfinite(yaw) || !std::isfinite(d_pitch) || !std::isfinite(d_yaw) || !std::isfinite(time0) ||
         !std::isfinite(d_time) || n < 0 || (n > 0 && !views))
@@ -2029,6 +2181,23 @@ int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void
 int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                 uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
     return ray_query_host(ctx, true, q, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, object);
+}
+
+int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *d_origins, const void *d_dirs, void *d_t,
+                        void *d_iters, void *d_sdf_calls, void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2,
+                        void *stream) {
+    return ray_light_device(ctx, q, light, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, d_lit, d_ao, d_iters2, d_sdf_calls2, stream);
+}
+
+int rm_ray_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
+                 uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
+    return ray_light_host(ctx, q, light, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2);
+}
+
+int rm_phong_light(float dir3[3]) {
+    if (!dir3) return RM_E_INVALID;
+    rmh::phong_light_dir(dir3);
+    return RM_OK;
 }
 
 int rm_scene_object(rm_ctx *ctx, int32_t index, rm_node *nodes, int32_t cap, int32_t *n_nodes) {

@@ -540,11 +540,12 @@ __device__ __forceinline__ Vec3f point_at(const Ray &r, double t) {
     return p;
 }
 
-// PhongModel.shade for one pixel (phongModel.ts:33-72).  A real function, not inlined: the device library's pow keeps
-// ~18 double constants in VGPRs, and inlined into the render kernels they were hoisted out of the wave loop and held
-// for the whole kernel (36 of its 128 VGPRs), whichever shader the frame used.
-__device__ __attribute__((noinline)) static uchar4 shade_phong(uint8_t depth, uint8_t n0, uint8_t n1, uint8_t n2, double l0,
-                                                                double l1, double l2) {
+// PhongModel.shade for one pixel (phongModel.ts:33-72): the arithmetic, inlined into the two functions below.
+// LIT (rm_shade_lit, include/rm_raymarch.h) scales the diffuse and specular terms by the light term s and the sum by the
+// occlusion term a: I = min((0.1 + diff s + spec s) a, 1), the association of the plain sum, so s = a = 1 gives its bytes.
+template <bool LIT>
+__device__ __forceinline__ uchar4 phong_pixel(uint8_t depth, uint8_t n0, uint8_t n1, uint8_t n2, double l0, double l1, double l2, double s,
+                                              double a) {
     if (depth >= 255) return make_uchar4(10, 10, 20, 255);
     float nx = to_f32(static_cast<double>(n0) / 127.5 - 1.0);
     float ny = to_f32(static_cast<double>(n1) / 127.5 - 1.0);
@@ -569,11 +570,23 @@ __device__ __attribute__((noinline)) static uchar4 shade_phong(uint8_t depth, ui
     const double base = vdr > 0.0 ? vdr : 0.0;
     // Math.pow is not correctly rounded on either side; the byte is within 1 LSB
     const double spec = 0.5 * pow(base, 32.0);
-    double inten = 0.1 + diffuse + spec;
+    double inten = LIT ? (0.1 + diffuse * s + spec * s) * a : 0.1 + diffuse + spec;
     inten = inten < 1.0 ? inten : 1.0;
     const double color = 255 * inten * (1 - static_cast<double>(depth) / 255);
     const uint8_t c = u8clamp(color);
     return make_uchar4(c, c, c, 255);
+}
+// PhongModel.shade.  A real function, not inlined: the device library's pow keeps ~18 double constants in VGPRs, and
+// inlined into the render kernels they were hoisted out of the wave loop and held for the whole kernel (36 of its 128
+// VGPRs), whichever shader the frame used.
+__device__ __attribute__((noinline)) static uchar4 shade_phong(uint8_t depth, uint8_t n0, uint8_t n1, uint8_t n2, double l0,
+                                                                double l1, double l2) {
+    return phong_pixel<false>(depth, n0, n1, n2, l0, l1, l2, 1.0, 1.0);
+}
+// PhongModel.shade with a light term s and an occlusion term a (rm_shade_lit); out of line for the same reason
+__device__ __attribute__((noinline)) static uchar4 shade_phong_lit(uint8_t depth, uint8_t n0, uint8_t n1, uint8_t n2, double l0,
+                                                                    double l1, double l2, double s, double a) {
+    return phong_pixel<true>(depth, n0, n1, n2, l0, l1, l2, s, a);
 }
 
 // ShadingModel.shade for one pixel.  Heatmaps (SDFHeatmap.ts:24-29, IterationHeatmap.ts:24-29)

@@ -7,6 +7,7 @@
 // 16-byte loads and stores, one workgroup per (stripe, column chunk); no reshaping into anything else.
 #include <hip/hip_runtime.h>
 
+#include "rm_device.h"
 #include "rm_kernels.h"
 
 namespace {
@@ -680,6 +681,25 @@ __global__ __launch_bounds__(256) void shade_ranged_kernel(const RmShadeRangedAr
     }
 }
 
+// ------------------------------------------------------------------ shade_lit_kernel (rm_shade_lit_device)
+//
+// PhongModel.shade (rm_device.h, shade_phong_lit) with the light and occlusion terms of a light query: blockIdx.y is the frame,
+// the frame's workgroups stride over its pixels, one pixel per lane and trip.  Not HBM-bound like its neighbours (12 B read,
+// 4 B written against two square roots and a binary64 pow per pixel), so the pixels are not grouped for wide loads.
+__global__ __launch_bounds__(256) void shade_lit_kernel(const RmShadeLitArgs A) {
+    const long long N = A.npx, first = static_cast<long long>(blockIdx.y) * N;
+    const uint8_t *depth = A.depth + first, *normal = A.normal + 3 * first;
+    const float *lit = A.lit + first, *ao = A.ao + first;
+    uint8_t *rgba = A.rgba + 4 * first;
+    const bool whole = (reinterpret_cast<uintptr_t>(rgba) & 3) == 0;
+    const long long step = static_cast<long long>(gridDim.x) * 256;
+    for (long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; i < N; i += step) {
+        const uchar4 c = rmd::shade_phong_lit(depth[i], normal[3 * i], normal[3 * i + 1], normal[3 * i + 2], A.light[0], A.light[1], A.light[2],
+                                              static_cast<double>(lit[i]), static_cast<double>(ao[i]));
+        store_pixel(rgba, i, c.x | (static_cast<unsigned int>(c.y) << 8) | (static_cast<unsigned int>(c.z) << 16) | (static_cast<unsigned int>(c.w) << 24), whole);
+    }
+}
+
 }  // namespace
 
 hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
@@ -759,5 +779,16 @@ hipError_t rm_launch_shade_ranged(const RmShadeRangedArgs &a, int32_t n_frames, 
     const dim3 grid(static_cast<unsigned>(rm_shade_ranged_blocks_per_frame(a.npx, n_frames)), static_cast<unsigned>(n_frames)), block(256);
     hipLaunchKernelGGL(shade_ranged_kernel, grid, block, 0, stream, a);
     if (kernel_name) *kernel_name = "shade_ranged_kernel";
+    return hipGetLastError();
+}
+
+hipError_t rm_launch_shade_lit(const RmShadeLitArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name) {
+    if (n_frames <= 0 || a.npx <= 0) return hipSuccess;
+    // ~4096 workgroups per launch, never more than a frame has pixels for
+    const int64_t want = (a.npx + 255) / 256, share = 4096 / n_frames;
+    const int64_t per_frame = want < share ? want : (share < 1 ? 1 : share);
+    const dim3 grid(static_cast<unsigned>(per_frame), static_cast<unsigned>(n_frames)), block(256);
+    hipLaunchKernelGGL(shade_lit_kernel, grid, block, 0, stream, a);
+    if (kernel_name) *kernel_name = "shade_lit_kernel";
     return hipGetLastError();
 }

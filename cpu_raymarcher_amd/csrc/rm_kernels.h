@@ -82,6 +82,27 @@ struct RmShadeRangedArgs {
     long long npx;
     unsigned int counter, lo, hi;  // counter: 0 takes hist[k].sdf, 1 hist[k].iters
 };
+// rm_shade_lit_device (rm_frame_ops.hip, shade_lit_kernel): frame k at element k * npx of every buffer (x3 normal, x4 rgba)
+struct RmShadeLitArgs {
+    const uint8_t *depth, *normal;
+    const float *lit, *ao;
+    uint8_t *rgba;
+    long long npx;
+    double light[3];  // PhongModel's binary32 light direction, widened (exact)
+};
+// rm_ray_light (rm_kernels.hip, light_kernel): the rays, the outputs (each may be null) and the rm_light of one launch
+struct RmLightArgs {
+    const float *origins, *dirs;  // f32[3n]
+    double *t;                    // the primary ray's outputs: what cast_kernel writes with want_normal
+    uint32_t *iters, *sdf;
+    float *normal;
+    float *lit, *ao;              // f32[n]
+    uint32_t *iters2, *sdf2;      // the shadow ray's iterations; its SDF calls plus those of the occlusion samples
+    long long n;
+    double bias, ao_step, ao_strength;
+    float light[3];               // towards the light, as given
+    int ao_samples;
+};
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
@@ -135,6 +156,12 @@ hipError_t rm_launch_query_sqrt(const RmRenderParams &p, bool pick, const float 
                                 const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
                                 hipStream_t stream, const char **kernel_name);
 
+// Light query (rm_ray_light): rm_launch_query's march with want_normal, then at hits one shadow ray towards a.light through
+// the same marcher and a.ao_samples Scene.getDistance samples along the normal (include/rm_raymarch.h has the rule).  One
+// launch of light_kernel, the LDS of rm_launch_query.
+hipError_t rm_launch_light(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
+
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics
 // (acc non-null) accumulated in blocks[k] (zero before and after the launch) and written to acc[k].  One launch of
@@ -166,6 +193,8 @@ hipError_t rm_launch_hist(const RmHistArgs &a, bool masked, int32_t n_frames, in
                           const char **kernel_name);
 // rm_shade_ranged_device: ONE launch of shade_ranged_kernel; nothing without a pixel or a frame.
 hipError_t rm_launch_shade_ranged(const RmShadeRangedArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name);
+// rm_shade_lit_device: ONE launch of shade_lit_kernel; nothing without a pixel or a frame.
+hipError_t rm_launch_shade_lit(const RmShadeLitArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name);
 
 hipError_t rm_launch_hypot(const float *xyz, int64_t n, double *out, hipStream_t stream);
 // rm_jsmath.h on the device: fn 0 sin, 1 cos, 2 atan2, 3 asin, 4 log, 5 pow, 6 round, 7 atan

@@ -1353,6 +1353,94 @@ __global__ __launch_bounds__(256) void pick_kernel(const RmRenderParams P, const
     query_body<ACCEL, OTHER, GEN, true>(P, origins, dirs, n, want_normal, slot_obj, t_out, iters_out, sdf_out, normal_out, obj_out);
 }
 
+// ------------------------------------------------------------------ light queries (rm_ray_light)
+
+// query_body's march and normal, then at hits the two light terms of include/rm_raymarch.h (rm_ray_light): one shadow ray
+// towards the light through the SAME marcher and acceleration structure, and K Scene.getDistance samples along the normal.
+// The marcher has one call site: trip 0 marches the caller's ray, trip 1 the shadow ray (a second inlined copy would double
+// the kernel and its register pressure).  The lane's BVH hit-leaf list in LDS is dead once the primary march has returned
+// (the marchers initialise it on entry), so the shadow ray reuses it.  Lanes whose ray missed, whose normal is zero or
+// that face away from the light leave the loop after trip 0 and idle while the rest of the wave marches its shadow rays;
+// lanes without a hit idle through the occlusion samples too.  That is accepted: the hit lanes of a wave of neighbouring
+// rays are mostly the same, and compacting them would cost a pass through memory.
+template <int ACCEL, bool OTHER, int GEN>
+__device__ __forceinline__ void light_body(const RmRenderParams &P, const RmLightArgs &A) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    Ray ray;
+    ray.o = Vec3f{A.origins[3 * i], A.origins[3 * i + 1], A.origins[3 * i + 2]};
+    ray.d = Vec3f{A.dirs[3 * i], A.dirs[3 * i + 1], A.dirs[3 * i + 2]};
+    ray.od[0] = static_cast<double>(ray.o.x);
+    ray.od[1] = static_cast<double>(ray.o.y);
+    ray.od[2] = static_cast<double>(ray.o.z);
+    Vec3f p{0.f, 0.f, 0.f}, nrm{0.f, 0.f, 0.f};
+    float lit = 1.f, ao = 1.f;
+    uint32_t iters2 = 0, count2 = 0;
+    bool hit = false;
+#pragma unroll 1
+    for (int trip = 0; trip < 2; ++trip) {
+        uint32_t count = 0, iters = 0;
+        const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters) : ray_march<ACCEL, GEN>(P, ray, count, iters);
+        if (trip) {  // the shadow ray
+            lit = t >= RM_MAX_DIST ? 1.f : 0.f;
+            iters2 = iters;
+            count2 = count;
+            break;
+        }
+        nrm = hit_normal<ACCEL, GEN>(P, ray, t, count);
+        if (A.t) A.t[i] = t;
+        if (A.iters) A.iters[i] = iters;
+        if (A.sdf) A.sdf[i] = count;
+        if (A.normal) {
+            A.normal[3 * i] = nrm.x;
+            A.normal[3 * i + 1] = nrm.y;
+            A.normal[3 * i + 2] = nrm.z;
+        }
+        if (t >= RM_MAX_DIST || (nrm.x == 0.f && nrm.y == 0.f && nrm.z == 0.f)) break;  // the neutral case
+        hit = true;
+        p.x = to_f32(static_cast<double>(ray.o.x) + static_cast<double>(ray.d.x) * t);  // hit_normal's point
+        p.y = to_f32(static_cast<double>(ray.o.y) + static_cast<double>(ray.d.y) * t);
+        p.z = to_f32(static_cast<double>(ray.o.z) + static_cast<double>(ray.d.z) * t);
+        const double c = static_cast<double>(nrm.x) * A.light[0] + static_cast<double>(nrm.y) * A.light[1] + static_cast<double>(nrm.z) * A.light[2];
+        if (!(c > 0.0)) {  // facing away (or NaN): dark, no shadow ray
+            lit = 0.f;
+            break;
+        }
+        ray.o.x = to_f32(static_cast<double>(p.x) + static_cast<double>(nrm.x) * A.bias);  // vec3.scaleAndAdd(p, n, bias)
+        ray.o.y = to_f32(static_cast<double>(p.y) + static_cast<double>(nrm.y) * A.bias);
+        ray.o.z = to_f32(static_cast<double>(p.z) + static_cast<double>(nrm.z) * A.bias);
+        ray.d = Vec3f{A.light[0], A.light[1], A.light[2]};
+        ray.od[0] = static_cast<double>(ray.o.x);
+        ray.od[1] = static_cast<double>(ray.o.y);
+        ray.od[2] = static_cast<double>(ray.o.z);
+    }
+    if (hit) {
+        double occ = 0.0, w = 1.0;  // w = 2^(1 - k), exact
+#pragma unroll 1
+        for (int k = 1; k <= A.ao_samples; ++k) {
+            const double h = static_cast<double>(k) * A.ao_step;
+            Vec3f q;
+            q.x = to_f32(static_cast<double>(p.x) + static_cast<double>(nrm.x) * h);
+            q.y = to_f32(static_cast<double>(p.y) + static_cast<double>(nrm.y) * h);
+            q.z = to_f32(static_cast<double>(p.z) + static_cast<double>(nrm.z) * h);
+            const double d = scene_distance<ACCEL, GEN>(P, q, count2);
+            occ = occ + (h - d) * w;
+            w = w * 0.5;
+        }
+        const double x = 1.0 - A.ao_strength * occ;  // (K = 0: occ = 0 and x = 1)
+        ao = to_f32(x > 0.0 ? (x > 1.0 ? 1.0 : x) : 0.0);  // NaN: 0
+    }
+    if (A.lit) A.lit[i] = lit;
+    if (A.ao) A.ao[i] = ao;
+    if (A.iters2) A.iters2[i] = iters2;
+    if (A.sdf2) A.sdf2[i] = count2;
+}
+
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void light_kernel(const RmRenderParams P, const RmLightArgs A) {
+    light_body<ACCEL, OTHER, GEN>(P, A);
+}
+
 #ifndef RM_LENGTH_SQRT
 __global__ __launch_bounds__(256) void hypot_kernel(const float *xyz, int64_t n, double *out) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -1638,6 +1726,28 @@ hipError_t RM_LEN_VARIANT(rm_launch_query)(const RmRenderParams &p, bool pick, c
     }
     RM_DISPATCH(RM_QK)
 #undef RM_QK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_light)(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n <= 0) return hipSuccess;
+    const int threads = 256;
+    const dim3 grid(static_cast<unsigned>((a.n + threads - 1) / threads)), block(threads);
+    const V1Lds lds = v1_lds_layout(p, threads, true);  // as rm_launch_query: both marches of a lane are a render's
+    const size_t shmem = lds.bytes;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    pl.v1_list_offset = lds.v1_list_offset;
+#define RM_LK(A, O, G)                                                                 \
+    {                                                                                  \
+        hipLaunchKernelGGL((light_kernel<A, O, G>), grid, block, shmem, stream, pl, a); \
+        if (kernel_name) *kernel_name = RM_KERNEL_NAME(light_kernel, A, O, G);         \
+    }
+    RM_DISPATCH(RM_LK)
+#undef RM_LK
     return hipGetLastError();
 }
 

@@ -209,6 +209,14 @@ class Raymarcher:
         return scene.ctx.pick(origins, directions, self.algorithm, normal=normal, time=scene.time,
                               overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None))
 
+    def lightBatch(self, scene, origins, directions, light_dir=None, bias=0.02, ao_samples=5, ao_step=0.05, ao_strength=1.0):
+        """rayMarchBatch with normals plus a shadow term and an ambient-occlusion term at each hit (Context.light with this
+        marcher, its options and the scene's time) -> (t, iters, sdf_calls, normal, lit, ao, iters2, sdf_calls2)."""
+        scene._activate()
+        return scene.ctx.light(origins, directions, light_dir=light_dir, bias=bias, ao_samples=ao_samples, ao_step=ao_step,
+                               ao_strength=ao_strength, algorithm=self.algorithm, time=scene.time,
+                               overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None))
+
 
 class SphereTracer(Raymarcher):  # cpu_algorithms/sphereTracer.ts
     algorithm = "sphere-tracer"

@@ -288,6 +288,58 @@ RM_API int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const floa
 RM_API int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs,
                               void *d_t, void *d_iters, void *d_sdf_calls, void *d_normal, void *d_object, void *stream);
 
+/* ---- light queries: shadow rays and ambient occlusion at hits ------------------------ */
+
+typedef struct rm_light {
+    float   dir[3];        /* towards the light, used as given (not normalised), like a ray direction */
+    int32_t ao_samples;    /* K, 0 .. 8; 0: no occlusion samples, ao = 1 */
+    double  bias;          /* shadow-ray origin offset along the normal, finite, >= 0 */
+    double  ao_step;       /* spacing of the occlusion samples, finite, > 0 when K > 0 */
+    double  ao_strength;   /* finite, >= 0 */
+} rm_light;
+
+/* rm_ray_march with q->normal = 1, plus two light terms at each hit, in ONE launch: a shadow ray towards a directional light
+ * through the query's own marcher and the scene's acceleration structure, and K ambient-occlusion samples of
+ * Scene.getDistance along the normal.  q->normal is ignored: normals are always computed and their four evaluations
+ * counted in sdf_calls.  The reference has neither term (its PhongModel has a light direction and no shadows); both are
+ * built from its own functions only.  The rule, per ray (o, d):
+ *   1. t, iters, sdf_calls, normal_xyz are bit-identical to rm_ray_march with q->normal = 1 for the same ray and query.
+ *   2. t >= 10 (getMaxDistance) or a normal of (0, 0, 0) (zero gradient): lit = 1, ao = 1, iters2 = 0, sdf_calls2 = 0;
+ *      nothing further is evaluated.
+ *   3. Else p = hitPosition = f32(o + d t) (vec3.scaleAndAdd, raymarcher.ts:94-95; getNormal's point), n = the binary32
+ *      normal, L = light->dir.
+ *   4. c = (double)n0 L0 + (double)n1 L1 + (double)n2 L2, left to right in binary64, no contraction.  c <= 0 or NaN:
+ *      lit = 0, no shadow ray (iters2 = 0, sdf_calls2 starts at 0).  Else the shadow origin is s = f32(p + n bias) per
+ *      component (the same scaleAndAdd form), and the ray (s, L) is marched by q's marcher with q's time, overshoot and
+ *      step through the acceleration structure: exactly what rm_ray_march returns for that ray with q->normal = 0.
+ *      lit = (t_s >= 10) ? 1 : 0, iters2 = its iterations, sdf_calls2 starts as its SDF calls.
+ *   5. For k = 1 .. K: h_k = k ao_step, q_k = f32(p + n h_k), d_k = Scene.getDistance(q_k) at q's time, its primitive
+ *      count added to sdf_calls2; occ = sum of (h_k - d_k) 2^(1-k) in order of increasing k in binary64;
+ *      x = 1 - ao_strength occ; ao = (float)(x > 0 ? (x > 1 ? 1 : x) : 0), so NaN gives 0.  K = 0: ao = 1.
+ *      getDistance is taken as it is (scene.ts:144-190): an empty octree leaf answers minDistance * 0.99, the minimum
+ *      starts at 10, and a point in no BVH leaf box is measured against every primitive -- d_k is a bound the marchers
+ *      are satisfied with, not always the exact distance, and the occlusion term inherits that.
+ * lit, ao: f32[n]; iters2, sdf_calls2: u32[n]; every output may be NULL.  Checks and return codes are rm_ray_march's,
+ * plus RM_E_INVALID -- like every argument check ahead of RM_E_NO_DEVICE and RM_E_NO_SCENE -- for a null light, a
+ * non-finite dir component, ao_samples outside 0 .. 8, a non-finite or negative bias or ao_strength, a non-finite
+ * ao_step or one that is not positive when K > 0; n == 0 is RM_OK.  A bias at or below the marchers' hit threshold
+ * (0.001) makes every shadow ray hit its own surface at once.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone; rm_last_kernel names the light_kernel<...>
+ * instantiation.  Lanes whose ray missed idle while their wave's hits run the secondary phases.  Host buffers,
+ * synchronous, chunked through the context's scratch buffer as rm_ray_march. */
+RM_API int rm_ray_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz,
+                        const float *dirs_xyz, double *t, uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz,
+                        float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2);
+
+/* Same with device pointers, asynchronous on `stream`, as rm_ray_march_device. */
+RM_API int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n,
+                               const void *d_origins, const void *d_dirs, void *d_t, void *d_iters, void *d_sdf_calls,
+                               void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2, void *stream);
+
+/* The binary32 light direction PhongModel normalises from (1, -1, 1.5) (phongModel.ts:15-16), what RM_SHADE_PHONG and
+ * rm_shade_lit shade with; host-only, no ctx.  RM_E_INVALID for a null pointer. */
+RM_API int rm_phong_light(float dir3[3]);
+
 /* Reads back object `index` of the active scene as an expression tree in the form rm_scene_from_nodes takes: operands
  * before their user, the object's root last.  A sphere, box or torus of a list scene is one leaf node (its world_to_local
  * and params; a sphere of rm_scene_from_spheres at rm_make_transform of its centre).  An uploaded scene comes back as it
@@ -496,6 +548,21 @@ RM_API int rm_shade_ranged_device(rm_ctx *ctx, int32_t counter, int32_t width, i
 RM_API int rm_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames,
                            const uint16_t *values, const rm_frame_hist *hist, uint32_t lo, uint32_t hi,
                            uint8_t *rgba);
+
+/* PhongModel.shade (phongModel.ts:33-72, as RM_SHADE_PHONG restates it) with the two terms of a light query, ONE launch for
+ * n_frames frames (layout as rm_shade_ranged_device: frame k at element k * W * rows of every buffer, x3 normal, x4 rgba),
+ * asynchronous on `stream`.  One line changes: I = min((0.1 + diff s + spec s) a, 1) with s = (double)lit[i] and
+ * a = (double)ao[i], evaluated in that order, so s = a = 1 gives RM_SHADE_PHONG's bytes exactly.  Background pixels
+ * (depth byte 255) keep PhongModel's (10, 10, 20, 255).  d_lit, d_ao: f32, what rm_ray_light writes for the frame's rays.
+ * RM_E_INVALID -- checked before anything else -- for a null buffer, a negative size, W * rows > UINT32_MAX,
+ * n_frames > 65535, a d_lit or d_ao that is not 4-byte aligned.  RM_E_NO_DEVICE on a host-only context; never
+ * RM_E_NO_SCENE; not a render entry.  Without a pixel or a frame no byte is written.  rm_last_kernel: shade_lit_kernel.
+ * Uses no ring: no call waits. */
+RM_API int rm_shade_lit_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *d_depth,
+                               const void *d_normal, const void *d_lit, const void *d_ao, void *d_rgba, void *stream);
+/* Same with host buffers (synchronous). */
+RM_API int rm_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint8_t *depth,
+                        const uint8_t *normal, const float *lit, const float *ao, uint8_t *rgba);
 
 /* Multi-GPU sharding of one Job (replaces the contiguous ceil(H/N) split of main.ts:444-449
  * by a load-balanced one): the rows [y_start, y_end) are cut into stripes of `stripe_rows`
