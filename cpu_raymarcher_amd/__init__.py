@@ -6,6 +6,7 @@ built: there is no CPU fallback on the product path.
 """
 from . import _native
 from ._native import RmError, RmUnsupported, RM_SCENE_UPLOADED
+from ._native import STEP_DTYPE, WALK_DTYPE, WALK_ENDS  # the records Context.walk returns
 
 _native.lib()  # raise now, not at first render, when the HIP library is missing
 

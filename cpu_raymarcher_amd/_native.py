@@ -54,6 +54,25 @@ class rm_light(C.Structure):  # include/rm_raymarch.h: struct rm_light
                 ("ao_strength", C.c_double)]
 
 
+class rm_step(C.Structure):  # include/rm_raymarch.h: struct rm_step
+    _fields_ = [("t", C.c_double), ("value", C.c_double), ("count", C.c_uint32), ("kind", C.c_int32)]
+
+
+class rm_walk(C.Structure):  # include/rm_raymarch.h: struct rm_walk
+    _fields_ = [("t", C.c_double), ("min_dist", C.c_double), ("t_min", C.c_double), ("skipped", C.c_double),
+                ("evals", C.c_uint32), ("skips", C.c_uint32), ("sdf_calls", C.c_uint32), ("end", C.c_int32)]
+
+
+# the same two records as numpy structured dtypes (what Context.walk returns), rm_step_kind, rm_walk_end
+STEP_DTYPE = [("t", "<f8"), ("value", "<f8"), ("count", "<u4"), ("kind", "<i4")]
+WALK_DTYPE = [("t", "<f8"), ("min_dist", "<f8"), ("t_min", "<f8"), ("skipped", "<f8"), ("evals", "<u4"), ("skips", "<u4"),
+              ("sdf_calls", "<u4"), ("end", "<i4")]
+RM_STEP_EVAL, RM_STEP_SKIP = 0, 1
+RM_END_HIT, RM_END_FAR, RM_END_STEPS, RM_END_ACCEL = 0, 1, 2, 3
+WALK_ENDS = {0: "hit", 1: "far", 2: "steps", 3: "accel"}
+RM_WALK_MAX_STEPS = 256
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -144,6 +163,8 @@ SIGNATURES = {
                                _VP]),
     "rm_ray_light_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.POINTER(rm_light), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP,
                                       _VP, _VP, _VP]),
+    "rm_ray_walk": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, C.c_int32, _VP, _VP]),
+    "rm_ray_walk_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, C.c_int32, _VP, _VP, _VP]),
     "rm_phong_light": (C.c_int, [_VP]),
     "rm_shade_lit_device": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_shade_lit": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_int32, _VP, _VP, _VP, _VP, _VP]),

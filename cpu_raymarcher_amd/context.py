@@ -380,6 +380,75 @@ class Context:
         out = self.light(o, dirs, **kw)
         return out[4], out[5]
 
+    def walk(self, origins, directions, algorithm="sphere-tracer", time=0.0, overshoot=None, step=None, trace=False, cap=200):
+        """How the marcher walks each ray, in one launch (rm_ray_walk; the rule is in include/rm_raymarch.h).  Returns `walks`,
+        one record of WALK_DTYPE per ray (t as ray_march returns it, min_dist / t_min: the closest evaluation and where,
+        skipped / skips: what the acceleration structure skipped, evals, sdf_calls, end: an RM_END_* value, WALK_ENDS names
+        them), or with `trace` (walks, steps): steps[n, cap] of STEP_DTYPE holds the first min(cap, evals + skips) records of
+        each ray -- one per distance evaluation (kind 0: t, the distance, the primitives counted) and per skip (kind 1: t
+        before it, its length) -- and zeros behind them.  No walk produces more than 200 records.  numpy input -> the host
+        entry and structured arrays; torch CUDA tensors -> rm_ray_walk_device on torch's current stream and uint8 tensors
+        [n, 48] and [n, cap, 24] holding the same records (`.cpu().numpy().view(...)` with the dtypes gives the fields)."""
+        q = N.rm_ray_query()
+        q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
+        q.normal = 0
+        q.time = float(time)
+        q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
+        q.step_size = float(step) if step is not None else float("nan")
+        cap = int(cap)
+        if _is_torch(origins) or _is_torch(directions):
+            import torch
+            if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
+                raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
+            self._same_device(dict(origins=origins, directions=directions))
+            for name, b in (("origins", origins), ("directions", directions)):
+                if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
+                    raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
+            n = origins.numel() // 3
+            if directions.numel() != 3 * n:
+                raise ValueError("origins and directions differ in length")
+            dev = origins.device
+            walks = torch.empty((n, 48), dtype=torch.uint8, device=dev)
+            steps = torch.zeros((n, max(cap, 0), 24), dtype=torch.uint8, device=dev) if trace else None
+            N.check(self._h, N.lib().rm_ray_walk_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), cap if trace else 0,
+                                                        _ptr(walks), _ptr(steps) if trace else None, _current_stream_ptr()))
+            return (walks, steps) if trace else walks
+        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("origins and directions differ in length")
+        n = len(o)
+        walks = np.zeros(n, N.WALK_DTYPE)
+        steps = np.zeros((n, max(cap, 0)), N.STEP_DTYPE) if trace else None
+        N.check(self._h, N.lib().rm_ray_walk(self._h, C.byref(q), n, _ptr(o), _ptr(d), cap if trace else 0, _ptr(walks),
+                                             _ptr(steps) if trace else None))
+        return (walks, steps) if trace else walks
+
+    def walk_frame(self, width, height, pitch=0.0, yaw=0.0, y_start=0, y_end=None, algorithm="sphere-tracer", time=0.0,
+                   overshoot=None, step=None, device=False):
+        """The walk summaries under every pixel of rows [y_start, y_end) of a width x height frame of the active scene: the
+        frame's camera rays (camera_rays) through `walk` -> WALK_DTYPE[rows, width], tile-local rows (an end-reason map is
+        its "end" field, a skipped-distance map its "skipped").  device=True: the rays go to rm_ray_walk_device as CUDA
+        tensors of this context's device and the result is a uint8 tensor [rows, width, 48]."""
+        if y_end is None:
+            y_end = height
+        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
+        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
+        kw = dict(algorithm=algorithm, time=time, overshoot=overshoot, step=step)
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            return self.walk(torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev), **kw).reshape(y_end - y_start, width, 48)
+        return self.walk(o, dirs, **kw).reshape(y_end - y_start, width)
+
+    def trace_pixel(self, width, height, x, y, pitch=0.0, yaw=0.0, algorithm="sphere-tracer", time=0.0, overshoot=None, step=None):
+        """The whole walk of the ray through pixel (x, y) of a width x height frame of the active scene -> (walk, steps):
+        the pixel's summary record and its step records, trimmed to the evals + skips the walk produced."""
+        org, dirs = camera_rays(width, height, pitch, yaw, int(y), int(y) + 1)
+        walks, steps = self.walk(org.reshape(1, 3), dirs[int(x)].reshape(1, 3), algorithm=algorithm, time=time, overshoot=overshoot,
+                                 step=step, trace=True, cap=N.RM_WALK_MAX_STEPS)
+        return walks[0], steps[0, :int(walks[0]["evals"]) + int(walks[0]["skips"])]
+
     def shade_lit(self, depth, normal, lit, ao, rgba, width=0, rows=0, n_frames=1):
         """The Phong shade with the light terms of `light` / `light_frame` (rm_shade_lit_device / rm_shade_lit):
         I = min((0.1 + diffuse * lit + specular * lit) * ao, 1); lit = ao = 1 gives the "phong" shader's bytes.  depth,

@@ -1174,6 +1174,88 @@ int ray_light_host(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, in
     return RM_OK;
 }
 
+// what both forms of rm_ray_walk check: the record capacity and the outputs (ahead of the device check, like every argument
+// check), then check_query
+static_assert(sizeof(rm_step) == 24 && sizeof(RmWalkStep) == 24 && sizeof(rm_walk) == 48 && sizeof(RmWalkSummary) == 48, "walk record layout");
+static_assert(offsetof(rm_step, count) == offsetof(RmWalkStep, count) && offsetof(rm_walk, end) == offsetof(RmWalkSummary, end), "walk record layout");
+static_assert(RM_END_HIT == 0 && RM_END_FAR == 1 && RM_END_STEPS == 2 && RM_END_ACCEL == 3 && RM_STEP_EVAL == 0 && RM_STEP_SKIP == 1,
+              "the kernel's recorder writes these values");
+int check_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs, int32_t cap, const void *walks, const void *steps) {
+    if (cap < 0 || cap > RM_WALK_MAX_STEPS) return fail(ctx, RM_E_INVALID, "cap must be in [0, RM_WALK_MAX_STEPS]");
+    if (steps && cap == 0) return fail(ctx, RM_E_INVALID, "step records asked for with cap 0");
+    if (n > 0 && !walks && !steps) return fail(ctx, RM_E_INVALID, "neither summaries nor step records asked for");
+    return check_query(ctx, q, n, origins, dirs);
+}
+
+int ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, int32_t cap, void *d_walks,
+                    void *d_steps, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    if ((reinterpret_cast<uintptr_t>(d_walks) | reinterpret_cast<uintptr_t>(d_steps)) & 7u) return fail(ctx, RM_E_INVALID, "d_walks and d_steps must be 8-byte aligned");
+    int rc = check_walk(ctx, q, n, d_origins, d_dirs, cap, d_walks, d_steps);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RmWalkArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.origins = static_cast<const float *>(d_origins);
+    a.dirs = static_cast<const float *>(d_dirs);
+    a.walks = static_cast<RmWalkSummary *>(d_walks);
+    a.steps = static_cast<RmWalkStep *>(d_steps);
+    a.n = n;
+    a.cap = cap;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_walk_sqrt : rm_launch_walk)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int ray_walk_host(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, int32_t cap, rm_walk *walks,
+                  rm_step *steps) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_walk(ctx, q, n, origins_xyz, dirs_xyz, cap, walks, steps);
+    if (rc || !n) return rc;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    RmRenderParams p;
+    rc = fill_query_params(ctx, q, p);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Through the scratch buffer in chunks, as ray_query_host.  Summaries only: 4 M rays (72 B per ray: 288 MB).  With step
+    // records the chunk is sized by bytes: at most 64 MiB of records, at least one ray (cap 256: 10 922 rays).
+    const size_t per_ray = steps ? sizeof(rm_step) * static_cast<size_t>(cap) : 0;
+    int64_t chunk = int64_t(1) << 22;
+    if (steps) chunk = static_cast<int64_t>((size_t(64) << 20) / per_ray);
+    if (chunk < 1) chunk = 1;
+    if (chunk > n) chunk = n;
+    const size_t c = static_cast<size_t>(chunk);
+    Staging st{ctx};
+    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_walks = st.region(walks ? sizeof(rm_walk) * c : 0),
+                 o_steps = st.region(per_ray * c);
+    if ((rc = st.reserve())) return rc;
+    RmWalkArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.origins = st.at<const float>(o_org);
+    a.dirs = st.at<const float>(o_dirs);
+    a.walks = walks ? st.at<RmWalkSummary>(o_walks) : nullptr;
+    a.steps = steps ? st.at<RmWalkStep>(o_steps) : nullptr;
+    a.cap = cap;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
+        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
+        // slots past a ray's length are left as the caller has them: the caller's records go in, the kernel overwrites the
+        // ones the walk produced, and all come back
+        if (steps) RM_HIP(ctx, st.in(o_steps, steps + at * static_cast<size_t>(cap), per_ray * k));
+        a.n = m;
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_walk_sqrt : rm_launch_walk)(p, a, ctx->stream, &ctx->last_kernel));
+        if (walks) RM_HIP(ctx, st.out(walks + at, o_walks, sizeof(rm_walk) * k));
+        if (steps) RM_HIP(ctx, st.out(steps + at * static_cast<size_t>(cap), o_steps, per_ray * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
 // Object `index` of the active scene as an rm_scene_from_nodes forest (operands before their user, the object's root last),
 // from the description the scene was built from: the upload as it was given (spheres as sphere leaves at
 // SceneManager.getTransform of their centre), or the preset's objects as the reference holds them -- vec3 members
@@ -2192,6 +2274,16 @@ int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *ligh
 int rm_ray_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
                  uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
     return ray_light_host(ctx, q, light, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2);
+}
+
+int rm_ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, int32_t cap, void *d_walks,
+                       void *d_steps, void *stream) {
+    return ray_walk_device(ctx, q, n, d_origins, d_dirs, cap, d_walks, d_steps, stream);
+}
+
+int rm_ray_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, int32_t cap, rm_walk *walks,
+                rm_step *steps) {
+    return ray_walk_host(ctx, q, n, origins_xyz, dirs_xyz, cap, walks, steps);
 }
 
 int rm_phong_light(float dir3[3]) {

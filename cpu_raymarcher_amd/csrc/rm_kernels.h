@@ -103,6 +103,25 @@ struct RmLightArgs {
     float light[3];               // towards the light, as given
     int ao_samples;
 };
+// rm_ray_walk (rm_kernels.hip, walk_kernel): rm_step and rm_walk as the kernel stores them, and the rays and outputs of one
+// launch.  steps: cap slots per ray, null for summaries only (the same for every lane); walks may be null when steps is not.
+struct RmWalkStep {  // rm_step (24 bytes)
+    double t, value;
+    uint32_t count;
+    int32_t kind;
+};
+struct RmWalkSummary {  // rm_walk (48 bytes)
+    double t, min_dist, t_min, skipped;
+    uint32_t evals, skips, sdf_calls;
+    int32_t end;
+};
+struct RmWalkArgs {
+    const float *origins, *dirs;  // f32[3n]
+    RmWalkSummary *walks;
+    RmWalkStep *steps;
+    long long n;
+    int cap, pad;
+};
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
@@ -161,6 +180,11 @@ hipError_t rm_launch_query_sqrt(const RmRenderParams &p, bool pick, const float 
 // launch of light_kernel, the LDS of rm_launch_query.
 hipError_t rm_launch_light(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
+
+// Walk query (rm_ray_walk): rm_launch_query's march without a normal, with a recorder that keeps the walk's summary and
+// stores its first a.cap step records (include/rm_raymarch.h has the rule).  One launch of walk_kernel, the LDS of rm_launch_query.
+hipError_t rm_launch_walk(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

@@ -500,9 +500,18 @@ __device__ __forceinline__ RayList v1_ray_list(const RmRenderParams &P) {
     return L;
 }
 
+// What a marcher tells about its walk (rm_ray_walk, include/rm_raymarch.h): eval at every Scene.getDistance call that adds to
+// iters (t: the parameter the point was formed at; n: the primitives that call counted), skip at every positive answer of
+// the acceleration structure (t: the parameter before it), end at every exit but the exhausted trip limit (a recorder
+// starts at RM_WALK_STEPS).  The recorder is a parameter pack of none or one: renders and the other ray queries pass none, and
+// their marchers keep the signature and the body they had -- every hook below is a fold over an empty pack, no code at all
+// (a defaulted no-op recorder argument was tried: it moved SGPR spills and two VGPRs in some GEN 2 / 3 instantiations).
+enum { RM_WALK_HIT = 0, RM_WALK_FAR = 1, RM_WALK_STEPS = 2, RM_WALK_ACCEL = 3 };  // rm_walk_end
+#define RM_REC(call) ((void)(rec.call), ...)
+
 // SphereTracer.rayMarch (sphereTracer.ts:15-83)
-template <int ACCEL, int GEN>
-__device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &count, uint32_t &iters) {
+template <int ACCEL, int GEN, typename... REC>
+__device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &count, uint32_t &iters, REC &...rec) {
     double t = 0.0;
     Interval cur;
     bool haveCur = false;
@@ -519,7 +528,10 @@ __device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &c
         } else {
             haveCur = bvh_next_interval(P, ray, ri, -__builtin_inf(), -1, cur);
         }
-        if (!haveCur) return RM_MAX_DIST;                                // bvh.ts:190-192
+        if (!haveCur) {  // bvh.ts:190-192
+            RM_REC(end(RM_WALK_ACCEL));
+            return RM_MAX_DIST;
+        }
     }
     for (int i = 0; i < RM_MAX_STEPS; ++i) {
         RM_CNT1(0)
@@ -531,18 +543,28 @@ __device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &c
         if (ACCEL == 2) {
             // BVH.onRayMarchStep (bvh.ts:204-240)
             double skip = 0.0;
-            if (!haveCur) return RM_MAX_DIST;  // currentIntervalIdx >= length
+            if (!haveCur) {  // currentIntervalIdx >= length
+                RM_REC(end(RM_WALK_ACCEL));
+                return RM_MAX_DIST;
+            }
             if (t < cur.tEnter) skip = cur.tEnter - t;
             else if (t > cur.tExit) {
                 const Interval prev = cur;
                 haveCur = lists ? bvh_next<false>(v1_view(P), ray, ri, L, prev.tEnter, prev.ord, cur)
                                 : bvh_next_interval(P, ray, ri, prev.tEnter, prev.ord, cur);  // idx++
-                if (!haveCur) return RM_MAX_DIST;
+                if (!haveCur) {
+                    RM_REC(end(RM_WALK_ACCEL));
+                    return RM_MAX_DIST;
+                }
                 if (cur.tEnter > t) skip = cur.tEnter - t;
             }
             if (skip > 0.0) {
+                RM_REC(skip(t, skip));
                 t += skip;
-                if (t > RM_MAX_DIST) break;
+                if (t > RM_MAX_DIST) {
+                    RM_REC(end(RM_WALK_FAR));
+                    break;
+                }
                 continue;
             }
         } else if (ACCEL == 1) {
@@ -551,19 +573,31 @@ __device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &c
                 const double skip = oct_skip(P.oct[onode], ray, t, oinv);
                 if (skip > 0.0) {
                     RM_CNT1(1)
+                    RM_REC(skip(t, skip));
                     t += skip;
-                    if (t > RM_MAX_DIST) break;
+                    if (t > RM_MAX_DIST) {
+                        RM_REC(end(RM_WALK_FAR));
+                        break;
+                    }
                     continue;
                 }
             }
         }
+        [[maybe_unused]] const uint32_t before = count;
         double dist;
         if (ACCEL == 1) dist = oct_node_distance<GEN>(P, onode, p, count);
         else dist = scene_distance<ACCEL, GEN>(P, p, count);
+        RM_REC(eval(t, dist, count - before));
         t += dist;
         iters += 1;
-        if (dist < RM_EPSILON) break;
-        if (t > RM_MAX_DIST) break;
+        if (dist < RM_EPSILON) {
+            RM_REC(end(RM_WALK_HIT));
+            break;
+        }
+        if (t > RM_MAX_DIST) {
+            RM_REC(end(RM_WALK_FAR));
+            break;
+        }
     }
     return t;
 }
@@ -574,8 +608,8 @@ __device__ double ray_march(const RmRenderParams &P, const Ray &ray, uint32_t &c
 //   2 AdaptiveStep    adaptiveStep.ts:22-105    MAX_STEPS 200, step = clamp(0.8 d, 0.025, 0.5) or 0.01 near
 //   3 AdaptiveStepV2  adaptiveStepV2.ts:22-124  overshoot by overshootFactor, step back when spheres do not overlap
 //   4 AdaptiveStepV3  adaptiveStepV3.ts:22-137  as V2 plus the "bridging" third evaluation
-template <int ACCEL, int GEN>
-__device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint32_t &count, uint32_t &iters) {
+template <int ACCEL, int GEN, typename... REC>
+__device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint32_t &count, uint32_t &iters, REC &...rec) {
     const int alg = P.algorithm;
     const int max_steps = (alg == 1 || alg == 2) ? 200 : 100;
     const double FIXED_STEP_SIZE = 0.1, STEP_SCALE = 0.8;
@@ -598,20 +632,29 @@ __device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint3
         } else {
             haveCur = bvh_next_interval(P, ray, ri, -__builtin_inf(), -1, cur);
         }
-        if (!haveCur) return RM_MAX_DIST;
+        if (!haveCur) {
+            RM_REC(end(RM_WALK_ACCEL));
+            return RM_MAX_DIST;
+        }
     }
     for (int i = 0; i < max_steps; ++i) {
         Vec3f p = point_at(ray, t);
         int onode = -1;
         double skip = 0.0;
         if (ACCEL == 2) {  // BVH.onRayMarchStep (bvh.ts:204-240)
-            if (!haveCur) return RM_MAX_DIST;
+            if (!haveCur) {
+                RM_REC(end(RM_WALK_ACCEL));
+                return RM_MAX_DIST;
+            }
             if (t < cur.tEnter) skip = cur.tEnter - t;
             else if (t > cur.tExit) {
                 const Interval prev = cur;
                 haveCur = lists ? bvh_next<false>(v1_view(P), ray, ri, L, prev.tEnter, prev.ord, cur)
                                 : bvh_next_interval(P, ray, ri, prev.tEnter, prev.ord, cur);
-                if (!haveCur) return RM_MAX_DIST;
+                if (!haveCur) {
+                    RM_REC(end(RM_WALK_ACCEL));
+                    return RM_MAX_DIST;
+                }
                 if (cur.tEnter > t) skip = cur.tEnter - t;
             }
         } else if (ACCEL == 1) {
@@ -619,16 +662,23 @@ __device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint3
             if (onode >= 0) skip = oct_skip(P.oct[onode], ray, t, oinv);
         }
         if (skip > 0.0) {
+            RM_REC(skip(t, skip));
             t += skip;
-            if (t > RM_MAX_DIST) break;
+            if (t > RM_MAX_DIST) {
+                RM_REC(end(RM_WALK_FAR));
+                break;
+            }
             prevSDF = 0.0;  // adaptiveStepV2.ts:73-74 (harmless for the marchers without this state)
             prevStep = 0.0;
             continue;
         }
+        [[maybe_unused]] const uint32_t before = count;
         const double dist = ACCEL == 1 ? oct_node_distance<GEN>(P, onode, p, count) : scene_distance<ACCEL, GEN>(P, p, count);
+        RM_REC(eval(t, dist, count - before));
         iters += 1;
         if (alg == 1 || alg == 2) {
             if (dist < RM_EPSILON) {
+                RM_REC(end(RM_WALK_HIT));
                 hit = true;
                 break;
             }
@@ -641,12 +691,21 @@ __device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint3
                 if (step > MAX_STEP) step = MAX_STEP;
             }
             t += step;
-            if (t > RM_MAX_DIST) break;
+            if (t > RM_MAX_DIST) {
+                RM_REC(end(RM_WALK_FAR));
+                break;
+            }
             continue;
         }
         // AdaptiveStepV2 / V3
-        if (dist < RM_EPSILON) break;
-        if (t > RM_MAX_DIST) break;
+        if (dist < RM_EPSILON) {
+            RM_REC(end(RM_WALK_HIT));
+            break;
+        }
+        if (t > RM_MAX_DIST) {
+            RM_REC(end(RM_WALK_FAR));
+            break;
+        }
         if (i == 0 || prevSDF == 0.0) {
             t += dist;
             prevSDF = dist;
@@ -670,7 +729,9 @@ __device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint3
         const double originalPos = t - prevStep;
         t = originalPos + prevSDF;
         p = point_at(ray, t);
+        [[maybe_unused]] const uint32_t before3 = count;
         const double d3 = scene_distance<ACCEL, GEN>(P, p, count);
+        RM_REC(eval(t, d3, count - before3));
         iters += 1;
         if (prevSDF + dist + d3 >= prevStep) {
             t = originalPos + prevStep + dist;
@@ -685,6 +746,8 @@ __device__ double ray_march_other(const RmRenderParams &P, const Ray &ray, uint3
     if (alg == 1 || alg == 2) return hit ? t : RM_MAX_DIST;
     return t;
 }
+
+#undef RM_REC
 
 // Workgroup id -> tile for the one-ray-per-lane kernels.  Workgroups go to the eight XCDs round-robin (id % 8), each with
 // its own L2; a wave tile is 8 pixels wide, so a tile row writes 32-byte pieces of 128-byte lines.  Tiles are therefore
@@ -1441,6 +1504,81 @@ __global__ __launch_bounds__(256) void light_kernel(const RmRenderParams P, cons
     light_body<ACCEL, OTHER, GEN>(P, A);
 }
 
+// ------------------------------------------------------------------ walk queries (rm_ray_walk)
+
+// query_body's march (no normal) with a recorder: the summary of include/rm_raymarch.h (rm_walk) in registers and, when the
+// launch wants traces (A.steps, the same for every lane), the first A.cap records of the ray at A.steps + i * A.cap.  The
+// record index is all the recorder counts: EVAL records are the marcher's iters, the sum of their counts is its count, and
+// the SKIP records are the rest.  A record leaves as plain stores (24 bytes at an 8-byte aligned address).
+struct WalkRecorder {
+    RmWalkStep *out;   // the ray's first slot, or null
+    uint32_t cap, k;   // slots of the ray; records so far
+    double min_dist, t_min, skipped;
+    int end_reason;
+    __device__ __forceinline__ void put(double t, double value, uint32_t n, int kind) {
+        if (out && k < cap) {
+            RmWalkStep s;
+            s.t = t;
+            s.value = value;
+            s.count = n;
+            s.kind = kind;
+            out[k] = s;
+        }
+        k += 1;
+    }
+    __device__ __forceinline__ void eval(double t, double value, uint32_t n) {
+        put(t, value, n, 0);
+        if (value < min_dist) {  // (a NaN is never taken; the first record to reach the minimum keeps t_min)
+            min_dist = value;
+            t_min = t;
+        }
+    }
+    __device__ __forceinline__ void skip(double t, double value) {
+        put(t, value, 0, 1);
+        skipped += value;
+    }
+    __device__ __forceinline__ void end(int reason) { end_reason = reason; }
+};
+
+template <int ACCEL, bool OTHER, int GEN>
+__device__ __forceinline__ void walk_body(const RmRenderParams &P, const RmWalkArgs &A) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    Ray ray;
+    ray.o = Vec3f{A.origins[3 * i], A.origins[3 * i + 1], A.origins[3 * i + 2]};
+    ray.d = Vec3f{A.dirs[3 * i], A.dirs[3 * i + 1], A.dirs[3 * i + 2]};
+    ray.od[0] = static_cast<double>(ray.o.x);
+    ray.od[1] = static_cast<double>(ray.o.y);
+    ray.od[2] = static_cast<double>(ray.o.z);
+    WalkRecorder rec;
+    rec.out = A.steps ? A.steps + i * A.cap : nullptr;
+    rec.cap = static_cast<uint32_t>(A.cap);
+    rec.k = 0;
+    rec.min_dist = __builtin_inf();
+    rec.t_min = 0.0;
+    rec.skipped = 0.0;
+    rec.end_reason = RM_WALK_STEPS;
+    uint32_t count = 0, iters = 0;
+    const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters, rec) : ray_march<ACCEL, GEN>(P, ray, count, iters, rec);
+    if (A.walks) {
+        RmWalkSummary w;
+        w.t = t;
+        w.min_dist = rec.min_dist;
+        w.t_min = rec.t_min;
+        w.skipped = rec.skipped;
+        w.evals = iters;
+        w.skips = rec.k - iters;
+        w.sdf_calls = count;
+        w.end = rec.end_reason;
+        A.walks[i] = w;
+    }
+}
+
+template <int ACCEL, bool OTHER, int GEN>
+__global__ __launch_bounds__(256) void walk_kernel(const RmRenderParams P, const RmWalkArgs A) {
+    walk_body<ACCEL, OTHER, GEN>(P, A);
+}
+
 #ifndef RM_LENGTH_SQRT
 __global__ __launch_bounds__(256) void hypot_kernel(const float *xyz, int64_t n, double *out) {
     const int64_t i = blockIdx.x * static_cast<int64_t>(blockDim.x) + threadIdx.x;
@@ -1748,6 +1886,28 @@ hipError_t RM_LEN_VARIANT(rm_launch_light)(const RmRenderParams &p, const RmLigh
     }
     RM_DISPATCH(RM_LK)
 #undef RM_LK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_walk)(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n <= 0) return hipSuccess;
+    const int threads = 256;
+    const dim3 grid(static_cast<unsigned>((a.n + threads - 1) / threads)), block(threads);
+    const V1Lds lds = v1_lds_layout(p, threads, true);  // as rm_launch_query: the march is a render's
+    const size_t shmem = lds.bytes;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    pl.v1_list_offset = lds.v1_list_offset;
+#define RM_WK(A, O, G)                                                                \
+    {                                                                                 \
+        hipLaunchKernelGGL((walk_kernel<A, O, G>), grid, block, shmem, stream, pl, a); \
+        if (kernel_name) *kernel_name = RM_KERNEL_NAME(walk_kernel, A, O, G);         \
+    }
+    RM_DISPATCH(RM_WK)
+#undef RM_WK
     return hipGetLastError();
 }
 

@@ -217,6 +217,13 @@ class Raymarcher:
                                ao_strength=ao_strength, algorithm=self.algorithm, time=scene.time,
                                overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None))
 
+    def walkBatch(self, scene, origins, directions, trace=False, cap=200):
+        """How this marcher walks each ray (Context.walk with this marcher, its options and the scene's time) -> walks, or
+        (walks, steps) with `trace`."""
+        scene._activate()
+        return scene.ctx.walk(origins, directions, algorithm=self.algorithm, time=scene.time,
+                              overshoot=getattr(self, "overshootFactor", None), step=getattr(self, "stepSize", None), trace=trace, cap=cap)
+
 
 class SphereTracer(Raymarcher):  # cpu_algorithms/sphereTracer.ts
     algorithm = "sphere-tracer"

@@ -336,6 +336,63 @@ RM_API int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_ligh
                                const void *d_origins, const void *d_dirs, void *d_t, void *d_iters, void *d_sdf_calls,
                                void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2, void *stream);
 
+/* ---- walk queries: how a marcher walked a ray ------------------------------------------ */
+
+typedef enum rm_step_kind { RM_STEP_EVAL = 0, RM_STEP_SKIP = 1 } rm_step_kind;
+typedef struct rm_step {      /* 24 bytes */
+    double   t;               /* march parameter the record was made at */
+    double   value;           /* EVAL: the distance returned; SKIP: the skip length (> 0) */
+    uint32_t count;           /* EVAL: primitives that evaluation counted; SKIP: 0 */
+    int32_t  kind;            /* rm_step_kind */
+} rm_step;
+
+typedef enum rm_walk_end { RM_END_HIT = 0, RM_END_FAR = 1, RM_END_STEPS = 2, RM_END_ACCEL = 3 } rm_walk_end;
+typedef struct rm_walk {      /* 48 bytes */
+    double   t;               /* what rm_ray_march returns for the ray */
+    double   min_dist, t_min; /* smallest EVAL value and the t of the record that set it */
+    double   skipped;         /* sum of the SKIP values */
+    uint32_t evals, skips;    /* EVAL records (== iters) and SKIP records the walk produced */
+    uint32_t sdf_calls;       /* sum of the EVAL counts (== rm_ray_march's sdf_calls with normal = 0) */
+    int32_t  end;             /* rm_walk_end */
+} rm_walk;
+
+#define RM_WALK_MAX_STEPS 256
+
+/* The walk itself, for n caller-supplied rays, in ONE launch: a summary per ray (walks[i]) and, with steps != NULL, the
+ * ray's step trace, one record per distance evaluation and per acceleration-structure skip.  The ray is marched exactly
+ * as rm_ray_march marches it with q->normal = 0; q->normal is ignored: a walk never evaluates a normal.  The rule, per
+ * ray (o, d):
+ *   EVAL  every call of Scene.getDistance the marcher makes -- the calls that add to iters, AdaptiveStepV3's bridging
+ *         third evaluation (adaptiveStepV3.ts:103-130) included -- produces one EVAL record: t = the parameter the point
+ *         p = f32(o + d t) was formed at, value = the distance, count = the primitives that call counted.
+ *   SKIP  every loop trip in which the acceleration structure answered a positive skip (BVH.onRayMarchStep: tEnter - t,
+ *         bvh.ts:204-240; Octree.marchRay's step, octree.ts:250-294) produces one SKIP record: t = the parameter before
+ *         the skip, value = the skip, count = 0.  The marcher continues at t + value, one binary64 addition.
+ *   No other record: V2's and V3's step-back moves t without one, and the next EVAL record's t shows it.  Records are in
+ *   program order, and no walk produces more than 200 (100 or 200 loop trips; V3 evaluates at most twice in each of 100).
+ *   end   the first of: RM_END_ACCEL -- the BVH gave no interval at onRayMarchStart or onRayMarchStep answered -1 (t is
+ *         10, possibly with no record at all); RM_END_HIT -- an evaluation below 0.001 ended the loop; RM_END_FAR --
+ *         t > 10 ended it, after a step or after a skip; RM_END_STEPS -- the trip limit ran out.  FixedStep and
+ *         AdaptiveStep return t = 10 for FAR and STEPS, as rm_ray_march does.
+ *   min_dist starts at +infinity and is replaced when value < min_dist (a NaN is never taken; the first record to reach
+ *   the minimum keeps t_min); without an EVAL record min_dist is +infinity and t_min 0.  skipped starts at 0.0 and adds
+ *   the skips in order, in binary64.  evals == rm_ray_march's iters and sdf_calls its sdf_calls, t its t.
+ * walks[i] is always written whole.  With steps != NULL the first min(cap, evals + skips) records of ray i go to
+ * steps[i * cap ...] and the remaining slots of that ray are left untouched; steps == NULL gives summaries only, and
+ * walks may be NULL when steps is not.  Checks and return codes are rm_ray_march's, plus RM_E_INVALID -- like every
+ * argument check ahead of RM_E_NO_DEVICE and RM_E_NO_SCENE -- for a cap outside 0 .. RM_WALK_MAX_STEPS, steps != NULL
+ * with cap == 0, and both outputs NULL with n > 0; n == 0 is RM_OK.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone; rm_last_kernel names the walk_kernel<...>
+ * instantiation.  Host buffers, synchronous, chunked through the context's scratch buffer as rm_ray_march: 4 M rays a
+ * chunk for summaries only; with step records at most 64 MiB of them a chunk and at least one ray (cap 256: 10 922 rays). */
+RM_API int rm_ray_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz,
+                       int32_t cap, rm_walk *walks, rm_step *steps);
+
+/* Same with device pointers (d_walks: rm_walk[n]; d_steps: rm_step[n * cap]), asynchronous on `stream`, as
+ * rm_ray_march_device.  Also RM_E_INVALID for a d_walks or d_steps that is not 8-byte aligned. */
+RM_API int rm_ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs,
+                              int32_t cap, void *d_walks, void *d_steps, void *stream);
+
 /* The binary32 light direction PhongModel normalises from (1, -1, 1.5) (phongModel.ts:15-16), what RM_SHADE_PHONG and
  * rm_shade_lit shade with; host-only, no ctx.  RM_E_INVALID for a null pointer. */
 RM_API int rm_phong_light(float dir3[3]);

@@ -7,7 +7,13 @@ C3: the 3840 x 2160 camera rays of the Dense Sphere Grid (BVH, angles 0.2 / 0.5)
 order (the wave tiles of the one-ray-per-lane render) -- against the `kernel` = 1 render of the same frame, which runs the
 same per-ray code.  C5: 1 M random rays from inside the octree cube through the 10 000-sphere scene.
 Times are HIP-event kernel times (median of --reps launches after --warmup); every variant must give the same hash
-(the depth / normal bytes and the u16 counters, in pixel order).  One JSON line per case."""
+(the depth / normal bytes and the u16 counters, in pixel order).  One JSON line per case.
+
+--walk measures the walk query (rm_ray_walk_device, walk_kernel<...>) on the same rays instead: the march without normals
+(what a walk marches), the summaries-only walk and the traced walk at cap 200, outputs allocated once (the traced C3 frame
+holds 8.3 M x 200 x 24 B = 39.8 GB of records).  With RM_HIP_LIB naming an older build of the library that has no walk
+entries, only the march is timed: the figure to put beside the walk's.  The summaries must carry the march's t, iterations
+and SDF calls, traced or not."""
 import argparse
 import hashlib
 import json
@@ -53,6 +59,53 @@ def query_bytes(R, out, order=None):
     return depth, normal, (sdf.view(np.uint32) & 0xFFFF).astype(np.uint16), (it.view(np.uint32) & 0xFFFF).astype(np.uint16)
 
 
+def walk_case(R, torch, args, ctx, res, sets):
+    """--walk: for every (name, origins, directions) of `sets` the march without normals, the summaries-only walk and the
+    traced walk at cap 200 through the device entries."""
+    import ctypes as C
+    N = R._native
+    L = N.lib()
+    have_walk = hasattr(L, "rm_ray_walk_device")
+    cap = 200
+    q = N.rm_ray_query()
+    q.algorithm, q.normal, q.time = 0, 0, 0.0
+    q.overshoot_factor = q.step_size = float("nan")
+    ok = True
+    for name, og, dg in sets:
+        n = og.shape[0]
+        out = [None]
+
+        def march():
+            out[0] = ctx.ray_march(og, dg, normal=False)
+        res["march_%s_ms" % name] = timed(torch, march, args.warmup, args.reps)
+        res["march_%s_per_s" % name] = n / (res["march_%s_ms" % name] * 1e-3)
+        res["march_kernel"] = ctx.last_kernel()
+        if not have_walk:
+            continue
+        t, it, sdf = (x.cpu().numpy() for x in out[0][:3])
+        walks = torch.empty((n, 48), dtype=torch.uint8, device="cuda")
+        for label, steps in (("walk", None), ("trace", torch.empty(n * cap * 24, dtype=torch.uint8, device="cuda"))):
+            sp = C.c_void_p(steps.data_ptr()) if steps is not None else None
+
+            def run():
+                N.check(ctx._h, L.rm_ray_walk_device(ctx._h, C.byref(q), n, C.c_void_p(og.data_ptr()), C.c_void_p(dg.data_ptr()),
+                                                     cap if steps is not None else 0, C.c_void_p(walks.data_ptr()), sp,
+                                                     C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+            walks.zero_()
+            res["%s_%s_ms" % (label, name)] = timed(torch, run, args.warmup, args.reps)
+            res["%s_%s_per_s" % (label, name)] = n / (res["%s_%s_ms" % (label, name)] * 1e-3)
+            res["%s_%s_vs_march" % (label, name)] = res["%s_%s_ms" % (label, name)] / res["march_%s_ms" % name]
+            w = walks.cpu().numpy().view(N.WALK_DTYPE).reshape(-1)
+            ok = ok and w["t"].tobytes() == t.tobytes() and np.array_equal(w["evals"], it.view(np.uint32)) and \
+                np.array_equal(w["sdf_calls"], sdf.view(np.uint32))
+            if steps is not None:
+                res["records_%s" % name] = int(w["evals"].astype(np.int64).sum() + w["skips"].sum())
+            del steps
+        res["walk_kernel"] = ctx.last_kernel()
+    res["same_hash"] = ok  # (the summaries carry the march's numbers)
+    return res
+
+
 def case_c3(R, torch, args):
     W, H, ang = 3840, 2160, (0.2, 0.5)
     scene = R.Scene("BVH")
@@ -60,6 +113,14 @@ def case_c3(R, torch, args):
     scene.camera.setAngles(*ang)
     ctx = scene.ctx
     res = {"case": "C3 rays", "rays": W * H}
+    if args.walk:
+        org, dirs = R.camera_rays(W, H, *ang)
+        y, x = np.divmod(np.arange(W * H), W)
+        sets = []
+        for name, order in (("row", None), ("tile8x8", np.lexsort((x % 8, y % 8, x // 8, y // 8)))):
+            d = dirs if order is None else dirs[order]
+            sets.append((name, torch.from_numpy(np.broadcast_to(org, d.shape).copy()).cuda(), torch.from_numpy(np.ascontiguousarray(d)).cuda()))
+        return walk_case(R, torch, args, ctx, res, sets)
     # the kernel = 1 render of the same frame
     ctx.set_option("kernel", 1)
     bufs = [torch.zeros(W * H, dtype=torch.uint8, device="cuda"), torch.zeros(3 * W * H, dtype=torch.uint8, device="cuda"),
@@ -114,6 +175,8 @@ def case_c5(R, torch, args):
     def run():
         out[0] = ctx.ray_march(og, dg)
     res = {"case": "C5 rays", "rays": n}
+    if args.walk:
+        return walk_case(R, torch, args, ctx, res, [("random", og, dg)])
     res["rays_ms"] = timed(torch, run, args.warmup, args.reps)
     res["rays_per_s"] = n / (res["rays_ms"] * 1e-3)
     res["kernel"] = ctx.last_kernel()
@@ -132,6 +195,7 @@ def main():
     ap.add_argument("--case", choices=("C3", "C5"), required=True)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--walk", action="store_true", help="time the walk query (summaries only, and traced at cap 200) beside the march")
     args = ap.parse_args()
     import torch
     import cpu_raymarcher_amd as R
