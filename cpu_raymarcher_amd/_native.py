@@ -73,6 +73,20 @@ WALK_ENDS = {0: "hit", 1: "far", 2: "steps", 3: "accel"}
 RM_WALK_MAX_STEPS = 256
 
 
+class rm_lattice(C.Structure):  # include/rm_raymarch.h: struct rm_lattice
+    _fields_ = [("origin", C.c_float * 3), ("du", C.c_float * 3), ("dv", C.c_float * 3), ("dw", C.c_float * 3),
+                ("nu", C.c_int32), ("nv", C.c_int32), ("nw", C.c_int32), ("reserved", C.c_int32), ("time", C.c_double)]
+
+
+class rm_field_shade(C.Structure):  # include/rm_raymarch.h: struct rm_field_shade
+    _fields_ = [("map", C.c_int32), ("reserved", C.c_int32), ("range", C.c_double), ("band", C.c_double), ("line", C.c_double),
+                ("lo", C.c_uint32), ("hi", C.c_uint32)]
+
+
+# rm_field_map by name
+FIELD_MAPS = {"distance": 0, "count": 1}
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -154,6 +168,11 @@ SIGNATURES = {
     "rm_camera_from_angles": (C.c_int, [C.c_double, C.c_double, _VP, _VP]),
     "rm_scene_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     "rm_debug_wave_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
+    "rm_scene_field": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, _VP]),
+    "rm_scene_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, _VP, _VP]),
+    "rm_lattice_points": (C.c_int, [C.POINTER(rm_lattice), C.c_int64, C.c_int64, _VP]),
+    "rm_shade_field_device": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP, _VP]),
+    "rm_shade_field": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

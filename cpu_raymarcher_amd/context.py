@@ -697,6 +697,87 @@ class Context:
                                                      _ptr(rgba)))
         return rgba
 
+    # ---- field queries: distance slices and volumes sampled on the device ------------------
+    def lattice_points(self, origin, du, dv, dw=None, shape=(1, 1)):
+        """The points of a lattice (rm_lattice_points) as float32 [nw, nv, nu, 3]: point (i, j, k) is
+        f32(origin + i * du + j * dv + k * dw), formed in binary64 with one rounding, exactly what `field` evaluates."""
+        lat = make_lattice(origin, du, dv, dw, shape)
+        out = np.zeros((lat.nw, lat.nv, lat.nu, 3), np.float32)
+        rc = N.lib().rm_lattice_points(C.byref(lat), 0, out.size // 3, _ptr(out))
+        if rc != N.RM_OK:
+            raise N.RmError(rc, "rm_lattice_points")
+        return out
+
+    def field(self, origin, du, dv, dw=None, shape=(1, 1), time=0.0, dist32=False, count=True, device=False):
+        """Scene.getDistance at every point of a lattice the device forms itself (rm_scene_field; the rule is in
+        include/rm_raymarch.h): point (i, j, k) = f32(origin + i * du + j * dv + k * dw), shape = (nu, nv) for a slice or
+        (nu, nv, nw) for a volume.  Returns (dist, count) shaped [nw, nv, nu] -- [nv, nu] for a two-element shape --: dist
+        float64, or float32 with `dist32` (half the traffic of a volume), count uint32 (the primitives each evaluation
+        counted) or None without `count`.  The values are scene_distance's at lattice_points(...) with the scene at `time`;
+        scene_set_time's value is left alone.  numpy results come through the host entry (synchronous); device=True returns
+        torch CUDA tensors through rm_scene_field_device on torch's current stream (count an int32 tensor holding the u32
+        bits, as ray_march's counts)."""
+        lat = make_lattice(origin, du, dv, dw, shape, time)
+        full = (lat.nw, lat.nv, lat.nu)
+        out_shape = full[1:] if len(tuple(shape)) == 2 else full
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            d = torch.empty(full, dtype=torch.float32 if dist32 else torch.float64, device=dev)
+            c = torch.empty(full, dtype=torch.int32, device=dev) if count else None
+            N.check(self._h, N.lib().rm_scene_field_device(self._h, C.byref(lat), None if dist32 else _ptr(d), _ptr(d) if dist32 else None,
+                                                           _ptr(c), _current_stream_ptr()))
+        else:
+            d = np.zeros(full, np.float32 if dist32 else np.float64)
+            c = np.zeros(full, np.uint32) if count else None
+            N.check(self._h, N.lib().rm_scene_field(self._h, C.byref(lat), None if dist32 else _ptr(d), _ptr(d) if dist32 else None, _ptr(c)))
+        return d.reshape(out_shape), (None if c is None else c.reshape(out_shape))
+
+    def field_slice(self, axis="z", offset=0.0, half_extent=5.0, size=(256, 256), time=0.0, dist32=False, count=True, device=False):
+        """`field` of slice_lattice(axis, offset, half_extent, size): the axis-aligned plane through the scene, sampled at
+        texel centres -> (dist, count) shaped [size[1], size[0]]."""
+        origin, du, dv, shape = slice_lattice(axis, offset, half_extent, size)
+        return self.field(origin, du, dv, shape=shape, time=time, dist32=dist32, count=count, device=device)
+
+    @staticmethod
+    def slice_lattice(axis="z", offset=0.0, half_extent=5.0, size=(256, 256)):
+        """The module's slice_lattice: (origin, du, dv, shape) of an axis-aligned plane sampled at texel centres."""
+        return slice_lattice(axis, offset, half_extent, size)
+
+    def shade_field(self, values, rgba=None, map="distance", range=2.0, band=0.25, line=0.02, lo=0, hi=0):
+        """The slice image of `field`'s results (rm_shade_field_device / rm_shade_field; the rule is in
+        include/rm_raymarch.h).  map "distance": `values` float64 -- blue inside, orange outside, brighter with |d| up to
+        `range`, every second iso-band of width `band` darker, a white zero line of half-width `line`, magenta for NaN.  map
+        "count": `values` uint32 (or the int32 tensor `field` returns on the device), the red-green ramp of shade_ranged over
+        (lo, hi).  The distance-map defaults are choices for a scene of unit-sized objects, not measured optima.  `rgba`:
+        uint8 [..., 4] of values' shape, or None: one is allocated beside `values`.  Returns it.  torch CUDA tensors -> the
+        device entry on torch's current stream; numpy arrays -> the host entry (synchronous)."""
+        m = N.FIELD_MAPS[map] if isinstance(map, str) else int(map)
+        sh = N.rm_field_shade()
+        sh.map, sh.reserved = m, 0
+        sh.range, sh.band, sh.line = float(range), float(band), float(line)
+        sh.lo, sh.hi = int(lo), int(hi)
+        if _is_torch(values):
+            import torch
+            want = (torch.float64,) if m == 0 else (torch.int32, torch.uint32)
+            if not (values.is_cuda and values.is_contiguous() and values.dtype in want):
+                raise ValueError("values must be a contiguous CUDA tensor of %s" % ("float64" if m == 0 else "int32 / uint32"))
+            n = values.numel()
+            if rgba is None:
+                rgba = torch.empty(tuple(values.shape) + (4,), dtype=torch.uint8, device=values.device)
+            if not (_is_torch(rgba) and rgba.is_cuda and rgba.is_contiguous() and rgba.numel() * rgba.element_size() >= 4 * n):
+                raise ValueError("rgba must be a contiguous CUDA tensor of 4 bytes per value")
+            self._same_device(dict(values=values, rgba=rgba))
+            N.check(self._h, N.lib().rm_shade_field_device(self._h, C.byref(sh), n, _ptr(values), _ptr(rgba), _current_stream_ptr()))
+            return rgba
+        values = np.ascontiguousarray(values, dtype=np.float64 if m == 0 else np.uint32)
+        if rgba is None:
+            rgba = np.zeros(values.shape + (4,), np.uint8)
+        if not (isinstance(rgba, np.ndarray) and rgba.flags["C_CONTIGUOUS"] and rgba.flags["WRITEABLE"] and rgba.nbytes >= 4 * values.size):
+            raise ValueError("rgba must be a writable contiguous numpy array of 4 bytes per value")
+        N.check(self._h, N.lib().rm_shade_field(self._h, C.byref(sh), values.size, _ptr(values), _ptr(rgba)))
+        return rgba
+
     def _same_device(self, bufs):
         for name, b in bufs.items():
             if b is not None and _is_torch(b) and b.is_cuda and b.device.index != self.device:
@@ -865,6 +946,38 @@ def _selftest_recip(self, mode):
 
 
 Context.selftest_recip = _selftest_recip
+
+
+def make_lattice(origin, du, dv, dw=None, shape=(1, 1), time=0.0):
+    """An rm_lattice: point (i, j, k) = origin + i * du + j * dv + k * dw (float32 vectors; dw None: zero), shape (nu, nv) or
+    (nu, nv, nw), the query's time."""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) not in (2, 3):
+        raise ValueError("shape is (nu, nv) or (nu, nv, nw)")
+    lat = N.rm_lattice()
+    for name, v in (("origin", origin), ("du", du), ("dv", dv), ("dw", (0, 0, 0) if dw is None else dw)):
+        getattr(lat, name)[:] = [float(x) for x in np.asarray(v, np.float32).reshape(3)]
+    lat.nu, lat.nv, lat.nw = shape[0], shape[1], (shape[2] if len(shape) == 3 else 1)
+    if min(lat.nu, lat.nv, lat.nw) < 0 or max(lat.nu, lat.nv, lat.nw) > 65535:
+        raise ValueError("lattice counts must be in [0, 65535]")
+    lat.reserved = 0
+    lat.time = float(time)
+    return lat
+
+
+def slice_lattice(axis="z", offset=0.0, half_extent=5.0, size=(256, 256)):
+    """The lattice of the axis-aligned plane axis = offset, [-half_extent, half_extent] in both other axes, sampled at the
+    centres of size = (nu, nv) texels -> (origin, du, dv, (nu, nv)), float32 vectors, what Context.field takes.  i runs along
+    x (y for axis "x"), j along y (z for axes "x" and "y")."""
+    a = {"x": 0, "y": 1, "z": 2}[axis]
+    u, v = [c for c in range(3) if c != a]
+    nu, nv = int(size[0]), int(size[1])
+    h = float(half_extent)
+    su, sv = 2.0 * h / max(nu, 1), 2.0 * h / max(nv, 1)
+    origin, du, dv = np.zeros(3, np.float32), np.zeros(3, np.float32), np.zeros(3, np.float32)
+    origin[a], origin[u], origin[v] = offset, -h + 0.5 * su, -h + 0.5 * sv
+    du[u], dv[v] = su, sv
+    return origin, du, dv, (nu, nv)
 
 
 def make_transform(x, y, z, rotation=None):

@@ -1458,6 +1458,84 @@ int check_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, 
     return RM_OK;
 }
 
+// ---- field queries: the lattice, its checks and the two kernels' arguments
+
+static_assert(sizeof(rm_lattice) == 72 && sizeof(rm_field_shade) == 40, "field query layout");
+static_assert(RM_FIELD_MAP_DISTANCE == 0 && RM_FIELD_MAP_COUNT == 1, "shade_field_kernel reads these values");
+
+// component c of lattice point (i, j, k): binary64, left to right, one rounding (the header's rule; field_kernel forms the same)
+float lattice_component(const rm_lattice &l, int c, int64_t i, int64_t j, int64_t k) {
+    return static_cast<float>(((static_cast<double>(l.origin[c]) + static_cast<double>(i) * static_cast<double>(l.du[c])) +
+                               static_cast<double>(j) * static_cast<double>(l.dv[c])) +
+                              static_cast<double>(k) * static_cast<double>(l.dw[c]));
+}
+
+// null when the lattice is well formed (then *n = nu * nv * nw), else what is wrong with it
+const char *lattice_error(const rm_lattice *l, int64_t *n) {
+    if (!l) return "null lattice";
+    if (l->nu < 0 || l->nu > 65535 || l->nv < 0 || l->nv > 65535 || l->nw < 0 || l->nw > 65535) return "lattice counts must be in [0, 65535]";
+    if (l->reserved != 0) return "rm_lattice.reserved must be 0";
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(l->origin[c]) || !std::isfinite(l->du[c]) || !std::isfinite(l->dv[c]) || !std::isfinite(l->dw[c])) return "non-finite lattice vector";
+    if (!std::isfinite(l->time)) return "non-finite time";
+    // every component is monotone in each index: the eight corners (indices 0 and count - 1; 0 for an empty axis) bound all points
+    const int64_t last[3] = {l->nu > 0 ? l->nu - 1 : 0, l->nv > 0 ? l->nv - 1 : 0, l->nw > 0 ? l->nw - 1 : 0};
+    for (int corner = 0; corner < 8; ++corner)
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(lattice_component(*l, c, corner & 1 ? last[0] : 0, corner & 2 ? last[1] : 0, corner & 4 ? last[2] : 0)))
+                return "a lattice corner is not a finite binary32 point";
+    *n = static_cast<int64_t>(l->nu) * l->nv * l->nw;
+    return nullptr;
+}
+
+// what both forms of rm_scene_field check, arguments first; *n receives the point count
+int check_field(rm_ctx *ctx, const rm_lattice *lat, const void *dist, const void *dist32, const void *count, int64_t *n) {
+    if (const char *bad = lattice_error(lat, n)) return fail(ctx, RM_E_INVALID, bad);
+    if (reinterpret_cast<uintptr_t>(dist) & 7) return fail(ctx, RM_E_INVALID, "dist must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(dist32) | reinterpret_cast<uintptr_t>(count)) & 3) return fail(ctx, RM_E_INVALID, "dist32 and count must be 4-byte aligned");
+    if (*n > 0 && !dist && !dist32 && !count) return fail(ctx, RM_E_INVALID, "no output asked for");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
+// The parameter block and the lattice of a field query: the active scene as rm_scene_distance passes it, at the lattice's own
+// time (ctx->time is not touched), ahead-of-time kernels only.
+void fill_field(const rm_ctx *ctx, const rm_lattice *lat, RmRenderParams &p, RmFieldArgs &a) {
+    std::memset(&p, 0, sizeof p);
+    fill_scene_view(ctx, p);
+    p.time = lat->time;
+    p.filter = static_cast<int32_t>(ctx->opt_filter);
+    p.tile_w = 8;
+    p.rtc_function = nullptr;
+    std::memset(&a, 0, sizeof a);
+    for (int c = 0; c < 3; ++c) {
+        a.origin[c] = lat->origin[c];
+        a.du[c] = lat->du[c];
+        a.dv[c] = lat->dv[c];
+        a.dw[c] = lat->dw[c];
+    }
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+}
+
+int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const void *values, const void *rgba) {
+    if (!sh || !values || !rgba) return fail(ctx, RM_E_INVALID, "null argument");
+    if (n < 0) return fail(ctx, RM_E_INVALID, "negative count");
+    if (sh->map != RM_FIELD_MAP_DISTANCE && sh->map != RM_FIELD_MAP_COUNT) return fail(ctx, RM_E_INVALID, "map must be RM_FIELD_MAP_DISTANCE or RM_FIELD_MAP_COUNT");
+    if (sh->reserved != 0) return fail(ctx, RM_E_INVALID, "rm_field_shade.reserved must be 0");
+    if (sh->map == RM_FIELD_MAP_DISTANCE) {
+        if (!std::isfinite(sh->range) || !(sh->range > 0) || !std::isfinite(sh->band) || !(sh->band > 0)) return fail(ctx, RM_E_INVALID, "range and band must be finite and positive");
+        if (!std::isfinite(sh->line) || sh->line < 0) return fail(ctx, RM_E_INVALID, "line must be finite and not negative");
+        if (reinterpret_cast<uintptr_t>(values) & 7) return fail(ctx, RM_E_INVALID, "distances must be 8-byte aligned");
+    } else {
+        if (sh->lo > sh->hi) return fail(ctx, RM_E_INVALID, "lo > hi");
+        if (reinterpret_cast<uintptr_t>(values) & 3) return fail(ctx, RM_E_INVALID, "counts must be 4-byte aligned");
+    }
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU shading path");
+    return RM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2185,6 +2263,118 @@ int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *d
                                                                                   st.at<uint32_t>(o_cnt), ctx->stream));
     RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
     RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_lattice_points(const rm_lattice *lattice, int64_t first, int64_t n, float *points_xyz) {
+    int64_t total = 0;
+    if (lattice_error(lattice, &total)) return RM_E_INVALID;
+    if (first < 0 || n < 0 || first > total || n > total - first || (n > 0 && !points_xyz)) return RM_E_INVALID;
+    if (!n) return RM_OK;
+    const int64_t nu = lattice->nu, nv = lattice->nv;
+    int64_t row = first / nu, i = first % nu, k = row / nv, j = row % nv;
+    for (int64_t at = 0; at < n; ++at) {
+        for (int c = 0; c < 3; ++c) points_xyz[3 * at + c] = lattice_component(*lattice, c, i, j, k);
+        if (++i == nu) {
+            i = 0;
+            if (++j == nv) {
+                j = 0;
+                ++k;
+            }
+        }
+    }
+    return RM_OK;
+}
+
+int rm_scene_field_device(rm_ctx *ctx, const rm_lattice *lattice, void *d_dist, void *d_dist32, void *d_count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    const int rc = check_field(ctx, lattice, d_dist, d_dist32, d_count, &n);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmFieldArgs a;
+    fill_field(ctx, lattice, p, a);
+    a.dist = static_cast<double *>(d_dist);
+    a.dist32 = static_cast<float *>(d_dist32);
+    a.count = static_cast<uint32_t *>(d_count);
+    a.first = 0;
+    a.n = n;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int rm_scene_field(rm_ctx *ctx, const rm_lattice *lattice, double *dist, float *dist32, uint32_t *count) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    int rc = check_field(ctx, lattice, dist, dist32, count, &n);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmFieldArgs a;
+    fill_field(ctx, lattice, p, a);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Through the scratch buffer in chunks of whole lattice rows, at most 4 M points (16 B per point with every output: 64 MB);
+    // a row always fits (nu <= 65535).  Only the outputs asked for are staged and copied back.
+    const int64_t nu = lattice->nu, rows = n / nu;
+    int64_t chunk_rows = (int64_t(1) << 22) / nu;
+    if (chunk_rows < 1) chunk_rows = 1;
+    if (chunk_rows > rows) chunk_rows = rows;
+    const size_t c = static_cast<size_t>(chunk_rows * nu);
+    Staging st{ctx};
+    const size_t o_dist = st.region(dist ? 8 * c : 0), o_d32 = st.region(dist32 ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
+    if ((rc = st.reserve())) return rc;
+    a.dist = dist ? st.at<double>(o_dist) : nullptr;
+    a.dist32 = dist32 ? st.at<float>(o_d32) : nullptr;
+    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
+    for (int64_t r = 0; r < rows; r += chunk_rows) {
+        const int64_t m = (rows - r < chunk_rows ? rows - r : chunk_rows) * nu;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(r * nu);
+        a.first = r * nu;
+        a.n = m;
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
+        if (dist) RM_HIP(ctx, st.out(dist + at, o_dist, 8 * k));
+        if (dist32) RM_HIP(ctx, st.out(dist32 + at, o_d32, 4 * k));
+        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
+int rm_shade_field_device(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *d_values, void *d_rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_field(ctx, shade, n, d_values, d_rgba);
+    if (rc || !n) return rc;
+    RmShadeFieldArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.values = d_values;
+    args.rgba = static_cast<uint8_t *>(d_rgba);
+    args.n = n;
+    args.range = shade->range;
+    args.band = shade->band;
+    args.line = shade->line;
+    args.lo = shade->lo;
+    args.hi = shade->hi;
+    args.map = shade->map;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const hipError_t e = rm_launch_shade_field(args, static_cast<hipStream_t>(stream), &ctx->last_kernel);
+    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_field_device");
+    return RM_OK;
+}
+
+int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *values, uint8_t *rgba) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_shade_field(ctx, shade, n, values, rgba);
+    if (rc || !n) return rc;
+    const size_t total = static_cast<size_t>(n), each = shade->map == RM_FIELD_MAP_DISTANCE ? 8 : 4;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const size_t o_val = st.region(each * total), o_rgba = st.region(4 * total);
+    if ((rc = st.reserve())) return rc;
+    RM_HIP(ctx, st.in(o_val, values, each * total));
+    rc = rm_shade_field_device(ctx, shade, n, st.at<void>(o_val), st.at<void>(o_rgba), ctx->stream);
+    if (rc) return rc;
+    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
     RM_HIP(ctx, st.sync());
     return RM_OK;
 }

@@ -700,6 +700,41 @@ __global__ __launch_bounds__(256) void shade_lit_kernel(const RmShadeLitArgs A) 
     }
 }
 
+// ------------------------------------------------------------------ shade_field_kernel (rm_shade_field_device)
+//
+// The slice image of a field query: one value in (a binary64 distance or a u32 evaluation count), one pixel out, the
+// workgroups stride over the n values.  DISTANCE: two binary64 quotients (|d| / range, |d| / band), everything after them in
+// integers -- intensity 96 .. 255 by |d|, every second iso-band a quarter darker, blue inside and orange outside, a white zero
+// line, magenta for NaN.  COUNT: shade_ranged_kernel's s and ramp over (lo, hi), the quotient taken in 64 bits.
+__device__ __forceinline__ unsigned int field_distance_pixel(double d, double range, double band, double line) {
+    if (d != d) return 0xFFFF00FFu;
+    const double a = __builtin_fabs(d);
+    if (a < line) return 0xFFFFFFFFu;
+    const double x = a / range, y = a / band;
+    const int s = x >= 1.0 ? 255 : static_cast<int>(x * 255.0);
+    int I = 96 + 159 * s / 255;
+    const int q = y < 2147483648.0 ? static_cast<int>(y) : 0;
+    if (q & 1) I = I * 3 / 4;
+    const bool inside = d < 0.0;  // -0.0 counts as outside
+    const unsigned int r = (inside ? 60 : 230) * I / 255, g = (inside ? 120 : 140) * I / 255, b = (inside ? 230 : 50) * I / 255;
+    return 0xFF000000u | r | (g << 8) | (b << 16);
+}
+
+__device__ __forceinline__ unsigned int field_count_pixel(unsigned int v, unsigned int lo, unsigned int hi) {
+    const unsigned int s = v <= lo ? 0u : v >= hi ? 255u : static_cast<unsigned int>(static_cast<unsigned long long>(v - lo) * 255ull / (hi - lo));
+    return 0xFF000000u | min(2u * s, 255u) | (min(512u - 2u * s, 255u) << 8);
+}
+
+__global__ __launch_bounds__(256) void shade_field_kernel(const RmShadeFieldArgs A) {
+    const bool whole = (reinterpret_cast<uintptr_t>(A.rgba) & 3) == 0;
+    const long long step = static_cast<long long>(gridDim.x) * 256;
+    for (long long i = static_cast<long long>(blockIdx.x) * 256 + threadIdx.x; i < A.n; i += step) {
+        const unsigned int px = A.map == 0 ? field_distance_pixel(static_cast<const double *>(A.values)[i], A.range, A.band, A.line)
+                                           : field_count_pixel(static_cast<const unsigned int *>(A.values)[i], A.lo, A.hi);
+        store_pixel(A.rgba, i, px, whole);
+    }
+}
+
 }  // namespace
 
 hipError_t rm_launch_assemble(const unsigned char *gathered, int64_t rank_stride, int64_t section_offset, int32_t row_bytes,
@@ -790,5 +825,15 @@ hipError_t rm_launch_shade_lit(const RmShadeLitArgs &a, int32_t n_frames, hipStr
     const dim3 grid(static_cast<unsigned>(per_frame), static_cast<unsigned>(n_frames)), block(256);
     hipLaunchKernelGGL(shade_lit_kernel, grid, block, 0, stream, a);
     if (kernel_name) *kernel_name = "shade_lit_kernel";
+    return hipGetLastError();
+}
+
+hipError_t rm_launch_shade_field(const RmShadeFieldArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (a.n <= 0) return hipSuccess;
+    // ~4096 workgroups per launch, never more than there are values for
+    const int64_t want = (a.n + 255) / 256;
+    const dim3 grid(static_cast<unsigned>(want < 4096 ? want : 4096)), block(256);
+    hipLaunchKernelGGL(shade_field_kernel, grid, block, 0, stream, a);
+    if (kernel_name) *kernel_name = "shade_field_kernel";
     return hipGetLastError();
 }

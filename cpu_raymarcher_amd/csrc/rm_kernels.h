@@ -122,6 +122,26 @@ struct RmWalkArgs {
     long long n;
     int cap, pad;
 };
+// rm_scene_field (rm_kernels.hip, field_kernel): the lattice (rm_lattice, its binary32 vectors widened: exact), the linear range
+// [first, first + n) of one call and the outputs, indexed from `first`, each of which may be null
+struct RmFieldArgs {
+    double origin[3], du[3], dv[3], dw[3];
+    double *dist;
+    float *dist32;
+    uint32_t *count;
+    long long first, n;
+    long long block_first;  // set by the launcher: the first of the range's workgroups this launch runs
+    unsigned int nu, nv;
+};
+// rm_shade_field_device (rm_frame_ops.hip, shade_field_kernel): n values (f64 distances or u32 counts) -> n pixels
+struct RmShadeFieldArgs {
+    const void *values;
+    uint8_t *rgba;
+    long long n;
+    double range, band, line;
+    unsigned int lo, hi;
+    int map, pad;  // 0 distance, 1 count
+};
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
@@ -186,6 +206,11 @@ hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmLightArgs &a, h
 hipError_t rm_launch_walk(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 
+// Field query (rm_scene_field): Scene.getDistance at the lattice points of a.first .. a.first + a.n, formed on the device
+// (include/rm_raymarch.h has the rule).  field_kernel, the LDS of rm_launch_distance, ahead-of-time kernels only.
+hipError_t rm_launch_field(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_field_sqrt(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
+
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics
 // (acc non-null) accumulated in blocks[k] (zero before and after the launch) and written to acc[k].  One launch of
@@ -219,6 +244,8 @@ hipError_t rm_launch_hist(const RmHistArgs &a, bool masked, int32_t n_frames, in
 hipError_t rm_launch_shade_ranged(const RmShadeRangedArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name);
 // rm_shade_lit_device: ONE launch of shade_lit_kernel; nothing without a pixel or a frame.
 hipError_t rm_launch_shade_lit(const RmShadeLitArgs &a, int32_t n_frames, hipStream_t stream, const char **kernel_name);
+// rm_shade_field_device: ONE launch of shade_field_kernel; nothing without a value.
+hipError_t rm_launch_shade_field(const RmShadeFieldArgs &a, hipStream_t stream, const char **kernel_name);
 
 hipError_t rm_launch_hypot(const float *xyz, int64_t n, double *out, hipStream_t stream);
 // rm_jsmath.h on the device: fn 0 sin, 1 cos, 2 atan2, 3 asin, 4 log, 5 pow, 6 round, 7 atan

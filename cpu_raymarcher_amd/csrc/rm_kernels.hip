@@ -1274,6 +1274,29 @@ __global__ __launch_bounds__(256) void distance_kernel(const RmRenderParams P, c
     distance_body<ACCEL, GEN>(P, pts, n, dist, count);
 }
 
+// ------------------------------------------------------------------ field queries (rm_scene_field)
+//
+// Scene.getDistance at the points of a lattice the lanes form themselves (include/rm_raymarch.h has the rule): lane r of the
+// range takes the point of linear index A.first + r -- 64 consecutive i per wave --, forms each component in binary64 left to
+// right with one rounding to binary32 (no contraction: -ffp-contract=off) and calls the scene_distance every other kernel
+// calls.  Outputs are indexed by r, each may be null.  (8 x 8 tiles of (i, j) per wave were measured and lost: DESIGN.md 4.)
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void field_kernel(const RmRenderParams P, const RmFieldArgs A) {
+    const unsigned long long r = ((static_cast<unsigned long long>(A.block_first) + blockIdx.x) << 8) + threadIdx.x;
+    if (r >= static_cast<unsigned long long>(A.n)) return;
+    const unsigned long long l = static_cast<unsigned long long>(A.first) + r, row = l / A.nu, k = row / A.nv;
+    const double fi = static_cast<double>(l - row * A.nu), fj = static_cast<double>(row - k * A.nv), fk = static_cast<double>(k);
+    Vec3f p;
+    p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
+    p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
+    p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+    uint32_t c = 0;
+    const double d = scene_distance<ACCEL, GEN>(P, p, c);
+    if (A.dist) A.dist[r] = d;
+    if (A.dist32) A.dist32[r] = static_cast<float>(d);
+    if (A.count) A.count[r] = c;
+}
+
 // ------------------------------------------------------------------ object picking (rm_ray_pick)
 
 // Primitive.sdf of device object `id`, bit-identical to the value the render's Scene.getDistance paths take for it (the
@@ -1834,6 +1857,33 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
     RM_DISPATCH(RM_DK)
 #undef RM_DK
     return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n <= 0 || a.nu == 0 || a.nv == 0) return hipSuccess;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_distance: a point has no ray
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    RmFieldArgs al = a;
+    const long long blocks = (a.n + 255) / 256;
+    for (long long done = 0; done < blocks; done += 1ll << 22) {  // one grid dimension: at most 2^22 workgroups (2^30 points) a launch
+        const long long m = blocks - done < (1ll << 22) ? blocks - done : (1ll << 22);
+        const dim3 grid(static_cast<unsigned>(m)), block(256);
+        al.block_first = done;
+#define RM_FLDK(A, O, G)                                                              \
+    {                                                                                 \
+        hipLaunchKernelGGL((field_kernel<A, G>), grid, block, shmem, stream, pl, al); \
+        if (kernel_name) *kernel_name = "field_kernel<" #A ", " #G ">" RM_LEN_TAG;    \
+    }
+        RM_DISPATCH(RM_FLDK)
+#undef RM_FLDK
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t RM_LEN_VARIANT(rm_launch_query)(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,

@@ -105,6 +105,12 @@ class Scene:
         self._activate()
         return self.ctx.scene_distance(points)
 
+    def distanceField(self, origin, du, dv, dw=None, shape=(1, 1), dist32=False, count=True, device=False):
+        """getDistance at every point origin + i * du + j * dv + k * dw of a lattice formed on the device, at this scene's
+        own time (Context.field) -> (dist, count) shaped [nw, nv, nu], [nv, nu] for shape = (nu, nv)."""
+        self._activate()
+        return self.ctx.field(origin, du, dv, dw, shape=shape, time=self.time, dist32=dist32, count=count, device=device)
+
     def info(self):
         self._activate()
         return self.ctx.scene_info()

@@ -219,6 +219,53 @@ RM_API int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t 
 RM_API int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist,
                              uint32_t *count);
 
+/* ---- field queries: distance slices and volumes sampled on the device ------------------- */
+
+typedef struct rm_lattice {      /* 72 bytes */
+    float   origin[3];           /* point (0, 0, 0) */
+    float   du[3], dv[3], dw[3]; /* step per index i, j, k */
+    int32_t nu, nv, nw;          /* points along i, j, k: each 0 .. 65535 */
+    int32_t reserved;            /* 0 */
+    double  time;                /* Scene.updateTime for this query; rm_scene_set_time's value is kept */
+} rm_lattice;
+
+/* Scene.getDistance (scene.ts:144-190) at the n = nu * nv * nw points of a lattice the device forms itself: a plane through
+ * the scene (nw = 1) for a slice image, a volume for a mesher, a collision grid or a 3D texture -- 72 bytes go up instead of
+ * 12 per point.  The rule:
+ *   index   point (i, j, k), 0 <= i < nu, 0 <= j < nv, 0 <= k < nw, has the linear index (k * nv + j) * nu + i, a 64-bit value;
+ *           every output is indexed by it.
+ *   point   component c of point (i, j, k) is
+ *             f32((((double)origin[c] + (double)i * (double)du[c]) + (double)j * (double)dv[c]) + (double)k * (double)dw[c]):
+ *           binary64 arithmetic, left to right, no contraction (no fused multiply-add), ONE rounding to binary32 at the end.
+ *           rm_lattice_points writes exactly these points on the host.
+ *   value   dist[l] and count[l] are what rm_scene_distance returns for that point with Scene.updateTime(lattice->time):
+ *           the same distance function the renders and the ray queries call, the primitives it counted; dist32[l] is
+ *           (float)dist[l].  getDistance is taken as it is: an empty octree leaf answers minDistance * 0.99, the minimum starts
+ *           at 10, a point in no BVH leaf box is measured against every primitive -- a field under a BVH or an octree is the
+ *           bound the marchers walk through, not always the exact distance, and a slice of it shows where.
+ * Each of dist (f64[n]), dist32 (f32[n]) and count (u32[n]) may be NULL.  RM_E_INVALID -- like every argument check ahead of
+ * RM_E_NO_DEVICE and RM_E_NO_SCENE, and also when a count is 0 -- for a null lattice, a count outside 0 .. 65535,
+ * reserved != 0, a non-finite origin, step or time, a non-finite binary32 component at any of the lattice's eight corner points
+ * (indices 0 and count - 1, 0 on an axis without points; each component is monotone in each index, so the corners bound every
+ * point), a dist that is not 8-byte or a dist32 / count that is not 4-byte aligned, and all three outputs NULL with n > 0.  A
+ * lattice with a zero count has n = 0: RM_OK, nothing is launched or written.
+ * Not a render entry: it neither consumes nor fires rm_render_attach_diagnostics and leaves rm_scene_set_time's value
+ * alone; knobs apply as for rm_scene_distance (`filter`, `length`).  Scenes whose renders run a run-time specialised kernel
+ * are served by the ahead-of-time kernels here (same values).  rm_last_kernel names the field_kernel<ACCEL, GEN>
+ * instantiation.  Host buffers, synchronous, chunked through the context's scratch buffer: a chunk is a set of whole lattice
+ * rows (runs of nu points) of at most 4 M points -- one row when nu alone is more --, and only the outputs asked for are staged
+ * and copied back. */
+RM_API int rm_scene_field(rm_ctx *ctx, const rm_lattice *lattice, double *dist, float *dist32, uint32_t *count);
+
+/* Same with device pointers, asynchronous on `stream` (a hipStream_t passed as void*, NULL = default stream), as
+ * rm_ray_march_device: one launch for up to 2^30 points. */
+RM_API int rm_scene_field_device(rm_ctx *ctx, const rm_lattice *lattice, void *d_dist, void *d_dist32, void *d_count, void *stream);
+
+/* The points of linear indices [first, first + n) of a lattice by the rule above (f32[3n]), host-only, no ctx:
+ * rm_scene_distance over them is by definition what the field query returns.  RM_E_INVALID for a lattice rm_scene_field
+ * refuses, first < 0, n < 0, first + n > nu * nv * nw or null points_xyz with n > 0. */
+RM_API int rm_lattice_points(const rm_lattice *lattice, int64_t first, int64_t n, float *points_xyz);
+
 /* ---- ray queries ------------------------------------------------------------------ */
 
 typedef struct rm_ray_query {
@@ -620,6 +667,33 @@ RM_API int rm_shade_lit_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t
 /* Same with host buffers (synchronous). */
 RM_API int rm_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint8_t *depth,
                         const uint8_t *normal, const float *lit, const float *ao, uint8_t *rgba);
+
+/* The slice image of a field query, ONE launch, asynchronous on `stream`: n values -> n pixels.  d_values is f64[n] (dist)
+ * for RM_FIELD_MAP_DISTANCE and u32[n] (count) for RM_FIELD_MAP_COUNT; d_rgba is 4n bytes, written as whole pixels with alpha
+ * 255, no pre-clear.
+ *   DISTANCE, per value d:  1. d is NaN: (255, 0, 255).  2. a = |d|; a < line: (255, 255, 255), the zero line.
+ *     3. x = a / range; s = 255 if x >= 1, else (int)(x * 255.0), truncating; I = 96 + 159 * s / 255.
+ *     4. y = a / band; q = (int)y if y < 2147483648.0, else 0; q odd: I = I * 3 / 4 -- every second iso-band is darker.
+ *     5. the base colour is (60, 120, 230) if d < 0 (inside), else (230, 140, 50); -0.0 counts as outside.
+ *     6. each channel is base * I / 255.  x and y are binary64 quotients; every other division is integer division.
+ *   COUNT, per value v: s = 0 if v <= lo, 255 if v >= hi, else (v - lo) * 255 / (hi - lo) in 64 bits, and the ramp of
+ *     rm_shade_ranged_device: R = min(2s, 255), G = min(512 - 2s, 255), B = 0.
+ * RM_E_INVALID -- checked before anything else -- for a null argument, n < 0, a map outside the enum, reserved != 0, for
+ * DISTANCE a non-finite or non-positive range or band or a non-finite or negative line, for COUNT lo > hi, a d_values that is
+ * not 8-byte (DISTANCE) or 4-byte (COUNT) aligned.  RM_E_NO_DEVICE on a host-only context; never RM_E_NO_SCENE; n == 0 is
+ * RM_OK.  Not a render entry; uses no ring: no call waits.  rm_last_kernel: shade_field_kernel. */
+typedef enum rm_field_map { RM_FIELD_MAP_DISTANCE = 0, RM_FIELD_MAP_COUNT = 1 } rm_field_map;
+typedef struct rm_field_shade {   /* 40 bytes */
+    int32_t  map, reserved;       /* rm_field_map; 0 */
+    double   range;               /* DISTANCE: |d| at which the intensity saturates; finite, > 0 */
+    double   band;                /* DISTANCE: width of an iso-band; finite, > 0 */
+    double   line;                /* DISTANCE: half-width of the white zero line; finite, >= 0 */
+    uint32_t lo, hi;              /* COUNT: ramp range, lo <= hi */
+} rm_field_shade;
+RM_API int rm_shade_field_device(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *d_values, void *d_rgba,
+                                 void *stream);
+/* Same with host buffers (synchronous), staged through the context's scratch buffer. */
+RM_API int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *values, uint8_t *rgba);
 
 /* Multi-GPU sharding of one Job (replaces the contiguous ceil(H/N) split of main.ts:444-449
  * by a load-balanced one): the rows [y_start, y_end) are cut into stripes of `stripe_rows`
