@@ -244,55 +244,71 @@ class Context:
         rm_ray_pick_device on torch's current stream (object an int32 tensor on the same device)."""
         return self._rays(True, origins, directions, algorithm, normal, time, overshoot, step)
 
-    def _rays(self, pick, origins, directions, algorithm, normal, time, overshoot, step):
-        """ray_march (pick False) or pick (True)."""
+    @staticmethod
+    def _query(algorithm, normal, time, overshoot, step):
+        """The rm_ray_query of a call; overshoot / step None -> NaN (JS `undefined`)."""
         q = N.rm_ray_query()
         q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
         q.normal = 1 if normal else 0
         q.time = float(time)
         q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
         q.step_size = float(step) if step is not None else float("nan")
+        return q
+
+    def _ray_input(self, origins, directions):
+        """(on_device, origins, directions, n) of a ray query's input: contiguous float32 CUDA tensors of this context's device
+        as they are, anything else as float32 [n, 3] numpy arrays."""
         if _is_torch(origins) or _is_torch(directions):
             import torch
             if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
                 raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
             self._same_device(dict(origins=origins, directions=directions))
-            if origins.device != directions.device:
-                raise ValueError("origins and directions are on different devices")
             for name, b in (("origins", origins), ("directions", directions)):
                 if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
                     raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
-            n = origins.numel() // 3
-            if directions.numel() != 3 * n:
+            if directions.numel() != origins.numel():
                 raise ValueError("origins and directions differ in length")
-            dev = origins.device
-            t = torch.empty(n, dtype=torch.float64, device=dev)
-            it = torch.empty(n, dtype=torch.int32, device=dev)  # the u32 counts as int32 tensors (same bits; counts stay < 2^31)
-            sdf = torch.empty(n, dtype=torch.int32, device=dev)
-            nrm = torch.empty((n, 3), dtype=torch.float32, device=dev)
-            if not pick:
-                N.check(self._h, N.lib().rm_ray_march_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
-                                                             _ptr(sdf), _ptr(nrm), _current_stream_ptr()))
-                return t, it, sdf, nrm
-            obj = torch.empty(n, dtype=torch.int32, device=dev)
-            N.check(self._h, N.lib().rm_ray_pick_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), _ptr(t), _ptr(it),
-                                                        _ptr(sdf), _ptr(nrm), _ptr(obj), _current_stream_ptr()))
-            return t, it, sdf, nrm, obj
+            return True, origins, directions, origins.numel() // 3
         o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
         d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
         if len(o) != len(d):
             raise ValueError("origins and directions differ in length")
-        n = len(o)
-        t = np.zeros(n, np.float64)
-        it = np.zeros(n, np.uint32)
-        sdf = np.zeros(n, np.uint32)
-        nrm = np.zeros((n, 3), np.float32)
-        if not pick:
-            N.check(self._h, N.lib().rm_ray_march(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm)))
-            return t, it, sdf, nrm
-        obj = np.zeros(n, np.int32)
-        N.check(self._h, N.lib().rm_ray_pick(self._h, C.byref(q), n, _ptr(o), _ptr(d), _ptr(t), _ptr(it), _ptr(sdf), _ptr(nrm), _ptr(obj)))
-        return t, it, sdf, nrm, obj
+        return False, o, d, len(o)
+
+    def _frame_rays(self, width, height, pitch, yaw, y_start, y_end, device):
+        """The camera rays of rows [y_start, y_end) (y_end None: height) with the origin repeated per ray -> (origins, directions,
+        rows): float32 [n, 3] numpy arrays, or with `device` CUDA tensors of this context's device, and the number of rows."""
+        if y_end is None:
+            y_end = height
+        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
+        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
+        if device:
+            import torch
+            dev = torch.device("cuda", self.device)
+            o, dirs = torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev)
+        return o, dirs, y_end - y_start
+
+    def _rays(self, pick, origins, directions, algorithm, normal, time, overshoot, step):
+        """ray_march (pick False) or pick (True)."""
+        q = self._query(algorithm, normal, time, overshoot, step)
+        on_dev, o, d, n = self._ray_input(origins, directions)
+        L = N.lib()
+        if on_dev:
+            import torch
+            # (the u32 counts as int32 tensors: same bits; counts stay < 2^31)
+            out = [torch.empty(n, dtype=torch.float64, device=o.device), torch.empty(n, dtype=torch.int32, device=o.device),
+                   torch.empty(n, dtype=torch.int32, device=o.device), torch.empty((n, 3), dtype=torch.float32, device=o.device)]
+            if pick:
+                out.append(torch.empty(n, dtype=torch.int32, device=o.device))
+            entry = L.rm_ray_pick_device if pick else L.rm_ray_march_device
+            N.check(self._h, entry(self._h, C.byref(q), n, _ptr(o), _ptr(d), *[_ptr(b) for b in out], _current_stream_ptr()))
+            return tuple(out)
+        out = [np.zeros(n, np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32)]
+        if pick:
+            out.append(np.zeros(n, np.int32))
+        entry = L.rm_ray_pick if pick else L.rm_ray_march
+        N.check(self._h, entry(self._h, C.byref(q), n, _ptr(o), _ptr(d), *[_ptr(b) for b in out]))
+        return tuple(out)
 
     def object_ids(self, width, height, pitch=0.0, yaw=0.0, y_start=0, y_end=None, algorithm="sphere-tracer", time=0.0,
                    device=False):
@@ -300,15 +316,8 @@ class Context:
         mask or outline without a render kernel): the frame's camera rays (camera_rays) picked without normals ->
         int32[(y_end - y_start) * width], tile-local rows, row-major, -1 where no object was hit.  device=True: the rays go
         to rm_ray_pick_device as CUDA tensors of this context's device and the result is one."""
-        if y_end is None:
-            y_end = height
-        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
-        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
-        if not device:
-            return self.pick(o, dirs, algorithm, normal=False, time=time)[4]
-        import torch
-        dev = torch.device("cuda", self.device)
-        return self.pick(torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev), algorithm, normal=False, time=time)[4]
+        o, dirs, _ = self._frame_rays(width, height, pitch, yaw, y_start, y_end, device)
+        return self.pick(o, dirs, algorithm, normal=False, time=time)[4]
 
     def light(self, origins, directions, light_dir=None, bias=0.02, ao_samples=5, ao_step=0.05, ao_strength=1.0,
               algorithm="sphere-tracer", time=0.0, overshoot=None, step=None):
@@ -322,40 +331,22 @@ class Context:
         normalised.  The default bias must exceed the marchers' hit threshold of 0.001, or every shadow ray hits its own
         surface at once; 0.02 is a choice that clears it on the presets, not a measured optimum.  numpy input -> the host
         entry; torch CUDA tensors -> rm_ray_light_device on torch's current stream (counts as int32 tensors, as ray_march)."""
-        q = N.rm_ray_query()
-        q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
-        q.normal = 1
-        q.time = float(time)
-        q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
-        q.step_size = float(step) if step is not None else float("nan")
+        q = self._query(algorithm, True, time, overshoot, step)
         lt = N.rm_light()
         lt.dir[:] = [float(v) for v in (phong_light() if light_dir is None else np.asarray(light_dir, np.float32).reshape(3))]
         lt.ao_samples = int(ao_samples)
         lt.bias, lt.ao_step, lt.ao_strength = float(bias), float(ao_step), float(ao_strength)
-        if _is_torch(origins) or _is_torch(directions):
+        on_dev, o, d, n = self._ray_input(origins, directions)
+        if on_dev:
             import torch
-            if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
-                raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
-            self._same_device(dict(origins=origins, directions=directions))
-            for name, b in (("origins", origins), ("directions", directions)):
-                if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
-                    raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
-            n = origins.numel() // 3
-            if directions.numel() != 3 * n:
-                raise ValueError("origins and directions differ in length")
-            dev = origins.device
+            dev = o.device
             out = (torch.empty(n, dtype=torch.float64, device=dev), torch.empty(n, dtype=torch.int32, device=dev),
                    torch.empty(n, dtype=torch.int32, device=dev), torch.empty((n, 3), dtype=torch.float32, device=dev),
                    torch.empty(n, dtype=torch.float32, device=dev), torch.empty(n, dtype=torch.float32, device=dev),
                    torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev))
-            N.check(self._h, N.lib().rm_ray_light_device(self._h, C.byref(q), C.byref(lt), n, _ptr(origins), _ptr(directions),
-                                                         *[_ptr(b) for b in out], _current_stream_ptr()))
+            N.check(self._h, N.lib().rm_ray_light_device(self._h, C.byref(q), C.byref(lt), n, _ptr(o), _ptr(d), *[_ptr(b) for b in out],
+                                                         _current_stream_ptr()))
             return out
-        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise ValueError("origins and directions differ in length")
-        n = len(o)
         out = (np.zeros(n, np.float64), np.zeros(n, np.uint32), np.zeros(n, np.uint32), np.zeros((n, 3), np.float32),
                np.zeros(n, np.float32), np.zeros(n, np.float32), np.zeros(n, np.uint32), np.zeros(n, np.uint32))
         N.check(self._h, N.lib().rm_ray_light(self._h, C.byref(q), C.byref(lt), n, _ptr(o), _ptr(d), *[_ptr(b) for b in out]))
@@ -367,17 +358,9 @@ class Context:
         frame's camera rays (camera_rays) through `light` -> (lit, ao), float32[(y_end - y_start) * width] each, tile-local
         rows, row-major: what shade_lit takes beside the frame's depth and normal buffers.  device=True: the rays go to
         rm_ray_light_device as CUDA tensors of this context's device and the results are tensors."""
-        if y_end is None:
-            y_end = height
-        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
-        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
-        kw = dict(light_dir=light_dir, bias=bias, ao_samples=ao_samples, ao_step=ao_step, ao_strength=ao_strength, algorithm=algorithm,
-                  time=time)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            o, dirs = torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev)
-        out = self.light(o, dirs, **kw)
+        o, dirs, _ = self._frame_rays(width, height, pitch, yaw, y_start, y_end, device)
+        out = self.light(o, dirs, light_dir=light_dir, bias=bias, ao_samples=ao_samples, ao_step=ao_step, ao_strength=ao_strength,
+                         algorithm=algorithm, time=time)
         return out[4], out[5]
 
     def walk(self, origins, directions, algorithm="sphere-tracer", time=0.0, overshoot=None, step=None, trace=False, cap=200):
@@ -389,39 +372,19 @@ class Context:
         before it, its length) -- and zeros behind them.  No walk produces more than 200 records.  numpy input -> the host
         entry and structured arrays; torch CUDA tensors -> rm_ray_walk_device on torch's current stream and uint8 tensors
         [n, 48] and [n, cap, 24] holding the same records (`.cpu().numpy().view(...)` with the dtypes gives the fields)."""
-        q = N.rm_ray_query()
-        q.algorithm = (N.lib().rm_algorithm_from_string(algorithm.encode()) if isinstance(algorithm, str) else int(algorithm))
-        q.normal = 0
-        q.time = float(time)
-        q.overshoot_factor = float(overshoot) if overshoot is not None else float("nan")
-        q.step_size = float(step) if step is not None else float("nan")
+        q = self._query(algorithm, False, time, overshoot, step)
         cap = int(cap)
-        if _is_torch(origins) or _is_torch(directions):
+        on_dev, o, d, n = self._ray_input(origins, directions)
+        if on_dev:
             import torch
-            if not (_is_torch(origins) and _is_torch(directions) and origins.is_cuda and directions.is_cuda):
-                raise ValueError("origins and directions must both be CUDA tensors (or both numpy arrays)")
-            self._same_device(dict(origins=origins, directions=directions))
-            for name, b in (("origins", origins), ("directions", directions)):
-                if b.dtype != torch.float32 or not b.is_contiguous() or b.numel() % 3:
-                    raise ValueError("%s must be a contiguous float32 tensor of [n, 3]" % name)
-            n = origins.numel() // 3
-            if directions.numel() != 3 * n:
-                raise ValueError("origins and directions differ in length")
-            dev = origins.device
-            walks = torch.empty((n, 48), dtype=torch.uint8, device=dev)
-            steps = torch.zeros((n, max(cap, 0), 24), dtype=torch.uint8, device=dev) if trace else None
-            N.check(self._h, N.lib().rm_ray_walk_device(self._h, C.byref(q), n, _ptr(origins), _ptr(directions), cap if trace else 0,
-                                                        _ptr(walks), _ptr(steps) if trace else None, _current_stream_ptr()))
+            walks = torch.empty((n, 48), dtype=torch.uint8, device=o.device)
+            steps = torch.zeros((n, max(cap, 0), 24), dtype=torch.uint8, device=o.device) if trace else None
+            N.check(self._h, N.lib().rm_ray_walk_device(self._h, C.byref(q), n, _ptr(o), _ptr(d), cap if trace else 0, _ptr(walks), _ptr(steps),
+                                                        _current_stream_ptr()))
             return (walks, steps) if trace else walks
-        o = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-        d = np.ascontiguousarray(directions, dtype=np.float32).reshape(-1, 3)
-        if len(o) != len(d):
-            raise ValueError("origins and directions differ in length")
-        n = len(o)
         walks = np.zeros(n, N.WALK_DTYPE)
         steps = np.zeros((n, max(cap, 0)), N.STEP_DTYPE) if trace else None
-        N.check(self._h, N.lib().rm_ray_walk(self._h, C.byref(q), n, _ptr(o), _ptr(d), cap if trace else 0, _ptr(walks),
-                                             _ptr(steps) if trace else None))
+        N.check(self._h, N.lib().rm_ray_walk(self._h, C.byref(q), n, _ptr(o), _ptr(d), cap if trace else 0, _ptr(walks), _ptr(steps)))
         return (walks, steps) if trace else walks
 
     def walk_frame(self, width, height, pitch=0.0, yaw=0.0, y_start=0, y_end=None, algorithm="sphere-tracer", time=0.0,
@@ -430,22 +393,15 @@ class Context:
         frame's camera rays (camera_rays) through `walk` -> WALK_DTYPE[rows, width], tile-local rows (an end-reason map is
         its "end" field, a skipped-distance map its "skipped").  device=True: the rays go to rm_ray_walk_device as CUDA
         tensors of this context's device and the result is a uint8 tensor [rows, width, 48]."""
-        if y_end is None:
-            y_end = height
-        org, dirs = camera_rays(width, height, pitch, yaw, y_start, y_end)
-        o = np.ascontiguousarray(np.broadcast_to(org, dirs.shape))
-        kw = dict(algorithm=algorithm, time=time, overshoot=overshoot, step=step)
-        if device:
-            import torch
-            dev = torch.device("cuda", self.device)
-            return self.walk(torch.from_numpy(o).to(dev), torch.from_numpy(dirs).to(dev), **kw).reshape(y_end - y_start, width, 48)
-        return self.walk(o, dirs, **kw).reshape(y_end - y_start, width)
+        o, dirs, rows = self._frame_rays(width, height, pitch, yaw, y_start, y_end, device)
+        walks = self.walk(o, dirs, algorithm=algorithm, time=time, overshoot=overshoot, step=step)
+        return walks.reshape(rows, width, 48) if device else walks.reshape(rows, width)
 
     def trace_pixel(self, width, height, x, y, pitch=0.0, yaw=0.0, algorithm="sphere-tracer", time=0.0, overshoot=None, step=None):
         """The whole walk of the ray through pixel (x, y) of a width x height frame of the active scene -> (walk, steps):
         the pixel's summary record and its step records, trimmed to the evals + skips the walk produced."""
-        org, dirs = camera_rays(width, height, pitch, yaw, int(y), int(y) + 1)
-        walks, steps = self.walk(org.reshape(1, 3), dirs[int(x)].reshape(1, 3), algorithm=algorithm, time=time, overshoot=overshoot,
+        o, dirs, _ = self._frame_rays(width, height, pitch, yaw, int(y), int(y) + 1, False)
+        walks, steps = self.walk(o[int(x)].reshape(1, 3), dirs[int(x)].reshape(1, 3), algorithm=algorithm, time=time, overshoot=overshoot,
                                  step=step, trace=True, cap=N.RM_WALK_MAX_STEPS)
         return walks[0], steps[0, :int(walks[0]["evals"]) + int(walks[0]["skips"])]
 

@@ -1021,63 +1021,95 @@ int check_query(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origi
     return RM_OK;
 }
 
-// rm_ray_march_device (pick false: cast_kernel, d_object unused) and rm_ray_pick_device (pick true: pick_kernel)
-int ray_query_device(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
-                     void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, d_origins, d_dirs);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_query_sqrt : rm_launch_query)(
-                    p, pick, static_cast<const float *>(d_origins), static_cast<const float *>(d_dirs), n, q->normal != 0, ctx->dev.slot_object,
-                    static_cast<double *>(d_t), static_cast<uint32_t *>(d_iters), static_cast<uint32_t *>(d_sdf_calls),
-                    static_cast<float *>(d_normal), static_cast<int32_t *>(d_object), static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
-}
+// One call of a ray query as data: what its family contributes to ray_call.  `args` is the kernel's argument block with the
+// non-pointer fields filled, `launch` the family's launcher by option `length`, `chunk` the most rays the host form takes
+// through the scratch buffer at a time, `cols` its n_cols buffers beside the rays.  A column that was not asked for (null) gets
+// no staging bytes and a null kernel pointer.
+struct RayColumn {
+    void *ptr;      // the caller's buffer: device (the _device form) or host
+    size_t bytes;   // per ray
+    size_t member;  // offsetof the pointer it feeds in the argument block
+    bool in;        // host form: the caller's content goes in ahead of the launch
+};
+constexpr int kRayMaxColumns = 8;
+template <typename Args>
+struct RayCall {
+    Args args;
+    hipError_t (*launch[2])(const RmRenderParams &, const RmRays &, const Args &, hipStream_t, const char **);
+    int64_t chunk;
+    int n_cols;
+    RayColumn cols[kRayMaxColumns];
+};
+constexpr int64_t kRayChunk = int64_t(1) << 22;  // 4 M rays: 208 MB with a march's columns, 224 MB a pick's, 272 MB a light's, 288 MB of walk summaries
 
-// rm_ray_march (pick false) and rm_ray_pick (pick true): host buffers, synchronous
-int ray_query_host(rm_ctx *ctx, bool pick, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
-                   uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
+// Both forms of every ray query.  `check` makes the family's own checks, ahead of check_query like every argument check ahead of
+// the device check; `describe` returns the family's RayCall once the arguments have passed.  host false: the rays and columns
+// are the caller's device buffers, one launch on `stream`.  host true: finite rays only, through the scratch buffer on the
+// context's stream in chunks of at most `chunk` rays, synchronous.  Nothing here depends on the family.
+template <typename Check, typename Describe>
+int ray_call(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs, bool host, void *stream, Check check,
+             Describe describe) {
     if (!ctx) return RM_E_INVALID;
-    int rc = check_query(ctx, q, n, origins_xyz, dirs_xyz);
+    int rc = check();
+    if (!rc) rc = check_query(ctx, q, n, origins, dirs);
     if (rc || !n) return rc;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
+    const float *origins_xyz = static_cast<const float *>(origins), *dirs_xyz = static_cast<const float *>(dirs);
+    if (host)
+        for (int64_t i = 0; i < 3 * n; ++i)
+            if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
     RmRenderParams p;
     rc = fill_query_params(ctx, q, p);
     if (rc) return rc;
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    // through the scratch buffer in chunks of at most 4 M rays (52 B per ray: 208 MB; a pick's objects 4 B more: 224 MB), whatever the batch
-    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
-    const size_t c = static_cast<size_t>(chunk);
+    auto c = describe();
+    const auto launch = c.launch[ctx->opt_length ? 1 : 0];
+    const auto feed = [&c](const RayColumn &col, void *ptr) { std::memcpy(reinterpret_cast<char *>(&c.args) + col.member, &ptr, sizeof ptr); };
+    if (!host) {
+        for (int j = 0; j < c.n_cols; ++j) feed(c.cols[j], c.cols[j].ptr);
+        RM_HIP(ctx, launch(p, RmRays{origins_xyz, dirs_xyz, n}, c.args, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+        return RM_OK;
+    }
+    const int64_t chunk = n < c.chunk ? n : c.chunk;
     Staging st{ctx};
-    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_t = st.region(8 * c), o_it = st.region(4 * c), o_sdf = st.region(4 * c),
-                 o_nrm = st.region(12 * c), o_obj = st.region(pick ? 4 * c : 0);
+    const size_t o_org = st.region(12 * static_cast<size_t>(chunk)), o_dirs = st.region(12 * static_cast<size_t>(chunk));
+    size_t o_col[kRayMaxColumns];
+    for (int j = 0; j < c.n_cols; ++j) o_col[j] = st.region(c.cols[j].ptr ? c.cols[j].bytes * static_cast<size_t>(chunk) : 0);
     if ((rc = st.reserve())) return rc;
+    for (int j = 0; j < c.n_cols; ++j) feed(c.cols[j], c.cols[j].ptr ? st.at<char>(o_col[j]) : nullptr);
     for (int64_t s = 0; s < n; s += chunk) {
         const int64_t m = n - s < chunk ? n - s : chunk;
         const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
         RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
         RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_query_sqrt : rm_launch_query)(
-                        p, pick, st.at<const float>(o_org), st.at<const float>(o_dirs), m, q->normal != 0, ctx->dev.slot_object,
-                        t ? st.at<double>(o_t) : nullptr, iters ? st.at<uint32_t>(o_it) : nullptr, sdf_calls ? st.at<uint32_t>(o_sdf) : nullptr,
-                        normal_xyz ? st.at<float>(o_nrm) : nullptr, object ? st.at<int32_t>(o_obj) : nullptr, ctx->stream, &ctx->last_kernel));
-        if (t) RM_HIP(ctx, st.out(t + at, o_t, 8 * k));
-        if (iters) RM_HIP(ctx, st.out(iters + at, o_it, 4 * k));
-        if (sdf_calls) RM_HIP(ctx, st.out(sdf_calls + at, o_sdf, 4 * k));
-        if (normal_xyz) RM_HIP(ctx, st.out(normal_xyz + 3 * at, o_nrm, 12 * k));
-        if (object) RM_HIP(ctx, st.out(object + at, o_obj, 4 * k));
+        for (int j = 0; j < c.n_cols; ++j) {
+            const RayColumn &col = c.cols[j];
+            if (col.ptr && col.in) RM_HIP(ctx, st.in(o_col[j], static_cast<char *>(col.ptr) + at * col.bytes, col.bytes * k));
+        }
+        RM_HIP(ctx, launch(p, RmRays{st.at<const float>(o_org), st.at<const float>(o_dirs), m}, c.args, ctx->stream, &ctx->last_kernel));
+        for (int j = 0; j < c.n_cols; ++j) {
+            const RayColumn &col = c.cols[j];
+            if (col.ptr) RM_HIP(ctx, st.out(static_cast<char *>(col.ptr) + at * col.bytes, o_col[j], col.bytes * k));
+        }
         RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
     }
     return RM_OK;
 }
 
-// what both forms of rm_ray_light check: the light (ahead of the device check, like every argument check), then check_query
-int check_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *origins, const void *dirs) {
+int no_check() { return RM_OK; }  // rm_ray_march and rm_ray_pick have no checks of their own
+
+// rm_ray_march (pick false: cast_kernel, no object column) and rm_ray_pick (pick true: pick_kernel)
+RayCall<RmQueryArgs> query_call(const rm_ctx *ctx, const rm_ray_query *q, bool pick, void *t, void *iters, void *sdf_calls, void *normal, void *object) {
+    RayCall<RmQueryArgs> c{{}, {pick ? rm_launch_pick : rm_launch_cast, pick ? rm_launch_pick_sqrt : rm_launch_cast_sqrt}, kRayChunk, pick ? 5 : 4,
+                           {{t, 8, offsetof(RmQueryArgs, t), false}, {iters, 4, offsetof(RmQueryArgs, iters), false},
+                            {sdf_calls, 4, offsetof(RmQueryArgs, sdf), false}, {normal, 12, offsetof(RmQueryArgs, normal), false},
+                            {object, 4, offsetof(RmQueryArgs, object), false}}};
+    c.args.want_normal = q->normal != 0;
+    c.args.slot_obj = ctx->dev.slot_object;
+    return c;
+}
+
+// what both forms of rm_ray_light check: the light
+int check_light(rm_ctx *ctx, const rm_light *light) {
     if (!light) return fail(ctx, RM_E_INVALID, "null light");
     for (int k = 0; k < 3; ++k)
         if (!std::isfinite(light->dir[k])) return fail(ctx, RM_E_INVALID, "non-finite light direction");
@@ -1086,174 +1118,49 @@ int check_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64
     if (!std::isfinite(light->ao_strength) || light->ao_strength < 0) return fail(ctx, RM_E_INVALID, "ao_strength must be finite and >= 0");
     if (!std::isfinite(light->ao_step) || (light->ao_samples > 0 && !(light->ao_step > 0)))
         return fail(ctx, RM_E_INVALID, "ao_step must be finite, and > 0 with occlusion samples");
-    return check_query(ctx, q, n, origins, dirs);
-}
-
-RmLightArgs light_args(const rm_light *light) {
-    RmLightArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.bias = light->bias;
-    a.ao_step = light->ao_step;
-    a.ao_strength = light->ao_strength;
-    std::memcpy(a.light, light->dir, sizeof a.light);
-    a.ao_samples = light->ao_samples;
-    return a;
-}
-
-int ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *d_origins, const void *d_dirs, void *d_t,
-                     void *d_iters, void *d_sdf_calls, void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_light(ctx, q, light, n, d_origins, d_dirs);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RmLightArgs a = light_args(light);
-    a.origins = static_cast<const float *>(d_origins);
-    a.dirs = static_cast<const float *>(d_dirs);
-    a.n = n;
-    a.t = static_cast<double *>(d_t);
-    a.iters = static_cast<uint32_t *>(d_iters);
-    a.sdf = static_cast<uint32_t *>(d_sdf_calls);
-    a.normal = static_cast<float *>(d_normal);
-    a.lit = static_cast<float *>(d_lit);
-    a.ao = static_cast<float *>(d_ao);
-    a.iters2 = static_cast<uint32_t *>(d_iters2);
-    a.sdf2 = static_cast<uint32_t *>(d_sdf_calls2);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_light_sqrt : rm_launch_light)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
     return RM_OK;
 }
 
-int ray_light_host(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
-                   uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_light(ctx, q, light, n, origins_xyz, dirs_xyz);
-    if (rc || !n) return rc;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // through the scratch buffer in chunks of at most 4 M rays, as ray_query_host (68 B per ray: 272 MB)
-    const int64_t chunk = n < (int64_t(1) << 22) ? n : (int64_t(1) << 22);
-    const size_t c = static_cast<size_t>(chunk);
-    Staging st{ctx};
-    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_t = st.region(8 * c), o_it = st.region(4 * c), o_sdf = st.region(4 * c),
-                 o_nrm = st.region(12 * c), o_lit = st.region(4 * c), o_ao = st.region(4 * c), o_it2 = st.region(4 * c), o_sdf2 = st.region(4 * c);
-    if ((rc = st.reserve())) return rc;
-    RmLightArgs a = light_args(light);
-    a.origins = st.at<const float>(o_org);
-    a.dirs = st.at<const float>(o_dirs);
-    a.t = t ? st.at<double>(o_t) : nullptr;
-    a.iters = iters ? st.at<uint32_t>(o_it) : nullptr;
-    a.sdf = sdf_calls ? st.at<uint32_t>(o_sdf) : nullptr;
-    a.normal = normal_xyz ? st.at<float>(o_nrm) : nullptr;
-    a.lit = lit ? st.at<float>(o_lit) : nullptr;
-    a.ao = ao ? st.at<float>(o_ao) : nullptr;
-    a.iters2 = iters2 ? st.at<uint32_t>(o_it2) : nullptr;
-    a.sdf2 = sdf_calls2 ? st.at<uint32_t>(o_sdf2) : nullptr;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
-        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
-        a.n = m;
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_light_sqrt : rm_launch_light)(p, a, ctx->stream, &ctx->last_kernel));
-        if (t) RM_HIP(ctx, st.out(t + at, o_t, 8 * k));
-        if (iters) RM_HIP(ctx, st.out(iters + at, o_it, 4 * k));
-        if (sdf_calls) RM_HIP(ctx, st.out(sdf_calls + at, o_sdf, 4 * k));
-        if (normal_xyz) RM_HIP(ctx, st.out(normal_xyz + 3 * at, o_nrm, 12 * k));
-        if (lit) RM_HIP(ctx, st.out(lit + at, o_lit, 4 * k));
-        if (ao) RM_HIP(ctx, st.out(ao + at, o_ao, 4 * k));
-        if (iters2) RM_HIP(ctx, st.out(iters2 + at, o_it2, 4 * k));
-        if (sdf_calls2) RM_HIP(ctx, st.out(sdf_calls2 + at, o_sdf2, 4 * k));
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+RayCall<RmLightArgs> light_call(const rm_light *light, void *t, void *iters, void *sdf_calls, void *normal, void *lit, void *ao, void *iters2,
+                                void *sdf_calls2) {
+    RayCall<RmLightArgs> c{{}, {rm_launch_light, rm_launch_light_sqrt}, kRayChunk, 8,
+                           {{t, 8, offsetof(RmLightArgs, t), false}, {iters, 4, offsetof(RmLightArgs, iters), false},
+                            {sdf_calls, 4, offsetof(RmLightArgs, sdf), false}, {normal, 12, offsetof(RmLightArgs, normal), false},
+                            {lit, 4, offsetof(RmLightArgs, lit), false}, {ao, 4, offsetof(RmLightArgs, ao), false},
+                            {iters2, 4, offsetof(RmLightArgs, iters2), false}, {sdf_calls2, 4, offsetof(RmLightArgs, sdf2), false}}};
+    c.args.bias = light->bias;
+    c.args.ao_step = light->ao_step;
+    c.args.ao_strength = light->ao_strength;
+    std::memcpy(c.args.light, light->dir, sizeof c.args.light);
+    c.args.ao_samples = light->ao_samples;
+    return c;
 }
 
-// what both forms of rm_ray_walk check: the record capacity and the outputs (ahead of the device check, like every argument
-// check), then check_query
+// what both forms of rm_ray_walk check: the record capacity and the outputs.  device: the caller's pointers are the kernel's,
+// which stores records as 8-byte words (checked ahead of the rest).
 static_assert(sizeof(rm_step) == 24 && sizeof(RmWalkStep) == 24 && sizeof(rm_walk) == 48 && sizeof(RmWalkSummary) == 48, "walk record layout");
 static_assert(offsetof(rm_step, count) == offsetof(RmWalkStep, count) && offsetof(rm_walk, end) == offsetof(RmWalkSummary, end), "walk record layout");
 static_assert(RM_END_HIT == 0 && RM_END_FAR == 1 && RM_END_STEPS == 2 && RM_END_ACCEL == 3 && RM_STEP_EVAL == 0 && RM_STEP_SKIP == 1,
               "the kernel's recorder writes these values");
-int check_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs, int32_t cap, const void *walks, const void *steps) {
+int check_walk(rm_ctx *ctx, bool device, int64_t n, int32_t cap, const void *walks, const void *steps) {
+    if (device && ((reinterpret_cast<uintptr_t>(walks) | reinterpret_cast<uintptr_t>(steps)) & 7u))
+        return fail(ctx, RM_E_INVALID, "d_walks and d_steps must be 8-byte aligned");
     if (cap < 0 || cap > RM_WALK_MAX_STEPS) return fail(ctx, RM_E_INVALID, "cap must be in [0, RM_WALK_MAX_STEPS]");
     if (steps && cap == 0) return fail(ctx, RM_E_INVALID, "step records asked for with cap 0");
     if (n > 0 && !walks && !steps) return fail(ctx, RM_E_INVALID, "neither summaries nor step records asked for");
-    return check_query(ctx, q, n, origins, dirs);
-}
-
-int ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, int32_t cap, void *d_walks,
-                    void *d_steps, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    if ((reinterpret_cast<uintptr_t>(d_walks) | reinterpret_cast<uintptr_t>(d_steps)) & 7u) return fail(ctx, RM_E_INVALID, "d_walks and d_steps must be 8-byte aligned");
-    int rc = check_walk(ctx, q, n, d_origins, d_dirs, cap, d_walks, d_steps);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RmWalkArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.origins = static_cast<const float *>(d_origins);
-    a.dirs = static_cast<const float *>(d_dirs);
-    a.walks = static_cast<RmWalkSummary *>(d_walks);
-    a.steps = static_cast<RmWalkStep *>(d_steps);
-    a.n = n;
-    a.cap = cap;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_walk_sqrt : rm_launch_walk)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
     return RM_OK;
 }
 
-int ray_walk_host(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, int32_t cap, rm_walk *walks,
-                  rm_step *steps) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_walk(ctx, q, n, origins_xyz, dirs_xyz, cap, walks, steps);
-    if (rc || !n) return rc;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(origins_xyz[i]) || !std::isfinite(dirs_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite ray");
-    RmRenderParams p;
-    rc = fill_query_params(ctx, q, p);
-    if (rc) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // Through the scratch buffer in chunks, as ray_query_host.  Summaries only: 4 M rays (72 B per ray: 288 MB).  With step
-    // records the chunk is sized by bytes: at most 64 MiB of records, at least one ray (cap 256: 10 922 rays).
-    const size_t per_ray = steps ? sizeof(rm_step) * static_cast<size_t>(cap) : 0;
-    int64_t chunk = int64_t(1) << 22;
-    if (steps) chunk = static_cast<int64_t>((size_t(64) << 20) / per_ray);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n) chunk = n;
-    const size_t c = static_cast<size_t>(chunk);
-    Staging st{ctx};
-    const size_t o_org = st.region(12 * c), o_dirs = st.region(12 * c), o_walks = st.region(walks ? sizeof(rm_walk) * c : 0),
-                 o_steps = st.region(per_ray * c);
-    if ((rc = st.reserve())) return rc;
-    RmWalkArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.origins = st.at<const float>(o_org);
-    a.dirs = st.at<const float>(o_dirs);
-    a.walks = walks ? st.at<RmWalkSummary>(o_walks) : nullptr;
-    a.steps = steps ? st.at<RmWalkStep>(o_steps) : nullptr;
-    a.cap = cap;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
-        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
-        // slots past a ray's length are left as the caller has them: the caller's records go in, the kernel overwrites the
-        // ones the walk produced, and all come back
-        if (steps) RM_HIP(ctx, st.in(o_steps, steps + at * static_cast<size_t>(cap), per_ray * k));
-        a.n = m;
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_walk_sqrt : rm_launch_walk)(p, a, ctx->stream, &ctx->last_kernel));
-        if (walks) RM_HIP(ctx, st.out(walks + at, o_walks, sizeof(rm_walk) * k));
-        if (steps) RM_HIP(ctx, st.out(steps + at * static_cast<size_t>(cap), o_steps, per_ray * k));
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+// With step records the host form's chunk is sized by bytes: at most 64 MiB of records, at least one ray (cap 256: 10 922
+// rays).  Slots past a ray's length are left as the caller has them: the caller's records go in, the kernel overwrites the
+// ones the walk produced, and all come back.
+RayCall<RmWalkArgs> walk_call(int32_t cap, void *walks, void *steps) {
+    const size_t per_ray = sizeof(rm_step) * static_cast<size_t>(cap);
+    const int64_t chunk = steps ? std::max<int64_t>(1, static_cast<int64_t>((size_t(64) << 20) / per_ray)) : kRayChunk;
+    RayCall<RmWalkArgs> c{{}, {rm_launch_walk, rm_launch_walk_sqrt}, chunk, 2,
+                          {{walks, sizeof(rm_walk), offsetof(RmWalkArgs, walks), false}, {steps, per_ray, offsetof(RmWalkArgs, steps), true}}};
+    c.args.cap = cap;
+    return c;
 }
 
 // Object `index` of the active scene as an rm_scene_from_nodes forest (operands before their user, the object's root last),
@@ -1533,6 +1440,32 @@ int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const vo
         if (reinterpret_cast<uintptr_t>(values) & 3) return fail(ctx, RM_E_INVALID, "counts must be 4-byte aligned");
     }
     if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU shading path");
+    return RM_OK;
+}
+
+// rm_scene_distance and rm_debug_wave_distance: n finite host points through the scratch buffer, synchronous.  `ready` runs
+// behind the argument checks and ahead of any device call and may refuse the call; `launch` enqueues the kernel on the
+// context's stream for the staged points and outputs.
+template <typename Ready, typename Launch>
+int points_call(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count, Ready ready, Launch launch) {
+    RM_NEED_DEVICE(ctx, "host-only context");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (n < 0 || (n > 0 && (!points_xyz || !dist || !count))) return fail(ctx, RM_E_INVALID, "bad buffers");
+    if (!n) return RM_OK;
+    for (int64_t i = 0; i < 3 * n; ++i)
+        if (!std::isfinite(points_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
+    int rc = ready();
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_pts = st.region(12 * k), o_dist = st.region(8 * k), o_cnt = st.region(4 * k);
+    if ((rc = st.reserve())) return rc;
+    RM_HIP(ctx, st.in(o_pts, points_xyz, 12 * k));
+    RM_HIP(ctx, launch(st.at<const float>(o_pts), st.at<double>(o_dist), st.at<uint32_t>(o_cnt)));
+    RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
+    RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
+    RM_HIP(ctx, st.sync());
     return RM_OK;
 }
 
@@ -2236,35 +2169,17 @@ int rm_partition_rows(int32_t height, int32_t n_workers, int32_t i, int32_t *y_s
 }
 
 int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
-    RM_NEED_DEVICE(ctx, "host-only context");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
-    if (n < 0 || (n > 0 && (!points_xyz || !dist || !count))) return fail(ctx, RM_E_INVALID, "bad buffers");
-    if (!n) return RM_OK;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(points_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t k = static_cast<size_t>(n);
-    Staging st{ctx};
-    const size_t o_pts = st.region(12 * k), o_dist = st.region(8 * k), o_cnt = st.region(4 * k);
-    int rc = st.reserve();
-    if (rc) return rc;
-    RmRenderParams p;
-    std::memset(&p, 0, sizeof p);
-    fill_scene_view(ctx, p);
-    p.time = ctx->time;
-    p.filter = static_cast<int32_t>(ctx->opt_filter);
-    p.tile_w = 8;
-    {
+    return points_call(ctx, points_xyz, n, dist, count, [] { return RM_OK; }, [&](const float *d_points, double *d_dist, uint32_t *d_count) {
+        RmRenderParams p;
+        std::memset(&p, 0, sizeof p);
+        fill_scene_view(ctx, p);
+        p.time = ctx->time;
+        p.filter = static_cast<int32_t>(ctx->opt_filter);
+        p.tile_w = 8;
         const rmrtc::Kernel *special = specialised_kernel(ctx, p.accel, false);
         p.rtc_function = special ? special->distance : nullptr;
-    }
-    RM_HIP(ctx, st.in(o_pts, points_xyz, 12 * k));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_distance_sqrt : rm_launch_distance)(p, st.at<const float>(o_pts), n, st.at<double>(o_dist),
-                                                                                  st.at<uint32_t>(o_cnt), ctx->stream));
-    RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
-    RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+        return (ctx->opt_length ? rm_launch_distance_sqrt : rm_launch_distance)(p, d_points, n, d_dist, d_count, ctx->stream);
+    });
 }
 
 int rm_lattice_points(const rm_lattice *lattice, int64_t first, int64_t n, float *points_xyz) {
@@ -2380,43 +2295,33 @@ int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const vo
 }
 
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
-    RM_NEED_DEVICE(ctx, "host-only context");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
-    if (n < 0 || (n > 0 && (!points_xyz || !dist || !count))) return fail(ctx, RM_E_INVALID, "bad buffers");
-    if (!n) return RM_OK;
-    for (int64_t i = 0; i < 3 * n; ++i)
-        if (!std::isfinite(points_xyz[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
-    rm_ray_query q;
-    std::memset(&q, 0, sizeof q);
-    q.algorithm = RM_ALG_SPHERE_TRACER;
-    q.time = ctx->time;
-    q.overshoot_factor = q.step_size = std::numeric_limits<double>::quiet_NaN();
     RmRenderParams p;
-    int rc = fill_query_params(ctx, &q, p);  // every option applies as it does to a render of the active scene
-    if (rc) return rc;
-    if (p.accel != RM_ACCEL_BVH || p.general || p.bvh_nodes <= 0) return fail(ctx, RM_E_UNSUPPORTED, "the wave loop's distance query serves BVH sphere scenes");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    const size_t k = static_cast<size_t>(n);
-    Staging st{ctx};
-    const size_t o_pts = st.region(12 * k), o_dist = st.region(8 * k), o_cnt = st.region(4 * k);
-    if ((rc = st.reserve())) return rc;
-    RM_HIP(ctx, st.in(o_pts, points_xyz, 12 * k));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_wave_distance_sqrt : rm_launch_wave_distance)(p, st.at<const float>(o_pts), n, st.at<double>(o_dist),
-                                                                                            st.at<uint32_t>(o_cnt), ctx->stream));
-    RM_HIP(ctx, st.out(dist, o_dist, 8 * k));
-    RM_HIP(ctx, st.out(count, o_cnt, 4 * k));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    const auto supported = [&] {
+        rm_ray_query q;
+        std::memset(&q, 0, sizeof q);
+        q.algorithm = RM_ALG_SPHERE_TRACER;
+        q.time = ctx->time;
+        q.overshoot_factor = q.step_size = std::numeric_limits<double>::quiet_NaN();
+        const int rc = fill_query_params(ctx, &q, p);  // every option applies as it does to a render of the active scene
+        if (rc) return rc;
+        if (p.accel != RM_ACCEL_BVH || p.general || p.bvh_nodes <= 0) return fail(ctx, RM_E_UNSUPPORTED, "the wave loop's distance query serves BVH sphere scenes");
+        return static_cast<int>(RM_OK);
+    };
+    return points_call(ctx, points_xyz, n, dist, count, supported, [&](const float *d_points, double *d_dist, uint32_t *d_count) {
+        return (ctx->opt_length ? rm_launch_wave_distance_sqrt : rm_launch_wave_distance)(p, d_points, n, d_dist, d_count, ctx->stream);
+    });
 }
 
 int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                         void *d_sdf_calls, void *d_normal, void *stream) {
-    return ray_query_device(ctx, false, q, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, nullptr, stream);
+    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
+                    [&] { return query_call(ctx, q, false, d_t, d_iters, d_sdf_calls, d_normal, nullptr); });
 }
 
 int rm_ray_march(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                  uint32_t *sdf_calls, float *normal_xyz) {
-    return ray_query_host(ctx, false, q, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, nullptr);
+    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
+                    [&] { return query_call(ctx, q, false, t, iters, sdf_calls, normal_xyz, nullptr); });
 }
 
 int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end, float *origin3, float *dirs_xyz) {
@@ -2447,33 +2352,39 @@ int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int3
 
 int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                        void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
-    return ray_query_device(ctx, true, q, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, d_object, stream);
+    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
+                    [&] { return query_call(ctx, q, true, d_t, d_iters, d_sdf_calls, d_normal, d_object); });
 }
 
 int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                 uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
-    return ray_query_host(ctx, true, q, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, object);
+    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
+                    [&] { return query_call(ctx, q, true, t, iters, sdf_calls, normal_xyz, object); });
 }
 
 int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *d_origins, const void *d_dirs, void *d_t,
                         void *d_iters, void *d_sdf_calls, void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2,
                         void *stream) {
-    return ray_light_device(ctx, q, light, n, d_origins, d_dirs, d_t, d_iters, d_sdf_calls, d_normal, d_lit, d_ao, d_iters2, d_sdf_calls2, stream);
+    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_light(ctx, light); },
+                    [&] { return light_call(light, d_t, d_iters, d_sdf_calls, d_normal, d_lit, d_ao, d_iters2, d_sdf_calls2); });
 }
 
 int rm_ray_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
                  uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
-    return ray_light_host(ctx, q, light, n, origins_xyz, dirs_xyz, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2);
+    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_light(ctx, light); },
+                    [&] { return light_call(light, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2); });
 }
 
 int rm_ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, int32_t cap, void *d_walks,
                        void *d_steps, void *stream) {
-    return ray_walk_device(ctx, q, n, d_origins, d_dirs, cap, d_walks, d_steps, stream);
+    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_walk(ctx, true, n, cap, d_walks, d_steps); },
+                    [&] { return walk_call(cap, d_walks, d_steps); });
 }
 
 int rm_ray_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, int32_t cap, rm_walk *walks,
                 rm_step *steps) {
-    return ray_walk_host(ctx, q, n, origins_xyz, dirs_xyz, cap, walks, steps);
+    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_walk(ctx, false, n, cap, walks, steps); },
+                    [&] { return walk_call(cap, walks, steps); });
 }
 
 int rm_phong_light(float dir3[3]) {

@@ -90,21 +90,38 @@ struct RmShadeLitArgs {
     long long npx;
     double light[3];  // PhongModel's binary32 light direction, widened (exact)
 };
-// rm_ray_light (rm_kernels.hip, light_kernel): the rays, the outputs (each may be null) and the rm_light of one launch
-struct RmLightArgs {
+// The ray queries (rm_kernels.hip).  RmRays: the rays of one launch, handed to the launchers beside the family's block.  The
+// kernels take their arguments where they took them before the launchers were unified: cast and pick loose, light and walk
+// their block with the rays in it.  (A block that opens with RmRays, for all four kernels, cost the BVH sphere kernels SGPR
+// spills and about 1 % on the C3 rays: profiles/NOTES.md.)  Every output may be null.
+struct RmRays {
     const float *origins, *dirs;  // f32[3n]
+    long long n;
+};
+// rm_ray_march (cast_kernel) and rm_ray_pick (pick_kernel, which alone reads slot_obj and writes object)
+struct RmQueryArgs {
+    int32_t want_normal, pad;
+    const int32_t *slot_obj;  // device sphere slot -> object index (sphere scenes stored in BVH leaf order), null when the two agree
+    double *t;
+    uint32_t *iters, *sdf;
+    float *normal;            // written whether or not want_normal is set (zeros without)
+    int32_t *object;          // i32[n], -1 = none
+};
+// rm_ray_light (light_kernel): the outputs and the rm_light of one launch
+struct RmLightArgs {
+    const float *origins, *dirs;  // set by the launcher: its RmRays
     double *t;                    // the primary ray's outputs: what cast_kernel writes with want_normal
     uint32_t *iters, *sdf;
     float *normal;
     float *lit, *ao;              // f32[n]
     uint32_t *iters2, *sdf2;      // the shadow ray's iterations; its SDF calls plus those of the occlusion samples
-    long long n;
+    long long n;                  // set by the launcher
     double bias, ao_step, ao_strength;
     float light[3];               // towards the light, as given
     int ao_samples;
 };
-// rm_ray_walk (rm_kernels.hip, walk_kernel): rm_step and rm_walk as the kernel stores them, and the rays and outputs of one
-// launch.  steps: cap slots per ray, null for summaries only (the same for every lane); walks may be null when steps is not.
+// rm_ray_walk (walk_kernel): rm_step and rm_walk as the kernel stores them, and the outputs of one launch.  steps: cap slots
+// per ray, null for summaries only (the same for every lane); walks may be null when steps is not.
 struct RmWalkStep {  // rm_step (24 bytes)
     double t, value;
     uint32_t count;
@@ -116,10 +133,10 @@ struct RmWalkSummary {  // rm_walk (48 bytes)
     int32_t end;
 };
 struct RmWalkArgs {
-    const float *origins, *dirs;  // f32[3n]
+    const float *origins, *dirs;  // set by the launcher: its RmRays
     RmWalkSummary *walks;
     RmWalkStep *steps;
-    long long n;
+    long long n;                  // set by the launcher
     int cap, pad;
 };
 // rm_scene_field (rm_kernels.hip, field_kernel): the lattice (rm_lattice, its binary32 vectors widened: exact), the linear range
@@ -183,28 +200,23 @@ hipError_t rm_launch_distance(const RmRenderParams &p, const float *points, int6
 hipError_t rm_launch_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist,
                                    uint32_t *count, hipStream_t stream);
 
-// Ray queries (rm_ray_march, rm_ray_pick): Raymarcher.rayMarch (+ getNormal when want_normal) for n caller-supplied rays
-// (origins, dirs: f32[3n]).  pick launches pick_kernel, which also writes the object each ray hit (object: i32[n], -1 =
-// none), else cast_kernel, which reads neither slot_obj nor object.  slot_obj: device sphere slot -> object index (sphere
-// scenes stored in BVH leaf order), null when the two agree.  Every output may be null.  *kernel_name (optional) receives
-// the instantiation that was launched (static string).
-hipError_t rm_launch_query(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                           const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                           hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_query_sqrt(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                                const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                                hipStream_t stream, const char **kernel_name);
-
-// Light query (rm_ray_light): rm_launch_query's march with want_normal, then at hits one shadow ray towards a.light through
-// the same marcher and a.ao_samples Scene.getDistance samples along the normal (include/rm_raymarch.h has the rule).  One
-// launch of light_kernel, the LDS of rm_launch_query.
-hipError_t rm_launch_light(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
-
-// Walk query (rm_ray_walk): rm_launch_query's march without a normal, with a recorder that keeps the walk's summary and
-// stores its first a.cap step records (include/rm_raymarch.h has the rule).  One launch of walk_kernel, the LDS of rm_launch_query.
-hipError_t rm_launch_walk(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
+// Ray queries: r.n caller-supplied rays through the march of a one-ray-per-lane render launch, one launch of 256-thread
+// workgroups with that launch's LDS.  The four launchers share one prologue (rm_kernels.hip, ray_launch) and differ in the kernel
+// they name and in how they hand it its arguments.  *kernel_name (optional) receives the instantiation that was launched (static string).
+// rm_ray_march (cast_kernel) and rm_ray_pick (pick_kernel): Raymarcher.rayMarch (+ getNormal when a.want_normal); pick_kernel
+// also writes the object each ray hit, cast_kernel reads neither a.slot_obj nor a.object.
+hipError_t rm_launch_cast(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_cast_sqrt(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_pick(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_pick_sqrt(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name);
+// rm_ray_light (light_kernel): the march with its normal, then at hits one shadow ray towards a.light through the same marcher
+// and a.ao_samples Scene.getDistance samples along the normal (include/rm_raymarch.h has the rule).
+hipError_t rm_launch_light(const RmRenderParams &p, const RmRays &r, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmRays &r, const RmLightArgs &a, hipStream_t stream, const char **kernel_name);
+// rm_ray_walk (walk_kernel): the march without a normal, with a recorder that keeps the walk's summary and stores its first
+// a.cap step records (include/rm_raymarch.h has the rule).
+hipError_t rm_launch_walk(const RmRenderParams &p, const RmRays &r, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmRays &r, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 
 // Field query (rm_scene_field): Scene.getDistance at the lattice points of a.first .. a.first + a.n, formed on the device
 // (include/rm_raymarch.h has the rule).  field_kernel, the LDS of rm_launch_distance, ahead-of-time kernels only.

@@ -1397,18 +1397,23 @@ __device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ra
 // given (rayMarch does not normalise it).  Counts are exact u32: the reference's Uint16Array holds them mod 65536.
 // PICK adds the object each ray hit; t, iters, sdf_calls and the normal do not depend on it (the object pass adds nothing to
 // the count).  (Ahead-of-time only: the run-time specialiser's build of this file does not carry the ray queries.)
-template <int ACCEL, bool OTHER, int GEN, bool PICK>
-__device__ __forceinline__ void query_body(const RmRenderParams &P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
-                                           const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out,
-                                           int32_t *obj_out) {
-    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
-    if (i >= n) return;
+__device__ __forceinline__ Ray load_ray(const float *origins, const float *dirs, int64_t i) {
     Ray ray;
     ray.o = Vec3f{origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]};
     ray.d = Vec3f{dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]};
     ray.od[0] = static_cast<double>(ray.o.x);  // per lane here (the camera's kernels take it from the parameter block)
     ray.od[1] = static_cast<double>(ray.o.y);
     ray.od[2] = static_cast<double>(ray.o.z);
+    return ray;
+}
+
+template <int ACCEL, bool OTHER, int GEN, bool PICK>
+__device__ __forceinline__ void query_body(const RmRenderParams &P, const float *origins, const float *dirs, int64_t n, int32_t want_normal,
+                                           const int32_t *slot_obj, double *t_out, uint32_t *iters_out, uint32_t *sdf_out, float *normal_out,
+                                           int32_t *obj_out) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Ray ray = load_ray(origins, dirs, i);
     uint32_t count = 0, iters = 0;
     const double t = OTHER ? ray_march_other<ACCEL, GEN>(P, ray, count, iters) : ray_march<ACCEL, GEN>(P, ray, count, iters);
     Vec3f nrm{0.f, 0.f, 0.f};
@@ -1453,12 +1458,7 @@ template <int ACCEL, bool OTHER, int GEN>
 __device__ __forceinline__ void light_body(const RmRenderParams &P, const RmLightArgs &A) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    Ray ray;
-    ray.o = Vec3f{A.origins[3 * i], A.origins[3 * i + 1], A.origins[3 * i + 2]};
-    ray.d = Vec3f{A.dirs[3 * i], A.dirs[3 * i + 1], A.dirs[3 * i + 2]};
-    ray.od[0] = static_cast<double>(ray.o.x);
-    ray.od[1] = static_cast<double>(ray.o.y);
-    ray.od[2] = static_cast<double>(ray.o.z);
+    Ray ray = load_ray(A.origins, A.dirs, i);
     Vec3f p{0.f, 0.f, 0.f}, nrm{0.f, 0.f, 0.f};
     float lit = 1.f, ao = 1.f;
     uint32_t iters2 = 0, count2 = 0;
@@ -1567,12 +1567,7 @@ template <int ACCEL, bool OTHER, int GEN>
 __device__ __forceinline__ void walk_body(const RmRenderParams &P, const RmWalkArgs &A) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
-    Ray ray;
-    ray.o = Vec3f{A.origins[3 * i], A.origins[3 * i + 1], A.origins[3 * i + 2]};
-    ray.d = Vec3f{A.dirs[3 * i], A.dirs[3 * i + 1], A.dirs[3 * i + 2]};
-    ray.od[0] = static_cast<double>(ray.o.x);
-    ray.od[1] = static_cast<double>(ray.o.y);
-    ray.od[2] = static_cast<double>(ray.o.z);
+    Ray ray = load_ray(A.origins, A.dirs, i);
     WalkRecorder rec;
     rec.out = A.steps ? A.steps + i * A.cap : nullptr;
     rec.cap = static_cast<uint32_t>(A.cap);
@@ -1886,80 +1881,79 @@ hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFiel
     return hipSuccess;
 }
 
-hipError_t RM_LEN_VARIANT(rm_launch_query)(const RmRenderParams &p, bool pick, const float *origins, const float *dirs, int64_t n, bool want_normal,
-                                           const int32_t *slot_obj, double *t, uint32_t *iters, uint32_t *sdf, float *normal, int32_t *object,
-                                           hipStream_t stream, const char **kernel_name) {
-    if (kernel_name) *kernel_name = "";
-    if (n <= 0) return hipSuccess;
+namespace {
+// What the launch of a ray query is, whichever kernel it names: nothing without a ray (grid.x 0), else one lane per ray in
+// 256-thread workgroups, the LDS of the one-ray-per-lane render launch -- so every march of a lane is a render's -- and the
+// parameter block without a run-time specialised kernel (the ray queries are ahead-of-time only) or diagnostics.
+struct RayLaunch {
+    dim3 grid, block;
+    size_t shmem;
+    RmRenderParams pl;
+};
+RayLaunch ray_launch(const RmRenderParams &p, long long n) {
     const int threads = 256;
-    const dim3 grid(static_cast<unsigned>((n + threads - 1) / threads)), block(threads);
-    const V1Lds lds = v1_lds_layout(p, threads, true);  // the LDS of the one-ray-per-lane render launch, so the march is the same
-    const size_t shmem = lds.bytes;
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
-    pl.v1_list_offset = lds.v1_list_offset;
-    const int32_t wn = want_normal ? 1 : 0;
-#define RM_QK(A, O, G)                                                                                                                \
-    {                                                                                                                                 \
-        if (pick) {                                                                                                                   \
-            hipLaunchKernelGGL((pick_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, slot_obj, t, iters, sdf, \
-                               normal, object);                                                                                       \
-            if (kernel_name) *kernel_name = RM_KERNEL_NAME(pick_kernel, A, O, G);                                                     \
-        } else {                                                                                                                      \
-            hipLaunchKernelGGL((cast_kernel<A, O, G>), grid, block, shmem, stream, pl, origins, dirs, n, wn, t, iters, sdf, normal);  \
-            if (kernel_name) *kernel_name = RM_KERNEL_NAME(cast_kernel, A, O, G);                                                     \
-        }                                                                                                                             \
+    const V1Lds lds = v1_lds_layout(p, threads, true);
+    RayLaunch l{dim3(n > 0 ? static_cast<unsigned>((n + threads - 1) / threads) : 0u), dim3(threads), lds.bytes, p};
+    l.pl.rtc_function = nullptr;
+    l.pl.diag_block = nullptr;
+    l.pl.diag_out = nullptr;
+    l.pl.v1_list_offset = lds.v1_list_offset;
+    return l;
+}
+}  // namespace
+// What is left per family: the line that names its kernel and hands it its arguments where the kernel reads them (RmRays `r`,
+// the block `a`, RayLaunch `l`, `stream` and `kernel_name` in scope).
+#define RM_RAY_K(kernel, A, O, G, ...)                                                              \
+    {                                                                                               \
+        hipLaunchKernelGGL((kernel<A, O, G>), l.grid, l.block, l.shmem, stream, l.pl, __VA_ARGS__); \
+        if (kernel_name) *kernel_name = RM_KERNEL_NAME(kernel, A, O, G);                            \
     }
-    RM_DISPATCH(RM_QK)
-#undef RM_QK
+#define RM_CK(A, O, G) RM_RAY_K(cast_kernel, A, O, G, r.origins, r.dirs, static_cast<int64_t>(r.n), a.want_normal, a.t, a.iters, a.sdf, a.normal)
+#define RM_PK(A, O, G) RM_RAY_K(pick_kernel, A, O, G, r.origins, r.dirs, static_cast<int64_t>(r.n), a.want_normal, a.slot_obj, a.t, a.iters, a.sdf, a.normal, a.object)
+#define RM_LK(A, O, G) RM_RAY_K(light_kernel, A, O, G, al)
+#define RM_WK(A, O, G) RM_RAY_K(walk_kernel, A, O, G, al)
+
+hipError_t RM_LEN_VARIANT(rm_launch_cast)(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name) {
+    const RayLaunch l = ray_launch(p, r.n);
+    if (kernel_name) *kernel_name = "";
+    if (!l.grid.x) return hipSuccess;
+    RM_DISPATCH(RM_CK)
     return hipGetLastError();
 }
-
-hipError_t RM_LEN_VARIANT(rm_launch_light)(const RmRenderParams &p, const RmLightArgs &a, hipStream_t stream, const char **kernel_name) {
+hipError_t RM_LEN_VARIANT(rm_launch_pick)(const RmRenderParams &p, const RmRays &r, const RmQueryArgs &a, hipStream_t stream, const char **kernel_name) {
+    const RayLaunch l = ray_launch(p, r.n);
     if (kernel_name) *kernel_name = "";
-    if (a.n <= 0) return hipSuccess;
-    const int threads = 256;
-    const dim3 grid(static_cast<unsigned>((a.n + threads - 1) / threads)), block(threads);
-    const V1Lds lds = v1_lds_layout(p, threads, true);  // as rm_launch_query: both marches of a lane are a render's
-    const size_t shmem = lds.bytes;
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
-    pl.v1_list_offset = lds.v1_list_offset;
-#define RM_LK(A, O, G)                                                                 \
-    {                                                                                  \
-        hipLaunchKernelGGL((light_kernel<A, O, G>), grid, block, shmem, stream, pl, a); \
-        if (kernel_name) *kernel_name = RM_KERNEL_NAME(light_kernel, A, O, G);         \
-    }
+    if (!l.grid.x) return hipSuccess;
+    RM_DISPATCH(RM_PK)
+    return hipGetLastError();
+}
+hipError_t RM_LEN_VARIANT(rm_launch_light)(const RmRenderParams &p, const RmRays &r, const RmLightArgs &a, hipStream_t stream, const char **kernel_name) {
+    const RayLaunch l = ray_launch(p, r.n);
+    if (kernel_name) *kernel_name = "";
+    if (!l.grid.x) return hipSuccess;
+    RmLightArgs al = a;
+    al.origins = r.origins;
+    al.dirs = r.dirs;
+    al.n = r.n;
     RM_DISPATCH(RM_LK)
-#undef RM_LK
     return hipGetLastError();
 }
-
-hipError_t RM_LEN_VARIANT(rm_launch_walk)(const RmRenderParams &p, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name) {
+hipError_t RM_LEN_VARIANT(rm_launch_walk)(const RmRenderParams &p, const RmRays &r, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name) {
+    const RayLaunch l = ray_launch(p, r.n);
     if (kernel_name) *kernel_name = "";
-    if (a.n <= 0) return hipSuccess;
-    const int threads = 256;
-    const dim3 grid(static_cast<unsigned>((a.n + threads - 1) / threads)), block(threads);
-    const V1Lds lds = v1_lds_layout(p, threads, true);  // as rm_launch_query: the march is a render's
-    const size_t shmem = lds.bytes;
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
-    pl.v1_list_offset = lds.v1_list_offset;
-#define RM_WK(A, O, G)                                                                \
-    {                                                                                 \
-        hipLaunchKernelGGL((walk_kernel<A, O, G>), grid, block, shmem, stream, pl, a); \
-        if (kernel_name) *kernel_name = RM_KERNEL_NAME(walk_kernel, A, O, G);         \
-    }
+    if (!l.grid.x) return hipSuccess;
+    RmWalkArgs al = a;
+    al.origins = r.origins;
+    al.dirs = r.dirs;
+    al.n = r.n;
     RM_DISPATCH(RM_WK)
-#undef RM_WK
     return hipGetLastError();
 }
+#undef RM_WK
+#undef RM_LK
+#undef RM_PK
+#undef RM_CK
+#undef RM_RAY_K
 
 #ifndef RM_LENGTH_SQRT
 __global__ __launch_bounds__(256) void jsmath_kernel(int fn, const double *a, const double *b, int64_t n, double *out) {
