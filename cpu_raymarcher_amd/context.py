@@ -152,6 +152,20 @@ class Context:
         N.check(self._h, N.lib().rm_get_option(self._h, key.encode(), C.byref(v)))
         return v.value
 
+    def launch_fill(self, asked):
+        """Workgroups per CU a v2 launch brings when `blocks_per_cu` is `asked`: option `min_fill` and the hardware-queue
+        count the context read from GPU_MAX_HW_QUEUES when it was made (rm_debug_launch_fill; no device needed)."""
+        v = C.c_int32(0)
+        N.check(self._h, N.lib().rm_debug_launch_fill(self._h, int(asked), C.byref(v)))
+        return v.value
+
+    def last_launch(self):
+        """The last launch of the v2 wave loop: dict(workgroups, threads, lds_bytes) and the context's CU count `cus`
+        (rm_debug_last_launch; zeros before the first such launch)."""
+        out = (C.c_uint32 * 4)()
+        N.check(self._h, N.lib().rm_debug_last_launch(self._h, out))
+        return dict(workgroups=out[0], threads=out[1], lds_bytes=out[2], cus=out[3])
+
     # ---- scene ----------------------------------------------------------------------
     def scene_from_preset(self, index, accel):
         N.check(self._h, N.lib().rm_scene_from_preset(self._h, int(index), int(accel)))

@@ -8,8 +8,11 @@
 
 #include <algorithm>
 #include <array>
+#include <cerrno>
+#include <climits>
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <functional>
 #include <limits>
@@ -418,6 +421,13 @@ struct rm_ctx {
     int64_t opt_ext = 1;  // the exterior candidate grid serves the all-primitive evaluations outside the BVH root box (rm_scene_host.cpp build_exterior_grid)
     int64_t opt_blocks_per_cu = 6;  // persistent workgroups per launch and CU: what the kernel's 80 VGPRs and 26 KB of LDS allow (a frame alone, round 3: 4: 1.42 ms, 6: 1.32, 7: 1.30)
     int64_t opt_lds_fill = 0;
+    // v2: a persistent launch brings at least ceil(RM_V2_WAVES / hw_queues) workgroups per CU (launch_fill below).  Launches on
+    // streams that share a hardware queue run one after the other, so a launch never overlaps with more launches than the
+    // process has queues: with HIP's default of four, launches of one workgroup per CU fill four of a SIMD's six wave slots
+    // whatever the caller keeps in flight.  0: bring exactly blocks_per_cu (measurement sweeps).
+    int64_t opt_min_fill = 1;
+    int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
+    uint32_t last_v2_shape[3] = {0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
     int64_t opt_multi_step = 1;  // v2 BVH: in-round march steps (rm_render_v2.hip, section M)
     int64_t opt_lds_kb = 0;         // v2: LDS budget per workgroup the launcher trims the hit lists to (0: as many workgroups per CU as the kernel's registers allow; 32: five per CU, 40: four)
@@ -493,6 +503,27 @@ int fail(rm_ctx *ctx, int code, const std::string &msg) {
 
 int hip_fail(rm_ctx *ctx, hipError_t e, const char *what) {
     return fail(ctx, RM_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The hardware queues the HIP runtime of this process opens: GPU_MAX_HW_QUEUES when it is a decimal integer >= 1, else 4 (HIP's
+// default: unset, empty, not a number, <= 0).  Read, never set: the count is the host's to choose.
+int read_hw_queues() {
+    const char *s = std::getenv("GPU_MAX_HW_QUEUES");
+    if (!s || !*s) return 4;
+    char *end = nullptr;
+    errno = 0;
+    const long long v = std::strtoll(s, &end, 10);
+    if (errno || end == s || *end != '\0' || v <= 0) return 4;
+    return static_cast<int>(std::min<long long>(v, INT_MAX));
+}
+
+// Workgroups per CU a persistent v2 launch brings when the caller asked for `asked` (option `blocks_per_cu`).  At most
+// `queues` launches run at once, and a CU holds RM_V2_WAVES of the wave loop's workgroups: a launch that brings fewer than
+// ceil(RM_V2_WAVES / queues) leaves wave slots empty whatever the caller overlaps.  Q = 4: 2; Q >= 6: 1 (as asked); Q = 1, 2, 3: 6, 3, 2.
+int launch_fill(int asked, int queues, bool min_fill) {
+    if (!min_fill) return asked;
+    const int q = queues > 0 ? queues : 4;
+    return std::max(asked, (RM_V2_WAVES + q - 1) / q);
 }
 
 // A kernel compiled at run time (rm_rtc.h), as `specialise` says: 1 waits for the compile; 2 never waits -- the ahead-of-time
@@ -578,7 +609,8 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
         const hipError_t ei = rm_launch_reduce_init(p.diag_out, stream);
         if (ei != hipSuccess) return ei;
     }
-    hipError_t e = ctx->opt_length ? rm_launch_render_sqrt(p, stream, &ctx->last_kernel) : rm_launch_render(p, stream, &ctx->last_kernel);
+    hipError_t e = ctx->opt_length ? rm_launch_render_sqrt(p, stream, &ctx->last_kernel, ctx->last_v2_shape)
+                                   : rm_launch_render(p, stream, &ctx->last_kernel, ctx->last_v2_shape);
     if (special && !empty) ctx->last_kernel = special->name.c_str();
     if (e == hipSuccess && reduce_after) {
         e = rm_launch_reduce_init(reduce_after, stream);
@@ -910,6 +942,7 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.bvh_prim_count = static_cast<int32_t>(ctx->host.bvh_prims.size());
     p.oct_prim_count = static_cast<int32_t>(ctx->host.oct_prims.size());
     p.blocks_per_cu = static_cast<int32_t>(ctx->opt_blocks_per_cu);
+    p.launch_per_cu = launch_fill(p.blocks_per_cu, ctx->hw_queues, ctx->opt_min_fill != 0);
     p.num_cus = ctx->num_cus;
     p.refill_threshold = static_cast<int32_t>(ctx->opt_refill);
     p.hw_xcd = static_cast<int32_t>(ctx->opt_hw_xcd);
@@ -1481,6 +1514,7 @@ int rm_create(int device, rm_ctx **out) {
     rm_ctx *ctx = new (std::nothrow) rm_ctx();
     if (!ctx) return RM_E_NOMEM;
     rmh::phong_light_dir(ctx->light);
+    ctx->hw_queues = read_hw_queues();  // once: what the variable says later is not what the runtime started with
     if (device >= 0) {
         int count = 0;
         hipError_t e = hipGetDeviceCount(&count);
@@ -2541,6 +2575,22 @@ int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n) {
     return RM_OK;
 }
 
+// what a v2 launch that asks for `asked` workgroups per CU would bring (launch_fill: option `min_fill`, the queue count rm_create read)
+int rm_debug_launch_fill(rm_ctx *ctx, int32_t asked, int32_t *effective) {
+    if (!ctx || !effective) return RM_E_INVALID;
+    if (asked < 1 || asked > 8) return fail(ctx, RM_E_INVALID, "blocks_per_cu must be in [1, 8]");
+    *effective = launch_fill(asked, ctx->hw_queues, ctx->opt_min_fill != 0);
+    return RM_OK;
+}
+
+// the last launch of the v2 wave loop: workgroups, threads per workgroup, dynamic LDS bytes (zeros before the first); the context's CU count
+int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]) {
+    if (!ctx || !out) return RM_E_INVALID;
+    for (int k = 0; k < 3; ++k) out[k] = ctx->last_v2_shape[k];
+    out[3] = static_cast<uint32_t>(ctx->num_cus);
+    return RM_OK;
+}
+
 // Every option once: its key, its member of rm_ctx (the defaults and what they were measured against are there; fill_params
 // reads the members), the values it takes and what rm_last_error says of any other.
 enum OptionKind {
@@ -2574,6 +2624,7 @@ static const OptionRow kOptions[] = {
     {"specialise_v2_after", &rm_ctx::opt_v2_after, kRange, {0, 1000000}, "specialise_v2_after must be 0 (never) .. 1000000 launches"},
     {"specialise", &rm_ctx::opt_specialise, kRange, {0, 2}, "specialise must be 0, 1 or 2"},
     {"lds_fill", &rm_ctx::opt_lds_fill, kSwitch, {}, nullptr},
+    {"min_fill", &rm_ctx::opt_min_fill, kSwitch, {}, nullptr},
     {"cull", &rm_ctx::opt_cull, kSwitch, {}, nullptr},
     {"rel", &rm_ctx::opt_rel, kSwitch, {}, nullptr},
     {"static", &rm_ctx::opt_static, kRange, {0, 95}, "static must be in [0, 95] percent"},  // stored, ignored (rm_ctx)

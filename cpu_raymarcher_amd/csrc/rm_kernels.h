@@ -162,9 +162,10 @@ struct RmShadeFieldArgs {
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
-// instantiation that was launched (static string).
-hipError_t rm_launch_render(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_render_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
+// instantiation that was launched (static string); v2_shape (optional) what a launch of the v2 wave loop was launched with:
+// workgroups, threads per workgroup, dynamic LDS bytes (left alone by every other launch).
+hipError_t rm_launch_render(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape = nullptr);
+hipError_t rm_launch_render_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape = nullptr);
 
 // Asked by rm_launch_render_v2 for every launch that carries a context (RmRenderParams::rtc_ctx): the hipFunction_t of the
 // wave loop compiled for this launch's configuration (rm_v2_fields.h), or null -- the library's own instantiation runs.
@@ -172,8 +173,8 @@ hipError_t rm_launch_render_sqrt(const RmRenderParams &p, hipStream_t stream, co
 const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur, bool rel, bool length_sqrt);
 
 // v2 kernel (rm_render_v2.hip); called by rm_launch_render when p.variant == 2
-hipError_t rm_launch_render_v2(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
-hipError_t rm_launch_render_v2_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_render_v2(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *shape = nullptr);
+hipError_t rm_launch_render_v2_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *shape = nullptr);
 
 // rm_debug_wave_distance: Scene.getDistance through the wave loop's bvh_distance_wave, one point per lane (BVH sphere scenes)
 hipError_t rm_launch_wave_distance(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);

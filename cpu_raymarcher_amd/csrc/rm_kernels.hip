@@ -1714,11 +1714,11 @@ V1Lds v1_lds_layout(const RmRenderParams &p, int threads, bool lists) {
 #define RM_DISPATCH(K) { if (p.general == 3) RM_DISPATCH_O(K, 3) else if (p.general == 2) RM_DISPATCH_O(K, 2) else if (p.general) RM_DISPATCH_O(K, 1) else RM_DISPATCH_O(K, 0) }
 #define RM_KERNEL_NAME(kernel, A, O, G) #kernel "<" #A ", " #O ", " #G ">" RM_LEN_TAG
 
-hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t stream, const char **kernel_name) {
+hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape) {
     const int rows = p.local_rows;
     if (kernel_name) *kernel_name = "";
     if (rows <= 0 || p.width <= 0) return hipSuccess;
-    if (p.variant == 2 && p.algorithm == 0) return RM_LEN_VARIANT(rm_launch_render_v2)(p, stream, kernel_name);
+    if (p.variant == 2 && p.algorithm == 0) return RM_LEN_VARIANT(rm_launch_render_v2)(p, stream, kernel_name, v2_shape);
     const int tw = p.tile_w, th = 64 / tw;
     const int wpw = p.v1_block >= 256 ? 4 : (p.v1_block >= 128 ? 2 : 1);  // waves per workgroup (option `v1_block`)
     const int threads = 64 * wpw;

@@ -957,8 +957,7 @@ template <int ACCEL, bool LDS, bool UR = false, bool REL = false>
 // Round 3: 80 VGPRs without a spill and without scratch in every instantiation, vec3.length = sqrt build included: six
 // waves per SIMD (tests/test_build_invariants.py holds all of them to that).  Round 2 needed 96 (five waves; the REL and sqrt
 // builds spilled at five and ran at four); what changed is the lane state (see "lane state" below), the wave index as an
-// SGPR, and -amdgpu-inline-max-bb (Makefile).
-#define RM_V2_WAVES 6
+// SGPR, and -amdgpu-inline-max-bb (Makefile).  (RM_V2_WAVES = 6: rm_types.h)
 __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
     // (RM_RTC_V2 builds: the literals are applied where the wave loop re-loads the block, cold_params; what runs once per
     // workgroup here reads the kernel argument as it is -- a patched local copy of the block indexed at run time, as the REL
@@ -1636,7 +1635,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_wave_distance)(const RmRenderParams &p, cons
     return hipGetLastError();
 }
 
-hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipStream_t stream, const char **kernel_name) {
+hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipStream_t stream, const char **kernel_name, uint32_t *shape) {
     RmRenderParams p = p_in;
     const int rows = p.local_rows;
     if (kernel_name) *kernel_name = "";
@@ -1721,8 +1720,16 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         for (int k = 0; k < 10; ++k) p.lds_off[k] = v[k];
         if (lay.end + list_bytes > shmem) return hipErrorInvalidValue;  // the layout and the allocation come from two formulas: they must agree
     }
-    resident = static_cast<unsigned>(p.num_cus > 0 ? p.num_cus : 256) * static_cast<unsigned>(p.blocks_per_cu > 0 ? p.blocks_per_cu : 4);
+    // the workgroups per CU the launch brings: what the caller asked, or what rm_api.cpp raised that to (launch_per_cu, option
+    // `min_fill`); `lds_fill` above went by what the caller asked
+    const int per_cu = p.launch_per_cu > 0 ? p.launch_per_cu : p.blocks_per_cu;
+    resident = static_cast<unsigned>(p.num_cus > 0 ? p.num_cus : 256) * static_cast<unsigned>(per_cu > 0 ? per_cu : 4);
     blocks = needed < resident ? (needed ? needed : 1u) : resident;
+    if (shape) {
+        shape[0] = blocks;
+        shape[1] = 256;
+        shape[2] = static_cast<uint32_t>(shmem);
+    }
     // the tile-queue heads are zero: a launch's last wave leaves them so (rm_diag.h).  Without an accumulator block
     // (a caller below the API layer) they are cleared here.
     hipError_t e = hipSuccess;

@@ -127,6 +127,10 @@ struct RmFrameView {
     double time;
 };
 
+// Waves per SIMD the v2 wave loop is compiled for (the __launch_bounds__ of render_kernel_v2, rm_render_v2.hip): as many
+// four-wave workgroups share a CU.  The launcher's LDS budgets and the launch-fill rule of rm_api.cpp go by it.
+#define RM_V2_WAVES 6
+
 // Kernel parameters (passed by value).
 struct RmRenderParams {
     int32_t width, height, y_start, y_end;
@@ -170,7 +174,12 @@ struct RmRenderParams {
     uint8_t *lpt_cost_out;
     const uint8_t *lpt_cost_prev;
     uint16_t *lpt_perm_out;  // what the sort kernel of this launch writes (== lpt_perm)
-    int32_t lpt_stride, lpt_pad;
+    int32_t lpt_stride;
+    // v2, launcher only: the persistent workgroups per CU this launch BRINGS (0: blocks_per_cu).  rm_api.cpp raises it above
+    // what the caller asked (blocks_per_cu, which `lds_fill` keeps deciding by) when the process has too few hardware queues
+    // for that many launches to overlap (option `min_fill`; launch_fill in rm_api.cpp).  Not in rm_v2_fields.h: the tail ramp of a burst
+    // changes both from launch to launch.  (It takes the slot that padded lpt_stride: the block's layout is what it was.)
+    int32_t launch_per_cu;
     int32_t v1_lists;          // v1 BVH: per-ray hit-leaf lists in LDS (option `v1_lists`), placed at v1_list_offset by the launcher
     int32_t v1_list_offset;
     uint32_t lds_off[10];      // v2: byte offsets of the staged tables in LDS (nodes, prims, cells, list, oct, oct_prims, spheres,

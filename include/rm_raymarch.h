@@ -821,6 +821,12 @@ RM_API int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32);
 /* The item durations (units of 2.56 us, one byte per work item: 64 queues x 4096 slots) the last v2 launch recorded for the
  * longest-first order of the next one (option lpt); scripts/lpt_costs.py. */
 RM_API int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n);
+/* Option min_fill (below), for tests and evidence.  rm_debug_launch_fill: *effective = the workgroups per CU a v2 launch
+ * brings when blocks_per_cu is `asked` (1..8), with the context's min_fill and queue count; works on a host-only context.
+ * rm_debug_last_launch: the last launch of the v2 wave loop -- out[0] workgroups, out[1] threads per workgroup, out[2]
+ * dynamic LDS bytes (zeros before the first such launch) -- and out[3] the context's CU count. */
+RM_API int rm_debug_launch_fill(rm_ctx *ctx, int32_t asked, int32_t *effective);
+RM_API int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]);
 /* Diagnostic builds only (make EXTRA=-DRM_STAMPS): start and end time (100 MHz ticks) of the first 8192 waves of the last
  * v2 launch -- out[w] start of the wave loop, out[8192 + w] end, out[16384 + w] kernel entry, 0 where no wave ran
  * (scripts/tail_hist.py). */
@@ -852,6 +858,12 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *   multi_step 0|1  v2 BVH: a lane takes further march steps inside a round while the leaf set and the winning sphere provably
  *                 stay the same (default 1; same bytes either way)
  *   lds_fill 0|1  v2: pad the LDS request so that exactly blocks_per_cu workgroups fit a CU (default 0; measurement knob)
+ *   min_fill 0|1  v2: a persistent launch brings max(blocks_per_cu, ceil(6 / Q)) workgroups per CU, Q = GPU_MAX_HW_QUEUES as
+ *                 rm_create found it (unset or not a positive integer: 4, HIP's default; never set by the library).  Launches
+ *                 on streams that share a hardware queue run one after the other, so no launch overlaps with more than Q - 1
+ *                 others and a CU holds six of the wave loop's workgroups: fewer per launch leave wave slots empty whatever the
+ *                 caller keeps in flight.  Q >= 6: as asked.  Q = 4: at least 2.  blocks_per_cu reads back as set and lds_fill
+ *                 keeps going by it (default 1; 0 = exactly blocks_per_cu, for sweeps; same bytes either way)
  *   item_wide 0|1 v2: the 64-pixel batches of a work item side by side (item = tile_w * item_px / 64 pixels wide) instead of one
  *                 above the other (default 0: measured no gain in write traffic, 2 % slower with frames in flight)
  *   specialise 0|1|2  small scenes: 1 (default) = the scene compiled into the kernel at run time (rm_rtc_* above), waiting for the
