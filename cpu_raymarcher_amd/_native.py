@@ -226,6 +226,7 @@ SIGNATURES = {
     "rm_debug_read_lpt_costs": (C.c_int, [_VP, _VP, C.c_int64]),
     "rm_debug_launch_fill": (C.c_int, [_VP, C.c_int32, C.POINTER(C.c_int32)]),
     "rm_debug_last_launch": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
+    "rm_debug_overlap_fill": (C.c_int, [_VP, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "rm_rtc_source": (C.c_int, [_VP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_rtc_compile_check": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_double)]),
     "rm_rtc_status": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),

@@ -166,6 +166,13 @@ class Context:
         N.check(self._h, N.lib().rm_debug_last_launch(self._h, out))
         return dict(workgroups=out[0], threads=out[1], lds_bytes=out[2], cus=out[3])
 
+    def overlap_fill(self, asked, items):
+        """Workgroups per CU a v2 launch brings for a frame of `items` work items when `blocks_per_cu` is `asked`: the floor
+        of launch_fill and, where the items pay for it, what option `overlap_fill` adds (rm_debug_overlap_fill; no device needed)."""
+        v = C.c_int32(0)
+        N.check(self._h, N.lib().rm_debug_overlap_fill(self._h, int(asked), int(items), C.byref(v)))
+        return v.value
+
     # ---- scene ----------------------------------------------------------------------
     def scene_from_preset(self, index, accel):
         N.check(self._h, N.lib().rm_scene_from_preset(self._h, int(index), int(accel)))

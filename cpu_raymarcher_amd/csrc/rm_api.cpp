@@ -426,6 +426,10 @@ struct rm_ctx {
     // process has queues: with HIP's default of four, launches of one workgroup per CU fill four of a SIMD's six wave slots
     // whatever the caller keeps in flight.  0: bring exactly blocks_per_cu (measurement sweeps).
     int64_t opt_min_fill = 1;
+    // v2, above that floor: the floor counts on Q launches overlapping, and with more streams than queues they do not (the short
+    // queues drain first: overlap_fill below).  A launch whose work items pay for it brings what fills the CU at the overlap
+    // that is really there.  0: the floor alone.
+    int64_t opt_overlap_fill = 1;
     int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
     uint32_t last_v2_shape[3] = {0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
@@ -524,6 +528,20 @@ int launch_fill(int asked, int queues, bool min_fill) {
     if (!min_fill) return asked;
     const int q = queues > 0 ? queues : 4;
     return std::max(asked, (RM_V2_WAVES + q - 1) / q);
+}
+
+// The workgroups per CU a v2 launch brings where its frame can pay for them (rm_v2_overlap_per_cu, rm_kernels.h), else the
+// floor above.  The floor fills a CU while all Q queues run a launch; streams are not dealt evenly over the queues, so for part
+// of every burst fewer run.  A kernel trace of twelve streams on four queues (profiles/NOTES.md, round 6) has fewer than four
+// launches running for 53 % of the busy time, 1.74 of them on average: E(Q) = 0.436 Q launches overlap while the short queues
+// are drained, and a launch brings ceil(RM_V2_WAVES / E(Q)), at most RM_V2_WAVES.  Q = 4 (measured): 4.  Q = 1, 2, 3, 5
+// (extrapolated with the same share): 6, 6, 5, 3.  Q >= RM_V2_WAVES: the floor, as asked.
+int overlap_fill(int asked, int queues, bool min_fill, bool overlap) {
+    const int floor = launch_fill(asked, queues, min_fill);
+    const int q = queues > 0 ? queues : 4;
+    if (!min_fill || !overlap || q >= RM_V2_WAVES) return floor;
+    const int per_mille = 436 * q;  // 1000 E(Q)
+    return std::max(floor, std::min(RM_V2_WAVES, (RM_V2_WAVES * 1000 + per_mille - 1) / per_mille));
 }
 
 // A kernel compiled at run time (rm_rtc.h), as `specialise` says: 1 waits for the compile; 2 never waits -- the ahead-of-time
@@ -943,6 +961,7 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.oct_prim_count = static_cast<int32_t>(ctx->host.oct_prims.size());
     p.blocks_per_cu = static_cast<int32_t>(ctx->opt_blocks_per_cu);
     p.launch_per_cu = launch_fill(p.blocks_per_cu, ctx->hw_queues, ctx->opt_min_fill != 0);
+    p.overlap_per_cu = overlap_fill(p.blocks_per_cu, ctx->hw_queues, ctx->opt_min_fill != 0, ctx->opt_overlap_fill != 0);
     p.num_cus = ctx->num_cus;
     p.refill_threshold = static_cast<int32_t>(ctx->opt_refill);
     p.hw_xcd = static_cast<int32_t>(ctx->opt_hw_xcd);
@@ -2583,6 +2602,18 @@ int rm_debug_launch_fill(rm_ctx *ctx, int32_t asked, int32_t *effective) {
     return RM_OK;
 }
 
+// ... and what it brings for a frame of `items` work items (overlap_fill above, rm_v2_overlap_per_cu): options `min_fill` and
+// `overlap_fill`, the queue count rm_create read, the context's CU count (256 without a device)
+int rm_debug_overlap_fill(rm_ctx *ctx, int32_t asked, int64_t items, int32_t *effective) {
+    if (!ctx || !effective) return RM_E_INVALID;
+    if (asked < 1 || asked > 8) return fail(ctx, RM_E_INVALID, "blocks_per_cu must be in [1, 8]");
+    if (items < 0) return fail(ctx, RM_E_INVALID, "items must not be negative");
+    const bool min_fill = ctx->opt_min_fill != 0;
+    *effective = rm_v2_overlap_per_cu(launch_fill(asked, ctx->hw_queues, min_fill),
+                                      overlap_fill(asked, ctx->hw_queues, min_fill, ctx->opt_overlap_fill != 0), items, ctx->num_cus);
+    return RM_OK;
+}
+
 // the last launch of the v2 wave loop: workgroups, threads per workgroup, dynamic LDS bytes (zeros before the first); the context's CU count
 int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]) {
     if (!ctx || !out) return RM_E_INVALID;
@@ -2625,6 +2656,7 @@ static const OptionRow kOptions[] = {
     {"specialise", &rm_ctx::opt_specialise, kRange, {0, 2}, "specialise must be 0, 1 or 2"},
     {"lds_fill", &rm_ctx::opt_lds_fill, kSwitch, {}, nullptr},
     {"min_fill", &rm_ctx::opt_min_fill, kSwitch, {}, nullptr},
+    {"overlap_fill", &rm_ctx::opt_overlap_fill, kSwitch, {}, nullptr},
     {"cull", &rm_ctx::opt_cull, kSwitch, {}, nullptr},
     {"rel", &rm_ctx::opt_rel, kSwitch, {}, nullptr},
     {"static", &rm_ctx::opt_static, kRange, {0, 95}, "static must be in [0, 95] percent"},  // stored, ignored (rm_ctx)

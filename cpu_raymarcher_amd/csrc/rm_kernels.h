@@ -176,6 +176,18 @@ const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur
 hipError_t rm_launch_render_v2(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *shape = nullptr);
 hipError_t rm_launch_render_v2_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *shape = nullptr);
 
+// The second stage of the launch fill (option `overlap_fill`): a launch whose floor is `floor_per_cu` workgroups
+// per CU brings `candidate` instead when every one of its waves still gets RM_V2_OVERLAP_ITEMS_PER_WAVE of the frame's `items`
+// (tiles_x * tiles_y work items) -- what a workgroup's start, ~20 KB of tables staged into LDS, has to be paid with.  The
+// threshold is measured (profiles/NOTES.md, round 6).  One definition for the launcher and rm_debug_overlap_fill.
+#define RM_V2_OVERLAP_ITEMS_PER_WAVE 3
+inline int rm_v2_overlap_per_cu(int floor_per_cu, int candidate, long long items, int cus) {
+    if (candidate <= floor_per_cu || cus <= 0) return floor_per_cu;
+    const long long needed = (items + 3) / 4, resident = static_cast<long long>(cus) * candidate;
+    const long long waves = 4 * (needed < resident ? needed : resident);
+    return items >= RM_V2_OVERLAP_ITEMS_PER_WAVE * waves ? candidate : floor_per_cu;
+}
+
 // rm_debug_wave_distance: Scene.getDistance through the wave loop's bvh_distance_wave, one point per lane (BVH sphere scenes)
 hipError_t rm_launch_wave_distance(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);
 hipError_t rm_launch_wave_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);

@@ -1721,9 +1721,12 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         if (lay.end + list_bytes > shmem) return hipErrorInvalidValue;  // the layout and the allocation come from two formulas: they must agree
     }
     // the workgroups per CU the launch brings: what the caller asked, or what rm_api.cpp raised that to (launch_per_cu, option
-    // `min_fill`); `lds_fill` above went by what the caller asked
-    const int per_cu = p.launch_per_cu > 0 ? p.launch_per_cu : p.blocks_per_cu;
-    resident = static_cast<unsigned>(p.num_cus > 0 ? p.num_cus : 256) * static_cast<unsigned>(per_cu > 0 ? per_cu : 4);
+    // `min_fill`), or overlap_per_cu where the frame's work items pay for it (option `overlap_fill`); `lds_fill` above went by
+    // what the caller asked
+    const int cus = p.num_cus > 0 ? p.num_cus : 256;
+    const int floor_per_cu = p.launch_per_cu > 0 ? p.launch_per_cu : p.blocks_per_cu;
+    const int per_cu = rm_v2_overlap_per_cu(floor_per_cu, p.overlap_per_cu, static_cast<long long>(tiles_x) * tiles_y, cus);
+    resident = static_cast<unsigned>(cus) * static_cast<unsigned>(per_cu > 0 ? per_cu : 4);
     blocks = needed < resident ? (needed ? needed : 1u) : resident;
     if (shape) {
         shape[0] = blocks;

@@ -213,6 +213,9 @@ struct RmRenderParams {
     int32_t leaf_order;  // BVH leaf lists are consecutive: leaf = spheres[first .. first+count), no id reads
     int32_t nn_dim[3];   // the nearest-candidate grid has its own (finer) resolution over the root box
     float nn_inv[3];
+    // v2, launcher only: the workgroups per CU the launch brings INSTEAD of launch_per_cu when its work items pay for them
+    // (0: none; rm_v2_overlap_per_cu in rm_kernels.h decides, option `overlap_fill`)
+    int32_t overlap_per_cu;
     // exterior candidate grid (rm_scene_host.cpp build_exterior_grid): nearest-candidate lists for points outside the BVH root box
     const uint32_t *ext_cells;
     const uint16_t *ext_list;

@@ -827,6 +827,10 @@ RM_API int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n);
  * dynamic LDS bytes (zeros before the first such launch) -- and out[3] the context's CU count. */
 RM_API int rm_debug_launch_fill(rm_ctx *ctx, int32_t asked, int32_t *effective);
 RM_API int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]);
+/* Option overlap_fill (below), for tests and evidence: the counterpart of rm_debug_launch_fill with both stages --
+ * *effective = the workgroups per CU a v2 launch brings for a frame of `items` work items when blocks_per_cu is `asked`
+ * (1..8); works on a host-only context (256 CUs). */
+RM_API int rm_debug_overlap_fill(rm_ctx *ctx, int32_t asked, int64_t items, int32_t *effective);
 /* Diagnostic builds only (make EXTRA=-DRM_STAMPS): start and end time (100 MHz ticks) of the first 8192 waves of the last
  * v2 launch -- out[w] start of the wave loop, out[8192 + w] end, out[16384 + w] kernel entry, 0 where no wave ran
  * (scripts/tail_hist.py). */
@@ -864,6 +868,10 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *                 others and a CU holds six of the wave loop's workgroups: fewer per launch leave wave slots empty whatever the
  *                 caller keeps in flight.  Q >= 6: as asked.  Q = 4: at least 2.  blocks_per_cu reads back as set and lds_fill
  *                 keeps going by it (default 1; 0 = exactly blocks_per_cu, for sweeps; same bytes either way)
+ *   overlap_fill 0|1  v2, above that floor, Q < 6: streams are not dealt evenly over the hardware queues, so for part of every
+ *                 burst fewer than Q launches run (Q = 4, twelve streams: 1.74 on average for 53 % of the busy time).  A launch
+ *                 brings min(6, ceil(6 / (0.436 Q))) workgroups per CU -- Q = 4: 4 -- when each of its waves still gets 3 of
+ *                 the frame's work items; smaller frames keep the floor (default 1; 0 = the floor alone; same bytes either way)
  *   item_wide 0|1 v2: the 64-pixel batches of a work item side by side (item = tile_w * item_px / 64 pixels wide) instead of one
  *                 above the other (default 0: measured no gain in write traffic, 2 % slower with frames in flight)
  *   specialise 0|1|2  small scenes: 1 (default) = the scene compiled into the kernel at run time (rm_rtc_* above), waiting for the
