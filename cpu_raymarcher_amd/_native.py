@@ -139,6 +139,20 @@ class rm_prim(C.Structure):  # include/rm_raymarch.h: struct rm_prim
                 ("params", C.c_double * 3), ("reserved2", C.c_double)]
 
 
+class rm_sphere_edit(C.Structure):  # include/rm_raymarch.h: struct rm_sphere_edit
+    _fields_ = [("op", C.c_int32), ("index", C.c_int32), ("center", C.c_float * 3), ("reserved", C.c_int32),
+                ("radius", C.c_double)]
+
+
+# rm_edit_op by name, and the element type of every scene table rm_debug_scene_table names
+RM_EDIT_SET, RM_EDIT_INSERT, RM_EDIT_REMOVE = 0, 1, 2
+EDIT_OPS = {"set": 0, "insert": 1, "remove": 2}
+SCENE_TABLES = {"spheres": "<f4", "radii": "<f8", "bvh": "u1", "bvh_prims": "<i4", "oct": "u1", "oct_prims": "<i4",
+                "pq_cells": "<u4", "pq_list": "<u2", "nn_cells": "<u4", "nn_list": "<u2", "prims": "u1", "prog": "u1",
+                "obj_ranges": "<i4", "oct_recs": "u1", "oct_lut": "<i4", "oct_sub_hdr": "<u4", "oct_sub_list": "u1",
+                "slot_object": "<i4", "ext_cells": "<u4", "ext_list": "<u2"}
+
+
 class rm_diagnostics(C.Structure):
     _fields_ = [("total_sdf_calls", C.c_uint64), ("total_iterations", C.c_uint64),
                 ("max_sdf_calls", C.c_uint32), ("min_sdf_calls", C.c_uint32), ("total_pixels", C.c_uint64)]
@@ -158,6 +172,9 @@ SIGNATURES = {
     "rm_preset_count": (C.c_int, []),
     "rm_scene_from_preset": (C.c_int, [_VP, C.c_int32, C.c_int32]),
     "rm_scene_from_spheres": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32]),
+    "rm_scene_edit_spheres": (C.c_int, [_VP, C.POINTER(rm_sphere_edit), C.c_int32]),
+    "rm_debug_scene_table": (C.c_int, [_VP, C.c_char_p, C.c_int32, _VP, C.c_int64, C.POINTER(C.c_int64)]),
+    "rm_selftest_hypot64": (C.c_int, [_VP, _VP, C.c_int64, C.c_int32, _VP]),
     "rm_scene_from_prims": (C.c_int, [_VP, C.POINTER(rm_prim), C.c_int32, C.c_int32]),
     "rm_make_transform": (C.c_int, [C.c_double, C.c_double, C.c_double, _VP, _VP]),
     "rm_scene_from_nodes": (C.c_int, [_VP, C.POINTER(rm_node), C.c_int32, _VP, C.c_int32, C.c_int32]),

@@ -210,6 +210,43 @@ class Context:
         r = np.ascontiguousarray(roots, dtype=np.int32)
         N.check(self._h, N.lib().rm_scene_from_nodes(self._h, arr, len(nodes), _ptr(r), len(r), int(accel)))
 
+    def edit_spheres(self, edits):
+        """Edits the active sphere scene in place (rm_scene_edit_spheres; the rule is in include/rm_raymarch.h).  edits: a
+        sequence of (op, index) for "remove" and (op, index, centre[3], radius) for "set" / "insert"; op a name of
+        N.EDIT_OPS or an rm_edit_op value; or a ready array of N.rm_sphere_edit.  Indices are object indices at the moment
+        each edit applies.  All or nothing."""
+        if isinstance(edits, C.Array) and edits._type_ is N.rm_sphere_edit:
+            arr, n = edits, len(edits)
+        else:
+            edits = list(edits)
+            n = len(edits)
+            arr = (N.rm_sphere_edit * max(1, n))()
+            for k, e in enumerate(edits):
+                arr[k].op = N.EDIT_OPS[e[0]] if isinstance(e[0], str) else int(e[0])
+                arr[k].index = int(e[1])
+                if len(e) > 2:
+                    arr[k].center[:] = [float(v) for v in np.asarray(e[2], np.float32).reshape(3)]
+                    arr[k].radius = float(e[3])
+        N.check(self._h, N.lib().rm_scene_edit_spheres(self._h, arr, n))
+
+    def scene_table(self, name, from_device=True):
+        """One table of the active scene (rm_debug_scene_table) as a numpy array of N.SCENE_TABLES[name] (records as
+        bytes): the device copy, or with from_device=False the host builder's (the only form a host-only context has)."""
+        size = C.c_int64(0)
+        key = name.encode()
+        N.check(self._h, N.lib().rm_debug_scene_table(self._h, key, int(bool(from_device)), None, 0, C.byref(size)))
+        out = np.zeros(size.value, np.uint8)
+        N.check(self._h, N.lib().rm_debug_scene_table(self._h, key, int(bool(from_device)), _ptr(out), out.size, C.byref(size)))
+        return out.view(N.SCENE_TABLES.get(name, "u1"))
+
+    def selftest_hypot64(self, xyz, on_device=True):
+        """Math.hypot of float64 triples [n, 3] as the host scene builder (on_device=False) or the device builder
+        evaluates it (rm_selftest_hypot64)."""
+        a = np.ascontiguousarray(xyz, dtype=np.float64).reshape(-1, 3)
+        out = np.zeros(len(a), np.float64)
+        N.check(self._h, N.lib().rm_selftest_hypot64(self._h, _ptr(a), len(a), int(bool(on_device)), _ptr(out)))
+        return out
+
     def scene_set_time(self, time):
         """Scene.updateTime(time) for scene_distance (renders take the job's time)."""
         N.check(self._h, N.lib().rm_scene_set_time(self._h, float(time)))

@@ -458,6 +458,10 @@ struct rm_ctx {
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
     const char *last_kernel = "";
+    std::string last_kernel_kept;  // rm_scene_edit_spheres: the name behind last_kernel across the upload (which releases run-time compiled kernels and their names)
+    // rm_scene_edit_spheres: the four pair loops of the scene build (rm_scene_host.h, PairLoops) run on the device
+    // (rm_scene_build.hip); 0: the host builder for everything.  The upload entries never read it.
+    int64_t opt_device_build = 1;
     // Expression forests: the scene's programs compiled into the one-ray-per-lane kernels at run time (rm_rtc.h; option
     // `specialise`, default on).  One kernel per (acceleration structure, marcher family, vec3.length form) the scene is
     // rendered with, compiled at its first launch (1.5 - 3 s, synchronous) and kept until the scene is replaced.  A compile
@@ -764,13 +768,13 @@ int upload_scene(rm_ctx *ctx) {
 int clamp_preset(int idx) { return idx < 0 ? 0 : (idx > rmh::kPresetCount - 1 ? rmh::kPresetCount - 1 : idx); }
 int norm_accel(int a) { return (a == RM_ACCEL_OCTREE || a == RM_ACCEL_BVH) ? a : RM_ACCEL_NONE; }
 
-int set_scene(rm_ctx *ctx, const SceneDesc &d, int accel, bool uploaded, int preset) {
+int set_scene(rm_ctx *ctx, const SceneDesc &d, int accel, bool uploaded, int preset, const rmh::PairLoops *loops = nullptr) {
     std::string err;
     rmh::HostScene hs;
     rmh::set_length_mode(static_cast<int>(ctx->opt_length));
     bool ok = false;
     switch (d.kind) {
-        case SceneDesc::kSpheres: ok = rmh::build_scene(hs, d.centers.data(), d.radii.data(), static_cast<int>(d.radii.size()), accel, err); break;
+        case SceneDesc::kSpheres: ok = rmh::build_scene(hs, d.centers.data(), d.radii.data(), static_cast<int>(d.radii.size()), accel, err, loops); break;
         case SceneDesc::kPrims: ok = rmh::build_scene_general(hs, d.prims.data(), static_cast<int>(d.prims.size()), accel, err); break;
         case SceneDesc::kNodes:
             ok = rmh::build_scene_nodes(hs, d.nodes.data(), static_cast<int>(d.nodes.size()), d.roots.data(), static_cast<int>(d.roots.size()), accel, err);
@@ -807,6 +811,220 @@ bool preset_desc(int preset, SceneDesc &d) {
     d.kind = SceneDesc::kNodes;
     return rmh::preset_nodes(preset, d.nodes, d.roots);
 }
+
+// ---- rm_scene_edit_spheres: the pair loops of the scene build on the device (rm_scene_build.hip) ---------------------------
+
+struct DevMem {  // a device allocation that lives as long as the call that made it
+    void *p = nullptr;
+    DevMem() = default;
+    DevMem(const DevMem &) = delete;
+    DevMem &operator=(const DevMem &) = delete;
+    ~DevMem() {
+        if (p) (void)hipFree(p);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+    template <typename T>
+    hipError_t put(const T *src, size_t n, hipStream_t stream) {  // (src stays valid until the stream is synchronised)
+        hipError_t e = alloc(n * sizeof(T));
+        if (e == hipSuccess && n) e = hipMemcpyAsync(p, src, n * sizeof(T), hipMemcpyHostToDevice, stream);
+        return e;
+    }
+    template <typename T>
+    T *as() const { return static_cast<T *>(p); }
+};
+
+#define RM_TRY(call)                            \
+    do {                                        \
+        if ((call) != hipSuccess) return false; \
+    } while (0)
+
+// The candidate rule (rm_scene_host.cpp, build_point_query_grid) over `grids` on the device -> per cell the header
+// (offset << 8) | count and the lists, byte for byte what the host loops produce.  `ids`: the table the grids' sphere ranges
+// index (null: the scene's spheres themselves).  cap255: the rule of the two grids -- a cell of 255 or more candidates, or
+// one that pass 1 marked (use_root: the exterior grid's cells inside the root box), keeps the header 255 and no list.
+// `order`: the order in which the host appends the cells' lists (null: linear cell order).
+// False, with hdr and list untouched, when the device failed or a list would reach 2^24 entries: that rule of the host's
+// is sequential (it drops the cell that would pass the limit), so the host builds such a table.
+template <typename E>
+bool device_cand_lists(rm_ctx *ctx, const rmh::HostScene &s, const std::vector<int32_t> *ids, const std::vector<RmCandGrid> &grids,
+                       int cells_per_grid, double u0, bool use_root, bool cap255, const std::vector<uint32_t> *order,
+                       std::vector<uint32_t> &hdr, std::vector<E> &list) {
+    const size_t n = s.spheres.size(), n_cells = grids.size() * static_cast<size_t>(cells_per_grid);
+    if (!n || !n_cells || n != s.radii.size() || n > 0x7FFFFFFFu || (order && order->size() != n_cells)) return false;
+    RM_TRY(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    std::vector<double> sp(4 * n);
+    for (size_t i = 0; i < n; ++i) {
+        sp[4 * i] = s.spheres[i].cx;
+        sp[4 * i + 1] = s.spheres[i].cy;
+        sp[4 * i + 2] = s.spheres[i].cz;
+        sp[4 * i + 3] = s.radii[i];
+    }
+    DevMem d_sp, d_ids, d_grids, d_counts, d_u, d_off, d_list;
+    RM_TRY(d_sp.put(sp.data(), sp.size(), st));
+    if (ids) RM_TRY(d_ids.put(ids->data(), ids->size(), st));
+    RM_TRY(d_grids.put(grids.data(), grids.size(), st));
+    RM_TRY(d_counts.alloc(n_cells * sizeof(uint32_t)));
+    RM_TRY(d_u.alloc(n_cells * sizeof(double)));
+    RmCandArgs a = {};
+    a.grids = d_grids.as<RmCandGrid>();
+    a.spheres = d_sp.as<double>();
+    a.ids = ids ? d_ids.as<int32_t>() : nullptr;
+    a.counts = d_counts.as<uint32_t>();
+    a.u = d_u.as<double>();
+    a.n_cells = static_cast<long long>(n_cells);
+    a.u0 = u0;
+    for (int k = 0; k < 3; ++k) {
+        a.root_lo[k] = s.root_min[k];
+        a.root_hi[k] = s.root_max[k];
+    }
+    a.n_grids = static_cast<int32_t>(grids.size());
+    a.cells_per_grid = cells_per_grid;
+    a.n_spheres = static_cast<int32_t>(n);
+    a.n_ids = ids ? static_cast<int32_t>(ids->size()) : 0;
+    a.use_root = use_root ? 1 : 0;
+    RM_TRY(rm_launch_cand_count(a, st));
+    std::vector<uint32_t> counts(n_cells);
+    RM_TRY(hipMemcpyAsync(counts.data(), d_counts.p, n_cells * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    RM_TRY(hipStreamSynchronize(st));
+    std::vector<uint32_t> offs(n_cells), h(n_cells);
+    size_t total = 0;
+    for (size_t i = 0; i < n_cells; ++i) {
+        const size_t c = order ? (*order)[i] : i;
+        if (c >= n_cells) return false;
+        const uint32_t cnt = counts[c];
+        if (cnt == RM_CAND_NO_LIST || cnt >= (cap255 ? 255u : 256u)) {
+            if (!cap255) return false;
+            offs[c] = RM_CAND_NO_LIST;
+            h[c] = 255;
+            continue;
+        }
+        if (total + cnt >= (1u << 24)) return false;
+        offs[c] = static_cast<uint32_t>(total);
+        h[c] = static_cast<uint32_t>(total << 8) | cnt;
+        total += cnt;
+    }
+    std::vector<E> out(total);
+    if (total) {
+        RM_TRY(d_off.put(offs.data(), offs.size(), st));
+        RM_TRY(d_list.alloc(total * sizeof(E)));
+        a.offsets = d_off.as<uint32_t>();
+        a.list_len = total;
+        RM_TRY(rm_launch_cand_fill(a, d_list.p, static_cast<int>(sizeof(E)), st));
+        RM_TRY(hipMemcpyAsync(out.data(), d_list.p, total * sizeof(E), hipMemcpyDeviceToHost, st));
+        RM_TRY(hipStreamSynchronize(st));
+    }
+    hdr.swap(h);
+    list.swap(out);
+    return true;
+}
+
+// rmh::PairLoops served by the device
+rmh::PairLoops device_pair_loops(rm_ctx *ctx) {
+    rmh::PairLoops L;
+    L.nn_grid = [ctx](rmh::HostScene &s) {
+        RmCandGrid g = {};
+        int cells = 1;
+        for (int k = 0; k < 3; ++k) {
+            g.org[k] = double(s.pq_origin[k]);
+            g.w[k] = s.nn_inv[k] > 0 ? 1.0 / double(s.nn_inv[k]) : 0.0;
+            g.dim[k] = s.nn_dim[k];
+            cells *= s.nn_dim[k];
+        }
+        g.n = static_cast<int32_t>(s.spheres.size());
+        std::vector<uint32_t> hdr;
+        std::vector<uint16_t> list;
+        if (!device_cand_lists<uint16_t>(ctx, s, nullptr, {g}, cells, 10.0, false, true, nullptr, hdr, list)) return false;
+        s.nn_cells.swap(hdr);
+        s.nn_list.swap(list);
+        return true;
+    };
+    L.ext_grid = [ctx](rmh::HostScene &s) {
+        RmCandGrid g = {};
+        const int dim = s.ext_dim[0];
+        if (dim <= 0 || dim % 4 || s.ext_dim[1] != dim || s.ext_dim[2] != dim) return false;
+        for (int k = 0; k < 3; ++k) {
+            g.org[k] = double(s.ext_origin[k]);
+            g.w[k] = 1.0 / double(s.ext_inv[k]);
+            g.dim[k] = dim;
+        }
+        g.n = static_cast<int32_t>(s.spheres.size());
+        // the host appends the lists block by block (4^3 cells, build_exterior_grid): the offsets follow that order
+        std::vector<uint32_t> order;
+        order.reserve(static_cast<size_t>(dim) * dim * dim);
+        for (int bz = 0; bz < dim; bz += 4)
+            for (int by = 0; by < dim; by += 4)
+                for (int bx = 0; bx < dim; bx += 4)
+                    for (int z = bz; z < bz + 4; ++z)
+                        for (int y = by; y < by + 4; ++y)
+                            for (int x = bx; x < bx + 4; ++x) order.push_back(static_cast<uint32_t>((z * dim + y) * dim + x));
+        std::vector<uint32_t> hdr;
+        std::vector<uint16_t> list;
+        if (!device_cand_lists<uint16_t>(ctx, s, nullptr, {g}, dim * dim * dim, 10.0, true, true, &order, hdr, list)) return false;
+        s.ext_cells.swap(hdr);
+        s.ext_list.swap(list);
+        return true;
+    };
+    L.oct_sub = [ctx](rmh::HostScene &s, const std::vector<int32_t> &leaves) {
+        const int kSub = RM_OCT_SUB * RM_OCT_SUB * RM_OCT_SUB;
+        std::vector<RmCandGrid> grids(leaves.size());
+        for (size_t i = 0; i < leaves.size(); ++i) {
+            if (leaves[i] < 0 || static_cast<size_t>(leaves[i]) >= s.oct.size()) return false;
+            const RmOctNode &nd = s.oct[leaves[i]];
+            RmCandGrid &g = grids[i];
+            g = RmCandGrid{};
+            for (int k = 0; k < 3; ++k) {
+                g.org[k] = double(nd.lo[k]);
+                g.w[k] = (double(nd.hi[k]) - double(nd.lo[k])) / double(RM_OCT_SUB);
+                g.dim[k] = RM_OCT_SUB;
+            }
+            g.first = nd.prim_first;
+            g.n = nd.prim_count;
+        }
+        std::vector<uint32_t> hdr;
+        std::vector<uint8_t> list;
+        if (!device_cand_lists<uint8_t>(ctx, s, &s.oct_prims, grids, kSub, std::numeric_limits<double>::infinity(), false, false, nullptr,
+                                        hdr, list))
+            return false;
+        for (size_t i = 0; i < leaves.size(); ++i)  // the host stops at the first leaf that could pass 2^24 entries
+            if ((hdr[i * kSub] >> 8) + static_cast<size_t>(kSub) * static_cast<size_t>(s.oct[leaves[i]].prim_count) >= (1u << 24)) return false;
+        s.oct_sub_hdr.swap(hdr);
+        s.oct_sub_list.swap(list);
+        return true;
+    };
+    L.empty_dist = [ctx](const rmh::HostScene &s, const std::vector<int32_t> &nodes, std::vector<double> &out) {
+        const size_t n_prims = s.prim_lo.size() / 3;
+        if (nodes.empty() || nodes.size() > 0x7FFFFFFFu || n_prims > 0x7FFFFFFFu || s.prim_hi.size() != s.prim_lo.size()) return false;
+        std::vector<float> boxes(6 * nodes.size());
+        for (size_t i = 0; i < nodes.size(); ++i) {
+            if (nodes[i] < 0 || static_cast<size_t>(nodes[i]) >= s.oct.size()) return false;
+            std::memcpy(&boxes[6 * i], s.oct[nodes[i]].lo, 3 * sizeof(float));
+            std::memcpy(&boxes[6 * i + 3], s.oct[nodes[i]].hi, 3 * sizeof(float));
+        }
+        RM_TRY(hipSetDevice(ctx->device));
+        hipStream_t st = ctx->stream;
+        DevMem d_boxes, d_lo, d_hi, d_out;
+        RM_TRY(d_boxes.put(boxes.data(), boxes.size(), st));
+        RM_TRY(d_lo.put(s.prim_lo.data(), s.prim_lo.size(), st));
+        RM_TRY(d_hi.put(s.prim_hi.data(), s.prim_hi.size(), st));
+        RM_TRY(d_out.alloc(nodes.size() * sizeof(double)));
+        RmEmptyDistArgs a = {};
+        a.boxes = d_boxes.as<float>();
+        a.prim_lo = d_lo.as<float>();
+        a.prim_hi = d_hi.as<float>();
+        a.out = d_out.as<double>();
+        a.n_nodes = static_cast<int32_t>(nodes.size());
+        a.n_prims = static_cast<int32_t>(n_prims);
+        RM_TRY(rm_launch_empty_dist(a, st));
+        std::vector<double> d(nodes.size());
+        RM_TRY(hipMemcpyAsync(d.data(), d_out.p, d.size() * sizeof(double), hipMemcpyDeviceToHost, st));
+        RM_TRY(hipStreamSynchronize(st));
+        out.swap(d);
+        return true;
+    };
+    return L;
+}
+#undef RM_TRY
 
 int scene_n_prims(const rm_ctx *ctx) {
     if (ctx->host.program) return static_cast<int>(ctx->host.obj_ranges.size() / 2);
@@ -1625,6 +1843,91 @@ int rm_scene_from_spheres(rm_ctx *ctx, const float *centers_xyz, const double *r
     if (n) d.centers.assign(centers_xyz, centers_xyz + 3 * static_cast<size_t>(n));
     if (n) d.radii.assign(radii, radii + n);
     return set_uploaded_scene(ctx, std::move(d), accel);
+}
+
+int rm_scene_edit_spheres(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits) {
+    if (!ctx) return RM_E_INVALID;
+    if (n_edits < 0 || (n_edits > 0 && !edits)) return fail(ctx, RM_E_INVALID, "bad edit list");
+    for (int32_t i = 0; i < n_edits; ++i) {  // what can be said of an edit without the scene
+        const rm_sphere_edit &e = edits[i];
+        if (e.op != RM_EDIT_SET && e.op != RM_EDIT_INSERT && e.op != RM_EDIT_REMOVE) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": unknown op");
+        if (e.reserved != 0) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": reserved must be 0");
+        if (e.op != RM_EDIT_REMOVE &&
+            !(std::isfinite(e.center[0]) && std::isfinite(e.center[1]) && std::isfinite(e.center[2]) && std::isfinite(e.radius)))
+            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": non-finite sphere centre or radius");
+    }
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    // the active scene's object list
+    SceneDesc d;
+    if (ctx->scene_is_uploaded) {
+        if (ctx->uploaded.kind != SceneDesc::kSpheres) return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
+        d.centers = ctx->uploaded.centers;
+        d.radii = ctx->uploaded.radii;
+    } else if (!rmh::preset_spheres(ctx->scene_preset, d.centers, d.radii)) {
+        return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
+    }
+    d.kind = SceneDesc::kSpheres;
+    for (int32_t i = 0; i < n_edits; ++i) {
+        const rm_sphere_edit &e = edits[i];
+        const int64_t n = static_cast<int64_t>(d.radii.size());
+        if (e.index < 0 || e.index > n || (e.op != RM_EDIT_INSERT && e.index == n))
+            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": index out of range");
+        const auto c = d.centers.begin() + 3 * static_cast<std::ptrdiff_t>(e.index);
+        const auto r = d.radii.begin() + e.index;
+        if (e.op == RM_EDIT_REMOVE) {
+            d.centers.erase(c, c + 3);
+            d.radii.erase(r);
+        } else if (e.op == RM_EDIT_INSERT) {
+            d.centers.insert(c, e.center, e.center + 3);
+            d.radii.insert(r, e.radius);
+        } else {
+            std::copy(e.center, e.center + 3, c);
+            *r = e.radius;
+        }
+    }
+    if (n_edits == 0) return RM_OK;
+    // from here on as rm_scene_from_spheres(edited list, same acceleration structure): nothing changes unless the build succeeds
+    std::string kernel_name = ctx->last_kernel ? ctx->last_kernel : "";
+    const rmh::PairLoops loops = (ctx->has_device && ctx->opt_device_build) ? device_pair_loops(ctx) : rmh::PairLoops();
+    const int rc = set_scene(ctx, d, ctx->host.accel, true, RM_SCENE_UPLOADED, &loops);
+    ctx->last_kernel_kept.swap(kernel_name);  // not a render entry: rm_last_kernel keeps its answer
+    ctx->last_kernel = ctx->last_kernel_kept.c_str();
+    if (rc) return rc;
+    ctx->uploaded = std::move(d);
+    ctx->have_uploaded = true;
+    return RM_OK;
+}
+
+int rm_debug_scene_table(rm_ctx *ctx, const char *name, int32_t from_device, void *out, int64_t cap, int64_t *bytes) {
+    if (!ctx) return RM_E_INVALID;
+    if (!name || !bytes || cap < 0 || (cap > 0 && !out)) return fail(ctx, RM_E_INVALID, "bad arguments");
+    *bytes = 0;
+    const void *host = nullptr, *dev = nullptr;
+    size_t size = 0;
+    bool found = false;
+#define RM_X(nm, always)                                                                        \
+    if (!found && !std::strcmp(name, #nm)) {                                                    \
+        found = true;                                                                           \
+        host = ctx->host.nm.data();                                                             \
+        size = ctx->host.nm.size() * sizeof(decltype(rmh::HostScene::nm)::value_type);          \
+        dev = ctx->dev.nm;                                                                      \
+    }
+    RM_SCENE_ARRAYS(RM_X)
+#undef RM_X
+    if (!found) return fail(ctx, RM_E_INVALID, std::string("unknown scene table ") + name);
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (from_device && !ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: read the host copy");
+    *bytes = static_cast<int64_t>(size);
+    if (!size || static_cast<int64_t>(size) > cap) return RM_OK;
+    if (!from_device) {
+        std::memcpy(out, host, size);
+        return RM_OK;
+    }
+    if (!dev) return fail(ctx, RM_E_HIP, std::string("no device copy of scene table ") + name);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, hipDeviceSynchronize());
+    RM_HIP(ctx, hipMemcpy(out, dev, size, hipMemcpyDeviceToHost));
+    return RM_OK;
 }
 
 int rm_scene_from_nodes(rm_ctx *ctx, const rm_node *nodes, int32_t n_nodes, const int32_t *roots, int32_t n_roots,
@@ -2497,6 +2800,28 @@ int rm_selftest_jsmath(rm_ctx *ctx, int32_t fn, const double *a, const double *b
     return RM_OK;
 }
 
+int rm_selftest_hypot64(rm_ctx *ctx, const double *xyz, int64_t n, int32_t on_device, double *out) {
+    if (!ctx) return RM_E_INVALID;
+    if (n < 0 || (n > 0 && (!xyz || !out))) return fail(ctx, RM_E_INVALID, "bad buffers");
+    if (!on_device) {  // the host builder's own Math.hypot
+        for (int64_t i = 0; i < n; ++i) out[i] = rmh::js_hypot3(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+        return RM_OK;
+    }
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context");
+    if (!n) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t k = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_xyz = st.region(24 * k), o_out = st.region(8 * k);
+    int rc = st.reserve();
+    if (rc) return rc;
+    RM_HIP(ctx, st.in(o_xyz, xyz, 24 * k));
+    RM_HIP(ctx, rm_launch_hypot64(st.at<const double>(o_xyz), n, st.at<double>(o_out), ctx->stream));
+    RM_HIP(ctx, st.out(out, o_out, 8 * k));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
 int rm_selftest_fastdiv(rm_ctx *ctx, uint64_t seed, int64_t n, uint64_t *mismatches) {
     if (!mismatches) return RM_E_INVALID;
     RM_NEED_DEVICE(ctx, "host-only context");
@@ -2673,6 +2998,7 @@ static const OptionRow kOptions[] = {
     {"oct_lean", &rm_ctx::opt_oct_lean, kSwitch, {}, nullptr},
     {"lpt", &rm_ctx::opt_lpt, kSwitch, {}, nullptr},
     {"n0_batch", &rm_ctx::opt_n0_batch, kRange, {1, 64}, "n0_batch must be in [1, 64]"},
+    {"device_build", &rm_ctx::opt_device_build, kSwitch, {}, nullptr},
     {"length", &rm_ctx::opt_length, kRange, {0, 1}, "length must be 0 (Math.hypot) or 1 (Math.sqrt)"},  // part of the numeric contract, not a measurement knob (rm_raymarch.h)
 };
 

@@ -159,8 +159,47 @@ struct RmShadeFieldArgs {
     unsigned int lo, hi;
     int map, pad;  // 0 distance, 1 count
 };
+// The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
+// A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
+// its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
+// id table -- or, without one, of its sphere table.
+struct RmCandGrid {
+    double org[3], w[3];
+    int32_t dim[3];
+    int32_t first, n, pad;
+};
+#define RM_CAND_NO_LIST 0xFFFFFFFFu  // counts / offsets: the cell keeps no list
+// One launch of the candidate rule over n_grids grids of cells_per_grid cells each (= dim[0] * dim[1] * dim[2] of every
+// grid), cells numbered grid after grid, x fastest.  Pass 1 (rm_launch_cand_count) writes counts and u; the caller turns
+// the counts into offsets; pass 2 (rm_launch_cand_fill) reads offsets and u and writes the lists.
+struct RmCandArgs {
+    const RmCandGrid *grids;
+    const double *spheres;  // per sphere cx, cy, cz (the binary32 centre, widened) and the radius
+    const int32_t *ids;     // sphere ids the grids' ranges index, or null
+    uint32_t *counts;       // pass 1, per cell: spheres with lb <= U + 1e-6, or RM_CAND_NO_LIST (use_root: the cell lies inside the root box)
+    double *u;              // per cell: U = min(u0, min_j ub_j)
+    const uint32_t *offsets;  // pass 2, per cell: where its list starts, or RM_CAND_NO_LIST
+    long long n_cells;      // n_grids * cells_per_grid
+    unsigned long long list_len;  // entries the list buffer of pass 2 holds
+    double u0;
+    double root_lo[3], root_hi[3];
+    int32_t n_grids, cells_per_grid, n_spheres, n_ids, use_root, pad;
+};
+// OctBuilder::nearest_prim_box for n_nodes node boxes (lo[3], hi[3] per node) against n_prims primitive boxes
+struct RmEmptyDistArgs {
+    const float *boxes, *prim_lo, *prim_hi;
+    double *out;  // per node: max(0, min_i box_gap(node, prim i)), 0 without a primitive
+    int32_t n_nodes, n_prims;
+};
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
+// rm_scene_build.hip.  elem_bytes: 2 (uint16_t lists: the two grids) or 1 (uint8_t: octree sub-cells)
+hipError_t rm_launch_cand_count(const RmCandArgs &a, hipStream_t stream);
+hipError_t rm_launch_cand_fill(const RmCandArgs &a, void *list, int elem_bytes, hipStream_t stream);
+hipError_t rm_launch_empty_dist(const RmEmptyDistArgs &a, hipStream_t stream);
+// rmh::js_hypot3 of n binary64 triples as the device builder evaluates it (rm_selftest_hypot64)
+hipError_t rm_launch_hypot64(const double *xyz, int64_t n, double *out, hipStream_t stream);
+
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
 // instantiation that was launched (static string); v2_shape (optional) what a launch of the v2 wave loop was launched with:
 // workgroups, threads per workgroup, dynamic LDS bytes (left alone by every other launch).

@@ -182,7 +182,7 @@ struct BvhBuilder {
 // cell grown by 1 % of a cell (the device computes the cell index in binary32, error ~1e-5
 // cell), and the device re-tests each listed leaf box with the reference's inclusive f32
 // compares, so the result set is identical.
-void build_point_query_grid(HostScene &s) {
+void build_point_query_grid(HostScene &s, const PairLoops *loops) {
     const int leaves = s.bvh_leaves;
     if (s.bvh.empty() || leaves == 0) return;
     int g = static_cast<int>(std::ceil(std::cbrt(static_cast<double>(leaves)) * 3.0));
@@ -252,6 +252,7 @@ void build_point_query_grid(HostScene &s) {
         ncells *= static_cast<size_t>(s.nn_dim[k]);
     }
     s.nn_cells.assign(ncells, 255);
+    if (loops && loops->nn_grid && loops->nn_grid(s)) return;  // (the same lists from outside: rm_scene_host.h, PairLoops)
     const double margin = 1e-6;
     std::vector<double> lb(n);
     for (int z = 0; z < s.nn_dim[2]; ++z)
@@ -301,7 +302,7 @@ void build_point_query_grid(HostScene &s) {
 // holds: whatever is not listed has lb_j > min_k ub_k >= min_k sdf_k(p) for every point p of the cell.  A cell whose grown
 // box lies inside the root box receives no exterior point and stays 255.
 // Refused (no grid): general scenes, fewer than 16 or more than 2048 spheres, a root box that covers the whole region.
-void build_exterior_grid(HostScene &s) {
+void build_exterior_grid(HostScene &s, const PairLoops *loops) {
     const double kExtReach = 8.7;  // > sqrt(3^2 + 10^2 - 2 * 3 * 10 / sqrt 3): orbit radius 3 (camera_from_angles), MAX_DIST 10 (raymarcher.ts)
     if (s.general || s.program || s.bvh.empty()) return;
     const size_t n = s.spheres.size();
@@ -324,6 +325,7 @@ void build_exterior_grid(HostScene &s) {
     }
     s.ext_dim[0] = s.ext_dim[1] = s.ext_dim[2] = g;
     s.ext_cells.assign(static_cast<size_t>(g) * g * g, 255);
+    if (loops && loops->ext_grid && loops->ext_grid(s)) return;  // (built flat there: the comment below has why the lists agree)
     const double margin = 1e-6;
     std::vector<double> lb(n);
     // the candidates of the box [lo, hi] among the spheres `from`, in their order
@@ -444,12 +446,17 @@ struct OctBuilder {
         return best != std::numeric_limits<double>::infinity() ? js_max2(0.0, best) : 0.0;
     }
 
+    // The empty nodes, in the order mark meets them: their min_distance is set by mark_distances once the walk is done
+    // (nearest_prim_box reads the primitive boxes alone, so the order of evaluation is free).
+    std::vector<int32_t> empty_nodes;
+
     bool mark(int me) {  // octree.ts:149-191
         RmOctNode &node = s.oct[me];
         if (node.first_child < 0) {
             const bool has = node.prim_count > 0;
             node.is_empty = has ? 0 : 1;
-            node.min_distance = has ? 0.0 : nearest_prim_box(node);
+            node.min_distance = 0.0;
+            if (!has) empty_nodes.push_back(me);
             s.oct_leaves++;
             if (!has) s.oct_empty++;
             s.oct_max_leaf = std::max(s.oct_max_leaf, node.prim_count);
@@ -460,8 +467,18 @@ struct OctBuilder {
         for (int i = 0; i < 8; ++i)
             if (mark(first + i)) any = true;
         s.oct[me].is_empty = any ? 0 : 1;
-        s.oct[me].min_distance = any ? 0.0 : nearest_prim_box(s.oct[me]);
+        s.oct[me].min_distance = 0.0;
+        if (!any) empty_nodes.push_back(me);
         return any;
+    }
+
+    void mark_distances(const PairLoops *loops) {
+        std::vector<double> d;
+        if (!(loops && loops->empty_dist && loops->empty_dist(s, empty_nodes, d) && d.size() == empty_nodes.size())) {
+            d.resize(empty_nodes.size());
+            for (size_t i = 0; i < empty_nodes.size(); ++i) d[i] = nearest_prim_box(s.oct[empty_nodes[i]]);
+        }
+        for (size_t i = 0; i < empty_nodes.size(); ++i) s.oct[empty_nodes[i]].min_distance = d[i];
     }
 };
 
@@ -551,7 +568,7 @@ bool preset_spheres(int index, std::vector<float> &centers, std::vector<double> 
 }
 
 // BVH / Octree over the padded primitive boxes already in s.prim_lo / prim_hi
-static bool build_accel(HostScene &s, int n, std::string &err) {
+static bool build_accel(HostScene &s, int n, std::string &err, const PairLoops *loops = nullptr) {
     std::vector<int32_t> all(n);
     std::iota(all.begin(), all.end(), 0);
     if (s.accel == 2) {
@@ -561,8 +578,8 @@ static bool build_accel(HostScene &s, int n, std::string &err) {
         if (!b.ok) return false;
         std::memcpy(s.root_min, root.lo, sizeof root.lo);
         std::memcpy(s.root_max, root.hi, sizeof root.hi);
-        build_point_query_grid(s);  // the leaf grid only knows leaf boxes: it serves every primitive representation
-        build_exterior_grid(s);
+        build_point_query_grid(s, loops);  // the leaf grid only knows leaf boxes: it serves every primitive representation
+        build_exterior_grid(s, loops);
     } else if (s.accel == 1) {
         Box root;  // scene.ts:81-85
         for (int k = 0; k < 3; ++k) {
@@ -573,6 +590,7 @@ static bool build_accel(HostScene &s, int n, std::string &err) {
         OctBuilder b{s};
         b.fill(0, all, root, 0);
         b.mark(0);
+        b.mark_distances(loops);
         {  // flat findNode table (see rm_scene_host.h); left empty if a leaf is not a box of whole cells
             std::vector<int32_t> lut(64 * 64 * 64, -1);
             bool ok = true;
@@ -597,11 +615,27 @@ static bool build_accel(HostScene &s, int n, std::string &err) {
         }
         if (!s.general) {  // sub-cell candidate lists of crowded leaves (see rm_scene_host.h)
             const double margin = 1e-6;
+            const size_t kSubCells = size_t(RM_OCT_SUB) * RM_OCT_SUB * RM_OCT_SUB;
+            std::vector<int32_t> crowded;
             for (size_t i = 0; i < s.oct.size(); ++i) {
-                RmOctNode &nd = s.oct[i];
+                const RmOctNode &nd = s.oct[i];
+                if (nd.first_child < 0 && nd.prim_count > 8 && nd.prim_count <= 255) crowded.push_back(static_cast<int32_t>(i));
+            }
+            bool supplied = loops && loops->oct_sub && !crowded.empty() && loops->oct_sub(s, crowded);
+            if (supplied && s.oct_sub_hdr.size() != crowded.size() * kSubCells) {
+                s.oct_sub_hdr.clear();
+                s.oct_sub_list.clear();
+                supplied = false;
+            }
+            for (size_t li = 0; li < crowded.size(); ++li) {
+                RmOctNode &nd = s.oct[crowded[li]];
                 const int n = nd.prim_count;
-                if (nd.first_child >= 0 || n <= 8 || n > 255) continue;
-                if (s.oct_sub_list.size() + size_t(RM_OCT_SUB) * RM_OCT_SUB * RM_OCT_SUB * size_t(n) >= (1u << 24)) break;
+                if (supplied) {  // (every leaf was admitted: PairLoops::oct_sub refuses otherwise)
+                    nd.sub_first = static_cast<int32_t>(li * kSubCells);
+                    for (int k = 0; k < 3; ++k) nd.center[k] = static_cast<float>(RM_OCT_SUB) / (nd.hi[k] - nd.lo[k]);
+                    continue;
+                }
+                if (s.oct_sub_list.size() + kSubCells * size_t(n) >= (1u << 24)) break;
                 nd.sub_first = static_cast<int32_t>(s.oct_sub_hdr.size());
                 // a leaf has no split point: `center` carries the sub-cells per unit length instead, so the kernel indexes a
                 // sub-cell with three multiplications and no division (binary32 quotient, as the kernel used to form it)
@@ -658,7 +692,7 @@ static bool build_accel(HostScene &s, int n, std::string &err) {
 }
 
 bool build_scene(HostScene &s, const float *centers, const double *radii, int n, int accel,
-                 std::string &err) {
+                 std::string &err, const PairLoops *loops) {
     if (n < 0 || (n > 0 && (!centers || !radii))) {
         err = "bad sphere list";
         return false;
@@ -688,7 +722,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
         }
     }
     s.world_pos.assign(centers, centers + 3 * size_t(n));
-    if (!build_accel(s, n, err)) return false;
+    if (!build_accel(s, n, err, loops)) return false;
     // BVH: every sphere lives in exactly one leaf, so the device arrays can be permuted into leaf order; a leaf's
     // spheres are then spheres[first .. first+count) and the id indirection (one dependent LDS read per sphere)
     // disappears.  min() and the counters do not depend on the order.

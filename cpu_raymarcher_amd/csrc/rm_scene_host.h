@@ -3,6 +3,7 @@
 // rm_types.h.  Runs once per scene change (the reference rebuilds per tile per frame,
 // raymarchWorker.ts:37-38).  Pure C++, no HIP.
 #pragma once
+#include <functional>
 #include <string>
 #include <vector>
 
@@ -103,9 +104,29 @@ double vec3_length_host(double x, double y, double z);
 // sceneManager.ts:102-170: sphere-only presets 0..4; false for the others
 bool preset_spheres(int index, std::vector<float> &centers, std::vector<double> &radii);
 
-// Builds spheres + acceleration structure.  Returns false and sets err on bad input.
+// The four pair loops of a sphere scene's build -- every (cell, sphere) or (node, box) pair, independent per cell or node --
+// as they can be supplied from outside (rm_api.cpp: the device builder of rm_scene_build.hip).  Each member may be empty, and
+// each call may return false: the host loop then builds that table, as it does without a PairLoops.  A supplier leaves the
+// table as it found it when it returns false.  The trees, the leaf grid, the octree cell table and the leaf-order
+// permutation (applied to nn_list / ext_list afterwards, whoever built them) stay with the host.
+struct PairLoops {
+    // build_point_query_grid, second half: nn_dim / nn_inv / pq_origin are set, nn_cells holds 255 per cell, nn_list is empty;
+    // s.spheres / s.radii are in input order.  Fills nn_cells and nn_list.
+    std::function<bool(HostScene &s)> nn_grid;
+    // build_exterior_grid: ext_dim / ext_origin / ext_inv are set, ext_cells holds 255 per cell, ext_list is empty.
+    std::function<bool(HostScene &s)> ext_grid;
+    // The sub-cell lists of the crowded octree leaves `leaves` (node indices, increasing; sub_first and center are not set
+    // yet): appends RM_OCT_SUB^3 headers per leaf to oct_sub_hdr and the lists to oct_sub_list, which are empty.  It must
+    // refuse (false) when a leaf would start at or beyond 2^24 - RM_OCT_SUB^3 * prim_count entries: the host stops there.
+    std::function<bool(HostScene &s, const std::vector<int32_t> &leaves)> oct_sub;
+    // OctBuilder::nearest_prim_box (octree.ts:155-160) of the nodes `nodes`: out[i] = max(0, min over all primitive boxes of
+    // box_gap(nodes[i], box)), 0 without a primitive.
+    std::function<bool(const HostScene &s, const std::vector<int32_t> &nodes, std::vector<double> &out)> empty_dist;
+};
+
+// Builds spheres + acceleration structure.  Returns false and sets err on bad input.  `loops`: see PairLoops.
 bool build_scene(HostScene &s, const float *centers, const double *radii, int n, int accel,
-                 std::string &err);
+                 std::string &err, const PairLoops *loops = nullptr);
 
 // SceneManager.getTransform (sceneManager.ts:21-37): world->local matrix of a primitive placed
 // at (x, y, z); rot == nullptr is the branch without a rotation argument

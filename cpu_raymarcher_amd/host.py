@@ -86,6 +86,27 @@ class Scene:
         self.ctx.scene_from_nodes(nodes, roots, self.accel_enum)
         self._uploaded = True
 
+    # ---- object CRUD on sphere scenes (the reference README's third plan; rm_scene_edit_spheres) ----
+    def editSpheres(self, edits):
+        """Applies a batch of edits to this scene's sphere list in place: edits = [("set", i, centre, radius),
+        ("insert", i, centre, radius), ("remove", i), ...], indices in object order (what objectAt returns) at the moment
+        each edit applies.  The scene must be a sphere list (loadSpheres, or preset 0..4); it is the uploaded scene
+        afterwards, exactly as loadSpheres(edited list) would leave it.  All or nothing."""
+        edits = list(edits)
+        self._activate()
+        self.ctx.edit_spheres(edits)
+        if edits:
+            self._uploaded = True
+
+    def setSphere(self, i, centre, radius):
+        self.editSpheres([("set", i, centre, radius)])
+
+    def insertSphere(self, i, centre, radius):
+        self.editSpheres([("insert", i, centre, radius)])
+
+    def removeSphere(self, i):
+        self.editSpheres([("remove", i)])
+
     def updateTime(self, time):  # scene.ts:135-140
         self.ctx.scene_set_time(time)
         self.time = float(time)

@@ -149,6 +149,42 @@ RM_API int rm_scene_from_preset(rm_ctx *ctx, int32_t preset_index, int32_t accel
 RM_API int rm_scene_from_spheres(rm_ctx *ctx, const float *centers_xyz, const double *radii,
                                  int32_t n, int32_t accel);
 
+/* Edits the active sphere scene in place: the "update" of object CRUD beside rm_ray_pick (which object) and rm_scene_object
+ * (read it back).  The active scene must be a sphere list -- one given to rm_scene_from_spheres, or preset 0..4.  Its objects,
+ * in object order (what rm_ray_pick and rm_scene_object index by, never a device slot), form a list, and the edits apply to
+ * that list in order: SET replaces entry index (0 <= index < n), INSERT puts a new sphere before index (0 <= index <= n),
+ * REMOVE deletes entry index; n is the list's length when the edit's turn comes.  Afterwards the context is in every observable
+ * respect what rm_scene_from_spheres(ctx, edited list, the active acceleration structure) leaves: the scene is the uploaded
+ * one (RM_SCENE_UPLOADED in jobs and in rm_scene_get_info, also when a preset was edited), a job that names another
+ * acceleration structure rebuilds the edited list, and every render, query, pick, object index and device table is
+ * bit-identical.  All or nothing: the whole list of edits is checked before anything changes, and on any error the scene, its
+ * device tables and the remembered upload are as before.
+ *   RM_E_INVALID      null edits with n_edits > 0, n_edits < 0, an op outside the enum, reserved != 0, a non-finite centre
+ *                     or radius in SET / INSERT (all checked ahead of everything else), an index out of range at its turn
+ *   RM_E_NO_SCENE     before any scene
+ *   RM_E_UNSUPPORTED  the active scene is a primitive list, a forest or preset 5..18: those keep no candidate tables and
+ *                     rebuild in milliseconds; rm_scene_object -> rm_scene_from_nodes stays their route
+ *   a build error of the edited list is reported as rm_scene_from_spheres reports it.
+ * n_edits == 0 (on a scene that could be edited) is RM_OK, rebuilds nothing and leaves a preset a preset.
+ * What makes the edit cheaper than an upload: with option device_build = 1 (default) and a device, the four (cell, sphere) /
+ * (node, box) pair loops of the build -- the BVH's nearest-candidate grid and exterior candidate grid, the sub-cell lists of
+ * crowded octree leaves, the empty octree nodes' distance to the nearest primitive box -- run as HIP kernels
+ * (csrc/rm_scene_build.hip) that repeat the host's binary64 arithmetic operation for operation; trees, leaf grid and cell
+ * table stay on the host.  A table whose lists would reach 2^24 entries (there the host's rule depends on the order of
+ * the cells), or whose device build fails, is built by the host loop instead: same bytes.  device_build = 0, or a host-only
+ * context: the host builder for everything.  The upload entries never read the option.
+ * Synchronises the device like every scene upload.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics, and leaves rm_last_kernel's answer and rm_scene_set_time's value alone. */
+typedef enum rm_edit_op { RM_EDIT_SET = 0, RM_EDIT_INSERT = 1, RM_EDIT_REMOVE = 2 } rm_edit_op;
+typedef struct rm_sphere_edit {   /* 32 bytes */
+    int32_t op;          /* rm_edit_op */
+    int32_t index;       /* object index at the moment this edit applies */
+    float   center[3];   /* SET, INSERT; ignored by REMOVE */
+    int32_t reserved;    /* 0 */
+    double  radius;      /* SET, INSERT; a double, as rm_scene_from_spheres takes it */
+} rm_sphere_edit;
+RM_API int rm_scene_edit_spheres(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits);
+
 /* General primitives: Sphere / Box / Torus with any world->local matrix
  * (primitives/sphere.ts, box.ts, torus.ts; Primitive.sdf primitive.ts:33-39). */
 typedef enum rm_prim_type { RM_PRIM_SPHERE = 0, RM_PRIM_BOX = 1, RM_PRIM_TORUS = 2 } rm_prim_type;
@@ -781,6 +817,11 @@ RM_API int rm_selftest_hypot(rm_ctx *ctx, const float *xyz, int64_t n, double *o
  * fn 0 sin, 1 cos, 2 atan2(a, b), 3 asin, 4 log, 5 pow(a, b), 6 round, 7 atan; b may be NULL. */
 RM_API int rm_selftest_jsmath(rm_ctx *ctx, int32_t fn, const double *a, const double *b, int64_t n, double *out);
 
+/* V8 Math.hypot of n binary64 triples (xyz f64[3n]) as the scene builders evaluate it for BoundingBox.distanceTo
+ * (boundingBox.ts:46): on_device 0 = the host builder's own function (works on a host-only context), 1 = the device
+ * builder's (csrc/rm_scene_build.hip, hypot3_f64).  The two agree bit for bit. */
+RM_API int rm_selftest_hypot64(rm_ctx *ctx, const double *xyz, int64_t n, int32_t on_device, double *out);
+
 /* Device check of the shared-reciprocal division used by the v2 kernel's sphere SDF: evaluates
  * Math.hypot with the compiler's IEEE divisions and with the shared reciprocal on n generated
  * binary32 triples (zeros, denormals, equal magnitudes included) and counts bitwise mismatches. */
@@ -821,6 +862,13 @@ RM_API int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32);
 /* The item durations (units of 2.56 us, one byte per work item: 64 queues x 4096 slots) the last v2 launch recorded for the
  * longest-first order of the next one (option lpt); scripts/lpt_costs.py. */
 RM_API int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n);
+/* One table of the active scene, for tests of the scene builders: `name` is a scene array as csrc/rm_api.cpp lists them
+ * (RM_SCENE_ARRAYS: spheres, radii, bvh, bvh_prims, oct, oct_prims, pq_cells, pq_list, nn_cells, nn_list, prims, prog,
+ * obj_ranges, oct_recs, oct_lut, oct_sub_hdr, oct_sub_list, slot_object, ext_cells, ext_list).  *bytes always receives the
+ * array's size; the bytes are copied to `out` only if cap holds them.  from_device != 0: the device copy, read after a device
+ * synchronise (RM_E_NO_DEVICE on a host-only context); 0: the host builder's copy.  RM_E_INVALID for an unknown name,
+ * RM_E_NO_SCENE before any scene. */
+RM_API int rm_debug_scene_table(rm_ctx *ctx, const char *name, int32_t from_device, void *out, int64_t cap, int64_t *bytes);
 /* Option min_fill (below), for tests and evidence.  rm_debug_launch_fill: *effective = the workgroups per CU a v2 launch
  * brings when blocks_per_cu is `asked` (1..8), with the context's min_fill and queue count; works on a host-only context.
  * rm_debug_last_launch: the last launch of the v2 wave loop -- out[0] workgroups, out[1] threads per workgroup, out[2]
@@ -846,6 +894,8 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *   nodes_in_lds 0|1 scene tables staged in LDS (v2)                        list_cap 1..64 hit-leaf list entries per ray (v2)
  *   grid 0|1 leaf grid for BVH.getPrimitivesAt (v2)                         nn 0|1|2 nearest-candidate grid off|on|auto
  *   ext 0|1       BVH (v2): all-primitive evaluations outside the root box scan the exterior candidate grid's cell list (default 1)
+ *   device_build 0|1  rm_scene_edit_spheres: the pair loops of the scene build on the device (default 1; 0: the host builder
+ *                 for everything -- the A/B baseline; same tables either way; never read by the upload entries)
  *   recs, lut, sub 0|1 octree: leaf-ordered records, findNode cell table, sub-cell candidate lists
  *   blocks_per_cu 1..8, refill 1..64, hw_xcd 0|1, item_px 64|128|256       persistent-kernel scheduling (v2)
  *   static 0..95 percent of every tile queue assigned to the waves without atomics (v2; for overlapping frames)

@@ -16,6 +16,8 @@
 const path = require('path');
 const native = require(path.join(__dirname, '..', 'build', 'rm_addon.node'));
 
+const RM_SCENE_UPLOADED = -2147483648; // include/rm_raymarch.h: the scene last uploaded or edited
+
 let created = false;
 function ensure(device) {
   if (!created) {
@@ -46,6 +48,23 @@ class Scene { // util/scene.ts
     this.currentPresetIndex = 0;
   }
   loadPreset(index) { this.currentPresetIndex = Math.max(0, Math.min(index, 18)); }
+  // Object CRUD on sphere scenes (the reference README's third plan; rm_scene_edit_spheres): edits is a list of
+  // { op: 'set' | 'insert' | 'remove', index, center: [x, y, z], radius } applied in order to the scene's sphere list, indices in
+  // object order at the moment each edit applies.  The scene (preset 0..4, or one edited before) is the uploaded scene
+  // afterwards: jobs select it with scenePresetIndex = RM_SCENE_UPLOADED, which currentPresetIndex then holds.  All or nothing.
+  editSpheres(edits) {
+    const ops = new Int32Array(2 * edits.length), spheres = new Float64Array(4 * edits.length);
+    edits.forEach((e, i) => {
+      ops[2 * i] = { set: 0, insert: 1, remove: 2 }[e.op];
+      ops[2 * i + 1] = e.index;
+      spheres.set([...(e.center || [0, 0, 0]), e.radius === undefined ? 0 : e.radius], 4 * i);
+    });
+    check(native.editSpheres(this.currentPresetIndex, this.accelerationStructure, ops, spheres));
+    if (edits.length) this.currentPresetIndex = RM_SCENE_UPLOADED;
+  }
+  setSphere(index, center, radius) { this.editSpheres([{ op: 'set', index, center, radius }]); }
+  insertSphere(index, center, radius) { this.editSpheres([{ op: 'insert', index, center, radius }]); }
+  removeSphere(index) { this.editSpheres([{ op: 'remove', index }]); }
 }
 
 class Raymarcher { // cpu_algorithms/raymarcher.ts:19-57

@@ -239,6 +239,59 @@ napi_value CompareFrames(napi_env env, napi_callback_info info) {
     return make_int(env, rm_compare_frames(g_ctx, v[0], v[1], v[2], &sets[0], &sets[1], v[3], v[4], rgba, static_cast<rm_compare_stats *>(stats)));
 }
 
+// editSpheres(presetIndex, accelerationStructure, ops, spheres) -> status   (rm_scene_edit_spheres)
+// Makes the scene a job with (presetIndex, accelerationStructure) would render the active one (RM_SCENE_UPLOADED: the scene
+// edited before) and applies the edits to it: ops an Int32Array of (op, index) pairs, spheres a Float64Array of (x, y, z,
+// radius) per edit (ignored by REMOVE).  Afterwards jobs select the edited scene with scenePresetIndex = RM_SCENE_UPLOADED.
+napi_value EditSpheres(napi_env env, napi_callback_info info) {
+    size_t argc = 4;
+    napi_value a[4];
+    napi_get_cb_info(env, info, &argc, a, nullptr, nullptr);
+    Addon *ad = addon_of(env);
+    rm_ctx *g_ctx = ad ? ad->ctx : nullptr;
+    if (!g_ctx || argc < 4) return make_int(env, RM_E_INVALID);
+    int32_t preset = 0;
+    napi_get_value_int32(env, a[0], &preset);
+    char accel[64];
+    size_t len = 0;
+    if (napi_get_value_string_utf8(env, a[1], accel, sizeof accel, &len) != napi_ok) accel[0] = 0;
+    size_t ops_bytes = 0, sph_bytes = 0;
+    const int32_t *ops = static_cast<const int32_t *>(typed(env, a[2], &ops_bytes));
+    const double *sph = static_cast<const double *>(typed(env, a[3], &sph_bytes));
+    const size_t n = ops_bytes / 8;
+    if ((n && (!ops || !sph)) || ops_bytes % 8 || sph_bytes != 32 * n || n > 0x7FFFFFFF) return make_int(env, RM_E_INVALID);
+    if (preset != RM_SCENE_UPLOADED) {
+        const int rc = rm_scene_from_preset(g_ctx, preset, rm_accel_from_string(accel));
+        if (rc) return make_int(env, rc);
+    }
+    std::string edits(n * sizeof(rm_sphere_edit), '\0');
+    rm_sphere_edit *e = reinterpret_cast<rm_sphere_edit *>(&edits[0]);
+    for (size_t i = 0; i < n; ++i) {
+        e[i].op = ops[2 * i];
+        e[i].index = ops[2 * i + 1];
+        for (int k = 0; k < 3; ++k) e[i].center[k] = static_cast<float>(sph[4 * i + k]);
+        e[i].reserved = 0;
+        e[i].radius = sph[4 * i + 3];
+    }
+    return make_int(env, rm_scene_edit_spheres(g_ctx, n ? e : nullptr, static_cast<int32_t>(n)));
+}
+
+// sceneInfo() -> {nPrims, presetIndex, accel} | status   (rm_scene_get_info)
+napi_value SceneInfo(napi_env env, napi_callback_info) {
+    Addon *ad = addon_of(env);
+    rm_ctx *g_ctx = ad ? ad->ctx : nullptr;
+    if (!g_ctx) return make_int(env, RM_E_INVALID);
+    rm_scene_info si;
+    const int rc = rm_scene_get_info(g_ctx, &si);
+    if (rc) return make_int(env, rc);
+    napi_value out;
+    napi_create_object(env, &out);
+    napi_set_named_property(env, out, "nPrims", make_int(env, si.n_prims));
+    napi_set_named_property(env, out, "presetIndex", make_int(env, si.preset_index));
+    napi_set_named_property(env, out, "accel", make_int(env, si.accel));
+    return out;
+}
+
 napi_value LastError(napi_env env, napi_callback_info) {
     napi_value out;
     Addon *ad = addon_of(env);
@@ -266,6 +319,9 @@ napi_value Init(napi_env env, napi_value exports) {
         // (not enumerable: Object.keys of the addon stays the worker's surface of raymarchWorker.ts; hosts reach it through
         // FrameComparison of native/host/raymarcher.js)
         {"compareFrames", nullptr, CompareFrames, nullptr, nullptr, nullptr, napi_default, nullptr},
+        // (likewise: Scene.editSpheres of native/host/raymarcher.js)
+        {"editSpheres", nullptr, EditSpheres, nullptr, nullptr, nullptr, napi_default, nullptr},
+        {"sceneInfo", nullptr, SceneInfo, nullptr, nullptr, nullptr, napi_default, nullptr},
     };
     napi_define_properties(env, exports, sizeof props / sizeof props[0], props);
     return exports;
