@@ -48,8 +48,22 @@ __shared__ unsigned int rm_cnt_s[32];
             atomicAdd(&rm_cnt_s[(i) + 16], n_);                                                    \
         }                                                                                          \
     }
+// why an in-round run of march steps (section M) ends: 0 the leaf set changed, 1 the point left the root box or met a crowded
+// cell, 2 the end of the BVH interval, 3 the runner-up came too close.  Executions at slot i, lanes at i + 4; added to
+// P.stamps[40 .. 47] (the first words of the wave-time block, which an RM_COUNTS build does not otherwise write).
+__shared__ unsigned int rm_cnt_e[8];
+#define RM_CNT_END(i)                                                                              \
+    {                                                                                              \
+        const unsigned int n_ = static_cast<unsigned int>(__popcll(__ballot(1)));                  \
+        const int l_ = static_cast<int>(__lane_id());                                              \
+        if (__builtin_amdgcn_readfirstlane(l_) == l_) {                                            \
+            atomicAdd(&rm_cnt_e[i], 1u);                                                           \
+            atomicAdd(&rm_cnt_e[(i) + 4], n_);                                                     \
+        }                                                                                          \
+    }
 #else
 #define RM_CNT(i) {}
+#define RM_CNT_END(i) {}
 #endif
 
 #include "rm_bvh_list.h"  // after RM_CNT: the diagnostic build counts the list scans too
@@ -395,7 +409,8 @@ __device__ __forceinline__ void scan_finish_uniform(BestScan &b, float rf) {
 struct NormalAux {
     int k1;
     float lb2;
-    uint32_t found;
+    uint32_t found;  // low half: primitives counted (all its users add it to the upper, wrapping half of `counters`); high half: how many of the
+                     // cell's listed leaves contain q (at most 254), or 0xFFFF when the leaves did not come from the cell's list (tree walk)
     float rho;       // every point within rho (per axis) of q lies in exactly those of the cell's LISTED leaves that q lies in (0: unknown)
     float rho_cell;  // every point within rho_cell (per axis) of q is covered by the leaf list of q's cell: the host grows every
                      // cell's list by 0.0101 (RM_NRM_DELTA and a margin), plus q's own distance to the faces of its cell
@@ -432,6 +447,7 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
     bool in_root = false;
     float rho = __builtin_inff();  // the leaf set is the same within rho of q (per axis): min |box_margin| over the root and the cell's leaves
     float rho_cell = 0.f;
+    uint32_t nleaf16 = 0xFFFF0000u;  // (leaves that contain q) << 16 when the cell's list gave them; 0xFFFF: not known as a count of listed leaves
     BestScan bs;
     bs.k1 = -1;
     bs.hi1 = bs.lb1 = bs.lb2 = __builtin_inff();
@@ -473,8 +489,13 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
                     const RmBvhNode node = S.nodes[lst[e]];
                     const float m = box_margin(node.lo, node.hi, q);
                     rho = __builtin_fminf(rho, __builtin_fabsf(m));
-                    if (m >= 0.f) scan_leaf(node);
+                    if (m >= 0.f) {
+                        scan_leaf(node);
+                        found += 0x10000u;  // how many leaves contain q, beside their primitive count (see NormalAux::found)
+                    }
                 }
+                nleaf16 = found & 0xFFFF0000u;
+                found &= 0xFFFFu;
             }
         }
     }
@@ -573,7 +594,7 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
     {   // the value came from sphere k1 alone, every other candidate of the leaf set (the same within rho) is at least lb2 away
         aux->k1 = bs.k1;
         aux->lb2 = bs.lb2;
-        aux->found = found;
+        aux->found = (found & 0xFFFFu) | nleaf16;
         aux->rho = rho;
         aux->rho_cell = rho_cell;
         aux->ok = need && in_root && found > 0 && bs.k1 >= 0 && !redo;
@@ -1121,6 +1142,7 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
 #endif
 #ifdef RM_COUNTS
     if (threadIdx.x < 32) rm_cnt_s[threadIdx.x] = 0;
+    if (threadIdx.x < 8) rm_cnt_e[threadIdx.x] = 0;
     __syncthreads();
 #endif
     for (;;) {
@@ -1419,34 +1441,75 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
         // the slowest rays of a batch set its number of rounds.  The next step is taken HERE, by the lane alone, when
         //  * the march goes on (trip count, epsilon and MAX_DIST tests as the loop makes them) and the point's parameter
         //    lies inside the current interval, so that onRayMarchStep answers 0 without touching its state;
-        //  * the new point p2 is within rho of this round's point q (distance measured between the two binary32 points,
-        //    rounded up), rho being the stability radius of the leaf set (box_margin of every leaf the cell lists, and not
-        //    beyond what that list covers: the cell grown by 0.0100): getPrimitivesAt returns the same leaves, the counter
-        //    advances by the same `found`;
-        //  * every other candidate, at least lb2 away at q and 1-Lipschitz, is still farther at p2 than the exact
-        //    distance of the sphere k1 that won at q: Math.min over the candidates is that distance.
+        //  * the leaves that contain the new point p2 are those that contained this round's point q.  The test is the exact one:
+        //    p2 lies in the root box, its cell -- found by the very expressions and clamps of bvh_distance_wave, in the same
+        //    tables -- is not a crowded one, and of the leaves that cell lists those with box_margin(leaf, p2) >= 0, the set B
+        //    the ordinary path would scan at p2, all contain q and are as many as the listed leaves A that contained q (their
+        //    number comes in the upper half of aux.found).  Every leaf that contains q is listed by q's cell, so the members
+        //    of B are members of A, and equal counts make the sets equal: no signature, no assumption on the order of a list,
+        //    and p2 may lie in another cell than q.  getPrimitivesAt returns the same leaves, the counter advances by the
+        //    same `found`.  (Until round 8 the test was a ball around q -- the smallest box_margin of the listed leaves and
+        //    the distance to the grown cell's faces -- which ended 3.2 runs per pixel of C3 where the set changes 0.2 times);
+        //  * every other candidate, at least lb2 away at q and 1-Lipschitz, is still farther at p2 (at most dd from q: the
+        //    distance between the two binary32 points, rounded up) than the exact distance of the sphere k1 that won at q:
+        //    Math.min over the candidates, those of an equal leaf set, is that distance.
         // The step is then exactly the one the ordinary path would take (same point, same value, same counters); a lane
         // that fails a test has committed nothing of that step and takes it in the next round.
         if (ACCEL == 2 && CB.multi_step) {
-            const bool go = was_marching && aux.ok && (st & ST_PHASE) == PH_MARCH;
+            const bool go = was_marching && aux.ok && (aux.found >> 16) != 0xFFFFu && (st & ST_PHASE) == PH_MARCH;
             if (__any(go)) {
                 if (go) {
-                    const SceneView SM = scene_view<ACCEL, LDS, REL>(cold_params(), smem);
+                    const RmRenderParams CM = cold_params();
+                    const SceneView SM = scene_view<ACCEL, LDS, REL>(CM, smem);
                     const RmSphere s1 = SM.spheres[aux.k1];
                     const double r1 = SM.radii[aux.k1];
-                    const float rho = __builtin_fminf(aux.rho, aux.rho_cell);
                     for (;;) {
                         if ((st & ST_TRIP_MASK) >= (RM_MAX_STEPS << ST_TRIP_SHIFT)) {  // loop exhausted: return totalDist
                             finish_march(t);
                             break;
                         }
-                        if (t < sA || t > sB) break;  // the interval state machine has work to do: the ordinary path
+                        if (t < sA || t > sB) {  // the interval state machine has work to do: the ordinary path
+                            RM_CNT_END(2)
+                            break;
+                        }
                         const Vec3f p2 = point_at(ray, t);
+                        {   // the leaves that contain p2, as bvh_distance_wave finds them, against those that contained q
+                            const RmBvhNode root = SM.nodes[0];
+                            bool same = box_margin(root.lo, root.hi, p2) >= 0.f;
+                            uint32_t cell = 255u;
+                            if (same) {
+                                const float gx = (p2.x - CM.pq_origin[0]) * CM.pq_inv[0], gy = (p2.y - CM.pq_origin[1]) * CM.pq_inv[1], gz = (p2.z - CM.pq_origin[2]) * CM.pq_inv[2];
+                                const int cx = min(max(static_cast<int>(gx), 0), CM.pq_dim[0] - 1);
+                                const int cy = min(max(static_cast<int>(gy), 0), CM.pq_dim[1] - 1);
+                                const int cz = min(max(static_cast<int>(gz), 0), CM.pq_dim[2] - 1);
+                                cell = SM.pq_cells[(cz * CM.pq_dim[1] + cy) * CM.pq_dim[0] + cx];
+                            }
+                            const int ccnt = static_cast<int>(cell & 0xFFu);
+                            if (ccnt == 255) {  // outside the root box, or a crowded cell (the tree walk)
+                                RM_CNT_END(1)
+                                break;
+                            }
+                            const uint16_t *lst = SM.pq_list + (cell >> 8);
+                            uint32_t left = aux.found >> 16;  // leaves of q's set not yet met at p2
+                            for (int k = 0; k < ccnt; ++k) {
+                                const RmBvhNode node = SM.nodes[lst[k]];
+                                if (box_margin(node.lo, node.hi, p2) >= 0.f) {
+                                    same = same && box_margin(node.lo, node.hi, q) >= 0.f;
+                                    left -= 1u;
+                                }
+                            }
+                            if (!same || left != 0u) {
+                                RM_CNT_END(0)
+                                break;
+                            }
+                        }
                         const float ex = p2.x - q.x, ey = p2.y - q.y, ez = p2.z - q.z;
                         const float dd = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) * 1.00001f + 1e-7f;  // >= |p2 - q|
-                        if (!(dd < rho)) break;
                         const double e = sphere_sdf_fast(s1, r1, p2);
-                        if (!(aux.lb2 - dd > f32_upper_bound(e))) break;
+                        if (!(aux.lb2 - dd > f32_upper_bound(e))) {
+                            RM_CNT_END(3)
+                            break;
+                        }
                         RM_CNT(15)
                         st += 1 << ST_TRIP_SHIFT;
                         counters += (aux.found << 16) + 1u;
@@ -1512,6 +1575,7 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
 #ifdef RM_COUNTS
     __syncthreads();
     if (threadIdx.x < 32 && P.stamps) atomicAdd(&P.stamps[8 + threadIdx.x], static_cast<unsigned long long>(rm_cnt_s[threadIdx.x]));
+    if (threadIdx.x < 8 && P.stamps) atomicAdd(&P.stamps[40 + threadIdx.x], static_cast<unsigned long long>(rm_cnt_e[threadIdx.x]));
 #endif
 }
 

@@ -27,6 +27,8 @@ it = torch.zeros(W * H, dtype=torch.int16, device=dev)
 rg = torch.zeros(4 * W * H, dtype=torch.uint8, device=dev)
 out = np.zeros(32, np.uint64)
 N.lib().rm_debug_read_counts(ctx._h, out.ctypes.data_as(C.c_void_p))
+ends = np.zeros(3 * 8192, np.uint64)
+N.lib().rm_debug_read_wave_times(ctx._h, ends.ctypes.data_as(C.c_void_p))  # (a read zeroes the block)
 R.SphereTracer().runRaymarcher(sc, d, nb, s, it, W, H, 0.0, shadedBuffer=rg, shader="iteration-heatmap")
 torch.cuda.synchronize()
 N.lib().rm_debug_read_counts(ctx._h, out.ctypes.data_as(C.c_void_p))
@@ -37,4 +39,9 @@ names = ["wave-loop iteration", "R refill section", "A march-step bookkeeping pa
 print("%-32s %12s %14s %6s %10s" % ("event", "wave execs", "lanes", "util", "lanes/px"))
 for i, n in enumerate(names):
     w, l = int(out[i]), int(out[i + 16])
+    print("%-32s %12d %14d %5.1f%% %10.2f" % (n, w, l, 100.0 * l / (64.0 * w) if w else 0.0, l / float(W * H)))
+# why an in-round run of march steps ends (RM_CNT_END of rm_render_v2.hip: the first eight words of the wave-time block)
+N.lib().rm_debug_read_wave_times(ctx._h, ends.ctypes.data_as(C.c_void_p))
+for i, n in enumerate(["M run ends: leaf set changed", "M run ends: root box / crowded", "M run ends: BVH interval", "M run ends: runner-up"]):
+    w, l = int(ends[i]), int(ends[i + 4])
     print("%-32s %12d %14d %5.1f%% %10.2f" % (n, w, l, 100.0 * l / (64.0 * w) if w else 0.0, l / float(W * H)))

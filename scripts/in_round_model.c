@@ -1,0 +1,267 @@
+/* CPU model of the in-round march steps of the v2 wave loop (rm_render_v2.hip, section M) on C3: the Dense Sphere Grid
+ * under the golden camera at 3840 x 2160, BVH.  It traces rays with the project's own C oracle, splits every ray's
+ * sequence of getDistance evaluations into rounds of the wave loop and in-round steps by section M's rules, and prints
+ * what each rule for "the leaf set at the new point is the round's" costs: lane rounds per pixel, and per 64-pixel
+ * batch the wave's rounds and in-round trips, with the reasons an in-round run ends.
+ *
+ *   build:  mkdir -p scripts/bin && gcc -O2 -std=c11 -ffp-contract=off -fno-fast-math -fexcess-precision=standard \
+ *               -o scripts/bin/in_round_model scripts/in_round_model.c -lm      (from the repository's root)
+ *   run:    scripts/bin/in_round_model            (a few seconds; no GPU)
+ *
+ * The model: lanes are grouped into 8 x 8 pixel batches; a wave's rounds are the maximum over its lanes, its in-round
+ * trips in its r-th round the maximum over its lanes' r-th rounds.  Every sixth batch in both directions over the whole
+ * frame: 3 600 batches.  Refill, the deferred normals (0.30 rounds per pixel) and the binary32 lower bound of the
+ * runner-up (the exact runner-up is used) are not modelled.  "today" is the rule before round 8 (a ball around the
+ * round's point); its three figures are to be held against scripts/counts.py on a -DRM_COUNTS build. */
+#include <stdio.h>
+
+#include "../oracle/rm_oracle.c"
+
+#define W_ 3840
+#define H_ 2160
+#define MAXL 64
+#define MAXSTEP 100
+
+typedef struct {
+    double t, d, second, enter, exit_;
+    float p[3];
+    unsigned long long set; /* leaves whose box contains p */
+    int k1;
+} Step;
+
+static BBox leaf_box[MAXL];
+static const BVHNode *leaf_node[MAXL];
+static int n_leaf;
+static BBox root_box;
+static int G;                 /* cells per axis */
+static float g_org[3], g_inv[3];
+static double g_cell[3];
+
+static void collect(const BVHNode *n) {
+    if (!n->left && !n->right) {
+        if (n_leaf >= MAXL) { fprintf(stderr, "more than %d leaves\n", MAXL); exit(1); }
+        leaf_box[n_leaf] = n->bounds;
+        leaf_node[n_leaf++] = n;
+        return;
+    }
+    if (n->left) collect(n->left);
+    if (n->right) collect(n->right);
+}
+
+/* rm_render_v2.hip box_margin */
+static float margin(const BBox *b, const float *p) {
+    float m = p[0] - b->min[0];
+    for (int k = 0; k < 3; k++) {
+        float a = p[k] - b->min[k], c = b->max[k] - p[k];
+        if (a < m) m = a;
+        if (c < m) m = c;
+    }
+    return m;
+}
+
+static void cell_of(const float *p, int *c, float *g) {
+    for (int k = 0; k < 3; k++) {
+        g[k] = (p[k] - g_org[k]) * g_inv[k];
+        int i = (int)g[k];
+        c[k] = i < 0 ? 0 : i > G - 1 ? G - 1 : i;
+    }
+}
+
+/* build_point_query_grid's rule with the lists grown by `grow` (the product: 0.0100, and 0.0001 on top) */
+static int listed(int leaf, const int *c, double grow) {
+    for (int k = 0; k < 3; k++) {
+        double a = ((double)leaf_box[leaf].min[k] - (grow + 0.0001) - (double)g_org[k]) * (double)g_inv[k] - 0.01;
+        double b = ((double)leaf_box[leaf].max[k] + (grow + 0.0001) - (double)g_org[k]) * (double)g_inv[k] + 0.01;
+        int c0 = (int)floor(a), c1 = (int)floor(b);
+        c0 = c0 < 0 ? 0 : c0 > G - 1 ? G - 1 : c0;
+        c1 = c1 < 0 ? 0 : c1 > G - 1 ? G - 1 : c1;
+        if (c[k] < c0 || c[k] > c1) return 0;
+    }
+    return 1;
+}
+
+static int trace(const ro_scene *s, const float *o, const float *dir, Scratch *sc, Step *st) {
+    int n = 0;
+    double total = 0;
+    AccelState as;
+    if (!accel_start(s, o, dir, sc, &as)) return 0;
+    for (int i = 0; i < 100; i++) {
+        float p[3];
+        vec3_scaleAndAdd(p, o, dir, total);
+        double skip = accel_step(s, o, dir, total, sc, &as);
+        if (skip == -1) break;
+        if (skip > 0) {
+            total += skip;
+            if (total > MAX_DIST) break;
+            continue;
+        }
+        Step *e = &st[n++];
+        e->t = total;
+        memcpy(e->p, p, sizeof p);
+        e->enter = sc->intervals[as.curIdx].tEnter;
+        e->exit_ = sc->intervals[as.curIdx].tExit;
+        e->set = 0;
+        e->k1 = -1;
+        double best = 1e300, second = 1e300;
+        for (int l = 0; l < n_leaf; l++)
+            if (margin(&leaf_box[l], p) >= 0.f) {
+                e->set |= 1ull << l;
+                for (int j = 0; j < leaf_node[l]->nprims; j++) {
+                    int id = leaf_node[l]->prims[j];
+                    double v = prim_sdf(&s->prims[id], p);
+                    if (v < best) { second = best; best = v; e->k1 = id; }
+                    else if (v < second) second = v;
+                }
+            }
+        uint32_t cnt = 0;
+        double dist = scene_get_distance(s, p, &cnt, sc);
+        e->d = dist;
+        e->second = second;
+        total += dist;
+        if (dist < EPSILON) break;
+        if (total > MAX_DIST) break;
+    }
+    return n;
+}
+
+typedef struct {
+    const char *name;
+    int exact;      /* 0: the ball of rho and rho_cell; 1: the exact leaf set at p2 */
+    double grow;    /* ball: how far the cell lists are grown */
+    double confine; /* exact: p2 stays within q's cell grown by this; < 0: anywhere in the root box */
+} Rule;
+
+enum { END_SET, END_CELL, END_INTERVAL, END_RUNNER, N_END };
+
+/* may step j be taken in the round whose point is step h?  returns -1, or the reason it may not */
+static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e) {
+    if (e->t < h->enter || e->t > h->exit_) return END_INTERVAL;
+    float ex = e->p[0] - h->p[0], ey = e->p[1] - h->p[1], ez = e->p[2] - h->p[2];
+    float dd = sqrtf(ex * ex + ey * ey + ez * ez) * 1.00001f + 1e-7f;
+    int c[3];
+    float g[3];
+    cell_of(h->p, c, g);
+    if (!r->exact) {
+        float rho = margin(&root_box, h->p);
+        for (int l = 0; l < n_leaf; l++)
+            if (listed(l, c, r->grow)) {
+                float m = fabsf(margin(&leaf_box[l], h->p));
+                if (m < rho) rho = m;
+            }
+        double in_cell = 1e30;
+        for (int k = 0; k < 3; k++) {
+            double f = g[k] - (float)c[k];
+            double v = (f < 1.0 - f ? f : 1.0 - f) * g_cell[k];
+            if (v < in_cell) in_cell = v;
+        }
+        float rho_cell = (float)(r->grow + (in_cell > 0 ? in_cell : 0));
+        if (!(dd < (rho < rho_cell ? rho : rho_cell))) return rho < rho_cell ? END_SET : END_CELL; /* whichever radius binds */
+    } else {
+        if (r->confine >= 0)
+            for (int k = 0; k < 3; k++) {
+                double lo = (double)g_org[k] + c[k] * g_cell[k] - r->confine, hi = (double)g_org[k] + (c[k] + 1) * g_cell[k] + r->confine;
+                if (e->p[k] < lo || e->p[k] > hi) return END_CELL;
+            }
+        if (margin(&root_box, e->p) < 0.f || e->set != h->set) return END_SET;
+    }
+    double v = prim_sdf(&s->prims[h->k1], e->p);
+    if (!((float)h->second - dd > (float)(v * (1 + 1e-6)))) return END_RUNNER;
+    return -1;
+}
+
+int main(void) {
+    ro_scene *s = ro_scene_from_preset(3, "BVH");
+    if (!s || !s->bvh) return 1;
+    collect(s->bvh);
+    root_box = s->bvh->bounds;
+    G = (int)ceil(cbrt((double)n_leaf) * 3.0);
+    G = G < 2 ? 2 : G > 32 ? 32 : G;
+    for (int k = 0; k < 3; k++) {
+        double ext = (double)root_box.max[k] - (double)root_box.min[k];
+        g_org[k] = root_box.min[k];
+        g_inv[k] = (float)(G / ext);
+        g_cell[k] = 1.0 / (double)g_inv[k];
+    }
+    const Rule rules[] = {
+        {"today: ball of rho, rho_cell", 0, 0.0100, 0},
+        {"exact set, p2 in q's cell + 0.0100", 1, 0, 0.0100},
+        {"exact set, p2 in q's cell + 0.24", 1, 0, 0.24},
+        {"exact set, p2's own cell", 1, 0, -1},
+        {"ball kept, lists grown by 0.06", 0, 0.06, 0},
+        {"ball kept, lists grown by 0.24", 0, 0.24, 0},
+    };
+    enum { NR = sizeof rules / sizeof rules[0] };
+    double lane_rounds[NR] = {0}, lane_steps[NR] = {0}, wave_rounds[NR] = {0}, wave_trips[NR] = {0}, ends[NR][N_END] = {{0}};
+    long batches = 0, pixels = 0;
+
+    float rot[9];
+    const float *ct = s->cameraTransform;
+    rot[0] = ct[0]; rot[1] = ct[1]; rot[2] = ct[2]; rot[3] = ct[4]; rot[4] = ct[5]; rot[5] = ct[6]; rot[6] = ct[8]; rot[7] = ct[9]; rot[8] = ct[10];
+    float org[3] = {ct[12], ct[13], ct[14]};
+    Scratch sc;
+    sc.cand = (int *)malloc((size_t)s->n * sizeof(int));
+    sc.intervals = (Interval *)malloc((size_t)s->bvh_leaves * sizeof(Interval));
+    sc.stack = (const BVHNode **)malloc((size_t)s->bvh_nodes * sizeof(BVHNode *));
+    static Step st[MAXSTEP];
+    static int trips[NR][64][MAXSTEP]; /* in-round trips of lane l's r-th round */
+    static int rounds[NR][64];
+
+    for (int by = 0; by < H_ / 8; by += 6)
+        for (int bx = 0; bx < W_ / 8; bx += 6) {
+            batches++;
+            for (int l = 0; l < 64; l++) {
+                int x = bx * 8 + (l & 7), y = by * 8 + (l >> 3);
+                double u = ((double)x / W_ - 0.5) * 2.0, v = ((double)y / H_ - 0.5) * 2.0;
+                float dir[3] = {f32(u), f32(v), -1.0f};
+                vec3_transformMat3(dir, dir, rot);
+                vec3_normalize(dir, dir);
+                int n = trace(s, org, dir, &sc, st);
+                pixels++;
+                for (int r = 0; r < NR; r++) {
+                    int nr = 0, h = 0;
+                    for (int j = 0; j < n; j++) {
+                        int in_round = 0;
+                        if (j > 0) {
+                            const Step *q = &st[h];
+                            /* aux.ok: leaves found, a winner, and no near tie with the runner-up */
+                            int ok = q->set != 0 && q->k1 >= 0 && (float)q->second > (float)(q->d * (1 + 1e-6));
+                            if (ok) {
+                                int why = refuse(s, &rules[r], q, &st[j]);
+                                if (why < 0) in_round = 1;
+                                else ends[r][why] += 1;
+                            }
+                        }
+                        if (in_round) {
+                            trips[r][l][nr - 1]++;
+                            lane_steps[r] += 1;
+                        } else {
+                            h = j;
+                            trips[r][l][nr++] = 0;
+                            lane_rounds[r] += 1;
+                        }
+                    }
+                    rounds[r][l] = nr;
+                }
+            }
+            for (int r = 0; r < NR; r++) {
+                int wr = 0;
+                for (int l = 0; l < 64; l++)
+                    if (rounds[r][l] > wr) wr = rounds[r][l];
+                wave_rounds[r] += wr;
+                for (int k = 0; k < wr; k++) {
+                    int m = 0;
+                    for (int l = 0; l < 64; l++)
+                        if (k < rounds[r][l] && trips[r][l][k] > m) m = trips[r][l][k];
+                    wave_trips[r] += m;
+                }
+            }
+        }
+    printf("%d leaves, leaf grid %d^3, %ld batches of 64 pixels\n", n_leaf, G, batches);
+    printf("%-38s %12s %12s %12s %12s   %s\n", "rule for continuing in M", "rounds/px", "steps/px", "wave rnd/b", "wave M/b", "run enders / px (set, cell, interval, runner-up)");
+    for (int r = 0; r < NR; r++)
+        printf("%-38s %12.2f %12.2f %12.2f %12.2f   %.2f / %.2f / %.2f / %.2f\n", rules[r].name, lane_rounds[r] / pixels, lane_steps[r] / pixels,
+               wave_rounds[r] / batches, wave_trips[r] / batches, ends[r][END_SET] / pixels, ends[r][END_CELL] / pixels,
+               ends[r][END_INTERVAL] / pixels, ends[r][END_RUNNER] / pixels);
+    ro_scene_free(s);
+    return 0;
+}
