@@ -16,6 +16,6 @@ from .host import (ALGORITHMS, SHADERS, AdaptiveStep, AdaptiveStepV2, AdaptiveSt
                    IterationHeatmap, Job, NormalModel, PhongModel, RangedIterationHeatmap, RangedSDFHeatmap, Raymarcher,
                    RaymarchWorker, Result, Scene,
                    SDFHeatmap, ShadingModel, SphereTracer, createRaymarcher, createShadingModelFromValue,
-                   diagnostics, renderFrame)
+                   diagnostics, renderFrame, save_obj)
 
 __all__ = [n for n in dir() if not n.startswith("_")]

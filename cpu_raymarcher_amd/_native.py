@@ -87,6 +87,13 @@ class rm_field_shade(C.Structure):  # include/rm_raymarch.h: struct rm_field_sha
 FIELD_MAPS = {"distance": 0, "count": 1}
 
 
+class rm_mesh_info(C.Structure):  # include/rm_raymarch.h: struct rm_mesh_info
+    _fields_ = [("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("n_holes", C.c_int64), ("reserved", C.c_int64)]
+
+
+RM_MESH_F64, RM_MESH_F32 = 0, 1
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -190,6 +197,8 @@ SIGNATURES = {
     "rm_lattice_points": (C.c_int, [C.POINTER(rm_lattice), C.c_int64, C.c_int64, _VP]),
     "rm_shade_field_device": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP, _VP]),
     "rm_shade_field": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP]),
+    "rm_mesh_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
+    "rm_scene_mesh": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rm_mesh_info)]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

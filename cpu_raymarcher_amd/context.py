@@ -792,6 +792,81 @@ class Context:
         N.check(self._h, N.lib().rm_shade_field(self._h, C.byref(sh), values.size, _ptr(values), _ptr(rgba)))
         return rgba
 
+    # ---- meshes: the surface of a distance volume, extracted on the device ------------------
+    def mesh_field(self, values, origin, du, dv, dw, shape, iso=0.0, device=False, triangles=False):
+        """Surface nets over a volume the caller already holds (rm_mesh_field_device; the rule is in include/rm_raymarch.h):
+        `values` is a torch CUDA tensor or a numpy array of nu * nv * nw float64 or float32 values in the lattice's order
+        ([nw, nv, nu]); the surface is where they pass `iso` (inside: value < iso).  The counting call, an exact allocation
+        and the filling call, on torch's current stream.  Returns (vertices float32 [V, 3], quads uint32 [Q, 4]): one vertex
+        per cell the surface passes through, one quad per lattice edge that changes side, wound so that normals point out of
+        the inside -- the winding is flipped here when (du, dv, dw) is left-handed, which the C entry does not do.
+        triangles=True returns uint32 [2Q, 3] instead, each quad split (0, 1, 2), (0, 2, 3).  device=True returns torch CUDA
+        tensors (the indices an int32 tensor holding the u32 bits)."""
+        lat = make_lattice(origin, du, dv, dw, shape)
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        n = lat.nu * lat.nv * lat.nw
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        import torch
+        dev = torch.device("cuda", self.device)
+        if _is_torch(values):
+            if not (values.is_cuda and values.is_contiguous() and values.dtype in (torch.float64, torch.float32)):
+                raise ValueError("values must be a contiguous CUDA tensor of float64 or float32")
+            self._same_device(dict(values=values))
+        else:
+            a = np.ascontiguousarray(values)
+            values = torch.from_numpy(a if a.dtype == np.float32 else a.astype(np.float64, copy=False)).to(dev)
+        if values.numel() != n:
+            raise ValueError("values must hold nu * nv * nw = %d elements" % n)
+        vt = N.RM_MESH_F32 if values.dtype == torch.float32 else N.RM_MESH_F64
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), None, 0, None, 0, _ptr(info),
+                                                      _current_stream_ptr()))
+        n_vertices, n_quads = (int(x) for x in info.cpu()[:2])
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        quads = torch.empty((n_quads, 4), dtype=torch.int32, device=dev)
+        if n_vertices or n_quads:
+            N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), _ptr(vertices) if n_vertices else None,
+                                                          n_vertices, _ptr(quads) if n_quads else None, n_quads, _ptr(info), _current_stream_ptr()))
+        u, v, w = (np.array(list(getattr(lat, k)), np.float64) for k in ("du", "dv", "dw"))
+        if float(np.dot(u, np.cross(v, w))) < 0:
+            quads = quads[:, [0, 3, 2, 1]].contiguous()
+        faces = quads[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).contiguous() if triangles else quads
+        if device:
+            return vertices, faces
+        return vertices.cpu().numpy(), faces.cpu().numpy().view(np.uint32)
+
+    def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False):
+        """The surface of the active scene over a lattice: `field` samples Scene.getDistance on the device at `time` (float64,
+        once; the volume stays there) and `mesh_field` extracts the surface getDistance = iso from it.  Returns what
+        mesh_field returns.  The field under a BVH or an octree is the marchers' bound, not always the exact distance: an
+        offset surface (iso != 0) wants acceleration None."""
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
+        return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles)
+
+    def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None):
+        """`mesh` over an axis-aligned lattice of cells[0] x cells[1] x cells[2] cells that covers scene_info()'s root box
+        and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
+        `box` = (lo, hi) replaces the root box: a scene without a structure reports none."""
+        if box is None:
+            info = self.scene_info()
+            box = (info["root_min"], info["root_max"])
+        lo, hi = (np.asarray(b, np.float64).reshape(3) for b in box)
+        if not (hi > lo).all():
+            raise ValueError("the scene reports no root box (acceleration None): pass box=(lo, hi)")
+        c = np.array([int(x) for x in cells], np.int64)
+        if (c < 5).any():
+            raise ValueError("at least 5 cells per axis")
+        m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
+        step = (hi - lo + 2 * m) / c
+        return self.mesh(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c), iso=iso, time=time,
+                         device=device, triangles=triangles)
+
     def _same_device(self, bufs):
         for name, b in bufs.items():
             if b is not None and _is_torch(b) and b.is_cuda and b.device.index != self.device:

@@ -405,6 +405,7 @@ struct rm_ctx {
 
     void *scratch = nullptr;
     size_t scratch_bytes = 0;
+    hipEvent_t scratch_busy = nullptr;  // behind the last launches that read the scratch after their entry returned (Staging::keep)
     RmDiagDevice *d_diag = nullptr;
     float light[3] = {0, 0, 0};
 
@@ -1093,6 +1094,8 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // regions out in the order they are named, each 256-byte aligned, and returns their offsets; reserve() grows the scratch
 // once to hold them all (it never shrinks, and the device is synchronised before an old buffer is freed) and asks for 256
 // bytes at least, so at() is a device pointer even when every region is empty.  in / zero / out are enqueued.
+// An asynchronous entry (rm_mesh_field_device) reserves for the caller's stream and calls keep() behind its launches: whoever
+// reserves next, on whatever stream, waits on the device for them, so two users of the scratch never overlap.
 struct Staging {
     rm_ctx *ctx;
     size_t total = 0;
@@ -1101,7 +1104,9 @@ struct Staging {
         total += align_up(bytes, 256);
         return offset;
     }
-    int reserve() const {
+    int reserve() const { return reserve_for(ctx->stream); }
+    int reserve_for(hipStream_t user) const {
+        if (ctx->scratch_busy) RM_HIP(ctx, hipStreamWaitEvent(user, ctx->scratch_busy, 0));
         const size_t bytes = total ? total : 256;
         if (bytes <= ctx->scratch_bytes) return RM_OK;
         if (ctx->scratch) {
@@ -1120,6 +1125,13 @@ struct Staging {
     hipError_t zero(size_t offset, size_t bytes) const { return hipMemsetAsync(at<char>(offset), 0, bytes, ctx->stream); }
     hipError_t out(void *host, size_t offset, size_t bytes) const { return hipMemcpyAsync(host, at<char>(offset), bytes, hipMemcpyDeviceToHost, ctx->stream); }
     hipError_t sync() const { return hipStreamSynchronize(ctx->stream); }
+    hipError_t keep(hipStream_t user) const {
+        if (!ctx->scratch_busy) {
+            const hipError_t e = hipEventCreateWithFlags(&ctx->scratch_busy, hipEventDisableTiming);
+            if (e != hipSuccess) return e;
+        }
+        return hipEventRecord(ctx->scratch_busy, user);
+    }
 };
 
 int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
@@ -1696,6 +1708,76 @@ void fill_field(const rm_ctx *ctx, const rm_lattice *lat, RmRenderParams &p, RmF
     a.nv = static_cast<unsigned int>(lat->nv);
 }
 
+// ---- meshes: surface nets over a lattice of values (rm_mesh.hip)
+
+static_assert(sizeof(rm_mesh_info) == 32 && sizeof(RmMeshInfo) == sizeof(rm_mesh_info), "rm_mesh_info layout");
+static_assert(RM_MESH_F64 == 0 && RM_MESH_F32 == 1, "rm_launch_mesh reads these values");
+
+// What both mesh entries check, arguments first, each described once; *n receives the point count and *cells whether the
+// lattice has a cell (every count at least 2).  `values` null: the entry samples the scene itself (rm_scene_mesh) and needs one.
+struct MeshCall {
+    const rm_lattice *lattice;
+    bool own_values;  // rm_mesh_field_device: d_values and value_type are arguments
+    const void *values;
+    int32_t value_type;
+    double iso;
+    const void *vertices, *quads, *info;
+    int64_t cap_vertices, cap_quads;
+};
+
+int check_mesh(rm_ctx *ctx, const MeshCall &m, int64_t *n, bool *cells) {
+    if (const char *bad = lattice_error(m.lattice, n)) return fail(ctx, RM_E_INVALID, bad);
+    if (*n > (int64_t(1) << 30)) return fail(ctx, RM_E_INVALID, "more than 2^30 lattice points: the mesher does not split a volume");
+    *cells = m.lattice->nu >= 2 && m.lattice->nv >= 2 && m.lattice->nw >= 2;
+    if (!m.info) return fail(ctx, RM_E_INVALID, "null info");
+    if (!std::isfinite(m.iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (m.cap_vertices < 0 || m.cap_quads < 0) return fail(ctx, RM_E_INVALID, "negative capacity");
+    if ((m.cap_vertices > 0 && !m.vertices) || (m.cap_quads > 0 && !m.quads)) return fail(ctx, RM_E_INVALID, "null buffer with a capacity above 0");
+    if ((reinterpret_cast<uintptr_t>(m.vertices) | reinterpret_cast<uintptr_t>(m.quads)) & 3) return fail(ctx, RM_E_INVALID, "vertices and quads must be 4-byte aligned");
+    if (m.own_values) {
+        if (m.value_type != RM_MESH_F64 && m.value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
+        if (*cells && !m.values) return fail(ctx, RM_E_INVALID, "null values");
+        if (reinterpret_cast<uintptr_t>(m.values) & (m.value_type == RM_MESH_F64 ? 7 : 3)) return fail(ctx, RM_E_INVALID, "values must be aligned to their type");
+        if (reinterpret_cast<uintptr_t>(m.info) & 7) return fail(ctx, RM_E_INVALID, "info must be 8-byte aligned");
+    }
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
+    if (!m.own_values && !ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
+// The launch both entries share: `values` laid out by the lattice, outputs and info on the device, the map and the block totals
+// at their places in the reserved scratch.
+int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices,
+                void *d_quads, void *d_info, size_t o_map, size_t o_totals, hipStream_t stream) {
+    RmMeshArgs a;
+    std::memset(&a, 0, sizeof a);
+    for (int c = 0; c < 3; ++c) {
+        a.origin[c] = m.lattice->origin[c];
+        a.du[c] = m.lattice->du[c];
+        a.dv[c] = m.lattice->dv[c];
+        a.dw[c] = m.lattice->dw[c];
+    }
+    a.values = d_values;
+    a.iso = m.iso;
+    a.vertices = static_cast<float *>(d_vertices);
+    a.quads = static_cast<uint32_t *>(d_quads);
+    a.info = static_cast<RmMeshInfo *>(d_info);
+    a.map = st.at<uint32_t>(o_map);
+    a.totals = st.at<uint32_t>(o_totals);
+    a.n = n;
+    a.cap_vertices = m.cap_vertices;
+    a.cap_quads = m.cap_quads;
+    a.nu = static_cast<unsigned int>(m.lattice->nu);
+    a.nv = static_cast<unsigned int>(m.lattice->nv);
+    a.nw = static_cast<unsigned int>(m.lattice->nw);
+    a.n_blocks = static_cast<unsigned int>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK);
+    a.f32 = value_type == RM_MESH_F32;
+    RM_HIP(ctx, rm_launch_mesh(a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+size_t mesh_blocks(int64_t n) { return static_cast<size_t>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK); }
+
 int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const void *values, const void *rgba) {
     if (!sh || !values || !rgba) return fail(ctx, RM_E_INVALID, "null argument");
     if (n < 0) return fail(ctx, RM_E_INVALID, "negative count");
@@ -1787,6 +1869,7 @@ void rm_destroy(rm_ctx *ctx) {
         (void)hipDeviceSynchronize();
         free_device_scene(ctx);
         (void)hipFree(ctx->scratch);
+        if (ctx->scratch_busy) (void)hipEventDestroy(ctx->scratch_busy);
         (void)hipFree(ctx->d_diag);
         (void)hipFree(ctx->d_stamps);
         for (auto &t : ctx->tables) (void)hipFree(t.dev);
@@ -2646,6 +2729,71 @@ int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const vo
     rc = rm_shade_field_device(ctx, shade, n, st.at<void>(o_val), st.at<void>(o_rgba), ctx->stream);
     if (rc) return rc;
     RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_vertices,
+                         int64_t cap_vertices, void *d_quads, int64_t cap_quads, void *d_info, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const MeshCall m{lattice, true, d_values, value_type, iso, d_vertices, d_quads, d_info, cap_vertices, cap_quads};
+    int64_t n = 0;
+    bool cells = false;
+    int rc = check_mesh(ctx, m, &n, &cells);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!cells) {  // no cell, no launch: the totals are zero
+        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
+        return RM_OK;
+    }
+    Staging st{ctx};
+    const size_t o_map = st.region(4 * static_cast<size_t>(n)), o_totals = st.region(12 * mesh_blocks(n));
+    if ((rc = st.reserve_for(s))) return rc;
+    rc = launch_mesh(ctx, st, m, n, d_values, value_type, d_vertices, d_quads, d_info, o_map, o_totals, s);
+    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
+    return rc;
+}
+
+int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *vertices, int64_t cap_vertices, uint32_t *quads,
+                  int64_t cap_quads, rm_mesh_info *info) {
+    if (!ctx) return RM_E_INVALID;
+    const MeshCall m{lattice, false, nullptr, RM_MESH_F64, iso, vertices, quads, info, cap_vertices, cap_quads};
+    int64_t n = 0;
+    bool cells = false;
+    int rc = check_mesh(ctx, m, &n, &cells);
+    if (rc) return rc;
+    std::memset(info, 0, sizeof *info);
+    if (!cells) return RM_OK;
+    // The volume, the mesher's scratch and the outputs side by side in the scratch buffer.  The outputs are sized by the
+    // capacities -- memory the caller holds on the host anyway -- and by what the lattice can yield at most: a vertex per cell,
+    // three quads per point.
+    const int64_t n_cells = static_cast<int64_t>(lattice->nu - 1) * (lattice->nv - 1) * (lattice->nw - 1);
+    const size_t room_v = static_cast<size_t>(std::min(cap_vertices, n_cells)), room_q = static_cast<size_t>(std::min(cap_quads, 3 * n));
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    Staging st{ctx};
+    const size_t o_vol = st.region(8 * static_cast<size_t>(n)), o_map = st.region(4 * static_cast<size_t>(n)), o_totals = st.region(12 * mesh_blocks(n)),
+                 o_info = st.region(sizeof(rm_mesh_info)), o_vert = st.region(12 * room_v), o_quad = st.region(16 * room_q);
+    if ((rc = st.reserve())) return rc;
+    RmRenderParams p;
+    RmFieldArgs a;
+    fill_field(ctx, lattice, p, a);  // the field entries' own launch, at the lattice's time
+    a.dist = st.at<double>(o_vol);
+    a.first = 0;
+    a.n = n;
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
+    MeshCall on_device = m;
+    on_device.cap_vertices = static_cast<int64_t>(room_v);
+    on_device.cap_quads = static_cast<int64_t>(room_q);
+    if ((rc = launch_mesh(ctx, st, on_device, n, st.at<void>(o_vol), RM_MESH_F64, st.at<void>(o_vert), st.at<void>(o_quad), st.at<void>(o_info), o_map,
+                          o_totals, ctx->stream)))
+        return rc;
+    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
+    RM_HIP(ctx, st.sync());
+    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
+                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
+    if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
+    if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
     RM_HIP(ctx, st.sync());
     return RM_OK;
 }

@@ -159,6 +159,25 @@ struct RmShadeFieldArgs {
     unsigned int lo, hi;
     int map, pad;  // 0 distance, 1 count
 };
+// rm_mesh_field_device / rm_scene_mesh (rm_mesh.hip): surface nets over the n = nu * nv * nw values of a lattice.
+#define RM_MESH_BLOCK 256       // points per workgroup of the three per-point kernels
+#define RM_MESH_SCAN_STEP 1024  // block totals mesh_scan_kernel takes per step of its loop
+struct RmMeshInfo {  // rm_mesh_info (32 bytes)
+    long long n_vertices, n_quads, n_holes, reserved;
+};
+struct RmMeshArgs {
+    double origin[3], du[3], dv[3], dw[3];  // the lattice's vectors, widened
+    const void *values;  // n binary64 values, or binary32 ones with f32
+    double iso;
+    float *vertices;     // cap_vertices x 3
+    uint32_t *quads;     // cap_quads x 4
+    RmMeshInfo *info;
+    uint32_t *map;       // n words: the vertex of the cell whose low corner the point is, or 0xFFFFFFFF
+    uint32_t *totals;    // 3 x n_blocks words: active cells, quads and holes per workgroup; the first two become offsets
+    long long n, cap_vertices, cap_quads;
+    unsigned int nu, nv, nw, n_blocks;  // n_blocks = ceil(n / RM_MESH_BLOCK)
+    int f32, pad;
+};
 // The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
 // A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
 // its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
@@ -274,6 +293,10 @@ hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmRays &r, const R
 // (include/rm_raymarch.h has the rule).  field_kernel, the LDS of rm_launch_distance, ahead-of-time kernels only.
 hipError_t rm_launch_field(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_field_sqrt(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
+
+// Surface nets (rm_mesh.hip): count, scan and -- with a capacity above 0 -- the two emit kernels, back to back on `stream`.
+// a.map and a.totals are the caller's scratch; 1 <= a.n <= 2^30.
+hipError_t rm_launch_mesh(const RmMeshArgs &a, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

@@ -132,6 +132,16 @@ class Scene:
         self._activate()
         return self.ctx.field(origin, du, dv, dw, shape=shape, time=self.time, dist32=dist32, count=count, device=device)
 
+    def toMesh(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, device=False,
+               triangles=False):
+        """The surface getDistance = iso at this scene's own time as (vertices float32 [V, 3], quads uint32 [Q, 4]) -- or
+        triangles uint32 [2Q, 3] --, extracted on the device (Context.mesh): over the lattice origin + i * du + j * dv + k * dw
+        of `shape` points, or, without one, over the root box in `cells` cells (Context.mesh_box)."""
+        self._activate()
+        if origin is None:
+            return self.ctx.mesh_box(cells, margin=margin, iso=iso, time=self.time, device=device, triangles=triangles)
+        return self.ctx.mesh(origin, du, dv, dw, shape, iso=iso, time=self.time, device=device, triangles=triangles)
+
     def info(self):
         self._activate()
         return self.ctx.scene_info()
@@ -442,3 +452,14 @@ def diagnostics(ctx, SDFevaluationBuffer, iterationsBuffer):
     d["average_sdf_calls"] = d["total_sdf"] / n
     d["average_iterations"] = d["total_iters"] / n
     return d
+
+
+def save_obj(path, vertices, faces):
+    """Writes a mesh as Wavefront OBJ text: one `v x y z` line per vertex (repr of the float32 value: it reads back exactly),
+    one `f a b c [d]` line per face with 1-based indices.  Plain writer: no normals, no materials."""
+    v = np.asarray(vertices.cpu() if _is_torch(vertices) else vertices, np.float32).reshape(-1, 3)
+    f = np.asarray(faces.cpu() if _is_torch(faces) else faces)
+    f = (f.view(np.uint32) if f.dtype == np.int32 else f).astype(np.int64).reshape(len(f), -1) + 1
+    with open(path, "w") as out:
+        out.write("".join("v %r %r %r\n" % tuple(float(x) for x in row) for row in v))
+        out.write("".join("f " + " ".join(str(int(i)) for i in row) + "\n" for row in f))

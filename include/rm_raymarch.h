@@ -302,6 +302,72 @@ RM_API int rm_scene_field_device(rm_ctx *ctx, const rm_lattice *lattice, void *d
  * refuses, first < 0, n < 0, first + n > nu * nv * nw or null points_xyz with n > 0. */
 RM_API int rm_lattice_points(const rm_lattice *lattice, int64_t first, int64_t n, float *points_xyz);
 
+/* ---- meshes: the surface of a distance volume, extracted on the device (naive surface nets) ------------------- */
+
+typedef struct rm_mesh_info {    /* 32 bytes */
+    int64_t n_vertices;          /* active cells: the true total, also when it exceeds the capacity */
+    int64_t n_quads;             /* likewise */
+    int64_t n_holes;
+    int64_t reserved;            /* written 0 */
+} rm_mesh_info;
+enum { RM_MESH_F64 = 0, RM_MESH_F32 = 1 };
+
+/* Surface nets over the values of a lattice: one vertex per cell the surface passes through, one quad per lattice edge whose
+ * ends lie on different sides.  The rule, operation for operation (tests/mesh_model.py restates it; results are equal byte
+ * for byte):
+ *   input     an rm_lattice (as rm_scene_field takes and checks it), one value per point at its linear index
+ *             l = (k * nv + j) * nu + i, binary64 or binary32 (widened: exact), and a binary64 `iso`.
+ *   inside    point l is inside iff value[l] < iso: NaN is outside, a value equal to iso is outside, -0.0 < 0.0 is false.
+ *   cells     cell (i, j, k), 0 <= i < nu - 1, 0 <= j < nv - 1, 0 <= k < nw - 1, has its corners at offsets (dx, dy, dz) in
+ *             {0, 1}^3.  It is ACTIVE iff all eight corner values are finite and the corners are neither all inside nor all
+ *             outside; a HOLE iff they are neither all inside nor all outside and a corner value is not finite: a hole emits
+ *             nothing and is counted.  A lattice with a count below 2 has no cells.
+ *   vertices  active cells are numbered 0, 1, 2, ... by the linear index of their low corner; that number is the vertex index.
+ *   position  visit the cell's twelve edges: axis A = 0, 1, 2, and within an axis the edge's low corner at offsets (0,0), (1,0),
+ *             (0,1), (1,1) on the other two axes, the lower-numbered axis first.  With a the value at the edge's low end and b
+ *             at its high end: if exactly one end is inside, t = (iso - a) / (b - a), the crossing's local coordinates are t on
+ *             axis A and the 0 / 1 offsets on the other two; add the three to three running sums that start at 0.0 and count
+ *             the crossing in m.  f = sum / (double)m per axis, and component c of the vertex is
+ *               f32((((double)origin[c] + ((double)i + f[0]) * (double)du[c]) + ((double)j + f[1]) * (double)dv[c])
+ *                   + ((double)k + f[2]) * (double)dw[c]):
+ *             binary64, left to right, one operation at a time, no contraction, ONE rounding to binary32 -- the lattice's own
+ *             point rule with a fractional index.  Vertices are float[3].
+ *   quads     every lattice edge from point p = (i, j, k) along axis A to p + e_A whose ends differ in `inside`: with (B, C) the
+ *             other two axes in cyclic order (A = 0: (1, 2); 1: (2, 0); 2: (0, 1)) the four cells around it have their low
+ *             corners at c0 = p - e_B - e_C, c1 = p - e_C, c2 = p, c3 = p - e_B.  The edge emits a quad iff all four cells
+ *             exist and are active: (v(c0), v(c1), v(c2), v(c3)) when p is inside -- counter-clockwise seen from +A in index
+ *             space, the normal points out of the inside --, (v(c0), v(c3), v(c2), v(c1)) when p is outside.  Quads are
+ *             uint32[4], in increasing 3 * l(p) + A.
+ *   winding   is defined in index space: a lattice whose (du, dv, dw) is left-handed gets world-space normals that point
+ *             inwards.  The Python helpers flip the winding then; this ABI does not.
+ * Capacities: nothing is written at or beyond a capacity; `info` always holds the true totals; a capacity of 0 with a null
+ * buffer is the counting call (it runs the count and the scan alone); truncation is RM_OK -- compare totals with capacities --,
+ * vertex r < cap_vertices and quad q < cap_quads are exactly what an untruncated call writes there, and a truncated quad list
+ * may name vertices >= cap_vertices.
+ *
+ * rm_mesh_field_device: values already on the device (rm_scene_field_device's dist or dist32, or anything else laid out by
+ * the lattice; lattice->time is not used), outputs and d_info (an rm_mesh_info) on the device, asynchronous on `stream` as
+ * rm_scene_field_device: four kernels, no host round trip.  It needs no scene.  RM_E_INVALID -- ahead of RM_E_NO_DEVICE --
+ * for everything rm_scene_field refuses about a lattice, more than 2^30 points (the mesher does not split a volume), null
+ * d_values when the lattice has cells, null d_info, a non-finite iso, a value_type outside the enum, a negative capacity, a
+ * null buffer with a capacity above 0, vertices or quads not 4-byte aligned, d_info or binary64 values not 8-byte aligned
+ * (binary32 values: 4).  A lattice without cells is RM_OK: zero totals, nothing launched.
+ * The cell -> vertex map (4 bytes per point) and the workgroup totals live in the context's scratch buffer.  Calls that use
+ * the scratch are ordered on the device, whatever their streams: the next one waits for this call's kernels.  When the
+ * scratch has to grow the device is synchronised first, so that one call is not asynchronous.
+ * Not a render entry: it neither consumes nor fires rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone;
+ * like rm_scene_field it names its own kernel in rm_last_kernel: mesh_count_kernel<double> or <float>, the first of the four. */
+RM_API int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso,
+                                void *d_vertices, int64_t cap_vertices, void *d_quads, int64_t cap_quads, void *d_info, void *stream);
+
+/* Samples the ACTIVE scene on the lattice at lattice->time (the launch of rm_scene_field_device, binary64, into the context's
+ * scratch buffer) and meshes the volume, all on the device; host buffers, synchronous: min(total, capacity) vertices and quads
+ * are copied back.  The same checks without d_values and value_type (no alignment is asked of `info`), and RM_E_NO_SCENE last.
+ * The scratch holds 12 bytes per point plus the outputs up to their capacities.  A field under a BVH or an octree is the
+ * marchers' bound, not always the exact distance: exact offset surfaces (iso != 0) want acceleration None. */
+RM_API int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *vertices, int64_t cap_vertices,
+                         uint32_t *quads, int64_t cap_quads, rm_mesh_info *info);
+
 /* ---- ray queries ------------------------------------------------------------------ */
 
 typedef struct rm_ray_query {
