@@ -173,6 +173,16 @@ class Context:
         N.check(self._h, N.lib().rm_debug_overlap_fill(self._h, int(asked), int(items), C.byref(v)))
         return v.value
 
+    def step_box(self):
+        """Section M of the v2 wave loop and the scene's step-box table (rm_debug_step_box; no device needed but for `last`):
+        dict(last = the last v2 launch tested its in-round steps against the table, planned = a launch of the active scene
+        would under the options as they stand, reason = why not (0 it would, 1 options or kind of scene, 2 no table, 3 no
+        room in LDS), list_cap / list_cap_without = the hit-list capacity of that launch with and without the table,
+        table_bytes)."""
+        out = (C.c_int32 * 6)()
+        N.check(self._h, N.lib().rm_debug_step_box(self._h, out))
+        return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], list_cap=out[3], list_cap_without=out[4], table_bytes=out[5])
+
     # ---- scene ----------------------------------------------------------------------
     def scene_from_preset(self, index, accel):
         N.check(self._h, N.lib().rm_scene_from_preset(self._h, int(index), int(accel)))

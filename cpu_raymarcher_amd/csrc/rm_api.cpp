@@ -36,7 +36,7 @@ namespace {
 #define RM_SCENE_ARRAYS(X)                                                                                                        \
     X(spheres, 1) X(radii, 1) X(bvh, 1) X(bvh_prims, 1) X(oct, 1) X(oct_prims, 1) X(pq_cells, 1) X(pq_list, 1) X(nn_cells, 1)      \
     X(nn_list, 1) X(prims, 1) X(prog, 1) X(obj_ranges, 1) X(oct_recs, 1) X(oct_lut, 1) X(oct_sub_hdr, 1) X(oct_sub_list, 1)       \
-    X(slot_object, 0) X(ext_cells, 1) X(ext_list, 1)
+    X(slot_object, 0) X(ext_cells, 1) X(ext_list, 1) X(step_tab, 1)
 
 struct DeviceScene {
 #define RM_X(name, always) decltype(rmh::HostScene::name)::value_type *name = nullptr;
@@ -432,9 +432,12 @@ struct rm_ctx {
     // that is really there.  0: the floor alone.
     int64_t opt_overlap_fill = 1;
     int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
-    uint32_t last_v2_shape[3] = {0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch)
+    uint32_t last_v2_shape[4] = {0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
+                                               // tested its steps against the step-box table (rm_debug_step_box)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
     int64_t opt_multi_step = 1;  // v2 BVH: in-round march steps (rm_render_v2.hip, section M)
+    int64_t opt_step_box = 1;    // ... test their leaf sets against the bracket of the round's point in the scene's threshold tables (rm_scene_host.cpp
+                                 // build_step_box) where the scene has them and they fit the launch's LDS; 0: the exact test against the leaf lists
     int64_t opt_lds_kb = 0;         // v2: LDS budget per workgroup the launcher trims the hit lists to (0: as many workgroups per CU as the kernel's registers allow; 32: five per CU, 40: four)
     int64_t opt_refill = 64;
     int64_t opt_recs = 1;  // octree leaves read leaf-ordered sphere records
@@ -1230,6 +1233,17 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.lds_fill = static_cast<int32_t>(ctx->opt_lds_fill);
     p.item_wide = static_cast<int32_t>(ctx->opt_item_wide);
     p.multi_step = static_cast<int32_t>(ctx->opt_multi_step);
+    // the step-box table of section M: asked for here, granted by the launcher (rm_v2_plan).  A context with a device reads it
+    // there; one without plans as if it had.
+    p.step_tab = ctx->dev.step_tab;
+    p.sb_bins = ctx->host.sb_bins;
+    p.sb_stride = ctx->host.sb_stride;
+    for (int k = 0; k < 3; ++k) {
+        p.sb_origin[k] = ctx->host.sb_origin[k];
+        p.sb_inv[k] = ctx->host.sb_inv[k];
+    }
+    p.step_box = (ctx->opt_step_box && ctx->opt_multi_step && ctx->host.accel == RM_ACCEL_BVH && !ctx->host.step_tab.empty() &&
+                  (ctx->dev.step_tab || !ctx->has_device)) ? 1 : 0;
     p.uniform_radius = 0;
     if (ctx->opt_uniform && !ctx->host.general && ctx->host.spheres.size() >= 2 &&
         ctx->host.spheres.size() <= 256) {  // one radius, bit for bit; at most 256 spheres: the scan keys carry the id in eight bits
@@ -3095,6 +3109,41 @@ int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]) {
     return RM_OK;
 }
 
+// Section M of the v2 wave loop and the step-box table (option `step_box`), without a device: out[0] whether the last v2 launch
+// tested its in-round steps against the table (0 before the first), out[1] whether a launch of the active scene under the
+// options as they stand would (the launcher's own decision, rm_v2_plan), out[2] why not -- 0 it would, 1 the options (`step_box`,
+// `multi_step`, `kernel`) or the scene's kind rule it out, 2 the scene has no table, 3 the table would cost LDS the launch
+// keeps for something else -- out[3] the hit-list capacity that launch gets and out[4] the one it would get with `step_box` 0,
+// out[5] the table's size in bytes.
+int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]) {
+    if (!ctx || !out) return RM_E_INVALID;
+    for (int k = 0; k < 6; ++k) out[k] = 0;
+    out[0] = static_cast<int32_t>(ctx->last_v2_shape[3]);
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    rm_job job;
+    std::memset(&job, 0, sizeof job);
+    job.width = job.height = job.y_end = 64;
+    job.algorithm = RM_ALG_SPHERE_TRACER;
+    job.scene_preset_index = ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset;
+    job.acceleration_structure = ctx->host.accel;
+    job.overshoot_factor = job.step_size = std::nan("");
+    const double scene_time = ctx->time;
+    RmRenderParams p;
+    const int rc = fill_params(ctx, &job, p);
+    ctx->time = scene_time;  // (a debug read leaves the scene's time alone)
+    if (rc) return rc;
+    out[5] = static_cast<int32_t>(ctx->host.step_tab.size() * sizeof(uint32_t));
+    RmRenderParams plain = p;
+    plain.step_box = 0;
+    out[4] = rm_v2_plan(plain).list_cap;
+    const RmV2Plan plan = rm_v2_plan(p);
+    out[3] = plan.list_cap;
+    const bool v2 = p.variant == 2 && p.algorithm == 0 && p.accel == 2;
+    out[1] = v2 && plan.step_box ? 1 : 0;
+    out[2] = out[1] ? 0 : (ctx->host.step_tab.empty() && v2 && ctx->opt_step_box && ctx->opt_multi_step ? 2 : (v2 && plan.refused ? 3 : 1));
+    return RM_OK;
+}
+
 // Every option once: its key, its member of rm_ctx (the defaults and what they were measured against are there; fill_params
 // reads the members), the values it takes and what rm_last_error says of any other.
 enum OptionKind {
@@ -3122,6 +3171,7 @@ static const OptionRow kOptions[] = {
     {"uniform", &rm_ctx::opt_uniform, kSwitch, {}, nullptr},
     {"lds_kb", &rm_ctx::opt_lds_kb, kZeroOrRange, {16, 64}, "lds_kb must be 0 (auto) or in [16, 64]"},
     {"multi_step", &rm_ctx::opt_multi_step, kSwitch, {}, nullptr},
+    {"step_box", &rm_ctx::opt_step_box, kSwitch, {}, nullptr},
     {"item_wide", &rm_ctx::opt_item_wide, kSwitch, {}, nullptr},
     {"prune", &rm_ctx::opt_prune, kSwitch, {}, nullptr},
     {"rtc_spheres", &rm_ctx::opt_rtc_spheres, kRange, {0, 33}, "rtc_spheres must be 0..33"},

@@ -246,6 +246,17 @@ inline int rm_v2_overlap_per_cu(int floor_per_cu, int candidate, long long items
     return items >= RM_V2_OVERLAP_ITEMS_PER_WAVE * waves ? candidate : floor_per_cu;
 }
 
+// What a launch of the v2 wave loop keeps in LDS, decided from its parameters alone (no device): the scene's tables (lds), the
+// origin-relative node boxes (rel), list_cap entries of hit list per ray, and the step-box table of section M (step_box: asked
+// for through RmRenderParams::step_box and granted; refused: asked for, but it would have cost the scene's staging, the
+// relative boxes or a workgroup per CU).  tier: which LDS budget the launch reaches (0: the first; rm_render_v2.hip).
+struct RmV2Plan {
+    bool lds, rel;
+    int list_cap, step_box, tier, refused;
+    size_t scene_bytes, list_bytes;
+};
+RmV2Plan rm_v2_plan(const RmRenderParams &p);
+
 // rm_debug_wave_distance: Scene.getDistance through the wave loop's bvh_distance_wave, one point per lane (BVH sphere scenes)
 hipError_t rm_launch_wave_distance(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);
 hipError_t rm_launch_wave_distance_sqrt(const RmRenderParams &p, const float *points, int64_t n, double *dist, uint32_t *count, hipStream_t stream);

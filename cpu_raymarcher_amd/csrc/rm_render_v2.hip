@@ -769,13 +769,13 @@ __device__ bool bvh_prologue_cull(const SceneView &S, const RmRenderParams &C, c
 // they do not fit: the first build spilled 130 SGPRs to VGPR lanes and a tenth of the wave loop's straight-line
 // instructions were v_readlane reloads (4.7 issue cycles each, profiles/r02/valu_issue_costs.json).
 struct LdsLayout {
-    uint32_t nodes, prims, cells, list, oct, oct_prims, spheres, radii, rel, end;
+    uint32_t nodes, prims, cells, list, oct, oct_prims, spheres, radii, rel, end, step;
 };
 // the one definition of the layout, used by the launcher (which writes it into RmRenderParams::lds_off)
 inline LdsLayout lds_layout_host(const RmRenderParams &C, int accel, bool lds, bool rel) {
     auto up = [](uint32_t v) { return (v + 15u) & ~15u; };
     auto words = [](uint32_t count, uint32_t size) { return ((count * size + 3u) / 4u) * 4u; };
-    LdsLayout o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    LdsLayout o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t off = 0;
     if (lds) {
         if (accel == 2) {
@@ -798,6 +798,10 @@ inline LdsLayout lds_layout_host(const RmRenderParams &C, int accel, bool lds, b
         o.radii = off = up(off);
         off += words(static_cast<uint32_t>(C.n_prims), 8);
         off = up(off);
+        if (accel == 2 && C.step_box) {  // the step-box thresholds (section M), 3 axes of sb_stride words
+            o.step = off;
+            off = up(off + 3u * static_cast<uint32_t>(C.sb_stride) * 4u);
+        }
         if (rel) {
             o.rel = off;
             off += static_cast<uint32_t>(C.bvh_nodes) * 48u;
@@ -819,6 +823,7 @@ __device__ __forceinline__ LdsLayout lds_layout(const RmRenderParams &C) {
     o.radii = C.lds_off[7];
     o.rel = C.lds_off[8];
     o.end = C.lds_off[9];
+    o.step = C.lds_off[10];
     return o;
 }
 template <int ACCEL, bool LDS, bool REL>
@@ -1023,6 +1028,10 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
             stage(smem, off, P.spheres, P.n_prims);
             off = lay.radii;
             stage(smem, off, P.radii, P.n_prims);
+            if (ACCEL == 2) {  // (nothing without the table: the offset is then unused)
+                off = lay.step;
+                stage(smem, off, P.step_tab, P.step_box ? 3 * P.sb_stride : 0);
+            }
             if (REL) {  // node boxes relative to this frame's ray origin (slab_rel)
                 double *rel = reinterpret_cast<double *>(smem + lay.rel);
                 for (int k = threadIdx.x; k < P.bvh_nodes * 6; k += blockDim.x) {
@@ -1449,7 +1458,10 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
         //    of B are members of A, and equal counts make the sets equal: no signature, no assumption on the order of a list,
         //    and p2 may lie in another cell than q.  getPrimitivesAt returns the same leaves, the counter advances by the
         //    same `found`.  (Until round 8 the test was a ball around q -- the smallest box_margin of the listed leaves and
-        //    the distance to the grown cell's faces -- which ended 3.2 runs per pixel of C3 where the set changes 0.2 times);
+        //    the distance to the grown cell's faces -- which ended 3.2 runs per pixel of C3 where the set changes 0.2 times.)
+        //    Since round 9 that exact test is the fall-back: where the launch has the scene's step-box table (option
+        //    `step_box`, CM.step_box) the same conclusion comes from six compares of p2 against a box found once per run
+        //    -- the derivation stands at the look-up below;
         //  * every other candidate, at least lb2 away at q and 1-Lipschitz, is still farther at p2 (at most dd from q: the
         //    distance between the two binary32 points, rounded up) than the exact distance of the sphere k1 that won at q:
         //    Math.min over the candidates, those of an equal leaf set, is that distance.
@@ -1463,6 +1475,46 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                     const SceneView SM = scene_view<ACCEL, LDS, REL>(CM, smem);
                     const RmSphere s1 = SM.spheres[aux.k1];
                     const double r1 = SM.radii[aux.k1];
+                    // Option `step_box` (round 9): the leaf-set test of a trip as six compares against a box found once per run.
+                    // box_margin(lo, hi, p) >= 0 holds exactly when lo[k] <= p[k] <= hi[k] on the three axes (the sign of a
+                    // binary32 difference is exact; denormals are kept), so which leaves contain a point, and whether the root
+                    // does, is decided by comparing its coordinates with the boxes' face coordinates.  Per axis k the scene's
+                    // table (rm_scene_host.cpp build_step_box) holds the thresholds T = lo[k] and T = nextup(hi[k]) of every leaf
+                    // box and the root -- p <= b is p < nextup(b) -- sorted and distinct: they cut the axis into half-open cells
+                    // [T_i, T_i+1).  With T_i <= q[k] < T_i+1 and T_i <= p2[k] < T_i+1 on all three axes every one of those
+                    // compares answers for p2 as for q: the leaf sets are equal, p2 is in the root box as q is (aux.ok),
+                    // getPrimitivesAt returns the same leaves and the counter advances by the same `found`.  No list, no cell
+                    // and no count takes part; a q on a face needs no special case.  Sufficient, not necessary: a far leaf's
+                    // threshold can end a run although the set would not change (the model, scripts/in_round_model.c, has
+                    // 6 % more rounds on C3 for it).  The half-open form matters: a ray's first point in an interval sits ON
+                    // a leaf face, and cells open on both sides would end every such run at once.
+                    // The bracket of q: the look-up byte of q's bin is an index at or below it (the host leaves 1 % of a bin
+                    // for the binary32 bin index), the walk up takes zero or one step unless thresholds crowd a bin.  It ends
+                    // at the +inf sentinel for every q the root box contains; the index bound keeps it inside the table for
+                    // any other value.
+                    const bool step_box = CM.step_box != 0;  // wave-uniform
+                    float b_lo[3], b_hi[3];
+                    if (step_box) {
+                        const uint32_t *tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CM.lds_off[10]) : CM.step_tab;
+                        const int last = CM.sb_stride - (CM.sb_bins >> 2) - 2;  // index of the axis' last threshold slot
+                        const float qk[3] = {q.x, q.y, q.z};
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            const uint32_t *axis = tab + k * CM.sb_stride;
+                            const int b = min(max(static_cast<int>((qk[k] - CM.sb_origin[k]) * CM.sb_inv[k]), 0), CM.sb_bins - 1);
+                            int i = static_cast<int>(reinterpret_cast<const uint8_t *>(axis)[b]);
+                            i = min(i, last);
+                            const float *T = reinterpret_cast<const float *>(axis + (CM.sb_bins >> 2));
+                            float lo = T[i], hi = T[i + 1];
+                            while (hi <= qk[k] && i < last) {
+                                i += 1;
+                                lo = hi;
+                                hi = T[i + 1];
+                            }
+                            b_lo[k] = lo;
+                            b_hi[k] = hi;
+                        }
+                    }
                     for (;;) {
                         if ((st & ST_TRIP_MASK) >= (RM_MAX_STEPS << ST_TRIP_SHIFT)) {  // loop exhausted: return totalDist
                             finish_march(t);
@@ -1473,7 +1525,12 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                             break;
                         }
                         const Vec3f p2 = point_at(ray, t);
-                        {   // the leaves that contain p2, as bvh_distance_wave finds them, against those that contained q
+                        if (step_box) {  // p2 in q's bracket on every axis: the same leaves, the root among the boxes
+                            if (!(p2.x >= b_lo[0] && p2.x < b_hi[0] && p2.y >= b_lo[1] && p2.y < b_hi[1] && p2.z >= b_lo[2] && p2.z < b_hi[2])) {
+                                RM_CNT_END(0)
+                                break;
+                            }
+                        } else {  // the exact test: the leaves that contain p2, as bvh_distance_wave finds them, against those that contained q
                             const RmBvhNode root = SM.nodes[0];
                             bool same = box_margin(root.lo, root.hi, p2) >= 0.f;
                             uint32_t cell = 255u;
@@ -1620,10 +1677,85 @@ size_t scene_lds_bytes(const RmRenderParams &p) {
         b += up(static_cast<size_t>(p.oct_nodes) * sizeof(RmOctNode)) + up(static_cast<size_t>(p.oct_prim_count) * 4);
     }
     b += up(static_cast<size_t>(p.n_prims) * sizeof(RmSphere)) + up(static_cast<size_t>(p.n_prims) * 8);
+    if (p.accel == 2 && p.step_box) b += up(static_cast<size_t>(3) * p.sb_stride * 4);
     return b + 16;
 }
 
 }  // namespace
+
+#ifndef RM_LENGTH_SQRT
+// What a launch of the wave loop stages in LDS (rm_kernels.h, RmV2Plan): pure host arithmetic on the launch parameters, one
+// definition for the launcher of both `length` builds and for rm_debug_step_box.
+// LDS budget per workgroup.  The kernels hold 80 VGPRs: six waves per SIMD = six four-wave workgroups per CU, if six
+// fit the CU's 160 KB of LDS.  LDS is handed out in granules of 1 280 bytes (measured in round 3: a workgroup of
+// 32 096 bytes, dynamic + static, no longer ran five to a CU -- 26 granules = 33 280 -- and the frame rate with frames in
+// flight fell 5 %; hipOccupancyMaxActiveBlocksPerMultiprocessor does not model it), so the budgets are whole granules:
+// 26 880 bytes for six, 32 000 for five, 40 960 for four.  The per-ray hit lists give way down to 12 entries to reach a
+// budget (rays that hit more leaves take the tree-walk form of bvh_next, as they do beyond any cap); origin-relative
+// node boxes (48 B per node) ride along when they fit the same budget.  Option `lds_kb` (> 0) names a budget itself.
+// The step-box table of section M (p.step_box: the caller asks for it) is planned for last: the launch is planned without it
+// and with it, and takes it when that costs neither the staging of the scene, nor the origin-relative boxes, nor a workgroup
+// per CU -- the same budget is reached, if need be with shorter hit lists (down to the 12 entries any budget may trim them to).  A launch that reads its
+// tables from global memory reads this one there too.
+RmV2Plan rm_v2_plan(const RmRenderParams &p_in) {
+    RmRenderParams p = p_in;
+    if (p.leaf_order) p.bvh_prim_count = 0;
+    if (p.list_cap < 1) p.list_cap = 1;
+    const bool want = p.accel == 2 && p.step_box != 0 && p.multi_step != 0 && p.sb_stride > 0;
+    auto pass = [&](bool with_table) {
+        RmRenderParams c = p;
+        c.step_box = with_table ? 1 : 0;
+        RmV2Plan r;
+        r.step_box = c.step_box;
+        r.list_cap = c.list_cap;
+        r.list_bytes = c.accel == 2 ? static_cast<size_t>(4) * c.list_cap * 128 : 0;
+        r.scene_bytes = scene_lds_bytes(c);
+        // stage the scene in LDS when it leaves room for >= 2 workgroups per CU (160 KB LDS)
+        r.lds = c.nodes_in_lds != 0 && r.scene_bytes + r.list_bytes + 16 <= 64 * 1024;
+        r.rel = false;
+        r.tier = 0;
+        r.refused = 0;
+        if (!(r.lds && c.accel == 2)) return r;
+        const size_t rel_bytes = static_cast<size_t>(c.bvh_nodes) * 48;
+        constexpr size_t kLdsPerCu = 160 * 1024, kGranule = 1280, kStatic = sizeof(WaveDiag) * 4;
+        auto budget_for = [&](size_t bytes) { return bytes / kGranule * kGranule - kStatic; };  // dynamic bytes of a workgroup
+        auto fits = [&](size_t extra, int cap, size_t budget) { return r.scene_bytes + extra + static_cast<size_t>(4) * cap * 128 + 16 <= budget; };
+        auto trim = [&](size_t extra, size_t budget) {  // largest cap <= list_cap (>= 12, or list_cap itself if smaller) that fits; 0 if none
+            int cap = c.list_cap;
+            while (cap > 12 && !fits(extra, cap, budget)) cap -= 1;
+            return fits(extra, cap, budget) ? cap : 0;
+        };
+        size_t budgets[4];
+        int nb = 0;
+        if (c.lds_budget_kb > 0) budgets[nb++] = budget_for(static_cast<size_t>(c.lds_budget_kb) * 1024);
+        else {
+            budgets[nb++] = budget_for(kLdsPerCu / RM_V2_WAVES);
+            budgets[nb++] = budget_for(kLdsPerCu / 5);
+        }
+        budgets[nb++] = budget_for(kLdsPerCu / 4);
+        r.tier = nb;  // no budget reached: the launch takes what it needs (at most 64 KB, above)
+        for (int b = 0; b < nb; ++b) {
+            int cap = c.rel_boxes ? trim(rel_bytes + 16, budgets[b]) : 0;
+            if (cap > 0) r.rel = true;
+            else cap = trim(0, budgets[b]);
+            if (cap > 0) {
+                r.list_cap = cap;
+                r.list_bytes = static_cast<size_t>(4) * cap * 128;
+                r.tier = b;
+                break;
+            }
+            r.rel = false;
+        }
+        return r;
+    };
+    RmV2Plan plain = pass(false);
+    if (!want) return plain;
+    const RmV2Plan with_table = pass(true);
+    if (with_table.lds == plain.lds && with_table.rel == plain.rel && with_table.tier <= plain.tier) return with_table;
+    plain.refused = 1;
+    return plain;
+}
+#endif
 
 #ifndef RM_LENGTH_SQRT
 namespace {
@@ -1725,51 +1857,14 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     p.tiles_x_magic = tiles_x == 1 ? 0u : static_cast<uint32_t>((1ull << 32) / static_cast<unsigned long long>(tiles_x)) + 1u;  // 0: k / 1
     const unsigned needed = static_cast<unsigned>((static_cast<long long>(tiles_x) * tiles_y + 3) / 4);  // 4 waves each
     unsigned resident = 0, blocks = 0;  // set below, once the LDS footprint (workgroups per CU) is known
-    if (p.list_cap < 1) p.list_cap = 1;
     if (p.refill_threshold < 1) p.refill_threshold = 1;
     if (p.refill_threshold > 64) p.refill_threshold = 64;
-    size_t list_bytes = p.accel == 2 ? static_cast<size_t>(4) * p.list_cap * 128 : 0;
-    const size_t scene_bytes = scene_lds_bytes(p);
-    // stage the scene in LDS when it leaves room for >= 2 workgroups per CU (160 KB LDS)
-    const bool lds = p.nodes_in_lds != 0 && scene_bytes + list_bytes + 16 <= 64 * 1024;
-    // LDS budget per workgroup.  The kernels hold 80 VGPRs: six waves per SIMD = six four-wave workgroups per CU, if six
-    // fit the CU's 160 KB of LDS.  LDS is handed out in granules of 1 280 bytes (measured in round 3: a workgroup of
-    // 32 096 bytes, dynamic + static, no longer ran five to a CU -- 26 granules = 33 280 -- and the frame rate with frames in
-    // flight fell 5 %; hipOccupancyMaxActiveBlocksPerMultiprocessor does not model it), so the budgets are whole granules:
-    // 26 880 bytes for six, 32 000 for five, 40 960 for four.  The per-ray hit lists give way down to 12 entries to reach a
-    // budget (rays that hit more leaves take the tree-walk form of bvh_next, as they do beyond any cap); origin-relative
-    // node boxes (48 B per node) ride along when they fit the same budget.  Option `lds_kb` (> 0) names a budget itself.
-    bool rel = false;
-    const size_t rel_bytes = static_cast<size_t>(p.bvh_nodes) * 48;
-    if (lds && p.accel == 2) {
-        constexpr size_t kLdsPerCu = 160 * 1024, kGranule = 1280, kStatic = sizeof(WaveDiag) * 4;
-        auto budget_for = [&](size_t bytes) { return bytes / kGranule * kGranule - kStatic; };  // dynamic bytes of a workgroup
-        auto fits = [&](size_t extra, int cap, size_t budget) { return scene_bytes + extra + static_cast<size_t>(4) * cap * 128 + 16 <= budget; };
-        auto trim = [&](size_t extra, size_t budget) {  // largest cap <= list_cap (>= 12, or list_cap itself if smaller) that fits; 0 if none
-            int cap = p.list_cap;
-            while (cap > 12 && !fits(extra, cap, budget)) cap -= 1;
-            return fits(extra, cap, budget) ? cap : 0;
-        };
-        size_t budgets[4];
-        int nb = 0;
-        if (p.lds_budget_kb > 0) budgets[nb++] = budget_for(static_cast<size_t>(p.lds_budget_kb) * 1024);
-        else {
-            budgets[nb++] = budget_for(kLdsPerCu / RM_V2_WAVES);
-            budgets[nb++] = budget_for(kLdsPerCu / 5);
-        }
-        budgets[nb++] = budget_for(kLdsPerCu / 4);
-        for (int b = 0; b < nb; ++b) {
-            int cap = p.rel_boxes ? trim(rel_bytes + 16, budgets[b]) : 0;
-            if (cap > 0) rel = true;
-            else cap = trim(0, budgets[b]);
-            if (cap > 0) {
-                p.list_cap = cap;
-                list_bytes = static_cast<size_t>(4) * cap * 128;
-                break;
-            }
-            rel = false;
-        }
-    }
+    // LDS: what is staged, the hit-list capacity, and whether section M gets its step-box table (v2_plan)
+    const RmV2Plan plan = rm_v2_plan(p);
+    const bool lds = plan.lds, rel = plan.rel;
+    p.list_cap = plan.list_cap;
+    p.step_box = plan.step_box;
+    const size_t list_bytes = plan.list_bytes, scene_bytes = plan.scene_bytes, rel_bytes = static_cast<size_t>(p.bvh_nodes) * 48;
     size_t shmem = (lds ? scene_bytes : 0) + (rel ? rel_bytes + 16 : 0) + list_bytes + 16;
     // Option `lds_fill`: a launch of k persistent workgroups per CU asks for as much LDS as still lets k of them share a CU, so
     // that the dispatcher CANNOT put more than k on one CU (and fewer on another): a frame that runs alone gets exactly k on
@@ -1780,8 +1875,8 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     }
     {
         const LdsLayout lay = lds_layout_host(p, p.accel, lds, rel && p.accel == 2);
-        const uint32_t v[10] = {lay.nodes, lay.prims, lay.cells, lay.list, lay.oct, lay.oct_prims, lay.spheres, lay.radii, lay.rel, lay.end};
-        for (int k = 0; k < 10; ++k) p.lds_off[k] = v[k];
+        const uint32_t v[11] = {lay.nodes, lay.prims, lay.cells, lay.list, lay.oct, lay.oct_prims, lay.spheres, lay.radii, lay.rel, lay.end, lay.step};
+        for (int k = 0; k < 11; ++k) p.lds_off[k] = v[k];
         if (lay.end + list_bytes > shmem) return hipErrorInvalidValue;  // the layout and the allocation come from two formulas: they must agree
     }
     // the workgroups per CU the launch brings: what the caller asked, or what rm_api.cpp raised that to (launch_per_cu, option
@@ -1796,6 +1891,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         shape[0] = blocks;
         shape[1] = 256;
         shape[2] = static_cast<uint32_t>(shmem);
+        shape[3] = p.step_box ? 1u : 0u;
     }
     // the tile-queue heads are zero: a launch's last wave leaves them so (rm_diag.h).  Without an accumulator block
     // (a caller below the API layer) they are cleared here.

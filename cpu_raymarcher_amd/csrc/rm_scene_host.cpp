@@ -292,6 +292,70 @@ void build_point_query_grid(HostScene &s, const PairLoops *loops) {
             }
 }
 
+// ---- threshold tables of the leaf boxes (the in-round march steps of the v2 wave loop, rm_render_v2.hip section M) ---------
+//
+// BoundingBox.contains(p) is lo[k] <= p[k] <= hi[k] on the three axes, so the set of leaves that contain a point -- and
+// whether the root does -- is decided by comparing each coordinate with the boxes' face coordinates alone.  Per axis k the
+// thresholds are T = lo[k] of every leaf box and the root, and T = nextup(hi[k]) of every leaf box and the root (the next
+// binary32 above: p <= b is p < nextup(b)).  Sorted and made distinct they cut the axis into half-open cells [T_i, T_i+1);
+// two points whose coordinates lie in the same cell on all three axes get the same answer from every one of those compares:
+// equal leaf sets, equal root membership.  The device's box_margin(lo, hi, p) >= 0 is those compares exactly as long as no
+// difference p - a is flushed to zero (the kernels keep binary32 denormals; a scene with a face coordinate that is non-zero
+// and below 1e-30 in magnitude gets no table all the same, so the rule never leans on it).
+// Per axis the table holds kStepBoxBins look-up bytes over the root extent and the thresholds between sentinels: T[0] = -inf,
+// T[1 .. n], then +inf up to the common length.  Byte b is the largest i with T[i] <= origin + (b - 0.01) bins: the device
+// forms the bin in binary32 (off by ~1e-5 of a bin), starts there and walks up, normally zero or one step.
+// The boxes are those the point-query lists are built from (non-empty leaves), plus the root as the kernel reads it (node 0).
+void build_step_box(HostScene &s) {
+    s.step_tab.clear();
+    s.sb_bins = s.sb_stride = 0;
+    if (s.general || s.program || s.bvh.empty() || s.bvh_leaves == 0) return;
+    std::vector<float> T[3];
+    for (size_t i = 0; i < s.bvh.size(); ++i) {
+        const RmBvhNode &nd = s.bvh[i];
+        if (i != 0 && (nd.leaf < 0 || (nd.leaf & 0xFF) == 0)) continue;
+        for (int k = 0; k < 3; ++k) {
+            for (const float v : {nd.lo[k], nd.hi[k]})
+                if (!std::isfinite(v) || (v != 0.0f && std::fabs(v) < 1e-30f)) return;
+            T[k].push_back(nd.lo[k]);
+            T[k].push_back(std::nextafter(nd.hi[k], std::numeric_limits<float>::infinity()));
+        }
+    }
+    size_t longest = 0;
+    for (int k = 0; k < 3; ++k) {
+        std::sort(T[k].begin(), T[k].end());
+        T[k].erase(std::unique(T[k].begin(), T[k].end()), T[k].end());
+        if (T[k].size() > static_cast<size_t>(kStepBoxCap)) return;
+        longest = std::max(longest, T[k].size());
+    }
+    const float inf = std::numeric_limits<float>::infinity();
+    s.sb_bins = kStepBoxBins;
+    s.sb_stride = kStepBoxBins / 4 + static_cast<int>(longest) + 2;
+    s.step_tab.assign(3 * static_cast<size_t>(s.sb_stride), 0);
+    for (int k = 0; k < 3; ++k) {
+        const RmBvhNode &root = s.bvh[0];
+        const double ext = double(root.hi[k]) - double(root.lo[k]);
+        s.sb_origin[k] = root.lo[k];
+        s.sb_inv[k] = ext > 0 ? static_cast<float>(kStepBoxBins / ext) : 0.0f;
+        if (!std::isfinite(s.sb_inv[k])) s.sb_inv[k] = 0.0f;  // (an extent so small that its inverse overflows: every point goes to bin 0)
+        uint32_t *axis = s.step_tab.data() + static_cast<size_t>(k) * s.sb_stride;
+        std::vector<float> th(static_cast<size_t>(longest) + 2, inf);
+        th[0] = -inf;
+        std::copy(T[k].begin(), T[k].end(), th.begin() + 1);
+        std::memcpy(axis + kStepBoxBins / 4, th.data(), th.size() * sizeof(float));
+        uint8_t *bins = reinterpret_cast<uint8_t *>(axis);
+        const double w = s.sb_inv[k] > 0 ? 1.0 / double(s.sb_inv[k]) : 0.0;
+        for (int b = 0; b < kStepBoxBins; ++b) {
+            size_t i = 0;
+            if (b > 0 && w > 0) {
+                const double edge = double(s.sb_origin[k]) + (b - 0.01) * w;
+                while (i < T[k].size() && double(T[k][i]) <= edge) ++i;  // i thresholds lie at or below the edge: T[i] is the last of them
+            }
+            bins[b] = static_cast<uint8_t>(i);
+        }
+    }
+}
+
 // Nearest-candidate lists for points OUTSIDE the root box.  A ray that has passed the scene still takes one march step per
 // remaining interval (bvh.ts:222-239, sphereTracer.ts:67), each at a point no leaf contains: scene.ts:173 evaluates every
 // primitive there.  The region is the root box grown to the cube |x_k| <= kExtReach (and by half a unit at least): the orbit
@@ -580,6 +644,7 @@ static bool build_accel(HostScene &s, int n, std::string &err, const PairLoops *
         std::memcpy(s.root_max, root.hi, sizeof root.hi);
         build_point_query_grid(s, loops);  // the leaf grid only knows leaf boxes: it serves every primitive representation
         build_exterior_grid(s, loops);
+        build_step_box(s);
     } else if (s.accel == 1) {
         Box root;  // scene.ts:81-85
         for (int k = 0; k < 3; ++k) {

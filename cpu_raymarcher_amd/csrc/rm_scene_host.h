@@ -12,6 +12,11 @@
 namespace rmh {
 
 constexpr int kPresetCount = 19;  // sceneManager.ts:102-357
+constexpr int kStepBoxCap = 62;   // distinct thresholds per axis a step-box table holds (with the two sentinels: 64 words)
+// look-up bins per axis over the root extent, one byte each.  32, not more: the Dense Sphere Grid's table is then 240 bytes,
+// and the 288 bytes its launch has left below the six-workgroups-per-CU budget hold it without a shorter hit list (13 entries);
+// its thresholds are 0.15 apart at least, a bin is 0.089 wide, so a bin still holds one threshold at most
+constexpr int kStepBoxBins = 32;
 
 // one primitive as the ABI hands it over (include/rm_raymarch.h: rm_prim)
 struct PrimDesc {
@@ -77,6 +82,13 @@ struct HostScene {
     float ext_origin[3] = {0, 0, 0}, ext_inv[3] = {0, 0, 0};
     std::vector<uint32_t> ext_cells;
     std::vector<uint16_t> ext_list;
+    // Threshold tables of the leaf boxes, per axis (build_step_box; the v2 wave loop's in-round march steps test a new point
+    // against the bracket of the round's point instead of against the leaf lists).  Axis k takes sb_stride words from word
+    // k * sb_stride on: sb_bins look-up bytes, then the thresholds as binary32 bit patterns between -inf and +inf sentinels.
+    // Empty: no table (no BVH sphere scene, more than kStepBoxCap thresholds on an axis, a tiny non-zero face coordinate).
+    int sb_bins = 0, sb_stride = 0;
+    float sb_origin[3] = {0, 0, 0}, sb_inv[3] = {0, 0, 0};
+    std::vector<uint32_t> step_tab;
     std::vector<RmOctNode> oct;
     std::vector<int32_t> oct_prims;
     std::vector<RmSphereRec> oct_recs;  // oct_prims expanded to sphere records (sphere scenes)

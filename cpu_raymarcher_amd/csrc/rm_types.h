@@ -182,8 +182,8 @@ struct RmRenderParams {
     int32_t launch_per_cu;
     int32_t v1_lists;          // v1 BVH: per-ray hit-leaf lists in LDS (option `v1_lists`), placed at v1_list_offset by the launcher
     int32_t v1_list_offset;
-    uint32_t lds_off[10];      // v2: byte offsets of the staged tables in LDS (nodes, prims, cells, list, oct, oct_prims, spheres,
-                               // radii, rel, end), computed by the launcher: a section rebuilds its view from one scalar load
+    uint32_t lds_off[11];      // v2: byte offsets of the staged tables in LDS (nodes, prims, cells, list, oct, oct_prims, spheres,
+                               // radii, rel, end, step_tab), computed by the launcher: a section rebuilds its view from one scalar load
     int32_t prim_filter;       // general primitives (RmPrim): `spheres` holds a bounding sphere per primitive (rigid transforms only)
     int32_t n0_batch;          // v2 BVH: lanes waiting for getNormal that trigger the normal round while others still march (64: never)
     const int32_t *stripe_ids; // non-null (with stripe_rows > 0): the launch renders the stripes stripe_ids[0 .. ) in this
@@ -255,4 +255,13 @@ struct RmRenderParams {
     int32_t multi_step;  // v2 BVH: march steps inside a round while the leaf set and the winning sphere provably stay the same (option `multi_step`)
     RmDiagBlock *diag_block;
     RmDiagDevice *diag_out;
+    // v2 BVH, section M: the per-axis threshold tables of the scene's leaf boxes (rm_scene_host.cpp build_step_box).  Axis k is
+    // sb_stride words from word k * sb_stride on: sb_bins bytes of the uniform look-up (bin b = clamp(int((x - sb_origin[k]) *
+    // sb_inv[k])) holds an index at or below the bracket of every x the device puts into b), then the sorted thresholds as
+    // binary32 between a sentinel -inf and sentinels +inf.  step_box: what fill_params asks for (option `step_box`, the scene
+    // has a table) and, from the launcher on, what the launch does (rm_v2_plan).
+    const uint32_t *step_tab;
+    float sb_origin[3], sb_inv[3];
+    int32_t sb_bins, sb_stride;
+    int32_t step_box;
 };

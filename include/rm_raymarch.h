@@ -930,7 +930,7 @@ RM_API int rm_debug_read_counts(rm_ctx *ctx, uint64_t *out32);
 RM_API int rm_debug_read_lpt_costs(rm_ctx *ctx, uint8_t *out, int64_t n);
 /* One table of the active scene, for tests of the scene builders: `name` is a scene array as csrc/rm_api.cpp lists them
  * (RM_SCENE_ARRAYS: spheres, radii, bvh, bvh_prims, oct, oct_prims, pq_cells, pq_list, nn_cells, nn_list, prims, prog,
- * obj_ranges, oct_recs, oct_lut, oct_sub_hdr, oct_sub_list, slot_object, ext_cells, ext_list).  *bytes always receives the
+ * obj_ranges, oct_recs, oct_lut, oct_sub_hdr, oct_sub_list, slot_object, ext_cells, ext_list, step_tab).  *bytes always receives the
  * array's size; the bytes are copied to `out` only if cap holds them.  from_device != 0: the device copy, read after a device
  * synchronise (RM_E_NO_DEVICE on a host-only context); 0: the host builder's copy.  RM_E_INVALID for an unknown name,
  * RM_E_NO_SCENE before any scene. */
@@ -945,6 +945,14 @@ RM_API int rm_debug_last_launch(rm_ctx *ctx, uint32_t out[4]);
  * *effective = the workgroups per CU a v2 launch brings for a frame of `items` work items when blocks_per_cu is `asked`
  * (1..8); works on a host-only context (256 CUs). */
 RM_API int rm_debug_overlap_fill(rm_ctx *ctx, int32_t asked, int64_t items, int32_t *effective);
+/* Option step_box (below), for tests and evidence; works on a host-only context except for out[0].  out[0]: whether the last
+ * launch of the v2 wave loop tested its in-round march steps against the scene's step-box table (0 before the first such
+ * launch); out[1]: whether a launch of the active scene would, with the options as they stand -- the launcher's own decision;
+ * out[2]: why not (0: it would; 1: the options step_box, multi_step or kernel, or the kind of scene; 2: the scene has no table --
+ * more than 62 distinct thresholds on an axis, or a face coordinate that is non-zero and below 1e-30 in magnitude; 3: the table
+ * would cost LDS that the launch keeps for the scene, the origin-relative boxes or a workgroup per CU); out[3]: the hit-list
+ * capacity that launch gets, out[4]: what it would get with step_box 0; out[5]: the table's size in bytes (0: none). */
+RM_API int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]);
 /* Diagnostic builds only (make EXTRA=-DRM_STAMPS): start and end time (100 MHz ticks) of the first 8192 waves of the last
  * v2 launch -- out[w] start of the wave loop, out[8192 + w] end, out[16384 + w] kernel entry, 0 where no wave ran
  * (scripts/tail_hist.py). */
@@ -977,6 +985,10 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *                 order gives the same bytes; default 1: a frame alone 1.07 against 1.14 ms; bench.py turns it off with frames in flight)
  *   multi_step 0|1  v2 BVH: a lane takes further march steps inside a round while the leaf set and the winning sphere provably
  *                 stay the same (default 1; same bytes either way)
+ *   step_box 0|1  v2 BVH, those steps: the leaf set at the new point is known to be the round's when the point lies in the same
+ *                 cell of the per-axis thresholds of the leaf boxes (lo, and the next binary32 above hi) as the round's point:
+ *                 six compares against a bracket found once per run, instead of the cell's leaf list per step (default 1; 0, a
+ *                 scene without the table, or a launch whose LDS has no room for it: the exact test; same bytes either way)
  *   lds_fill 0|1  v2: pad the LDS request so that exactly blocks_per_cu workgroups fit a CU (default 0; measurement knob)
  *   min_fill 0|1  v2: a persistent launch brings max(blocks_per_cu, ceil(6 / Q)) workgroups per CU, Q = GPU_MAX_HW_QUEUES as
  *                 rm_create found it (unset or not a positive integer: 4, HIP's default; never set by the library).  Launches

@@ -124,9 +124,53 @@ static int trace(const ro_scene *s, const float *o, const float *dir, Scratch *s
     return n;
 }
 
+/* Round 9: per axis the thresholds lo[k] and nextup(hi[k]) of every leaf box and the root (rm_scene_host.cpp build_step_box),
+ * sorted and distinct: two points in one half-open cell [T_i, T_i+1) on all three axes have the same leaves.  The strict
+ * form, for comparison: thresholds lo[k] and hi[k], cells open on both sides. */
+static float thr[3][4 * MAXL + 4], thr_strict[3][4 * MAXL + 4];
+static int n_thr[3], n_thr_strict[3];
+static int cmp_float(const void *a, const void *b) { float x = *(const float *)a, y = *(const float *)b; return x < y ? -1 : x > y; }
+static int sort_unique(float *v, int n) {
+    qsort(v, (size_t)n, sizeof(float), cmp_float);
+    int m = 0;
+    for (int i = 0; i < n; i++)
+        if (m == 0 || v[i] != v[m - 1]) v[m++] = v[i];
+    return m;
+}
+static void build_thresholds(void) {
+    for (int k = 0; k < 3; k++) {
+        int n = 0, ns = 0;
+        for (int l = -1; l < n_leaf; l++) {
+            const BBox *b = l < 0 ? &root_box : &leaf_box[l];
+            thr[k][n++] = b->min[k];
+            thr[k][n++] = nextafterf(b->max[k], INFINITY);
+            thr_strict[k][ns++] = b->min[k];
+            thr_strict[k][ns++] = b->max[k];
+        }
+        n_thr[k] = sort_unique(thr[k], n);
+        n_thr_strict[k] = sort_unique(thr_strict[k], ns);
+    }
+}
+/* q and p in one cell of the thresholds on every axis? */
+static int same_cell(const float *q, const float *p, int strict) {
+    for (int k = 0; k < 3; k++) {
+        const float *T = strict ? thr_strict[k] : thr[k];
+        const int n = strict ? n_thr_strict[k] : n_thr[k];
+        float lo = -INFINITY, hi = INFINITY;
+        for (int i = 0; i < n; i++) {
+            if (T[i] <= q[k]) lo = T[i];
+            else { hi = T[i]; break; }
+        }
+        if (strict) {
+            if (!(q[k] > lo && p[k] > lo && p[k] < hi)) return 0;
+        } else if (!(p[k] >= lo && p[k] < hi)) return 0;
+    }
+    return 1;
+}
+
 typedef struct {
     const char *name;
-    int exact;      /* 0: the ball of rho and rho_cell; 1: the exact leaf set at p2 */
+    int exact;      /* 0: the ball of rho and rho_cell; 1: the exact leaf set at p2; 2: one half-open threshold cell; 3: one open cell */
     double grow;    /* ball: how far the cell lists are grown */
     double confine; /* exact: p2 stays within q's cell grown by this; < 0: anywhere in the root box */
 } Rule;
@@ -156,6 +200,10 @@ static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e
         }
         float rho_cell = (float)(r->grow + (in_cell > 0 ? in_cell : 0));
         if (!(dd < (rho < rho_cell ? rho : rho_cell))) return rho < rho_cell ? END_SET : END_CELL; /* whichever radius binds */
+    } else if (r->exact >= 2) {
+        if (!same_cell(h->p, e->p, r->exact == 3)) return END_SET;
+        /* the rule's claim, checked against the oracle's sets on every accepted step */
+        if (e->set != h->set || margin(&root_box, e->p) < 0.f) { fprintf(stderr, "threshold rule accepted a step whose leaf set differs\n"); exit(2); }
     } else {
         if (r->confine >= 0)
             for (int k = 0; k < 3; k++) {
@@ -174,6 +222,7 @@ int main(void) {
     if (!s || !s->bvh) return 1;
     collect(s->bvh);
     root_box = s->bvh->bounds;
+    build_thresholds();
     G = (int)ceil(cbrt((double)n_leaf) * 3.0);
     G = G < 2 ? 2 : G > 32 ? 32 : G;
     for (int k = 0; k < 3; k++) {
@@ -189,6 +238,8 @@ int main(void) {
         {"exact set, p2's own cell", 1, 0, -1},
         {"ball kept, lists grown by 0.06", 0, 0.06, 0},
         {"ball kept, lists grown by 0.24", 0, 0.24, 0},
+        {"half-open threshold cells (round 9)", 2, 0, 0},
+        {"open threshold cells", 3, 0, 0},
     };
     enum { NR = sizeof rules / sizeof rules[0] };
     double lane_rounds[NR] = {0}, lane_steps[NR] = {0}, wave_rounds[NR] = {0}, wave_trips[NR] = {0}, ends[NR][N_END] = {{0}};
