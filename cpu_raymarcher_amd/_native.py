@@ -256,6 +256,8 @@ SIGNATURES = {
     "rm_debug_last_launch": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
     "rm_debug_overlap_fill": (C.c_int, [_VP, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "rm_debug_step_box": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "rm_debug_rect_cull": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "rm_debug_leaf_rects": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_rtc_source": (C.c_int, [_VP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_rtc_compile_check": (C.c_int, [_VP, C.c_int32, C.c_int32, C.c_char_p, C.c_int64, C.POINTER(C.c_double)]),
     "rm_rtc_status": (C.c_int, [_VP, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.c_char_p, C.c_int64]),

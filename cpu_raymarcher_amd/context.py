@@ -183,6 +183,31 @@ class Context:
         N.check(self._h, N.lib().rm_debug_step_box(self._h, out))
         return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], list_cap=out[3], list_cap_without=out[4], table_bytes=out[5])
 
+    def rect_cull(self, rot, origin, width, height):
+        """The leaf rectangles of the v2 bundle cull for a camera (rot[9], origin[3]: rm_camera_from_angles) and a full
+        frame (rm_debug_rect_cull; no device needed but for `last`): dict(last = the last v2 launch culled by rectangles,
+        planned = a launch of the active scene with this camera would, reason = why not (0 it would, 1 options or kind
+        of scene, 2 too many leaves, 3 the camera or the frame), leaves, max_leaves)."""
+        r = np.ascontiguousarray(rot, dtype=np.float32).reshape(9)
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+        out = (C.c_int32 * 5)()
+        N.check(self._h, N.lib().rm_debug_rect_cull(self._h, _ptr(r), _ptr(o), int(width), int(height), out))
+        return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], leaves=out[3], max_leaves=out[4])
+
+    def leaf_rects(self, rot, origin, width, height):
+        """The table of leaf screen rectangles such a launch fills, from the kernel's own text on the host
+        (rm_debug_leaf_rects; no device needed): (rects uint16 [n, 4] = inclusive x_lo, x_hi, y_lo, y_hi; nodes int32 [n] =
+        each leaf's index in the scene's BVH table).  n = 0: the launch would take the plane cull."""
+        r = np.ascontiguousarray(rot, dtype=np.float32).reshape(9)
+        o = np.ascontiguousarray(origin, dtype=np.float32).reshape(3)
+        n = C.c_int64(0)
+        N.check(self._h, N.lib().rm_debug_leaf_rects(self._h, _ptr(r), _ptr(o), int(width), int(height), None, None, 0, C.byref(n)))
+        rects = np.zeros((max(1, n.value), 4), np.uint16)
+        nodes = np.zeros(max(1, n.value), np.int32)
+        N.check(self._h, N.lib().rm_debug_leaf_rects(self._h, _ptr(r), _ptr(o), int(width), int(height), _ptr(rects), _ptr(nodes),
+                                                     n.value, C.byref(n)))
+        return rects[:n.value], nodes[:n.value]
+
     # ---- scene ----------------------------------------------------------------------
     def scene_from_preset(self, index, accel):
         N.check(self._h, N.lib().rm_scene_from_preset(self._h, int(index), int(accel)))

@@ -59,11 +59,13 @@ struct SceneDesc {
 
 // The three rings of launch_render.  Per-launch control slots: the 64 queue heads of a v2 launch, 256 bytes apart (rm_render_v2.hip RM_QUEUES, RM_QSTRIDE), and the
 // accumulator block of the fused diagnostics (rm_diag.h).  Zeroed once, in init; every launch's last wave leaves its slots
-// zeroed.  A launch owns what it took until kLaunches - 1 later launches have taken theirs (frames in flight on several streams).
+// zeroed.  Beside a launch's heads, under the same slot number, the table of leaf screen rectangles its workgroups fill
+// (option `rect_cull`; RM_RECT_CULL_MAX_LEAVES entries, written before they are read: never cleared).  A launch owns what it took until kLaunches - 1 later launches have taken theirs (frames in flight on several streams).
 struct LaunchSlots {
     static constexpr unsigned kLaunches = 1024, kHeads = 64, kHeadWords = 64;
     unsigned int *heads = nullptr;  // [kLaunches][kHeads][kHeadWords]
     RmDiagBlock *blocks = nullptr;  // [kLaunches]
+    RmLeafRect *rects = nullptr;    // [kLaunches][RM_RECT_CULL_MAX_LEAVES]
     unsigned int head_slot = 0, block_slot = 0;
 
     hipError_t init() {
@@ -71,12 +73,16 @@ struct LaunchSlots {
         hipError_t e = hipMalloc(reinterpret_cast<void **>(&heads), head_bytes);
         if (e == hipSuccess) e = hipMemset(heads, 0, head_bytes);
         if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&blocks), block_bytes);
-        return e == hipSuccess ? hipMemset(blocks, 0, block_bytes) : e;
+        if (e == hipSuccess) e = hipMemset(blocks, 0, block_bytes);
+        return e == hipSuccess ? hipMalloc(reinterpret_cast<void **>(&rects), sizeof(RmLeafRect) * kLaunches * RM_RECT_CULL_MAX_LEAVES) : e;
     }
     void release() {
         (void)hipFree(heads);
         (void)hipFree(blocks);
+        (void)hipFree(rects);
     }
+    // the rectangle table that goes with the heads take_heads() handed out last
+    RmLeafRect *rects_of_last_heads() { return rects && head_slot ? rects + static_cast<size_t>(RM_RECT_CULL_MAX_LEAVES) * ((head_slot - 1) % kLaunches) : nullptr; }
     unsigned int *take_heads() { return heads ? heads + static_cast<size_t>(kHeads) * kHeadWords * (head_slot++ % kLaunches) : nullptr; }
     RmDiagBlock *take_block() { return blocks ? blocks + block_slot++ % kLaunches : nullptr; }
 };
@@ -432,8 +438,8 @@ struct rm_ctx {
     // that is really there.  0: the floor alone.
     int64_t opt_overlap_fill = 1;
     int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
-    uint32_t last_v2_shape[4] = {0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
-                                               // tested its steps against the step-box table (rm_debug_step_box)
+    uint32_t last_v2_shape[5] = {0, 0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
+                                                  // tested its steps against the step-box table (rm_debug_step_box); whether its cull went by leaf rectangles (rm_debug_rect_cull)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
     int64_t opt_multi_step = 1;  // v2 BVH: in-round march steps (rm_render_v2.hip, section M)
     int64_t opt_step_box = 1;    // ... test their leaf sets against the bracket of the round's point in the scene's threshold tables (rm_scene_host.cpp
@@ -444,6 +450,11 @@ struct rm_ctx {
     int64_t opt_static = 0;  // accepted and ignored since round 3 (a static share of every tile queue, overtaken in round 2; the 64 queue heads of round 3 removed its reason)
     int64_t opt_lut = 1;   // Octree.findNode through the 64^3 cell table
     int64_t opt_cull = 1;     // v2: whole 64-pixel batches find their hit leaves by a bundle-frustum cull instead of the tree walk
+    // v2, with `cull`: the cull compares the batch's pixel rectangle with a per-launch table of leaf screen rectangles instead of
+    // working four planes out per batch and leaf (rm_kernels.h rm_leaf_rect; scenes of up to RM_RECT_CULL_MAX_LEAVES leaves,
+    // cameras rm_rect_cull_camera_ok admits), and a batch without a candidate sets up no ray; 0: the plane cull
+    int64_t opt_rect_cull = 1;
+    std::vector<uint16_t> cull_leaves;  // cull_leaf_table of the active scene (what DeviceScene::bvh_leaves holds; kept for contexts without a device)
     int64_t opt_rel = 1;      // v2: BVH node boxes relative to the frame's ray origin, as doubles in LDS (slab test without conversions)
     int64_t opt_uniform = 1;  // v2: scenes whose spheres all have one radius rank candidates by squared centre distance
     int64_t opt_sub = 1;   // crowded octree leaves scan their sub-cell candidate lists
@@ -588,9 +599,11 @@ const void *rm_rtc_v2_hook(const RmRenderParams &p, int accel, bool lds, bool ur
     if (e.state == 1) return e.k.render;
     if (e.state < 0) return nullptr;
     if (e.state == 0 && ++e.launches < ctx->opt_v2_after) return nullptr;
-    // with the scene's counts as literals first; a kernel refused for spilling (small scenes: their loops unroll) once more without
+    // with the scene's counts as literals first; a kernel refused for spilling (small scenes: their loops unroll) once more without.
+    // Either form, when refused as the compiler's defaults make it, once more without machine-level hoisting (rm_rtc.cpp compile_v2).
     for (;;) {
-        const int st = obtain_kernel(ctx, rmrtc::v2_fixed_source(p, !e.lite), bits, false, length_sqrt, e.k);
+        int st = obtain_kernel(ctx, rmrtc::v2_fixed_source(p, !e.lite), bits, false, length_sqrt, e.k);
+        if (st < 0) st = obtain_kernel(ctx, rmrtc::v2_fixed_source(p, !e.lite), bits | rmrtc::kV2NoLicmBit, false, length_sqrt, e.k);
         e.state = st > 0 ? 1 : (st < 0 ? -1 : 2);
         if (st >= 0 || e.lite) break;
         e.lite = true;
@@ -617,6 +630,8 @@ hipError_t launch_render(rm_ctx *ctx, const RmRenderParams &p_in, RmDiagDevice *
     p.oct_frame = oct_table ? oct_table->dev : nullptr;  // null: the launcher takes render_kernel<1, false, 0>
     if (ctx->opt_lpt && v2) ctx->lpt.acquire(p);  // longest-first item order
     if (v2 && !empty) p.tile_counters = ctx->slots.take_heads();
+    p.leaf_rects = v2 && !empty && p.rect_cull ? ctx->slots.rects_of_last_heads() : nullptr;
+    if (!p.leaf_rects) p.rect_cull = 0;
     // Fused diagnostics (rm_render_attach_diagnostics).  v2 launches always get an accumulator block: their last
     // wave also re-zeroes the launch's queue heads.  A launch without pixels writes the neutral elements.
     p.diag_out = diag_out;
@@ -751,6 +766,7 @@ int upload_scene(rm_ctx *ctx) {
         if (rmh::leaf_objects(ctx->host, prog, ranges, tree, roots))
             ctx->rtc_src = rmrtc::scene_source(prog, ranges, tree, roots, false, ctx->host.bvh, ctx->host.bvh_prims, true);
     }
+    ctx->cull_leaves = cull_leaf_table(ctx->host.bvh);
     if (!ctx->has_device) {
         free_device_scene(ctx);
         return RM_OK;
@@ -764,9 +780,8 @@ int upload_scene(rm_ctx *ctx) {
     if ((always || !ctx->host.name.empty()) && (rc = upload_vec(ctx, ctx->host.name, &ctx->dev.name))) return rc;
     RM_SCENE_ARRAYS(RM_X)
 #undef RM_X
-    const std::vector<uint16_t> leaves = cull_leaf_table(ctx->host.bvh);
-    ctx->dev.bvh_leaf_count = static_cast<int32_t>(leaves.size());
-    return upload_vec(ctx, leaves, &ctx->dev.bvh_leaves);
+    ctx->dev.bvh_leaf_count = static_cast<int32_t>(ctx->cull_leaves.size());
+    return upload_vec(ctx, ctx->cull_leaves, &ctx->dev.bvh_leaves);
 }
 
 int clamp_preset(int idx) { return idx < 0 ? 0 : (idx > rmh::kPresetCount - 1 ? rmh::kPresetCount - 1 : idx); }
@@ -1137,6 +1152,18 @@ struct Staging {
     }
 };
 
+// Why a launch of the active scene with this camera and frame would not cull by leaf rectangles (option `rect_cull`): 0 it would,
+// 1 the options (`rect_cull`, `cull`) or the scene's kind (no BVH, or a tree the cull does not serve), 2 more leaves than
+// a launch keeps rectangles for (the bundle cull itself stops there), 3 the camera (rm_rect_cull_camera_ok) or a frame beyond 65 536 pixels a side.  Whether the
+// launch runs the wave loop at all is fill_params' to say.
+int rect_cull_refusal(const rm_ctx *ctx, const float rot[9], const float origin[3], int32_t width, int32_t height) {
+    if (!ctx->opt_rect_cull || !ctx->opt_cull || ctx->host.accel != RM_ACCEL_BVH) return 1;
+    if (ctx->cull_leaves.size() > RM_RECT_CULL_MAX_LEAVES || (ctx->cull_leaves.empty() && ctx->host.bvh_leaves > RM_RECT_CULL_MAX_LEAVES)) return 2;
+    if (ctx->cull_leaves.empty()) return 1;
+    if (!rm_rect_cull_camera_ok(rot, origin) || width < 1 || height < 1 || width > 65536 || height > 65536) return 3;
+    return 0;
+}
+
 int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     if (!job) return fail(ctx, RM_E_INVALID, "null job");
     if (job->height <= 0 || job->width < 0) return fail(ctx, RM_E_INVALID, "width must be >= 0 and height > 0");
@@ -1214,6 +1241,7 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.pq_list = ctx->dev.pq_list;
     p.bvh_leaves = ctx->dev.bvh_leaves;
     p.bvh_leaf_count = (ctx->opt_cull && ctx->host.accel == RM_ACCEL_BVH) ? ctx->dev.bvh_leaf_count : 0;
+    p.rect_cull = rect_cull_refusal(ctx, p.rot, p.origin, p.width, p.height) == 0 ? 1 : 0;  // (the launch's table: launch_render)
     p.nn_cells = ctx->dev.nn_cells;
     p.nn_list = ctx->dev.nn_list;
     p.nn_cell_count = static_cast<int32_t>(ctx->host.nn_cells.size());
@@ -3144,6 +3172,62 @@ int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]) {
     return RM_OK;
 }
 
+// The leaf rectangles of the bundle cull (option `rect_cull`), without a device.  `rot9` / `origin3`: the camera
+// (rm_camera_from_angles gives a job's), width x height the full frame.  out[0] whether the last v2 launch culled by
+// rectangles (0 before the first), out[1] whether a launch of the active scene with this camera and frame would, out[2] why
+// not (rect_cull_refusal above; 1 also when the options or the scene keep the launch out of the wave loop), out[3] the
+// scene's leaves in the cull's table, out[4] the most a launch keeps rectangles for.
+int rm_debug_rect_cull(rm_ctx *ctx, const float *rot9, const float *origin3, int32_t width, int32_t height, int32_t out[5]) {
+    if (!ctx || !out || !rot9 || !origin3) return RM_E_INVALID;
+    for (int k = 0; k < 5; ++k) out[k] = 0;
+    out[0] = static_cast<int32_t>(ctx->last_v2_shape[4]);
+    out[4] = RM_RECT_CULL_MAX_LEAVES;
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    rm_job job;
+    std::memset(&job, 0, sizeof job);
+    job.width = job.height = job.y_end = 64;
+    job.algorithm = RM_ALG_SPHERE_TRACER;
+    job.scene_preset_index = ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset;
+    job.acceleration_structure = ctx->host.accel;
+    job.overshoot_factor = job.step_size = std::nan("");
+    const double scene_time = ctx->time;
+    RmRenderParams p;
+    const int rc = fill_params(ctx, &job, p);
+    ctx->time = scene_time;  // (a debug read leaves the scene's time alone)
+    if (rc) return rc;
+    out[3] = static_cast<int32_t>(ctx->cull_leaves.size());
+    const bool v2 = p.variant == 2 && p.algorithm == 0 && p.accel == 2;
+    out[2] = v2 ? rect_cull_refusal(ctx, rot9, origin3, width, height) : 1;
+    out[1] = out[2] == 0 ? 1 : 0;
+    return RM_OK;
+}
+
+// The table such a launch's workgroups fill (rm_kernels.h rm_leaf_rect, the text the kernel runs), on the host: entry j, four
+// uint16 x_lo, x_hi, y_lo, y_hi, for node nodes[j] of the scene's BVH.  *n: the entries there are -- 0 when the launch would
+// take the plane cull (rm_debug_rect_cull says why) -- of which the first `cap` are written.  `rects` and `nodes` may be null.
+int rm_debug_leaf_rects(rm_ctx *ctx, const float *rot9, const float *origin3, int32_t width, int32_t height, uint16_t *rects,
+                        int32_t *nodes, int64_t cap, int64_t *n) {
+    if (!ctx || !n || !rot9 || !origin3 || cap < 0) return RM_E_INVALID;
+    *n = 0;
+    int32_t why[5];
+    const int rc = rm_debug_rect_cull(ctx, rot9, origin3, width, height, why);
+    if (rc) return rc;
+    if (!why[1]) return RM_OK;
+    *n = static_cast<int64_t>(ctx->cull_leaves.size());
+    for (int64_t j = 0; j < *n && j < cap; ++j) {
+        const RmBvhNode &nd = ctx->host.bvh[ctx->cull_leaves[static_cast<size_t>(j)]];
+        const RmLeafRect r = rm_leaf_rect(nd.lo, nd.hi, origin3, rot9, width, height);
+        if (rects) {
+            rects[4 * j] = r.x_lo;
+            rects[4 * j + 1] = r.x_hi;
+            rects[4 * j + 2] = r.y_lo;
+            rects[4 * j + 3] = r.y_hi;
+        }
+        if (nodes) nodes[j] = ctx->cull_leaves[static_cast<size_t>(j)];
+    }
+    return RM_OK;
+}
+
 // Every option once: its key, its member of rm_ctx (the defaults and what they were measured against are there; fill_params
 // reads the members), the values it takes and what rm_last_error says of any other.
 enum OptionKind {
@@ -3181,6 +3265,7 @@ static const OptionRow kOptions[] = {
     {"min_fill", &rm_ctx::opt_min_fill, kSwitch, {}, nullptr},
     {"overlap_fill", &rm_ctx::opt_overlap_fill, kSwitch, {}, nullptr},
     {"cull", &rm_ctx::opt_cull, kSwitch, {}, nullptr},
+    {"rect_cull", &rm_ctx::opt_rect_cull, kSwitch, {}, nullptr},
     {"rel", &rm_ctx::opt_rel, kSwitch, {}, nullptr},
     {"static", &rm_ctx::opt_static, kRange, {0, 95}, "static must be in [0, 95] percent"},  // stored, ignored (rm_ctx)
     {"sub", &rm_ctx::opt_sub, kSwitch, {}, nullptr},

@@ -28,6 +28,59 @@ struct RmDiagDevice {  // accumulator of rm_reduce_counters_device (32 bytes)
 #define RM_LEN_IS_SQRT false
 #endif
 
+// The screen rectangle of a leaf box under a launch's camera (RmLeafRect; option `rect_cull`): one text for the wave loop,
+// which fills the launch's table with it, and for rm_debug_leaf_rects, which needs no device.  make_ray sends pixel (x, y) of
+// the W x H frame along d = u c0 + v c1 - c2 with u = (x / W - 0.5) * 2, v = (y / H - 0.5) * 2 and c0, c1, c2 the columns of
+// `rot`.  With orthonormal columns a point q = s d (s >= 0) of that ray, taken from the camera position, has -q.c2 = s and
+// q.c0 = s u, q.c1 = s v: the ray passes through a box only if (u, v) lies in the box's image under q -> (q.c0, q.c1) / z,
+// z = -q.c2.  Where z > 0 on all of the box, each coordinate is a ratio of linear functions with a positive denominator, which
+// takes its extremes over a box at corners: the image lies in [min u, max u] x [min v, max v] over the eight corners.
+//   * binary64 throughout; host and device compile it without contraction, so both give the same table;
+//   * a corner with z at or below 1e-6 of its own L1 norm (at or behind the camera plane, or NaN) gives the whole frame;
+//   * the rectangle is widened by what the plane cull widens its bundle by, half a pixel spacing max(1 / W, 1e-4) -- a
+//     thousand times the rounding of a ray direction to binary32 and of the columns' departure from orthonormal that
+//     rm_rect_cull_camera_ok admits (each moves u by less than 1e-5 inside the frame) -- plus 1e-6 (1 + |u|) for this function's own roundings;
+//   * pixel bounds are rounded outwards and clamped to 0 .. 65535: W, H <= 65536 is the caller's to check;
+//   * a rectangle that misses the frame on one side holds no pixel; anything non-finite gives the whole frame.
+inline __host__ __device__ RmLeafRect rm_leaf_rect(const float lo[3], const float hi[3], const float o[3], const float rot[9], int W, int H) {
+    const RmLeafRect whole = {0, 65535, 0, 65535}, none = {65535, 0, 65535, 0};
+    double ql[3], qh[3];
+    for (int k = 0; k < 3; ++k) {
+        ql[k] = static_cast<double>(lo[k]) - static_cast<double>(o[k]);
+        qh[k] = static_cast<double>(hi[k]) - static_cast<double>(o[k]);
+    }
+    double umin = 0.0, umax = 0.0, vmin = 0.0, vmax = 0.0;
+    bool behind = false;
+#pragma unroll 1  // (in the wave loop's kernel: eight corners side by side, two divisions each, would want more registers than it has)
+    for (int corner = 0; corner < 8; ++corner) {
+        const double qx = (corner & 1) ? qh[0] : ql[0], qy = (corner & 2) ? qh[1] : ql[1], qz = (corner & 4) ? qh[2] : ql[2];
+        const double z = -(qx * rot[6] + qy * rot[7] + qz * rot[8]);
+        const double a = qx * rot[0] + qy * rot[1] + qz * rot[2];
+        const double b = qx * rot[3] + qy * rot[4] + qz * rot[5];
+        if (!(z > 1e-6 * (__builtin_fabs(qx) + __builtin_fabs(qy) + __builtin_fabs(qz)))) behind = true;
+        const double u = a / z, v = b / z;
+        if (corner == 0 || u < umin) umin = u;
+        if (corner == 0 || u > umax) umax = u;
+        if (corner == 0 || v < vmin) vmin = v;
+        if (corner == 0 || v > vmax) vmax = v;
+    }
+    if (behind) return whole;
+    const double mu = __builtin_fmax(1.0 / W, 1e-4), mv = __builtin_fmax(1.0 / H, 1e-4);
+    // pixel x has u = (x / W - 0.5) * 2: x = (u / 2 + 0.5) W
+    const double xl = ((umin - mu - 1e-6 * (1.0 + __builtin_fabs(umin))) * 0.5 + 0.5) * W;
+    const double xh = ((umax + mu + 1e-6 * (1.0 + __builtin_fabs(umax))) * 0.5 + 0.5) * W;
+    const double yl = ((vmin - mv - 1e-6 * (1.0 + __builtin_fabs(vmin))) * 0.5 + 0.5) * H;
+    const double yh = ((vmax + mv + 1e-6 * (1.0 + __builtin_fabs(vmax))) * 0.5 + 0.5) * H;
+    if (!(xl - xl == 0.0 && xh - xh == 0.0 && yl - yl == 0.0 && yh - yh == 0.0)) return whole;  // an infinity or a NaN
+    if (xh < 0.0 || yh < 0.0 || xl > W - 1.0 || yl > H - 1.0) return none;
+    RmLeafRect r;
+    r.x_lo = static_cast<uint16_t>(xl <= 0.0 ? 0 : (xl >= 65535.0 ? 65535 : static_cast<int>(__builtin_floor(xl))));
+    r.x_hi = static_cast<uint16_t>(xh >= 65535.0 ? 65535 : static_cast<int>(__builtin_ceil(xh)));
+    r.y_lo = static_cast<uint16_t>(yl <= 0.0 ? 0 : (yl >= 65535.0 ? 65535 : static_cast<int>(__builtin_floor(yl))));
+    r.y_hi = static_cast<uint16_t>(yh >= 65535.0 ? 65535 : static_cast<int>(__builtin_ceil(yh)));
+    return r;
+}
+
 // rm_compare_frames_device (rm_frame_ops.hip, compare_kernel).  The maps are rm_compare_map's values.
 enum { RM_CMP_NONE = -1, RM_CMP_SDF = 0, RM_CMP_ITERS = 1, RM_CMP_DEPTH = 2, RM_CMP_NORMAL = 3, RM_CMP_SURFACE = 4 };
 struct RmCompareStats {  // rm_compare_stats: sums = sum_sdf_a .. a_cheaper in the order of the header
@@ -221,7 +274,8 @@ hipError_t rm_launch_hypot64(const double *xyz, int64_t n, double *out, hipStrea
 
 // Renders rows [y_start, y_end) (runRaymarcher + optional fused shade).  *kernel_name (optional) receives the
 // instantiation that was launched (static string); v2_shape (optional) what a launch of the v2 wave loop was launched with:
-// workgroups, threads per workgroup, dynamic LDS bytes (left alone by every other launch).
+// workgroups, threads per workgroup, dynamic LDS bytes, whether it took the step-box table and whether the leaf rectangles:
+// five words (left alone by every other launch).
 hipError_t rm_launch_render(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape = nullptr);
 hipError_t rm_launch_render_sqrt(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape = nullptr);
 
@@ -244,6 +298,22 @@ inline int rm_v2_overlap_per_cu(int floor_per_cu, int candidate, long long items
     const long long needed = (items + 3) / 4, resident = static_cast<long long>(cus) * candidate;
     const long long waves = 4 * (needed < resident ? needed : resident);
     return items >= RM_V2_OVERLAP_ITEMS_PER_WAVE * waves ? candidate : floor_per_cu;
+}
+
+// Whether rm_leaf_rect's premise holds for a camera: finite, and the columns of `rot` orthonormal within 1e-6 (every pairwise
+// dot product against the identity, in binary64; a rotation rounded to binary32 is within 2e-7).  One definition for
+// fill_params and the debug entries.
+inline bool rm_rect_cull_camera_ok(const float rot[9], const float origin[3]) {
+    for (int k = 0; k < 3; ++k)
+        if (!(origin[k] - origin[k] == 0.f)) return false;
+    for (int i = 0; i < 3; ++i)
+        for (int j = i; j < 3; ++j) {
+            double d = 0.0;
+            for (int k = 0; k < 3; ++k) d += static_cast<double>(rot[3 * i + k]) * static_cast<double>(rot[3 * j + k]);
+            const double err = d - (i == j ? 1.0 : 0.0);
+            if (!(err >= -1e-6 && err <= 1e-6)) return false;
+        }
+    return true;
 }
 
 // What a launch of the v2 wave loop keeps in LDS, decided from its parameters alone (no device): the scene's tables (lds), the

@@ -707,12 +707,29 @@ __device__ __forceinline__ bool bundle_misses_box(const Bundle &b, const float l
     return miss;
 }
 
+// Option `rect_cull` (round 10): the plane cull is a rectangle-overlap test in screen space worked out the long way -- the four
+// planes pass through the camera position and the columns of `rot` are orthonormal, so "the box lies entirely on the wrong
+// side of the left plane" is "the box's largest u is below u0".  A leaf's screen rectangle depends on the camera and the
+// scene, not on the batch: every workgroup works the launch's table out once (render_v2_body, rm_leaf_rect) and the cull of
+// a batch is four integer compares of its pixel rectangle [x0, x1] x [y0, y1] against the lane's entry (rect_overlaps).
+// The refill section forms the candidate ballot of the table's first 64 leaves itself, ahead of the rays -- it needs it to
+// skip the ray set-up of a batch without a candidate, and asks for the lane's rectangle ahead of the tile claim -- and hands
+// it in (cand0); a scene with more leaves reads the rectangles of its further trips here.  `rect` is wave-uniform; without
+// it the plane cull runs as it did.
+__device__ __forceinline__ bool rect_overlaps(const RmLeafRect &q, int x0, int x1, int y0, int y1) {
+    return x0 <= static_cast<int>(q.x_hi) && x1 >= static_cast<int>(q.x_lo) && y0 <= static_cast<int>(q.y_hi) && y1 >= static_cast<int>(q.y_lo);
+}
+
 template <bool REL>
-__device__ bool bvh_prologue_cull(const SceneView &S, const RmRenderParams &C, const Bundle &B, bool active, const Ray &r,
+__device__ bool bvh_prologue_cull(const SceneView &S, const RmRenderParams &C, int x0, int x1, int y0, int y1, bool rect,
+                                  unsigned long long cand0, bool active, const Ray &r,
                                   const RayInv &ri, RayList &L, Interval &first, int lane) {
     bool have = false;
     L.cnt = 0;
-    {   // the root first: a batch of background rays ends here, as it does in the tree walk
+    // the root first: a batch of background rays ends here, as it does in the tree walk.  Not with rectangles: a batch whose
+    // rays all miss the root has next to no candidate (the leaves lie inside the root), every ray that misses the root fails the
+    // exact test of each of them, and the lists come out empty all the same -- the root's slab test per batch buys nothing
+    if (!rect) {
         const RmBvhNode root = S.nodes[0];
         double tE = 0.0, tX = 0.0;
         const bool hit = active && node_slab<REL>(S, root, 0, r, ri, tE, tX) && !(tX < 0.0) && !(tE > RM_MAX_DIST);
@@ -723,16 +740,22 @@ __device__ bool bvh_prologue_cull(const SceneView &S, const RmRenderParams &C, c
         active = hit;  // a ray that misses the root hits no leaf
     }
     const float o[3] = {C.origin[0], C.origin[1], C.origin[2]};
+    Bundle B = {};
+    if (!rect) B = make_bundle(C, x0, x1, y0, y1);
     for (int j0 = 0; j0 < C.bvh_leaf_count; j0 += 64) {  // wave-uniform trip count
         const int j = j0 + lane;
         int li = 0;
         bool cand = false;
         if (j < C.bvh_leaf_count) {
             li = C.bvh_leaves[j];
-            const RmBvhNode nd = S.nodes[li];
-            cand = !bundle_misses_box(B, nd.lo, nd.hi, o);
+            if (!rect) {
+                const RmBvhNode nd = S.nodes[li];
+                cand = !bundle_misses_box(B, nd.lo, nd.hi, o);
+            } else if (j0 != 0) {
+                cand = rect_overlaps(C.leaf_rects[j], x0, x1, y0, y1);
+            }
         }
-        unsigned long long m = __ballot(cand);
+        unsigned long long m = rect && j0 == 0 ? cand0 : __ballot(cand);
         while (m) {  // survivors in increasing node index = traversal order
             const int src = __builtin_ctzll(m);
             m &= m - 1;
@@ -1003,6 +1026,19 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
     if (lane == 0 && P.stamps && blockIdx.x * 4 + wave < 8192) P.stamps[40 + 2 * 8192 + blockIdx.x * 4 + wave] = __builtin_amdgcn_s_memrealtime();
 #endif
 
+    // Option `rect_cull`: the launch's table of leaf screen rectangles, one leaf per lane, in the launch's own ring slot.
+    // Every workgroup writes all of it (the same values: a function of the kernel arguments alone) and reads only its own
+    // writes, behind a workgroup barrier -- the one that ends the staging below where there is one.  Not in LDS: the Dense
+    // Grid launch has 288 bytes left under the six-workgroups-per-CU budget and the table is 512.
+    if (ACCEL == 2 && P.rect_cull) {
+        const float o[3] = {P.origin[0], P.origin[1], P.origin[2]};
+        const float rot[9] = {P.rot[0], P.rot[1], P.rot[2], P.rot[3], P.rot[4], P.rot[5], P.rot[6], P.rot[7], P.rot[8]};
+        for (int j = threadIdx.x; j < P.bvh_leaf_count && j < RM_RECT_CULL_MAX_LEAVES; j += blockDim.x) {  // (one trip)
+            const RmBvhNode nd = P.bvh[P.bvh_leaves[j]];
+            P.leaf_rects[j] = rm_leaf_rect(nd.lo, nd.hi, o, rot, P.width, P.height);
+        }
+        if (!LDS) __syncthreads();
+    }
     {   // staged once per persistent workgroup, at the places lds_layout() names
         const LdsLayout lay = lds_layout<ACCEL, LDS, REL>(P);
         if (LDS) {
@@ -1182,6 +1218,11 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
             Q.perm_stride = C.lpt_stride;
             const bool want_tile = !no_more && qpos >= Q.item_px;
             const int lane_r = lane_now();
+            // option `rect_cull`: this lane's entries of the launch's leaf rectangles, asked for ahead of the claim so that the
+            // claim's round trip covers them (a lane without a leaf holds the rectangle without a pixel)
+            const bool rect_batch = ACCEL == 2 && C.rect_cull && n_idle == 64;  // wave-uniform
+            RmLeafRect rect0 = {65535, 0, 65535, 0};
+            if (rect_batch && lane_r < C.bvh_leaf_count) rect0 = C.leaf_rects[lane_r];
             if (want_tile) {
                 // (before the pixel stores are issued: the wait for the claim's answer then covers no store of this refill.
                 // Tried in round 3 and dropped: claiming one item AHEAD so that the answer is never waited for -- no gain with
@@ -1208,6 +1249,22 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                 }
 #endif
             }
+            // the batch's pixel rectangle against the leaf rectangles: the ballot of the first 64 leaves and whether any leaf
+            // beyond them is a candidate -- nothing else of the rectangles is live across the stores and the ray set-up
+            const bool rect_cull_now = rect_batch && !no_more && (qpos & 63) == 0;  // wave-uniform: a whole batch from one sub-tile
+            unsigned long long cand0 = 0;
+            bool cand_beyond = false;
+            if (rect_cull_now) {
+                const int bsub = qpos >> 6;
+                const int bx0 = (tile_col << C.item_w_log2) + bsub * C.sub_dx, br0 = (tile_row << C.tile_h_log2) + bsub * C.sub_dy;
+                const int bx1 = bx0 + C.tile_w - 1, by0 = row_to_y(C, br0), by1 = row_to_y(C, br0 + (64 >> C.tile_w_log2) - 1);
+                cand0 = __ballot(rect_overlaps(rect0, bx0, bx1, by0, by1));
+                for (int j0 = 64; j0 < C.bvh_leaf_count && !cand_beyond; j0 += 64)  // wave-uniform
+                    cand_beyond = __any(j0 + lane_r < C.bvh_leaf_count && rect_overlaps(C.leaf_rects[j0 + lane_r], bx0, bx1, by0, by1));
+            }
+            // No leaf of the launch can be hit by a ray of this batch: every pixel of it takes the result of bvh.ts:190-192
+            // (exactly MAX_DIST, no step, no evaluation) without its ray being set up
+            const bool no_cand = rect_cull_now && cand0 == 0 && !cand_beyond;
             if ((st & (ST_PHASE | ST_PIXEL)) == (PH_DONE | ST_PIXEL)) {
                 store_mine(C);
                 st &= ~ST_PIXEL;
@@ -1231,21 +1288,26 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                     if (px < C.width && prow < C.local_rows) {
                         in_frame = true;
                         pidx = static_cast<uint32_t>(prow) * static_cast<uint32_t>(C.width) + static_cast<uint32_t>(px);
-                        ray = make_ray(C, px, row_to_y(C, prow));
-                        rd = ray.d;
                         counters = 0;
-                        t = 0.0;
-                        st = PH_MARCH | ST_PIXEL;  // no trips yet, no interval, no parallel axis
-                        if (ACCEL == 2) {
-                            ri = make_ray_inv(ray);
-                            inv0 = ri.inv[0];
-                            inv1 = ri.inv[1];
-                            inv2 = ri.inv[2];
-                            st |= ((ri.par[0] ? 1 : 0) | (ri.par[1] ? 2 : 0) | (ri.par[2] ? 4 : 0)) << ST_PAR_SHIFT;
+                        if (no_cand) {  // (wave-uniform) what the cull below would leave: nothing reads the ray of a finished pixel
+                            t = RM_MAX_DIST;
+                            st = PH_DONE | ST_PIXEL;
+                        } else {
+                            ray = make_ray(C, px, row_to_y(C, prow));
+                            rd = ray.d;
+                            t = 0.0;
+                            st = PH_MARCH | ST_PIXEL;  // no trips yet, no interval, no parallel axis
+                            if (ACCEL == 2) {
+                                ri = make_ray_inv(ray);
+                                inv0 = ri.inv[0];
+                                inv1 = ri.inv[1];
+                                inv2 = ri.inv[2];
+                                st |= ((ri.par[0] ? 1 : 0) | (ri.par[1] ? 2 : 0) | (ri.par[2] ? 4 : 0)) << ST_PAR_SHIFT;
+                            }
                         }
                     }
                 }
-                if (ACCEL == 2) {
+                if (ACCEL == 2 && !no_cand) {
 #ifdef RM_STAMPS
                     const unsigned long long t_pr0 = __builtin_amdgcn_s_memtime();
 #endif
@@ -1258,9 +1320,9 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                     if (whole_batch) {
                         const int x0 = (tile_col << C.item_w_log2) + batch_sub * C.sub_dx;
                         const int r0 = (tile_row << C.tile_h_log2) + batch_sub * C.sub_dy;
-                        const Bundle B = make_bundle(C, x0, x0 + Q.tile_w - 1, row_to_y(C, r0),
-                                                     row_to_y(C, r0 + (64 >> C.tile_w_log2) - 1));
-                        hc = bvh_prologue_cull<REL>(scene_view<ACCEL, LDS, REL>(C, smem), C, B, in_frame, ray, ri, L, cur, lane_now());
+                        hc = bvh_prologue_cull<REL>(scene_view<ACCEL, LDS, REL>(C, smem), C, x0, x0 + Q.tile_w - 1, row_to_y(C, r0),
+                                                    row_to_y(C, r0 + (64 >> C.tile_w_log2) - 1), rect_cull_now, cand0, in_frame, ray,
+                                                    ri, L, cur, lane_now());
                     } else if (in_frame) {
                         RM_CNT(15)
                         hc = bvh_prologue<REL>(scene_view<ACCEL, LDS, REL>(C, smem), ray, ri, L, cur);
@@ -1864,6 +1926,10 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     const bool lds = plan.lds, rel = plan.rel;
     p.list_cap = plan.list_cap;
     p.step_box = plan.step_box;
+    // the leaf rectangles need the cull they serve, a slot for the table and a leaf count the slot holds
+    if (p.accel != 2 || !p.leaf_rects || !p.bvh_leaves || p.bvh_leaf_count <= 0 || p.bvh_leaf_count > RM_RECT_CULL_MAX_LEAVES ||
+        p.width > 65536 || p.height > 65536)
+        p.rect_cull = 0;
     const size_t list_bytes = plan.list_bytes, scene_bytes = plan.scene_bytes, rel_bytes = static_cast<size_t>(p.bvh_nodes) * 48;
     size_t shmem = (lds ? scene_bytes : 0) + (rel ? rel_bytes + 16 : 0) + list_bytes + 16;
     // Option `lds_fill`: a launch of k persistent workgroups per CU asks for as much LDS as still lets k of them share a CU, so
@@ -1892,6 +1958,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         shape[1] = 256;
         shape[2] = static_cast<uint32_t>(shmem);
         shape[3] = p.step_box ? 1u : 0u;
+        shape[4] = p.rect_cull ? 1u : 0u;
     }
     // the tile-queue heads are zero: a launch's last wave leaves them so (rm_diag.h).  Without an accumulator block
     // (a caller below the API layer) they are cleared here.

@@ -504,6 +504,7 @@ struct Unit {
     const char *render_fn;    // kernel to look up (out.render)
     const char *distance_fn;  // second kernel (out.distance) or null
     std::string display;      // what rm_last_kernel reports
+    bool no_machine_licm;     // compile without the machine-level hoisting of loop invariants (compile_v2 says when)
     bool no_scratch;          // refuse a kernel that uses scratch at all (the v2 wave loop: the ahead-of-time build holds that line); scene kernels
                               // may carry scratch (the fdlibm tables of rm_jsmath.h), never a spilled VGPR
 };
@@ -551,6 +552,10 @@ bool compile_unit(const Unit &u, bool load_module, Kernel &out, std::string &log
     std::vector<const char *> opts = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-amdgpu-inline-max-bb=100000"};
     // (always: every kernel compiled here is held to zero spilled VGPRs, see below)
     opts.push_back("-Rpass-analysis=kernel-resource-usage");
+    if (u.no_machine_licm) {
+        opts.push_back("-mllvm");
+        opts.push_back("-disable-machine-licm");
+    }
     const auto t0 = std::chrono::steady_clock::now();
     const hiprtcResult res = r.compile(prog, static_cast<int>(opts.size()), opts.data());
     out.compile_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -630,6 +635,7 @@ bool compile(const std::string &scene_src, int accel, bool other, bool length_sq
     u.distance_fn = "rm_rtc_distance";
     u.display = std::string("rm_rtc_render<") + std::to_string(accel) + ", " + (other ? "true" : "false") + ">" + (length_sqrt ? " [length=sqrt]" : "");
     u.no_scratch = false;
+    u.no_machine_licm = false;
     return compile_unit(u, load_module, out, log);
 }
 
@@ -666,7 +672,13 @@ uint64_t v2_fixed_hash(const RmRenderParams &p, int variant_bits) {
     return h;
 }
 
-bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool rel, bool length_sqrt, bool load_module, Kernel &out, std::string &log) {
+// no_machine_licm: the wave loop holds exactly the 80 VGPRs of six waves, and the compiler's machine-level hoisting keeps half
+// a dozen literal operands of the inner loops (scan-key masks, +inf, ...) in VGPRs across the whole wave loop: whether a
+// specialised copy then spills two of the lane-state registers depends on details of unrelated code (round 10: any form of the
+// leaf-rectangle cull did, even as dead code beside a prologue).  Without that pass the literals are materialised where they are
+// used and the copy fits (the second try of rm_rtc_v2_hook).
+bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool rel, bool length_sqrt, bool no_machine_licm, bool load_module, Kernel &out,
+                std::string &log) {
     Unit u;
     u.defines = "#define RM_RTC_V2 1\n#define RM_RTC_V2_ACCEL " + std::to_string(accel) + "\n#define RM_RTC_V2_LDS " + (lds ? "1" : "0") + "\n#define RM_RTC_V2_UR " +
                 (ur ? "1" : "0") + "\n#define RM_RTC_V2_REL " + (rel ? "1" : "0") + "\n" + (length_sqrt ? "#define RM_LENGTH_SQRT 1\n" : "");
@@ -677,6 +689,7 @@ bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool
     u.distance_fn = nullptr;
     u.display = "rm_rtc_render_v2";
     u.no_scratch = true;
+    u.no_machine_licm = no_machine_licm;
     return compile_unit(u, load_module, out, log);
 }
 
@@ -699,7 +712,7 @@ std::string cache_key(int device, const std::string &scene_src, int accel, bool 
     return std::to_string(device) + "|" + std::to_string(accel) + (other ? "|o" : "|s") + (length_sqrt ? "|q|" : "|h|") + (env ? env : "") + "|" + scene_src;
 }
 bool compile_any(const std::string &src, int accel, bool other, bool length_sqrt, Kernel &out, std::string &log) {
-    if (accel & kV2Bit) return compile_v2(src, accel & 3, (accel >> 2) & 1, (accel >> 3) & 1, (accel >> 4) & 1, length_sqrt, true, out, log);
+    if (accel & kV2Bit) return compile_v2(src, accel & 3, (accel >> 2) & 1, (accel >> 3) & 1, (accel >> 4) & 1, length_sqrt, (accel & kV2NoLicmBit) != 0, true, out, log);
     return compile(src, accel, other, length_sqrt, true, out, log);
 }
 // What the cache knows of `key` (the caller holds c.mu): 1 = the kernel (out, and its compile's log), -1 = that its compile

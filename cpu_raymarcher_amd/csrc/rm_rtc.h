@@ -53,7 +53,9 @@ std::string v2_fixed_source(const RmRenderParams &p, bool with_counts);  // with
 uint64_t v2_fixed_hash(const RmRenderParams &p, int variant_bits);  // cheap identity of (configuration, instantiation) for the per-launch lookup
 // accel / lds / ur / rel: the instantiation render_kernel_v2<ACCEL, LDS, UR, REL> the launcher chose.  A kernel that spills or
 // uses scratch is refused (log says so).
-bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool rel, bool length_sqrt, bool load_module, Kernel &out, std::string &log);
+bool compile_v2(const std::string &fixed_src, int accel, bool lds, bool ur, bool rel, bool length_sqrt, bool no_machine_licm, bool load_module, Kernel &out,
+                std::string &log);
+constexpr int kV2NoLicmBit = 1 << 10;  // ... | kV2NoLicmBit: compiled without machine-level loop-invariant hoisting (rm_rtc.cpp compile_v2)
 constexpr int kV2Bit = 1 << 8;  // in the `accel` argument of compile_cached / compile_async: ACCEL | LDS << 2 | UR << 3 | REL << 4 | kV2Bit
 
 // compile(..., load_module = true) through a process-wide cache keyed by (device, source text, accel, other, length): a host

@@ -131,6 +131,16 @@ struct RmFrameView {
 // four-wave workgroups share a CU.  The launcher's LDS budgets and the launch-fill rule of rm_api.cpp go by it.
 #define RM_V2_WAVES 6
 
+// Screen rectangle of a BVH leaf under one launch's camera (rm_kernels.h, rm_leaf_rect): inclusive pixel bounds.  A batch of
+// pixels [x0, x1] x [y0, y1] can hold a ray that hits the leaf only if x0 <= x_hi, x1 >= x_lo, y0 <= y_hi and y1 >= y_lo.
+// Whole frame: {0, 65535, 0, 65535}.  No pixel: {65535, 0, 65535, 0}.
+struct alignas(8) RmLeafRect {  // (one 8-byte load or store)
+    uint16_t x_lo, x_hi, y_lo, y_hi;
+};
+// Leaves a launch keeps rectangles for (one ring slot of 2 KB per launch; a workgroup fills it one leaf per lane); as many
+// as the bundle cull's leaf table may hold.  A scene with more has no rectangles.
+#define RM_RECT_CULL_MAX_LEAVES 256
+
 // Kernel parameters (passed by value).
 struct RmRenderParams {
     int32_t width, height, y_start, y_end;
@@ -264,4 +274,11 @@ struct RmRenderParams {
     float sb_origin[3], sb_inv[3];
     int32_t sb_bins, sb_stride;
     int32_t step_box;
+    // v2 BVH, refill section: the launch's table of leaf screen rectangles (rm_kernels.h, rm_leaf_rect), entry j for node
+    // bvh_leaves[j].  It belongs to the launch, not to the scene -- it depends on the camera -- and lives in a slot of the
+    // launch ring beside the queue heads (rm_api.cpp): every persistent workgroup writes all of it (the same values) before
+    // it reads any of it.  rect_cull: the bundle cull compares the batch's pixel rectangle with these (fill_params decides:
+    // option `rect_cull`, the leaf count, the camera); 0: the plane cull.
+    RmLeafRect *leaf_rects;
+    int32_t rect_cull;
 };

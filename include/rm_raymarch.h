@@ -953,6 +953,20 @@ RM_API int rm_debug_overlap_fill(rm_ctx *ctx, int32_t asked, int64_t items, int3
  * would cost LDS that the launch keeps for the scene, the origin-relative boxes or a workgroup per CU); out[3]: the hit-list
  * capacity that launch gets, out[4]: what it would get with step_box 0; out[5]: the table's size in bytes (0: none). */
 RM_API int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]);
+/* Option rect_cull (below), for tests and evidence; both work on a host-only context (except for out[0]).  rot9 / origin3: a
+ * camera as rm_camera_from_angles gives it; width x height: the full frame.
+ * rm_debug_rect_cull -- out[0]: whether the last launch of the v2 wave loop culled its batches' leaves by screen rectangles (0
+ * before the first such launch); out[1]: whether a launch of the active scene with this camera and frame would; out[2]: why not
+ * (0: it would; 1: the options rect_cull, cull or kernel, or the kind of scene; 2: more leaves than out[4]; 3: the columns of
+ * rot9 are not orthonormal within 1e-6, the camera is not finite, or a side of the frame exceeds 65 536 pixels); out[3]: the
+ * leaves in the cull's table; out[4]: the most a launch keeps rectangles for.
+ * rm_debug_leaf_rects -- the table the workgroups of such a launch fill, from the same text, on the host: per leaf the
+ * inclusive pixel bounds x_lo, x_hi, y_lo, y_hi (four uint16; whole frame 0, 65535, 0, 65535; no pixel 65535, 0, 65535, 0) of
+ * every pixel whose ray can hit the leaf's box, and in nodes[] the leaf's index in the scene's BVH table.  *n: the leaves, of
+ * which the first `cap` are written; 0 when the launch would take the plane cull.  rects and nodes may be null. */
+RM_API int rm_debug_rect_cull(rm_ctx *ctx, const float *rot9, const float *origin3, int32_t width, int32_t height, int32_t out[5]);
+RM_API int rm_debug_leaf_rects(rm_ctx *ctx, const float *rot9, const float *origin3, int32_t width, int32_t height,
+                               uint16_t *rects, int32_t *nodes, int64_t cap, int64_t *n);
 /* Diagnostic builds only (make EXTRA=-DRM_STAMPS): start and end time (100 MHz ticks) of the first 8192 waves of the last
  * v2 launch -- out[w] start of the wave loop, out[8192 + w] end, out[16384 + w] kernel entry, 0 where no wave ran
  * (scripts/tail_hist.py). */
@@ -976,6 +990,10 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *   uniform 0|1   scenes whose spheres share one radius: rank leaf candidates by squared centre distance (v2, default 1)
  *   rel 0|1       BVH node boxes relative to the frame's ray origin, as doubles in LDS, when they fit (v2, default 1)
  *   cull 0|1      whole 64-pixel batches find their hit BVH leaves by a bundle-frustum cull (v2, <= 256 leaves, default 1)
+ *   rect_cull 0|1 v2, with cull: a batch's candidate leaves come from comparing its pixel rectangle with a table of leaf screen
+ *                 rectangles that every workgroup of the launch works out once for the launch's camera, and a batch without a
+ *                 candidate sets up no ray (default 1; 0, more than 256 leaves (no bundle cull at all), or a camera whose axes are not orthonormal: four
+ *                 bundle planes per batch and leaf; same bytes either way; rm_debug_rect_cull)
  *   lds_kb 0|16..64  LDS budget per workgroup the v2 launcher trims the per-ray hit lists to (0, default: as many workgroups per CU
  *                 as the kernel's registers allow -- six, 26 880 bytes each --, then five, then four; 32: five; 40: four)
  *   n0_batch 1..64 BVH (v2): getNormal is deferred until no lane of the wave needs a march distance, then evaluated for all waiting
