@@ -87,6 +87,14 @@ class rm_field_shade(C.Structure):  # include/rm_raymarch.h: struct rm_field_sha
 FIELD_MAPS = {"distance": 0, "count": 1}
 
 
+class rm_point_query(C.Structure):  # include/rm_raymarch.h: struct rm_point_query
+    _fields_ = [("time", C.c_double), ("iso", C.c_double), ("snap_tol", C.c_double), ("snap_steps", C.c_int32), ("flags", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
+RM_POINT_NORMAL = 1
+
+
 class rm_mesh_info(C.Structure):  # include/rm_raymarch.h: struct rm_mesh_info
     _fields_ = [("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("n_holes", C.c_int64), ("reserved", C.c_int64)]
 
@@ -196,6 +204,8 @@ SIGNATURES = {
     "rm_debug_wave_distance": (C.c_int, [_VP, _VP, C.c_int64, _VP, _VP]),
     "rm_scene_field": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, _VP]),
     "rm_scene_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, _VP, _VP]),
+    "rm_scene_points": (C.c_int, [_VP, C.POINTER(rm_point_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "rm_scene_points_device": (C.c_int, [_VP, C.POINTER(rm_point_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_lattice_points": (C.c_int, [C.POINTER(rm_lattice), C.c_int64, C.c_int64, _VP]),
     "rm_shade_field_device": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP, _VP]),
     "rm_shade_field": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP]),

@@ -1,9 +1,13 @@
 """One rm_ctx per GPU (include/rm_raymarch.h "Threading"): owns the device-resident scene."""
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _native as N
+
+# what Context.points returns
+Points = collections.namedtuple("Points", "position dist normal object steps count")
 
 
 def _is_torch(x):
@@ -827,8 +831,81 @@ class Context:
         N.check(self._h, N.lib().rm_shade_field(self._h, C.byref(sh), values.size, _ptr(values), _ptr(rgba)))
         return rgba
 
+    # ---- point queries: distance, normal, object and projection onto the surface ------------
+    @staticmethod
+    def _point_query(normal, snap, tol, iso, time):
+        q = N.rm_point_query()
+        q.time, q.iso, q.snap_tol = float(time), float(iso), float(tol)
+        q.snap_steps = int(snap)
+        q.flags = N.RM_POINT_NORMAL if normal else 0
+        return q
+
+    def _points_device(self, q, points, position, want_normal, want_object):
+        """rm_scene_points_device on torch's current stream for the CUDA tensor `points` (float32 [n, 3], contiguous); the
+        positions go to `position` (which may be `points`).  Returns the other five outputs (None where not asked for)."""
+        import torch
+        n = points.numel() // 3
+        dev = points.device
+        dist = torch.empty(n, dtype=torch.float64, device=dev)
+        nrm = torch.empty((n, 3), dtype=torch.float32, device=dev) if want_normal else None
+        obj = torch.empty(n, dtype=torch.int32, device=dev) if want_object else None
+        steps = torch.empty(n, dtype=torch.int32, device=dev)
+        cnt = torch.empty(n, dtype=torch.int32, device=dev)  # (the u32 counts as an int32 tensor, as ray_march's)
+        N.check(self._h, N.lib().rm_scene_points_device(self._h, C.byref(q), n, _ptr(points), _ptr(position), _ptr(dist), _ptr(nrm), _ptr(obj),
+                                                        _ptr(steps), _ptr(cnt), _current_stream_ptr()))
+        return dist, nrm, obj, steps, cnt
+
+    def points(self, points, normal=True, object=True, snap=0, tol=1e-4, iso=0.0, time=0.0, device=False):
+        """What can be asked about a point (rm_scene_points; the rule is in include/rm_raymarch.h), for float32 [n, 3] points:
+        Scene.getDistance there, getNormal's normal, the object that attains the distance, and -- with snap = K > 0 -- the
+        point moved onto the surface getDistance == iso by up to K steps of its distance along the normal, until
+        |dist - iso| <= tol.  Returns the named tuple Points(position float32 [n, 3], dist float64 [n], normal float32 [n, 3]
+        or None, object int32 [n] or None, steps int32 [n], count uint32 [n]), everything taken at `position` (the points as
+        given with snap = 0), with the scene at `time`; scene_set_time's value is left alone.  numpy in -> numpy out through
+        the host entry (synchronous); a CUDA tensor in, or device=True, -> CUDA tensors through rm_scene_points_device on
+        torch's current stream (count an int32 tensor holding the u32 bits).  An empty octree leaf has a constant distance
+        and so no gradient: a projection wants acceleration None or BVH."""
+        q = self._point_query(normal, snap, tol, iso, time)
+        if _is_torch(points) or device:
+            import torch
+            if self.device < 0:
+                raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance path")
+            if _is_torch(points):
+                if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous() and points.numel() % 3 == 0):
+                    raise ValueError("points must be a contiguous float32 CUDA tensor of [n, 3]")
+                self._same_device(dict(points=points))
+                p = points
+            else:
+                p = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)).to(torch.device("cuda", self.device))
+            pos = torch.empty((p.numel() // 3, 3), dtype=torch.float32, device=p.device)
+            return Points(pos, *self._points_device(q, p, pos, normal, object))
+        p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
+        n = len(p)
+        pos, dist = np.zeros((n, 3), np.float32), np.zeros(n, np.float64)
+        nrm = np.zeros((n, 3), np.float32) if normal else None
+        obj = np.zeros(n, np.int32) if object else None
+        steps, cnt = np.zeros(n, np.int32), np.zeros(n, np.uint32)
+        N.check(self._h, N.lib().rm_scene_points(self._h, C.byref(q), n, _ptr(p), _ptr(pos), _ptr(dist), _ptr(nrm), _ptr(obj), _ptr(steps),
+                                                 _ptr(cnt)))
+        return Points(pos, dist, nrm, obj, steps, cnt)
+
+    def project(self, points, steps=4, tol=1e-4, iso=0.0, time=0.0, device=False):
+        """The snap alone: `points` moved onto the surface getDistance == iso by up to `steps` steps (points(...) without
+        normal and object).  Returns (position, dist, steps)."""
+        r = self.points(points, normal=False, object=False, snap=steps, tol=tol, iso=iso, time=time, device=device)
+        return r.position, r.dist, r.steps
+
+    def _mesh_attributes(self, vertices, iso, time, snap, tol):
+        """The vertices of a mesh (a CUDA tensor) through rm_scene_points_device IN PLACE, K = snap: -> (normals, objects)."""
+        if vertices.numel() == 0:
+            import torch
+            return torch.empty((0, 3), dtype=torch.float32, device=vertices.device), torch.empty(0, dtype=torch.int32, device=vertices.device)
+        _, nrm, obj, _, _ = self._points_device(self._point_query(True, snap, tol, iso, time), vertices, vertices, True, True)
+        return nrm, obj
+
     # ---- meshes: the surface of a distance volume, extracted on the device ------------------
-    def mesh_field(self, values, origin, du, dv, dw, shape, iso=0.0, device=False, triangles=False):
+    def mesh_field(self, values, origin, du, dv, dw, shape, iso=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4,
+                   time=0.0):
         """Surface nets over a volume the caller already holds (rm_mesh_field_device; the rule is in include/rm_raymarch.h):
         `values` is a torch CUDA tensor or a numpy array of nu * nv * nw float64 or float32 values in the lattice's order
         ([nw, nv, nu]); the surface is where they pass `iso` (inside: value < iso).  The counting call, an exact allocation
@@ -836,7 +913,11 @@ class Context:
         per cell the surface passes through, one quad per lattice edge that changes side, wound so that normals point out of
         the inside -- the winding is flipped here when (du, dv, dw) is left-handed, which the C entry does not do.
         triangles=True returns uint32 [2Q, 3] instead, each quad split (0, 1, 2), (0, 2, 3).  device=True returns torch CUDA
-        tensors (the indices an int32 tensor holding the u32 bits)."""
+        tensors (the indices an int32 tensor holding the u32 bits).
+        attributes=True returns (vertices, faces, normals float32 [V, 3], objects int32 [V]): the vertices have been put
+        through rm_scene_points_device in place on the device -- the ACTIVE scene at `time`, this call's iso, K = snap
+        projection steps with tolerance tol (0: the vertices as the mesher left them) -- and carry the normal and the object
+        there (`points`).  The faces do not depend on it."""
         lat = make_lattice(origin, du, dv, dw, shape)
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
@@ -868,23 +949,26 @@ class Context:
         if float(np.dot(u, np.cross(v, w))) < 0:
             quads = quads[:, [0, 3, 2, 1]].contiguous()
         faces = quads[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).contiguous() if triangles else quads
+        out = (vertices, faces) + (self._mesh_attributes(vertices, iso, time, snap, tol) if attributes else ())
         if device:
-            return vertices, faces
-        return vertices.cpu().numpy(), faces.cpu().numpy().view(np.uint32)
+            return out
+        return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
 
-    def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False):
+    def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4):
         """The surface of the active scene over a lattice: `field` samples Scene.getDistance on the device at `time` (float64,
         once; the volume stays there) and `mesh_field` extracts the surface getDistance = iso from it.  Returns what
-        mesh_field returns.  The field under a BVH or an octree is the marchers' bound, not always the exact distance: an
-        offset surface (iso != 0) wants acceleration None."""
+        mesh_field returns (attributes, snap, tol: as there).  The field under a BVH or an octree is the marchers' bound, not
+        always the exact distance: an offset surface (iso != 0) wants acceleration None."""
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
         if self.device < 0:
             raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
         vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
-        return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles)
+        return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
+                               tol=tol, time=time)
 
-    def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None):
+    def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None, attributes=False, snap=0,
+                 tol=1e-4):
         """`mesh` over an axis-aligned lattice of cells[0] x cells[1] x cells[2] cells that covers scene_info()'s root box
         and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
         `box` = (lo, hi) replaces the root box: a scene without a structure reports none."""
@@ -900,7 +984,7 @@ class Context:
         m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
         step = (hi - lo + 2 * m) / c
         return self.mesh(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c), iso=iso, time=time,
-                         device=device, triangles=triangles)
+                         device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
 
     def _same_device(self, bufs):
         for name, b in bufs.items():

@@ -1863,6 +1863,51 @@ int points_call(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, u
     return RM_OK;
 }
 
+// ---- point queries (rm_scene_points)
+
+static_assert(sizeof(rm_point_query) == 40, "rm_point_query layout");
+
+// what both forms of rm_scene_points check, arguments first; host: the points are the caller's host buffer and must be finite
+int check_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float *points, bool host, const void *position, const void *dist,
+                 const void *normal, const void *object, const void *steps, const void *count) {
+    if (!q) return fail(ctx, RM_E_INVALID, "null query");
+    if (q->reserved[0] != 0 || q->reserved[1] != 0) return fail(ctx, RM_E_INVALID, "rm_point_query.reserved must be 0");
+    if (q->flags & ~RM_POINT_NORMAL) return fail(ctx, RM_E_INVALID, "unknown flag bits");
+    if (q->snap_steps < 0 || q->snap_steps > 16) return fail(ctx, RM_E_INVALID, "snap_steps must be in [0, 16]");
+    if (!std::isfinite(q->time) || !std::isfinite(q->iso) || !std::isfinite(q->snap_tol)) return fail(ctx, RM_E_INVALID, "non-finite time, iso or snap_tol");
+    if (q->snap_tol < 0) return fail(ctx, RM_E_INVALID, "snap_tol must be >= 0");
+    if (n < 0 || n > std::numeric_limits<int32_t>::max()) return fail(ctx, RM_E_INVALID, "point count out of range");
+    if (n > 0 && !points) return fail(ctx, RM_E_INVALID, "null point buffer");
+    if (n > 0 && !position && !dist && !normal && !object && !steps && !count) return fail(ctx, RM_E_INVALID, "no output asked for");
+    if (reinterpret_cast<uintptr_t>(dist) & 7) return fail(ctx, RM_E_INVALID, "dist must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(position) | reinterpret_cast<uintptr_t>(normal) | reinterpret_cast<uintptr_t>(object) | reinterpret_cast<uintptr_t>(steps) |
+         reinterpret_cast<uintptr_t>(count) | reinterpret_cast<uintptr_t>(points)) & 3)
+        return fail(ctx, RM_E_INVALID, "points, position, normal, object, steps and count must be 4-byte aligned");
+    if (host)
+        for (int64_t i = 0; i < 3 * n; ++i)
+            if (!std::isfinite(points[i])) return fail(ctx, RM_E_INVALID, "non-finite point");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
+// The parameter block and the query of a point query: the active scene as rm_scene_field passes it, at the query's own time
+// (ctx->time is not touched), ahead-of-time kernels only.
+void fill_points(const rm_ctx *ctx, const rm_point_query *q, RmRenderParams &p, RmPointArgs &a) {
+    std::memset(&p, 0, sizeof p);
+    fill_scene_view(ctx, p);
+    p.time = q->time;
+    p.filter = static_cast<int32_t>(ctx->opt_filter);
+    p.tile_w = 8;
+    p.rtc_function = nullptr;
+    std::memset(&a, 0, sizeof a);
+    a.slot_obj = ctx->dev.slot_object;
+    a.iso = q->iso;
+    a.snap_tol = q->snap_tol;
+    a.snap_steps = q->snap_steps;
+    a.want_normal = (q->flags & RM_POINT_NORMAL) ? 1 : 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -2731,6 +2776,69 @@ int rm_scene_field(rm_ctx *ctx, const rm_lattice *lattice, double *dist, float *
         RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
         if (dist) RM_HIP(ctx, st.out(dist + at, o_dist, 8 * k));
         if (dist32) RM_HIP(ctx, st.out(dist32 + at, o_d32, 4 * k));
+        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
+
+int rm_scene_points_device(rm_ctx *ctx, const rm_point_query *q, int64_t n, const void *d_points, void *d_position, void *d_dist, void *d_normal,
+                           void *d_object, void *d_steps, void *d_count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_points(ctx, q, n, static_cast<const float *>(d_points), false, d_position, d_dist, d_normal, d_object, d_steps, d_count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmPointArgs a;
+    fill_points(ctx, q, p, a);
+    a.points = static_cast<const float *>(d_points);
+    a.position = static_cast<float *>(d_position);
+    a.dist = static_cast<double *>(d_dist);
+    a.normal = static_cast<float *>(d_normal);
+    a.object = static_cast<int32_t *>(d_object);
+    a.steps = static_cast<int32_t *>(d_steps);
+    a.count = static_cast<uint32_t *>(d_count);
+    a.n = n;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_points_sqrt : rm_launch_points)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int rm_scene_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float *points_xyz, float *position, double *dist, float *normal,
+                    int32_t *object, int32_t *steps, uint32_t *count) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_points(ctx, q, n, points_xyz, true, position, dist, normal, object, steps, count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmPointArgs a;
+    fill_points(ctx, q, p, a);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Through the scratch buffer in chunks of at most 4 M points, as the ray queries (ray_call): 12 B per point go up, and only
+    // the outputs asked for are staged and copied back (48 B per point with all six: 192 MB).  The positions are written over the
+    // staged points.
+    const int64_t chunk = n < kRayChunk ? n : kRayChunk;
+    const size_t c = static_cast<size_t>(chunk);
+    Staging st{ctx};
+    const size_t o_pts = st.region(12 * c), o_dist = st.region(dist ? 8 * c : 0), o_nrm = st.region(normal ? 12 * c : 0), o_obj = st.region(object ? 4 * c : 0),
+                 o_steps = st.region(steps ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
+    if ((rc = st.reserve())) return rc;
+    a.points = st.at<const float>(o_pts);
+    a.position = position ? st.at<float>(o_pts) : nullptr;
+    a.dist = dist ? st.at<double>(o_dist) : nullptr;
+    a.normal = normal ? st.at<float>(o_nrm) : nullptr;
+    a.object = object ? st.at<int32_t>(o_obj) : nullptr;
+    a.steps = steps ? st.at<int32_t>(o_steps) : nullptr;
+    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        a.n = m;
+        RM_HIP(ctx, st.in(o_pts, points_xyz + 3 * at, 12 * k));
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_points_sqrt : rm_launch_points)(p, a, ctx->stream, &ctx->last_kernel));
+        if (position) RM_HIP(ctx, st.out(position + 3 * at, o_pts, 12 * k));
+        if (dist) RM_HIP(ctx, st.out(dist + at, o_dist, 8 * k));
+        if (normal) RM_HIP(ctx, st.out(normal + 3 * at, o_nrm, 12 * k));
+        if (object) RM_HIP(ctx, st.out(object + at, o_obj, 4 * k));
+        if (steps) RM_HIP(ctx, st.out(steps + at, o_steps, 4 * k));
         if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
         RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
     }

@@ -203,6 +203,21 @@ struct RmFieldArgs {
     long long block_first;  // set by the launcher: the first of the range's workgroups this launch runs
     unsigned int nu, nv;
 };
+// rm_scene_points (rm_kernels.hip, point_kernel): n points, the query and the outputs, each of which may be null; position may
+// be points (a lane reads its point before it writes)
+struct RmPointArgs {
+    const float *points;      // f32[3n]
+    float *position;          // f32[3n]
+    double *dist;
+    float *normal;            // f32[3n]: zeros without want_normal
+    int32_t *object;          // i32[n], -1 = none: computed only when asked for
+    int32_t *steps;
+    uint32_t *count;
+    const int32_t *slot_obj;  // as RmQueryArgs::slot_obj
+    long long n;
+    double iso, snap_tol;
+    int32_t snap_steps, want_normal;
+};
 // rm_shade_field_device (rm_frame_ops.hip, shade_field_kernel): n values (f64 distances or u32 counts) -> n pixels
 struct RmShadeFieldArgs {
     const void *values;
@@ -374,6 +389,12 @@ hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmRays &r, const R
 // (include/rm_raymarch.h has the rule).  field_kernel, the LDS of rm_launch_distance, ahead-of-time kernels only.
 hipError_t rm_launch_field(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_field_sqrt(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
+
+// Point query (rm_scene_points): distance, gradient, object and up to a.snap_steps projection steps for a.n caller-supplied
+// points, one per lane (include/rm_raymarch.h has the rule).  point_kernel, the launch of rm_launch_field, ahead-of-time
+// kernels only; 0 <= a.n <= INT32_MAX.
+hipError_t rm_launch_points(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_points_sqrt(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
 
 // Surface nets (rm_mesh.hip): count, scan and -- with a capacity above 0 -- the two emit kernels, back to back on `stream`.
 // a.map and a.totals are the caller's scratch; 1 <= a.n <= 2^30.

@@ -424,6 +424,28 @@ __device__ bool bvh_next_interval(const RmRenderParams &P, const Ray &r, const R
 
 // ------------------------------------------------------------------ the render kernel
 
+// raymarcher.ts:123-135 getNormal at `hit`, its first evaluation -- Scene.getDistance(hit) -- handed in as d0: the three
+// offset evaluations are added to count.  hit_normal's arithmetic, and G(p, d) of the point queries (point_kernel).
+template <int ACCEL, int GEN>
+__device__ __forceinline__ Vec3f distance_gradient(const RmRenderParams &P, const Vec3f &hit, double d0, uint32_t &count) {
+    float nx, ny, nz;
+    Vec3f q = hit;
+    q.x = to_f32(static_cast<double>(hit.x) - 0.01);
+    nx = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
+    q = hit;
+    q.y = to_f32(static_cast<double>(hit.y) - 0.01);
+    ny = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
+    q = hit;
+    q.z = to_f32(static_cast<double>(hit.z) - 0.01);
+    nz = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
+    double len = static_cast<double>(nx) * nx + static_cast<double>(ny) * ny + static_cast<double>(nz) * nz;
+    if (len > 0) len = 1 / __builtin_sqrt(len);
+    nx = to_f32(nx * len);
+    ny = to_f32(ny * len);
+    nz = to_f32(nz * len);
+    return Vec3f{nx, ny, nz};
+}
+
 // raymarcher.ts:94-102: the normal at hitPosition = f32(o + d * depth), (0, 0, 0) when depth >= MAX_DIST; getNormal's four
 // evaluations are added to count.  Shared by the render kernels (normal_and_store) and the ray queries (cast_kernel).
 template <int ACCEL, int GEN>
@@ -435,22 +457,11 @@ __device__ __forceinline__ Vec3f hit_normal(const RmRenderParams &P, const Ray &
     float nx = 0.f, ny = 0.f, nz = 0.f;
     if (!(depth >= RM_MAX_DIST)) {
         RM_CNT1(13)
-        // raymarcher.ts:123-135 getNormal
         const double d0 = scene_distance<ACCEL, GEN>(P, hit, count);
-        Vec3f q = hit;
-        q.x = to_f32(static_cast<double>(hit.x) - 0.01);
-        nx = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
-        q = hit;
-        q.y = to_f32(static_cast<double>(hit.y) - 0.01);
-        ny = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
-        q = hit;
-        q.z = to_f32(static_cast<double>(hit.z) - 0.01);
-        nz = to_f32(d0 - scene_distance<ACCEL, GEN>(P, q, count));
-        double len = static_cast<double>(nx) * nx + static_cast<double>(ny) * ny + static_cast<double>(nz) * nz;
-        if (len > 0) len = 1 / __builtin_sqrt(len);
-        nx = to_f32(nx * len);
-        ny = to_f32(ny * len);
-        nz = to_f32(nz * len);
+        const Vec3f n = distance_gradient<ACCEL, GEN>(P, hit, d0, count);
+        nx = n.x;
+        ny = n.y;
+        nz = n.z;
     }
     return Vec3f{nx, ny, nz};
 }
@@ -1342,18 +1353,13 @@ __device__ void pick_list(const RmRenderParams &P, const int32_t *ids, int n, co
     }
 }
 
-// The object a ray hit (include/rm_raymarch.h, rm_ray_pick): -1 for depth >= MAX_DIST, else the lowest-index candidate of
-// Scene.getDistance at hitPosition = f32(o + d * depth) (hit_normal's point) whose Primitive.sdf attains the distance.
+// The object at a point (include/rm_raymarch.h, rm_ray_pick and rm_scene_points): the lowest-index candidate of
+// Scene.getDistance at `hit` whose Primitive.sdf attains the distance; the walk forms that minimum again, so it takes no distance.
 // The candidates are what getDistance evaluates there (scene.ts:144-190): the octree leaf's primitives (none for an empty
 // leaf, all of them outside the cube), the primitives of every BVH leaf whose box contains the point (plain skip-linked
 // walk; all of them when that set is empty), or all.  Not counted: the pick is no part of the reference's work.
 template <int ACCEL, int GEN>
-__device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ray, double depth, const int32_t *slot_obj) {
-    if (depth >= RM_MAX_DIST) return -1;
-    Vec3f hit;
-    hit.x = to_f32(static_cast<double>(ray.o.x) + static_cast<double>(ray.d.x) * depth);
-    hit.y = to_f32(static_cast<double>(ray.o.y) + static_cast<double>(ray.d.y) * depth);
-    hit.z = to_f32(static_cast<double>(ray.o.z) + static_cast<double>(ray.d.z) * depth);
+__device__ __forceinline__ int object_at(const RmRenderParams &P, const Vec3f &hit, const int32_t *slot_obj) {
     double best = RM_MAX_DIST;
     int obj = -1;
     if (ACCEL == 1) {
@@ -1386,6 +1392,65 @@ __device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ra
     }
     pick_list<GEN>(P, nullptr, P.n_prims, slot_obj, hit, best, obj);
     return obj;
+}
+
+// The object a ray hit: -1 for depth >= MAX_DIST, else the object at hitPosition = f32(o + d * depth) (hit_normal's point).
+template <int ACCEL, int GEN>
+__device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ray, double depth, const int32_t *slot_obj) {
+    if (depth >= RM_MAX_DIST) return -1;
+    Vec3f hit;
+    hit.x = to_f32(static_cast<double>(ray.o.x) + static_cast<double>(ray.d.x) * depth);
+    hit.y = to_f32(static_cast<double>(ray.o.y) + static_cast<double>(ray.d.y) * depth);
+    hit.z = to_f32(static_cast<double>(ray.o.z) + static_cast<double>(ray.d.z) * depth);
+    return object_at<ACCEL, GEN>(P, hit, slot_obj);
+}
+
+// ------------------------------------------------------------------ point queries (rm_scene_points)
+//
+// Distance, gradient, object and projection onto the surface for caller-supplied points (include/rm_raymarch.h has the rule):
+// one point per lane, in input order, the field query's launch.  A visit of a point is Scene.getDistance there and -- when a
+// step or the normal is wanted -- getNormal's three further evaluations; the loop below is that visit, so the distance
+// evaluation and the gradient have ONE call site each however many steps a lane takes (a copy of scene_distance per use would
+// multiply the kernel as it would have light_body's marcher).  The last visit's gradient is the normal: a loop that ends on a
+// zero gradient has it already.  Lanes that converge early idle until their wave's last lane has: neighbouring points of a
+// mesh or a hit buffer take about the same number of steps, and compacting them would cost a pass through memory.  A lane
+// reads its point before it writes anything, so A.position may be A.points.
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void point_kernel(const RmRenderParams P, const RmPointArgs A) {
+    const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (i >= A.n) return;
+    Vec3f p{A.points[3 * i], A.points[3 * i + 1], A.points[3 * i + 2]}, g{0.f, 0.f, 0.f};
+    uint32_t count = 0;
+    int32_t steps = 0;
+    double d;
+#pragma unroll 1
+    for (;;) {
+        d = scene_distance<ACCEL, GEN>(P, p, count);
+        const double r = d - A.iso;
+        const bool step = steps < A.snap_steps && __builtin_fabs(r) > A.snap_tol;  // (a NaN r: no step)
+        if (!step && !A.want_normal) break;
+        g = distance_gradient<ACCEL, GEN>(P, p, d, count);
+        if (!step || (g.x == 0.f && g.y == 0.f && g.z == 0.f)) break;
+        p.x = to_f32(static_cast<double>(p.x) + static_cast<double>(g.x) * -r);
+        p.y = to_f32(static_cast<double>(p.y) + static_cast<double>(g.y) * -r);
+        p.z = to_f32(static_cast<double>(p.z) + static_cast<double>(g.z) * -r);
+        ++steps;
+    }
+    if (!A.want_normal) g = Vec3f{0.f, 0.f, 0.f};
+    if (A.position) {
+        A.position[3 * i] = p.x;
+        A.position[3 * i + 1] = p.y;
+        A.position[3 * i + 2] = p.z;
+    }
+    if (A.dist) A.dist[i] = d;
+    if (A.normal) {
+        A.normal[3 * i] = g.x;
+        A.normal[3 * i + 1] = g.y;
+        A.normal[3 * i + 2] = g.z;
+    }
+    if (A.steps) A.steps[i] = steps;
+    if (A.count) A.count[i] = count;
+    if (A.object) A.object[i] = object_at<ACCEL, GEN>(P, p, A.slot_obj);
 }
 
 // ------------------------------------------------------------------ ray queries (rm_ray_march, rm_ray_pick)
@@ -1879,6 +1944,25 @@ hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFiel
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_points)(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n <= 0) return hipSuccess;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    const dim3 grid(static_cast<unsigned>((a.n + 255) / 256)), block(256);  // (a.n <= INT32_MAX: one grid dimension)
+#define RM_PTK(A, O, G)                                                             \
+    {                                                                               \
+        hipLaunchKernelGGL((point_kernel<A, G>), grid, block, shmem, stream, pl, a); \
+        if (kernel_name) *kernel_name = "point_kernel<" #A ", " #G ">" RM_LEN_TAG;  \
+    }
+    RM_DISPATCH(RM_PTK)
+#undef RM_PTK
+    return hipGetLastError();
 }
 
 namespace {

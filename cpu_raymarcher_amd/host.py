@@ -132,15 +132,34 @@ class Scene:
         self._activate()
         return self.ctx.field(origin, du, dv, dw, shape=shape, time=self.time, dist32=dist32, count=count, device=device)
 
+    def getNormal(self, position):
+        """Raymarcher.getNormal (raymarcher.ts:123-135) at a point, at this scene's own time (Context.points): three floats."""
+        self._activate()
+        r = self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), object=False, time=self.time)
+        return [float(x) for x in r.normal[0]]
+
+    def nearestObject(self, position):
+        """Index of the object that attains getDistance at a point (a 3D cursor), at this scene's own time; -1: none."""
+        self._activate()
+        return int(self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), normal=False, time=self.time).object[0])
+
+    def projectToSurface(self, points, steps=4, tol=1e-4):
+        """`points` dropped onto the surface getDistance = 0 at this scene's own time (Context.project) -> (position, dist,
+        steps).  An empty octree leaf has no gradient: wants acceleration None or BVH."""
+        self._activate()
+        return self.ctx.project(points, steps=steps, tol=tol, time=self.time)
+
     def toMesh(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, device=False,
-               triangles=False):
+               triangles=False, attributes=False, snap=0, tol=1e-4):
         """The surface getDistance = iso at this scene's own time as (vertices float32 [V, 3], quads uint32 [Q, 4]) -- or
         triangles uint32 [2Q, 3] --, extracted on the device (Context.mesh): over the lattice origin + i * du + j * dv + k * dw
-        of `shape` points, or, without one, over the root box in `cells` cells (Context.mesh_box)."""
+        of `shape` points, or, without one, over the root box in `cells` cells (Context.mesh_box).  attributes=True adds
+        (normals, objects) per vertex, the vertices snapped onto the surface by up to `snap` steps (Context.mesh_field)."""
         self._activate()
+        more = dict(iso=iso, time=self.time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
         if origin is None:
-            return self.ctx.mesh_box(cells, margin=margin, iso=iso, time=self.time, device=device, triangles=triangles)
-        return self.ctx.mesh(origin, du, dv, dw, shape, iso=iso, time=self.time, device=device, triangles=triangles)
+            return self.ctx.mesh_box(cells, margin=margin, **more)
+        return self.ctx.mesh(origin, du, dv, dw, shape, **more)
 
     def info(self):
         self._activate()
@@ -454,12 +473,33 @@ def diagnostics(ctx, SDFevaluationBuffer, iterationsBuffer):
     return d
 
 
-def save_obj(path, vertices, faces):
+def save_obj(path, vertices, faces, normals=None, objects=None):
     """Writes a mesh as Wavefront OBJ text: one `v x y z` line per vertex (repr of the float32 value: it reads back exactly),
-    one `f a b c [d]` line per face with 1-based indices.  Plain writer: no normals, no materials."""
-    v = np.asarray(vertices.cpu() if _is_torch(vertices) else vertices, np.float32).reshape(-1, 3)
-    f = np.asarray(faces.cpu() if _is_torch(faces) else faces)
+    one `f a b c [d]` line per face with 1-based indices.  With `normals` (float32 [V, 3], one per vertex: what the meshers
+    return with attributes=True) a `vn x y z` line per vertex follows the vertices and the faces read `f a//a b//b ...`.  With
+    `objects` (int32 [V]) the faces are sorted, stably, by the object of their first vertex and each run stands under a
+    `g object_<k>` line (`g background` for -1).  No materials.  With neither: the plain file."""
+    host = lambda a: np.asarray(a.cpu() if _is_torch(a) else a)  # noqa: E731
+    v = host(vertices).astype(np.float32, copy=False).reshape(-1, 3)
+    f = host(faces)
     f = (f.view(np.uint32) if f.dtype == np.int32 else f).astype(np.int64).reshape(len(f), -1) + 1
+    corner = (lambda i: "%d//%d" % (i, i)) if normals is not None else str
+    lines = ["f " + " ".join(corner(int(i)) for i in row) + "\n" for row in f]
+    vn = None if normals is None else host(normals).astype(np.float32, copy=False).reshape(-1, 3)
+    obj = None if objects is None else host(objects).astype(np.int64).reshape(-1)
+    if (vn is not None and len(vn) != len(v)) or (obj is not None and len(obj) != len(v)):
+        raise ValueError("normals and objects must hold one entry per vertex")
     with open(path, "w") as out:
         out.write("".join("v %r %r %r\n" % tuple(float(x) for x in row) for row in v))
-        out.write("".join("f " + " ".join(str(int(i)) for i in row) + "\n" for row in f))
+        if vn is not None:
+            out.write("".join("vn %r %r %r\n" % tuple(float(x) for x in row) for row in vn))
+        if obj is None:
+            out.write("".join(lines))
+            return
+        of_face = obj[f[:, 0] - 1] if len(f) else np.zeros(0, np.int64)
+        last = None
+        for k in np.argsort(of_face, kind="stable"):
+            if last is None or of_face[k] != last:
+                last = of_face[k]
+                out.write("g background\n" if last < 0 else "g object_%d\n" % last)
+            out.write(lines[k])

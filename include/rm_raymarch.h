@@ -542,6 +542,65 @@ RM_API int rm_ray_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const floa
 RM_API int rm_ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs,
                               int32_t cap, void *d_walks, void *d_steps, void *stream);
 
+/* ---- point queries: distance, normal, object and projection onto the surface ------------- */
+
+enum { RM_POINT_NORMAL = 1 };    /* rm_point_query.flags */
+
+typedef struct rm_point_query {  /* 40 bytes */
+    double  time;        /* Scene.updateTime for this query; rm_scene_set_time's value is kept */
+    double  iso;         /* the surface is getDistance == iso; finite */
+    double  snap_tol;    /* finite, >= 0 */
+    int32_t snap_steps;  /* K, 0 .. 16; 0: the points as given */
+    int32_t flags;       /* RM_POINT_NORMAL or 0 */
+    int32_t reserved[2]; /* 0 */
+} rm_point_query;
+
+/* What can be asked about a point, for n caller-supplied points in ONE launch: Scene.getDistance, the normal getNormal
+ * returns there, the object that attains the distance, and the point moved onto the surface getDistance == iso by up to K
+ * steps along the normal -- for the vertices of a mesh, the hit points of a ray query, a 3D cursor, a collision probe.  The
+ * reference has no such entry; everything is built from its own getDistance (scene.ts:144-190) and getNormal
+ * (raymarcher.ts:123-135) only.  The rule, per point p0 (three binary32 values), with D(x) = Scene.getDistance(x) with
+ * Scene.updateTime(q->time), exactly as rm_scene_distance returns it, its primitive count added to count:
+ *     p = p0; steps = 0
+ *     loop:  d = D(p)
+ *            r = d - iso                                              (binary64)
+ *            if steps == K or !(|r| > snap_tol): break                (a NaN r breaks)
+ *            g = G(p, d);  if g == (0, 0, 0): break                   (IEEE ==: -0 is 0)
+ *            p.c = f32((double)p.c + (double)g.c * (-r))              per component c: binary64, no contraction, ONE rounding
+ *            steps += 1
+ *   G(p, d) is getNormal at p with its first evaluation taken as d: q_c = p with component c replaced by
+ *           f32((double)p.c - 0.01); n.c = f32(d - D(q_c)) for c = x, y, z in that order; len = n.x n.x + n.y n.y + n.z n.z in
+ *           binary64, left to right; n.c = f32(n.c * (1 / sqrt(len))) when len > 0, f32(n.c * len) otherwise.  It is the
+ *           arithmetic of the normal rm_ray_march returns, operation for operation; its three evaluations are counted.
+ *   outputs are taken at the final p: position = p; dist = d, the un-offset getDistance, always D(position); steps as
+ *           the loop left it; normal = G(p, d) with RM_POINT_NORMAL, else (0, 0, 0).  G is evaluated at most once per point
+ *           visited: a loop that ended on the zero-gradient break has it already.  count is the primitives of every
+ *           evaluation actually made, exact u32.
+ *   object  follows rm_ray_pick's candidate rule at position with D = dist, without its t >= 10 clause: the candidates are
+ *           what getDistance evaluates there, object is the lowest index whose Primitive.sdf equals D under IEEE ==, the
+ *           lowest NaN candidate when D is NaN, -1 without a match.  It is computed only when the output is non-NULL and adds
+ *           nothing to count.
+ * getDistance is taken as it is: an empty octree leaf answers the constant minDistance * 0.99, so G is (0, 0, 0) there and a
+ * projection stops at once with steps = 0; a projection wants acceleration None or BVH.  With K = 0 and no flags, dist and
+ * count are rm_scene_distance's.
+ * position, normal: f32[3n]; dist: f64[n]; object, steps: i32[n]; count: u32[n]; every output may be NULL.  RM_E_INVALID --
+ * like every argument check ahead of RM_E_NO_DEVICE and RM_E_NO_SCENE -- for a null query, a non-zero reserved, unknown flag
+ * bits, K outside 0 .. 16, a non-finite time, iso or snap_tol, a negative snap_tol, n < 0 or n > INT32_MAX, null points with
+ * n > 0, all six outputs NULL with n > 0, a dist that is not 8-byte or another buffer that is not 4-byte aligned, and a
+ * non-finite point component.  n == 0 is RM_OK.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone; knobs apply as for rm_scene_distance (`filter`,
+ * `length`).  Scenes whose renders run a run-time specialised kernel are served by the ahead-of-time kernels here (same
+ * values).  rm_last_kernel names the point_kernel<ACCEL, GEN> instantiation.  Lanes that converge early idle until their
+ * wave's last lane has.  Host buffers, synchronous, chunked through the context's scratch buffer in chunks of 4 M points;
+ * only the outputs asked for are staged and copied back. */
+RM_API int rm_scene_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float *points_xyz, float *position,
+                           double *dist, float *normal, int32_t *object, int32_t *steps, uint32_t *count);
+
+/* Same with device pointers, asynchronous on `stream`, as rm_ray_march_device: one launch.  The points are not checked
+ * (every loop is bounded by K).  d_position may be d_points: a lane reads its point before it writes. */
+RM_API int rm_scene_points_device(rm_ctx *ctx, const rm_point_query *q, int64_t n, const void *d_points, void *d_position,
+                                  void *d_dist, void *d_normal, void *d_object, void *d_steps, void *d_count, void *stream);
+
 /* The binary32 light direction PhongModel normalises from (1, -1, 1.5) (phongModel.ts:15-16), what RM_SHADE_PHONG and
  * rm_shade_lit shade with; host-only, no ctx.  RM_E_INVALID for a null pointer. */
 RM_API int rm_phong_light(float dir3[3]);
