@@ -165,7 +165,7 @@ EDIT_OPS = {"set": 0, "insert": 1, "remove": 2}
 SCENE_TABLES = {"spheres": "<f4", "radii": "<f8", "bvh": "u1", "bvh_prims": "<i4", "oct": "u1", "oct_prims": "<i4",
                 "pq_cells": "<u4", "pq_list": "<u2", "nn_cells": "<u4", "nn_list": "<u2", "prims": "u1", "prog": "u1",
                 "obj_ranges": "<i4", "oct_recs": "u1", "oct_lut": "<i4", "oct_sub_hdr": "<u4", "oct_sub_list": "u1",
-                "slot_object": "<i4", "ext_cells": "<u4", "ext_list": "<u2", "step_tab": "<u4"}
+                "slot_object": "<i4", "ext_cells": "<u4", "ext_list": "<u2", "step_tab": "<u4", "cell_tab": "<u4"}
 # step_tab (csrc/rm_scene_host.h): look-up bins per axis, one byte each, ahead of the thresholds; thresholds an axis may hold
 STEP_BOX_BINS, STEP_BOX_CAP = 32, 62
 
@@ -266,6 +266,7 @@ SIGNATURES = {
     "rm_debug_last_launch": (C.c_int, [_VP, C.POINTER(C.c_uint32)]),
     "rm_debug_overlap_fill": (C.c_int, [_VP, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "rm_debug_step_box": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "rm_debug_cell_tab": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "rm_debug_rect_cull": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "rm_debug_leaf_rects": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_rtc_source": (C.c_int, [_VP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),

@@ -187,6 +187,17 @@ class Context:
         N.check(self._h, N.lib().rm_debug_step_box(self._h, out))
         return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], list_cap=out[3], list_cap_without=out[4], table_bytes=out[5])
 
+    def cell_tab(self):
+        """Sections B and M of the v2 wave loop and the scene's cell table (rm_debug_cell_tab; no device needed but for
+        `last`): dict(last = the last v2 launch read its candidates from the table, planned = a launch of the active scene
+        would under the options as they stand, reason = why not (0 it would, 1 options, kind of scene or no step-box table
+        in the launch, 2 no table, 3 no room in LDS), list_cap / list_cap_without, table_bytes, per_cu = workgroups of that
+        launch a CU holds, scene_bytes / scene_bytes_without = what the launch stages, cells, records, leaf_sets)."""
+        out = (C.c_int32 * 12)()
+        N.check(self._h, N.lib().rm_debug_cell_tab(self._h, out))
+        return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], list_cap=out[3], list_cap_without=out[4], table_bytes=out[5],
+                    per_cu=out[6], scene_bytes=out[7], scene_bytes_without=out[8], cells=out[9], records=out[10], leaf_sets=out[11])
+
     def rect_cull(self, rot, origin, width, height):
         """The leaf rectangles of the v2 bundle cull for a camera (rot[9], origin[3]: rm_camera_from_angles) and a full
         frame (rm_debug_rect_cull; no device needed but for `last`): dict(last = the last v2 launch culled by rectangles,

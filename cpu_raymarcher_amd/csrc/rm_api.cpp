@@ -36,7 +36,7 @@ namespace {
 #define RM_SCENE_ARRAYS(X)                                                                                                        \
     X(spheres, 1) X(radii, 1) X(bvh, 1) X(bvh_prims, 1) X(oct, 1) X(oct_prims, 1) X(pq_cells, 1) X(pq_list, 1) X(nn_cells, 1)      \
     X(nn_list, 1) X(prims, 1) X(prog, 1) X(obj_ranges, 1) X(oct_recs, 1) X(oct_lut, 1) X(oct_sub_hdr, 1) X(oct_sub_list, 1)       \
-    X(slot_object, 0) X(ext_cells, 1) X(ext_list, 1) X(step_tab, 1)
+    X(slot_object, 0) X(ext_cells, 1) X(ext_list, 1) X(step_tab, 1) X(cell_tab, 1)
 
 struct DeviceScene {
 #define RM_X(name, always) decltype(rmh::HostScene::name)::value_type *name = nullptr;
@@ -438,12 +438,15 @@ struct rm_ctx {
     // that is really there.  0: the floor alone.
     int64_t opt_overlap_fill = 1;
     int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
-    uint32_t last_v2_shape[5] = {0, 0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
-                                                  // tested its steps against the step-box table (rm_debug_step_box); whether its cull went by leaf rectangles (rm_debug_rect_cull)
+    uint32_t last_v2_shape[6] = {0, 0, 0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
+                                                  // tested its steps against the step-box table (rm_debug_step_box); whether its cull went by leaf rectangles (rm_debug_rect_cull);
+                                                  // whether section B read its candidates from the cell table (rm_debug_cell_tab)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
     int64_t opt_multi_step = 1;  // v2 BVH: in-round march steps (rm_render_v2.hip, section M)
     int64_t opt_step_box = 1;    // ... test their leaf sets against the bracket of the round's point in the scene's threshold tables (rm_scene_host.cpp
                                  // build_step_box) where the scene has them and they fit the launch's LDS; 0: the exact test against the leaf lists
+    int64_t opt_cell_tab = 1;    // v2 BVH: section B reads a point's candidate spheres, and section M its step box, from the scene's table of threshold cells
+                                 // (rm_scene_host.cpp build_cell_tab) where the launch takes the step-box table and the cell table fits the LDS the point-query grid frees
     int64_t opt_lds_kb = 0;         // v2: LDS budget per workgroup the launcher trims the hit lists to (0: as many workgroups per CU as the kernel's registers allow; 32: five per CU, 40: four)
     int64_t opt_refill = 64;
     int64_t opt_recs = 1;  // octree leaves read leaf-ordered sphere records
@@ -1272,6 +1275,13 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     }
     p.step_box = (ctx->opt_step_box && ctx->opt_multi_step && ctx->host.accel == RM_ACCEL_BVH && !ctx->host.step_tab.empty() &&
                   (ctx->dev.step_tab || !ctx->has_device)) ? 1 : 0;
+    // ... and the cell table of sections B, M and N: it goes with the step-box table (its records are indices into it)
+    p.cell_tab = ctx->dev.cell_tab;
+    p.ct_rec_off = ctx->host.ct_rec_off;
+    p.ct_list_off = ctx->host.ct_list_off;
+    p.ct_words = static_cast<int32_t>(ctx->host.cell_tab.size());
+    for (int k = 0; k < 3; ++k) p.ct_dim[k] = ctx->host.ct_dim[k];
+    p.cell_on = (ctx->opt_cell_tab && p.step_box && !ctx->host.cell_tab.empty() && (ctx->dev.cell_tab || !ctx->has_device)) ? 1 : 0;
     p.uniform_radius = 0;
     if (ctx->opt_uniform && !ctx->host.general && ctx->host.spheres.size() >= 2 &&
         ctx->host.spheres.size() <= 256) {  // one radius, bit for bit; at most 256 spheres: the scan keys carry the id in eight bits
@@ -3280,6 +3290,53 @@ int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]) {
     return RM_OK;
 }
 
+// Sections B and M of the v2 wave loop and the scene's cell table (option `cell_tab`), without a device: out[0] whether the last
+// v2 launch read its candidates from the table (0 before the first), out[1] whether a launch of the active scene under the
+// options as they stand would (rm_v2_plan), out[2] why not -- 0 it would, 1 the options (`cell_tab`, `step_box`, `multi_step`,
+// `kernel`), the kind of scene or a launch without the step-box table rule it out, 2 the scene has no table, 3 the table would
+// cost the launch a workgroup per CU, hit-list entries or its staging -- out[3] the hit-list capacity that launch gets and
+// out[4] the one it would get with `cell_tab` 0, out[5] the table's size in bytes, out[6] the workgroups of that launch a CU
+// holds by its LDS, out[7] / out[8] the bytes of scene tables it stages and would stage with `cell_tab` 0, out[9] the table's
+// cells, out[10] its records, out[11] its distinct leaf sets.
+int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]) {
+    if (!ctx || !out) return RM_E_INVALID;
+    for (int k = 0; k < 12; ++k) out[k] = 0;
+    out[0] = static_cast<int32_t>(ctx->last_v2_shape[5]);
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    rm_job job;
+    std::memset(&job, 0, sizeof job);
+    job.width = job.height = job.y_end = 64;
+    job.algorithm = RM_ALG_SPHERE_TRACER;
+    job.scene_preset_index = ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset;
+    job.acceleration_structure = ctx->host.accel;
+    job.overshoot_factor = job.step_size = std::nan("");
+    const double scene_time = ctx->time;
+    RmRenderParams p;
+    const int rc = fill_params(ctx, &job, p);
+    ctx->time = scene_time;  // (a debug read leaves the scene's time alone)
+    if (rc) return rc;
+    const auto &tab = ctx->host.cell_tab;
+    out[5] = static_cast<int32_t>(tab.size() * sizeof(uint32_t));
+    if (!tab.empty()) {
+        out[9] = static_cast<int32_t>(tab[0] * tab[1] * tab[2]);
+        out[10] = static_cast<int32_t>(tab[3]);
+        out[11] = static_cast<int32_t>(tab[7]);
+    }
+    RmRenderParams plain = p;
+    plain.cell_on = 0;
+    const RmV2Plan without = rm_v2_plan(plain);
+    out[4] = without.list_cap;
+    out[8] = static_cast<int32_t>(without.lds ? without.scene_bytes : 0);
+    const RmV2Plan plan = rm_v2_plan(p);
+    out[3] = plan.list_cap;
+    out[6] = plan.per_cu;
+    out[7] = static_cast<int32_t>(plan.lds ? plan.scene_bytes : 0);
+    const bool v2 = p.variant == 2 && p.algorithm == 0 && p.accel == 2;
+    out[1] = v2 && plan.cell_on ? 1 : 0;
+    out[2] = out[1] ? 0 : (tab.empty() && v2 && ctx->opt_cell_tab && ctx->opt_step_box && ctx->opt_multi_step ? 2 : (v2 && plan.cell_refused ? 3 : 1));
+    return RM_OK;
+}
+
 // The leaf rectangles of the bundle cull (option `rect_cull`), without a device.  `rot9` / `origin3`: the camera
 // (rm_camera_from_angles gives a job's), width x height the full frame.  out[0] whether the last v2 launch culled by
 // rectangles (0 before the first), out[1] whether a launch of the active scene with this camera and frame would, out[2] why
@@ -3364,6 +3421,7 @@ static const OptionRow kOptions[] = {
     {"lds_kb", &rm_ctx::opt_lds_kb, kZeroOrRange, {16, 64}, "lds_kb must be 0 (auto) or in [16, 64]"},
     {"multi_step", &rm_ctx::opt_multi_step, kSwitch, {}, nullptr},
     {"step_box", &rm_ctx::opt_step_box, kSwitch, {}, nullptr},
+    {"cell_tab", &rm_ctx::opt_cell_tab, kSwitch, {}, nullptr},
     {"item_wide", &rm_ctx::opt_item_wide, kSwitch, {}, nullptr},
     {"prune", &rm_ctx::opt_prune, kSwitch, {}, nullptr},
     {"rtc_spheres", &rm_ctx::opt_rtc_spheres, kRange, {0, 33}, "rtc_spheres must be 0..33"},

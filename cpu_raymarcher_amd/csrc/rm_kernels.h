@@ -335,9 +335,13 @@ inline bool rm_rect_cull_camera_ok(const float rot[9], const float origin[3]) {
 // origin-relative node boxes (rel), list_cap entries of hit list per ray, and the step-box table of section M (step_box: asked
 // for through RmRenderParams::step_box and granted; refused: asked for, but it would have cost the scene's staging, the
 // relative boxes or a workgroup per CU).  tier: which LDS budget the launch reaches (0: the first; rm_render_v2.hip).
+// cell_on: the launch reads its candidates from the scene's cell table and does not stage the point-query grid (asked for
+// through RmRenderParams::cell_on; granted when the step-box table is taken, the scene stays staged, the same budget is
+// reached and the hit lists are no shorter than without it); cell_refused: asked for and not granted.
 struct RmV2Plan {
     bool lds, rel;
-    int list_cap, step_box, tier, refused;
+    int list_cap, step_box, tier, refused, cell_on, cell_refused;
+    int per_cu;  // workgroups of the launch that a CU's LDS holds (at most RM_V2_WAVES: the registers')
     size_t scene_bytes, list_bytes;
 };
 RmV2Plan rm_v2_plan(const RmRenderParams &p);

@@ -284,11 +284,13 @@ __device__ double bvh_distance_wave_seq(const RmRenderParams &P, const SceneView
             const int cy = min(max(static_cast<int>((q.y - P.pq_origin[1]) * P.pq_inv[1]), 0), P.pq_dim[1] - 1);
             const int cz = min(max(static_cast<int>((q.z - P.pq_origin[2]) * P.pq_inv[2]), 0), P.pq_dim[2] - 1);
             in_root = true;
-            const uint32_t cell = S.pq_cells[(cz * P.pq_dim[1] + cy) * P.pq_dim[0] + cx];
+            // (the grid through the kernel argument, global memory whatever the view stages: a launch that takes the cell
+            // table does not stage the grid, and this rare path is the same code with and without it)
+            const uint32_t cell = P.pq_cells[(cz * P.pq_dim[1] + cy) * P.pq_dim[0] + cx];
             const int ccnt = static_cast<int>(cell & 0xFFu);
             if (ccnt == 255) walk_tree = true;  // crowded cell: fall back to the tree walk below
             else {
-                const uint16_t *lst = S.pq_list + (cell >> 8);
+                const uint16_t *lst = P.pq_list + (cell >> 8);
                 for (int e = 0; e < ccnt; ++e) {
                     const RmBvhNode node = S.nodes[lst[e]];
                     if (!box_contains(node.lo, node.hi, q)) continue;
@@ -410,7 +412,8 @@ struct NormalAux {
     int k1;
     float lb2;
     uint32_t found;  // low half: primitives counted (all its users add it to the upper, wrapping half of `counters`); high half: how many of the
-                     // cell's listed leaves contain q (at most 254), or 0xFFFF when the leaves did not come from the cell's list (tree walk)
+                     // cell's listed leaves contain q (at most 254), or 0xFFFF when the leaves did not come from the cell's list (tree walk);
+                     // with the cell table (option `cell_tab`) instead the record of q's threshold cell, whose merged box sections M and N read
     float rho;       // every point within rho (per axis) of q lies in exactly those of the cell's LISTED leaves that q lies in (0: unknown)
     float rho_cell;  // every point within rho_cell (per axis) of q is covered by the leaf list of q's cell: the host grows every
                      // cell's list by 0.0101 (RM_NRM_DELTA and a margin), plus q's own distance to the faces of its cell
@@ -433,10 +436,29 @@ __device__ __forceinline__ float box_margin(const float lo[3], const float hi[3]
     return __builtin_fminf(a, b);
 }
 
+// Option `cell_tab` (round 11): the tables a launch that took the scene's cell table reads (rm_scene_host.cpp build_cell_tab;
+// on false: it did not).  Both pointers are LDS in a launch that stages its scene and global otherwise, decided where
+// the view is formed, at compile time.
+struct CellTabView {
+    const uint32_t *tab;   // the cell table
+    const uint32_t *step;  // the step-box thresholds its indices refer to
+    bool on;               // wave-uniform
+};
+// index of the threshold cell of x on axis k: the look-up byte of x's bin and the walk up (see section M), kept inside the axis
+__device__ __forceinline__ int cell_axis_index(const RmRenderParams &P, const uint32_t *step, int k, float x) {
+    const uint32_t *axis = step + k * P.sb_stride;
+    const int last = P.ct_dim[k] - 1;  // the axis' last cell: T[last] is its last threshold, T[last + 1] = +inf
+    const int b = min(max(static_cast<int>((x - P.sb_origin[k]) * P.sb_inv[k]), 0), P.sb_bins - 1);
+    int i = min(static_cast<int>(reinterpret_cast<const uint8_t *>(axis)[b]), last);
+    const float *T = reinterpret_cast<const float *>(axis + (P.sb_bins >> 2));
+    while (i < last && T[i + 1] <= x) i += 1;
+    return i;
+}
+
 template <bool UR>
 __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S, bool need, const Vec3f &q,
                                     uint32_t &count, int lane, bool coop, bool filter, bool use_grid,
-                                    unsigned long long *dbg_fallback_cycles, NormalAux *aux) {
+                                    unsigned long long *dbg_fallback_cycles, NormalAux *aux, const CellTabView CT) {
     aux->ok = false;
     aux->rho = 0.f;
     aux->rho_cell = 0.f;
@@ -461,7 +483,27 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
         }
         found += static_cast<uint32_t>(cnt);
     };
-    if (need && use_grid) {
+    if (CT.on) {  // wave-uniform
+        // The leaves that contain q, and whether the root does, are a function of q's threshold cell: the cell's record names
+        // the spheres to scan (leaf by leaf, in the order of the lists below) and their number.  No box is tested.
+        if (need) {
+            const int ix = cell_axis_index(P, CT.step, 0, q.x), iy = cell_axis_index(P, CT.step, 1, q.y), iz = cell_axis_index(P, CT.step, 2, q.z);
+            const uint32_t r = reinterpret_cast<const uint16_t *>(CT.tab + 8)[(iz * P.ct_dim[1] + iy) * P.ct_dim[0] + ix];
+            const uint32_t *rec = CT.tab + P.ct_rec_off + 3u * r;
+            const uint32_t w0 = rec[0], w1 = rec[1], w2 = rec[2];
+            in_root = (w0 >> 24) != 0u;
+            const int cnt = static_cast<int>(w1 >> 24);
+            const uint16_t *lst = reinterpret_cast<const uint16_t *>(CT.tab + P.ct_list_off) + (w2 & 0xFFFFu);
+            for (int e = 0; e < cnt; ++e) {
+                const int id = lst[e];
+                RM_CNT(8)
+                scan_sphere<UR>(bs, S.spheres[id], id, q);
+            }
+            found = w2 >> 16;
+            nleaf16 = r << 16;  // the record: sections M and N find the merged box there
+            rho = 0.f;          // (section N works its own out, from the merged box)
+        }
+    } else if (need && use_grid) {
         const RmBvhNode root = S.nodes[0];
         const float m_root = box_margin(root.lo, root.hi, q);
         if (m_root >= 0.f) {
@@ -499,7 +541,7 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
             }
         }
     }
-    if (need && (!use_grid || walk_tree)) {
+    if (need && !CT.on && (!use_grid || walk_tree)) {
         rho = 0.f;  // the fused normal evaluation and the in-round steps rely on the cell's leaf list (grown by RM_NRM_DELTA on the host)
         int i = 0;
         const int n = S.bvh_nodes;
@@ -792,13 +834,13 @@ __device__ bool bvh_prologue_cull(const SceneView &S, const RmRenderParams &C, i
 // they do not fit: the first build spilled 130 SGPRs to VGPR lanes and a tenth of the wave loop's straight-line
 // instructions were v_readlane reloads (4.7 issue cycles each, profiles/r02/valu_issue_costs.json).
 struct LdsLayout {
-    uint32_t nodes, prims, cells, list, oct, oct_prims, spheres, radii, rel, end, step;
+    uint32_t nodes, prims, cells, list, oct, oct_prims, spheres, radii, rel, end, step, ctab;
 };
 // the one definition of the layout, used by the launcher (which writes it into RmRenderParams::lds_off)
 inline LdsLayout lds_layout_host(const RmRenderParams &C, int accel, bool lds, bool rel) {
     auto up = [](uint32_t v) { return (v + 15u) & ~15u; };
     auto words = [](uint32_t count, uint32_t size) { return ((count * size + 3u) / 4u) * 4u; };
-    LdsLayout o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    LdsLayout o = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t off = 0;
     if (lds) {
         if (accel == 2) {
@@ -806,10 +848,14 @@ inline LdsLayout lds_layout_host(const RmRenderParams &C, int accel, bool lds, b
             off += words(static_cast<uint32_t>(C.bvh_nodes), sizeof(RmBvhNode));
             o.prims = off = up(off);
             off += words(static_cast<uint32_t>(C.bvh_prim_count), 4);
-            o.cells = off = up(off);
-            off += words(static_cast<uint32_t>(C.pq_cell_count), 4);
+            o.cells = off = up(off);  // (with the cell table the point-query grid is not staged: nothing of the wave loop reads it in LDS)
+            off += words(static_cast<uint32_t>(C.cell_on ? 0 : C.pq_cell_count), 4);
             o.list = off = up(off);
-            off += words(static_cast<uint32_t>(C.pq_list_count), 2);
+            off += words(static_cast<uint32_t>(C.cell_on ? 0 : C.pq_list_count), 2);
+            if (C.cell_on) {
+                o.ctab = off = up(off);
+                off += static_cast<uint32_t>(C.ct_words) * 4u;
+            }
         } else if (accel == 1) {
             o.oct = off = up(off);
             off += words(static_cast<uint32_t>(C.oct_nodes), sizeof(RmOctNode));
@@ -847,6 +893,7 @@ __device__ __forceinline__ LdsLayout lds_layout(const RmRenderParams &C) {
     o.rel = C.lds_off[8];
     o.end = C.lds_off[9];
     o.step = C.lds_off[10];
+    o.ctab = C.lds_off[11];
     return o;
 }
 template <int ACCEL, bool LDS, bool REL>
@@ -1050,10 +1097,14 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                 stage(smem, off, P.bvh_prims, P.bvh_prim_count);
                 // staged unconditionally: a pointer that is LDS on one path and global on the other is a generic
                 // pointer, and every list read in the leaf loop became a flat_load with a full s_waitcnt
+                // (... unless the launch took the cell table: the hot loops then read that, and the rare paths that still want
+                // the grid read it through the kernel argument)
                 off = lay.cells;
-                stage(smem, off, P.pq_cells, P.pq_cell_count);
+                stage(smem, off, P.pq_cells, P.cell_on ? 0 : P.pq_cell_count);
                 off = lay.list;
-                stage(smem, off, P.pq_list, P.pq_list_count);
+                stage(smem, off, P.pq_list, P.cell_on ? 0 : P.pq_list_count);
+                off = lay.ctab;
+                stage(smem, off, P.cell_tab, P.cell_on ? P.ct_words : 0);
             } else if (ACCEL == 1) {
                 off = lay.oct;
                 stage(smem, off, P.oct, P.oct_nodes);
@@ -1463,14 +1514,20 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
         aux.found = 0;
         aux.rho = 0.f;
         aux.rho_cell = 0.f;
+        // option `cell_tab` (wave-uniform): the candidates from the cell table, with the thresholds its indices name
+        const bool cell_on = ACCEL == 2 && CB.cell_on != 0;
         if (ACCEL == 2) {
+            CellTabView CT;  // (the pointers are formed whether or not the table is there: their address space is then a compile-time fact)
+            CT.tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CB.lds_off[11]) : CB.cell_tab;
+            CT.step = LDS ? reinterpret_cast<const uint32_t *>(smem + CB.lds_off[10]) : CB.step_tab;
+            CT.on = cell_on;
 #ifdef RM_STAMPS
             unsigned long long fbc = 0;
-            dist = bvh_distance_wave<UR>(CB, SB, need, q, evaluated, lane_b, coop, filter, use_grid, &fbc, &aux);
+            dist = bvh_distance_wave<UR>(CB, SB, need, q, evaluated, lane_b, coop, filter, use_grid, &fbc, &aux, CT);
             t_acc_[4] += fbc;
             t_prev_ += fbc;  // keep section 2 = query + leaf evaluation only
 #else
-            dist = bvh_distance_wave<UR>(CB, SB, need, q, evaluated, lane_b, coop, filter, use_grid, nullptr, &aux);
+            dist = bvh_distance_wave<UR>(CB, SB, need, q, evaluated, lane_b, coop, filter, use_grid, nullptr, &aux, CT);
 #endif
         }
         else if (ACCEL == 1) dist = need ? oct_distance_lane(SB, onode, q, evaluated, filter) : RM_MAX_DIST;
@@ -1482,7 +1539,8 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
 
         RM_T(2)
         // ---- C: consume -------------------------------------------------------------------------
-        const bool fuse = ACCEL == 2 && need && (st & ST_PHASE) == PH_N0 && aux.ok && aux.rho > RM_NRM_DELTA;
+        // (with the cell table the stability radius is worked out in section N itself, for the lanes that get there)
+        const bool fuse = ACCEL == 2 && need && (st & ST_PHASE) == PH_N0 && aux.ok && (cell_on || aux.rho > RM_NRM_DELTA);
         const bool was_marching = need && (st & ST_PHASE) == PH_MARCH;
         if (need) {
             const int ph = st & ST_PHASE;
@@ -1556,7 +1614,22 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                     // any other value.
                     const bool step_box = CM.step_box != 0;  // wave-uniform
                     float b_lo[3], b_hi[3];
-                    if (step_box) {
+                    if (step_box && CM.cell_on) {
+                        // Option `cell_tab`: section B found q's cell, and the cell's record names a block of cells with q's
+                        // leaf set and root membership (merged on the host, rm_scene_host.cpp build_cell_tab): its six
+                        // thresholds are the run's box.  The argument above holds for any such block -- every compare that
+                        // decides a leaf or the root answers alike in all its cells -- and a far leaf's threshold inside
+                        // the block no longer ends a run.
+                        const uint32_t *tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CM.lds_off[10]) : CM.step_tab;
+                        const uint32_t *rec = (LDS ? reinterpret_cast<const uint32_t *>(smem + CM.lds_off[11]) : CM.cell_tab) + CM.ct_rec_off + 3u * (aux.found >> 16);
+                        const uint32_t w0 = rec[0], w1 = rec[1];
+#pragma unroll
+                        for (int k = 0; k < 3; ++k) {
+                            const float *T = reinterpret_cast<const float *>(tab + k * CM.sb_stride + (CM.sb_bins >> 2));
+                            b_lo[k] = T[(w0 >> (8 * k)) & 0xFFu];
+                            b_hi[k] = T[(w1 >> (8 * k)) & 0xFFu];
+                        }
+                    } else if (step_box) {
                         const uint32_t *tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CM.lds_off[10]) : CM.step_tab;
                         const int last = CM.sb_stride - (CM.sb_bins >> 2) - 2;  // index of the axis' last threshold slot
                         const float qk[3] = {q.x, q.y, q.z};
@@ -1649,7 +1722,25 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
         // of k1 there, k1 is the minimum (Math.min is order independent): three exact evaluations replace three rounds.
         // A lane for which one of the three checks fails keeps d0 and goes on through PH_N1..PH_N3 as before.
         if (ACCEL == 2 && __any(fuse)) {
-            if (fuse) {
+            bool stable = true;
+            if (fuse && cell_on) {
+                // the leaf set is the same within rho of q per axis: q's distance to the faces of its record's merged box,
+                // T[lo] <= p < T[hi] (an upper threshold is a box's nextup(hi) or a lower face: the margin of RM_NRM_DELTA
+                // covers the ulp as it covers the roundings of the offset points, for |coordinate| < 16)
+                const RmRenderParams CN = cold_params();
+                const uint32_t *tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CN.lds_off[10]) : CN.step_tab;
+                const uint32_t *rec = (LDS ? reinterpret_cast<const uint32_t *>(smem + CN.lds_off[11]) : CN.cell_tab) + CN.ct_rec_off + 3u * (aux.found >> 16);
+                const uint32_t w0 = rec[0], w1 = rec[1];
+                const float qk[3] = {q.x, q.y, q.z};
+                float rho = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(q.x), __builtin_fabsf(q.y)), __builtin_fabsf(q.z)) < 16.0f ? __builtin_inff() : 0.f;
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    const float *T = reinterpret_cast<const float *>(tab + k * CN.sb_stride + (CN.sb_bins >> 2));
+                    rho = __builtin_fminf(rho, __builtin_fminf(qk[k] - T[(w0 >> (8 * k)) & 0xFFu], T[(w1 >> (8 * k)) & 0xFFu] - qk[k]));
+                }
+                stable = rho > RM_NRM_DELTA;
+            }
+            if (fuse && stable) {
                 const SceneView SN = scene_view<ACCEL, LDS, REL>(cold_params(), smem);
                 const RmSphere s1 = SN.spheres[aux.k1];
                 const double r1 = SN.radii[aux.k1];
@@ -1722,7 +1813,8 @@ __global__ __launch_bounds__(256) void wave_distance_kernel(const RmRenderParams
     const SceneView S = scene_view<2, false, false>(P, nullptr);
     uint32_t c = 0;
     NormalAux aux;
-    const double d = bvh_distance_wave<UR>(P, S, need, q, c, static_cast<int>(threadIdx.x & 63), P.coop != 0, P.filter != 0, P.use_grid != 0, nullptr, &aux);
+    const CellTabView CT = {P.cell_tab, P.step_tab, P.cell_on != 0};  // (option `cell_tab`: the same switch as the wave loop's, the tables in global memory)
+    const double d = bvh_distance_wave<UR>(P, S, need, q, c, static_cast<int>(threadIdx.x & 63), P.coop != 0, P.filter != 0, P.use_grid != 0, nullptr, &aux, CT);
     if (need) {
         dist[i] = d;
         count[i] = c;
@@ -1734,7 +1826,8 @@ size_t scene_lds_bytes(const RmRenderParams &p) {
     size_t b = 0;
     if (p.accel == 2) {
         b += up(static_cast<size_t>(p.bvh_nodes) * sizeof(RmBvhNode)) + up(static_cast<size_t>(p.bvh_prim_count) * 4);
-        b += up(static_cast<size_t>(p.pq_cell_count) * 4) + up(static_cast<size_t>(p.pq_list_count) * 2 + 4);
+        if (p.cell_on) b += 2 * 16 + up(static_cast<size_t>(p.ct_words) * 4);  // the cell table in the point-query grid's place
+        else b += up(static_cast<size_t>(p.pq_cell_count) * 4) + up(static_cast<size_t>(p.pq_list_count) * 2 + 4);
     } else if (p.accel == 1) {
         b += up(static_cast<size_t>(p.oct_nodes) * sizeof(RmOctNode)) + up(static_cast<size_t>(p.oct_prim_count) * 4);
     }
@@ -1764,11 +1857,17 @@ RmV2Plan rm_v2_plan(const RmRenderParams &p_in) {
     if (p.leaf_order) p.bvh_prim_count = 0;
     if (p.list_cap < 1) p.list_cap = 1;
     const bool want = p.accel == 2 && p.step_box != 0 && p.multi_step != 0 && p.sb_stride > 0;
-    auto pass = [&](bool with_table) {
+    const bool want_cells = want && p.cell_on != 0 && p.ct_words > 0 && !p.general;
+    auto pass = [&](bool with_table, bool with_cells = false, bool rel_allowed = true, int cap_most = 64) {
         RmRenderParams c = p;
         c.step_box = with_table ? 1 : 0;
+        c.cell_on = with_cells ? 1 : 0;
+        if (!rel_allowed) c.rel_boxes = 0;
+        if (c.list_cap > cap_most) c.list_cap = cap_most;
         RmV2Plan r;
         r.step_box = c.step_box;
+        r.cell_on = c.cell_on;
+        r.cell_refused = 0;
         r.list_cap = c.list_cap;
         r.list_bytes = c.accel == 2 ? static_cast<size_t>(4) * c.list_cap * 128 : 0;
         r.scene_bytes = scene_lds_bytes(c);
@@ -1777,9 +1876,15 @@ RmV2Plan rm_v2_plan(const RmRenderParams &p_in) {
         r.rel = false;
         r.tier = 0;
         r.refused = 0;
-        if (!(r.lds && c.accel == 2)) return r;
         const size_t rel_bytes = static_cast<size_t>(c.bvh_nodes) * 48;
         constexpr size_t kLdsPerCu = 160 * 1024, kGranule = 1280, kStatic = sizeof(WaveDiag) * 4;
+        auto per_cu = [&](const RmV2Plan &v) {  // by the launch's LDS, in whole granules
+            const size_t bytes = (v.lds ? v.scene_bytes : 0) + (v.rel ? rel_bytes + 16 : 0) + v.list_bytes + 16 + kStatic;
+            const size_t n = kLdsPerCu / ((bytes + kGranule - 1) / kGranule * kGranule);
+            return static_cast<int>(n < RM_V2_WAVES ? n : RM_V2_WAVES);
+        };
+        r.per_cu = per_cu(r);
+        if (!(r.lds && c.accel == 2)) return r;
         auto budget_for = [&](size_t bytes) { return bytes / kGranule * kGranule - kStatic; };  // dynamic bytes of a workgroup
         auto fits = [&](size_t extra, int cap, size_t budget) { return r.scene_bytes + extra + static_cast<size_t>(4) * cap * 128 + 16 <= budget; };
         auto trim = [&](size_t extra, size_t budget) {  // largest cap <= list_cap (>= 12, or list_cap itself if smaller) that fits; 0 if none
@@ -1808,13 +1913,29 @@ RmV2Plan rm_v2_plan(const RmRenderParams &p_in) {
             }
             r.rel = false;
         }
+        r.per_cu = per_cu(r);
         return r;
     };
     RmV2Plan plain = pass(false);
     if (!want) return plain;
-    const RmV2Plan with_table = pass(true);
-    if (with_table.lds == plain.lds && with_table.rel == plain.rel && with_table.tier <= plain.tier) return with_table;
+    RmV2Plan with_table = pass(true);
+    if (with_table.lds == plain.lds && with_table.rel == plain.rel && with_table.tier <= plain.tier) {
+        // The cell table (option `cell_tab`) last of all: it needs the step-box table (its records are indices into it) and a
+        // staged scene (the table replaces the staged point-query grid; a launch that reads its tables from global memory
+        // gains nothing), and must cost neither the relative boxes, nor a workgroup per CU, nor an entry of the hit lists.
+        if (want_cells) {
+            // (the LDS the table frees stays free: neither origin-relative boxes the launch did not have nor longer hit
+            // lists -- the launch runs in the instantiation and with the lists it ran with)
+            const RmV2Plan with_cells = pass(true, true, with_table.rel, with_table.list_cap);
+            if (with_cells.lds && with_table.lds && with_cells.rel == with_table.rel && with_cells.tier <= with_table.tier &&
+                with_cells.list_cap >= with_table.list_cap)
+                return with_cells;
+            with_table.cell_refused = 1;
+        }
+        return with_table;
+    }
     plain.refused = 1;
+    plain.cell_refused = want_cells ? 1 : 0;
     return plain;
 }
 #endif
@@ -1926,6 +2047,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     const bool lds = plan.lds, rel = plan.rel;
     p.list_cap = plan.list_cap;
     p.step_box = plan.step_box;
+    p.cell_on = plan.cell_on;
     // the leaf rectangles need the cull they serve, a slot for the table and a leaf count the slot holds
     if (p.accel != 2 || !p.leaf_rects || !p.bvh_leaves || p.bvh_leaf_count <= 0 || p.bvh_leaf_count > RM_RECT_CULL_MAX_LEAVES ||
         p.width > 65536 || p.height > 65536)
@@ -1941,8 +2063,8 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     }
     {
         const LdsLayout lay = lds_layout_host(p, p.accel, lds, rel && p.accel == 2);
-        const uint32_t v[11] = {lay.nodes, lay.prims, lay.cells, lay.list, lay.oct, lay.oct_prims, lay.spheres, lay.radii, lay.rel, lay.end, lay.step};
-        for (int k = 0; k < 11; ++k) p.lds_off[k] = v[k];
+        const uint32_t v[12] = {lay.nodes, lay.prims, lay.cells, lay.list, lay.oct, lay.oct_prims, lay.spheres, lay.radii, lay.rel, lay.end, lay.step, lay.ctab};
+        for (int k = 0; k < 12; ++k) p.lds_off[k] = v[k];
         if (lay.end + list_bytes > shmem) return hipErrorInvalidValue;  // the layout and the allocation come from two formulas: they must agree
     }
     // the workgroups per CU the launch brings: what the caller asked, or what rm_api.cpp raised that to (launch_per_cu, option
@@ -1959,6 +2081,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         shape[2] = static_cast<uint32_t>(shmem);
         shape[3] = p.step_box ? 1u : 0u;
         shape[4] = p.rect_cull ? 1u : 0u;
+        shape[5] = p.cell_on ? 1u : 0u;
     }
     // the tile-queue heads are zero: a launch's last wave leaves them so (rm_diag.h).  Without an accumulator block
     // (a caller below the API layer) they are cleared here.

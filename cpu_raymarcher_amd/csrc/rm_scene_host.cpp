@@ -7,9 +7,11 @@
 #include "rm_scene_host.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
 #include <cstring>
 #include <limits>
+#include <map>
 #include <numeric>
 
 namespace rmh {
@@ -354,6 +356,174 @@ void build_step_box(HostScene &s) {
             bins[b] = static_cast<uint8_t>(i);
         }
     }
+}
+
+// ---- the threshold cells' own table (section B of the v2 wave loop, option `cell_tab`) -------------------------------------
+//
+// The thresholds above cut space into n_x * n_y * n_z half-open cells (n_k = thresholds of axis k + 1: the cells below the
+// first and above the last threshold included), and every point of a cell lies in the same leaves and is in the root box or
+// not as every other.  So what Scene.getDistance needs at a point -- the spheres of the leaves that contain it, in the order
+// the device scans them, and their number -- is a function of the cell, and this table holds it per cell; the device finds the
+// cell with section M's look-up and makes no box test.  Membership is decided here with BoundingBox.contains' own inclusive
+// compares at the cell's representative point, its lower threshold on each axis (-inf for the first cell).
+// Words: [0..2] n_x, n_y, n_z, [3] records, [4] word offset of the records, [5] word offset of the sphere lists, [6] words in
+// all, [7] distinct leaf sets; from word 8 one uint16 per cell ((z * n_y + y) * n_x + x): its record; a record is three words,
+//   lo_x | lo_y << 8 | lo_z << 16 | root << 24,   hi_x | hi_y << 8 | hi_z << 16 | spheres << 24,   list offset | found << 16
+// lo / hi: the cell's merged box as indices into the axis' thresholds (sentinels included: index 0 is -inf), the box being
+// T[lo] <= p < T[hi]; the list offset counts uint16 entries from the lists' start; `found` is the sum of the leaves'
+// primitive counts.  The spheres are listed leaf by leaf in increasing node index -- the order of the point-query lists and
+// of the tree walk -- and inside a leaf in the leaf's own order.  Equal lists are stored once, equal records once.
+// Merged boxes: the cells are visited in index order; a cell that has no record yet grows a block from itself, one layer of
+// cells at a time in the order -x, +x, -y, +y, -z, +z, again and again until no direction accepts a layer (a layer is
+// accepted when every cell of it has the starting cell's leaf set and root membership); the block becomes the record of
+// every cell in it that has none yet.  Blocks may overlap: all that a user of a record relies on is that every cell of its
+// box has the set of the cell that names it.
+// No table: no step-box table, more than kCellTabCells cells, a cell with more than 255 spheres, lists beyond 16 bits.
+void build_cell_tab(HostScene &s) {
+    s.cell_tab.clear();
+    s.ct_dim[0] = s.ct_dim[1] = s.ct_dim[2] = 0;
+    s.ct_rec_off = s.ct_list_off = 0;
+    if (s.step_tab.empty() || s.general || s.program || s.bvh.empty() || s.bvh.size() >= 65536) return;
+    std::vector<float> th[3];
+    size_t cells = 1;
+    for (int k = 0; k < 3; ++k) {
+        const float *T = reinterpret_cast<const float *>(s.step_tab.data() + static_cast<size_t>(k) * s.sb_stride + s.sb_bins / 4);
+        const int slots = s.sb_stride - s.sb_bins / 4;
+        th[k].push_back(T[0]);  // -inf
+        for (int i = 1; i < slots && std::isfinite(T[i]); ++i) th[k].push_back(T[i]);
+        s.ct_dim[k] = static_cast<int>(th[k].size());
+        cells *= th[k].size();
+    }
+    const int nx = s.ct_dim[0], ny = s.ct_dim[1], nz = s.ct_dim[2];
+    auto fail = [&]() {
+        s.cell_tab.clear();
+        s.ct_dim[0] = s.ct_dim[1] = s.ct_dim[2] = 0;
+        s.ct_rec_off = s.ct_list_off = 0;
+    };
+    if (cells > static_cast<size_t>(kCellTabCells)) return fail();
+    std::vector<int> leaves;
+    for (size_t i = 0; i < s.bvh.size(); ++i)
+        if (s.bvh[i].leaf >= 0 && (s.bvh[i].leaf & 0xFF) > 0) leaves.push_back(static_cast<int>(i));
+    auto contains = [](const RmBvhNode &nd, const float p[3]) {
+        return p[0] >= nd.lo[0] && p[0] <= nd.hi[0] && p[1] >= nd.lo[1] && p[1] <= nd.hi[1] && p[2] >= nd.lo[2] && p[2] <= nd.hi[2];
+    };
+    // the key of a cell: its leaf set and root membership, as an id
+    std::map<std::vector<int>, int> set_ids;
+    std::vector<std::vector<int>> sets;
+    std::vector<int> key(cells);
+    for (int z = 0; z < nz; ++z)
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const float p[3] = {th[0][x], th[1][y], th[2][z]};
+                std::vector<int> v;
+                v.push_back(contains(s.bvh[0], p) ? 1 : 0);
+                for (const int i : leaves)
+                    if (contains(s.bvh[i], p)) v.push_back(i);
+                auto it = set_ids.find(v);
+                if (it == set_ids.end()) {
+                    it = set_ids.emplace(v, static_cast<int>(sets.size())).first;
+                    sets.push_back(v);
+                }
+                key[(static_cast<size_t>(z) * ny + y) * nx + x] = it->second;
+            }
+    // a set's sphere list, stored once per distinct list
+    std::vector<uint16_t> lists;
+    std::map<std::vector<uint16_t>, uint32_t> list_at;
+    std::vector<uint32_t> set_w1(sets.size()), set_w2(sets.size());  // spheres << 24; list offset | found << 16
+    for (size_t j = 0; j < sets.size(); ++j) {
+        std::vector<uint16_t> ids;
+        for (size_t e = 1; e < sets[j].size(); ++e) {
+            const RmBvhNode &nd = s.bvh[sets[j][e]];
+            const int first = nd.leaf >> 8, cnt = nd.leaf & 0xFF;
+            for (int k = 0; k < cnt; ++k) {
+                const int32_t id = s.bvh_prims[first + k];
+                if (id < 0 || id >= 65536) return fail();
+                ids.push_back(static_cast<uint16_t>(id));
+            }
+        }
+        if (ids.size() > 255) return fail();
+        auto it = list_at.find(ids);
+        if (it == list_at.end()) {
+            if (lists.size() + ids.size() > 65535) return fail();
+            it = list_at.emplace(ids, static_cast<uint32_t>(lists.size())).first;
+            lists.insert(lists.end(), ids.begin(), ids.end());
+        }
+        set_w1[j] = static_cast<uint32_t>(ids.size()) << 24;
+        set_w2[j] = it->second | (static_cast<uint32_t>(ids.size()) << 16);
+    }
+    // merged boxes and records
+    std::vector<int> rec_of(cells, -1);
+    std::vector<uint32_t> recs;
+    std::map<std::array<uint32_t, 3>, int> rec_ids;
+    const int dim[3] = {nx, ny, nz};
+    for (int z = 0; z < nz; ++z)
+        for (int y = 0; y < ny; ++y)
+            for (int x = 0; x < nx; ++x) {
+                const size_t c = (static_cast<size_t>(z) * ny + y) * nx + x;
+                if (rec_of[c] >= 0) continue;
+                int lo[3] = {x, y, z}, hi[3] = {x + 1, y + 1, z + 1};  // cells lo .. hi - 1
+                auto layer_ok = [&](int axis, int at) {
+                    int a[3] = {lo[0], lo[1], lo[2]}, b[3] = {hi[0], hi[1], hi[2]};
+                    a[axis] = at;
+                    b[axis] = at + 1;
+                    for (int cz = a[2]; cz < b[2]; ++cz)
+                        for (int cy = a[1]; cy < b[1]; ++cy)
+                            for (int cx = a[0]; cx < b[0]; ++cx)
+                                if (key[(static_cast<size_t>(cz) * ny + cy) * nx + cx] != key[c]) return false;
+                    return true;
+                };
+                for (bool grew = kCellTabMerge; grew;) {
+                    grew = false;
+                    for (int axis = 0; axis < 3; ++axis) {
+                        if (lo[axis] > 0 && layer_ok(axis, lo[axis] - 1)) {
+                            lo[axis] -= 1;
+                            grew = true;
+                        }
+                        if (hi[axis] < dim[axis] && layer_ok(axis, hi[axis])) {
+                            hi[axis] += 1;
+                            grew = true;
+                        }
+                    }
+                }
+                const uint32_t root = static_cast<uint32_t>(sets[key[c]][0]);
+                const std::array<uint32_t, 3> w = {
+                    static_cast<uint32_t>(lo[0]) | static_cast<uint32_t>(lo[1]) << 8 | static_cast<uint32_t>(lo[2]) << 16 | root << 24,
+                    static_cast<uint32_t>(hi[0]) | static_cast<uint32_t>(hi[1]) << 8 | static_cast<uint32_t>(hi[2]) << 16 | set_w1[key[c]],
+                    set_w2[key[c]]};
+                auto it = rec_ids.find(w);
+                if (it == rec_ids.end()) {
+                    it = rec_ids.emplace(w, static_cast<int>(recs.size() / 3)).first;
+                    recs.insert(recs.end(), w.begin(), w.end());
+                }
+                for (int cz = lo[2]; cz < hi[2]; ++cz)
+                    for (int cy = lo[1]; cy < hi[1]; ++cy)
+                        for (int cx = lo[0]; cx < hi[0]; ++cx) {
+                            int &r = rec_of[(static_cast<size_t>(cz) * ny + cy) * nx + cx];
+                            if (r < 0) r = it->second;
+                        }
+            }
+    const size_t cell_words = (cells + 1) / 2, list_words = (lists.size() + 1) / 2;
+    s.ct_rec_off = static_cast<int>(8 + cell_words);
+    s.ct_list_off = static_cast<int>(s.ct_rec_off + recs.size());
+    s.cell_tab.assign(static_cast<size_t>(s.ct_list_off) + list_words, 0);
+    uint32_t *w = s.cell_tab.data();
+    w[0] = static_cast<uint32_t>(nx);
+    w[1] = static_cast<uint32_t>(ny);
+    w[2] = static_cast<uint32_t>(nz);
+    w[3] = static_cast<uint32_t>(recs.size() / 3);
+    w[4] = static_cast<uint32_t>(s.ct_rec_off);
+    w[5] = static_cast<uint32_t>(s.ct_list_off);
+    w[6] = static_cast<uint32_t>(s.cell_tab.size());
+    {   // distinct leaf sets (the empty set inside and outside the root box is one set, and two keys)
+        std::vector<std::vector<int>> bare;
+        for (const auto &v : sets) bare.emplace_back(v.begin() + 1, v.end());
+        std::sort(bare.begin(), bare.end());
+        w[7] = static_cast<uint32_t>(std::unique(bare.begin(), bare.end()) - bare.begin());
+    }
+    uint16_t *cw = reinterpret_cast<uint16_t *>(w + 8);
+    for (size_t c = 0; c < cells; ++c) cw[c] = static_cast<uint16_t>(rec_of[c]);
+    std::copy(recs.begin(), recs.end(), w + s.ct_rec_off);
+    if (!lists.empty()) std::memcpy(w + s.ct_list_off, lists.data(), lists.size() * sizeof(uint16_t));
 }
 
 // Nearest-candidate lists for points OUTSIDE the root box.  A ray that has passed the scene still takes one march step per
@@ -817,6 +987,7 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
             s.slot_object.swap(obj);
         }
     }
+    build_cell_tab(s);  // (after the permutation: the table names spheres by their device slots)
     return true;
 }
 

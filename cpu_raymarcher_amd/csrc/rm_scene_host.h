@@ -17,6 +17,16 @@ constexpr int kStepBoxCap = 62;   // distinct thresholds per axis a step-box tab
 // and the 288 bytes its launch has left below the six-workgroups-per-CU budget hold it without a shorter hit list (13 entries);
 // its thresholds are 0.15 apart at least, a bin is 0.089 wide, so a bin still holds one threshold at most
 constexpr int kStepBoxBins = 32;
+// threshold cells a cell table (build_cell_tab) may have: two bytes each, and the table must fit the LDS that the point-query
+// grid frees in a launch that takes it (from that budget, not from a measurement)
+constexpr int kCellTabCells = 4096;
+// false (a measurement build, EXTRA=-DRM_CELL_TAB_SINGLE): every cell's box is the cell itself -- the arm that separates the
+// table's two gains, the look-up in place of the box tests and the merged boxes
+#ifdef RM_CELL_TAB_SINGLE
+constexpr bool kCellTabMerge = false;
+#else
+constexpr bool kCellTabMerge = true;
+#endif
 
 // one primitive as the ABI hands it over (include/rm_raymarch.h: rm_prim)
 struct PrimDesc {
@@ -89,6 +99,13 @@ struct HostScene {
     int sb_bins = 0, sb_stride = 0;
     float sb_origin[3] = {0, 0, 0}, sb_inv[3] = {0, 0, 0};
     std::vector<uint32_t> step_tab;
+    // The threshold cells of step_tab as a table (build_cell_tab, sphere scenes only): per cell whether the root contains it, the
+    // spheres of the leaves that contain it in scan order, their number, and a maximal block of cells with the same leaf set
+    // (section B of the v2 wave loop reads its candidates there, section M its step box).  ct_dim: cells per axis; ct_rec_off /
+    // ct_list_off: word offsets of the records and the sphere lists.  Empty: no table.
+    int ct_dim[3] = {0, 0, 0};
+    int ct_rec_off = 0, ct_list_off = 0;
+    std::vector<uint32_t> cell_tab;
     std::vector<RmOctNode> oct;
     std::vector<int32_t> oct_prims;
     std::vector<RmSphereRec> oct_recs;  // oct_prims expanded to sphere records (sphere scenes)

@@ -192,8 +192,8 @@ struct RmRenderParams {
     int32_t launch_per_cu;
     int32_t v1_lists;          // v1 BVH: per-ray hit-leaf lists in LDS (option `v1_lists`), placed at v1_list_offset by the launcher
     int32_t v1_list_offset;
-    uint32_t lds_off[11];      // v2: byte offsets of the staged tables in LDS (nodes, prims, cells, list, oct, oct_prims, spheres,
-                               // radii, rel, end, step_tab), computed by the launcher: a section rebuilds its view from one scalar load
+    uint32_t lds_off[12];      // v2: byte offsets of the staged tables in LDS (nodes, prims, cells, list, oct, oct_prims, spheres,
+                               // radii, rel, end, step_tab, cell_tab), computed by the launcher: a section rebuilds its view from one scalar load
     int32_t prim_filter;       // general primitives (RmPrim): `spheres` holds a bounding sphere per primitive (rigid transforms only)
     int32_t n0_batch;          // v2 BVH: lanes waiting for getNormal that trigger the normal round while others still march (64: never)
     const int32_t *stripe_ids; // non-null (with stripe_rows > 0): the launch renders the stripes stripe_ids[0 .. ) in this
@@ -281,4 +281,13 @@ struct RmRenderParams {
     // option `rect_cull`, the leaf count, the camera); 0: the plane cull.
     RmLeafRect *leaf_rects;
     int32_t rect_cull;
+    // v2 BVH, sections B, M and N: the table of the step-box thresholds' cells (rm_scene_host.cpp build_cell_tab; the layout is
+    // described there).  ct_dim: cells per axis, ct_rec_off / ct_list_off: word offsets of the records and the sphere lists,
+    // ct_words: the table's length.  cell_on: what fill_params asks for (option `cell_tab`, the scene has a table) and, from the
+    // launcher on, what the launch does (rm_v2_plan): section B reads a point's candidates from the table and the launch does
+    // not stage the point-query grid.
+    const uint32_t *cell_tab;
+    int32_t ct_dim[3];
+    int32_t ct_rec_off, ct_list_off, ct_words;
+    int32_t cell_on;
 };

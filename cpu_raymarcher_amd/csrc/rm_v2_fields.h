@@ -14,7 +14,8 @@
     X(width) X(height) X(accel) X(shader) X(tile_w) X(nodes_in_lds) X(filter) X(variant) X(list_cap) X(coop) X(use_grid)         \
     X(refill_threshold) X(hw_xcd) X(item_px) X(rel_boxes) X(lpt_stride) X(prim_filter) X(n0_batch) X(use_nn) X(tile_w_log2)     \
     X(tile_h_log2) X(tiles_x) X(item_wide) X(item_w_log2) X(sub_dx) X(sub_dy) X(tiles_x_magic) X(leaf_order) X(algorithm)       \
-    X(general) X(uniform_radius) X(multi_step) X(use_ext) X(step_box) X(sb_bins) X(sb_stride) X(rect_cull)
+    X(general) X(uniform_radius) X(multi_step) X(use_ext) X(step_box) X(sb_bins) X(sb_stride) X(rect_cull) \
+    X(ct_rec_off) X(ct_list_off) X(ct_words) X(cell_on)
 
 // The scene's counts.  As literals they are loop bounds too: worth another 2 - 3 % on the 125-sphere grid, but on a nine-sphere
 // scene the optimiser unrolls the node and leaf loops completely and the instantiation that held 80 VGPRs spills 53 -- such a
@@ -24,5 +25,5 @@
     X(nn_cell_count) X(nn_list_count)
 
 #define RM_V2_FIXED_ARRAYS(X) \
-    X(pq_dim, 3) X(lds_off, 11) X(nn_dim, 3) X(pq_origin, 3) X(pq_inv, 3) X(pq_cell, 3) X(nn_inv, 3) X(light, 3) X(light_d, 3) \
-    X(ext_dim, 3) X(ext_origin, 3) X(ext_inv, 3) X(sb_origin, 3) X(sb_inv, 3)
+    X(pq_dim, 3) X(lds_off, 12) X(nn_dim, 3) X(pq_origin, 3) X(pq_inv, 3) X(pq_cell, 3) X(nn_inv, 3) X(light, 3) X(light_d, 3) \
+    X(ext_dim, 3) X(ext_origin, 3) X(ext_inv, 3) X(sb_origin, 3) X(sb_inv, 3) X(ct_dim, 3)

@@ -1012,6 +1012,16 @@ RM_API int rm_debug_overlap_fill(rm_ctx *ctx, int32_t asked, int64_t items, int3
  * would cost LDS that the launch keeps for the scene, the origin-relative boxes or a workgroup per CU); out[3]: the hit-list
  * capacity that launch gets, out[4]: what it would get with step_box 0; out[5]: the table's size in bytes (0: none). */
 RM_API int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]);
+/* Option cell_tab (below), for tests and evidence; works on a host-only context except for out[0].  out[0]: whether the last
+ * launch of the v2 wave loop read its candidate spheres from the scene's cell table (scene table "cell_tab"; 0 before the first
+ * such launch); out[1]: whether a launch of the active scene would, with the options as they stand; out[2]: why not (0: it
+ * would; 1: the options cell_tab, step_box, multi_step or kernel, the kind of scene, or a launch that does not take the
+ * step-box table; 2: the scene has no table -- no step-box table, more than 4 096 threshold cells, a cell with more than 255
+ * spheres, a primitive that is not a sphere; 3: the table would cost the launch a workgroup per CU, entries of its hit lists or
+ * its staging); out[3]: the hit-list capacity that launch gets, out[4]: what it would get with cell_tab 0; out[5]: the table's
+ * size in bytes (0: none); out[6]: the workgroups of that launch a CU holds; out[7], out[8]: the bytes of scene tables the
+ * launch stages in LDS, and would with cell_tab 0; out[9..11]: the table's cells, records and distinct leaf sets. */
+RM_API int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]);
 /* Option rect_cull (below), for tests and evidence; both work on a host-only context (except for out[0]).  rot9 / origin3: a
  * camera as rm_camera_from_angles gives it; width x height: the full frame.
  * rm_debug_rect_cull -- out[0]: whether the last launch of the v2 wave loop culled its batches' leaves by screen rectangles (0
@@ -1066,6 +1076,11 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *                 cell of the per-axis thresholds of the leaf boxes (lo, and the next binary32 above hi) as the round's point:
  *                 six compares against a bracket found once per run, instead of the cell's leaf list per step (default 1; 0, a
  *                 scene without the table, or a launch whose LDS has no room for it: the exact test; same bytes either way)
+ *   cell_tab 0|1  v2 BVH, with step_box: a point's candidate spheres, their number and the box of those steps come from a table
+ *                 over the cells of those thresholds (sphere scenes of at most 4 096 cells), found with one look-up per round,
+ *                 instead of from box tests against the leaf grid's lists; the launch then stages the table in the leaf
+ *                 grid's place (default 1; 0, a scene without the table, or a launch it does not fit: as before; same bytes
+ *                 either way; rm_debug_cell_tab)
  *   lds_fill 0|1  v2: pad the LDS request so that exactly blocks_per_cu workgroups fit a CU (default 0; measurement knob)
  *   min_fill 0|1  v2: a persistent launch brings max(blocks_per_cu, ceil(6 / Q)) workgroups per CU, Q = GPU_MAX_HW_QUEUES as
  *                 rm_create found it (unset or not a positive integer: 4, HIP's default; never set by the library).  Launches

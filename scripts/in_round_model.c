@@ -168,9 +168,108 @@ static int same_cell(const float *q, const float *p, int strict) {
     return 1;
 }
 
+/* Round 11: the half-open threshold cells as a table (rm_scene_host.cpp build_cell_tab).  Every cell has a key -- the leaves
+ * that contain its representative point (its lower threshold on each axis, -inf for the first cell) and whether the root
+ * does -- and a merged box: the cells are visited in index order, a cell without a box grows a block from itself one layer
+ * at a time in the order -x, +x, -y, +y, -z, +z, again and again until no direction accepts a layer (every cell of the
+ * layer has the starting cell's key), and the block becomes the box of every cell in it that has none yet. */
+static int ct_dim[3], *ct_box; /* per cell: lo[3], hi[3] as cell indices, hi exclusive */
+static unsigned long long *ct_key; /* the cell's leaves */
+static unsigned char *ct_root;     /* whether the root box contains the cell */
+static float ct_T(int k, int i) { return i <= 0 ? -INFINITY : i > n_thr[k] ? INFINITY : thr[k][i - 1]; } /* cell i is [T(i), T(i + 1)) */
+static int ct_index(const int *c) { return (c[2] * ct_dim[1] + c[1]) * ct_dim[0] + c[0]; }
+static void ct_cell(const float *p, int *c) {
+    for (int k = 0; k < 3; k++) {
+        int i = 0;
+        while (i < n_thr[k] && thr[k][i] <= p[k]) i++;
+        c[k] = i;
+    }
+}
+static int ct_layer_ok(const int *lo, const int *hi, int axis, int at, unsigned long long key, int root) {
+    int a[3] = {lo[0], lo[1], lo[2]}, b[3] = {hi[0], hi[1], hi[2]}, c[3];
+    a[axis] = at;
+    b[axis] = at + 1;
+    for (c[2] = a[2]; c[2] < b[2]; c[2]++)
+        for (c[1] = a[1]; c[1] < b[1]; c[1]++)
+            for (c[0] = a[0]; c[0] < b[0]; c[0]++)
+                if (ct_key[ct_index(c)] != key || ct_root[ct_index(c)] != root) return 0;
+    return 1;
+}
+static void build_cell_table(int merge) {
+    for (int k = 0; k < 3; k++) ct_dim[k] = n_thr[k] + 1;
+    const int cells = ct_dim[0] * ct_dim[1] * ct_dim[2];
+    ct_key = (unsigned long long *)calloc((size_t)cells, sizeof *ct_key);
+    ct_root = (unsigned char *)calloc((size_t)cells, 1);
+    ct_box = (int *)malloc((size_t)cells * 6 * sizeof(int));
+    int c[3], in_root = 0, leafless = 0, most_leaves = 0, most_spheres = 0;
+    for (c[2] = 0; c[2] < ct_dim[2]; c[2]++)
+        for (c[1] = 0; c[1] < ct_dim[1]; c[1]++)
+            for (c[0] = 0; c[0] < ct_dim[0]; c[0]++) {
+                const float p[3] = {ct_T(0, c[0]), ct_T(1, c[1]), ct_T(2, c[2])};
+                unsigned long long key = 0;
+                int leaves = 0, spheres = 0;
+                for (int l = 0; l < n_leaf; l++)
+                    if (margin(&leaf_box[l], p) >= 0.f) {
+                        key |= 1ull << l;
+                        leaves++;
+                        spheres += leaf_node[l]->nprims;
+                    }
+                const int root = margin(&root_box, p) >= 0.f;
+                ct_root[ct_index(c)] = (unsigned char)root;
+                in_root += root;
+                leafless += root && leaves == 0;
+                if (leaves > most_leaves) most_leaves = leaves;
+                if (spheres > most_spheres) most_spheres = spheres;
+                ct_key[ct_index(c)] = key;
+                ct_box[6 * ct_index(c)] = -1;
+            }
+    int boxes = 0;
+    for (c[2] = 0; c[2] < ct_dim[2]; c[2]++)
+        for (c[1] = 0; c[1] < ct_dim[1]; c[1]++)
+            for (c[0] = 0; c[0] < ct_dim[0]; c[0]++) {
+                if (ct_box[6 * ct_index(c)] >= 0) continue;
+                int lo[3] = {c[0], c[1], c[2]}, hi[3] = {c[0] + 1, c[1] + 1, c[2] + 1};
+                const unsigned long long key = ct_key[ct_index(c)];
+                const int root = ct_root[ct_index(c)];
+                for (int grew = merge; grew;) {
+                    grew = 0;
+                    for (int axis = 0; axis < 3; axis++) {
+                        if (lo[axis] > 0 && ct_layer_ok(lo, hi, axis, lo[axis] - 1, key, root)) { lo[axis]--; grew = 1; }
+                        if (hi[axis] < ct_dim[axis] && ct_layer_ok(lo, hi, axis, hi[axis], key, root)) { hi[axis]++; grew = 1; }
+                    }
+                }
+                boxes++;
+                int d[3];
+                for (d[2] = lo[2]; d[2] < hi[2]; d[2]++)
+                    for (d[1] = lo[1]; d[1] < hi[1]; d[1]++)
+                        for (d[0] = lo[0]; d[0] < hi[0]; d[0]++) {
+                            int *b = ct_box + 6 * ct_index(d);
+                            if (b[0] < 0) { memcpy(b, lo, sizeof lo); memcpy(b + 3, hi, sizeof hi); }
+                        }
+            }
+    int sets = 0;
+    for (int i = 0; i < cells; i++) {
+        int seen = 0;
+        for (int j = 0; j < i && !seen; j++) seen = ct_key[j] == ct_key[i];
+        sets += !seen;
+    }
+    printf("cell table: %d x %d x %d = %d cells, %d in the root box of which %d without a leaf, %d distinct leaf sets, at most %d leaves "
+           "and %d spheres per cell, %d merged boxes\n", ct_dim[0], ct_dim[1], ct_dim[2], cells, in_root, leafless, sets, most_leaves, most_spheres, boxes);
+}
+/* p in the merged box of q's cell? */
+static int same_box(const float *q, const float *p) {
+    int c[3];
+    ct_cell(q, c);
+    const int *b = ct_box + 6 * ct_index(c);
+    for (int k = 0; k < 3; k++)
+        if (!(p[k] >= ct_T(k, b[k]) && p[k] < ct_T(k, b[3 + k]))) return 0;
+    return 1;
+}
+
 typedef struct {
     const char *name;
-    int exact;      /* 0: the ball of rho and rho_cell; 1: the exact leaf set at p2; 2: one half-open threshold cell; 3: one open cell */
+    int exact;      /* 0: the ball of rho and rho_cell; 1: the exact leaf set at p2; 2: one half-open threshold cell; 3: one open cell;
+                     * 4: the merged box of q's threshold cell */
     double grow;    /* ball: how far the cell lists are grown */
     double confine; /* exact: p2 stays within q's cell grown by this; < 0: anywhere in the root box */
 } Rule;
@@ -201,7 +300,7 @@ static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e
         float rho_cell = (float)(r->grow + (in_cell > 0 ? in_cell : 0));
         if (!(dd < (rho < rho_cell ? rho : rho_cell))) return rho < rho_cell ? END_SET : END_CELL; /* whichever radius binds */
     } else if (r->exact >= 2) {
-        if (!same_cell(h->p, e->p, r->exact == 3)) return END_SET;
+        if (r->exact == 4 ? !same_box(h->p, e->p) : !same_cell(h->p, e->p, r->exact == 3)) return END_SET;
         /* the rule's claim, checked against the oracle's sets on every accepted step */
         if (e->set != h->set || margin(&root_box, e->p) < 0.f) { fprintf(stderr, "threshold rule accepted a step whose leaf set differs\n"); exit(2); }
     } else {
@@ -223,6 +322,7 @@ int main(void) {
     collect(s->bvh);
     root_box = s->bvh->bounds;
     build_thresholds();
+    build_cell_table(1);
     G = (int)ceil(cbrt((double)n_leaf) * 3.0);
     G = G < 2 ? 2 : G > 32 ? 32 : G;
     for (int k = 0; k < 3; k++) {
@@ -240,6 +340,7 @@ int main(void) {
         {"ball kept, lists grown by 0.24", 0, 0.24, 0},
         {"half-open threshold cells (round 9)", 2, 0, 0},
         {"open threshold cells", 3, 0, 0},
+        {"merged threshold-cell boxes (round 11)", 4, 0, 0},
     };
     enum { NR = sizeof rules / sizeof rules[0] };
     double lane_rounds[NR] = {0}, lane_steps[NR] = {0}, wave_rounds[NR] = {0}, wave_trips[NR] = {0}, ends[NR][N_END] = {{0}};
