@@ -102,6 +102,13 @@ class rm_mesh_info(C.Structure):  # include/rm_raymarch.h: struct rm_mesh_info
 RM_MESH_F64, RM_MESH_F32 = 0, 1
 
 
+class rm_sparse_info(C.Structure):  # include/rm_raymarch.h: struct rm_sparse_info
+    _fields_ = [("n_blocks", C.c_int64), ("n_kept", C.c_int64), ("reserved", C.c_int64 * 2)]
+
+
+RM_SPARSE_BLOCK = 8
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -211,6 +218,13 @@ SIGNATURES = {
     "rm_shade_field": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP]),
     "rm_mesh_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "rm_scene_mesh": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rm_mesh_info)]),
+    "rm_lattice_blocks": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(C.c_int32)]),
+    "rm_scene_blocks_device": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP]),
+    "rm_scene_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int64, _VP, _VP]),
+    "rm_mesh_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, C.c_int64, _VP, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                       _VP, _VP]),
+    "rm_scene_mesh_sparse": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
+                                       C.POINTER(rm_mesh_info), C.POINTER(rm_sparse_info)]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

@@ -8,6 +8,7 @@ from . import _native as N
 
 # what Context.points returns
 Points = collections.namedtuple("Points", "position dist normal object steps count")
+SparseBlocks = collections.namedtuple("SparseBlocks", "slot list dist n_kept dims")
 
 
 def _is_torch(x):
@@ -978,11 +979,93 @@ class Context:
         return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
                                tol=tol, time=time)
 
+    # ---- sparse meshes: the same mesh from the 8 x 8 x 8-cell blocks near the surface ---------
+    def sparse_blocks(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, dist=True):
+        """The coarse pass of the sparse mesher (rm_scene_blocks_device; the rule is in include/rm_raymarch.h) on torch's
+        current stream: one exact distance per block of 8 x 8 x 8 cells, at its centre; a block is kept unless
+        |d - iso| > lipschitz * R + slack proves it empty.  Returns the named tuple SparseBlocks(slot int32 [n_blocks]: the
+        block's rank among the kept ones or -1, list int32 [n_kept]: the kept blocks in that order, dist float64 [n_blocks] or
+        None, n_kept, dims = (nbu, nbv, nbw)); CUDA tensors."""
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        import torch
+        lat = make_lattice(origin, du, dv, dw, shape, time)
+        dims = (C.c_int32 * 3)()
+        rc = N.lib().rm_lattice_blocks(C.byref(lat), dims)
+        if rc != N.RM_OK:
+            raise N.RmError(rc, "rm_lattice_blocks")
+        n_blocks = dims[0] * dims[1] * dims[2]
+        dev = torch.device("cuda", self.device)
+        room = min(n_blocks, 1 << 24)  # (beyond that the entry refuses before it touches a buffer)
+        slot = torch.empty(room, dtype=torch.int32, device=dev)
+        lst = torch.empty(room, dtype=torch.int32, device=dev)
+        d = torch.empty(room, dtype=torch.float64, device=dev) if dist else None
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        N.check(self._h, N.lib().rm_scene_blocks_device(self._h, C.byref(lat), float(iso), float(lipschitz), _ptr(slot), _ptr(lst), _ptr(d),
+                                                        _ptr(info), _current_stream_ptr()))
+        n_kept = int(info.cpu()[1])
+        return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
+
+    def mesh_sparse(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, order="dense", device=False, triangles=False,
+                    attributes=False, snap=0, tol=1e-4):
+        """`mesh` from the blocks near the surface only (include/rm_raymarch.h, "sparse meshes"): `sparse_blocks` keeps the
+        blocks of 8 x 8 x 8 cells that can hold the surface when the exact field is `lipschitz`-Lipschitz (1 for primitives
+        and their unions), rm_scene_tiles_device samples the active scene at the 729 points of each kept block and
+        rm_mesh_tiles_device runs surface nets over those tiles (the counting call, an exact allocation, the filling call), all
+        on torch's current stream.  Memory and work follow the surface, not the volume: lattices of 512^3 and more points are
+        possible.  order="dense" sorts the vertices and the quads by the dense mesher's keys on the device and renames the
+        vertices: the result is `mesh`'s, byte for byte, whenever every cell the dense volume has active lies in a kept block
+        -- what `lipschitz` guarantees for an exact field.  order="tile" returns the ABI's order, by kept block.  Everything
+        else as `mesh` (the winding of a left-handed lattice is flipped here too)."""
+        if order not in ("dense", "tile"):
+            raise ValueError("order is 'dense' or 'tile'")
+        blocks = self.sparse_blocks(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, dist=False)
+        import torch
+        lat = make_lattice(origin, du, dv, dw, shape, time)
+        dev = torch.device("cuda", self.device)
+        k = blocks.n_kept
+        tiles = torch.empty((k, 729), dtype=torch.float64, device=dev)
+        N.check(self._h, N.lib().rm_scene_tiles_device(self._h, C.byref(lat), _ptr(blocks.list) if k else None, k, _ptr(tiles) if k else None,
+                                                       _current_stream_ptr()))
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+
+        def call(v, nv_, q, nq_, c, e):
+            N.check(self._h, N.lib().rm_mesh_tiles_device(self._h, C.byref(lat), _ptr(blocks.slot), _ptr(blocks.list) if k else None, k,
+                                                          _ptr(tiles) if k else None, float(iso), _ptr(v) if nv_ else None, nv_, _ptr(q) if nq_ else None,
+                                                          nq_, _ptr(c) if nv_ else None, _ptr(e) if nq_ else None, _ptr(info), _current_stream_ptr()))
+        call(None, 0, None, 0, None, None)
+        n_vertices, n_quads = (int(x) for x in info.cpu()[:2])
+        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+        quads = torch.empty((n_quads, 4), dtype=torch.int32, device=dev)
+        dense = order == "dense"
+        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev) if dense else None
+        edges = torch.empty(n_quads, dtype=torch.int64, device=dev) if dense else None
+        if n_vertices or n_quads:
+            call(vertices, n_vertices, quads, n_quads, cells, edges)
+        if dense and n_vertices:
+            by_cell = torch.argsort(cells)  # (the keys are distinct)
+            vertices = vertices[by_cell].contiguous()
+            rename = torch.empty(n_vertices, dtype=torch.int32, device=dev)
+            rename[by_cell] = torch.arange(n_vertices, dtype=torch.int32, device=dev)
+            if n_quads:
+                quads = rename[quads[torch.argsort(edges)].long()].contiguous()
+        u, v, w = (np.array(list(getattr(lat, name)), np.float64) for name in ("du", "dv", "dw"))
+        if float(np.dot(u, np.cross(v, w))) < 0:
+            quads = quads[:, [0, 3, 2, 1]].contiguous()
+        faces = quads[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).contiguous() if triangles else quads
+        out = (vertices, faces) + (self._mesh_attributes(vertices, iso, time, snap, tol) if attributes else ())
+        if device:
+            return out
+        return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
+
     def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None, attributes=False, snap=0,
-                 tol=1e-4):
+                 tol=1e-4, sparse=False, lipschitz=1.0):
         """`mesh` over an axis-aligned lattice of cells[0] x cells[1] x cells[2] cells that covers scene_info()'s root box
         and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
-        `box` = (lo, hi) replaces the root box: a scene without a structure reports none."""
+        `box` = (lo, hi) replaces the root box: a scene without a structure reports none.  sparse=True: `mesh_sparse` with
+        `lipschitz` over the same lattice (order "dense": the same mesh)."""
         if box is None:
             info = self.scene_info()
             box = (info["root_min"], info["root_max"])
@@ -994,8 +1077,11 @@ class Context:
             raise ValueError("at least 5 cells per axis")
         m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
         step = (hi - lo + 2 * m) / c
-        return self.mesh(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c), iso=iso, time=time,
-                         device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
+        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
+        if sparse:
+            more["lipschitz"] = lipschitz
+        return (self.mesh_sparse if sparse else self.mesh)(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c),
+                                                           **more)
 
     def _same_device(self, bufs):
         for name, b in bufs.items():

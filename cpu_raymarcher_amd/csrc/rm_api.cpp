@@ -1830,6 +1830,139 @@ int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, co
 
 size_t mesh_blocks(int64_t n) { return static_cast<size_t>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK); }
 
+// ---- sparse meshes: blocks of 8 x 8 x 8 cells, their tiles and the mesher over them (rm_kernels.hip, rm_mesh_sparse.hip)
+
+static_assert(sizeof(rm_sparse_info) == 32 && sizeof(RmSparseInfo) == sizeof(rm_sparse_info), "rm_sparse_info layout");
+
+struct SparseGrid {
+    int64_t n;         // lattice points
+    int32_t nb[3];     // blocks per axis
+    int64_t n_blocks;
+};
+
+// null when the lattice is well formed and has at most 2^24 blocks (then *g is filled), else what is wrong with it
+const char *sparse_error(const rm_lattice *l, SparseGrid *g, bool limit = true) {
+    if (const char *bad = lattice_error(l, &g->n)) return bad;
+    const int32_t count[3] = {l->nu, l->nv, l->nw};
+    for (int c = 0; c < 3; ++c) g->nb[c] = count[c] >= 2 ? (count[c] - 1 + RM_SPARSE_BLOCK - 1) / RM_SPARSE_BLOCK : 0;
+    g->n_blocks = static_cast<int64_t>(g->nb[0]) * g->nb[1] * g->nb[2];
+    if (limit && g->n_blocks > RM_SPARSE_MAX_BLOCKS) return "more than 2^24 blocks";
+    return nullptr;
+}
+
+// lipschitz * R + slack of the header's rule, one binary64 operation at a time
+double sparse_bound(const rm_lattice &l, double lipschitz) {
+    const auto norm = [](const float v[3]) {
+        const double x = v[0], y = v[1], z = v[2];
+        return std::sqrt((x * x + y * y) + z * z);
+    };
+    const double R = 4.0 * ((norm(l.du) + norm(l.dv)) + norm(l.dw));
+    const int64_t last[3] = {l.nu > 0 ? l.nu - 1 : 0, l.nv > 0 ? l.nv - 1 : 0, l.nw > 0 ? l.nw - 1 : 0};
+    double M = 0.0;
+    for (int corner = 0; corner < 8; ++corner)
+        for (int c = 0; c < 3; ++c)
+            M = std::max(M, std::fabs(static_cast<double>(lattice_component(l, c, corner & 1 ? last[0] : 0, corner & 2 ? last[1] : 0, corner & 4 ? last[2] : 0))));
+    const double slack = M * 0x1p-20;
+    return lipschitz * R + slack;
+}
+
+template <typename ARGS>
+void fill_sparse_lattice(const rm_lattice *lat, const SparseGrid &g, ARGS &a) {
+    std::memset(&a, 0, sizeof a);
+    for (int c = 0; c < 3; ++c) {
+        a.origin[c] = lat->origin[c];
+        a.du[c] = lat->du[c];
+        a.dv[c] = lat->dv[c];
+        a.dw[c] = lat->dw[c];
+    }
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.nbu = static_cast<unsigned int>(g.nb[0]);
+    a.nbv = static_cast<unsigned int>(g.nb[1]);
+}
+
+size_t sparse_groups(int64_t n_blocks) { return static_cast<size_t>((n_blocks + 255) / 256); }
+
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// The three launches; every pointer a device pointer, the scene the active one at the lattice's time.
+int launch_blocks(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, double iso, double lipschitz, void *d_slot, void *d_list, void *d_dist,
+                  void *d_info, uint32_t *d_totals, hipStream_t stream) {
+    RmRenderParams p;
+    RmFieldArgs unused;
+    fill_field(ctx, lat, p, unused);
+    RmBlocksArgs a;
+    fill_sparse_lattice(lat, g, a);
+    a.nbw = static_cast<unsigned int>(g.nb[2]);
+    a.iso = iso;
+    a.bound = sparse_bound(*lat, lipschitz);
+    a.slot = static_cast<int32_t *>(d_slot);
+    a.list = static_cast<int32_t *>(d_list);
+    a.dist = static_cast<double *>(d_dist);
+    a.info = static_cast<RmSparseInfo *>(d_info);
+    a.totals = d_totals;
+    a.n_blocks = static_cast<unsigned int>(g.n_blocks);
+    a.n_groups = static_cast<unsigned int>(sparse_groups(g.n_blocks));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_blocks_sqrt : rm_launch_blocks)(p, a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream) {
+    RmRenderParams p;
+    RmFieldArgs unused;
+    fill_field(ctx, lat, p, unused);
+    RmTilesArgs a;
+    fill_sparse_lattice(lat, g, a);
+    a.list = static_cast<const int32_t *>(d_list);
+    a.tiles = static_cast<double *>(d_tiles);
+    a.n_kept = static_cast<unsigned int>(n_kept);
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_tiles_sqrt : rm_launch_tiles)(p, a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+struct SparseMeshCall {
+    const void *slot, *list, *tiles;
+    int64_t n_kept;
+    double iso;
+    void *vertices, *quads, *cells, *edges, *info;
+    int64_t cap_vertices, cap_quads;
+};
+
+int launch_mesh_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const SparseMeshCall &m, uint32_t *d_map, uint32_t *d_totals,
+                      hipStream_t stream) {
+    RmSparseMeshArgs a;
+    fill_sparse_lattice(lat, g, a);
+    a.nbw = static_cast<unsigned int>(g.nb[2]);
+    a.iso = m.iso;
+    a.slot = static_cast<const int32_t *>(m.slot);
+    a.list = static_cast<const int32_t *>(m.list);
+    a.tiles = static_cast<const double *>(m.tiles);
+    a.vertices = static_cast<float *>(m.vertices);
+    a.quads = static_cast<uint32_t *>(m.quads);
+    a.cells = static_cast<long long *>(m.cells);
+    a.edges = static_cast<long long *>(m.edges);
+    a.info = static_cast<RmMeshInfo *>(m.info);
+    a.map = d_map;
+    a.totals = d_totals;
+    a.cap_vertices = m.cap_vertices;
+    a.cap_quads = m.cap_quads;
+    a.n_kept = static_cast<unsigned int>(m.n_kept);
+    RM_HIP(ctx, rm_launch_mesh_tiles(a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+// what the mesh entries share about iso, capacities and output buffers (device entry: d_cells and d_edges too)
+const char *mesh_outputs_error(double iso, const void *vertices, int64_t cap_vertices, const void *quads, int64_t cap_quads, const void *cells,
+                               const void *edges) {
+    if (!std::isfinite(iso)) return "non-finite iso";
+    if (cap_vertices < 0 || cap_quads < 0) return "negative capacity";
+    if ((cap_vertices > 0 && !vertices) || (cap_quads > 0 && !quads)) return "null buffer with a capacity above 0";
+    if (misaligned(vertices, 3) || misaligned(quads, 3)) return "vertices and quads must be 4-byte aligned";
+    if (misaligned(cells, 7) || misaligned(edges, 7)) return "cells and edges must be 8-byte aligned";
+    return nullptr;
+}
+
 int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const void *values, const void *rgba) {
     if (!sh || !values || !rgba) return fail(ctx, RM_E_INVALID, "null argument");
     if (n < 0) return fail(ctx, RM_E_INVALID, "negative count");
@@ -2954,6 +3087,152 @@ int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *ver
                  got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
     if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
     if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_lattice_blocks(const rm_lattice *lattice, int32_t dims[3]) {
+    SparseGrid g;
+    if (!dims || sparse_error(lattice, &g, false)) return RM_E_INVALID;
+    for (int c = 0; c < 3; ++c) dims[c] = g.nb[c];
+    return RM_OK;
+}
+
+int rm_scene_blocks_device(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, void *d_slot, void *d_list, void *d_dist, void *d_info,
+                           void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (!std::isfinite(iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (!std::isfinite(lipschitz) || !(lipschitz > 0.0)) return fail(ctx, RM_E_INVALID, "lipschitz must be finite and > 0");
+    if (!d_info) return fail(ctx, RM_E_INVALID, "null info");
+    if (g.n_blocks > 0 && (!d_slot || !d_list)) return fail(ctx, RM_E_INVALID, "null slot or list");
+    if (misaligned(d_slot, 3) || misaligned(d_list, 3)) return fail(ctx, RM_E_INVALID, "slot and list must be 4-byte aligned");
+    if (misaligned(d_dist, 7) || misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "dist and info must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!g.n_blocks) {  // no block, no launch
+        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_sparse_info), s));
+        return RM_OK;
+    }
+    Staging st{ctx};
+    const size_t o_totals = st.region(4 * sparse_groups(g.n_blocks));
+    int rc = st.reserve_for(s);
+    if (rc) return rc;
+    rc = launch_blocks(ctx, lattice, g, iso, lipschitz, d_slot, d_list, d_dist, d_info, st.at<uint32_t>(o_totals), s);
+    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
+    return rc;
+}
+
+int rm_scene_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_list, int64_t n_kept, void *d_tiles, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (n_kept < 0 || n_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, n_blocks]");
+    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
+    if (misaligned(d_list, 3) || misaligned(d_tiles, 7)) return fail(ctx, RM_E_INVALID, "list must be 4-byte and tiles 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (!n_kept) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    return launch_tiles(ctx, lattice, g, d_list, n_kept, d_tiles, static_cast<hipStream_t>(stream));
+}
+
+int rm_mesh_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept, const void *d_tiles, double iso,
+                         void *d_vertices, int64_t cap_vertices, void *d_quads, int64_t cap_quads, void *d_cells, void *d_edges, void *d_info,
+                         void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (n_kept < 0 || n_kept > g.n_blocks || n_kept > RM_SPARSE_MAX_KEPT) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, min(n_blocks, 2^21)]");
+    if (!d_info) return fail(ctx, RM_E_INVALID, "null info");
+    if (g.n_blocks > 0 && !d_slot) return fail(ctx, RM_E_INVALID, "null slot");
+    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
+    if (const char *bad = mesh_outputs_error(iso, d_vertices, cap_vertices, d_quads, cap_quads, d_cells, d_edges)) return fail(ctx, RM_E_INVALID, bad);
+    if (misaligned(d_slot, 3) || misaligned(d_list, 3)) return fail(ctx, RM_E_INVALID, "slot and list must be 4-byte aligned");
+    if (misaligned(d_tiles, 7) || misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "tiles and info must be 8-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!n_kept) {  // no kept block, no launch: the totals are zero
+        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
+        return RM_OK;
+    }
+    Staging st{ctx};
+    const size_t k = static_cast<size_t>(n_kept), o_map = st.region(4 * RM_SPARSE_CELLS * k), o_totals = st.region(12 * k);
+    int rc = st.reserve_for(s);
+    if (rc) return rc;
+    const SparseMeshCall m{d_slot, d_list, d_tiles, n_kept, iso, d_vertices, d_quads, d_cells, d_edges, d_info, cap_vertices, cap_quads};
+    rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), s);
+    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
+    return rc;
+}
+
+int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, float *vertices, int64_t cap_vertices, uint32_t *quads,
+                         int64_t cap_quads, int64_t *cells, int64_t *edges, rm_mesh_info *info, rm_sparse_info *sparse_info) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (!info) return fail(ctx, RM_E_INVALID, "null info");
+    if (!std::isfinite(lipschitz) || !(lipschitz > 0.0)) return fail(ctx, RM_E_INVALID, "lipschitz must be finite and > 0");
+    if (const char *bad = mesh_outputs_error(iso, vertices, cap_vertices, quads, cap_quads, cells, edges)) return fail(ctx, RM_E_INVALID, bad);
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    std::memset(info, 0, sizeof *info);
+    rm_sparse_info si;
+    std::memset(&si, 0, sizeof si);
+    si.n_blocks = g.n_blocks;
+    if (sparse_info) *sparse_info = si;
+    if (!g.n_blocks) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Step 1 in the scratch buffer: the slot map, the list, the info and the scan's totals.
+    const size_t nb = static_cast<size_t>(g.n_blocks);
+    Staging st{ctx};
+    const size_t o_slot = st.region(4 * nb), o_list = st.region(4 * nb), o_sinfo = st.region(sizeof si), o_groups = st.region(4 * sparse_groups(g.n_blocks));
+    int rc = st.reserve();
+    if (rc) return rc;
+    if ((rc = launch_blocks(ctx, lattice, g, iso, lipschitz, st.at<void>(o_slot), st.at<void>(o_list), nullptr, st.at<void>(o_sinfo),
+                            st.at<uint32_t>(o_groups), ctx->stream)))
+        return rc;
+    RM_HIP(ctx, st.out(&si, o_sinfo, sizeof si));
+    RM_HIP(ctx, st.sync());
+    if (sparse_info) *sparse_info = si;
+    const int64_t n_kept = si.n_kept;
+    if (n_kept <= 0) return RM_OK;
+    if (n_kept > RM_SPARSE_MAX_KEPT) return fail(ctx, RM_E_UNSUPPORTED, "more than 2^21 kept blocks: vertex numbers are 32-bit");
+    // Steps 2 and 3 behind the same four regions: the tiles, the mesher's scratch and the outputs, sized by the capacities and by
+    // what the kept blocks can yield at most (a vertex per cell, three quads per cell).
+    const size_t k = static_cast<size_t>(n_kept);
+    const size_t room_v = static_cast<size_t>(std::min<int64_t>(cap_vertices, RM_SPARSE_CELLS * n_kept)),
+                 room_q = static_cast<size_t>(std::min<int64_t>(cap_quads, 3 * RM_SPARSE_CELLS * n_kept));
+    const size_t o_tiles = st.region(8 * RM_SPARSE_TILE * k), o_map = st.region(4 * RM_SPARSE_CELLS * k), o_totals = st.region(12 * k),
+                 o_info = st.region(sizeof(rm_mesh_info)), o_vert = st.region(12 * room_v), o_quad = st.region(16 * room_q),
+                 o_cells = st.region(cells ? 8 * room_v : 0), o_edges = st.region(edges ? 8 * room_q : 0);
+    if (st.total > ctx->scratch_bytes) {  // the scratch has to grow, which frees it: the map and the list go through the host
+        std::vector<int32_t> slot(nb), list(k);
+        RM_HIP(ctx, st.out(slot.data(), o_slot, 4 * nb));
+        RM_HIP(ctx, st.out(list.data(), o_list, 4 * k));
+        RM_HIP(ctx, st.sync());
+        if ((rc = st.reserve())) return rc;
+        RM_HIP(ctx, st.in(o_slot, slot.data(), 4 * nb));
+        RM_HIP(ctx, st.in(o_list, list.data(), 4 * k));
+        RM_HIP(ctx, st.sync());  // (the vectors end here)
+    }
+    if ((rc = launch_tiles(ctx, lattice, g, st.at<void>(o_list), n_kept, st.at<void>(o_tiles), ctx->stream))) return rc;
+    const SparseMeshCall m{st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_tiles), n_kept, iso, st.at<void>(o_vert), st.at<void>(o_quad),
+                           cells ? st.at<void>(o_cells) : nullptr, edges ? st.at<void>(o_edges) : nullptr, st.at<void>(o_info),
+                           static_cast<int64_t>(room_v), static_cast<int64_t>(room_q)};
+    if ((rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), ctx->stream))) return rc;
+    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
+    RM_HIP(ctx, st.sync());
+    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
+                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
+    if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
+    if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
+    if (got_v && cells) RM_HIP(ctx, st.out(cells, o_cells, 8 * got_v));
+    if (got_q && edges) RM_HIP(ctx, st.out(edges, o_edges, 8 * got_q));
     RM_HIP(ctx, st.sync());
     return RM_OK;
 }

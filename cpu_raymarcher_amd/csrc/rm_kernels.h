@@ -246,6 +246,51 @@ struct RmMeshArgs {
     unsigned int nu, nv, nw, n_blocks;  // n_blocks = ceil(n / RM_MESH_BLOCK)
     int f32, pad;
 };
+// The sparse mesher (rm_scene_blocks_device, rm_scene_tiles_device, rm_mesh_tiles_device): blocks of RM_SPARSE_BLOCK^3 cells,
+// each with a tile of (RM_SPARSE_BLOCK + 1)^3 lattice points.  include/rm_raymarch.h ("sparse meshes") has the rule.
+#define RM_SPARSE_BLOCK 8
+#define RM_SPARSE_TILE 729          // 9 * 9 * 9 values of a tile, a fastest
+#define RM_SPARSE_CELLS 512         // cells of a block, local index (z * 8 + y) * 8 + x
+#define RM_SPARSE_MAX_BLOCKS (1 << 24)
+#define RM_SPARSE_MAX_KEPT (1 << 21)  // what rm_mesh_tiles_device takes: 2^30 cells, so vertex and quad numbers fit 32 bits
+struct RmSparseInfo {  // rm_sparse_info (32 bytes)
+    long long n_blocks, n_kept, reserved[2];
+};
+// The coarse pass (rm_kernels.hip blocks_kernel, then rm_mesh_sparse.hip): one lane per block.  blocks_kernel writes the keep
+// flag (0 kept, -1 dropped) into slot and the kept blocks of each workgroup of 256 into totals; the scan turns the totals into
+// offsets and writes info; the scatter turns the flags into ranks and writes list.
+struct RmBlocksArgs {
+    double origin[3], du[3], dv[3], dw[3];
+    double iso, bound;
+    int32_t *slot, *list;
+    double *dist;       // may be null
+    RmSparseInfo *info;
+    uint32_t *totals;   // ceil(n_blocks / 256) words
+    unsigned int nu, nv, nw, nbu, nbv, nbw;
+    unsigned int n_blocks, n_groups;
+};
+// rm_scene_tiles_device (rm_kernels.hip tiles_kernel): one workgroup per kept block
+struct RmTilesArgs {
+    double origin[3], du[3], dv[3], dw[3];
+    const int32_t *list;
+    double *tiles;      // n_kept x RM_SPARSE_TILE
+    unsigned int nu, nv, nw, nbu, nbv, n_kept;
+};
+// rm_mesh_tiles_device (rm_mesh_sparse.hip): one workgroup per kept block, the fields vertex_position reads named as in RmMeshArgs
+struct RmSparseMeshArgs {
+    double origin[3], du[3], dv[3], dw[3];
+    double iso;
+    const int32_t *slot, *list;
+    const double *tiles;
+    float *vertices;
+    uint32_t *quads;
+    long long *cells, *edges;  // the dense mesher's sort keys per vertex and per quad; each may be null
+    RmMeshInfo *info;
+    uint32_t *map;       // n_kept x RM_SPARSE_CELLS words: the vertex of the cell, or 0xFFFFFFFF
+    uint32_t *totals;    // 3 x n_kept words, as RmMeshArgs::totals with one workgroup per kept block
+    long long cap_vertices, cap_quads;
+    unsigned int nu, nv, nw, nbu, nbv, nbw, n_kept, pad;
+};
 // The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
 // A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
 // its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
@@ -403,6 +448,18 @@ hipError_t rm_launch_points_sqrt(const RmRenderParams &p, const RmPointArgs &a, 
 // Surface nets (rm_mesh.hip): count, scan and -- with a capacity above 0 -- the two emit kernels, back to back on `stream`.
 // a.map and a.totals are the caller's scratch; 1 <= a.n <= 2^30.
 hipError_t rm_launch_mesh(const RmMeshArgs &a, hipStream_t stream, const char **kernel_name);
+
+// The sparse mesher.  rm_launch_blocks (rm_kernels.hip): blocks_kernel<GEN, WALK> -- the exact distance at every block centre,
+// by the pruned walk of the BVH where the scene has one and is no expression program, else over all objects -- and, through
+// rm_launch_blocks_compact (rm_mesh_sparse.hip), the scan and the scatter.  rm_launch_tiles (rm_kernels.hip): tiles_kernel<ACCEL,
+// GEN>.  rm_launch_mesh_tiles (rm_mesh_sparse.hip): count, scan and -- with a capacity above 0 -- the two emit kernels.
+// 1 <= n_blocks <= RM_SPARSE_MAX_BLOCKS; 1 <= n_kept (RM_SPARSE_MAX_KEPT for the mesher).
+hipError_t rm_launch_blocks(const RmRenderParams &p, const RmBlocksArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_blocks_sqrt(const RmRenderParams &p, const RmBlocksArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_blocks_compact(const RmBlocksArgs &a, hipStream_t stream);
+hipError_t rm_launch_tiles(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_tiles_sqrt(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_mesh_tiles(const RmSparseMeshArgs &a, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

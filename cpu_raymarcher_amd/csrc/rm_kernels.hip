@@ -1405,6 +1405,95 @@ __device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ra
     return object_at<ACCEL, GEN>(P, hit, slot_obj);
 }
 
+// ------------------------------------------------------------------ sparse meshes: the coarse pass and the tiles
+//
+// include/rm_raymarch.h ("sparse meshes") has the rule.  The coarse pass wants the EXACT field at a block's centre --
+// min(10, min over all objects of Primitive.sdf), what an acceleration-None upload of the scene answers -- whatever structure the
+// active scene has: a BVH or octree field is the marchers' bound and proves nothing about a block.  Under a BVH (sphere and
+// primitive-record scenes) the minimum is found by a pruned walk of the skip-linked nodes: a primitive lies inside its leaf's
+// box, so no primitive of a subtree is nearer than the subtree's box, and a subtree whose box is farther than the best value so
+// far -- by a margin of 2^-20, relative and absolute, for the binary32 boxes and the roundings of the distance itself -- cannot
+// lower it.  Math.min does not depend on the order, so the pruned minimum is the full one, bit for bit.
+template <int GEN>
+__device__ double bvh_exact_distance(const RmRenderParams &P, const Vec3f &p) {
+    double best = RM_MAX_DIST;
+    const double x = p.x, y = p.y, z = p.z;
+    for (int i = 0; i < P.bvh_nodes;) {
+        const RmBvhNode node = P.bvh[i];
+        const double ex = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[0]) - x, x - static_cast<double>(node.hi[0])), 0.0);
+        const double ey = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[1]) - y, y - static_cast<double>(node.hi[1])), 0.0);
+        const double ez = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[2]) - z, z - static_cast<double>(node.hi[2])), 0.0);
+        const double db = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+        if (db * (1.0 - 0x1p-20) - 0x1p-20 > best) {
+            i = node.skip;
+            continue;
+        }
+        if (node.leaf < 0) {
+            i = i + 1;
+            continue;
+        }
+        const int first = node.leaf >> 8, cnt = node.leaf & 0xFF;
+        for (int k = 0; k < cnt; ++k) best = min_dist(pick_sdf<GEN>(P, P.bvh_prims[first + k], p), best);
+        i = node.skip;
+    }
+    return best;
+}
+
+// One lane per block: the exact distance at the block's centre, the keep flag into slot (0 kept, -1 dropped; the scatter of
+// rm_mesh_sparse.hip turns it into the rank) and the kept blocks of the workgroup into totals.
+template <int GEN, bool WALK>
+__global__ __launch_bounds__(256) void blocks_kernel(const RmRenderParams P, const RmBlocksArgs A) {
+    __shared__ unsigned int s_kept[4];
+    const unsigned int b = blockIdx.x * 256u + threadIdx.x;
+    bool keep = false;
+    if (b < A.n_blocks) {
+        const unsigned int row = b / A.nbu, bx = b - row * A.nbu, bz = row / A.nbv, by = row - bz * A.nbv;
+        const double fi = static_cast<double>(min(8u * bx + 4u, A.nu - 1u)), fj = static_cast<double>(min(8u * by + 4u, A.nv - 1u)),
+                     fk = static_cast<double>(min(8u * bz + 4u, A.nw - 1u));
+        Vec3f p;
+        p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
+        p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
+        p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+        uint32_t c = 0;
+        const double d = WALK ? bvh_exact_distance<GEN>(P, p) : all_prims_distance<GEN>(P, p, c);
+        keep = !(__builtin_fabs(d - A.iso) > A.bound);  // a NaN distance keeps the block
+        if (A.dist) A.dist[b] = d;
+        A.slot[b] = keep ? 0 : -1;
+    }
+    const unsigned long long kept = __ballot(keep);
+    if ((threadIdx.x & 63u) == 0) s_kept[threadIdx.x >> 6] = static_cast<unsigned int>(__popcll(kept));
+    __syncthreads();
+    if (threadIdx.x == 0) A.totals[blockIdx.x] = s_kept[0] + s_kept[1] + s_kept[2] + s_kept[3];
+}
+
+// One workgroup per kept block, three passes over the 729 points of its tile, a fastest: the scene_distance of field_kernel at
+// the lattice's own points, so a tile holds what rm_scene_field returns there, bit for bit; a tile point beyond the lattice
+// holds the quiet NaN 0x7FF8000000000000.  A wave's points lie in a box of 9 x 9 x 2 lattice steps: its BVH candidates are
+// coherent.  Faces shared by two kept blocks are evaluated by both (729 evaluations for 512 points of a block's own).
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void tiles_kernel(const RmRenderParams P, const RmTilesArgs A) {
+    const unsigned int r = blockIdx.x;
+    const unsigned int b = static_cast<unsigned int>(A.list[r]);
+    const unsigned int row = b / A.nbu, bx = b - row * A.nbu, bz = row / A.nbv, by = row - bz * A.nbv;
+    double *out = A.tiles + static_cast<size_t>(r) * RM_SPARSE_TILE;
+#pragma unroll 1
+    for (unsigned int t = threadIdx.x; t < RM_SPARSE_TILE; t += 256u) {
+        const unsigned int q = t / 9u, ta = t - q * 9u, tg = q / 9u, tb = q - tg * 9u;
+        const unsigned int i = 8u * bx + ta, j = 8u * by + tb, k = 8u * bz + tg;
+        double d = __longlong_as_double(0x7FF8000000000000ll);
+        if (i < A.nu && j < A.nv && k < A.nw) {
+            const double fi = static_cast<double>(i), fj = static_cast<double>(j), fk = static_cast<double>(k);
+            Vec3f p;
+            p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
+            p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
+            p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+            uint32_t c = 0;
+            d = scene_distance<ACCEL, GEN>(P, p, c);
+        }
+        out[t] = d;
+    }
+}
+
 // ------------------------------------------------------------------ point queries (rm_scene_points)
 //
 // Distance, gradient, object and projection onto the surface for caller-supplied points (include/rm_raymarch.h has the rule):
@@ -1944,6 +2033,54 @@ hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFiel
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_blocks)(const RmRenderParams &p, const RmBlocksArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n_blocks == 0 || a.n_blocks > RM_SPARSE_MAX_BLOCKS || a.n_groups != (a.n_blocks + 255u) / 256u) return hipErrorInvalidValue;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    const dim3 grid(a.n_groups), block(256);
+    // the pruned walk where there is a tree of boxes around sphere or primitive records; every object otherwise
+    const bool walk = p.accel == 2 && p.general < 2 && p.bvh_nodes > 0;
+#define RM_BLK(G, W)                                                                   \
+    {                                                                                  \
+        hipLaunchKernelGGL((blocks_kernel<G, W>), grid, block, shmem, stream, pl, a);   \
+        if (kernel_name) *kernel_name = "blocks_kernel<" #G ", " #W ">" RM_LEN_TAG;    \
+    }
+    if (p.general == 3) RM_BLK(3, false)
+    else if (p.general == 2) RM_BLK(2, false)
+    else if (p.general) {
+        if (walk) RM_BLK(1, true) else RM_BLK(1, false)
+    } else {
+        if (walk) RM_BLK(0, true) else RM_BLK(0, false)
+    }
+#undef RM_BLK
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    return rm_launch_blocks_compact(a, stream);
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_tiles)(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n_kept == 0 || a.n_kept > RM_SPARSE_MAX_BLOCKS) return hipErrorInvalidValue;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    const dim3 grid(a.n_kept), block(256);
+#define RM_TLK(A, O, G)                                                              \
+    {                                                                                \
+        hipLaunchKernelGGL((tiles_kernel<A, G>), grid, block, shmem, stream, pl, a);  \
+        if (kernel_name) *kernel_name = "tiles_kernel<" #A ", " #G ">" RM_LEN_TAG;   \
+    }
+    RM_DISPATCH(RM_TLK)
+#undef RM_TLK
+    return hipGetLastError();
 }
 
 hipError_t RM_LEN_VARIANT(rm_launch_points)(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name) {

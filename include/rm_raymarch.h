@@ -368,6 +368,101 @@ RM_API int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const vo
 RM_API int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *vertices, int64_t cap_vertices,
                          uint32_t *quads, int64_t cap_quads, rm_mesh_info *info);
 
+/* ---- sparse meshes: the same mesh from the 8 x 8 x 8-cell blocks near the surface ------------------------------ */
+
+#define RM_SPARSE_BLOCK 8
+typedef struct rm_sparse_info {  /* 32 bytes */
+    int64_t n_blocks;            /* blocks of the lattice */
+    int64_t n_kept;              /* blocks the coarse pass kept */
+    int64_t reserved[2];         /* written 0 */
+} rm_sparse_info;
+
+/* Only a thin shell of cells around the surface can hold a vertex, and a distance says how far the surface is: one exact
+ * evaluation per block proves most of a volume empty.  Three device entries in the style of the dense path -- the caller owns
+ * every buffer, counting and filling calls are asynchronous -- and one host convenience entry.  The rule, operation for
+ * operation (tests/mesh_sparse_model.py restates it; results are equal byte for byte):
+ *   blocks    B = RM_SPARSE_BLOCK = 8.  An axis with n points has ceil((n - 1) / 8) blocks, 0 when n < 2 (rm_lattice_blocks).
+ *             Block (bx, by, bz) has the linear index (bz * nbv + by) * nbu + bx; its cells are 8 bx .. min(8 bx + 8, nu - 1) - 1
+ *             on axis i and likewise on j and k.  At most 2^24 blocks; the 2^30-point limit of the dense mesher does not
+ *             apply, counts up to 65 535 per axis are allowed, fine linear indices are 64-bit values everywhere.
+ *   tile      the 9 x 9 x 9 lattice points (8 bx + a, 8 by + b, 8 bz + g), a, b, g = 0 .. 8, of a block; the value of tile
+ *             point (a, b, g) sits at (g * 9 + b) * 9 + a.  A tile point beyond the lattice holds the quiet NaN
+ *             0x7FF8000000000000; no existing cell reads it.
+ *   centre    of a block: the lattice point (min(8 bx + 4, nu - 1), min(8 by + 4, nv - 1), min(8 bz + 4, nw - 1)), formed by
+ *             the lattice's own point rule (binary64, left to right, one rounding to binary32).
+ *   d         the EXACT field at the centre at lattice->time: min(10, min over all objects of Primitive.sdf) -- what
+ *             rm_scene_distance returns for an acceleration-None upload of the same scene, byte for byte, whatever
+ *             acceleration the active scene has.  (A BVH or octree field is the marchers' bound; under a BVH it is an
+ *             over-estimate and cannot prove a block empty.)  Under a BVH, sphere and primitive-record scenes find d by a
+ *             pruned walk of the skip-linked nodes: best starts at 10; with db the binary64 distance from the centre to a
+ *             node's box (0 inside), sqrt((ex * ex + ey * ey) + ez * ez) of the per-axis excesses, the subtree is skipped iff
+ *             db * (1 - 2^-20) - 2^-20 > best; at a leaf best = min(best, Primitive.sdf) for each of its primitives.  A
+ *             primitive lies inside its leaf's box, so the pruned minimum is the full minimum.  Every other scene evaluates
+ *             every object.
+ *   bound     R = 4 * (|du| + |dv| + |dw|), each norm sqrt((x * x + y * y) + z * z) in binary64 of the widened binary32 step:
+ *             no point of a block's cells is farther from its centre.  slack = M * 2^-20, M the largest |component| among the
+ *             lattice's eight binary32 corner points (indices 0 and count - 1): it covers the binary32 rounding of two points.
+ *             bound = lipschitz * R + slack, binary64, in that order.
+ *   keep      a block is KEPT iff !(fabs(d - iso) > bound): a NaN distance keeps the block.
+ *             GUARANTEE: if the exact field is `lipschitz`-Lipschitz (every distance function of primitives and of unions is
+ *             1-Lipschitz; smooth blends and displacements may need more), no dropped block contains a point where
+ *             field - iso changes sign.
+ *   slots     kept blocks are numbered 0, 1, 2, ... in increasing block index: the block's slot.
+ *   mesh      inside / active / hole, the vertex position, the quad ring and the winding are rm_mesh_field_device's rule
+ *             unchanged, on the tile values, except: a cell of a block that was not kept is not active, and holes are counted
+ *             in kept blocks only.  Vertices are numbered by (slot, local cell index (z * 8 + y) * 8 + x); quads are in
+ *             increasing (slot of the block whose cell has its low corner at p, 3 * local(p) + A).
+ *   keys      cells[v] is the fine linear index l = (k * nv + j) * nu + i of vertex v's cell, edges[q] is 3 * l(p) + A of quad
+ *             q: the dense mesher's sort keys.  Sorting the vertices by cells and the quads by edges (and renaming the
+ *             vertices) gives rm_mesh_field_device's mesh of the same values, byte for byte, whenever every cell that is
+ *             active in the dense volume lies in a kept block.
+ *
+ * rm_lattice_blocks: the three block counts of a lattice, host-only, no ctx; RM_E_INVALID for a lattice rm_scene_field
+ * refuses or null dims.
+ *
+ * rm_scene_blocks_device: which blocks to keep, one lane per block; a count kernel, a scan and a scatter, asynchronous on
+ * `stream`, nothing depends on arrival order.  d_slot int32[n_blocks]: the block's slot or -1.  d_list int32[n_blocks]: the
+ * kept blocks in slot order (entries from n_kept on are not written).  d_dist f64[n_blocks], optional: d per block.  d_info:
+ * an rm_sparse_info.  RM_E_INVALID -- ahead of RM_E_NO_DEVICE, and RM_E_NO_SCENE last -- for everything rm_scene_field
+ * refuses about a lattice, more than 2^24 blocks, a non-finite iso, a lipschitz that is not finite and > 0, null d_info, null
+ * d_slot or d_list when the lattice has blocks, d_slot / d_list not 4-byte or d_dist / d_info not 8-byte aligned.  A lattice
+ * without blocks is RM_OK: zero info, nothing launched.  rm_last_kernel: blocks_kernel<GEN, WALK>.
+ *
+ * rm_scene_tiles_device: the ACTIVE scene's own distance function -- the values rm_scene_field returns, bit for bit -- at the
+ * 729 points of each of the n_kept blocks of d_list, into d_tiles f64[n_kept][729].  One 256-thread workgroup per kept block,
+ * three passes, a fastest: a wave's points sit in one small box, so its BVH candidates are coherent.  Faces shared by two kept
+ * blocks are evaluated once per block that touches them: 729 evaluations against 512 points of a block's own.  Ahead-of-time
+ * kernels only; the knobs `filter` and `length` apply as for rm_scene_field.  RM_E_INVALID for the lattice as above, n_kept
+ * outside 0 .. n_blocks, a null d_list or d_tiles with n_kept > 0, d_list not 4-byte or d_tiles not 8-byte aligned;
+ * RM_E_NO_DEVICE; RM_E_NO_SCENE last.  n_kept == 0 is RM_OK.  rm_last_kernel: tiles_kernel<ACCEL, GEN>.
+ *
+ * rm_mesh_tiles_device: surface nets over the tiles; it needs no scene, like rm_mesh_field_device.  One workgroup per kept
+ * block, the tile staged once in LDS, two cells per lane; neighbour blocks are reached through d_slot; a cell -> vertex map
+ * (2 KB per kept block) and the workgroup totals live in the context's scratch buffer, ordered as rm_mesh_field_device's.
+ * d_cells (int64 per vertex) and d_edges (int64 per quad) are optional and sized by the capacities.  The counting and
+ * capacity protocol, the truncation semantics and rm_mesh_info are exactly rm_mesh_field_device's.  RM_E_INVALID for the
+ * lattice as above, n_kept outside 0 .. min(n_blocks, 2^21) (vertex numbers are 32-bit), null d_info, null d_slot when the
+ * lattice has blocks, null d_list or d_tiles with n_kept > 0, a non-finite iso, a negative capacity, a null vertex or quad
+ * buffer with a capacity above 0, d_slot / d_list / vertices / quads not 4-byte or d_tiles / d_cells / d_edges / d_info not
+ * 8-byte aligned; RM_E_NO_DEVICE.  n_kept == 0 is RM_OK: zero totals.  rm_last_kernel: mesh_tiles_count_kernel.
+ *
+ * rm_scene_mesh_sparse: the three steps in the context's scratch buffer with n_kept read back once in between; host buffers,
+ * synchronous: min(total, capacity) vertices, quads and keys are copied back.  cells, edges and sparse_info may be NULL.  The
+ * checks of the three entries for its own arguments (no alignment is asked of info and sparse_info), ahead of RM_E_NO_DEVICE;
+ * RM_E_NO_SCENE last; RM_E_UNSUPPORTED when more than 2^21 blocks are kept (sparse_info says how many).  The scratch holds 8
+ * bytes per block, and per kept block its tile and its map, plus the outputs up to their capacities.  None of the four is a render entry: they neither consume nor fire rm_render_attach_diagnostics and
+ * leave rm_scene_set_time's value alone. */
+RM_API int rm_lattice_blocks(const rm_lattice *lattice, int32_t dims[3]);
+RM_API int rm_scene_blocks_device(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, void *d_slot, void *d_list,
+                                  void *d_dist, void *d_info, void *stream);
+RM_API int rm_scene_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_list, int64_t n_kept, void *d_tiles, void *stream);
+RM_API int rm_mesh_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept,
+                                const void *d_tiles, double iso, void *d_vertices, int64_t cap_vertices, void *d_quads, int64_t cap_quads,
+                                void *d_cells, void *d_edges, void *d_info, void *stream);
+RM_API int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, float *vertices, int64_t cap_vertices,
+                                uint32_t *quads, int64_t cap_quads, int64_t *cells, int64_t *edges, rm_mesh_info *info,
+                                rm_sparse_info *sparse_info);
+
 /* ---- ray queries ------------------------------------------------------------------ */
 
 typedef struct rm_ray_query {
