@@ -281,6 +281,7 @@ SIGNATURES = {
     "rm_debug_overlap_fill": (C.c_int, [_VP, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "rm_debug_step_box": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "rm_debug_cell_tab": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "rm_debug_exact_tree": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "rm_debug_rect_cull": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "rm_debug_leaf_rects": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),
     "rm_rtc_source": (C.c_int, [_VP, C.c_char_p, C.c_int64, C.POINTER(C.c_int64)]),

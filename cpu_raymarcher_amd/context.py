@@ -1,5 +1,6 @@
 """One rm_ctx per GPU (include/rm_raymarch.h "Threading"): owns the device-resident scene."""
 import collections
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -156,6 +157,27 @@ class Context:
         v = C.c_int64(0)
         N.check(self._h, N.lib().rm_get_option(self._h, key.encode(), C.byref(v)))
         return v.value
+
+    @contextlib.contextmanager
+    def _exact(self, exact):
+        """Option `exact` = 1 for the length of one call (the keyword `exact` of the point, field and mesh queries): the
+        value the option had comes back afterwards, also when the call raises.  exact=False leaves the option as it is."""
+        if not exact:
+            yield
+            return
+        before = self.get_option("exact")
+        self.set_option("exact", 1)
+        try:
+            yield
+        finally:
+            self.set_option("exact", before)
+
+    def exact_tree(self):
+        """What an exact query of the active scene walks (rm_debug_exact_tree; no device needed): dict(mode = 0 every object,
+        1 the scene's BVH, 2 an exact tree of its own -- built now if it is due --, nodes, leaves, depth of that tree)."""
+        out = (C.c_int32 * 4)()
+        N.check(self._h, N.lib().rm_debug_exact_tree(self._h, out))
+        return dict(mode=out[0], nodes=out[1], leaves=out[2], depth=out[3])
 
     def launch_fill(self, asked):
         """Workgroups per CU a v2 launch brings when `blocks_per_cu` is `asked`: option `min_fill` and the hardware-queue
@@ -773,7 +795,7 @@ class Context:
             raise N.RmError(rc, "rm_lattice_points")
         return out
 
-    def field(self, origin, du, dv, dw=None, shape=(1, 1), time=0.0, dist32=False, count=True, device=False):
+    def field(self, origin, du, dv, dw=None, shape=(1, 1), time=0.0, dist32=False, count=True, device=False, exact=False):
         """Scene.getDistance at every point of a lattice the device forms itself (rm_scene_field; the rule is in
         include/rm_raymarch.h): point (i, j, k) = f32(origin + i * du + j * dv + k * dw), shape = (nu, nv) for a slice or
         (nu, nv, nw) for a volume.  Returns (dist, count) shaped [nw, nv, nu] -- [nv, nu] for a two-element shape --: dist
@@ -781,7 +803,13 @@ class Context:
         counted) or None without `count`.  The values are scene_distance's at lattice_points(...) with the scene at `time`;
         scene_set_time's value is left alone.  numpy results come through the host entry (synchronous); device=True returns
         torch CUDA tensors through rm_scene_field_device on torch's current stream (count an int32 tensor holding the u32
-        bits, as ray_march's counts)."""
+        bits, as ray_march's counts).  exact=True: the exact field (option `exact` for this call) -- min(10, min over ALL
+        objects of Primitive.sdf), what an acceleration-None upload answers, whatever structure the scene has; count is then
+        the evaluations made."""
+        with self._exact(exact):
+            return self._field(origin, du, dv, dw, shape, time, dist32, count, device)
+
+    def _field(self, origin, du, dv, dw, shape, time, dist32, count, device):
         lat = make_lattice(origin, du, dv, dw, shape, time)
         full = (lat.nw, lat.nv, lat.nu)
         out_shape = full[1:] if len(tuple(shape)) == 2 else full
@@ -798,11 +826,11 @@ class Context:
             N.check(self._h, N.lib().rm_scene_field(self._h, C.byref(lat), None if dist32 else _ptr(d), _ptr(d) if dist32 else None, _ptr(c)))
         return d.reshape(out_shape), (None if c is None else c.reshape(out_shape))
 
-    def field_slice(self, axis="z", offset=0.0, half_extent=5.0, size=(256, 256), time=0.0, dist32=False, count=True, device=False):
+    def field_slice(self, axis="z", offset=0.0, half_extent=5.0, size=(256, 256), time=0.0, dist32=False, count=True, device=False, exact=False):
         """`field` of slice_lattice(axis, offset, half_extent, size): the axis-aligned plane through the scene, sampled at
         texel centres -> (dist, count) shaped [size[1], size[0]]."""
         origin, du, dv, shape = slice_lattice(axis, offset, half_extent, size)
-        return self.field(origin, du, dv, shape=shape, time=time, dist32=dist32, count=count, device=device)
+        return self.field(origin, du, dv, shape=shape, time=time, dist32=dist32, count=count, device=device, exact=exact)
 
     @staticmethod
     def slice_lattice(axis="z", offset=0.0, half_extent=5.0, size=(256, 256)):
@@ -867,7 +895,7 @@ class Context:
                                                         _ptr(steps), _ptr(cnt), _current_stream_ptr()))
         return dist, nrm, obj, steps, cnt
 
-    def points(self, points, normal=True, object=True, snap=0, tol=1e-4, iso=0.0, time=0.0, device=False):
+    def points(self, points, normal=True, object=True, snap=0, tol=1e-4, iso=0.0, time=0.0, device=False, exact=False):
         """What can be asked about a point (rm_scene_points; the rule is in include/rm_raymarch.h), for float32 [n, 3] points:
         Scene.getDistance there, getNormal's normal, the object that attains the distance, and -- with snap = K > 0 -- the
         point moved onto the surface getDistance == iso by up to K steps of its distance along the normal, until
@@ -876,7 +904,12 @@ class Context:
         given with snap = 0), with the scene at `time`; scene_set_time's value is left alone.  numpy in -> numpy out through
         the host entry (synchronous); a CUDA tensor in, or device=True, -> CUDA tensors through rm_scene_points_device on
         torch's current stream (count an int32 tensor holding the u32 bits).  An empty octree leaf has a constant distance
-        and so no gradient: a projection wants acceleration None or BVH."""
+        and so no gradient, and a BVH's distance over-estimates inside leaf boxes: exact=True (option `exact` for this call)
+        answers all of it from the exact field instead, whatever structure the scene has."""
+        with self._exact(exact):
+            return self._points(points, normal, object, snap, tol, iso, time, device)
+
+    def _points(self, points, normal, object, snap, tol, iso, time, device):
         q = self._point_query(normal, snap, tol, iso, time)
         if _is_torch(points) or device:
             import torch
@@ -901,10 +934,10 @@ class Context:
                                                  _ptr(cnt)))
         return Points(pos, dist, nrm, obj, steps, cnt)
 
-    def project(self, points, steps=4, tol=1e-4, iso=0.0, time=0.0, device=False):
+    def project(self, points, steps=4, tol=1e-4, iso=0.0, time=0.0, device=False, exact=False):
         """The snap alone: `points` moved onto the surface getDistance == iso by up to `steps` steps (points(...) without
-        normal and object).  Returns (position, dist, steps)."""
-        r = self.points(points, normal=False, object=False, snap=steps, tol=tol, iso=iso, time=time, device=device)
+        normal and object; exact: as there).  Returns (position, dist, steps)."""
+        r = self.points(points, normal=False, object=False, snap=steps, tol=tol, iso=iso, time=time, device=device, exact=exact)
         return r.position, r.dist, r.steps
 
     def _mesh_attributes(self, vertices, iso, time, snap, tol):
@@ -966,18 +999,21 @@ class Context:
             return out
         return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
 
-    def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4):
+    def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4,
+             exact=False):
         """The surface of the active scene over a lattice: `field` samples Scene.getDistance on the device at `time` (float64,
         once; the volume stays there) and `mesh_field` extracts the surface getDistance = iso from it.  Returns what
         mesh_field returns (attributes, snap, tol: as there).  The field under a BVH or an octree is the marchers' bound, not
-        always the exact distance: an offset surface (iso != 0) wants acceleration None."""
+        always the exact distance: an offset surface (iso != 0) wants exact=True (option `exact` for this call: the volume
+        and the attribute pass then come from the exact field)."""
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
         if self.device < 0:
             raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
-        vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
-        return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
-                               tol=tol, time=time)
+        with self._exact(exact):
+            vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
+            return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
+                                   tol=tol, time=time)
 
     # ---- sparse meshes: the same mesh from the 8 x 8 x 8-cell blocks near the surface ---------
     def sparse_blocks(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, dist=True):
@@ -1009,7 +1045,7 @@ class Context:
         return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
 
     def mesh_sparse(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, order="dense", device=False, triangles=False,
-                    attributes=False, snap=0, tol=1e-4):
+                    attributes=False, snap=0, tol=1e-4, exact=False):
         """`mesh` from the blocks near the surface only (include/rm_raymarch.h, "sparse meshes"): `sparse_blocks` keeps the
         blocks of 8 x 8 x 8 cells that can hold the surface when the exact field is `lipschitz`-Lipschitz (1 for primitives
         and their unions), rm_scene_tiles_device samples the active scene at the 729 points of each kept block and
@@ -1018,9 +1054,14 @@ class Context:
         possible.  order="dense" sorts the vertices and the quads by the dense mesher's keys on the device and renames the
         vertices: the result is `mesh`'s, byte for byte, whenever every cell the dense volume has active lies in a kept block
         -- what `lipschitz` guarantees for an exact field.  order="tile" returns the ABI's order, by kept block.  Everything
-        else as `mesh` (the winding of a left-handed lattice is flipped here too)."""
+        else as `mesh` (the winding of a left-handed lattice is flipped here too; exact=True: the tiles and the attribute
+        pass come from the exact field, which the coarse pass uses anyway)."""
         if order not in ("dense", "tile"):
             raise ValueError("order is 'dense' or 'tile'")
+        with self._exact(exact):
+            return self._mesh_sparse(origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol)
+
+    def _mesh_sparse(self, origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol):
         blocks = self.sparse_blocks(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, dist=False)
         import torch
         lat = make_lattice(origin, du, dv, dw, shape, time)
@@ -1061,11 +1102,11 @@ class Context:
         return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
 
     def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None, attributes=False, snap=0,
-                 tol=1e-4, sparse=False, lipschitz=1.0):
+                 tol=1e-4, sparse=False, lipschitz=1.0, exact=False):
         """`mesh` over an axis-aligned lattice of cells[0] x cells[1] x cells[2] cells that covers scene_info()'s root box
         and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
         `box` = (lo, hi) replaces the root box: a scene without a structure reports none.  sparse=True: `mesh_sparse` with
-        `lipschitz` over the same lattice (order "dense": the same mesh)."""
+        `lipschitz` over the same lattice (order "dense": the same mesh).  exact: as `mesh`."""
         if box is None:
             info = self.scene_info()
             box = (info["root_min"], info["root_max"])
@@ -1077,7 +1118,7 @@ class Context:
             raise ValueError("at least 5 cells per axis")
         m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
         step = (hi - lo + 2 * m) / c
-        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
+        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact)
         if sparse:
             more["lipschitz"] = lipschitz
         return (self.mesh_sparse if sparse else self.mesh)(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c),

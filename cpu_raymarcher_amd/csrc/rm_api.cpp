@@ -475,6 +475,16 @@ struct rm_ctx {
     unsigned long long scene_gen = 0;  // bumped by every upload_scene
     int64_t opt_n0_batch = 64;  // v2 BVH: see RmRenderParams::n0_batch
     int64_t opt_length = 0;  // vec3.length: 0 Math.hypot (gl-matrix 3.0 - 3.4.3), 1 Math.sqrt(x*x + y*y + z*z)
+    // Point, field, tile and mesh queries answer from the exact field E(x) = min(10, min over ALL objects of Primitive.sdf(x))
+    // instead of Scene.getDistance (include/rm_raymarch.h, "the exact field").  What they walk (ensure_exact_tree): the scene's
+    // BVH, or -- octree and None scenes -- the exact tree below, built at the first exact query after the scene was made and
+    // dropped by every upload_scene.
+    int64_t opt_exact = 0;
+    bool exact_ready = false;  // exact_mode and exact_tree are the active scene's
+    int exact_mode = 0;        // rmh::exact_tree_mode, or 0 where the own tree could not be built
+    rmh::ExactTree exact_tree; // mode 2
+    RmBvhNode *d_exact_nodes = nullptr;  // mode 2 on a context with a device
+    int32_t *d_exact_ids = nullptr;
     const char *last_kernel = "";
     std::string last_kernel_kept;  // rm_scene_edit_spheres: the name behind last_kernel across the upload (which releases run-time compiled kernels and their names)
     // rm_scene_edit_spheres: the four pair loops of the scene build (rm_scene_host.h, PairLoops) run on the device
@@ -687,7 +697,14 @@ void free_device_scene(rm_ctx *ctx) {
     ctx->v2_special.clear();  // (a new scene is a new configuration anyway: its counts and LDS layout are in the key)
     ctx->rtc_failed.clear();
     ctx->last_kernel = "";
+    ctx->exact_ready = false;  // the exact tree is the old scene's: the next exact query builds the new one's
+    ctx->exact_mode = 0;
+    ctx->exact_tree = rmh::ExactTree();
     if (!ctx->has_device) return;
+    (void)hipFree(ctx->d_exact_nodes);
+    (void)hipFree(ctx->d_exact_ids);
+    ctx->d_exact_nodes = nullptr;
+    ctx->d_exact_ids = nullptr;
     DeviceScene &d = ctx->dev;
 #define RM_X(name, always) (void)hipFree(d.name);
     RM_SCENE_ARRAYS(RM_X)
@@ -1090,6 +1107,42 @@ void fill_scene_view(const rm_ctx *ctx, RmRenderParams &p) {
         p.ext_inv[k] = ctx->host.ext_inv[k];
     }
     p.use_ext = (ctx->opt_ext && ctx->host.accel == RM_ACCEL_BVH && !ctx->host.ext_cells.empty() && ctx->host.ext_dim[0] > 0) ? 1 : 0;
+}
+
+// Option `exact`: what the next exact query of the active scene walks (rmh::exact_tree_mode), decided -- and, for an own tree,
+// built on the host and copied up, synchronously -- once per scene; free_device_scene drops it with the scene.  A tree that
+// cannot be built or uploaded leaves mode 0 (every object), which answers the same values.
+int ensure_exact_tree(rm_ctx *ctx) {
+    if (ctx->exact_ready) return RM_OK;
+    int mode = rmh::exact_tree_mode(ctx->host);
+    if (mode == 2 && !rmh::build_exact_tree(ctx->host, ctx->exact_tree)) mode = 0;
+    if (mode == 2 && ctx->has_device) {
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        int rc;
+        if ((rc = upload_vec(ctx, ctx->exact_tree.nodes, &ctx->d_exact_nodes))) return rc;
+        if ((rc = upload_vec(ctx, ctx->exact_tree.ids, &ctx->d_exact_ids))) return rc;
+    }
+    ctx->exact_mode = mode;
+    ctx->exact_ready = true;
+    return RM_OK;
+}
+
+// The parameter block of a point, field or tile launch under option `exact`: the exact instantiation and the tree it walks
+// (RM_ACCEL_EXACT, rm_kernels.h).  Without the option the block stays as it is.
+int apply_exact(rm_ctx *ctx, RmRenderParams &p) {
+    if (!ctx->opt_exact) return RM_OK;
+    const int rc = ensure_exact_tree(ctx);
+    if (rc) return rc;
+    p.accel = RM_ACCEL_EXACT;
+    if (ctx->exact_mode == 2) {
+        p.bvh = ctx->d_exact_nodes;
+        p.bvh_prims = ctx->d_exact_ids;
+        p.bvh_nodes = static_cast<int32_t>(ctx->exact_tree.nodes.size());
+    } else if (ctx->exact_mode == 0) {
+        p.bvh_nodes = 0;
+    }
+    p.use_ext = 0;
+    return RM_OK;
 }
 
 
@@ -1912,8 +1965,14 @@ int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const 
     RmRenderParams p;
     RmFieldArgs unused;
     fill_field(ctx, lat, p, unused);
+    if (const int erc = apply_exact(ctx, p)) return erc;
     RmTilesArgs a;
     fill_sparse_lattice(lat, g, a);
+    // read by the exact launch only: the coarse pass's bound for a 1-Lipschitz field, and per axis the same four steps and slack
+    a.radius = sparse_bound(*lat, 1.0);
+    const double slack = sparse_bound(*lat, 0.0);
+    for (int c = 0; c < 3; ++c)
+        a.half[c] = 4.0 * ((std::fabs(static_cast<double>(lat->du[c])) + std::fabs(static_cast<double>(lat->dv[c]))) + std::fabs(static_cast<double>(lat->dw[c]))) + slack;
     a.list = static_cast<const int32_t *>(d_list);
     a.tiles = static_cast<double *>(d_tiles);
     a.n_kept = static_cast<unsigned int>(n_kept);
@@ -2879,6 +2938,7 @@ int rm_scene_field_device(rm_ctx *ctx, const rm_lattice *lattice, void *d_dist, 
     RmRenderParams p;
     RmFieldArgs a;
     fill_field(ctx, lattice, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
     a.dist = static_cast<double *>(d_dist);
     a.dist32 = static_cast<float *>(d_dist32);
     a.count = static_cast<uint32_t *>(d_count);
@@ -2897,6 +2957,7 @@ int rm_scene_field(rm_ctx *ctx, const rm_lattice *lattice, double *dist, float *
     RmRenderParams p;
     RmFieldArgs a;
     fill_field(ctx, lattice, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
     RM_HIP(ctx, hipSetDevice(ctx->device));
     // Through the scratch buffer in chunks of whole lattice rows, at most 4 M points (16 B per point with every output: 64 MB);
     // a row always fits (nu <= 65535).  Only the outputs asked for are staged and copied back.
@@ -2933,6 +2994,7 @@ int rm_scene_points_device(rm_ctx *ctx, const rm_point_query *q, int64_t n, cons
     RmRenderParams p;
     RmPointArgs a;
     fill_points(ctx, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
     a.points = static_cast<const float *>(d_points);
     a.position = static_cast<float *>(d_position);
     a.dist = static_cast<double *>(d_dist);
@@ -2954,6 +3016,7 @@ int rm_scene_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float
     RmRenderParams p;
     RmPointArgs a;
     fill_points(ctx, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
     RM_HIP(ctx, hipSetDevice(ctx->device));
     // Through the scratch buffer in chunks of at most 4 M points, as the ray queries (ray_call): 12 B per point go up, and only
     // the outputs asked for are staged and copied back (48 B per point with all six: 192 MB).  The positions are written over the
@@ -3071,6 +3134,7 @@ int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *ver
     RmRenderParams p;
     RmFieldArgs a;
     fill_field(ctx, lattice, p, a);  // the field entries' own launch, at the lattice's time
+    if (const int erc = apply_exact(ctx, p)) return erc;
     a.dist = st.at<double>(o_vol);
     a.first = 0;
     a.n = n;
@@ -3616,6 +3680,28 @@ int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]) {
     return RM_OK;
 }
 
+// What the next exact query (option `exact`) of the active scene walks, without a device: out[0] the mode (0 every object, 1 the
+// scene's BVH, 2 an own tree), out[1 .. 3] the nodes, leaves and depth of that tree (zeros in mode 0).  Builds the own tree if
+// it is due, whatever the option says.
+int rm_debug_exact_tree(rm_ctx *ctx, int32_t out[4]) {
+    if (!ctx || !out) return RM_E_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    const int rc = ensure_exact_tree(ctx);
+    if (rc) return rc;
+    out[0] = ctx->exact_mode;
+    if (ctx->exact_mode == 1) {
+        out[1] = static_cast<int32_t>(ctx->host.bvh.size());
+        out[2] = ctx->host.bvh_leaves;
+        out[3] = ctx->host.bvh_depth;
+    } else if (ctx->exact_mode == 2) {
+        out[1] = static_cast<int32_t>(ctx->exact_tree.nodes.size());
+        out[2] = ctx->exact_tree.leaves;
+        out[3] = ctx->exact_tree.depth;
+    }
+    return RM_OK;
+}
+
 // The leaf rectangles of the bundle cull (option `rect_cull`), without a device.  `rot9` / `origin3`: the camera
 // (rm_camera_from_angles gives a job's), width x height the full frame.  out[0] whether the last v2 launch culled by
 // rectangles (0 before the first), out[1] whether a launch of the active scene with this camera and frame would, out[2] why
@@ -3728,6 +3814,7 @@ static const OptionRow kOptions[] = {
     {"n0_batch", &rm_ctx::opt_n0_batch, kRange, {1, 64}, "n0_batch must be in [1, 64]"},
     {"device_build", &rm_ctx::opt_device_build, kSwitch, {}, nullptr},
     {"length", &rm_ctx::opt_length, kRange, {0, 1}, "length must be 0 (Math.hypot) or 1 (Math.sqrt)"},  // part of the numeric contract, not a measurement knob (rm_raymarch.h)
+    {"exact", &rm_ctx::opt_exact, kRange, {0, 1}, "exact must be 0 (Scene.getDistance) or 1 (the exact field)"},  // as `length`: selects among defined results
 };
 
 static const OptionRow *find_option(const char *key) {

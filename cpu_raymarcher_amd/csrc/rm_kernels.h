@@ -275,7 +275,14 @@ struct RmTilesArgs {
     const int32_t *list;
     double *tiles;      // n_kept x RM_SPARSE_TILE
     unsigned int nu, nv, nw, nbu, nbv, n_kept;
+    // read by the exact launch only: what a tile point is away from the tile's centre point at most, per axis and in all
+    // (4 (|du| + |dv| + |dw|), the coarse pass's R, and its slack for the roundings)
+    double half[3], radius;
 };
+// Option `exact`: the value of RmRenderParams::accel in a point, field or tile launch that evaluates the exact field
+// (rm_kernels.hip, exact_distance).  Such a launch names the tree to walk in bvh / bvh_prims / bvh_nodes -- the scene's BVH or
+// its exact tree -- and bvh_nodes = 0 where every object is evaluated.
+#define RM_ACCEL_EXACT 3
 // rm_mesh_tiles_device (rm_mesh_sparse.hip): one workgroup per kept block, the fields vertex_position reads named as in RmMeshArgs
 struct RmSparseMeshArgs {
     double origin[3], du[3], dv[3], dw[3];

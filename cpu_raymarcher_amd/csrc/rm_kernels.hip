@@ -371,8 +371,13 @@ __device__ double oct_node_distance(const RmRenderParams &P, int node, const Vec
     return closest;
 }
 
+// ACCEL 3 (option `exact`; point, field and tile queries only): the exact field, defined with the sparse mesher below
+template <int GEN>
+__device__ double exact_distance(const RmRenderParams &P, const Vec3f &p, uint32_t &count);
+
 template <int ACCEL, int GEN>
 __device__ __forceinline__ double scene_distance(const RmRenderParams &P, const Vec3f &p, uint32_t &count) {
+    if constexpr (ACCEL == 3) return exact_distance<GEN>(P, p, count);
     if (ACCEL == 2) return bvh_distance<GEN>(P, p, count);
     if (ACCEL == 1) return oct_node_distance<GEN>(P, oct_find(P, p), p, count);
     return all_prims_distance<GEN>(P, p, count);
@@ -1291,8 +1296,12 @@ __global__ __launch_bounds__(256) void distance_kernel(const RmRenderParams P, c
 // range takes the point of linear index A.first + r -- 64 consecutive i per wave --, forms each component in binary64 left to
 // right with one rounding to binary32 (no contraction: -ffp-contract=off) and calls the scene_distance every other kernel
 // calls.  Outputs are indexed by r, each may be null.  (8 x 8 tiles of (i, j) per wave were measured and lost: DESIGN.md 4.)
+// The bodies of the field, tile and point kernels are device functions: the kernels of a scene's own field (field_kernel<ACCEL,
+// GEN>, ...) and those of the exact field (field_exact_kernel<GEN>, ...: ACCEL = RM_ACCEL_EXACT, sphere and primitive records
+// only -- expression programs have no tree to walk and run the acceleration-None instantiation, which evaluates every object)
+// instantiate them.
 template <int ACCEL, int GEN>
-__global__ __launch_bounds__(256) void field_kernel(const RmRenderParams P, const RmFieldArgs A) {
+__device__ __forceinline__ void field_body(const RmRenderParams &P, const RmFieldArgs &A) {
     const unsigned long long r = ((static_cast<unsigned long long>(A.block_first) + blockIdx.x) << 8) + threadIdx.x;
     if (r >= static_cast<unsigned long long>(A.n)) return;
     const unsigned long long l = static_cast<unsigned long long>(A.first) + r, row = l / A.nu, k = row / A.nv;
@@ -1306,6 +1315,14 @@ __global__ __launch_bounds__(256) void field_kernel(const RmRenderParams P, cons
     if (A.dist) A.dist[r] = d;
     if (A.dist32) A.dist32[r] = static_cast<float>(d);
     if (A.count) A.count[r] = c;
+}
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void field_kernel(const RmRenderParams P, const RmFieldArgs A) {
+    field_body<ACCEL, GEN>(P, A);
+}
+template <int GEN>
+__global__ __launch_bounds__(256) void field_exact_kernel(const RmRenderParams P, const RmFieldArgs A) {
+    field_body<3, GEN>(P, A);
 }
 
 // ------------------------------------------------------------------ object picking (rm_ray_pick)
@@ -1353,6 +1370,47 @@ __device__ void pick_list(const RmRenderParams &P, const int32_t *ids, int n, co
     }
 }
 
+// Whether no primitive inside the box lo .. hi can be nearer to (x, y, z) than `best`: the box is farther, by a margin of 2^-20,
+// relative and absolute, for the binary32 boxes and the roundings of the distance itself.  Strict: a primitive that ties
+// `best` is never pruned.  A point outside a primitive's padded box is outside the primitive, at least the box's distance
+// away; a point INSIDE the box may be inside the primitive, as deep as the primitive is large, and there the box says nothing
+// against a negative `best` (two overlapping spheres: once the first gave a negative value, the inequality alone prunes the
+// box of the second, whose distance is 0, though the point may lie deeper in it).  OUTSIDE_ONLY prunes only boxes that do not
+// contain the point.  The coarse pass of the sparse mesher keeps the inequality alone, as it was written.
+template <bool OUTSIDE_ONLY>
+__device__ __forceinline__ bool box_beyond(const float lo[3], const float hi[3], double x, double y, double z, double best) {
+    const double ex = __builtin_fmax(__builtin_fmax(static_cast<double>(lo[0]) - x, x - static_cast<double>(hi[0])), 0.0);
+    const double ey = __builtin_fmax(__builtin_fmax(static_cast<double>(lo[1]) - y, y - static_cast<double>(hi[1])), 0.0);
+    const double ez = __builtin_fmax(__builtin_fmax(static_cast<double>(lo[2]) - z, z - static_cast<double>(hi[2])), 0.0);
+    const double db = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+    return (!OUTSIDE_ONLY || db > 0.0) && db * (1.0 - 0x1p-20) - 0x1p-20 > best;
+}
+
+// min(10, min over the objects ids[] names of Primitive.sdf(p)) by a pruned walk of the skip-linked boxes `nodes` around them
+// (sphere and primitive records; the comment at bvh_exact_distance has the argument).  evaluated takes the evaluations made.
+template <int GEN, bool OUTSIDE_ONLY>
+__device__ double tree_exact_distance(const RmRenderParams &P, const RmBvhNode *nodes, int n_nodes, const int32_t *ids, const Vec3f &p,
+                                      uint32_t &evaluated) {
+    double best = RM_MAX_DIST;
+    const double x = p.x, y = p.y, z = p.z;
+    for (int i = 0; i < n_nodes;) {
+        const RmBvhNode node = nodes[i];
+        if (box_beyond<OUTSIDE_ONLY>(node.lo, node.hi, x, y, z, best)) {
+            i = node.skip;
+            continue;
+        }
+        if (node.leaf < 0) {
+            i = i + 1;
+            continue;
+        }
+        const int first = node.leaf >> 8, cnt = node.leaf & 0xFF;
+        for (int k = 0; k < cnt; ++k) best = min_dist(pick_sdf<GEN>(P, ids[first + k], p), best);
+        evaluated += static_cast<uint32_t>(cnt);
+        i = node.skip;
+    }
+    return best;
+}
+
 // The object at a point (include/rm_raymarch.h, rm_ray_pick and rm_scene_points): the lowest-index candidate of
 // Scene.getDistance at `hit` whose Primitive.sdf attains the distance; the walk forms that minimum again, so it takes no distance.
 // The candidates are what getDistance evaluates there (scene.ts:144-190): the octree leaf's primitives (none for an empty
@@ -1362,6 +1420,27 @@ template <int ACCEL, int GEN>
 __device__ __forceinline__ int object_at(const RmRenderParams &P, const Vec3f &hit, const int32_t *slot_obj) {
     double best = RM_MAX_DIST;
     int obj = -1;
+    if constexpr (ACCEL == 3) {  // option `exact`: every object is a candidate; the walk and the pruning of tree_exact_distance
+        if (GEN < 2 && P.bvh_nodes > 0) {
+            const double x = hit.x, y = hit.y, z = hit.z;
+            for (int i = 0; i < P.bvh_nodes;) {
+                const RmBvhNode node = P.bvh[i];
+                if (box_beyond<true>(node.lo, node.hi, x, y, z, best)) {
+                    i = node.skip;
+                    continue;
+                }
+                if (node.leaf < 0) {
+                    i = i + 1;
+                    continue;
+                }
+                pick_list<GEN>(P, P.bvh_prims + (node.leaf >> 8), node.leaf & 0xFF, slot_obj, hit, best, obj);
+                i = node.skip;
+            }
+            return obj;
+        }
+        pick_list<GEN>(P, nullptr, P.n_prims, slot_obj, hit, best, obj);
+        return obj;
+    }
     if (ACCEL == 1) {
         const int node = oct_find(P, hit);
         if (node < 0) pick_list<GEN>(P, nullptr, P.n_prims, slot_obj, hit, best, obj);
@@ -1414,29 +1493,24 @@ __device__ __forceinline__ int hit_object(const RmRenderParams &P, const Ray &ra
 // box, so no primitive of a subtree is nearer than the subtree's box, and a subtree whose box is farther than the best value so
 // far -- by a margin of 2^-20, relative and absolute, for the binary32 boxes and the roundings of the distance itself -- cannot
 // lower it.  Math.min does not depend on the order, so the pruned minimum is the full one, bit for bit.
+// (The walk itself is tree_exact_distance, with the point queries above: one text for this pass and for option `exact`.)
 template <int GEN>
 __device__ double bvh_exact_distance(const RmRenderParams &P, const Vec3f &p) {
-    double best = RM_MAX_DIST;
-    const double x = p.x, y = p.y, z = p.z;
-    for (int i = 0; i < P.bvh_nodes;) {
-        const RmBvhNode node = P.bvh[i];
-        const double ex = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[0]) - x, x - static_cast<double>(node.hi[0])), 0.0);
-        const double ey = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[1]) - y, y - static_cast<double>(node.hi[1])), 0.0);
-        const double ez = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[2]) - z, z - static_cast<double>(node.hi[2])), 0.0);
-        const double db = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
-        if (db * (1.0 - 0x1p-20) - 0x1p-20 > best) {
-            i = node.skip;
-            continue;
-        }
-        if (node.leaf < 0) {
-            i = i + 1;
-            continue;
-        }
-        const int first = node.leaf >> 8, cnt = node.leaf & 0xFF;
-        for (int k = 0; k < cnt; ++k) best = min_dist(pick_sdf<GEN>(P, P.bvh_prims[first + k], p), best);
-        i = node.skip;
+    uint32_t evaluated = 0;
+    return tree_exact_distance<GEN, false>(P, P.bvh, P.bvh_nodes, P.bvh_prims, p, evaluated);
+}
+
+// Option `exact` (include/rm_raymarch.h): E(x) = min(10, min over ALL objects of Primitive.sdf(x)) for the point, field and tile
+// queries, whatever structure the scene has.  The launch names the tree to walk in P.bvh / P.bvh_prims / P.bvh_nodes -- the
+// scene's own BVH or the exact tree the host built for an octree or None scene (rm_scene_host.h, ExactTree) -- and 0 nodes
+// where there is none to walk (expression programs, non-rigid transforms, ...): every object then, as acceleration None.
+// count takes the Primitive.sdf evaluations made.
+template <int GEN>
+__device__ double exact_distance(const RmRenderParams &P, const Vec3f &p, uint32_t &count) {
+    if constexpr (GEN < 2) {
+        if (P.bvh_nodes > 0) return tree_exact_distance<GEN, true>(P, P.bvh, P.bvh_nodes, P.bvh_prims, p, count);
     }
-    return best;
+    return all_prims_distance<GEN>(P, p, count);
 }
 
 // One lane per block: the exact distance at the block's centre, the keep flag into slot (0 kept, -1 dropped; the scatter of
@@ -1470,12 +1544,89 @@ __global__ __launch_bounds__(256) void blocks_kernel(const RmRenderParams P, con
 // the lattice's own points, so a tile holds what rm_scene_field returns there, bit for bit; a tile point beyond the lattice
 // holds the quiet NaN 0x7FF8000000000000.  A wave's points lie in a box of 9 x 9 x 2 lattice steps: its BVH candidates are
 // coherent.  Faces shared by two kept blocks are evaluated by both (729 evaluations for 512 points of a block's own).
+//
+// Option `exact` (ACCEL 3) with a tree to walk: the 729 points share a small box, so the workgroup culls the tree once.  Every
+// lane forms E at the tile's centre point c (lattice point 8 b + 4 per axis, inside the lattice or not; the same walk in every
+// lane, so the loads are broadcasts).  E is 1-Lipschitz where the tree is used -- a minimum of true distances and 10 -- so
+// U = E(c) + A.radius bounds E on the whole tile (radius: 4 (|du| + |dv| + |dw|) and the roundings' slack, as the coarse pass's
+// bound).  An object attains E at a tile point x only if its sdf(x) <= U, and sdf(x) is at least the distance from x to the
+// object's leaf box, which is at least the gap between that box and the tile's box c +- A.half: leaves whose gap is positive and
+// exceeds U, by the margins of box_beyond, are dropped, the objects of the others go to an LDS list, and each point takes list_min over it --
+// Math.min does not depend on the order, so the value is E bit for bit.  Wave 0 culls 64 consecutive nodes a step: the nodes
+// are in pre-order and a node's subtree ends at its skip link, so a dropped node rules out the nodes up to there (a prefix
+// maximum over the lanes), and the next step starts behind whatever the step ruled out.  A list of more than
+// RM_EXACT_LIST_CAP ids sends the workgroup's points through the per-lane walk.
+#define RM_EXACT_LIST_CAP 1024
 template <int ACCEL, int GEN>
-__global__ __launch_bounds__(256) void tiles_kernel(const RmRenderParams P, const RmTilesArgs A) {
+__device__ __forceinline__ void tiles_body(const RmRenderParams &P, const RmTilesArgs &A) {
     const unsigned int r = blockIdx.x;
     const unsigned int b = static_cast<unsigned int>(A.list[r]);
     const unsigned int row = b / A.nbu, bx = b - row * A.nbu, bz = row / A.nbv, by = row - bz * A.nbv;
     double *out = A.tiles + static_cast<size_t>(r) * RM_SPARSE_TILE;
+    bool from_list = false;
+    int n_list = 0;
+    const int32_t *cand = nullptr;
+#ifndef RM_EXACT_NO_LIST  // (a measurement build: every point through the per-lane walk)
+    if constexpr (ACCEL == 3 && GEN < 2) {
+        __shared__ int32_t s_list[RM_EXACT_LIST_CAP];
+        __shared__ int s_n, s_over;
+        const double fi = static_cast<double>(8u * bx + 4u), fj = static_cast<double>(8u * by + 4u), fk = static_cast<double>(8u * bz + 4u);
+        Vec3f c;
+        c.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
+        c.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
+        c.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+        // (uniform; a centre beyond the lattice's last point may overflow binary32 where the lattice's own points do not: no list then)
+        if (P.bvh_nodes > 0 && c.x - c.x == 0.f && c.y - c.y == 0.f && c.z - c.z == 0.f) {
+            uint32_t unused = 0;
+            const double U = tree_exact_distance<GEN, true>(P, P.bvh, P.bvh_nodes, P.bvh_prims, c, unused) + A.radius;
+            if (threadIdx.x == 0) {
+                s_n = 0;
+                s_over = 0;
+            }
+            __syncthreads();
+            if (threadIdx.x < 64u) {
+                const int lane = static_cast<int>(threadIdx.x);
+                const double lx = static_cast<double>(c.x) - A.half[0], hx = static_cast<double>(c.x) + A.half[0];
+                const double ly = static_cast<double>(c.y) - A.half[1], hy = static_cast<double>(c.y) + A.half[1];
+                const double lz = static_cast<double>(c.z) - A.half[2], hz = static_cast<double>(c.z) + A.half[2];
+                for (int base = 0; base < P.bvh_nodes;) {
+                    const int idx = base + lane;
+                    int cover = 0, leaf = -1;  // cover: where the subtree of a dropped node ends
+                    if (idx < P.bvh_nodes) {
+                        const RmBvhNode node = P.bvh[idx];
+                        const double ex = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[0]) - hx, lx - static_cast<double>(node.hi[0])), 0.0);
+                        const double ey = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[1]) - hy, ly - static_cast<double>(node.hi[1])), 0.0);
+                        const double ez = __builtin_fmax(__builtin_fmax(static_cast<double>(node.lo[2]) - hz, lz - static_cast<double>(node.hi[2])), 0.0);
+                        const double gap = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+                        // (a box that touches the tile's box stays: U may be negative, and inside a box so may an sdf)
+                        if (gap > 0.0 && gap * (1.0 - 0x1p-20) - 0x1p-20 > U) cover = node.skip;
+                        else leaf = node.leaf;
+                    }
+                    int ruled = cover;  // inclusive prefix maximum of cover
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const int o = __shfl_up(ruled, d);
+                        if (lane >= d) ruled = max(ruled, o);
+                    }
+                    const int before = __shfl_up(ruled, 1);
+                    const bool live = lane == 0 || idx >= before;  // not inside a subtree an earlier lane's node dropped
+                    if (live && leaf >= 0 && (leaf & 0xFF) > 0) {
+                        const int first = leaf >> 8, cnt = leaf & 0xFF;
+                        const int at = atomicAdd(&s_n, cnt);
+                        if (at + cnt <= RM_EXACT_LIST_CAP)
+                            for (int k = 0; k < cnt; ++k) s_list[at + k] = P.bvh_prims[first + k];
+                        else s_over = 1;
+                    }
+                    base = max(base + 64, __shfl(ruled, 63));
+                }
+            }
+            __syncthreads();
+            from_list = s_over == 0;
+            n_list = s_n;
+            cand = s_list;
+        }
+    }
+#endif
 #pragma unroll 1
     for (unsigned int t = threadIdx.x; t < RM_SPARSE_TILE; t += 256u) {
         const unsigned int q = t / 9u, ta = t - q * 9u, tg = q / 9u, tb = q - tg * 9u;
@@ -1488,10 +1639,19 @@ __global__ __launch_bounds__(256) void tiles_kernel(const RmRenderParams P, cons
             p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
             p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
             uint32_t c = 0;
-            d = scene_distance<ACCEL, GEN>(P, p, c);
+            if (from_list) d = list_min<GEN>(P, cand, n_list, p, RM_MAX_DIST);
+            else d = scene_distance<ACCEL, GEN>(P, p, c);
         }
         out[t] = d;
     }
+}
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void tiles_kernel(const RmRenderParams P, const RmTilesArgs A) {
+    tiles_body<ACCEL, GEN>(P, A);
+}
+template <int GEN>
+__global__ __launch_bounds__(256) void tiles_exact_kernel(const RmRenderParams P, const RmTilesArgs A) {
+    tiles_body<3, GEN>(P, A);
 }
 
 // ------------------------------------------------------------------ point queries (rm_scene_points)
@@ -1505,7 +1665,7 @@ __global__ __launch_bounds__(256) void tiles_kernel(const RmRenderParams P, cons
 // mesh or a hit buffer take about the same number of steps, and compacting them would cost a pass through memory.  A lane
 // reads its point before it writes anything, so A.position may be A.points.
 template <int ACCEL, int GEN>
-__global__ __launch_bounds__(256) void point_kernel(const RmRenderParams P, const RmPointArgs A) {
+__device__ __forceinline__ void point_body(const RmRenderParams &P, const RmPointArgs &A) {
     const int64_t i = static_cast<int64_t>(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= A.n) return;
     Vec3f p{A.points[3 * i], A.points[3 * i + 1], A.points[3 * i + 2]}, g{0.f, 0.f, 0.f};
@@ -1540,6 +1700,14 @@ __global__ __launch_bounds__(256) void point_kernel(const RmRenderParams P, cons
     if (A.steps) A.steps[i] = steps;
     if (A.count) A.count[i] = count;
     if (A.object) A.object[i] = object_at<ACCEL, GEN>(P, p, A.slot_obj);
+}
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void point_kernel(const RmRenderParams P, const RmPointArgs A) {
+    point_body<ACCEL, GEN>(P, A);
+}
+template <int GEN>
+__global__ __launch_bounds__(256) void point_exact_kernel(const RmRenderParams P, const RmPointArgs A) {
+    point_body<3, GEN>(P, A);
 }
 
 // ------------------------------------------------------------------ ray queries (rm_ray_march, rm_ray_pick)
@@ -1867,6 +2035,21 @@ V1Lds v1_lds_layout(const RmRenderParams &p, int threads, bool lists) {
 #define RM_DISPATCH_O(K, G) { if (p.algorithm == 0) RM_DISPATCH_A(K, false, G) else RM_DISPATCH_A(K, true, G) }
 #define RM_DISPATCH(K) { if (p.general == 3) RM_DISPATCH_O(K, 3) else if (p.general == 2) RM_DISPATCH_O(K, 2) else if (p.general) RM_DISPATCH_O(K, 1) else RM_DISPATCH_O(K, 0) }
 #define RM_KERNEL_NAME(kernel, A, O, G) #kernel "<" #A ", " #O ", " #G ">" RM_LEN_TAG
+// The point, field and tile launches of option `exact` (p.accel == RM_ACCEL_EXACT), with grid, block, shmem, stream and
+// kernel_name in scope: <name>_exact_kernel<GEN> for sphere and primitive records; expression programs have no tree to walk and
+// run <name>_kernel<0, GEN>, which evaluates every object.  rm_last_kernel reports "<name>_kernel<EXACT, GEN>" for all of them.
+#define RM_EXACT_ONE(label, KERNEL, G, ...)                                          \
+    {                                                                                \
+        hipLaunchKernelGGL(KERNEL, grid, block, shmem, stream, __VA_ARGS__);         \
+        if (kernel_name) *kernel_name = label "<EXACT, " #G ">" RM_LEN_TAG;          \
+    }
+#define RM_LAUNCH_EXACT(name, ...)                                                                             \
+    {                                                                                                          \
+        if (p.general == 3) RM_EXACT_ONE(#name "_kernel", (name##_kernel<0, 3>), 3, __VA_ARGS__)               \
+        else if (p.general == 2) RM_EXACT_ONE(#name "_kernel", (name##_kernel<0, 2>), 2, __VA_ARGS__)          \
+        else if (p.general) RM_EXACT_ONE(#name "_kernel", (name##_exact_kernel<1>), 1, __VA_ARGS__)            \
+        else RM_EXACT_ONE(#name "_kernel", (name##_exact_kernel<0>), 0, __VA_ARGS__)                           \
+    }
 
 hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape) {
     const int rows = p.local_rows;
@@ -2027,7 +2210,8 @@ hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFiel
         hipLaunchKernelGGL((field_kernel<A, G>), grid, block, shmem, stream, pl, al); \
         if (kernel_name) *kernel_name = "field_kernel<" #A ", " #G ">" RM_LEN_TAG;    \
     }
-        RM_DISPATCH(RM_FLDK)
+        if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(field, pl, al)
+        else RM_DISPATCH(RM_FLDK)
 #undef RM_FLDK
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
@@ -2078,7 +2262,8 @@ hipError_t RM_LEN_VARIANT(rm_launch_tiles)(const RmRenderParams &p, const RmTile
         hipLaunchKernelGGL((tiles_kernel<A, G>), grid, block, shmem, stream, pl, a);  \
         if (kernel_name) *kernel_name = "tiles_kernel<" #A ", " #G ">" RM_LEN_TAG;   \
     }
-    RM_DISPATCH(RM_TLK)
+    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(tiles, pl, a)
+    else RM_DISPATCH(RM_TLK)
 #undef RM_TLK
     return hipGetLastError();
 }
@@ -2097,7 +2282,8 @@ hipError_t RM_LEN_VARIANT(rm_launch_points)(const RmRenderParams &p, const RmPoi
         hipLaunchKernelGGL((point_kernel<A, G>), grid, block, shmem, stream, pl, a); \
         if (kernel_name) *kernel_name = "point_kernel<" #A ", " #G ">" RM_LEN_TAG;  \
     }
-    RM_DISPATCH(RM_PTK)
+    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(point, pl, a)
+    else RM_DISPATCH(RM_PTK)
 #undef RM_PTK
     return hipGetLastError();
 }

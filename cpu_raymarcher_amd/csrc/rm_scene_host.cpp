@@ -991,6 +991,47 @@ bool build_scene(HostScene &s, const float *centers, const double *radii, int n,
     return true;
 }
 
+// ---- the exact tree (option `exact`; rm_scene_host.h) -------------------------------------------
+
+int exact_tree_mode(const HostScene &s) {
+    if (s.program) return 0;
+    const size_t n = s.general ? s.prims.size() : s.spheres.size();
+    if (n == 0 || s.prim_lo.size() != 3 * n || s.prim_hi.size() != 3 * n || s.world_pos.size() != 3 * n) return 0;
+    if (s.general) {
+        if (!s.prim_filter_ok) return 0;
+        for (const RmPrim &q : s.prims)
+            if (!(q.half[0] >= 0.0f && q.half[1] >= 0.0f && q.half[2] >= 0.0f && q.a >= 0.0 && q.b >= 0.0)) return 0;
+    } else {
+        for (const double r : s.radii)
+            if (!(r >= 0.0)) return 0;
+    }
+    for (size_t i = 0; i < 3 * n; ++i)  // (what the checks above imply for finite input; an overflowed pad is caught here)
+        if (!(s.prim_lo[i] <= s.prim_hi[i]) || !std::isfinite(s.prim_lo[i]) || !std::isfinite(s.prim_hi[i])) return 0;
+    if (s.accel == 2) return s.bvh.empty() ? 0 : 1;
+    // BvhBuilder splits at the median down to depth 20: a leaf holds more than 255 objects from 255 * 2^20 objects on
+    return n > (size_t(RM_BVH_LEAF_MAX) << 20) ? 0 : 2;
+}
+
+bool build_exact_tree(const HostScene &s, ExactTree &out) {
+    out = ExactTree();
+    const int n = static_cast<int>(s.prim_lo.size() / 3);
+    HostScene t;  // BvhBuilder reads the boxes and the sort keys and writes bvh / bvh_prims: a scene of just those
+    t.prim_lo = s.prim_lo;
+    t.prim_hi = s.prim_hi;
+    t.world_pos = s.world_pos;
+    std::vector<int32_t> all(n);
+    std::iota(all.begin(), all.end(), 0);
+    std::string err;
+    BvhBuilder b{t, err};
+    b.emit(all, bounds_of(t, all.data(), n), 0);
+    if (!b.ok) return false;
+    out.nodes.swap(t.bvh);
+    out.ids.swap(t.bvh_prims);
+    out.leaves = t.bvh_leaves;
+    out.depth = t.bvh_depth;
+    return true;
+}
+
 // ---- general primitives -----------------------------------------------------------------------
 
 namespace {

@@ -181,6 +181,26 @@ bool build_scene_nodes(HostScene &s, const NodeDesc *nodes, int n_nodes, const i
 bool leaf_objects(const HostScene &s, std::vector<RmInstr> &prog, std::vector<int32_t> &obj_ranges, std::vector<ProgTreeNode> &tree,
                   std::vector<int32_t> &roots);
 
+// Option `exact` (include/rm_raymarch.h): the tree of boxes an exact query walks to find min over ALL objects of Primitive.sdf.
+// Pruning a box needs sdf >= distance to the object's padded box for every object inside, which holds when Primitive.sdf is a
+// true world-space distance to a body inside that box: sphere records, and primitive records whose transforms are all rigid
+// (prim_filter_ok), with radii and extents that are finite and not negative.  exact_tree_mode says what such a query does:
+//   0  every object is evaluated (expression forests, a non-rigid transform, a negative radius or extent, an empty scene, a
+//      scene whose own tree could not be built: a leaf of more than 255 objects)
+//   1  the scene's own BVH (s.bvh / s.bvh_prims)
+//   2  an own tree (octree and None scenes): build_exact_tree
+// The own tree is BvhBuilder's over s.prim_lo / prim_hi / world_pos -- skip-linked nodes in right-first pre-order and an id
+// list; the ids index the scene's arrays as the scene's kernels index them (object order: only BVH sphere scenes are permuted)
+// -- kept apart from the render tables of HostScene, which it does not touch.
+struct ExactTree {
+    std::vector<RmBvhNode> nodes;
+    std::vector<int32_t> ids;
+    int leaves = 0, depth = 0;
+};
+int exact_tree_mode(const HostScene &s);
+// false (and an empty tree) when BvhBuilder refuses the scene; call only for mode 2
+bool build_exact_tree(const HostScene &s, ExactTree &out);
+
 // gl-matrix mat4.scale(m, m, [x, y, z]) in place (sceneManager.ts:63: the Mandelbulb's world->local is post-scaled)
 void scale_transform(float m[16], double x, double y, double z);
 

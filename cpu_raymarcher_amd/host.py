@@ -126,39 +126,43 @@ class Scene:
         self._activate()
         return self.ctx.scene_distance(points)
 
-    def distanceField(self, origin, du, dv, dw=None, shape=(1, 1), dist32=False, count=True, device=False):
+    def distanceField(self, origin, du, dv, dw=None, shape=(1, 1), dist32=False, count=True, device=False, exact=False):
         """getDistance at every point origin + i * du + j * dv + k * dw of a lattice formed on the device, at this scene's
-        own time (Context.field) -> (dist, count) shaped [nw, nv, nu], [nv, nu] for shape = (nu, nv)."""
+        own time (Context.field) -> (dist, count) shaped [nw, nv, nu], [nv, nu] for shape = (nu, nv).  exact=True: the exact
+        field -- min over ALL objects -- whatever acceleration structure the scene has (option `exact` for this call)."""
         self._activate()
-        return self.ctx.field(origin, du, dv, dw, shape=shape, time=self.time, dist32=dist32, count=count, device=device)
+        return self.ctx.field(origin, du, dv, dw, shape=shape, time=self.time, dist32=dist32, count=count, device=device, exact=exact)
 
-    def getNormal(self, position):
-        """Raymarcher.getNormal (raymarcher.ts:123-135) at a point, at this scene's own time (Context.points): three floats."""
+    def getNormal(self, position, exact=False):
+        """Raymarcher.getNormal (raymarcher.ts:123-135) at a point, at this scene's own time (Context.points): three floats.
+        exact=True: the gradient of the exact field."""
         self._activate()
-        r = self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), object=False, time=self.time)
+        r = self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), object=False, time=self.time, exact=exact)
         return [float(x) for x in r.normal[0]]
 
-    def nearestObject(self, position):
-        """Index of the object that attains getDistance at a point (a 3D cursor), at this scene's own time; -1: none."""
+    def nearestObject(self, position, exact=False):
+        """Index of the object that attains getDistance at a point (a 3D cursor), at this scene's own time; -1: none.
+        exact=True: among ALL objects (under a BVH or an octree getDistance only sees the leaves at the point)."""
         self._activate()
-        return int(self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), normal=False, time=self.time).object[0])
+        return int(self.ctx.points(np.asarray(position, np.float32).reshape(1, 3), normal=False, time=self.time, exact=exact).object[0])
 
-    def projectToSurface(self, points, steps=4, tol=1e-4):
+    def projectToSurface(self, points, steps=4, tol=1e-4, exact=False):
         """`points` dropped onto the surface getDistance = 0 at this scene's own time (Context.project) -> (position, dist,
-        steps).  An empty octree leaf has no gradient: wants acceleration None or BVH."""
+        steps).  An empty octree leaf has no gradient and a BVH's distance over-estimates: exact=True projects along the exact field."""
         self._activate()
-        return self.ctx.project(points, steps=steps, tol=tol, time=self.time)
+        return self.ctx.project(points, steps=steps, tol=tol, time=self.time, exact=exact)
 
     def toMesh(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, device=False,
-               triangles=False, attributes=False, snap=0, tol=1e-4, sparse=False, lipschitz=1.0):
+               triangles=False, attributes=False, snap=0, tol=1e-4, sparse=False, lipschitz=1.0, exact=False):
         """The surface getDistance = iso at this scene's own time as (vertices float32 [V, 3], quads uint32 [Q, 4]) -- or
         triangles uint32 [2Q, 3] --, extracted on the device (Context.mesh): over the lattice origin + i * du + j * dv + k * dw
         of `shape` points, or, without one, over the root box in `cells` cells (Context.mesh_box).  attributes=True adds
         (normals, objects) per vertex, the vertices snapped onto the surface by up to `snap` steps (Context.mesh_field).
         sparse=True samples and meshes only the 8 x 8 x 8-cell blocks that can hold the surface when the exact field is
-        `lipschitz`-Lipschitz (Context.mesh_sparse, order "dense"): the same mesh, and lattices the dense path cannot hold."""
+        `lipschitz`-Lipschitz (Context.mesh_sparse, order "dense"): the same mesh, and lattices the dense path cannot hold.
+        exact=True meshes the exact field (offset surfaces, octree scenes), attributes included."""
         self._activate()
-        more = dict(iso=iso, time=self.time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol)
+        more = dict(iso=iso, time=self.time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact)
         if origin is None:
             return self.ctx.mesh_box(cells, margin=margin, sparse=sparse, lipschitz=lipschitz, **more)
         if sparse:

@@ -278,7 +278,8 @@ typedef struct rm_lattice {      /* 72 bytes */
  *           the same distance function the renders and the ray queries call, the primitives it counted; dist32[l] is
  *           (float)dist[l].  getDistance is taken as it is: an empty octree leaf answers minDistance * 0.99, the minimum starts
  *           at 10, a point in no BVH leaf box is measured against every primitive -- a field under a BVH or an octree is the
- *           bound the marchers walk through, not always the exact distance, and a slice of it shows where.
+ *           bound the marchers walk through, not always the exact distance, and a slice of it shows where.  Option `exact`
+ *           (below) answers the exact field E instead; count is then the evaluations made.
  * Each of dist (f64[n]), dist32 (f32[n]) and count (u32[n]) may be NULL.  RM_E_INVALID -- like every argument check ahead of
  * RM_E_NO_DEVICE and RM_E_NO_SCENE, and also when a count is 0 -- for a null lattice, a count outside 0 .. 65535,
  * reserved != 0, a non-finite origin, step or time, a non-finite binary32 component at any of the lattice's eight corner points
@@ -364,7 +365,7 @@ RM_API int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const vo
  * scratch buffer) and meshes the volume, all on the device; host buffers, synchronous: min(total, capacity) vertices and quads
  * are copied back.  The same checks without d_values and value_type (no alignment is asked of `info`), and RM_E_NO_SCENE last.
  * The scratch holds 12 bytes per point plus the outputs up to their capacities.  A field under a BVH or an octree is the
- * marchers' bound, not always the exact distance: exact offset surfaces (iso != 0) want acceleration None. */
+ * marchers' bound, not always the exact distance: exact offset surfaces (iso != 0) want option `exact` (below). */
 RM_API int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *vertices, int64_t cap_vertices,
                          uint32_t *quads, int64_t cap_quads, rm_mesh_info *info);
 
@@ -434,7 +435,8 @@ typedef struct rm_sparse_info {  /* 32 bytes */
  * blocks are evaluated once per block that touches them: 729 evaluations against 512 points of a block's own.  Ahead-of-time
  * kernels only; the knobs `filter` and `length` apply as for rm_scene_field.  RM_E_INVALID for the lattice as above, n_kept
  * outside 0 .. n_blocks, a null d_list or d_tiles with n_kept > 0, d_list not 4-byte or d_tiles not 8-byte aligned;
- * RM_E_NO_DEVICE; RM_E_NO_SCENE last.  n_kept == 0 is RM_OK.  rm_last_kernel: tiles_kernel<ACCEL, GEN>.
+ * RM_E_NO_DEVICE; RM_E_NO_SCENE last.  n_kept == 0 is RM_OK.  rm_last_kernel: tiles_kernel<ACCEL, GEN>.  With option `exact`
+ * (below) the tiles hold the exact field E -- what the coarse pass decided by -- instead, for offset surfaces and octree scenes.
  *
  * rm_mesh_tiles_device: surface nets over the tiles; it needs no scene, like rm_mesh_field_device.  One workgroup per kept
  * block, the tile staged once in LDS, two cells per lane; neighbour blocks are reached through d_slot; a cell -> vertex map
@@ -676,8 +678,9 @@ typedef struct rm_point_query {  /* 40 bytes */
  *           lowest NaN candidate when D is NaN, -1 without a match.  It is computed only when the output is non-NULL and adds
  *           nothing to count.
  * getDistance is taken as it is: an empty octree leaf answers the constant minDistance * 0.99, so G is (0, 0, 0) there and a
- * projection stops at once with steps = 0; a projection wants acceleration None or BVH.  With K = 0 and no flags, dist and
- * count are rm_scene_distance's.
+ * projection stops at once with steps = 0, and under a BVH D over-estimates inside leaf boxes: a projection, a nearest-object
+ * or a collision probe wants option `exact` (below), which puts the exact field E in D's place whatever the acceleration.  With
+ * K = 0, no flags and exact = 0, dist and count are rm_scene_distance's.
  * position, normal: f32[3n]; dist: f64[n]; object, steps: i32[n]; count: u32[n]; every output may be NULL.  RM_E_INVALID --
  * like every argument check ahead of RM_E_NO_DEVICE and RM_E_NO_SCENE -- for a null query, a non-zero reserved, unknown flag
  * bits, K outside 0 .. 16, a non-finite time, iso or snap_tol, a negative snap_tol, n < 0 or n > INT32_MAX, null points with
@@ -1117,6 +1120,11 @@ RM_API int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]);
  * size in bytes (0: none); out[6]: the workgroups of that launch a CU holds; out[7], out[8]: the bytes of scene tables the
  * launch stages in LDS, and would with cell_tab 0; out[9..11]: the table's cells, records and distinct leaf sets. */
 RM_API int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]);
+/* Option exact (below), for tests and evidence; works on a host-only context.  What the next exact query of the active scene
+ * walks -- out[0]: 0 every object, 1 the scene's BVH, 2 an exact tree of its own -- and that tree's nodes (out[1]), leaves
+ * (out[2]) and depth (out[3]); zeros in mode 0.  It builds the exact tree if it is due (and, with a device, copies it up),
+ * whatever the option says.  RM_E_NO_SCENE without a scene. */
+RM_API int rm_debug_exact_tree(rm_ctx *ctx, int32_t out[4]);
 /* Option rect_cull (below), for tests and evidence; both work on a host-only context (except for out[0]).  rot9 / origin3: a
  * camera as rm_camera_from_angles gives it; width x height: the full frame.
  * rm_debug_rect_cull -- out[0]: whether the last launch of the v2 wave loop culled its batches' leaves by screen rectangles (0
@@ -1209,8 +1217,10 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *   oct_lean 0|1  octree + sphere scene + sphere tracer: the lean kernel render_kernel_oct (march and getNormal as phases of one
  *                 loop, eight waves per SIMD, node boxes relative to the camera position from a per-camera table) instead of
  *                 render_kernel<1, false, 0> (default 1; needs recs, lut and filter on)
- * The one option that is NOT a measurement knob but part of the numeric contract:
- *   length 0|1    gl-matrix vec3.length / vec3.distance (sphere.ts:12-14, box.ts:26,33, mandelbulb.ts:46, smoothUnion.ts:45):
+ * The two options that are NOT measurement knobs but part of the numeric contract:
+ *   exact 0|1     the point, field, tile and mesh queries answer from the exact field instead of Scene.getDistance (default 0;
+ *                 "the exact field" below has the rule; every other entry ignores it)
+ *   length 0|1   gl-matrix vec3.length / vec3.distance (sphere.ts:12-14, box.ts:26,33, mandelbulb.ts:46, smoothUnion.ts:45):
  *                 0 = Math.hypot(x, y, z) (gl-matrix 3.0 - 3.4.3, default), 1 = Math.sqrt(x*x + y*y + z*z) (the form a later
  *                 3.4.x release may use).  Results differ by <= 1 ulp(f64) per distance; the active scene is
  *                 rebuilt (bounding radii of boxes and smooth unions use it too).
@@ -1218,7 +1228,43 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *                 DEFAULT follows the formula of 3.0 - 3.4.3.  Nothing in the reference tree decides between the two (no
  *                 fixture, no test): parity is unpinned on this point.  Goldens, the cross-check shim and the benchmark exist
  *                 for both modes (tests/golden/, bench.py --opt length=1), so the default is a one-line change
- *                 (rm_api.cpp: opt_length) once the pinned version's formula is known. */
+ *                 (rm_api.cpp: opt_length) once the pinned version's formula is known.
+ *
+ * The exact field (option `exact` = 1).  Scene.getDistance is the marchers' bound: an empty octree leaf answers a constant, a
+ * point inside some BVH leaf box is measured against those leaves only (an over-estimate, by any amount).  With exact = 1 the
+ * distance function D(x) in the rules of the entries below is replaced by
+ *     E(x) = min(10, min over ALL objects of Primitive.sdf(x))   at the query's time,
+ * which is what rm_scene_distance returns, bit for bit, from a context that holds the same scene uploaded with acceleration
+ * None, the same `length` option and the same time -- whatever acceleration the active scene has.  Everything else in each
+ * rule is unchanged.
+ *   rm_scene_points, rm_scene_points_device   D becomes E everywhere: the loop, the gradient G, dist and the object.  The
+ *                 object's candidates are all objects: the lowest index with sdf == E under IEEE ==, the lowest NaN candidate
+ *                 when E is NaN, -1 without a match.
+ *   rm_scene_field, rm_scene_field_device     dist and dist32 come from E.
+ *   rm_scene_tiles_device                     the tiles hold E, so rm_scene_mesh_sparse meshes E.
+ *   rm_scene_mesh                             samples E (it goes through the field launch).
+ * rm_scene_blocks_device uses the exact field with or without the option.  rm_scene_distance, rm_debug_wave_distance, every
+ * render entry, rm_ray_march / _pick / _light / _walk and rm_shade_* ignore the option: they restate the reference's marchers,
+ * which are defined on the bounded field.  With exact = 0 no entry changes a byte or a kernel name; with exact = 1
+ * rm_last_kernel names point_kernel<EXACT, GEN>, field_kernel<EXACT, GEN> or tiles_kernel<EXACT, GEN> (the device symbols
+ * are point_exact_kernel<GEN>, field_exact_kernel<GEN> and tiles_exact_kernel<GEN> for sphere and primitive records;
+ * expression programs, which evaluate every object, run the acceleration-None instantiation <0, GEN> under that name).
+ * How E is found depends on the scene (rm_debug_exact_tree reports it) and never changes its value.  Sphere and
+ * primitive-record scenes under a BVH walk the scene's BVH with the pruning of the sparse mesher's coarse pass (skip a subtree
+ * iff db * (1 - 2^-20) - 2^-20 > best: strict, so no pruned object ties the minimum) and one more condition, db > 0: inside a
+ * box an sdf may be negative, as deep as the object is large, so a box that contains the point is never skipped -- a point
+ * inside two overlapping spheres finds the deeper one.  (The coarse pass walks by the inequality alone, as it is written there.)  Octree and None scenes of such records
+ * walk an EXACT TREE of their own, built by the BVH's rule over the same padded object boxes, on the host, at the first exact
+ * query (or rm_debug_exact_tree) after the scene was made, and copied to the device once -- that one call is synchronous, also
+ * for the _device entries -- and dropped by every change of the scene (an upload, a preset switch, rm_scene_edit_spheres, the
+ * rebuild `length` triggers).  Pruning needs Primitive.sdf >= the distance to the object's padded box, which holds when the
+ * sdf is a true world-space distance: every other scene -- expression forests, a primitive with a transform that is not rigid,
+ * a negative radius or extent, an empty scene, a tree that would need a leaf of more than 255 objects -- evaluates every object.
+ * Exact tiles cull the tree once per tile into a candidate list (csrc/rm_kernels.hip, tiles_kernel); the values are E bit for bit.
+ *   count (points and field) is the number of Primitive.sdf evaluations the lane actually made: deterministic for a scene, a
+ *                 point and the options, equal between the host and the _device entries, at most (objects) x (evaluations of
+ *                 E), and exactly that product where every object is evaluated.  Its value under a tree is otherwise not part
+ *                 of the contract. */
 RM_API int rm_set_option(rm_ctx *ctx, const char *key, int64_t value);
 RM_API int rm_get_option(const rm_ctx *ctx, const char *key, int64_t *value);
 
