@@ -95,6 +95,10 @@ class rm_point_query(C.Structure):  # include/rm_raymarch.h: struct rm_point_que
 RM_POINT_NORMAL = 1
 
 
+class rm_sharp_query(C.Structure):  # include/rm_raymarch.h: struct rm_sharp_query
+    _fields_ = [("iso", C.c_double), ("rank_tol", C.c_double), ("reach", C.c_double), ("refine", C.c_int32), ("reserved", C.c_int32)]
+
+
 class rm_mesh_info(C.Structure):  # include/rm_raymarch.h: struct rm_mesh_info
     _fields_ = [("n_vertices", C.c_int64), ("n_quads", C.c_int64), ("n_holes", C.c_int64), ("reserved", C.c_int64)]
 
@@ -218,6 +222,9 @@ SIGNATURES = {
     "rm_shade_field": (C.c_int, [_VP, C.POINTER(rm_field_shade), C.c_int64, _VP, _VP]),
     "rm_mesh_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP]),
     "rm_scene_mesh": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, _VP, C.c_int64, _VP, C.c_int64, C.POINTER(rm_mesh_info)]),
+    "rm_mesh_cells_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, _VP, C.c_int64, _VP, _VP]),
+    "rm_scene_sharpen_device": (C.c_int, [_VP, C.POINTER(rm_lattice), C.POINTER(rm_sharp_query), C.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "rm_scene_sharpen": (C.c_int, [_VP, C.POINTER(rm_lattice), C.POINTER(rm_sharp_query), C.c_int64, _VP, _VP, _VP, _VP]),
     "rm_lattice_blocks": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(C.c_int32)]),
     "rm_scene_blocks_device": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP]),
     "rm_scene_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int64, _VP, _VP]),

@@ -10,6 +10,7 @@ from . import _native as N
 # what Context.points returns
 Points = collections.namedtuple("Points", "position dist normal object steps count")
 SparseBlocks = collections.namedtuple("SparseBlocks", "slot list dist n_kept dims")
+Sharp = collections.namedtuple("Sharp", "position feature count")
 
 
 def _is_torch(x):
@@ -950,7 +951,7 @@ class Context:
 
     # ---- meshes: the surface of a distance volume, extracted on the device ------------------
     def mesh_field(self, values, origin, du, dv, dw, shape, iso=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4,
-                   time=0.0):
+                   time=0.0, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
         """Surface nets over a volume the caller already holds (rm_mesh_field_device; the rule is in include/rm_raymarch.h):
         `values` is a torch CUDA tensor or a numpy array of nu * nv * nw float64 or float32 values in the lattice's order
         ([nw, nv, nu]); the surface is where they pass `iso` (inside: value < iso).  The counting call, an exact allocation
@@ -962,7 +963,10 @@ class Context:
         attributes=True returns (vertices, faces, normals float32 [V, 3], objects int32 [V]): the vertices have been put
         through rm_scene_points_device in place on the device -- the ACTIVE scene at `time`, this call's iso, K = snap
         projection steps with tolerance tol (0: the vertices as the mesher left them) -- and carry the normal and the object
-        there (`points`).  The faces do not depend on it."""
+        there (`points`).  The faces do not depend on it.
+        sharp=True moves every vertex to dual contouring's place first (`mesh_cells`, then `sharpen` with refine, rank_tol and
+        reach against the ACTIVE scene at `time`): edges and corners of the solid are kept; the faces are untouched and the
+        attribute pass runs on the sharpened vertices."""
         lat = make_lattice(origin, du, dv, dw, shape)
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
@@ -971,16 +975,7 @@ class Context:
             raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
         import torch
         dev = torch.device("cuda", self.device)
-        if _is_torch(values):
-            if not (values.is_cuda and values.is_contiguous() and values.dtype in (torch.float64, torch.float32)):
-                raise ValueError("values must be a contiguous CUDA tensor of float64 or float32")
-            self._same_device(dict(values=values))
-        else:
-            a = np.ascontiguousarray(values)
-            values = torch.from_numpy(a if a.dtype == np.float32 else a.astype(np.float64, copy=False)).to(dev)
-        if values.numel() != n:
-            raise ValueError("values must hold nu * nv * nw = %d elements" % n)
-        vt = N.RM_MESH_F32 if values.dtype == torch.float32 else N.RM_MESH_F64
+        values, vt = self._mesh_values(values, n)
         info = torch.zeros(4, dtype=torch.int64, device=dev)
         N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), None, 0, None, 0, _ptr(info),
                                                       _current_stream_ptr()))
@@ -990,6 +985,9 @@ class Context:
         if n_vertices or n_quads:
             N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), _ptr(vertices) if n_vertices else None,
                                                           n_vertices, _ptr(quads) if n_quads else None, n_quads, _ptr(info), _current_stream_ptr()))
+        if sharp and n_vertices:
+            cells = self._mesh_cells(lat, values, vt, iso, n_vertices)
+            vertices = self._sharpen_device(make_lattice(origin, du, dv, dw, shape, time), cells, iso, refine, rank_tol, reach, False, False)[0]
         u, v, w = (np.array(list(getattr(lat, k)), np.float64) for k in ("du", "dv", "dw"))
         if float(np.dot(u, np.cross(v, w))) < 0:
             quads = quads[:, [0, 3, 2, 1]].contiguous()
@@ -999,13 +997,108 @@ class Context:
             return out
         return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
 
+    def _mesh_values(self, values, n):
+        """`values` as mesh_field takes them -> (a contiguous CUDA tensor of n float64 or float32 values, its RM_MESH_* type)."""
+        import torch
+        if _is_torch(values):
+            if not (values.is_cuda and values.is_contiguous() and values.dtype in (torch.float64, torch.float32)):
+                raise ValueError("values must be a contiguous CUDA tensor of float64 or float32")
+            self._same_device(dict(values=values))
+        else:
+            a = np.ascontiguousarray(values)
+            values = torch.from_numpy(a if a.dtype == np.float32 else a.astype(np.float64, copy=False)).to(torch.device("cuda", self.device))
+        if values.numel() != n:
+            raise ValueError("values must hold nu * nv * nw = %d elements" % n)
+        return values, (N.RM_MESH_F32 if values.dtype == torch.float32 else N.RM_MESH_F64)
+
+    def _mesh_cells(self, lat, values, vt, iso, n_vertices=None):
+        """rm_mesh_cells_device on torch's current stream -> int64 CUDA tensor [V]; n_vertices None: the counting call first."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        if n_vertices is None:
+            N.check(self._h, N.lib().rm_mesh_cells_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), None, 0, _ptr(info),
+                                                          _current_stream_ptr()))
+            n_vertices = int(info.cpu()[0])
+        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev)
+        if n_vertices:
+            N.check(self._h, N.lib().rm_mesh_cells_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), _ptr(cells), n_vertices, _ptr(info),
+                                                          _current_stream_ptr()))
+        return cells
+
+    def mesh_cells(self, values, origin, du, dv, dw, shape, iso=0.0, device=False):
+        """The cell of every vertex of `mesh_field`'s mesh of the same values (rm_mesh_cells_device): int64 [V], the key
+        l = (k * nv + j) * nu + i of the cell's low corner, in vertex order -- what `sharpen` takes, and what the sparse mesher
+        returns as `cells`.  device=True returns a CUDA tensor."""
+        lat = make_lattice(origin, du, dv, dw, shape)
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        values, vt = self._mesh_values(values, lat.nu * lat.nv * lat.nw)
+        cells = self._mesh_cells(lat, values, vt, iso)
+        return cells if device else cells.cpu().numpy()
+
+    # ---- sharp meshes: vertices from Hermite data ----------------------------------------------
+    @staticmethod
+    def _sharp_query(iso, refine, rank_tol, reach):
+        q = N.rm_sharp_query()
+        q.iso, q.rank_tol, q.reach = float(iso), float(rank_tol), float(reach)
+        q.refine, q.reserved = int(refine), 0
+        return q
+
+    def _sharpen_device(self, lat, cells, iso, refine, rank_tol, reach, want_feature=True, want_count=True):
+        """rm_scene_sharpen_device on torch's current stream for the int64 CUDA tensor `cells` -> (position, feature, count)."""
+        import torch
+        n = cells.numel()
+        dev = cells.device
+        pos = torch.empty((n, 3), dtype=torch.float32, device=dev)
+        feat = torch.empty(n, dtype=torch.int32, device=dev) if want_feature else None
+        cnt = torch.empty(n, dtype=torch.int32, device=dev) if want_count else None  # (the u32 counts as an int32 tensor)
+        q = self._sharp_query(iso, refine, rank_tol, reach)
+        N.check(self._h, N.lib().rm_scene_sharpen_device(self._h, C.byref(lat), C.byref(q), n, _ptr(cells) if n else None, _ptr(pos) if n else None,
+                                                         _ptr(feat), _ptr(cnt), _current_stream_ptr()))
+        return pos, feat, cnt
+
+    def sharpen(self, cells, origin, du, dv, dw, shape, iso=0.0, time=0.0, refine=2, rank_tol=0.1, reach=1.0, device=False, exact=False):
+        """Dual contouring's vertex for the cells `cells` (int64 keys, `mesh_cells`) of a lattice (rm_scene_sharpen; the rule is
+        in include/rm_raymarch.h): the point that minimises the distance to the tangent planes of the ACTIVE scene at `time`,
+        sampled where the surface getDistance = iso crosses the cell's edges -- each crossing refined `refine` times --, solved
+        in the eigenvectors whose eigenvalue exceeds rank_tol times the largest and kept within reach times half a cell's
+        diagonal of the cell's centre.  Returns the named tuple Sharp(position float32 [n, 3], feature int32 [n]: 3 a corner, 2
+        an edge, 1 a face, 0 the mean of the crossings, -1 no active cell; count uint32 [n]: primitives evaluated).  numpy in
+        -> numpy out through the host entry (synchronous); a CUDA tensor in, or device=True, -> CUDA tensors on torch's
+        current stream (count an int32 tensor holding the u32 bits).  exact=True: against the exact field, as `points`."""
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        lat = make_lattice(origin, du, dv, dw, shape, time)
+        with self._exact(exact):
+            if _is_torch(cells) or device:
+                import torch
+                if self.device < 0:
+                    raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance path")
+                if _is_torch(cells):
+                    if not (cells.is_cuda and cells.dtype == torch.int64 and cells.is_contiguous()):
+                        raise ValueError("cells must be a contiguous int64 CUDA tensor")
+                    self._same_device(dict(cells=cells))
+                    c = cells.reshape(-1)
+                else:
+                    c = torch.from_numpy(np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)).to(torch.device("cuda", self.device))
+                return Sharp(*self._sharpen_device(lat, c, iso, refine, rank_tol, reach))
+            c = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)
+            n = len(c)
+            pos, feat, cnt = np.zeros((n, 3), np.float32), np.zeros(n, np.int32), np.zeros(n, np.uint32)
+            q = self._sharp_query(iso, refine, rank_tol, reach)
+            N.check(self._h, N.lib().rm_scene_sharpen(self._h, C.byref(lat), C.byref(q), n, _ptr(c), _ptr(pos), _ptr(feat), _ptr(cnt)))
+            return Sharp(pos, feat, cnt)
+
     def mesh(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, device=False, triangles=False, attributes=False, snap=0, tol=1e-4,
-             exact=False):
+             exact=False, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
         """The surface of the active scene over a lattice: `field` samples Scene.getDistance on the device at `time` (float64,
         once; the volume stays there) and `mesh_field` extracts the surface getDistance = iso from it.  Returns what
         mesh_field returns (attributes, snap, tol: as there).  The field under a BVH or an octree is the marchers' bound, not
         always the exact distance: an offset surface (iso != 0) wants exact=True (option `exact` for this call: the volume
-        and the attribute pass then come from the exact field)."""
+        and the attribute pass then come from the exact field).  sharp, refine, rank_tol, reach: as mesh_field."""
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
         if self.device < 0:
@@ -1013,7 +1106,7 @@ class Context:
         with self._exact(exact):
             vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
             return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
-                                   tol=tol, time=time)
+                                   tol=tol, time=time, sharp=sharp, refine=refine, rank_tol=rank_tol, reach=reach)
 
     # ---- sparse meshes: the same mesh from the 8 x 8 x 8-cell blocks near the surface ---------
     def sparse_blocks(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, dist=True):
@@ -1045,7 +1138,7 @@ class Context:
         return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
 
     def mesh_sparse(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, order="dense", device=False, triangles=False,
-                    attributes=False, snap=0, tol=1e-4, exact=False):
+                    attributes=False, snap=0, tol=1e-4, exact=False, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
         """`mesh` from the blocks near the surface only (include/rm_raymarch.h, "sparse meshes"): `sparse_blocks` keeps the
         blocks of 8 x 8 x 8 cells that can hold the surface when the exact field is `lipschitz`-Lipschitz (1 for primitives
         and their unions), rm_scene_tiles_device samples the active scene at the 729 points of each kept block and
@@ -1055,13 +1148,15 @@ class Context:
         vertices: the result is `mesh`'s, byte for byte, whenever every cell the dense volume has active lies in a kept block
         -- what `lipschitz` guarantees for an exact field.  order="tile" returns the ABI's order, by kept block.  Everything
         else as `mesh` (the winding of a left-handed lattice is flipped here too; exact=True: the tiles and the attribute
-        pass come from the exact field, which the coarse pass uses anyway)."""
+        pass come from the exact field, which the coarse pass uses anyway; sharp, refine, rank_tol, reach: as mesh_field, with
+        the cell keys the sparse mesher returns itself)."""
         if order not in ("dense", "tile"):
             raise ValueError("order is 'dense' or 'tile'")
         with self._exact(exact):
-            return self._mesh_sparse(origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol)
+            return self._mesh_sparse(origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol,
+                                     (refine, rank_tol, reach) if sharp else None)
 
-    def _mesh_sparse(self, origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol):
+    def _mesh_sparse(self, origin, du, dv, dw, shape, iso, time, lipschitz, order, device, triangles, attributes, snap, tol, sharp=None):
         blocks = self.sparse_blocks(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, dist=False)
         import torch
         lat = make_lattice(origin, du, dv, dw, shape, time)
@@ -1081,17 +1176,20 @@ class Context:
         vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
         quads = torch.empty((n_quads, 4), dtype=torch.int32, device=dev)
         dense = order == "dense"
-        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev) if dense else None
+        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev) if dense or sharp else None
         edges = torch.empty(n_quads, dtype=torch.int64, device=dev) if dense else None
         if n_vertices or n_quads:
             call(vertices, n_vertices, quads, n_quads, cells, edges)
         if dense and n_vertices:
             by_cell = torch.argsort(cells)  # (the keys are distinct)
             vertices = vertices[by_cell].contiguous()
+            cells = cells[by_cell].contiguous()
             rename = torch.empty(n_vertices, dtype=torch.int32, device=dev)
             rename[by_cell] = torch.arange(n_vertices, dtype=torch.int32, device=dev)
             if n_quads:
                 quads = rename[quads[torch.argsort(edges)].long()].contiguous()
+        if sharp and n_vertices:
+            vertices = self._sharpen_device(lat, cells, iso, *sharp, False, False)[0]
         u, v, w = (np.array(list(getattr(lat, name)), np.float64) for name in ("du", "dv", "dw"))
         if float(np.dot(u, np.cross(v, w))) < 0:
             quads = quads[:, [0, 3, 2, 1]].contiguous()
@@ -1102,11 +1200,11 @@ class Context:
         return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
 
     def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None, attributes=False, snap=0,
-                 tol=1e-4, sparse=False, lipschitz=1.0, exact=False):
+                 tol=1e-4, sparse=False, lipschitz=1.0, exact=False, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
         """`mesh` over an axis-aligned lattice of cells[0] x cells[1] x cells[2] cells that covers scene_info()'s root box
         and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
         `box` = (lo, hi) replaces the root box: a scene without a structure reports none.  sparse=True: `mesh_sparse` with
-        `lipschitz` over the same lattice (order "dense": the same mesh).  exact: as `mesh`."""
+        `lipschitz` over the same lattice (order "dense": the same mesh).  exact, sharp, refine, rank_tol, reach: as `mesh`."""
         if box is None:
             info = self.scene_info()
             box = (info["root_min"], info["root_max"])
@@ -1118,7 +1216,8 @@ class Context:
             raise ValueError("at least 5 cells per axis")
         m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
         step = (hi - lo + 2 * m) / c
-        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact)
+        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact, sharp=sharp,
+                    refine=refine, rank_tol=rank_tol, reach=reach)
         if sparse:
             more["lipschitz"] = lipschitz
         return (self.mesh_sparse if sparse else self.mesh)(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c),

@@ -1852,8 +1852,8 @@ int check_mesh(rm_ctx *ctx, const MeshCall &m, int64_t *n, bool *cells) {
 
 // The launch both entries share: `values` laid out by the lattice, outputs and info on the device, the map and the block totals
 // at their places in the reserved scratch.
-int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices,
-                void *d_quads, void *d_info, size_t o_map, size_t o_totals, hipStream_t stream) {
+RmMeshArgs mesh_args(const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices, void *d_quads,
+                     void *d_info, size_t o_map, size_t o_totals) {
     RmMeshArgs a;
     std::memset(&a, 0, sizeof a);
     for (int c = 0; c < 3; ++c) {
@@ -1877,6 +1877,12 @@ int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, co
     a.nw = static_cast<unsigned int>(m.lattice->nw);
     a.n_blocks = static_cast<unsigned int>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK);
     a.f32 = value_type == RM_MESH_F32;
+    return a;
+}
+
+int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices,
+                void *d_quads, void *d_info, size_t o_map, size_t o_totals, hipStream_t stream) {
+    const RmMeshArgs a = mesh_args(st, m, n, d_values, value_type, d_vertices, d_quads, d_info, o_map, o_totals);
     RM_HIP(ctx, rm_launch_mesh(a, stream, &ctx->last_kernel));
     return RM_OK;
 }
@@ -2108,6 +2114,62 @@ void fill_points(const rm_ctx *ctx, const rm_point_query *q, RmRenderParams &p, 
     a.snap_tol = q->snap_tol;
     a.snap_steps = q->snap_steps;
     a.want_normal = (q->flags & RM_POINT_NORMAL) ? 1 : 0;
+}
+
+// ---- sharp vertices (rm_scene_sharpen)
+
+static_assert(sizeof(rm_sharp_query) == 32, "rm_sharp_query layout");
+
+// what both forms of rm_scene_sharpen check, arguments first
+int check_sharp(rm_ctx *ctx, const rm_lattice *lat, const rm_sharp_query *q, int64_t n, const void *cells, const void *position, const void *feature,
+                const void *count) {
+    int64_t points = 0;
+    if (const char *bad = lattice_error(lat, &points)) return fail(ctx, RM_E_INVALID, bad);
+    if (!q) return fail(ctx, RM_E_INVALID, "null query");
+    if (q->reserved != 0) return fail(ctx, RM_E_INVALID, "rm_sharp_query.reserved must be 0");
+    if (q->refine < 0 || q->refine > 8) return fail(ctx, RM_E_INVALID, "refine must be in [0, 8]");
+    if (!std::isfinite(q->iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (!(q->rank_tol >= 0 && q->rank_tol <= 1)) return fail(ctx, RM_E_INVALID, "rank_tol must be in [0, 1]");
+    if (!std::isfinite(q->reach) || q->reach < 0) return fail(ctx, RM_E_INVALID, "reach must be finite and >= 0");
+    if (n < 0 || n > std::numeric_limits<int32_t>::max()) return fail(ctx, RM_E_INVALID, "vertex count out of range");
+    if (n > 0 && (!cells || !position)) return fail(ctx, RM_E_INVALID, "null cells or position");
+    if (reinterpret_cast<uintptr_t>(cells) & 7) return fail(ctx, RM_E_INVALID, "cells must be 8-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(position) | reinterpret_cast<uintptr_t>(feature) | reinterpret_cast<uintptr_t>(count)) & 3)
+        return fail(ctx, RM_E_INVALID, "position, feature and count must be 4-byte aligned");
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
+}
+
+// The parameter block and the query of rm_scene_sharpen: the active scene as rm_scene_field passes it, at the lattice's own time
+// (ctx->time is not touched).  rho, half the longest body diagonal of a cell, and the limit reach * rho in the rule's order.
+void fill_sharp(const rm_ctx *ctx, const rm_lattice *lat, const rm_sharp_query *q, RmRenderParams &p, RmSharpArgs &a) {
+    RmFieldArgs f;
+    fill_field(ctx, lat, p, f);
+    std::memset(&a, 0, sizeof a);
+    double longest = 0.0;
+    for (int c = 0; c < 3; ++c) {
+        a.origin[c] = f.origin[c];
+        a.du[c] = f.du[c];
+        a.dv[c] = f.dv[c];
+        a.dw[c] = f.dw[c];
+    }
+    for (int s = 0; s < 4; ++s) {  // (du + dv) + dw, (du + dv) - dw, (du - dv) + dw, (du - dv) - dw
+        double d[3];
+        for (int c = 0; c < 3; ++c) {
+            const double uv = s < 2 ? a.du[c] + a.dv[c] : a.du[c] - a.dv[c];
+            d[c] = s % 2 == 0 ? uv + a.dw[c] : uv - a.dw[c];
+        }
+        const double length = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        if (s == 0 || length > longest) longest = length;
+    }
+    a.iso = q->iso;
+    a.rank_tol = q->rank_tol;
+    a.limit = q->reach * (0.5 * longest);
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.refine = q->refine;
 }
 
 }  // namespace
@@ -3152,6 +3214,84 @@ int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *ver
     if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
     if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
     RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_mesh_cells_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_cells,
+                         int64_t cap_vertices, void *d_info, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    if (reinterpret_cast<uintptr_t>(d_cells) & 7) return fail(ctx, RM_E_INVALID, "cells must be 8-byte aligned");
+    const MeshCall m{lattice, true, d_values, value_type, iso, d_cells, nullptr, d_info, cap_vertices, 0};
+    int64_t n = 0;
+    bool cells = false;
+    int rc = check_mesh(ctx, m, &n, &cells);
+    if (rc) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!cells) {  // no cell, no launch: the totals are zero
+        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
+        return RM_OK;
+    }
+    Staging st{ctx};
+    const size_t o_totals = st.region(12 * mesh_blocks(n));
+    if ((rc = st.reserve_for(s))) return rc;
+    const RmMeshArgs a = mesh_args(st, m, n, d_values, value_type, nullptr, nullptr, d_info, o_totals, o_totals);  // (no map: nothing reads one)
+    RM_HIP(ctx, rm_launch_mesh_cells(a, static_cast<long long *>(d_cells), s, &ctx->last_kernel));
+    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
+    return RM_OK;
+}
+
+int rm_scene_sharpen_device(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const void *d_cells, void *d_position,
+                            void *d_feature, void *d_count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_sharp(ctx, lattice, q, n, d_cells, d_position, d_feature, d_count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmSharpArgs a;
+    fill_sharp(ctx, lattice, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    a.cells = static_cast<const long long *>(d_cells);
+    a.position = static_cast<float *>(d_position);
+    a.feature = static_cast<int32_t *>(d_feature);
+    a.count = static_cast<uint32_t *>(d_count);
+    a.n = n;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_sharp_sqrt : rm_launch_sharp)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
+    return RM_OK;
+}
+
+int rm_scene_sharpen(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const int64_t *cells, float *position,
+                     int32_t *feature, uint32_t *count) {
+    if (!ctx) return RM_E_INVALID;
+    int rc = check_sharp(ctx, lattice, q, n, cells, position, feature, count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmSharpArgs a;
+    fill_sharp(ctx, lattice, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Through the scratch buffer in chunks of at most 4 M vertices, as rm_scene_points: 8 B per vertex go up, 12 B and the optional
+    // outputs come back.
+    const int64_t chunk = n < kRayChunk ? n : kRayChunk;
+    const size_t c = static_cast<size_t>(chunk);
+    Staging st{ctx};
+    const size_t o_cells = st.region(8 * c), o_pos = st.region(12 * c), o_feat = st.region(feature ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
+    if ((rc = st.reserve())) return rc;
+    a.cells = st.at<const long long>(o_cells);
+    a.position = st.at<float>(o_pos);
+    a.feature = feature ? st.at<int32_t>(o_feat) : nullptr;
+    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        a.n = m;
+        RM_HIP(ctx, st.in(o_cells, cells + at, 8 * k));
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_sharp_sqrt : rm_launch_sharp)(p, a, ctx->stream, &ctx->last_kernel));
+        RM_HIP(ctx, st.out(position + 3 * at, o_pos, 12 * k));
+        if (feature) RM_HIP(ctx, st.out(feature + at, o_feat, 4 * k));
+        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
     return RM_OK;
 }
 

@@ -218,6 +218,22 @@ struct RmPointArgs {
     double iso, snap_tol;
     int32_t snap_steps, want_normal;
 };
+// rm_scene_sharpen (rm_kernels.hip, sharp_kernel): n vertices named by the keys of their cells, RM_SHARP_CELLS consecutive ones
+// per workgroup of 256 lanes (include/rm_raymarch.h, "sharp meshes", has the rule)
+#define RM_SHARP_CELLS 64
+#define RM_SHARP_CROSSINGS (12 * RM_SHARP_CELLS)  // what the cells of a workgroup can hold at most
+struct RmSharpArgs {
+    double origin[3], du[3], dv[3], dw[3];  // the lattice's vectors, widened
+    double iso, rank_tol;
+    double limit;             // reach * rho, formed by the host in the rule's order
+    const long long *cells;   // i64[n]
+    float *position;          // f32[3n]
+    int32_t *feature;         // i32[n], may be null
+    uint32_t *count;          // u32[n], may be null
+    long long n;
+    unsigned int nu, nv, nw;
+    int32_t refine;
+};
 // rm_shade_field_device (rm_frame_ops.hip, shade_field_kernel): n values (f64 distances or u32 counts) -> n pixels
 struct RmShadeFieldArgs {
     const void *values;
@@ -452,9 +468,17 @@ hipError_t rm_launch_field_sqrt(const RmRenderParams &p, const RmFieldArgs &a, h
 hipError_t rm_launch_points(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_points_sqrt(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
 
+// Sharp vertices (rm_scene_sharpen): sharp_kernel, one workgroup per RM_SHARP_CELLS vertices, the LDS of rm_launch_field beside
+// its own static arrays, ahead-of-time kernels only; 0 <= a.n <= INT32_MAX.
+hipError_t rm_launch_sharp(const RmRenderParams &p, const RmSharpArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_sharp_sqrt(const RmRenderParams &p, const RmSharpArgs &a, hipStream_t stream, const char **kernel_name);
+
 // Surface nets (rm_mesh.hip): count, scan and -- with a capacity above 0 -- the two emit kernels, back to back on `stream`.
 // a.map and a.totals are the caller's scratch; 1 <= a.n <= 2^30.
 hipError_t rm_launch_mesh(const RmMeshArgs &a, hipStream_t stream, const char **kernel_name);
+// rm_mesh_cells_device: the same count and scan, then the key of every active cell at its vertex number into a.cells
+// (a.vertices, a.quads and a.map are not read; a.cap_quads is 0).
+hipError_t rm_launch_mesh_cells(const RmMeshArgs &a, long long *cells, hipStream_t stream, const char **kernel_name);
 
 // The sparse mesher.  rm_launch_blocks (rm_kernels.hip): blocks_kernel<GEN, WALK> -- the exact distance at every block centre,
 // by the pruned walk of the BVH where the scene has one and is no expression program, else over all objects -- and, through

@@ -1710,6 +1710,307 @@ __global__ __launch_bounds__(256) void point_exact_kernel(const RmRenderParams P
     point_body<3, GEN>(P, A);
 }
 
+// ------------------------------------------------------------------ sharp vertices (rm_scene_sharpen)
+//
+// Dual contouring's vertex for the cells of a mesh (include/rm_raymarch.h, "sharp meshes", has the rule; tests/sharp_model.py
+// restates it): the point that minimises the distance to the tangent planes sampled at the cell's edge crossings.  A workgroup of
+// 256 lanes takes RM_SHARP_CELLS = 64 consecutive vertices -- neighbouring cells, so the BVH walks of a wave stay coherent:
+//   stage 1  the 512 corner evaluations, two per lane (a wave takes one corner of all 64 cells at a time), into LDS
+//   stage 2  wave 0 compacts the crossing edges of the 64 cells in (cell, edge) order -- at most 768 --, then all lanes take them
+//            in turn: the refinement's evaluations, the last one and the gradient's three, the point and the normal into LDS.  A
+//            cell has 3 to 7 crossings: one lane per vertex would idle half the workgroup through the longest part.
+//   stage 3  lanes 0 .. 63 accumulate their cell's records in edge order and solve: the order is fixed by the list, so the result
+//            does not depend on which lane evaluated what.
+// Counts are integers: the lanes add theirs to the cell's word in LDS.  scene_distance has one call site in the corner pass and
+// one in the loop that refines a bracket and, on its last trip, evaluates the crossing itself; the gradient is point_body's
+// distance_gradient (point_body says why the call sites are kept few).  binary64 throughout, no contraction.
+struct SharpCell {
+    unsigned int i, j, k;
+    bool exists;
+};
+__device__ __forceinline__ SharpCell sharp_locate(const RmSharpArgs &A, long long l) {
+    SharpCell c{0u, 0u, 0u, false};
+    const unsigned long long n = static_cast<unsigned long long>(A.nu) * A.nv * A.nw;
+    if (l < 0 || static_cast<unsigned long long>(l) >= n) return c;
+    const unsigned long long key = static_cast<unsigned long long>(l), row = key / A.nu, k = row / A.nv;
+    c.i = static_cast<unsigned int>(key - row * A.nu);
+    c.j = static_cast<unsigned int>(row - k * A.nv);
+    c.k = static_cast<unsigned int>(k);
+    c.exists = c.i + 1u < A.nu && c.j + 1u < A.nv && c.k + 1u < A.nw;
+    return c;
+}
+// component c of the lattice's point rule at a fractional index, before its rounding
+__device__ __forceinline__ double sharp_component(const RmSharpArgs &A, int c, double fi, double fj, double fk) {
+    return ((A.origin[c] + fi * A.du[c]) + fj * A.dv[c]) + fk * A.dw[c];
+}
+__device__ __forceinline__ bool sharp_finite(double x) { return x - x == 0.0; }
+__device__ __forceinline__ bool sharp_finite(float x) { return x - x == 0.f; }
+// one Jacobi rotation of the symmetric a and of the rows of V in the plane (p, q); r is the third index
+template <int p, int q>
+__device__ __forceinline__ void sharp_rotate(double (&a)[3][3], double (&V)[3][3]) {
+    constexpr int r = 3 - p - q;
+    const double apq = a[p][q];
+    if (apq == 0.0) return;
+    const double theta = (a[q][q] - a[p][p]) / (2.0 * apq);
+    double t = 1.0 / (__builtin_fabs(theta) + __builtin_sqrt(theta * theta + 1.0));
+    if (!(theta >= 0.0)) t = -t;
+    const double c = 1.0 / __builtin_sqrt(t * t + 1.0), s = t * c, h = t * apq;
+    a[p][p] = a[p][p] - h;
+    a[q][q] = a[q][q] + h;
+    a[p][q] = a[q][p] = 0.0;
+    const double arp = c * a[r][p] - s * a[r][q], arq = s * a[r][p] + c * a[r][q];
+    a[r][p] = a[p][r] = arp;
+    a[r][q] = a[q][r] = arq;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double vp = c * V[k][p] - s * V[k][q], vq = s * V[k][p] + c * V[k][q];
+        V[k][p] = vp;
+        V[k][q] = vq;
+    }
+}
+// eigenpair y ahead of eigenpair x when its value is strictly greater
+template <int x, int y>
+__device__ __forceinline__ void sharp_order(double (&lam)[3], double (&V)[3][3]) {
+    if (!(lam[y] > lam[x])) return;
+    const double l = lam[x];
+    lam[x] = lam[y];
+    lam[y] = l;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double v = V[k][x];
+        V[k][x] = V[k][y];
+        V[k][y] = v;
+    }
+}
+
+template <int ACCEL, int GEN>
+__device__ __forceinline__ void sharp_body(const RmRenderParams &P, const RmSharpArgs &A) {
+    __shared__ double s_val[8][RM_SHARP_CELLS];            // corner dx + 2 dy + 4 dz of every cell; NaN for a cell that does not exist
+    __shared__ float s_rec[RM_SHARP_CROSSINGS][6];         // p and n of a crossing, in list order
+    __shared__ unsigned short s_list[RM_SHARP_CROSSINGS];  // cell << 4 | edge; bit 15: dropped
+    __shared__ unsigned int s_count[RM_SHARP_CELLS], s_first[RM_SHARP_CELLS], s_mask[RM_SHARP_CELLS], s_total;
+    const unsigned int tid = threadIdx.x;
+    const long long base = static_cast<long long>(blockIdx.x) * RM_SHARP_CELLS;
+    if (tid < RM_SHARP_CELLS) s_count[tid] = 0u;
+    __syncthreads();
+
+    // stage 1: the corners
+#pragma unroll 1
+    for (unsigned int e = tid; e < 8u * RM_SHARP_CELLS; e += 256u) {
+        const unsigned int cell = e & (RM_SHARP_CELLS - 1u), corner = e / RM_SHARP_CELLS;
+        double d = __longlong_as_double(0x7FF8000000000000ll);
+        if (base + cell < A.n) {
+            const SharpCell c = sharp_locate(A, A.cells[base + cell]);
+            if (c.exists) {
+                const double fi = static_cast<double>(c.i + (corner & 1u)), fj = static_cast<double>(c.j + ((corner >> 1) & 1u)),
+                             fk = static_cast<double>(c.k + (corner >> 2));
+                const Vec3f p{static_cast<float>(sharp_component(A, 0, fi, fj, fk)), static_cast<float>(sharp_component(A, 1, fi, fj, fk)),
+                              static_cast<float>(sharp_component(A, 2, fi, fj, fk))};
+                uint32_t n = 0;
+                d = scene_distance<ACCEL, GEN>(P, p, n);
+                atomicAdd(&s_count[cell], n);
+            }
+        }
+        s_val[corner][cell] = d;
+    }
+    __syncthreads();
+
+    // stage 2: the crossing edges of the active cells, compacted in (cell, edge) order by wave 0
+    if (tid < RM_SHARP_CELLS) {
+        unsigned int inside = 0u, mask = 0u;
+        bool finite = true;
+#pragma unroll
+        for (unsigned int n = 0; n < 8u; ++n) {
+            const double v = s_val[n][tid];
+            finite = finite && sharp_finite(v);
+            inside |= (v < A.iso ? 1u : 0u) << n;
+        }
+        if (finite && inside != 0u && inside != 255u) {
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                const int lo_axis = ax == 0 ? 1 : 0, hi_axis = ax == 2 ? 1 : 2;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int low = ((e & 1) << lo_axis) | ((e >> 1) << hi_axis), high = low | (1 << ax);
+                    if (((inside >> low) ^ (inside >> high)) & 1u) mask |= 1u << (4 * ax + e);
+                }
+            }
+        }
+        const unsigned int mine = static_cast<unsigned int>(__popc(mask));
+        unsigned int upto = mine;  // inclusive prefix sum over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const unsigned int o = __shfl_up(upto, d);
+            if (static_cast<int>(tid) >= d) upto += o;
+        }
+        unsigned int at = upto - mine;
+        s_first[tid] = at;
+        s_mask[tid] = mask;
+        for (unsigned int b = 0; b < 12u; ++b)
+            if ((mask >> b) & 1u) s_list[at++] = static_cast<unsigned short>((tid << 4) | b);
+        if (tid == RM_SHARP_CELLS - 1u) s_total = upto;
+    }
+    __syncthreads();
+
+    const unsigned int total = s_total;  // <= RM_SHARP_CROSSINGS: twelve bits per cell
+#pragma unroll 1
+    for (unsigned int x = tid; x < total; x += 256u) {
+        const unsigned int entry = s_list[x], cell = entry >> 4, edge = entry & 15u, ax = edge >> 2, e = edge & 3u;
+        const SharpCell c = sharp_locate(A, A.cells[base + cell]);
+        const unsigned int lo_axis = ax == 0u ? 1u : 0u, hi_axis = ax == 2u ? 1u : 2u;
+        const unsigned int low = ((e & 1u) << lo_axis) | ((e >> 1) << hi_axis), high = low | (1u << ax);
+        const double a = s_val[low][cell], b = s_val[high][cell];
+        const double bi = static_cast<double>(c.i + (low & 1u)), bj = static_cast<double>(c.j + ((low >> 1) & 1u)),
+                     bk = static_cast<double>(c.k + (low >> 2));
+        const bool a_inside = a < A.iso;
+        double tl = 0.0, fl = a, th = 1.0, fh = b, d = 0.0;
+        Vec3f p{0.f, 0.f, 0.f}, g{0.f, 0.f, 0.f};
+        bool alive = true;
+        uint32_t n = 0;
+#pragma unroll 1
+        for (int it = 0;; ++it) {  // R refinements of the bracket, then the crossing itself
+            const double t = tl + (A.iso - fl) * (th - tl) / (fh - fl);
+            const double fi = ax == 0u ? bi + t : bi, fj = ax == 1u ? bj + t : bj, fk = ax == 2u ? bk + t : bk;
+            p = Vec3f{static_cast<float>(sharp_component(A, 0, fi, fj, fk)), static_cast<float>(sharp_component(A, 1, fi, fj, fk)),
+                      static_cast<float>(sharp_component(A, 2, fi, fj, fk))};
+            if (!(sharp_finite(t) && sharp_finite(p.x) && sharp_finite(p.y) && sharp_finite(p.z))) {
+                alive = false;
+                break;
+            }
+            const double f = scene_distance<ACCEL, GEN>(P, p, n);
+            if (it >= A.refine) {
+                d = f;
+                break;
+            }
+            if ((f < A.iso) == a_inside) {
+                tl = t;
+                fl = f;
+            } else {
+                th = t;
+                fh = f;
+            }
+        }
+        if (alive) {
+            g = distance_gradient<ACCEL, GEN>(P, p, d, n);
+            alive = sharp_finite(g.x) && sharp_finite(g.y) && sharp_finite(g.z);
+        }
+        s_rec[x][0] = p.x;
+        s_rec[x][1] = p.y;
+        s_rec[x][2] = p.z;
+        s_rec[x][3] = g.x;
+        s_rec[x][4] = g.y;
+        s_rec[x][5] = g.z;
+        if (!alive) s_list[x] = static_cast<unsigned short>(entry | 0x8000u);
+        atomicAdd(&s_count[cell], n);
+    }
+    __syncthreads();
+
+    // stage 3: one lane per vertex
+    if (tid >= RM_SHARP_CELLS || base + tid >= A.n) return;
+    const long long v = base + tid;
+    const SharpCell c = sharp_locate(A, A.cells[v]);
+    double x[3] = {0.0, 0.0, 0.0};
+    int32_t feature = -1;
+    if (c.exists) {
+        const double fi = static_cast<double>(c.i) + 0.5, fj = static_cast<double>(c.j) + 0.5, fk = static_cast<double>(c.k) + 0.5;
+        const double centre[3] = {sharp_component(A, 0, fi, fj, fk), sharp_component(A, 1, fi, fj, fk), sharp_component(A, 2, fi, fj, fk)};
+        x[0] = centre[0];
+        x[1] = centre[1];
+        x[2] = centre[2];
+        const unsigned int mask = s_mask[tid], first = s_first[tid], last = first + static_cast<unsigned int>(__popc(mask));
+        double m[3] = {0.0, 0.0, 0.0};
+        unsigned int kept = 0u;
+        if (mask) {
+            feature = 0;
+            for (unsigned int q = first; q < last; ++q) {
+                if (s_list[q] & 0x8000u) continue;
+                m[0] = m[0] + static_cast<double>(s_rec[q][0]);
+                m[1] = m[1] + static_cast<double>(s_rec[q][1]);
+                m[2] = m[2] + static_cast<double>(s_rec[q][2]);
+                ++kept;
+            }
+        }
+        if (kept) {
+            const double count = static_cast<double>(kept);
+            m[0] = m[0] / count;
+            m[1] = m[1] / count;
+            m[2] = m[2] / count;
+            double a[3][3] = {{0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}, {0.0, 0.0, 0.0}}, V[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+            double b[3] = {0.0, 0.0, 0.0};
+            for (unsigned int q = first; q < last; ++q) {
+                if (s_list[q] & 0x8000u) continue;
+                const double px = s_rec[q][0], py = s_rec[q][1], pz = s_rec[q][2], nx = s_rec[q][3], ny = s_rec[q][4], nz = s_rec[q][5];
+                a[0][0] = a[0][0] + nx * nx;
+                a[0][1] = a[0][1] + nx * ny;
+                a[0][2] = a[0][2] + nx * nz;
+                a[1][1] = a[1][1] + ny * ny;
+                a[1][2] = a[1][2] + ny * nz;
+                a[2][2] = a[2][2] + nz * nz;
+                const double s = (nx * (px - m[0]) + ny * (py - m[1])) + nz * (pz - m[2]);
+                b[0] = b[0] + nx * s;
+                b[1] = b[1] + ny * s;
+                b[2] = b[2] + nz * s;
+            }
+            a[1][0] = a[0][1];
+            a[2][0] = a[0][2];
+            a[2][1] = a[1][2];
+#pragma unroll 1
+            for (int sweep = 0; sweep < 6; ++sweep) {
+                sharp_rotate<0, 1>(a, V);
+                sharp_rotate<0, 2>(a, V);
+                sharp_rotate<1, 2>(a, V);
+            }
+            double lam[3] = {a[0][0], a[1][1], a[2][2]};
+            sharp_order<0, 1>(lam, V);
+            sharp_order<1, 2>(lam, V);
+            sharp_order<0, 1>(lam, V);
+            int r0 = 0;
+            if (lam[0] > 0.0) {
+                const double least = A.rank_tol * lam[0];
+                r0 = (lam[0] > least ? 1 : 0) + (lam[1] > least ? 1 : 0) + (lam[2] > least ? 1 : 0);
+            }
+            double coef[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) coef[i] = ((V[0][i] * b[0] + V[1][i] * b[1]) + V[2][i] * b[2]) / lam[i];
+            x[0] = m[0];
+            x[1] = m[1];
+            x[2] = m[2];
+#pragma unroll
+            for (int r = 3; r >= 1; --r) {
+                if (feature != 0 || r0 < r) continue;
+                double cand[3];
+#pragma unroll
+                for (int k = 0; k < 3; ++k) {
+                    double acc = m[k];
+#pragma unroll
+                    for (int i = 0; i < r; ++i) acc = acc + V[k][i] * coef[i];
+                    cand[k] = acc;
+                }
+                const double dx = cand[0] - centre[0], dy = cand[1] - centre[1], dz = cand[2] - centre[2];
+                if (__builtin_sqrt((dx * dx + dy * dy) + dz * dz) <= A.limit) {
+                    x[0] = cand[0];
+                    x[1] = cand[1];
+                    x[2] = cand[2];
+                    feature = r;
+                }
+            }
+        }
+    }
+    A.position[3 * v] = static_cast<float>(x[0]);
+    A.position[3 * v + 1] = static_cast<float>(x[1]);
+    A.position[3 * v + 2] = static_cast<float>(x[2]);
+    if (A.feature) A.feature[v] = feature;
+    if (A.count) A.count[v] = s_count[tid];
+}
+template <int ACCEL, int GEN>
+__global__ __launch_bounds__(256) void sharp_kernel(const RmRenderParams P, const RmSharpArgs A) {
+    sharp_body<ACCEL, GEN>(P, A);
+}
+template <int GEN>
+__global__ __launch_bounds__(256) void sharp_kernel_exact(const RmRenderParams P, const RmSharpArgs A) {
+    sharp_body<3, GEN>(P, A);
+}
+
 // ------------------------------------------------------------------ ray queries (rm_ray_march, rm_ray_pick)
 
 // Raymarcher.rayMarch (+ getNormal) for caller-supplied rays: one ray per lane, in input order.  The march is render_body's
@@ -2285,6 +2586,31 @@ hipError_t RM_LEN_VARIANT(rm_launch_points)(const RmRenderParams &p, const RmPoi
     if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(point, pl, a)
     else RM_DISPATCH(RM_PTK)
 #undef RM_PTK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_sharp)(const RmRenderParams &p, const RmSharpArgs &a, hipStream_t stream, const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n <= 0) return hipSuccess;
+    if (a.refine < 0 || a.refine > 8) return hipErrorInvalidValue;
+    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
+    RmRenderParams pl = p;
+    pl.rtc_function = nullptr;
+    pl.diag_block = nullptr;
+    pl.diag_out = nullptr;
+    const dim3 grid(static_cast<unsigned>((a.n + RM_SHARP_CELLS - 1) / RM_SHARP_CELLS)), block(256);  // (a.n <= INT32_MAX: one grid dimension)
+#define RM_SHK(A, O, G)                                                             \
+    {                                                                               \
+        hipLaunchKernelGGL((sharp_kernel<A, G>), grid, block, shmem, stream, pl, a); \
+        if (kernel_name) *kernel_name = "sharp_kernel<" #A ", " #G ">" RM_LEN_TAG;  \
+    }
+    if (p.accel == RM_ACCEL_EXACT) {  // RM_LAUNCH_EXACT's choice, with this family's kernel names
+        if (p.general == 3) RM_EXACT_ONE("sharp_kernel", (sharp_kernel<0, 3>), 3, pl, a)
+        else if (p.general == 2) RM_EXACT_ONE("sharp_kernel", (sharp_kernel<0, 2>), 2, pl, a)
+        else if (p.general) RM_EXACT_ONE("sharp_kernel", (sharp_kernel_exact<1>), 1, pl, a)
+        else RM_EXACT_ONE("sharp_kernel", (sharp_kernel_exact<0>), 0, pl, a)
+    } else RM_DISPATCH(RM_SHK)
+#undef RM_SHK
     return hipGetLastError();
 }
 

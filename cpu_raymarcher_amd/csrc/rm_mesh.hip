@@ -146,6 +146,28 @@ __global__ __launch_bounds__(kBlock) void mesh_quad_kernel(RmMeshArgs a) {
     }
 }
 
+// rm_mesh_cells_device: mesh_vertex_kernel's flags and ranks, the cell's key l where that kernel writes the position
+template <typename T>
+__global__ __launch_bounds__(kBlock) void cell_keys_kernel(RmMeshArgs a, long long *cells) {
+    __shared__ unsigned s_sums[kWaves];
+    const unsigned l = blockIdx.x * kBlock + threadIdx.x;
+    double v[8];
+    const Cell c = load_cell<T, 0xFFu>(a, l, v);
+    const bool act[1] = {c.active()};
+    unsigned total;
+    const unsigned r = a.totals[blockIdx.x] + block_rank<1>(act, s_sums, &total);
+    if (act[0] && static_cast<long long>(r) < a.cap_vertices) cells[r] = static_cast<long long>(l);
+}
+
+template <typename T>
+hipError_t launch_cells(const RmMeshArgs &a, long long *cells, hipStream_t stream) {
+    const dim3 grid(a.n_blocks), block(kBlock);
+    hipLaunchKernelGGL(mesh_count_kernel<T>, grid, block, 0, stream, a);
+    hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(kScan), 0, stream, a.totals, a.n_blocks, a.info);
+    if (a.cap_vertices > 0) hipLaunchKernelGGL(cell_keys_kernel<T>, grid, block, 0, stream, a, cells);
+    return hipGetLastError();
+}
+
 template <typename T>
 hipError_t launch(const RmMeshArgs &a, hipStream_t stream) {
     const dim3 grid(a.n_blocks), block(kBlock);
@@ -162,4 +184,11 @@ hipError_t rm_launch_mesh(const RmMeshArgs &a, hipStream_t stream, const char **
     if (a.n <= 0 || a.n > (1ll << 30) || a.n_blocks != static_cast<unsigned>((a.n + kBlock - 1) / kBlock)) return hipErrorInvalidValue;
     if (kernel_name) *kernel_name = a.f32 ? "mesh_count_kernel<float>" : "mesh_count_kernel<double>";
     return a.f32 ? launch<float>(a, stream) : launch<double>(a, stream);
+}
+
+hipError_t rm_launch_mesh_cells(const RmMeshArgs &a, long long *cells, hipStream_t stream, const char **kernel_name) {
+    if (a.n <= 0 || a.n > (1ll << 30) || a.n_blocks != static_cast<unsigned>((a.n + kBlock - 1) / kBlock)) return hipErrorInvalidValue;
+    if (a.cap_vertices > 0 && !cells) return hipErrorInvalidValue;
+    if (kernel_name) *kernel_name = a.f32 ? "mesh_count_kernel<float>" : "mesh_count_kernel<double>";
+    return a.f32 ? launch_cells<float>(a, cells, stream) : launch_cells<double>(a, cells, stream);
 }

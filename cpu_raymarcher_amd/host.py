@@ -153,16 +153,19 @@ class Scene:
         return self.ctx.project(points, steps=steps, tol=tol, time=self.time, exact=exact)
 
     def toMesh(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, device=False,
-               triangles=False, attributes=False, snap=0, tol=1e-4, sparse=False, lipschitz=1.0, exact=False):
+               triangles=False, attributes=False, snap=0, tol=1e-4, sparse=False, lipschitz=1.0, exact=False, sharp=False, refine=2,
+               rank_tol=0.1, reach=1.0):
         """The surface getDistance = iso at this scene's own time as (vertices float32 [V, 3], quads uint32 [Q, 4]) -- or
         triangles uint32 [2Q, 3] --, extracted on the device (Context.mesh): over the lattice origin + i * du + j * dv + k * dw
         of `shape` points, or, without one, over the root box in `cells` cells (Context.mesh_box).  attributes=True adds
         (normals, objects) per vertex, the vertices snapped onto the surface by up to `snap` steps (Context.mesh_field).
         sparse=True samples and meshes only the 8 x 8 x 8-cell blocks that can hold the surface when the exact field is
         `lipschitz`-Lipschitz (Context.mesh_sparse, order "dense"): the same mesh, and lattices the dense path cannot hold.
-        exact=True meshes the exact field (offset surfaces, octree scenes), attributes included."""
+        exact=True meshes the exact field (offset surfaces, octree scenes), attributes included.  sharp=True keeps edges and
+        corners: the vertices are dual contouring's (Context.sharpen with refine, rank_tol and reach), the faces the same."""
         self._activate()
-        more = dict(iso=iso, time=self.time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact)
+        more = dict(iso=iso, time=self.time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact, sharp=sharp,
+                    refine=refine, rank_tol=rank_tol, reach=reach)
         if origin is None:
             return self.ctx.mesh_box(cells, margin=margin, sparse=sparse, lipschitz=lipschitz, **more)
         if sparse:

@@ -465,6 +465,81 @@ RM_API int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double i
                                 uint32_t *quads, int64_t cap_quads, int64_t *cells, int64_t *edges, rm_mesh_info *info,
                                 rm_sparse_info *sparse_info);
 
+/* ---- sharp meshes: vertices from Hermite data (dual contouring's vertex rule) --------------------------------- */
+
+typedef struct rm_sharp_query {  /* 32 bytes */
+    double  iso;        /* the surface is D == iso; finite */
+    double  rank_tol;   /* an eigenvalue counts when it exceeds rank_tol * the largest; in [0, 1] */
+    double  reach;      /* a vertex may lie up to reach * rho from its cell's centre; finite, >= 0 */
+    int32_t refine;     /* R, 0 .. 8: refinements of each crossing's bracket */
+    int32_t reserved;   /* 0 */
+} rm_sharp_query;
+
+/* Surface nets place a vertex at the mean of its cell's edge crossings, which cannot represent a crease: every edge of a box
+ * comes out chamfered and every corner cut off by about half a cell, and the snap of rm_scene_points moves a vertex onto ONE
+ * face, not onto the line where two meet.  This pass keeps the topology -- one vertex per active cell, the quads untouched --
+ * and moves each vertex to the point that minimises the distance to the tangent planes sampled at its cell's edge crossings (the
+ * Hermite data), as dual contouring does.  The rule, operation for operation (tests/sharp_model.py restates it; results are
+ * equal byte for byte).  All arithmetic is binary64, one operation at a time, no contraction, in the stated order.
+ *   input     an rm_lattice (as rm_scene_field takes and checks it), the key l = (k * nv + j) * nu + i of the vertex's cell (what
+ *             rm_mesh_cells_device and the sparse mesher's `cells` return) and the query.  D is Scene.getDistance with
+ *             Scene.updateTime(lattice->time), exactly as rm_scene_distance returns it -- with option `exact` the exact field E,
+ *             as for the point queries; the primitive count of every evaluation made is added to count.
+ *   corners   the eight corner values are D at the lattice's own points (i + dx, j + dy, k + dz); inside and active follow
+ *             rm_mesh_field_device's rule (a hole is not active).  A key that names no cell (l < 0, l >= nu * nv * nw, or an
+ *             index at the last point of its axis): position (0, 0, 0), feature -1, count 0, nothing is evaluated.  A cell that
+ *             is not active: position = the lattice's point rule at index (i + 0.5, j + 0.5, k + 0.5), feature -1, count = the
+ *             corners' counts, nothing more is evaluated.
+ *   crossings the twelve edges in the surface-nets order, a and b the values at an edge's low and high end.  When exactly one end
+ *             is inside: start the bracket at (tl, fl, th, fh) = (0, a, 1, b) and repeat R times
+ *                 t = tl + (iso - fl) * (th - tl) / (fh - fl)                  (product, quotient, sum)
+ *                 f = D(P(t))         P(t): the point rule with index (double)index + t on the edge's axis, one rounding
+ *                 if (f < iso) == (a < iso): (tl, fl) = (t, f)   else: (th, fh) = (t, f)
+ *             then form t once more from the final bracket: p = P(t), d = D(p), n = G(p, d), G exactly rm_scene_points' G, its
+ *             three evaluations counted.  A t or a component of P(t) that is not finite drops the crossing at once, before
+ *             anything is evaluated there; a non-finite component of n drops it too.
+ *   quadric   over the kept crossings in edge order, p and n widened: m = (sum of p) / (double)kept per component;
+ *             A = sum of n n^T as six sums a00, a01, a02, a11, a12, a22; b = sum of n * s with
+ *             s = (n.x * (p.x - m.x) + n.y * (p.y - m.y)) + n.z * (p.z - m.z).  No kept crossing: position as for a cell that is
+ *             not active, feature 0.
+ *   eigen     six cyclic Jacobi sweeps over (p, q) = (0, 1), (0, 2), (1, 2), V = I at the start.  a[p][q] == 0 skips the
+ *             rotation; else theta = (aqq - app) / (2 * apq); t = 1 / (|theta| + sqrt(theta * theta + 1)), negated unless
+ *             theta >= 0; c = 1 / sqrt(t * t + 1); s = t * c; h = t * apq; app = app - h; aqq = aqq + h; apq = 0; with r the
+ *             third index (arp, arq) = (c * arp - s * arq, s * arp + c * arq), kept symmetric; every row k of V likewise:
+ *             (V[k][p], V[k][q]) = (c * V[k][p] - s * V[k][q], s * V[k][p] + c * V[k][q]).  Eigenvalue i is a[i][i], its vector
+ *             column i of V.  The pairs are put in descending order by compare-and-swap on positions (0, 1), (1, 2), (0, 1),
+ *             swapping only when the later value is strictly greater: on ties the lower index comes first.
+ *   rank      lmax is the first eigenvalue; r0 = the number of eigenvalues > rank_tol * lmax, 0 unless lmax > 0.  c is the
+ *             unrounded binary64 cell centre (index + 0.5); rho is half the longest of |(du + dv) + dw|, |(du + dv) - dw|,
+ *             |(du - dv) + dw|, |(du - dv) - dw|, each norm sqrt((x * x + y * y) + z * z); limit = reach * rho.  With
+ *             k_i = ((v_i.x * b.x + v_i.y * b.y) + v_i.z * b.z) / lambda_i, for r = r0 down to 1:
+ *             x = ((m + v_0 * k_0) + v_1 * k_1) + v_2 * k_2 per component, the first r terms only; x is accepted when
+ *             sqrt((dx * dx + dy * dy) + dz * dz) <= limit for (dx, dy, dz) = x - c.  None accepted: x = m, r = 0.
+ *   outputs   position = f32(x); feature = r: 1 a face, 2 an edge, 3 a corner, 0 the mean of the crossings; count exact u32.
+ * Known limit: a cell that an edge of the solid clips without crossing one of the cell's own lattice edges sees one face
+ * only (rank 1) and stays where that face puts it; that is inherent to the method.  About R + 4 evaluations per crossing and
+ * 8 per cell: some 32 per vertex with R = 2.
+ *
+ * rm_mesh_cells_device: the key of every vertex of rm_mesh_field_device's mesh of the same values, d_cells int64[cap_vertices],
+ * by the same count and scan (three kernels).  Checks, the counting call (capacity 0, null buffer) and the truncation protocol
+ * are rm_mesh_field_device's, with d_cells 8-byte aligned; d_info receives the same rm_mesh_info.
+ *
+ * rm_scene_sharpen_device: n vertices, one launch, asynchronous on `stream`.  d_cells int64[n], d_position f32[3n], d_feature
+ * i32[n] or NULL, d_count u32[n] or NULL.  RM_E_INVALID -- ahead of RM_E_NO_DEVICE and RM_E_NO_SCENE -- for a lattice
+ * rm_scene_field refuses, a null query, a non-zero reserved, R outside 0 .. 8, a non-finite iso, a rank_tol outside [0, 1], a
+ * reach that is not finite or < 0, n < 0 or n > INT32_MAX, null cells or position with n > 0, cells not 8-byte or another
+ * buffer not 4-byte aligned.  n == 0 is RM_OK.  Keys may repeat and come in any order; consecutive keys of neighbouring cells
+ * keep a workgroup's tree walks coherent.  Not a render entry: it neither consumes nor fires rm_render_attach_diagnostics and
+ * leaves rm_scene_set_time's value alone; knobs apply as for rm_scene_field (`filter`, `length`, `exact`); ahead-of-time
+ * kernels only.  rm_last_kernel names the sharp_kernel<ACCEL, GEN> instantiation.
+ * rm_scene_sharpen: host buffers, synchronous, chunked through the context's scratch buffer by 4 M vertices. */
+RM_API int rm_mesh_cells_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso,
+                                void *d_cells, int64_t cap_vertices, void *d_info, void *stream);
+RM_API int rm_scene_sharpen_device(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const void *d_cells,
+                                   void *d_position, void *d_feature, void *d_count, void *stream);
+RM_API int rm_scene_sharpen(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const int64_t *cells,
+                            float *position, int32_t *feature, uint32_t *count);
+
 /* ---- ray queries ------------------------------------------------------------------ */
 
 typedef struct rm_ray_query {
