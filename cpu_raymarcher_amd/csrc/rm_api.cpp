@@ -1109,6 +1109,18 @@ void fill_scene_view(const rm_ctx *ctx, RmRenderParams &p) {
     p.use_ext = (ctx->opt_ext && ctx->host.accel == RM_ACCEL_BVH && !ctx->host.ext_cells.empty() && ctx->host.ext_dim[0] > 0) ? 1 : 0;
 }
 
+// The parameter block of a query without a ray (rm_scene_distance, and the field, point, sharp-vertex, block and tile launches):
+// the active scene at `time` -- ctx->time is not touched --, the ahead-of-time kernels (rm_scene_distance alone names its
+// specialised kernel afterwards).
+void fill_scene_query(const rm_ctx *ctx, double time, RmRenderParams &p) {
+    std::memset(&p, 0, sizeof p);
+    fill_scene_view(ctx, p);
+    p.time = time;
+    p.filter = static_cast<int32_t>(ctx->opt_filter);
+    p.tile_w = 8;
+    p.rtc_function = nullptr;
+}
+
 // Option `exact`: what the next exact query of the active scene walks (rmh::exact_tree_mode), decided -- and, for an own tree,
 // built on the host and copied up, synchronously -- once per scene; free_device_scene drops it with the scene.  A tree that
 // cannot be built or uploaded leaves mode 0 (every object), which answers the same values.
@@ -1207,6 +1219,60 @@ struct Staging {
         return hipEventRecord(ctx->scratch_busy, user);
     }
 };
+
+// One buffer of a call that has a device form and a host form (staged_call): the caller's pointer -- device or host by the form;
+// null: not asked for, no staging bytes and a null kernel pointer --, its bytes per element, where the kernel's argument block
+// takes its pointer, and which way the host form copies it.  over >= 0: the column has no region of its own, the kernel writes
+// it over the staged column of that index, which is always asked for (rm_scene_points: the positions over the points; the
+// kernel reads an element before it writes it).
+struct Column {
+    const void *ptr;
+    size_t bytes;
+    void *slot;      // the pointer member of the argument block that this column feeds
+    bool in, out;    // host form: the caller's content goes in ahead of the launch / comes back behind it
+    int over = -1;
+};
+constexpr int kMaxColumns = 10;
+// What a host form takes through the scratch at a time unless its records are large: 4 M elements -- 208 MB with a march's
+// columns, 224 MB a pick's, 272 MB a light's, 288 MB of walk summaries, 192 MB of a point query's, 64 MB of a field's.
+constexpr int64_t kHostChunk = int64_t(1) << 22;
+
+// Both forms of a query over n > 0 elements, behind its checks.  launch(first, m, stream) enqueues the kernel for elements
+// [first, first + m) with every column's pointer fed and indexed from `first`.  host false: the columns are the caller's device
+// buffers, one launch of all n on `stream`.  host true: through the scratch buffer on the context's stream in chunks of at most
+// `limit` elements, whole rows of `row` (a row at least; n is a multiple of row), synchronous; only the columns asked for are
+// staged and copied.  Nothing here depends on the query.
+template <typename Launch>
+int staged_call(rm_ctx *ctx, bool host, hipStream_t stream, int64_t n, int64_t row, int64_t limit, const Column *cols, int n_cols, Launch launch) {
+    const auto feed = [](const Column &col, const void *ptr) { std::memcpy(col.slot, &ptr, sizeof ptr); };
+    if (!host) {
+        for (int j = 0; j < n_cols; ++j) feed(cols[j], cols[j].ptr);
+        RM_HIP(ctx, launch(int64_t(0), n, stream));
+        return RM_OK;
+    }
+    const int64_t chunk = std::min(n, std::max<int64_t>(1, limit / row) * row);
+    Staging st{ctx};
+    size_t o_col[kMaxColumns];
+    for (int j = 0; j < n_cols; ++j)
+        o_col[j] = cols[j].over >= 0 ? o_col[cols[j].over] : st.region(cols[j].ptr ? cols[j].bytes * static_cast<size_t>(chunk) : 0);
+    if (const int rc = st.reserve()) return rc;
+    for (int j = 0; j < n_cols; ++j) feed(cols[j], cols[j].ptr ? st.at<char>(o_col[j]) : nullptr);
+    for (int64_t s = 0; s < n; s += chunk) {
+        const int64_t m = n - s < chunk ? n - s : chunk;
+        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
+        for (int j = 0; j < n_cols; ++j) {
+            const Column &col = cols[j];
+            if (col.ptr && col.in) RM_HIP(ctx, st.in(o_col[j], static_cast<const char *>(col.ptr) + at * col.bytes, col.bytes * k));
+        }
+        RM_HIP(ctx, launch(s, m, ctx->stream));
+        for (int j = 0; j < n_cols; ++j) {
+            const Column &col = cols[j];
+            if (col.ptr && col.out) RM_HIP(ctx, st.out(static_cast<char *>(const_cast<void *>(col.ptr)) + at * col.bytes, o_col[j], col.bytes * k));
+        }
+        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
+    }
+    return RM_OK;
+}
 
 // Why a launch of the active scene with this camera and frame would not cull by leaf rectangles (option `rect_cull`): 0 it would,
 // 1 the options (`rect_cull`, `cull`) or the scene's kind (no BVH, or a tree the cull does not serve), 2 more leaves than
@@ -1408,32 +1474,26 @@ int check_query(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origi
     return RM_OK;
 }
 
-// One call of a ray query as data: what its family contributes to ray_call.  `args` is the kernel's argument block with the
-// non-pointer fields filled, `launch` the family's launcher by option `length`, `chunk` the most rays the host form takes
-// through the scratch buffer at a time, `cols` its n_cols buffers beside the rays.  A column that was not asked for (null) gets
-// no staging bytes and a null kernel pointer.
-struct RayColumn {
-    void *ptr;      // the caller's buffer: device (the _device form) or host
-    size_t bytes;   // per ray
-    size_t member;  // offsetof the pointer it feeds in the argument block
-    bool in;        // host form: the caller's content goes in ahead of the launch
-};
-constexpr int kRayMaxColumns = 8;
+// One call of a ray query as data.  ray_call owns it and names the rays as its first two columns; the family's describer fills
+// the rest in place (so a column can point at the member it feeds): `args`, the kernel's argument block, with the non-pointer
+// fields, `launch` the family's launcher by option `length`, `chunk` the most rays the host form takes through the scratch
+// buffer at a time, and a column per buffer beside the rays (at most kMaxColumns - 2) -- every one comes back, and the
+// caller's content goes in first where `in` is set.
 template <typename Args>
 struct RayCall {
+    RmRays rays;
     Args args;
     hipError_t (*launch[2])(const RmRenderParams &, const RmRays &, const Args &, hipStream_t, const char **);
     int64_t chunk;
     int n_cols;
-    RayColumn cols[kRayMaxColumns];
+    Column cols[kMaxColumns];
+    void column(const void *ptr, size_t bytes, void *slot, bool in, bool out = true) { cols[n_cols++] = Column{ptr, bytes, slot, in, out}; }
 };
-constexpr int64_t kRayChunk = int64_t(1) << 22;  // 4 M rays: 208 MB with a march's columns, 224 MB a pick's, 272 MB a light's, 288 MB of walk summaries
 
 // Both forms of every ray query.  `check` makes the family's own checks, ahead of check_query like every argument check ahead of
-// the device check; `describe` returns the family's RayCall once the arguments have passed.  host false: the rays and columns
-// are the caller's device buffers, one launch on `stream`.  host true: finite rays only, through the scratch buffer on the
-// context's stream in chunks of at most `chunk` rays, synchronous.  Nothing here depends on the family.
-template <typename Check, typename Describe>
+// the device check; `describe` fills the family's RayCall once the arguments have passed.  The two forms are staged_call's,
+// with the rays as two input columns; the host form takes finite rays only.  Nothing here depends on the family.
+template <typename Args, typename Check, typename Describe>
 int ray_call(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins, const void *dirs, bool host, void *stream, Check check,
              Describe describe) {
     if (!ctx) return RM_E_INVALID;
@@ -1448,51 +1508,32 @@ int ray_call(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *origins,
     rc = fill_query_params(ctx, q, p);
     if (rc) return rc;
     RM_HIP(ctx, hipSetDevice(ctx->device));
-    auto c = describe();
+    RayCall<Args> c{};
+    c.column(origins, 12, &c.rays.origins, true, false);
+    c.column(dirs, 12, &c.rays.dirs, true, false);
+    describe(c);
     const auto launch = c.launch[ctx->opt_length ? 1 : 0];
-    const auto feed = [&c](const RayColumn &col, void *ptr) { std::memcpy(reinterpret_cast<char *>(&c.args) + col.member, &ptr, sizeof ptr); };
-    if (!host) {
-        for (int j = 0; j < c.n_cols; ++j) feed(c.cols[j], c.cols[j].ptr);
-        RM_HIP(ctx, launch(p, RmRays{origins_xyz, dirs_xyz, n}, c.args, static_cast<hipStream_t>(stream), &ctx->last_kernel));
-        return RM_OK;
-    }
-    const int64_t chunk = n < c.chunk ? n : c.chunk;
-    Staging st{ctx};
-    const size_t o_org = st.region(12 * static_cast<size_t>(chunk)), o_dirs = st.region(12 * static_cast<size_t>(chunk));
-    size_t o_col[kRayMaxColumns];
-    for (int j = 0; j < c.n_cols; ++j) o_col[j] = st.region(c.cols[j].ptr ? c.cols[j].bytes * static_cast<size_t>(chunk) : 0);
-    if ((rc = st.reserve())) return rc;
-    for (int j = 0; j < c.n_cols; ++j) feed(c.cols[j], c.cols[j].ptr ? st.at<char>(o_col[j]) : nullptr);
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        RM_HIP(ctx, st.in(o_org, origins_xyz + 3 * at, 12 * k));
-        RM_HIP(ctx, st.in(o_dirs, dirs_xyz + 3 * at, 12 * k));
-        for (int j = 0; j < c.n_cols; ++j) {
-            const RayColumn &col = c.cols[j];
-            if (col.ptr && col.in) RM_HIP(ctx, st.in(o_col[j], static_cast<char *>(col.ptr) + at * col.bytes, col.bytes * k));
-        }
-        RM_HIP(ctx, launch(p, RmRays{st.at<const float>(o_org), st.at<const float>(o_dirs), m}, c.args, ctx->stream, &ctx->last_kernel));
-        for (int j = 0; j < c.n_cols; ++j) {
-            const RayColumn &col = c.cols[j];
-            if (col.ptr) RM_HIP(ctx, st.out(static_cast<char *>(col.ptr) + at * col.bytes, o_col[j], col.bytes * k));
-        }
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n, 1, c.chunk, c.cols, c.n_cols, [&](int64_t, int64_t m, hipStream_t s) {
+        c.rays.n = m;
+        return launch(p, c.rays, c.args, s, &ctx->last_kernel);
+    });
 }
 
 int no_check() { return RM_OK; }  // rm_ray_march and rm_ray_pick have no checks of their own
 
 // rm_ray_march (pick false: cast_kernel, no object column) and rm_ray_pick (pick true: pick_kernel)
-RayCall<RmQueryArgs> query_call(const rm_ctx *ctx, const rm_ray_query *q, bool pick, void *t, void *iters, void *sdf_calls, void *normal, void *object) {
-    RayCall<RmQueryArgs> c{{}, {pick ? rm_launch_pick : rm_launch_cast, pick ? rm_launch_pick_sqrt : rm_launch_cast_sqrt}, kRayChunk, pick ? 5 : 4,
-                           {{t, 8, offsetof(RmQueryArgs, t), false}, {iters, 4, offsetof(RmQueryArgs, iters), false},
-                            {sdf_calls, 4, offsetof(RmQueryArgs, sdf), false}, {normal, 12, offsetof(RmQueryArgs, normal), false},
-                            {object, 4, offsetof(RmQueryArgs, object), false}}};
+void query_call(RayCall<RmQueryArgs> &c, const rm_ctx *ctx, const rm_ray_query *q, bool pick, void *t, void *iters, void *sdf_calls, void *normal,
+                void *object) {
+    c.launch[0] = pick ? rm_launch_pick : rm_launch_cast;
+    c.launch[1] = pick ? rm_launch_pick_sqrt : rm_launch_cast_sqrt;
+    c.chunk = kHostChunk;
+    c.column(t, 8, &c.args.t, false);
+    c.column(iters, 4, &c.args.iters, false);
+    c.column(sdf_calls, 4, &c.args.sdf, false);
+    c.column(normal, 12, &c.args.normal, false);
+    if (pick) c.column(object, 4, &c.args.object, false);
     c.args.want_normal = q->normal != 0;
     c.args.slot_obj = ctx->dev.slot_object;
-    return c;
 }
 
 // what both forms of rm_ray_light check: the light
@@ -1508,19 +1549,24 @@ int check_light(rm_ctx *ctx, const rm_light *light) {
     return RM_OK;
 }
 
-RayCall<RmLightArgs> light_call(const rm_light *light, void *t, void *iters, void *sdf_calls, void *normal, void *lit, void *ao, void *iters2,
-                                void *sdf_calls2) {
-    RayCall<RmLightArgs> c{{}, {rm_launch_light, rm_launch_light_sqrt}, kRayChunk, 8,
-                           {{t, 8, offsetof(RmLightArgs, t), false}, {iters, 4, offsetof(RmLightArgs, iters), false},
-                            {sdf_calls, 4, offsetof(RmLightArgs, sdf), false}, {normal, 12, offsetof(RmLightArgs, normal), false},
-                            {lit, 4, offsetof(RmLightArgs, lit), false}, {ao, 4, offsetof(RmLightArgs, ao), false},
-                            {iters2, 4, offsetof(RmLightArgs, iters2), false}, {sdf_calls2, 4, offsetof(RmLightArgs, sdf2), false}}};
+void light_call(RayCall<RmLightArgs> &c, const rm_light *light, void *t, void *iters, void *sdf_calls, void *normal, void *lit, void *ao, void *iters2,
+                void *sdf_calls2) {
+    c.launch[0] = rm_launch_light;
+    c.launch[1] = rm_launch_light_sqrt;
+    c.chunk = kHostChunk;
+    c.column(t, 8, &c.args.t, false);
+    c.column(iters, 4, &c.args.iters, false);
+    c.column(sdf_calls, 4, &c.args.sdf, false);
+    c.column(normal, 12, &c.args.normal, false);
+    c.column(lit, 4, &c.args.lit, false);
+    c.column(ao, 4, &c.args.ao, false);
+    c.column(iters2, 4, &c.args.iters2, false);
+    c.column(sdf_calls2, 4, &c.args.sdf2, false);
     c.args.bias = light->bias;
     c.args.ao_step = light->ao_step;
     c.args.ao_strength = light->ao_strength;
     std::memcpy(c.args.light, light->dir, sizeof c.args.light);
     c.args.ao_samples = light->ao_samples;
-    return c;
 }
 
 // what both forms of rm_ray_walk check: the record capacity and the outputs.  device: the caller's pointers are the kernel's,
@@ -1541,13 +1587,14 @@ int check_walk(rm_ctx *ctx, bool device, int64_t n, int32_t cap, const void *wal
 // With step records the host form's chunk is sized by bytes: at most 64 MiB of records, at least one ray (cap 256: 10 922
 // rays).  Slots past a ray's length are left as the caller has them: the caller's records go in, the kernel overwrites the
 // ones the walk produced, and all come back.
-RayCall<RmWalkArgs> walk_call(int32_t cap, void *walks, void *steps) {
+void walk_call(RayCall<RmWalkArgs> &c, int32_t cap, void *walks, void *steps) {
     const size_t per_ray = sizeof(rm_step) * static_cast<size_t>(cap);
-    const int64_t chunk = steps ? std::max<int64_t>(1, static_cast<int64_t>((size_t(64) << 20) / per_ray)) : kRayChunk;
-    RayCall<RmWalkArgs> c{{}, {rm_launch_walk, rm_launch_walk_sqrt}, chunk, 2,
-                          {{walks, sizeof(rm_walk), offsetof(RmWalkArgs, walks), false}, {steps, per_ray, offsetof(RmWalkArgs, steps), true}}};
+    c.launch[0] = rm_launch_walk;
+    c.launch[1] = rm_launch_walk_sqrt;
+    c.chunk = steps ? std::max<int64_t>(1, static_cast<int64_t>((size_t(64) << 20) / per_ray)) : kHostChunk;
+    c.column(walks, sizeof(rm_walk), &c.args.walks, false);
+    c.column(steps, per_ray, &c.args.steps, true);
     c.args.cap = cap;
-    return c;
 }
 
 // Object `index` of the active scene as an rm_scene_from_nodes forest (operands before their user, the object's root last),
@@ -1793,22 +1840,23 @@ int check_field(rm_ctx *ctx, const rm_lattice *lat, const void *dist, const void
     return RM_OK;
 }
 
-// The parameter block and the lattice of a field query: the active scene as rm_scene_distance passes it, at the lattice's own
-// time (ctx->time is not touched), ahead-of-time kernels only.
-void fill_field(const rm_ctx *ctx, const rm_lattice *lat, RmRenderParams &p, RmFieldArgs &a) {
-    std::memset(&p, 0, sizeof p);
-    fill_scene_view(ctx, p);
-    p.time = lat->time;
-    p.filter = static_cast<int32_t>(ctx->opt_filter);
-    p.tile_w = 8;
-    p.rtc_function = nullptr;
-    std::memset(&a, 0, sizeof a);
+// The lattice as the kernels take it: the binary32 vectors widened (exact).  Every argument block that names a lattice opens with it.
+RmLattice widen_lattice(const rm_lattice &l) {
+    RmLattice w;
     for (int c = 0; c < 3; ++c) {
-        a.origin[c] = lat->origin[c];
-        a.du[c] = lat->du[c];
-        a.dv[c] = lat->dv[c];
-        a.dw[c] = lat->dw[c];
+        w.origin[c] = l.origin[c];
+        w.du[c] = l.du[c];
+        w.dv[c] = l.dv[c];
+        w.dw[c] = l.dw[c];
     }
+    return w;
+}
+
+// The parameter block and the lattice of a field query: the active scene at the lattice's own time (fill_scene_query).
+void fill_field(const rm_ctx *ctx, const rm_lattice *lat, RmRenderParams &p, RmFieldArgs &a) {
+    fill_scene_query(ctx, lat->time, p);
+    std::memset(&a, 0, sizeof a);
+    a.lat = widen_lattice(*lat);
     a.nu = static_cast<unsigned int>(lat->nu);
     a.nv = static_cast<unsigned int>(lat->nv);
 }
@@ -1830,15 +1878,25 @@ struct MeshCall {
     int64_t cap_vertices, cap_quads;
 };
 
+bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
+
+// what every mesh entry, dense or sparse, checks about iso, capacities and output buffers (the sparse ones: cells and edges too)
+const char *mesh_outputs_error(double iso, const void *vertices, int64_t cap_vertices, const void *quads, int64_t cap_quads, const void *cells,
+                               const void *edges) {
+    if (!std::isfinite(iso)) return "non-finite iso";
+    if (cap_vertices < 0 || cap_quads < 0) return "negative capacity";
+    if ((cap_vertices > 0 && !vertices) || (cap_quads > 0 && !quads)) return "null buffer with a capacity above 0";
+    if (misaligned(vertices, 3) || misaligned(quads, 3)) return "vertices and quads must be 4-byte aligned";
+    if (misaligned(cells, 7) || misaligned(edges, 7)) return "cells and edges must be 8-byte aligned";
+    return nullptr;
+}
+
 int check_mesh(rm_ctx *ctx, const MeshCall &m, int64_t *n, bool *cells) {
     if (const char *bad = lattice_error(m.lattice, n)) return fail(ctx, RM_E_INVALID, bad);
     if (*n > (int64_t(1) << 30)) return fail(ctx, RM_E_INVALID, "more than 2^30 lattice points: the mesher does not split a volume");
     *cells = m.lattice->nu >= 2 && m.lattice->nv >= 2 && m.lattice->nw >= 2;
     if (!m.info) return fail(ctx, RM_E_INVALID, "null info");
-    if (!std::isfinite(m.iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
-    if (m.cap_vertices < 0 || m.cap_quads < 0) return fail(ctx, RM_E_INVALID, "negative capacity");
-    if ((m.cap_vertices > 0 && !m.vertices) || (m.cap_quads > 0 && !m.quads)) return fail(ctx, RM_E_INVALID, "null buffer with a capacity above 0");
-    if ((reinterpret_cast<uintptr_t>(m.vertices) | reinterpret_cast<uintptr_t>(m.quads)) & 3) return fail(ctx, RM_E_INVALID, "vertices and quads must be 4-byte aligned");
+    if (const char *bad = mesh_outputs_error(m.iso, m.vertices, m.cap_vertices, m.quads, m.cap_quads, nullptr, nullptr)) return fail(ctx, RM_E_INVALID, bad);
     if (m.own_values) {
         if (m.value_type != RM_MESH_F64 && m.value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
         if (*cells && !m.values) return fail(ctx, RM_E_INVALID, "null values");
@@ -1856,12 +1914,7 @@ RmMeshArgs mesh_args(const Staging &st, const MeshCall &m, int64_t n, const void
                      void *d_info, size_t o_map, size_t o_totals) {
     RmMeshArgs a;
     std::memset(&a, 0, sizeof a);
-    for (int c = 0; c < 3; ++c) {
-        a.origin[c] = m.lattice->origin[c];
-        a.du[c] = m.lattice->du[c];
-        a.dv[c] = m.lattice->dv[c];
-        a.dw[c] = m.lattice->dw[c];
-    }
+    a.lat = widen_lattice(*m.lattice);
     a.values = d_values;
     a.iso = m.iso;
     a.vertices = static_cast<float *>(d_vertices);
@@ -1888,6 +1941,26 @@ int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, co
 }
 
 size_t mesh_blocks(int64_t n) { return static_cast<size_t>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK); }
+
+// How both host mesh entries end: the info comes back first, then of every output asked for what the mesher wrote of it --
+// min(info->n_vertices, room_v) records per vertex, min(info->n_quads, room_q) per quad.
+struct MeshOutput {
+    void *host;  // null: not asked for
+    size_t offset, bytes;
+    bool per_quad;
+};
+int read_mesh(rm_ctx *ctx, const Staging &st, rm_mesh_info *info, size_t o_info, size_t room_v, size_t room_q, std::initializer_list<MeshOutput> outputs) {
+    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
+    RM_HIP(ctx, st.sync());
+    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
+                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
+    for (const MeshOutput &o : outputs) {
+        const size_t got = o.per_quad ? got_q : got_v;
+        if (got && o.host) RM_HIP(ctx, st.out(o.host, o.offset, o.bytes * got));
+    }
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
 
 // ---- sparse meshes: blocks of 8 x 8 x 8 cells, their tiles and the mesher over them (rm_kernels.hip, rm_mesh_sparse.hip)
 
@@ -1928,12 +2001,7 @@ double sparse_bound(const rm_lattice &l, double lipschitz) {
 template <typename ARGS>
 void fill_sparse_lattice(const rm_lattice *lat, const SparseGrid &g, ARGS &a) {
     std::memset(&a, 0, sizeof a);
-    for (int c = 0; c < 3; ++c) {
-        a.origin[c] = lat->origin[c];
-        a.du[c] = lat->du[c];
-        a.dv[c] = lat->dv[c];
-        a.dw[c] = lat->dw[c];
-    }
+    a.lat = widen_lattice(*lat);
     a.nu = static_cast<unsigned int>(lat->nu);
     a.nv = static_cast<unsigned int>(lat->nv);
     a.nw = static_cast<unsigned int>(lat->nw);
@@ -1943,14 +2011,11 @@ void fill_sparse_lattice(const rm_lattice *lat, const SparseGrid &g, ARGS &a) {
 
 size_t sparse_groups(int64_t n_blocks) { return static_cast<size_t>((n_blocks + 255) / 256); }
 
-bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
-
 // The three launches; every pointer a device pointer, the scene the active one at the lattice's time.
 int launch_blocks(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, double iso, double lipschitz, void *d_slot, void *d_list, void *d_dist,
                   void *d_info, uint32_t *d_totals, hipStream_t stream) {
     RmRenderParams p;
-    RmFieldArgs unused;
-    fill_field(ctx, lat, p, unused);
+    fill_scene_query(ctx, lat->time, p);
     RmBlocksArgs a;
     fill_sparse_lattice(lat, g, a);
     a.nbw = static_cast<unsigned int>(g.nb[2]);
@@ -1969,8 +2034,7 @@ int launch_blocks(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, doubl
 
 int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream) {
     RmRenderParams p;
-    RmFieldArgs unused;
-    fill_field(ctx, lat, p, unused);
+    fill_scene_query(ctx, lat->time, p);
     if (const int erc = apply_exact(ctx, p)) return erc;
     RmTilesArgs a;
     fill_sparse_lattice(lat, g, a);
@@ -2015,17 +2079,6 @@ int launch_mesh_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, c
     a.n_kept = static_cast<unsigned int>(m.n_kept);
     RM_HIP(ctx, rm_launch_mesh_tiles(a, stream, &ctx->last_kernel));
     return RM_OK;
-}
-
-// what the mesh entries share about iso, capacities and output buffers (device entry: d_cells and d_edges too)
-const char *mesh_outputs_error(double iso, const void *vertices, int64_t cap_vertices, const void *quads, int64_t cap_quads, const void *cells,
-                               const void *edges) {
-    if (!std::isfinite(iso)) return "non-finite iso";
-    if (cap_vertices < 0 || cap_quads < 0) return "negative capacity";
-    if ((cap_vertices > 0 && !vertices) || (cap_quads > 0 && !quads)) return "null buffer with a capacity above 0";
-    if (misaligned(vertices, 3) || misaligned(quads, 3)) return "vertices and quads must be 4-byte aligned";
-    if (misaligned(cells, 7) || misaligned(edges, 7)) return "cells and edges must be 8-byte aligned";
-    return nullptr;
 }
 
 int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const void *values, const void *rgba) {
@@ -2099,15 +2152,9 @@ int check_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float *p
     return RM_OK;
 }
 
-// The parameter block and the query of a point query: the active scene as rm_scene_field passes it, at the query's own time
-// (ctx->time is not touched), ahead-of-time kernels only.
+// The parameter block and the query of a point query: the active scene at the query's own time (fill_scene_query).
 void fill_points(const rm_ctx *ctx, const rm_point_query *q, RmRenderParams &p, RmPointArgs &a) {
-    std::memset(&p, 0, sizeof p);
-    fill_scene_view(ctx, p);
-    p.time = q->time;
-    p.filter = static_cast<int32_t>(ctx->opt_filter);
-    p.tile_w = 8;
-    p.rtc_function = nullptr;
+    fill_scene_query(ctx, q->time, p);
     std::memset(&a, 0, sizeof a);
     a.slot_obj = ctx->dev.slot_object;
     a.iso = q->iso;
@@ -2141,24 +2188,19 @@ int check_sharp(rm_ctx *ctx, const rm_lattice *lat, const rm_sharp_query *q, int
     return RM_OK;
 }
 
-// The parameter block and the query of rm_scene_sharpen: the active scene as rm_scene_field passes it, at the lattice's own time
-// (ctx->time is not touched).  rho, half the longest body diagonal of a cell, and the limit reach * rho in the rule's order.
+// The parameter block and the query of rm_scene_sharpen: the active scene at the lattice's own time (fill_scene_query).  rho,
+// half the longest body diagonal of a cell, and the limit reach * rho in the rule's order.
 void fill_sharp(const rm_ctx *ctx, const rm_lattice *lat, const rm_sharp_query *q, RmRenderParams &p, RmSharpArgs &a) {
-    RmFieldArgs f;
-    fill_field(ctx, lat, p, f);
+    fill_scene_query(ctx, lat->time, p);
     std::memset(&a, 0, sizeof a);
+    a.lat = widen_lattice(*lat);
+    const RmLattice &l = a.lat;
     double longest = 0.0;
-    for (int c = 0; c < 3; ++c) {
-        a.origin[c] = f.origin[c];
-        a.du[c] = f.du[c];
-        a.dv[c] = f.dv[c];
-        a.dw[c] = f.dw[c];
-    }
     for (int s = 0; s < 4; ++s) {  // (du + dv) + dw, (du + dv) - dw, (du - dv) + dw, (du - dv) - dw
         double d[3];
         for (int c = 0; c < 3; ++c) {
-            const double uv = s < 2 ? a.du[c] + a.dv[c] : a.du[c] - a.dv[c];
-            d[c] = s % 2 == 0 ? uv + a.dw[c] : uv - a.dw[c];
+            const double uv = s < 2 ? l.du[c] + l.dv[c] : l.du[c] - l.dv[c];
+            d[c] = s % 2 == 0 ? uv + l.dw[c] : uv - l.dw[c];
         }
         const double length = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
         if (s == 0 || length > longest) longest = length;
@@ -2170,6 +2212,69 @@ void fill_sharp(const rm_ctx *ctx, const rm_lattice *lat, const rm_sharp_query *
     a.nv = static_cast<unsigned int>(lat->nv);
     a.nw = static_cast<unsigned int>(lat->nw);
     a.refine = q->refine;
+}
+
+// Both forms of rm_scene_field, rm_scene_points and rm_scene_sharpen, as ray_call is both forms of a ray query: the checks,
+// the launch's two blocks, then staged_call with the entry's columns.  host: the buffers are the caller's host memory.
+
+// The host form goes in chunks of whole lattice rows, at most 4 M points (16 B per point with every output: 64 MB); a row
+// always fits (nu <= 65535).  The launch is told where its range starts.
+int scene_field_call(rm_ctx *ctx, const rm_lattice *lattice, bool host, void *dist, void *dist32, void *count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    const int rc = check_field(ctx, lattice, dist, dist32, count, &n);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmFieldArgs a;
+    fill_field(ctx, lattice, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{dist, 8, &a.dist, false, true}, {dist32, 4, &a.dist32, false, true}, {count, 4, &a.count, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n, lattice->nu, kHostChunk, cols, 3, [&](int64_t first, int64_t m, hipStream_t s) {
+        a.first = first;
+        a.n = m;
+        return (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, s, &ctx->last_kernel);
+    });
+}
+
+// The host form goes in chunks of at most 4 M points, as the ray queries: 12 B per point go up, and the positions are written
+// over the staged points (48 B per point with all six outputs: 192 MB).
+int scene_points_call(rm_ctx *ctx, const rm_point_query *q, int64_t n, const void *points, bool host, void *position, void *dist, void *normal,
+                      void *object, void *steps, void *count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_points(ctx, q, n, static_cast<const float *>(points), host, position, dist, normal, object, steps, count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmPointArgs a;
+    fill_points(ctx, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{points, 12, &a.points, true, false},  {position, 12, &a.position, false, true, 0}, {dist, 8, &a.dist, false, true},
+                           {normal, 12, &a.normal, false, true}, {object, 4, &a.object, false, true},         {steps, 4, &a.steps, false, true},
+                           {count, 4, &a.count, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n, 1, kHostChunk, cols, 7, [&](int64_t, int64_t m, hipStream_t s) {
+        a.n = m;
+        return (ctx->opt_length ? rm_launch_points_sqrt : rm_launch_points)(p, a, s, &ctx->last_kernel);
+    });
+}
+
+// The host form goes in chunks of at most 4 M vertices: 8 B per vertex go up, 12 B and the optional outputs come back.
+int scene_sharpen_call(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const void *cells, bool host, void *position,
+                       void *feature, void *count, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_sharp(ctx, lattice, q, n, cells, position, feature, count);
+    if (rc || !n) return rc;
+    RmRenderParams p;
+    RmSharpArgs a;
+    fill_sharp(ctx, lattice, q, p, a);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{cells, 8, &a.cells, true, false}, {position, 12, &a.position, false, true}, {feature, 4, &a.feature, false, true},
+                           {count, 4, &a.count, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n, 1, kHostChunk, cols, 4, [&](int64_t, int64_t m, hipStream_t s) {
+        a.n = m;
+        return (ctx->opt_length ? rm_launch_sharp_sqrt : rm_launch_sharp)(p, a, s, &ctx->last_kernel);
+    });
 }
 
 }  // namespace
@@ -2961,11 +3066,7 @@ int rm_partition_rows(int32_t height, int32_t n_workers, int32_t i, int32_t *y_s
 int rm_scene_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
     return points_call(ctx, points_xyz, n, dist, count, [] { return RM_OK; }, [&](const float *d_points, double *d_dist, uint32_t *d_count) {
         RmRenderParams p;
-        std::memset(&p, 0, sizeof p);
-        fill_scene_view(ctx, p);
-        p.time = ctx->time;
-        p.filter = static_cast<int32_t>(ctx->opt_filter);
-        p.tile_w = 8;
+        fill_scene_query(ctx, ctx->time, p);
         const rmrtc::Kernel *special = specialised_kernel(ctx, p.accel, false);
         p.rtc_function = special ? special->distance : nullptr;
         return (ctx->opt_length ? rm_launch_distance_sqrt : rm_launch_distance)(p, d_points, n, d_dist, d_count, ctx->stream);
@@ -2993,124 +3094,21 @@ int rm_lattice_points(const rm_lattice *lattice, int64_t first, int64_t n, float
 }
 
 int rm_scene_field_device(rm_ctx *ctx, const rm_lattice *lattice, void *d_dist, void *d_dist32, void *d_count, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    int64_t n = 0;
-    const int rc = check_field(ctx, lattice, d_dist, d_dist32, d_count, &n);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmFieldArgs a;
-    fill_field(ctx, lattice, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    a.dist = static_cast<double *>(d_dist);
-    a.dist32 = static_cast<float *>(d_dist32);
-    a.count = static_cast<uint32_t *>(d_count);
-    a.first = 0;
-    a.n = n;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
+    return scene_field_call(ctx, lattice, false, d_dist, d_dist32, d_count, stream);
 }
 
 int rm_scene_field(rm_ctx *ctx, const rm_lattice *lattice, double *dist, float *dist32, uint32_t *count) {
-    if (!ctx) return RM_E_INVALID;
-    int64_t n = 0;
-    int rc = check_field(ctx, lattice, dist, dist32, count, &n);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmFieldArgs a;
-    fill_field(ctx, lattice, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // Through the scratch buffer in chunks of whole lattice rows, at most 4 M points (16 B per point with every output: 64 MB);
-    // a row always fits (nu <= 65535).  Only the outputs asked for are staged and copied back.
-    const int64_t nu = lattice->nu, rows = n / nu;
-    int64_t chunk_rows = (int64_t(1) << 22) / nu;
-    if (chunk_rows < 1) chunk_rows = 1;
-    if (chunk_rows > rows) chunk_rows = rows;
-    const size_t c = static_cast<size_t>(chunk_rows * nu);
-    Staging st{ctx};
-    const size_t o_dist = st.region(dist ? 8 * c : 0), o_d32 = st.region(dist32 ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
-    if ((rc = st.reserve())) return rc;
-    a.dist = dist ? st.at<double>(o_dist) : nullptr;
-    a.dist32 = dist32 ? st.at<float>(o_d32) : nullptr;
-    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
-    for (int64_t r = 0; r < rows; r += chunk_rows) {
-        const int64_t m = (rows - r < chunk_rows ? rows - r : chunk_rows) * nu;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(r * nu);
-        a.first = r * nu;
-        a.n = m;
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
-        if (dist) RM_HIP(ctx, st.out(dist + at, o_dist, 8 * k));
-        if (dist32) RM_HIP(ctx, st.out(dist32 + at, o_d32, 4 * k));
-        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return scene_field_call(ctx, lattice, true, dist, dist32, count, nullptr);
 }
 
 int rm_scene_points_device(rm_ctx *ctx, const rm_point_query *q, int64_t n, const void *d_points, void *d_position, void *d_dist, void *d_normal,
                            void *d_object, void *d_steps, void *d_count, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_points(ctx, q, n, static_cast<const float *>(d_points), false, d_position, d_dist, d_normal, d_object, d_steps, d_count);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmPointArgs a;
-    fill_points(ctx, q, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    a.points = static_cast<const float *>(d_points);
-    a.position = static_cast<float *>(d_position);
-    a.dist = static_cast<double *>(d_dist);
-    a.normal = static_cast<float *>(d_normal);
-    a.object = static_cast<int32_t *>(d_object);
-    a.steps = static_cast<int32_t *>(d_steps);
-    a.count = static_cast<uint32_t *>(d_count);
-    a.n = n;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_points_sqrt : rm_launch_points)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
+    return scene_points_call(ctx, q, n, d_points, false, d_position, d_dist, d_normal, d_object, d_steps, d_count, stream);
 }
 
 int rm_scene_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float *points_xyz, float *position, double *dist, float *normal,
                     int32_t *object, int32_t *steps, uint32_t *count) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_points(ctx, q, n, points_xyz, true, position, dist, normal, object, steps, count);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmPointArgs a;
-    fill_points(ctx, q, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // Through the scratch buffer in chunks of at most 4 M points, as the ray queries (ray_call): 12 B per point go up, and only
-    // the outputs asked for are staged and copied back (48 B per point with all six: 192 MB).  The positions are written over the
-    // staged points.
-    const int64_t chunk = n < kRayChunk ? n : kRayChunk;
-    const size_t c = static_cast<size_t>(chunk);
-    Staging st{ctx};
-    const size_t o_pts = st.region(12 * c), o_dist = st.region(dist ? 8 * c : 0), o_nrm = st.region(normal ? 12 * c : 0), o_obj = st.region(object ? 4 * c : 0),
-                 o_steps = st.region(steps ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
-    if ((rc = st.reserve())) return rc;
-    a.points = st.at<const float>(o_pts);
-    a.position = position ? st.at<float>(o_pts) : nullptr;
-    a.dist = dist ? st.at<double>(o_dist) : nullptr;
-    a.normal = normal ? st.at<float>(o_nrm) : nullptr;
-    a.object = object ? st.at<int32_t>(o_obj) : nullptr;
-    a.steps = steps ? st.at<int32_t>(o_steps) : nullptr;
-    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        a.n = m;
-        RM_HIP(ctx, st.in(o_pts, points_xyz + 3 * at, 12 * k));
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_points_sqrt : rm_launch_points)(p, a, ctx->stream, &ctx->last_kernel));
-        if (position) RM_HIP(ctx, st.out(position + 3 * at, o_pts, 12 * k));
-        if (dist) RM_HIP(ctx, st.out(dist + at, o_dist, 8 * k));
-        if (normal) RM_HIP(ctx, st.out(normal + 3 * at, o_nrm, 12 * k));
-        if (object) RM_HIP(ctx, st.out(object + at, o_obj, 4 * k));
-        if (steps) RM_HIP(ctx, st.out(steps + at, o_steps, 4 * k));
-        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return scene_points_call(ctx, q, n, points_xyz, true, position, dist, normal, object, steps, count, nullptr);
 }
 
 int rm_shade_field_device(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *d_values, void *d_rgba, void *stream) {
@@ -3207,14 +3205,7 @@ int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *ver
     if ((rc = launch_mesh(ctx, st, on_device, n, st.at<void>(o_vol), RM_MESH_F64, st.at<void>(o_vert), st.at<void>(o_quad), st.at<void>(o_info), o_map,
                           o_totals, ctx->stream)))
         return rc;
-    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
-    RM_HIP(ctx, st.sync());
-    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
-                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
-    if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
-    if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return read_mesh(ctx, st, info, o_info, room_v, room_q, {{vertices, o_vert, 12, false}, {quads, o_quad, 16, true}});
 }
 
 int rm_mesh_cells_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_cells,
@@ -3243,56 +3234,12 @@ int rm_mesh_cells_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_v
 
 int rm_scene_sharpen_device(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const void *d_cells, void *d_position,
                             void *d_feature, void *d_count, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_sharp(ctx, lattice, q, n, d_cells, d_position, d_feature, d_count);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmSharpArgs a;
-    fill_sharp(ctx, lattice, q, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    a.cells = static_cast<const long long *>(d_cells);
-    a.position = static_cast<float *>(d_position);
-    a.feature = static_cast<int32_t *>(d_feature);
-    a.count = static_cast<uint32_t *>(d_count);
-    a.n = n;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, (ctx->opt_length ? rm_launch_sharp_sqrt : rm_launch_sharp)(p, a, static_cast<hipStream_t>(stream), &ctx->last_kernel));
-    return RM_OK;
+    return scene_sharpen_call(ctx, lattice, q, n, d_cells, false, d_position, d_feature, d_count, stream);
 }
 
 int rm_scene_sharpen(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const int64_t *cells, float *position,
                      int32_t *feature, uint32_t *count) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_sharp(ctx, lattice, q, n, cells, position, feature, count);
-    if (rc || !n) return rc;
-    RmRenderParams p;
-    RmSharpArgs a;
-    fill_sharp(ctx, lattice, q, p, a);
-    if (const int erc = apply_exact(ctx, p)) return erc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    // Through the scratch buffer in chunks of at most 4 M vertices, as rm_scene_points: 8 B per vertex go up, 12 B and the optional
-    // outputs come back.
-    const int64_t chunk = n < kRayChunk ? n : kRayChunk;
-    const size_t c = static_cast<size_t>(chunk);
-    Staging st{ctx};
-    const size_t o_cells = st.region(8 * c), o_pos = st.region(12 * c), o_feat = st.region(feature ? 4 * c : 0), o_cnt = st.region(count ? 4 * c : 0);
-    if ((rc = st.reserve())) return rc;
-    a.cells = st.at<const long long>(o_cells);
-    a.position = st.at<float>(o_pos);
-    a.feature = feature ? st.at<int32_t>(o_feat) : nullptr;
-    a.count = count ? st.at<uint32_t>(o_cnt) : nullptr;
-    for (int64_t s = 0; s < n; s += chunk) {
-        const int64_t m = n - s < chunk ? n - s : chunk;
-        const size_t k = static_cast<size_t>(m), at = static_cast<size_t>(s);
-        a.n = m;
-        RM_HIP(ctx, st.in(o_cells, cells + at, 8 * k));
-        RM_HIP(ctx, (ctx->opt_length ? rm_launch_sharp_sqrt : rm_launch_sharp)(p, a, ctx->stream, &ctx->last_kernel));
-        RM_HIP(ctx, st.out(position + 3 * at, o_pos, 12 * k));
-        if (feature) RM_HIP(ctx, st.out(feature + at, o_feat, 4 * k));
-        if (count) RM_HIP(ctx, st.out(count + at, o_cnt, 4 * k));
-        RM_HIP(ctx, st.sync());  // the next chunk reuses the scratch
-    }
-    return RM_OK;
+    return scene_sharpen_call(ctx, lattice, q, n, cells, true, position, feature, count, nullptr);
 }
 
 int rm_lattice_blocks(const rm_lattice *lattice, int32_t dims[3]) {
@@ -3429,16 +3376,8 @@ int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, dou
                            cells ? st.at<void>(o_cells) : nullptr, edges ? st.at<void>(o_edges) : nullptr, st.at<void>(o_info),
                            static_cast<int64_t>(room_v), static_cast<int64_t>(room_q)};
     if ((rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), ctx->stream))) return rc;
-    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
-    RM_HIP(ctx, st.sync());
-    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
-                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
-    if (got_v) RM_HIP(ctx, st.out(vertices, o_vert, 12 * got_v));
-    if (got_q) RM_HIP(ctx, st.out(quads, o_quad, 16 * got_q));
-    if (got_v && cells) RM_HIP(ctx, st.out(cells, o_cells, 8 * got_v));
-    if (got_q && edges) RM_HIP(ctx, st.out(edges, o_edges, 8 * got_q));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return read_mesh(ctx, st, info, o_info, room_v, room_q,
+                     {{vertices, o_vert, 12, false}, {quads, o_quad, 16, true}, {cells, o_cells, 8, false}, {edges, o_edges, 8, true}});
 }
 
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
@@ -3461,14 +3400,14 @@ int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, doub
 
 int rm_ray_march_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                         void *d_sdf_calls, void *d_normal, void *stream) {
-    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
-                    [&] { return query_call(ctx, q, false, d_t, d_iters, d_sdf_calls, d_normal, nullptr); });
+    return ray_call<RmQueryArgs>(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
+                                 [&](RayCall<RmQueryArgs> &c) { query_call(c, ctx, q, false, d_t, d_iters, d_sdf_calls, d_normal, nullptr); });
 }
 
 int rm_ray_march(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                  uint32_t *sdf_calls, float *normal_xyz) {
-    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
-                    [&] { return query_call(ctx, q, false, t, iters, sdf_calls, normal_xyz, nullptr); });
+    return ray_call<RmQueryArgs>(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
+                                 [&](RayCall<RmQueryArgs> &c) { query_call(c, ctx, q, false, t, iters, sdf_calls, normal_xyz, nullptr); });
 }
 
 int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int32_t y_start, int32_t y_end, float *origin3, float *dirs_xyz) {
@@ -3499,39 +3438,39 @@ int rm_camera_rays(int32_t width, int32_t height, double pitch, double yaw, int3
 
 int rm_ray_pick_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, void *d_t, void *d_iters,
                        void *d_sdf_calls, void *d_normal, void *d_object, void *stream) {
-    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
-                    [&] { return query_call(ctx, q, true, d_t, d_iters, d_sdf_calls, d_normal, d_object); });
+    return ray_call<RmQueryArgs>(ctx, q, n, d_origins, d_dirs, false, stream, no_check,
+                                 [&](RayCall<RmQueryArgs> &c) { query_call(c, ctx, q, true, d_t, d_iters, d_sdf_calls, d_normal, d_object); });
 }
 
 int rm_ray_pick(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t, uint32_t *iters,
                 uint32_t *sdf_calls, float *normal_xyz, int32_t *object) {
-    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
-                    [&] { return query_call(ctx, q, true, t, iters, sdf_calls, normal_xyz, object); });
+    return ray_call<RmQueryArgs>(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, no_check,
+                                 [&](RayCall<RmQueryArgs> &c) { query_call(c, ctx, q, true, t, iters, sdf_calls, normal_xyz, object); });
 }
 
 int rm_ray_light_device(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const void *d_origins, const void *d_dirs, void *d_t,
                         void *d_iters, void *d_sdf_calls, void *d_normal, void *d_lit, void *d_ao, void *d_iters2, void *d_sdf_calls2,
                         void *stream) {
-    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_light(ctx, light); },
-                    [&] { return light_call(light, d_t, d_iters, d_sdf_calls, d_normal, d_lit, d_ao, d_iters2, d_sdf_calls2); });
+    return ray_call<RmLightArgs>(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_light(ctx, light); },
+                                 [&](RayCall<RmLightArgs> &c) { light_call(c, light, d_t, d_iters, d_sdf_calls, d_normal, d_lit, d_ao, d_iters2, d_sdf_calls2); });
 }
 
 int rm_ray_light(rm_ctx *ctx, const rm_ray_query *q, const rm_light *light, int64_t n, const float *origins_xyz, const float *dirs_xyz, double *t,
                  uint32_t *iters, uint32_t *sdf_calls, float *normal_xyz, float *lit, float *ao, uint32_t *iters2, uint32_t *sdf_calls2) {
-    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_light(ctx, light); },
-                    [&] { return light_call(light, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2); });
+    return ray_call<RmLightArgs>(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_light(ctx, light); },
+                                 [&](RayCall<RmLightArgs> &c) { light_call(c, light, t, iters, sdf_calls, normal_xyz, lit, ao, iters2, sdf_calls2); });
 }
 
 int rm_ray_walk_device(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const void *d_origins, const void *d_dirs, int32_t cap, void *d_walks,
                        void *d_steps, void *stream) {
-    return ray_call(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_walk(ctx, true, n, cap, d_walks, d_steps); },
-                    [&] { return walk_call(cap, d_walks, d_steps); });
+    return ray_call<RmWalkArgs>(ctx, q, n, d_origins, d_dirs, false, stream, [&] { return check_walk(ctx, true, n, cap, d_walks, d_steps); },
+                                [&](RayCall<RmWalkArgs> &c) { walk_call(c, cap, d_walks, d_steps); });
 }
 
 int rm_ray_walk(rm_ctx *ctx, const rm_ray_query *q, int64_t n, const float *origins_xyz, const float *dirs_xyz, int32_t cap, rm_walk *walks,
                 rm_step *steps) {
-    return ray_call(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_walk(ctx, false, n, cap, walks, steps); },
-                    [&] { return walk_call(cap, walks, steps); });
+    return ray_call<RmWalkArgs>(ctx, q, n, origins_xyz, dirs_xyz, true, nullptr, [&] { return check_walk(ctx, false, n, cap, walks, steps); },
+                                [&](RayCall<RmWalkArgs> &c) { walk_call(c, cap, walks, steps); });
 }
 
 int rm_phong_light(float dir3[3]) {

@@ -2,6 +2,7 @@
 #pragma once
 #ifndef __HIPCC_RTC__
 #include <hip/hip_runtime_api.h>
+#include <stddef.h>
 #include <stdint.h>
 #endif
 
@@ -192,10 +193,27 @@ struct RmWalkArgs {
     long long n;                  // set by the launcher
     int cap, pad;
 };
-// rm_scene_field (rm_kernels.hip, field_kernel): the lattice (rm_lattice, its binary32 vectors widened: exact), the linear range
-// [first, first + n) of one call and the outputs, indexed from `first`, each of which may be null
-struct RmFieldArgs {
+// The lattice of the field, sharp-vertex and mesh launches: rm_lattice's binary32 vectors, widened (exact).  It is the first
+// member of every argument block that names a lattice, so the vectors sit where they sat when each block spelled them out (the
+// static_asserts ahead of the launchers' declarations pin the layouts: the kernels take the blocks by value).
+struct RmLattice {
     double origin[3], du[3], dv[3], dw[3];
+};
+// The point rule of include/rm_raymarch.h, the contract of every lattice entry: component c of the point with index (fi, fj, fk)
+// -- whole numbers for a lattice point, fractional ones for a mesh vertex or an edge crossing -- in binary64, left to right, one
+// operation at a time (-ffp-contract=off).  This is the rule's only text on the device: field values, tiles, mesh vertices and
+// sharp vertices agree bit for bit because all of them call it.  A point is its three components, each rounded once to binary32
+// (rm_kernels.hip, lattice_point); the sharp vertices also take a component before its rounding.  (The library's own
+// kernels only: a scene kernel compiled at run time samples no lattice.)
+#if defined(__HIP__) && !defined(RM_RTC)
+__device__ __forceinline__ double rm_lattice_component(const RmLattice &l, int c, double fi, double fj, double fk) {
+    return ((l.origin[c] + fi * l.du[c]) + fj * l.dv[c]) + fk * l.dw[c];
+}
+#endif
+// rm_scene_field (rm_kernels.hip, field_kernel): the lattice, the linear range [first, first + n) of one call and the outputs,
+// indexed from `first`, each of which may be null
+struct RmFieldArgs {
+    RmLattice lat;
     double *dist;
     float *dist32;
     uint32_t *count;
@@ -223,7 +241,7 @@ struct RmPointArgs {
 #define RM_SHARP_CELLS 64
 #define RM_SHARP_CROSSINGS (12 * RM_SHARP_CELLS)  // what the cells of a workgroup can hold at most
 struct RmSharpArgs {
-    double origin[3], du[3], dv[3], dw[3];  // the lattice's vectors, widened
+    RmLattice lat;
     double iso, rank_tol;
     double limit;             // reach * rho, formed by the host in the rule's order
     const long long *cells;   // i64[n]
@@ -250,7 +268,7 @@ struct RmMeshInfo {  // rm_mesh_info (32 bytes)
     long long n_vertices, n_quads, n_holes, reserved;
 };
 struct RmMeshArgs {
-    double origin[3], du[3], dv[3], dw[3];  // the lattice's vectors, widened
+    RmLattice lat;
     const void *values;  // n binary64 values, or binary32 ones with f32
     double iso;
     float *vertices;     // cap_vertices x 3
@@ -276,7 +294,7 @@ struct RmSparseInfo {  // rm_sparse_info (32 bytes)
 // flag (0 kept, -1 dropped) into slot and the kept blocks of each workgroup of 256 into totals; the scan turns the totals into
 // offsets and writes info; the scatter turns the flags into ranks and writes list.
 struct RmBlocksArgs {
-    double origin[3], du[3], dv[3], dw[3];
+    RmLattice lat;
     double iso, bound;
     int32_t *slot, *list;
     double *dist;       // may be null
@@ -287,7 +305,7 @@ struct RmBlocksArgs {
 };
 // rm_scene_tiles_device (rm_kernels.hip tiles_kernel): one workgroup per kept block
 struct RmTilesArgs {
-    double origin[3], du[3], dv[3], dw[3];
+    RmLattice lat;
     const int32_t *list;
     double *tiles;      // n_kept x RM_SPARSE_TILE
     unsigned int nu, nv, nw, nbu, nbv, n_kept;
@@ -301,7 +319,7 @@ struct RmTilesArgs {
 #define RM_ACCEL_EXACT 3
 // rm_mesh_tiles_device (rm_mesh_sparse.hip): one workgroup per kept block, the fields vertex_position reads named as in RmMeshArgs
 struct RmSparseMeshArgs {
-    double origin[3], du[3], dv[3], dw[3];
+    RmLattice lat;
     double iso;
     const int32_t *slot, *list;
     const double *tiles;
@@ -348,6 +366,17 @@ struct RmEmptyDistArgs {
 };
 
 #ifndef __HIPCC_RTC__  // (host side: the launchers)
+// The blocks that open with the lattice are kernel arguments by value, filled by rm_api.cpp and read by the kernels: their layout
+// is an ABI between the two.  The sizes, and where the first member behind the vectors starts, as they were when every block
+// spelled the four vectors out.
+static_assert(sizeof(RmLattice) == 96, "the lattice's four vectors");
+static_assert(sizeof(RmFieldArgs) == 152 && offsetof(RmFieldArgs, dist) == 96, "RmFieldArgs layout");
+static_assert(sizeof(RmSharpArgs) == 176 && offsetof(RmSharpArgs, iso) == 96, "RmSharpArgs layout");
+static_assert(sizeof(RmMeshArgs) == 200 && offsetof(RmMeshArgs, values) == 96, "RmMeshArgs layout");
+static_assert(sizeof(RmBlocksArgs) == 184 && offsetof(RmBlocksArgs, iso) == 96, "RmBlocksArgs layout");
+static_assert(sizeof(RmTilesArgs) == 168 && offsetof(RmTilesArgs, list) == 96, "RmTilesArgs layout");
+static_assert(sizeof(RmSparseMeshArgs) == 232 && offsetof(RmSparseMeshArgs, iso) == 96, "RmSparseMeshArgs layout");
+
 // rm_scene_build.hip.  elem_bytes: 2 (uint16_t lists: the two grids) or 1 (uint8_t: octree sub-cells)
 hipError_t rm_launch_cand_count(const RmCandArgs &a, hipStream_t stream);
 hipError_t rm_launch_cand_fill(const RmCandArgs &a, void *list, int elem_bytes, hipStream_t stream);
@@ -457,19 +486,22 @@ hipError_t rm_launch_light_sqrt(const RmRenderParams &p, const RmRays &r, const 
 hipError_t rm_launch_walk(const RmRenderParams &p, const RmRays &r, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_walk_sqrt(const RmRenderParams &p, const RmRays &r, const RmWalkArgs &a, hipStream_t stream, const char **kernel_name);
 
+// The queries that sample the scene at points and have no ray: field, points, sharp vertices, and the sparse mesher's blocks and
+// tiles below.  The five launchers share one prologue (rm_kernels.hip, scene_launch): 256-thread workgroups, the dynamic LDS of
+// rm_launch_distance (no hit-leaf lists) and the parameter block without a run-time specialised kernel or diagnostics --
+// ahead-of-time kernels only.  Each is left with its guard, its grid and the line that names its kernel.
 // Field query (rm_scene_field): Scene.getDistance at the lattice points of a.first .. a.first + a.n, formed on the device
-// (include/rm_raymarch.h has the rule).  field_kernel, the LDS of rm_launch_distance, ahead-of-time kernels only.
+// (include/rm_raymarch.h has the rule; rm_lattice_component above is its text).  field_kernel.
 hipError_t rm_launch_field(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_field_sqrt(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name);
 
 // Point query (rm_scene_points): distance, gradient, object and up to a.snap_steps projection steps for a.n caller-supplied
-// points, one per lane (include/rm_raymarch.h has the rule).  point_kernel, the launch of rm_launch_field, ahead-of-time
-// kernels only; 0 <= a.n <= INT32_MAX.
+// points, one per lane (include/rm_raymarch.h has the rule).  point_kernel; 0 <= a.n <= INT32_MAX.
 hipError_t rm_launch_points(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_points_sqrt(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name);
 
-// Sharp vertices (rm_scene_sharpen): sharp_kernel, one workgroup per RM_SHARP_CELLS vertices, the LDS of rm_launch_field beside
-// its own static arrays, ahead-of-time kernels only; 0 <= a.n <= INT32_MAX.
+// Sharp vertices (rm_scene_sharpen): sharp_kernel, one workgroup per RM_SHARP_CELLS vertices, the prologue's LDS beside its own
+// static arrays; 0 <= a.n <= INT32_MAX.
 hipError_t rm_launch_sharp(const RmRenderParams &p, const RmSharpArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_sharp_sqrt(const RmRenderParams &p, const RmSharpArgs &a, hipStream_t stream, const char **kernel_name);
 

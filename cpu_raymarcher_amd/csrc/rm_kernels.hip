@@ -1300,16 +1300,21 @@ __global__ __launch_bounds__(256) void distance_kernel(const RmRenderParams P, c
 // GEN>, ...) and those of the exact field (field_exact_kernel<GEN>, ...: ACCEL = RM_ACCEL_EXACT, sphere and primitive records
 // only -- expression programs have no tree to walk and run the acceleration-None instantiation, which evaluates every object)
 // instantiate them.
+
+// The lattice's point with index (fi, fj, fk): the rule's three components (rm_kernels.h, rm_lattice_component), each rounded
+// once to binary32.  What the field, block, tile and sharp-vertex kernels evaluate the scene at.
+__device__ __forceinline__ Vec3f lattice_point(const RmLattice &l, double fi, double fj, double fk) {
+    return Vec3f{static_cast<float>(rm_lattice_component(l, 0, fi, fj, fk)), static_cast<float>(rm_lattice_component(l, 1, fi, fj, fk)),
+                 static_cast<float>(rm_lattice_component(l, 2, fi, fj, fk))};
+}
+
 template <int ACCEL, int GEN>
 __device__ __forceinline__ void field_body(const RmRenderParams &P, const RmFieldArgs &A) {
     const unsigned long long r = ((static_cast<unsigned long long>(A.block_first) + blockIdx.x) << 8) + threadIdx.x;
     if (r >= static_cast<unsigned long long>(A.n)) return;
     const unsigned long long l = static_cast<unsigned long long>(A.first) + r, row = l / A.nu, k = row / A.nv;
     const double fi = static_cast<double>(l - row * A.nu), fj = static_cast<double>(row - k * A.nv), fk = static_cast<double>(k);
-    Vec3f p;
-    p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
-    p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
-    p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+    const Vec3f p = lattice_point(A.lat, fi, fj, fk);
     uint32_t c = 0;
     const double d = scene_distance<ACCEL, GEN>(P, p, c);
     if (A.dist) A.dist[r] = d;
@@ -1524,10 +1529,7 @@ __global__ __launch_bounds__(256) void blocks_kernel(const RmRenderParams P, con
         const unsigned int row = b / A.nbu, bx = b - row * A.nbu, bz = row / A.nbv, by = row - bz * A.nbv;
         const double fi = static_cast<double>(min(8u * bx + 4u, A.nu - 1u)), fj = static_cast<double>(min(8u * by + 4u, A.nv - 1u)),
                      fk = static_cast<double>(min(8u * bz + 4u, A.nw - 1u));
-        Vec3f p;
-        p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
-        p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
-        p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+        const Vec3f p = lattice_point(A.lat, fi, fj, fk);
         uint32_t c = 0;
         const double d = WALK ? bvh_exact_distance<GEN>(P, p) : all_prims_distance<GEN>(P, p, c);
         keep = !(__builtin_fabs(d - A.iso) > A.bound);  // a NaN distance keeps the block
@@ -1571,10 +1573,7 @@ __device__ __forceinline__ void tiles_body(const RmRenderParams &P, const RmTile
         __shared__ int32_t s_list[RM_EXACT_LIST_CAP];
         __shared__ int s_n, s_over;
         const double fi = static_cast<double>(8u * bx + 4u), fj = static_cast<double>(8u * by + 4u), fk = static_cast<double>(8u * bz + 4u);
-        Vec3f c;
-        c.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
-        c.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
-        c.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+        const Vec3f c = lattice_point(A.lat, fi, fj, fk);
         // (uniform; a centre beyond the lattice's last point may overflow binary32 where the lattice's own points do not: no list then)
         if (P.bvh_nodes > 0 && c.x - c.x == 0.f && c.y - c.y == 0.f && c.z - c.z == 0.f) {
             uint32_t unused = 0;
@@ -1634,10 +1633,7 @@ __device__ __forceinline__ void tiles_body(const RmRenderParams &P, const RmTile
         double d = __longlong_as_double(0x7FF8000000000000ll);
         if (i < A.nu && j < A.nv && k < A.nw) {
             const double fi = static_cast<double>(i), fj = static_cast<double>(j), fk = static_cast<double>(k);
-            Vec3f p;
-            p.x = static_cast<float>(((A.origin[0] + fi * A.du[0]) + fj * A.dv[0]) + fk * A.dw[0]);
-            p.y = static_cast<float>(((A.origin[1] + fi * A.du[1]) + fj * A.dv[1]) + fk * A.dw[1]);
-            p.z = static_cast<float>(((A.origin[2] + fi * A.du[2]) + fj * A.dv[2]) + fk * A.dw[2]);
+            const Vec3f p = lattice_point(A.lat, fi, fj, fk);
             uint32_t c = 0;
             if (from_list) d = list_min<GEN>(P, cand, n_list, p, RM_MAX_DIST);
             else d = scene_distance<ACCEL, GEN>(P, p, c);
@@ -1657,10 +1653,10 @@ __global__ __launch_bounds__(256) void tiles_exact_kernel(const RmRenderParams P
 // ------------------------------------------------------------------ point queries (rm_scene_points)
 //
 // Distance, gradient, object and projection onto the surface for caller-supplied points (include/rm_raymarch.h has the rule):
-// one point per lane, in input order, the field query's launch.  A visit of a point is Scene.getDistance there and -- when a
-// step or the normal is wanted -- getNormal's three further evaluations; the loop below is that visit, so the distance
-// evaluation and the gradient have ONE call site each however many steps a lane takes (a copy of scene_distance per use would
-// multiply the kernel as it would have light_body's marcher).  The last visit's gradient is the normal: a loop that ends on a
+// one point per lane, in input order, the launch of every query without a ray (scene_launch).  A visit of a point is
+// Scene.getDistance there and -- when a step or the normal is wanted -- getNormal's three further evaluations; the loop below
+// is that visit, so the distance evaluation and the gradient have ONE call site each however many steps a lane takes (a copy
+// of scene_distance per use would multiply the kernel as it would have light_body's marcher).  The last visit's gradient is the normal: a loop that ends on a
 // zero gradient has it already.  Lanes that converge early idle until their wave's last lane has: neighbouring points of a
 // mesh or a hit buffer take about the same number of steps, and compacting them would cost a pass through memory.  A lane
 // reads its point before it writes anything, so A.position may be A.points.
@@ -1739,10 +1735,6 @@ __device__ __forceinline__ SharpCell sharp_locate(const RmSharpArgs &A, long lon
     c.exists = c.i + 1u < A.nu && c.j + 1u < A.nv && c.k + 1u < A.nw;
     return c;
 }
-// component c of the lattice's point rule at a fractional index, before its rounding
-__device__ __forceinline__ double sharp_component(const RmSharpArgs &A, int c, double fi, double fj, double fk) {
-    return ((A.origin[c] + fi * A.du[c]) + fj * A.dv[c]) + fk * A.dw[c];
-}
 __device__ __forceinline__ bool sharp_finite(double x) { return x - x == 0.0; }
 __device__ __forceinline__ bool sharp_finite(float x) { return x - x == 0.f; }
 // one Jacobi rotation of the symmetric a and of the rows of V in the plane (p, q); r is the third index
@@ -1804,8 +1796,7 @@ __device__ __forceinline__ void sharp_body(const RmRenderParams &P, const RmShar
             if (c.exists) {
                 const double fi = static_cast<double>(c.i + (corner & 1u)), fj = static_cast<double>(c.j + ((corner >> 1) & 1u)),
                              fk = static_cast<double>(c.k + (corner >> 2));
-                const Vec3f p{static_cast<float>(sharp_component(A, 0, fi, fj, fk)), static_cast<float>(sharp_component(A, 1, fi, fj, fk)),
-                              static_cast<float>(sharp_component(A, 2, fi, fj, fk))};
+                const Vec3f p = lattice_point(A.lat, fi, fj, fk);
                 uint32_t n = 0;
                 d = scene_distance<ACCEL, GEN>(P, p, n);
                 atomicAdd(&s_count[cell], n);
@@ -1871,8 +1862,7 @@ __device__ __forceinline__ void sharp_body(const RmRenderParams &P, const RmShar
         for (int it = 0;; ++it) {  // R refinements of the bracket, then the crossing itself
             const double t = tl + (A.iso - fl) * (th - tl) / (fh - fl);
             const double fi = ax == 0u ? bi + t : bi, fj = ax == 1u ? bj + t : bj, fk = ax == 2u ? bk + t : bk;
-            p = Vec3f{static_cast<float>(sharp_component(A, 0, fi, fj, fk)), static_cast<float>(sharp_component(A, 1, fi, fj, fk)),
-                      static_cast<float>(sharp_component(A, 2, fi, fj, fk))};
+            p = lattice_point(A.lat, fi, fj, fk);
             if (!(sharp_finite(t) && sharp_finite(p.x) && sharp_finite(p.y) && sharp_finite(p.z))) {
                 alive = false;
                 break;
@@ -1913,7 +1903,9 @@ __device__ __forceinline__ void sharp_body(const RmRenderParams &P, const RmShar
     int32_t feature = -1;
     if (c.exists) {
         const double fi = static_cast<double>(c.i) + 0.5, fj = static_cast<double>(c.j) + 0.5, fk = static_cast<double>(c.k) + 0.5;
-        const double centre[3] = {sharp_component(A, 0, fi, fj, fk), sharp_component(A, 1, fi, fj, fk), sharp_component(A, 2, fi, fj, fk)};
+        // (the rule's components before their rounding: the solve is binary64 around the cell's centre)
+        const double centre[3] = {rm_lattice_component(A.lat, 0, fi, fj, fk), rm_lattice_component(A.lat, 1, fi, fj, fk),
+                                  rm_lattice_component(A.lat, 2, fi, fj, fk)};
         x[0] = centre[0];
         x[1] = centre[1];
         x[2] = centre[2];
@@ -2329,6 +2321,39 @@ V1Lds v1_lds_layout(const RmRenderParams &p, int threads, bool lists) {
     }
     return l;
 }
+
+// What the launch of a ray query is, whichever kernel it names: nothing without a ray (grid.x 0), else one lane per ray in
+// 256-thread workgroups, the LDS of the one-ray-per-lane render launch -- so every march of a lane is a render's -- and the
+// parameter block without a run-time specialised kernel (the ray queries are ahead-of-time only) or diagnostics.
+struct RayLaunch {
+    dim3 grid, block;
+    size_t shmem;
+    RmRenderParams pl;
+};
+RayLaunch ray_launch(const RmRenderParams &p, long long n) {
+    const int threads = 256;
+    const V1Lds lds = v1_lds_layout(p, threads, true);
+    RayLaunch l{dim3(n > 0 ? static_cast<unsigned>((n + threads - 1) / threads) : 0u), dim3(threads), lds.bytes, p};
+    l.pl.rtc_function = nullptr;
+    l.pl.diag_block = nullptr;
+    l.pl.diag_out = nullptr;
+    l.pl.v1_list_offset = lds.v1_list_offset;
+    return l;
+}
+// What the launch of a query without a ray is (field, blocks, tiles, points, sharp vertices), whichever kernel it names: the
+// dynamic LDS of a 256-thread workgroup without hit-leaf lists -- a point has no ray -- and the parameter block without a
+// run-time specialised kernel or diagnostics.  The grid is the launcher's: each family counts its workgroups its own way.
+struct SceneLaunch {
+    size_t shmem;
+    RmRenderParams pl;
+};
+SceneLaunch scene_launch(const RmRenderParams &p) {
+    SceneLaunch l{v1_lds_layout(p, 256, false).bytes, p};
+    l.pl.rtc_function = nullptr;
+    l.pl.diag_block = nullptr;
+    l.pl.diag_out = nullptr;
+    return l;
+}
 }  // namespace
 
 // RM_DISPATCH(K): K(ACCEL, OTHER, GEN) for the instantiation the parameter block `p` in scope selects (accel, algorithm, general).
@@ -2336,20 +2361,20 @@ V1Lds v1_lds_layout(const RmRenderParams &p, int threads, bool lists) {
 #define RM_DISPATCH_O(K, G) { if (p.algorithm == 0) RM_DISPATCH_A(K, false, G) else RM_DISPATCH_A(K, true, G) }
 #define RM_DISPATCH(K) { if (p.general == 3) RM_DISPATCH_O(K, 3) else if (p.general == 2) RM_DISPATCH_O(K, 2) else if (p.general) RM_DISPATCH_O(K, 1) else RM_DISPATCH_O(K, 0) }
 #define RM_KERNEL_NAME(kernel, A, O, G) #kernel "<" #A ", " #O ", " #G ">" RM_LEN_TAG
-// The point, field and tile launches of option `exact` (p.accel == RM_ACCEL_EXACT), with grid, block, shmem, stream and
-// kernel_name in scope: <name>_exact_kernel<GEN> for sphere and primitive records; expression programs have no tree to walk and
-// run <name>_kernel<0, GEN>, which evaluates every object.  rm_last_kernel reports "<name>_kernel<EXACT, GEN>" for all of them.
+// The point, field, tile and sharp-vertex launches of option `exact` (p.accel == RM_ACCEL_EXACT), with grid, block, the
+// SceneLaunch `l`, stream and kernel_name in scope: exact_kernel<GEN> for sphere and primitive records; expression programs have
+// no tree to walk and run kernel<0, GEN>, which evaluates every object.  rm_last_kernel reports "kernel<EXACT, GEN>" for all of them.
 #define RM_EXACT_ONE(label, KERNEL, G, ...)                                          \
     {                                                                                \
-        hipLaunchKernelGGL(KERNEL, grid, block, shmem, stream, __VA_ARGS__);         \
+        hipLaunchKernelGGL(KERNEL, grid, block, l.shmem, stream, __VA_ARGS__);       \
         if (kernel_name) *kernel_name = label "<EXACT, " #G ">" RM_LEN_TAG;          \
     }
-#define RM_LAUNCH_EXACT(name, ...)                                                                             \
-    {                                                                                                          \
-        if (p.general == 3) RM_EXACT_ONE(#name "_kernel", (name##_kernel<0, 3>), 3, __VA_ARGS__)               \
-        else if (p.general == 2) RM_EXACT_ONE(#name "_kernel", (name##_kernel<0, 2>), 2, __VA_ARGS__)          \
-        else if (p.general) RM_EXACT_ONE(#name "_kernel", (name##_exact_kernel<1>), 1, __VA_ARGS__)            \
-        else RM_EXACT_ONE(#name "_kernel", (name##_exact_kernel<0>), 0, __VA_ARGS__)                           \
+#define RM_LAUNCH_EXACT(kernel, exact_kernel, ...)                                                 \
+    {                                                                                              \
+        if (p.general == 3) RM_EXACT_ONE(#kernel, (kernel<0, 3>), 3, __VA_ARGS__)                  \
+        else if (p.general == 2) RM_EXACT_ONE(#kernel, (kernel<0, 2>), 2, __VA_ARGS__)             \
+        else if (p.general) RM_EXACT_ONE(#kernel, (exact_kernel<1>), 1, __VA_ARGS__)               \
+        else RM_EXACT_ONE(#kernel, (exact_kernel<0>), 0, __VA_ARGS__)                              \
     }
 
 hipError_t RM_LEN_VARIANT(rm_launch_render)(const RmRenderParams &p, hipStream_t stream, const char **kernel_name, uint32_t *v2_shape) {
@@ -2472,7 +2497,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
                               hipStream_t stream) {
     if (n <= 0) return hipSuccess;
     const dim3 grid(static_cast<unsigned>((n + 255) / 256)), block(256);
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // (a point has no ray: no hit-leaf lists)
+    const size_t shmem = scene_launch(p).shmem;  // (its LDS only: this launch keeps p.rtc_function, the branch below)
     if (p.rtc_function) {  // rm_rtc_distance(RmRenderParams, const float *, int64_t, double *, uint32_t *)
         struct Args {
             RmRenderParams p;
@@ -2495,23 +2520,19 @@ hipError_t RM_LEN_VARIANT(rm_launch_distance)(const RmRenderParams &p, const flo
 hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFieldArgs &a, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "";
     if (a.n <= 0 || a.nu == 0 || a.nv == 0) return hipSuccess;
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_distance: a point has no ray
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
+    const SceneLaunch l = scene_launch(p);
     RmFieldArgs al = a;
     const long long blocks = (a.n + 255) / 256;
     for (long long done = 0; done < blocks; done += 1ll << 22) {  // one grid dimension: at most 2^22 workgroups (2^30 points) a launch
         const long long m = blocks - done < (1ll << 22) ? blocks - done : (1ll << 22);
         const dim3 grid(static_cast<unsigned>(m)), block(256);
         al.block_first = done;
-#define RM_FLDK(A, O, G)                                                              \
-    {                                                                                 \
-        hipLaunchKernelGGL((field_kernel<A, G>), grid, block, shmem, stream, pl, al); \
-        if (kernel_name) *kernel_name = "field_kernel<" #A ", " #G ">" RM_LEN_TAG;    \
+#define RM_FLDK(A, O, G)                                                                    \
+    {                                                                                       \
+        hipLaunchKernelGGL((field_kernel<A, G>), grid, block, l.shmem, stream, l.pl, al);   \
+        if (kernel_name) *kernel_name = "field_kernel<" #A ", " #G ">" RM_LEN_TAG;          \
     }
-        if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(field, pl, al)
+        if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(field_kernel, field_exact_kernel, l.pl, al)
         else RM_DISPATCH(RM_FLDK)
 #undef RM_FLDK
         const hipError_t e = hipGetLastError();
@@ -2523,17 +2544,13 @@ hipError_t RM_LEN_VARIANT(rm_launch_field)(const RmRenderParams &p, const RmFiel
 hipError_t RM_LEN_VARIANT(rm_launch_blocks)(const RmRenderParams &p, const RmBlocksArgs &a, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "";
     if (a.n_blocks == 0 || a.n_blocks > RM_SPARSE_MAX_BLOCKS || a.n_groups != (a.n_blocks + 255u) / 256u) return hipErrorInvalidValue;
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
+    const SceneLaunch l = scene_launch(p);
     const dim3 grid(a.n_groups), block(256);
     // the pruned walk where there is a tree of boxes around sphere or primitive records; every object otherwise
     const bool walk = p.accel == 2 && p.general < 2 && p.bvh_nodes > 0;
 #define RM_BLK(G, W)                                                                   \
     {                                                                                  \
-        hipLaunchKernelGGL((blocks_kernel<G, W>), grid, block, shmem, stream, pl, a);   \
+        hipLaunchKernelGGL((blocks_kernel<G, W>), grid, block, l.shmem, stream, l.pl, a); \
         if (kernel_name) *kernel_name = "blocks_kernel<" #G ", " #W ">" RM_LEN_TAG;    \
     }
     if (p.general == 3) RM_BLK(3, false)
@@ -2552,18 +2569,14 @@ hipError_t RM_LEN_VARIANT(rm_launch_blocks)(const RmRenderParams &p, const RmBlo
 hipError_t RM_LEN_VARIANT(rm_launch_tiles)(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "";
     if (a.n_kept == 0 || a.n_kept > RM_SPARSE_MAX_BLOCKS) return hipErrorInvalidValue;
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
+    const SceneLaunch l = scene_launch(p);
     const dim3 grid(a.n_kept), block(256);
-#define RM_TLK(A, O, G)                                                              \
-    {                                                                                \
-        hipLaunchKernelGGL((tiles_kernel<A, G>), grid, block, shmem, stream, pl, a);  \
-        if (kernel_name) *kernel_name = "tiles_kernel<" #A ", " #G ">" RM_LEN_TAG;   \
+#define RM_TLK(A, O, G)                                                                  \
+    {                                                                                    \
+        hipLaunchKernelGGL((tiles_kernel<A, G>), grid, block, l.shmem, stream, l.pl, a); \
+        if (kernel_name) *kernel_name = "tiles_kernel<" #A ", " #G ">" RM_LEN_TAG;       \
     }
-    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(tiles, pl, a)
+    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(tiles_kernel, tiles_exact_kernel, l.pl, a)
     else RM_DISPATCH(RM_TLK)
 #undef RM_TLK
     return hipGetLastError();
@@ -2572,18 +2585,14 @@ hipError_t RM_LEN_VARIANT(rm_launch_tiles)(const RmRenderParams &p, const RmTile
 hipError_t RM_LEN_VARIANT(rm_launch_points)(const RmRenderParams &p, const RmPointArgs &a, hipStream_t stream, const char **kernel_name) {
     if (kernel_name) *kernel_name = "";
     if (a.n <= 0) return hipSuccess;
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
+    const SceneLaunch l = scene_launch(p);
     const dim3 grid(static_cast<unsigned>((a.n + 255) / 256)), block(256);  // (a.n <= INT32_MAX: one grid dimension)
-#define RM_PTK(A, O, G)                                                             \
-    {                                                                               \
-        hipLaunchKernelGGL((point_kernel<A, G>), grid, block, shmem, stream, pl, a); \
-        if (kernel_name) *kernel_name = "point_kernel<" #A ", " #G ">" RM_LEN_TAG;  \
+#define RM_PTK(A, O, G)                                                                  \
+    {                                                                                    \
+        hipLaunchKernelGGL((point_kernel<A, G>), grid, block, l.shmem, stream, l.pl, a); \
+        if (kernel_name) *kernel_name = "point_kernel<" #A ", " #G ">" RM_LEN_TAG;       \
     }
-    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(point, pl, a)
+    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(point_kernel, point_exact_kernel, l.pl, a)
     else RM_DISPATCH(RM_PTK)
 #undef RM_PTK
     return hipGetLastError();
@@ -2593,49 +2602,21 @@ hipError_t RM_LEN_VARIANT(rm_launch_sharp)(const RmRenderParams &p, const RmShar
     if (kernel_name) *kernel_name = "";
     if (a.n <= 0) return hipSuccess;
     if (a.refine < 0 || a.refine > 8) return hipErrorInvalidValue;
-    const size_t shmem = v1_lds_layout(p, 256, false).bytes;  // as rm_launch_field: a point has no ray
-    RmRenderParams pl = p;
-    pl.rtc_function = nullptr;
-    pl.diag_block = nullptr;
-    pl.diag_out = nullptr;
+    const SceneLaunch l = scene_launch(p);
     const dim3 grid(static_cast<unsigned>((a.n + RM_SHARP_CELLS - 1) / RM_SHARP_CELLS)), block(256);  // (a.n <= INT32_MAX: one grid dimension)
-#define RM_SHK(A, O, G)                                                             \
-    {                                                                               \
-        hipLaunchKernelGGL((sharp_kernel<A, G>), grid, block, shmem, stream, pl, a); \
-        if (kernel_name) *kernel_name = "sharp_kernel<" #A ", " #G ">" RM_LEN_TAG;  \
+#define RM_SHK(A, O, G)                                                                  \
+    {                                                                                    \
+        hipLaunchKernelGGL((sharp_kernel<A, G>), grid, block, l.shmem, stream, l.pl, a); \
+        if (kernel_name) *kernel_name = "sharp_kernel<" #A ", " #G ">" RM_LEN_TAG;       \
     }
-    if (p.accel == RM_ACCEL_EXACT) {  // RM_LAUNCH_EXACT's choice, with this family's kernel names
-        if (p.general == 3) RM_EXACT_ONE("sharp_kernel", (sharp_kernel<0, 3>), 3, pl, a)
-        else if (p.general == 2) RM_EXACT_ONE("sharp_kernel", (sharp_kernel<0, 2>), 2, pl, a)
-        else if (p.general) RM_EXACT_ONE("sharp_kernel", (sharp_kernel_exact<1>), 1, pl, a)
-        else RM_EXACT_ONE("sharp_kernel", (sharp_kernel_exact<0>), 0, pl, a)
-    } else RM_DISPATCH(RM_SHK)
+    if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(sharp_kernel, sharp_kernel_exact, l.pl, a)
+    else RM_DISPATCH(RM_SHK)
 #undef RM_SHK
     return hipGetLastError();
 }
 
-namespace {
-// What the launch of a ray query is, whichever kernel it names: nothing without a ray (grid.x 0), else one lane per ray in
-// 256-thread workgroups, the LDS of the one-ray-per-lane render launch -- so every march of a lane is a render's -- and the
-// parameter block without a run-time specialised kernel (the ray queries are ahead-of-time only) or diagnostics.
-struct RayLaunch {
-    dim3 grid, block;
-    size_t shmem;
-    RmRenderParams pl;
-};
-RayLaunch ray_launch(const RmRenderParams &p, long long n) {
-    const int threads = 256;
-    const V1Lds lds = v1_lds_layout(p, threads, true);
-    RayLaunch l{dim3(n > 0 ? static_cast<unsigned>((n + threads - 1) / threads) : 0u), dim3(threads), lds.bytes, p};
-    l.pl.rtc_function = nullptr;
-    l.pl.diag_block = nullptr;
-    l.pl.diag_out = nullptr;
-    l.pl.v1_list_offset = lds.v1_list_offset;
-    return l;
-}
-}  // namespace
-// What is left per family: the line that names its kernel and hands it its arguments where the kernel reads them (RmRays `r`,
-// the block `a`, RayLaunch `l`, `stream` and `kernel_name` in scope).
+// The ray queries (ray_launch, above).  What is left per family: the line that names its kernel and hands it its arguments
+// where the kernel reads them (RmRays `r`, the block `a`, RayLaunch `l`, `stream` and `kernel_name` in scope).
 #define RM_RAY_K(kernel, A, O, G, ...)                                                              \
     {                                                                                               \
         hipLaunchKernelGGL((kernel<A, O, G>), l.grid, l.block, l.shmem, stream, l.pl, __VA_ARGS__); \

@@ -112,7 +112,8 @@ __global__ __launch_bounds__(kScan) void mesh_scan_kernel(uint32_t *totals, unsi
 
 // The vertex of an active cell: the mean of its edge crossings in the order of the rule (axis 0, 1, 2; within an axis the low
 // end's offsets on the other two axes (0,0), (1,0), (0,1), (1,1), the lower-numbered axis first), then the lattice's point rule
-// with the fractional index.  binary64, one operation at a time (-ffp-contract=off), one rounding to binary32.
+// (rm_kernels.h, rm_lattice_component) with the fractional index.  binary64, one operation at a time (-ffp-contract=off), one
+// rounding to binary32.
 template <typename ARGS>
 __device__ __forceinline__ void vertex_position(const ARGS &a, const Cell &c, const double (&v)[8], float out[3]) {
     double sum[3] = {0.0, 0.0, 0.0};
@@ -139,7 +140,7 @@ __device__ __forceinline__ void vertex_position(const ARGS &a, const Cell &c, co
     const double fi = static_cast<double>(c.i) + sum[0] / count, fj = static_cast<double>(c.j) + sum[1] / count,
                  fk = static_cast<double>(c.k) + sum[2] / count;
 #pragma unroll
-    for (int n = 0; n < 3; ++n) out[n] = static_cast<float>(((a.origin[n] + fi * a.du[n]) + fj * a.dv[n]) + fk * a.dw[n]);
+    for (int n = 0; n < 3; ++n) out[n] = static_cast<float>(rm_lattice_component(a.lat, n, fi, fj, fk));
 }
 
 }  // namespace

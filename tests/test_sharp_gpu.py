@@ -224,6 +224,33 @@ def test_feature_and_count_are_optional(rm, sctx, rotated_box):
             assert same(dev[2].cpu().numpy().view(np.uint32), full.count)
 
 
+def test_a_host_batch_crosses_the_chunk_of_the_host_form(rm, sctx):
+    """2^22 + 65 keys -- the active cells of a 17^3 lattice around the Sphere preset, repeated --, position and feature only: the
+    host form takes 2^22 at a time, and the second trip ends in a partial workgroup of RM_SHARP_CELLS = 64 vertices."""
+    import torch
+    N = rm._native
+    sctx.scene_from_preset(0, NONE)
+    lat = cube(17, 2.0)
+    active = lattice_cells(sctx, lat)
+    assert len(active) > 100
+    chunk, n = 1 << 22, (1 << 22) + 65
+    keys = np.ascontiguousarray(np.resize(active, n), np.int64)
+    l = rm.context.make_lattice(*lat)
+    q = sctx._sharp_query(0.0, 2, 0.1, 1.0)
+    vp = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    pos, feat = np.full((n, 3), np.nan, np.float32), np.full(n, -7, np.int32)
+    N.check(sctx._h, N.lib().rm_scene_sharpen(sctx._h, C.byref(l), C.byref(q), n, vp(keys), vp(pos), vp(feat), None))
+    assert sctx.last_kernel() == "sharp_kernel<0, 0>"
+    d_pos, d_feat, d_cnt = sctx._sharpen_device(l, torch.from_numpy(keys).cuda(), 0.0, 2, 0.1, 1.0, True, False)
+    assert d_cnt is None
+    assert same(pos, d_pos.cpu().numpy()) and same(feat, d_feat.cpu().numpy())
+    assert (feat >= 0).all() and np.isfinite(pos).all()
+    for i in (0, chunk - 1, chunk, n - 1):
+        one_pos, one_feat = np.zeros((1, 3), np.float32), np.zeros(1, np.int32)
+        N.check(sctx._h, N.lib().rm_scene_sharpen(sctx._h, C.byref(l), C.byref(q), 1, vp(keys[i:i + 1]), vp(one_pos), vp(one_feat), None))
+        assert same(one_pos, pos[i:i + 1]) and one_feat[0] == feat[i], i
+
+
 # ------------------------------------------------------------------------------------------------- cells and meshers
 
 def test_mesh_cells_are_the_active_cells_in_vertex_order(rm, sctx):
