@@ -170,6 +170,17 @@ class rm_sphere_edit(C.Structure):  # include/rm_raymarch.h: struct rm_sphere_ed
                 ("radius", C.c_double)]
 
 
+class rm_ball(C.Structure):  # include/rm_raymarch.h: struct rm_ball
+    _fields_ = [("center", C.c_float * 3), ("reserved", C.c_int32), ("radius", C.c_double)]
+
+
+class rm_tiles_update_info(C.Structure):  # include/rm_raymarch.h: struct rm_tiles_update_info
+    _fields_ = [("n_kept", C.c_int64), ("n_reused", C.c_int64), ("n_evaluated", C.c_int64), ("reserved", C.c_int64)]
+
+
+BALL_DTYPE = [("center", "<f4", (3,)), ("reserved", "<i4"), ("radius", "<f8")]  # rm_ball as a numpy record
+RM_TILES_UPDATE_MAX_BALLS = 65536
+
 # rm_edit_op by name, and the element type of every scene table rm_debug_scene_table names
 RM_EDIT_SET, RM_EDIT_INSERT, RM_EDIT_REMOVE = 0, 1, 2
 EDIT_OPS = {"set": 0, "insert": 1, "remove": 2}
@@ -228,6 +239,8 @@ SIGNATURES = {
     "rm_lattice_blocks": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(C.c_int32)]),
     "rm_scene_blocks_device": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, _VP, _VP, _VP, _VP]),
     "rm_scene_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int64, _VP, _VP]),
+    "rm_scene_edit_balls": (C.c_int, [_VP, C.POINTER(rm_sphere_edit), C.c_int32, C.POINTER(rm_ball), C.c_int32, C.POINTER(C.c_int32)]),
+    "rm_scene_tiles_update_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, C.c_int64, _VP, C.c_int32, _VP, C.c_int64, _VP, _VP, _VP, _VP]),
     "rm_mesh_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, C.c_int64, _VP, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
                                        _VP, _VP]),
     "rm_scene_mesh_sparse": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,

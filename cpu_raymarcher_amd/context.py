@@ -289,19 +289,33 @@ class Context:
         sequence of (op, index) for "remove" and (op, index, centre[3], radius) for "set" / "insert"; op a name of
         N.EDIT_OPS or an rm_edit_op value; or a ready array of N.rm_sphere_edit.  Indices are object indices at the moment
         each edit applies.  All or nothing."""
-        if isinstance(edits, C.Array) and edits._type_ is N.rm_sphere_edit:
-            arr, n = edits, len(edits)
-        else:
-            edits = list(edits)
-            n = len(edits)
-            arr = (N.rm_sphere_edit * max(1, n))()
-            for k, e in enumerate(edits):
-                arr[k].op = N.EDIT_OPS[e[0]] if isinstance(e[0], str) else int(e[0])
-                arr[k].index = int(e[1])
-                if len(e) > 2:
-                    arr[k].center[:] = [float(v) for v in np.asarray(e[2], np.float32).reshape(3)]
-                    arr[k].radius = float(e[3])
+        arr, n = self._edit_array(edits)
         N.check(self._h, N.lib().rm_scene_edit_spheres(self._h, arr, n))
+
+    @staticmethod
+    def _edit_array(edits):
+        if isinstance(edits, C.Array) and edits._type_ is N.rm_sphere_edit:
+            return edits, len(edits)
+        edits = list(edits)
+        n = len(edits)
+        arr = (N.rm_sphere_edit * max(1, n))()
+        for k, e in enumerate(edits):
+            arr[k].op = N.EDIT_OPS[e[0]] if isinstance(e[0], str) else int(e[0])
+            arr[k].index = int(e[1])
+            if len(e) > 2:
+                arr[k].center[:] = [float(v) for v in np.asarray(e[2], np.float32).reshape(3)]
+                arr[k].radius = float(e[3])
+        return arr, n
+
+    def edit_balls(self, edits):
+        """The balls of an edit list (rm_scene_edit_balls; host-only): for every sphere version the edits remove or add, its
+        centre and radius, in edit order -- what rm_scene_tiles_update_device needs to know of the edit.  Call it BEFORE
+        edit_spheres with the same list; it changes nothing.  Returns a numpy record array of N.BALL_DTYPE."""
+        arr, n = self._edit_array(edits)
+        count = C.c_int32(0)
+        out = np.zeros(2 * n, N.BALL_DTYPE)
+        N.check(self._h, N.lib().rm_scene_edit_balls(self._h, arr, n, out.ctypes.data_as(C.POINTER(N.rm_ball)) if n else None, 2 * n, C.byref(count)))
+        return out[:count.value]
 
     def scene_table(self, name, from_device=True):
         """One table of the active scene (rm_debug_scene_table) as a numpy array of N.SCENE_TABLES[name] (records as
@@ -1131,11 +1145,16 @@ class Context:
         slot = torch.empty(room, dtype=torch.int32, device=dev)
         lst = torch.empty(room, dtype=torch.int32, device=dev)
         d = torch.empty(room, dtype=torch.float64, device=dev) if dist else None
-        info = torch.zeros(4, dtype=torch.int64, device=dev)
+        n_kept = self._sparse_blocks_into(lat, iso, lipschitz, slot, lst, d)
+        return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
+
+    def _sparse_blocks_into(self, lat, iso, lipschitz, slot, lst, d=None):
+        """The coarse pass into the caller's buffers -> n_kept."""
+        import torch
+        info = torch.zeros(4, dtype=torch.int64, device=slot.device)
         N.check(self._h, N.lib().rm_scene_blocks_device(self._h, C.byref(lat), float(iso), float(lipschitz), _ptr(slot), _ptr(lst), _ptr(d),
                                                         _ptr(info), _current_stream_ptr()))
-        n_kept = int(info.cpu()[1])
-        return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
+        return int(info.cpu()[1])
 
     def mesh_sparse(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, order="dense", device=False, triangles=False,
                     attributes=False, snap=0, tol=1e-4, exact=False, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
@@ -1165,10 +1184,17 @@ class Context:
         tiles = torch.empty((k, 729), dtype=torch.float64, device=dev)
         N.check(self._h, N.lib().rm_scene_tiles_device(self._h, C.byref(lat), _ptr(blocks.list) if k else None, k, _ptr(tiles) if k else None,
                                                        _current_stream_ptr()))
+        return self._mesh_tiles(lat, blocks.slot, blocks.list, k, tiles, iso, time, order, device, triangles, attributes, snap, tol, sharp)
+
+    def _mesh_tiles(self, lat, slot, lst, k, tiles, iso, time, order, device, triangles, attributes, snap, tol, sharp=None):
+        """mesh_sparse from the tiles onward (rm_mesh_tiles_device: the counting call, an exact allocation, the filling call):
+        slot int32 [n_blocks], lst and tiles hold k kept blocks at least.  What `mesh_sparse` and a MeshSession share."""
+        import torch
+        dev = torch.device("cuda", self.device)
         info = torch.zeros(4, dtype=torch.int64, device=dev)
 
         def call(v, nv_, q, nq_, c, e):
-            N.check(self._h, N.lib().rm_mesh_tiles_device(self._h, C.byref(lat), _ptr(blocks.slot), _ptr(blocks.list) if k else None, k,
+            N.check(self._h, N.lib().rm_mesh_tiles_device(self._h, C.byref(lat), _ptr(slot), _ptr(lst) if k else None, k,
                                                           _ptr(tiles) if k else None, float(iso), _ptr(v) if nv_ else None, nv_, _ptr(q) if nq_ else None,
                                                           nq_, _ptr(c) if nv_ else None, _ptr(e) if nq_ else None, _ptr(info), _current_stream_ptr()))
         call(None, 0, None, 0, None, None)
@@ -1198,6 +1224,12 @@ class Context:
         if device:
             return out
         return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
+
+    def mesh_session(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0):
+        """A MeshSession over this lattice: the exact sparse mesh of the active scene whose tiles are kept on the device, so
+        that after an edit only the tiles the edit can reach are sampled again (include/rm_raymarch.h, "re-meshing an edited
+        scene")."""
+        return MeshSession(self, origin, du, dv, dw, shape, iso, time, lipschitz)
 
     def mesh_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, device=False, triangles=False, box=None, attributes=False, snap=0,
                  tol=1e-4, sparse=False, lipschitz=1.0, exact=False, sharp=False, refine=2, rank_tol=0.1, reach=1.0):
@@ -1507,3 +1539,108 @@ def partition_rows(height, n_workers, i):
     if rc != N.RM_OK:
         raise N.RmError(rc, "rm_partition_rows")
     return a.value, b.value
+
+
+class MeshSession:
+    """The exact sparse mesh of a context's active scene over one lattice, kept up to date across edits (Context.mesh_session;
+    the rule is in include/rm_raymarch.h, "re-meshing an edited scene").  It owns two sets of (slot, list, tiles) on the
+    device: the current one, which `mesh` reads, and the one the next update writes while it copies from the current one.
+    Everything runs on torch's current stream.  `stats`: the last update's rm_tiles_update_info as a dict (n_kept, n_reused,
+    n_evaluated)."""
+
+    def __init__(self, ctx, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0):
+        if len(tuple(shape)) != 3:
+            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
+        if ctx.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        import torch
+        self.ctx, self.iso, self.time, self.lipschitz = ctx, float(iso), float(time), float(lipschitz)
+        self.lattice = make_lattice(origin, du, dv, dw, shape, time)
+        dims = (C.c_int32 * 3)()
+        rc = N.lib().rm_lattice_blocks(C.byref(self.lattice), dims)
+        if rc != N.RM_OK:
+            raise N.RmError(rc, "rm_lattice_blocks")
+        self.dims = tuple(dims)
+        self.n_blocks = dims[0] * dims[1] * dims[2]
+        dev = torch.device("cuda", ctx.device)
+        room = min(self.n_blocks, 1 << 24)
+        # [slot, list, tiles, n_kept] twice; the tiles grow with the kept set
+        self._sets = [[torch.empty(room, dtype=torch.int32, device=dev), torch.empty(room, dtype=torch.int32, device=dev),
+                       torch.empty((0, 729), dtype=torch.float64, device=dev), 0] for _ in range(2)]
+        self._cur = None  # index of the current set
+        self._info = torch.zeros(4, dtype=torch.int64, device=dev)
+        self.reused = None  # int32 [n_kept]: the last update's flags (1: the tile was copied), on the device
+        self.stats = None
+        self.update(None)
+
+    @property
+    def slot(self):
+        return self._sets[self._cur][0]
+
+    @property
+    def list(self):
+        s = self._sets[self._cur]
+        return s[1][:s[3]]
+
+    @property
+    def tiles(self):
+        s = self._sets[self._cur]
+        return s[2][:s[3]]
+
+    @property
+    def n_kept(self):
+        return self._sets[self._cur][3]
+
+    def update(self, balls=None):
+        """Brings the tiles up to the ACTIVE scene: a fresh coarse pass, then rm_scene_tiles_update_device with `balls` -- a
+        record array of N.BALL_DTYPE (Context.edit_balls), or a sequence of (centre[3], radius) -- that cover every object
+        version the scenes differ by; then the sets swap.  balls=None: every kept block is sampled again (the full exact
+        path: what a caller who changed the scene in ways no ball describes asks for, and what a forest always takes)."""
+        import torch
+        ctx, lat = self.ctx, self.lattice
+        target = 1 - self._cur if self._cur is not None else 0
+        new = self._sets[target]
+        k = ctx._sparse_blocks_into(lat, self.iso, self.lipschitz, new[0], new[1])
+        if new[2].shape[0] < k:
+            new[2] = torch.empty((k + k // 8, 729), dtype=torch.float64, device=new[0].device)
+        new[3] = k
+        stream = _current_stream_ptr()
+        if balls is None or self._cur is None:
+            with ctx._exact(True):
+                N.check(ctx._h, N.lib().rm_scene_tiles_device(ctx._h, C.byref(lat), _ptr(new[1]) if k else None, k, _ptr(new[2]) if k else None,
+                                                              stream))
+            self.reused = torch.zeros(k, dtype=torch.int32, device=new[0].device)
+            self.stats = dict(n_kept=k, n_reused=0, n_evaluated=k)
+        else:
+            if not (isinstance(balls, np.ndarray) and balls.dtype == np.dtype(N.BALL_DTYPE)):
+                rec = np.zeros(len(balls), N.BALL_DTYPE)
+                for i, (centre, radius) in enumerate(balls):
+                    rec[i]["center"], rec[i]["radius"] = np.asarray(centre, np.float32).reshape(3), float(radius)
+                balls = rec
+            n = len(balls)
+            d_balls = torch.from_numpy(np.ascontiguousarray(balls).view(np.uint8).reshape(-1).copy()).to(new[0].device) if n else None
+            old = self._sets[self._cur]
+            self.reused = torch.empty(k, dtype=torch.int32, device=new[0].device)
+            N.check(ctx._h, N.lib().rm_scene_tiles_update_device(
+                ctx._h, C.byref(lat), _ptr(old[0]), _ptr(old[2]) if old[3] else None, old[3], _ptr(d_balls), n, _ptr(new[1]) if k else None, k,
+                _ptr(new[2]) if k else None, _ptr(self.reused) if k else None, _ptr(self._info), stream))
+            info = [int(x) for x in self._info.cpu()]
+            self.stats = dict(n_kept=info[0], n_reused=info[1], n_evaluated=info[2])
+        self._cur = target
+        return self.stats
+
+    def edit_spheres(self, edits):
+        """Context.edit_spheres, then the update with the edits' own balls (Context.edit_balls).  All or nothing as the edit is:
+        a refused edit leaves the scene and the session as they were."""
+        edits = edits if isinstance(edits, C.Array) else list(edits)
+        balls = self.ctx.edit_balls(edits)
+        self.ctx.edit_spheres(edits)
+        return self.update(balls)
+
+    def mesh(self, order="dense", triangles=False, device=False):
+        """The mesh of the current tiles: what Context.mesh_sparse(exact=True) returns for the active scene over the session's
+        lattice, byte for byte, without its coarse pass and its tile pass."""
+        if order not in ("dense", "tile"):
+            raise ValueError("order is 'dense' or 'tile'")
+        s = self._sets[self._cur]
+        return self.ctx._mesh_tiles(self.lattice, s[0], s[1], s[3], s[2], self.iso, self.time, order, device, triangles, False, 0, 1e-4)

@@ -1140,9 +1140,9 @@ int ensure_exact_tree(rm_ctx *ctx) {
 }
 
 // The parameter block of a point, field or tile launch under option `exact`: the exact instantiation and the tree it walks
-// (RM_ACCEL_EXACT, rm_kernels.h).  Without the option the block stays as it is.
-int apply_exact(rm_ctx *ctx, RmRenderParams &p) {
-    if (!ctx->opt_exact) return RM_OK;
+// (RM_ACCEL_EXACT, rm_kernels.h).  Without the option the block stays as it is.  use_exact: the same whatever the option says
+// (rm_scene_tiles_update_device is defined for the exact field only).
+int use_exact(rm_ctx *ctx, RmRenderParams &p) {
     const int rc = ensure_exact_tree(ctx);
     if (rc) return rc;
     p.accel = RM_ACCEL_EXACT;
@@ -1156,6 +1156,7 @@ int apply_exact(rm_ctx *ctx, RmRenderParams &p) {
     p.use_ext = 0;
     return RM_OK;
 }
+int apply_exact(rm_ctx *ctx, RmRenderParams &p) { return ctx->opt_exact ? use_exact(ctx, p) : static_cast<int>(RM_OK); }
 
 
 // makes the scene named by the job the active one (raymarchWorker.ts:37-38)
@@ -2032,10 +2033,8 @@ int launch_blocks(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, doubl
     return RM_OK;
 }
 
-int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream) {
-    RmRenderParams p;
-    fill_scene_query(ctx, lat->time, p);
-    if (const int erc = apply_exact(ctx, p)) return erc;
+// The argument block of a tile launch, the full one and the update
+RmTilesArgs tiles_args(const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles) {
     RmTilesArgs a;
     fill_sparse_lattice(lat, g, a);
     // read by the exact launch only: the coarse pass's bound for a 1-Lipschitz field, and per axis the same four steps and slack
@@ -2046,7 +2045,43 @@ int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const 
     a.list = static_cast<const int32_t *>(d_list);
     a.tiles = static_cast<double *>(d_tiles);
     a.n_kept = static_cast<unsigned int>(n_kept);
+    return a;
+}
+
+int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream) {
+    RmRenderParams p;
+    fill_scene_query(ctx, lat->time, p);
+    if (const int erc = apply_exact(ctx, p)) return erc;
+    const RmTilesArgs a = tiles_args(lat, g, d_list, n_kept, d_tiles);
     RM_HIP(ctx, (ctx->opt_length ? rm_launch_tiles_sqrt : rm_launch_tiles)(p, a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+// rm_scene_tiles_update_device: the exact tile launch with a previous scene's tiles to copy from (rm_kernels.hip,
+// tiles_update_kernel) and, where flags are written, their totals.
+struct TilesUpdateCall {
+    const void *prev_slot, *prev_tiles, *balls;
+    int64_t n_prev_kept;
+    int32_t n_balls;
+    void *reused, *info;  // reused: the caller's flags or scratch, null when neither flags nor totals are asked for
+};
+int launch_tiles_update(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const TilesUpdateCall &c, const void *d_list, int64_t n_kept,
+                        void *d_tiles, hipStream_t stream) {
+    RmRenderParams p;
+    fill_scene_query(ctx, lat->time, p);
+    if (const int erc = use_exact(ctx, p)) return erc;
+    const RmTilesArgs a = tiles_args(lat, g, d_list, n_kept, d_tiles);
+    RmTilesUpdateArgs u;
+    std::memset(&u, 0, sizeof u);
+    u.prev_slot = static_cast<const int32_t *>(c.prev_slot);
+    u.prev_tiles = static_cast<const double *>(c.prev_tiles);
+    u.balls = static_cast<const RmBall *>(c.balls);
+    u.reused = static_cast<int32_t *>(c.reused);
+    u.n_blocks = static_cast<unsigned int>(g.n_blocks);
+    u.n_prev_kept = static_cast<unsigned int>(c.n_prev_kept);
+    u.n_balls = c.n_balls;
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_tiles_update_sqrt : rm_launch_tiles_update)(p, a, u, stream, &ctx->last_kernel));
+    if (c.info) RM_HIP(ctx, rm_launch_tiles_update_totals(u.reused, a.n_kept, static_cast<RmTilesUpdateInfo *>(c.info), stream));
     return RM_OK;
 }
 
@@ -2277,6 +2312,53 @@ int scene_sharpen_call(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_qu
     });
 }
 
+
+// What rm_scene_edit_spheres and rm_scene_edit_balls share: the checks of an edit list in their order -- the list, each edit
+// without the scene, the scene, each index at its turn -- and the edits applied to the active scene's object list `d`.
+// on_ball(centre, radius) takes every sphere version an edit removes (SET, REMOVE) or adds (SET, INSERT), in edit order.
+template <typename OnBall>
+int replay_sphere_edits(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits, SceneDesc &d, OnBall on_ball) {
+    if (n_edits < 0 || (n_edits > 0 && !edits)) return fail(ctx, RM_E_INVALID, "bad edit list");
+    for (int32_t i = 0; i < n_edits; ++i) {  // what can be said of an edit without the scene
+        const rm_sphere_edit &e = edits[i];
+        if (e.op != RM_EDIT_SET && e.op != RM_EDIT_INSERT && e.op != RM_EDIT_REMOVE) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": unknown op");
+        if (e.reserved != 0) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": reserved must be 0");
+        if (e.op != RM_EDIT_REMOVE &&
+            !(std::isfinite(e.center[0]) && std::isfinite(e.center[1]) && std::isfinite(e.center[2]) && std::isfinite(e.radius)))
+            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": non-finite sphere centre or radius");
+    }
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    // the active scene's object list
+    if (ctx->scene_is_uploaded) {
+        if (ctx->uploaded.kind != SceneDesc::kSpheres) return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
+        d.centers = ctx->uploaded.centers;
+        d.radii = ctx->uploaded.radii;
+    } else if (!rmh::preset_spheres(ctx->scene_preset, d.centers, d.radii)) {
+        return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
+    }
+    d.kind = SceneDesc::kSpheres;
+    for (int32_t i = 0; i < n_edits; ++i) {
+        const rm_sphere_edit &e = edits[i];
+        const int64_t n = static_cast<int64_t>(d.radii.size());
+        if (e.index < 0 || e.index > n || (e.op != RM_EDIT_INSERT && e.index == n))
+            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": index out of range");
+        const auto c = d.centers.begin() + 3 * static_cast<std::ptrdiff_t>(e.index);
+        const auto r = d.radii.begin() + e.index;
+        if (e.op != RM_EDIT_INSERT) on_ball(&*c, *r);
+        if (e.op == RM_EDIT_REMOVE) {
+            d.centers.erase(c, c + 3);
+            d.radii.erase(r);
+        } else if (e.op == RM_EDIT_INSERT) {
+            d.centers.insert(c, e.center, e.center + 3);
+            d.radii.insert(r, e.radius);
+        } else {
+            std::copy(e.center, e.center + 3, c);
+            *r = e.radius;
+        }
+        if (e.op != RM_EDIT_REMOVE) on_ball(e.center, e.radius);
+    }
+    return RM_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -2384,46 +2466,30 @@ int rm_scene_from_spheres(rm_ctx *ctx, const float *centers_xyz, const double *r
     return set_uploaded_scene(ctx, std::move(d), accel);
 }
 
+int rm_scene_edit_balls(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits, rm_ball *balls, int32_t cap, int32_t *n_balls) {
+    if (!ctx) return RM_E_INVALID;
+    if (!n_balls || cap < 0 || (cap > 0 && !balls)) return fail(ctx, RM_E_INVALID, "bad ball buffer");
+    *n_balls = 0;
+    SceneDesc d;
+    int32_t n = 0;
+    const int rc = replay_sphere_edits(ctx, edits, n_edits, d, [&](const float *centre, double radius) {
+        if (n < cap) {
+            rm_ball &b = balls[n];
+            std::copy(centre, centre + 3, b.center);
+            b.reserved = 0;
+            b.radius = radius;
+        }
+        ++n;
+    });
+    if (rc) return rc;  // (balls written ahead of a refused index mean nothing)
+    *n_balls = n;
+    return RM_OK;
+}
+
 int rm_scene_edit_spheres(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits) {
     if (!ctx) return RM_E_INVALID;
-    if (n_edits < 0 || (n_edits > 0 && !edits)) return fail(ctx, RM_E_INVALID, "bad edit list");
-    for (int32_t i = 0; i < n_edits; ++i) {  // what can be said of an edit without the scene
-        const rm_sphere_edit &e = edits[i];
-        if (e.op != RM_EDIT_SET && e.op != RM_EDIT_INSERT && e.op != RM_EDIT_REMOVE) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": unknown op");
-        if (e.reserved != 0) return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": reserved must be 0");
-        if (e.op != RM_EDIT_REMOVE &&
-            !(std::isfinite(e.center[0]) && std::isfinite(e.center[1]) && std::isfinite(e.center[2]) && std::isfinite(e.radius)))
-            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": non-finite sphere centre or radius");
-    }
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
-    // the active scene's object list
     SceneDesc d;
-    if (ctx->scene_is_uploaded) {
-        if (ctx->uploaded.kind != SceneDesc::kSpheres) return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
-        d.centers = ctx->uploaded.centers;
-        d.radii = ctx->uploaded.radii;
-    } else if (!rmh::preset_spheres(ctx->scene_preset, d.centers, d.radii)) {
-        return fail(ctx, RM_E_UNSUPPORTED, "the active scene is not a sphere list");
-    }
-    d.kind = SceneDesc::kSpheres;
-    for (int32_t i = 0; i < n_edits; ++i) {
-        const rm_sphere_edit &e = edits[i];
-        const int64_t n = static_cast<int64_t>(d.radii.size());
-        if (e.index < 0 || e.index > n || (e.op != RM_EDIT_INSERT && e.index == n))
-            return fail(ctx, RM_E_INVALID, "edit " + std::to_string(i) + ": index out of range");
-        const auto c = d.centers.begin() + 3 * static_cast<std::ptrdiff_t>(e.index);
-        const auto r = d.radii.begin() + e.index;
-        if (e.op == RM_EDIT_REMOVE) {
-            d.centers.erase(c, c + 3);
-            d.radii.erase(r);
-        } else if (e.op == RM_EDIT_INSERT) {
-            d.centers.insert(c, e.center, e.center + 3);
-            d.radii.insert(r, e.radius);
-        } else {
-            std::copy(e.center, e.center + 3, c);
-            *r = e.radius;
-        }
-    }
+    if (const int bad = replay_sphere_edits(ctx, edits, n_edits, d, [](const float *, double) {})) return bad;
     if (n_edits == 0) return RM_OK;
     // from here on as rm_scene_from_spheres(edited list, same acceleration structure): nothing changes unless the build succeeds
     std::string kernel_name = ctx->last_kernel ? ctx->last_kernel : "";
@@ -3289,6 +3355,53 @@ int rm_scene_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_
     if (!n_kept) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
     return launch_tiles(ctx, lattice, g, d_list, n_kept, d_tiles, static_cast<hipStream_t>(stream));
+}
+
+static_assert(sizeof(rm_ball) == 24 && sizeof(RmBall) == sizeof(rm_ball) && offsetof(rm_ball, radius) == 16, "rm_ball layout");
+static_assert(sizeof(rm_tiles_update_info) == 32 && sizeof(RmTilesUpdateInfo) == sizeof(rm_tiles_update_info), "rm_tiles_update_info layout");
+static_assert(RM_TILES_UPDATE_MAX_BALLS == RM_UPDATE_MAX_BALLS, "the cap on balls");
+
+int rm_scene_tiles_update_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_prev_slot, const void *d_prev_tiles, int64_t n_prev_kept,
+                                 const void *d_balls, int32_t n_balls, const void *d_list, int64_t n_kept, void *d_tiles, void *d_reused, void *d_info,
+                                 void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (n_kept < 0 || n_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, n_blocks]");
+    if (n_prev_kept < 0 || n_prev_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_prev_kept must be in [0, n_blocks]");
+    if (n_balls < 0 || n_balls > RM_TILES_UPDATE_MAX_BALLS) return fail(ctx, RM_E_INVALID, "n_balls must be in [0, 65536]");
+    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
+    if (n_kept > 0 && !d_prev_slot) return fail(ctx, RM_E_INVALID, "null previous slot map");
+    if (n_kept > 0 && n_prev_kept > 0 && !d_prev_tiles) return fail(ctx, RM_E_INVALID, "null previous tiles");
+    if (n_balls > 0 && !d_balls) return fail(ctx, RM_E_INVALID, "null balls");
+    if (misaligned(d_list, 3) || misaligned(d_prev_slot, 3) || misaligned(d_reused, 3))
+        return fail(ctx, RM_E_INVALID, "list, previous slot map and reused must be 4-byte aligned");
+    if (misaligned(d_tiles, 7) || misaligned(d_prev_tiles, 7) || misaligned(d_balls, 7) || misaligned(d_info, 7))
+        return fail(ctx, RM_E_INVALID, "tiles, previous tiles, balls and info must be 8-byte aligned");
+    {  // slots shift when the kept set changes: the update never runs in place
+        const uintptr_t a = reinterpret_cast<uintptr_t>(d_tiles), b = reinterpret_cast<uintptr_t>(d_prev_tiles);
+        const uintptr_t na = static_cast<uintptr_t>(n_kept) * 8 * RM_SPARSE_TILE, nb = static_cast<uintptr_t>(n_prev_kept) * 8 * RM_SPARSE_TILE;
+        if (d_tiles && d_prev_tiles && na && nb && a < b + nb && b < a + na) return fail(ctx, RM_E_INVALID, "tiles and previous tiles overlap");
+    }
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (ctx->host.program) return fail(ctx, RM_E_UNSUPPORTED, "expression-program scenes take the full path: rm_scene_tiles_device with option exact");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!n_kept) {  // no kept block, no launch: the totals are zero
+        if (d_info) RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_tiles_update_info), s));
+        return RM_OK;
+    }
+    TilesUpdateCall c{d_prev_slot, d_prev_tiles, d_balls, n_prev_kept, n_balls, d_reused, d_info};
+    if (d_reused || !d_info) return launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
+    Staging st{ctx};  // the totals without the caller's flags: the flags live in the scratch
+    const size_t o_flags = st.region(4 * static_cast<size_t>(n_kept));
+    int rc = st.reserve_for(s);
+    if (rc) return rc;
+    c.reused = st.at<void>(o_flags);
+    rc = launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
+    RM_HIP(ctx, st.keep(s));  // the kernels touch the scratch after this call returns
+    return rc;
 }
 
 int rm_mesh_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept, const void *d_tiles, double iso,

@@ -313,6 +313,24 @@ struct RmTilesArgs {
     // (4 (|du| + |dv| + |dw|), the coarse pass's R, and its slack for the roundings)
     double half[3], radius;
 };
+// rm_scene_tiles_update_device (rm_kernels.hip tiles_update_kernel): what the update reads beside the tile launch's RmTilesArgs
+struct RmBall {  // rm_ball (24 bytes)
+    float center[3];
+    int32_t reserved;
+    double radius;
+};
+struct RmTilesUpdateInfo {  // rm_tiles_update_info (32 bytes)
+    long long n_kept, n_reused, n_evaluated, reserved;
+};
+#define RM_UPDATE_MAX_BALLS (1 << 16)
+struct RmTilesUpdateArgs {
+    const int32_t *prev_slot;   // n_blocks: the previous scene's slot map
+    const double *prev_tiles;   // n_prev_kept x RM_SPARSE_TILE
+    const RmBall *balls;
+    int32_t *reused;            // n_kept flags (1: the tile was copied), or null
+    unsigned int n_blocks, n_prev_kept;
+    int n_balls, pad;
+};
 // Option `exact`: the value of RmRenderParams::accel in a point, field or tile launch that evaluates the exact field
 // (rm_kernels.hip, exact_distance).  Such a launch names the tree to walk in bvh / bvh_prims / bvh_nodes -- the scene's BVH or
 // its exact tree -- and bvh_nodes = 0 where every object is evaluated.
@@ -523,6 +541,12 @@ hipError_t rm_launch_blocks_compact(const RmBlocksArgs &a, hipStream_t stream);
 hipError_t rm_launch_tiles(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_tiles_sqrt(const RmRenderParams &p, const RmTilesArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_mesh_tiles(const RmSparseMeshArgs &a, hipStream_t stream, const char **kernel_name);
+// rm_launch_tiles_update (rm_kernels.hip): tiles_update_kernel<GEN> over a.n_kept blocks, sphere and primitive records only
+// (p.general < 2, p.accel == RM_ACCEL_EXACT).  rm_launch_tiles_update_totals (rm_mesh_sparse.hip): the n_kept flags -> info,
+// one workgroup, plain sums.
+hipError_t rm_launch_tiles_update(const RmRenderParams &p, const RmTilesArgs &a, const RmTilesUpdateArgs &u, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_tiles_update_sqrt(const RmRenderParams &p, const RmTilesArgs &a, const RmTilesUpdateArgs &u, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_tiles_update_totals(const int32_t *reused, unsigned int n_kept, RmTilesUpdateInfo *info, hipStream_t stream);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

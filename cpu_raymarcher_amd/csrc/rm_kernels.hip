@@ -1650,6 +1650,81 @@ __global__ __launch_bounds__(256) void tiles_exact_kernel(const RmRenderParams P
     tiles_body<3, GEN>(P, A);
 }
 
+// rm_scene_tiles_update_device (include/rm_raymarch.h, "re-meshing an edited scene"; DESIGN.md 4 has the argument): the exact
+// tiles of the ACTIVE scene from those of the previous one.  One workgroup per kept block, as tiles_exact_kernel, and one
+// decision for the whole workgroup: the block's previous tile is COPIED unless a ball of the edit can reach it, and a reached
+// block -- or one that had no tile -- is EVALUATED by tiles_body<3, GEN>, the code the full path runs.  The previous tile is
+// staged in LDS with coalesced loads (729 doubles; with tiles_body's candidate list the static LDS stays near 10 KB); M, the
+// largest previous value at the tile's points inside the lattice, and the NaN flag are reduced across the four waves; the balls
+// are dealt to the lanes, strided over 256, and a workgroup-wide OR says whether one reaches.  Every changed object version o
+// has sdf_o(x) >= gap(ball, tile box) - rho at every tile point x, so with gap - rho > M (by the margins of box_beyond) none
+// attains the old minimum and none can lower it: the new value is the old one, bit for bit.  A NaN anywhere evaluates.
+template <int GEN>
+__global__ __launch_bounds__(256) void tiles_update_kernel(const RmRenderParams P, const RmTilesArgs A, const RmTilesUpdateArgs U) {
+    __shared__ double s_tile[RM_SPARSE_TILE];
+    __shared__ double s_max[4];
+    __shared__ int s_flag[4];
+    const unsigned int r = blockIdx.x;
+    const unsigned int b = static_cast<unsigned int>(A.list[r]);
+    // (uniform from here to the branch: b, p and c are the same in every lane)
+    const int p = b < U.n_blocks ? U.prev_slot[b] : -1;
+    bool evaluate = p < 0 || static_cast<unsigned int>(p) >= U.n_prev_kept;
+    const unsigned int row = b / A.nbu, bx = b - row * A.nbu, bz = row / A.nbv, by = row - bz * A.nbv;
+    const double fi = static_cast<double>(8u * bx + 4u), fj = static_cast<double>(8u * by + 4u), fk = static_cast<double>(8u * bz + 4u);
+    const Vec3f c = lattice_point(A.lat, fi, fj, fk);  // tiles_body's centre point: not clamped to the lattice
+    if (!(c.x - c.x == 0.f && c.y - c.y == 0.f && c.z - c.z == 0.f)) evaluate = true;
+    if (!evaluate) {
+        const double *src = U.prev_tiles + static_cast<size_t>(p) * RM_SPARSE_TILE;
+        double m = -__builtin_inf();
+        bool flag = false;  // first: a NaN at a point inside the lattice
+#pragma unroll
+        for (unsigned int t = threadIdx.x; t < RM_SPARSE_TILE; t += 256u) {
+            const double v = src[t];
+            s_tile[t] = v;
+            const unsigned int q = t / 9u, ta = t - q * 9u, tg = q / 9u, tb = q - tg * 9u;
+            if (8u * bx + ta < A.nu && 8u * by + tb < A.nv && 8u * bz + tg < A.nw) {
+                flag = flag || v != v;
+                m = __builtin_fmax(m, v);
+            }
+        }
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) m = __builtin_fmax(m, __shfl_xor(m, d));
+        const bool wave_flag = __ballot(flag) != 0ull;
+        if ((threadIdx.x & 63u) == 0) {
+            s_max[threadIdx.x >> 6] = m;
+            s_flag[threadIdx.x >> 6] = wave_flag ? 1 : 0;
+        }
+        __syncthreads();
+        const double M = __builtin_fmax(__builtin_fmax(s_max[0], s_max[1]), __builtin_fmax(s_max[2], s_max[3]));
+        const bool any_nan = (s_flag[0] | s_flag[1] | s_flag[2] | s_flag[3]) != 0;
+        __syncthreads();  // s_flag is written again below
+        const double lx = static_cast<double>(c.x) - A.half[0], hx = static_cast<double>(c.x) + A.half[0];
+        const double ly = static_cast<double>(c.y) - A.half[1], hy = static_cast<double>(c.y) + A.half[1];
+        const double lz = static_cast<double>(c.z) - A.half[2], hz = static_cast<double>(c.z) + A.half[2];
+        flag = false;  // now: a ball reaches the tile
+        for (int i = static_cast<int>(threadIdx.x); i < U.n_balls; i += 256) {
+            const RmBall ball = U.balls[i];
+            const double cx = static_cast<double>(ball.center[0]), cy = static_cast<double>(ball.center[1]), cz = static_cast<double>(ball.center[2]);
+            const double ex = __builtin_fmax(__builtin_fmax(lx - cx, cx - hx), 0.0);
+            const double ey = __builtin_fmax(__builtin_fmax(ly - cy, cy - hy), 0.0);
+            const double ez = __builtin_fmax(__builtin_fmax(lz - cz, cz - hz), 0.0);
+            const double gap = __builtin_sqrt((ex * ex + ey * ey) + ez * ez);
+            flag = flag || !(gap * (1.0 - 0x1p-20) - 0x1p-20 - ball.radius > M);
+        }
+        const bool wave_reach = __ballot(flag) != 0ull;
+        if ((threadIdx.x & 63u) == 0) s_flag[threadIdx.x >> 6] = wave_reach ? 1 : 0;
+        __syncthreads();
+        evaluate = any_nan || (s_flag[0] | s_flag[1] | s_flag[2] | s_flag[3]) != 0;
+    }
+    if (threadIdx.x == 0 && U.reused) U.reused[r] = evaluate ? 0 : 1;
+    if (evaluate) {
+        tiles_body<3, GEN>(P, A);
+    } else {
+        double *out = A.tiles + static_cast<size_t>(r) * RM_SPARSE_TILE;
+        for (unsigned int t = threadIdx.x; t < RM_SPARSE_TILE; t += 256u) out[t] = s_tile[t];
+    }
+}
+
 // ------------------------------------------------------------------ point queries (rm_scene_points)
 //
 // Distance, gradient, object and projection onto the surface for caller-supplied points (include/rm_raymarch.h has the rule):
@@ -2579,6 +2654,23 @@ hipError_t RM_LEN_VARIANT(rm_launch_tiles)(const RmRenderParams &p, const RmTile
     if (p.accel == RM_ACCEL_EXACT) RM_LAUNCH_EXACT(tiles_kernel, tiles_exact_kernel, l.pl, a)
     else RM_DISPATCH(RM_TLK)
 #undef RM_TLK
+    return hipGetLastError();
+}
+
+hipError_t RM_LEN_VARIANT(rm_launch_tiles_update)(const RmRenderParams &p, const RmTilesArgs &a, const RmTilesUpdateArgs &u, hipStream_t stream,
+                                                  const char **kernel_name) {
+    if (kernel_name) *kernel_name = "";
+    if (a.n_kept == 0 || a.n_kept > RM_SPARSE_MAX_BLOCKS || u.n_balls < 0 || u.n_balls > RM_UPDATE_MAX_BALLS) return hipErrorInvalidValue;
+    if (p.accel != RM_ACCEL_EXACT || p.general >= 2) return hipErrorInvalidValue;  // (expression programs: the full path)
+    const SceneLaunch l = scene_launch(p);
+    const dim3 grid(a.n_kept), block(256);
+    if (p.general) {
+        hipLaunchKernelGGL((tiles_update_kernel<1>), grid, block, l.shmem, stream, l.pl, a, u);
+        if (kernel_name) *kernel_name = "tiles_update_kernel<1>" RM_LEN_TAG;
+    } else {
+        hipLaunchKernelGGL((tiles_update_kernel<0>), grid, block, l.shmem, stream, l.pl, a, u);
+        if (kernel_name) *kernel_name = "tiles_update_kernel<0>" RM_LEN_TAG;
+    }
     return hipGetLastError();
 }
 

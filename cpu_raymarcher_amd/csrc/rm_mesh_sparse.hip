@@ -266,7 +266,28 @@ __global__ __launch_bounds__(kBlock) void mesh_tiles_quad_kernel(RmSparseMeshArg
     }
 }
 
+// rm_scene_tiles_update_device: the flags of the kept blocks (1: the previous tile was copied) -> info.  One workgroup, plain
+// sums of integers: nothing depends on arrival order.
+__global__ __launch_bounds__(kScan) void tiles_update_totals_kernel(const int32_t *reused, unsigned n_kept, RmTilesUpdateInfo *info) {
+    __shared__ unsigned s_sums[kScan / 64];
+    unsigned mine = 0;
+    for (unsigned at = threadIdx.x; at < n_kept; at += kScan) mine += reused[at] != 0 ? 1u : 0u;
+    unsigned total;
+    scan_step(mine, s_sums, &total);
+    if (threadIdx.x == 0) {
+        info->n_kept = static_cast<long long>(n_kept);
+        info->n_reused = static_cast<long long>(total);
+        info->n_evaluated = static_cast<long long>(n_kept - total);
+        info->reserved = 0;
+    }
+}
+
 }  // namespace
+
+hipError_t rm_launch_tiles_update_totals(const int32_t *reused, unsigned int n_kept, RmTilesUpdateInfo *info, hipStream_t stream) {
+    hipLaunchKernelGGL(tiles_update_totals_kernel, dim3(1), dim3(kScan), 0, stream, reused, n_kept, info);
+    return hipGetLastError();
+}
 
 hipError_t rm_launch_blocks_compact(const RmBlocksArgs &a, hipStream_t stream) {
     if (a.n_blocks == 0 || a.n_blocks > RM_SPARSE_MAX_BLOCKS || a.n_groups != (a.n_blocks + kBlock - 1) / kBlock) return hipErrorInvalidValue;

@@ -56,6 +56,7 @@ class Scene:
         self.accelerationStructure = accelerationStructure
         self.camera = Camera()
         self._uploaded = False
+        self._session = None  # the open MeshSession (meshSession); every load of another scene closes it
         self.currentPresetIndex = 0
         self.time = 0.0  # Scene.updateTime's value (scene.ts:135-140): what rayMarch / getNormal march with
         self.loadPreset(0)  # scene.ts:28
@@ -68,33 +69,41 @@ class Scene:
         count = N.lib().rm_preset_count()
         self.currentPresetIndex = max(0, min(int(index), count - 1))
         self._uploaded = False
+        self._session = None
         self.ctx.scene_from_preset(self.currentPresetIndex, self.accel_enum)
 
     def loadSpheres(self, centers, radii):
         """Build-defined: n spheres as SceneManager.createSphere(x,y,z,r) makes them."""
         self.ctx.scene_from_spheres(centers, radii, self.accel_enum)
         self._uploaded = True
+        self._session = None
 
     def loadPrims(self, prims):
         """Build-defined: spheres / boxes / tori as (type, world_to_local[16], params)."""
         self.ctx.scene_from_prims(prims, self.accel_enum)
         self._uploaded = True
+        self._session = None
 
     def loadNodes(self, nodes, roots):
         """Build-defined: an SDF expression forest (operators of util/primitive_operations/ over
         sphere / box / torus / mandelbulb leaves); see Context.scene_from_nodes."""
         self.ctx.scene_from_nodes(nodes, roots, self.accel_enum)
         self._uploaded = True
+        self._session = None
 
     # ---- object CRUD on sphere scenes (the reference README's third plan; rm_scene_edit_spheres) ----
     def editSpheres(self, edits):
         """Applies a batch of edits to this scene's sphere list in place: edits = [("set", i, centre, radius),
         ("insert", i, centre, radius), ("remove", i), ...], indices in object order (what objectAt returns) at the moment
         each edit applies.  The scene must be a sphere list (loadSpheres, or preset 0..4); it is the uploaded scene
-        afterwards, exactly as loadSpheres(edited list) would leave it.  All or nothing."""
+        afterwards, exactly as loadSpheres(edited list) would leave it.  All or nothing.  With a mesh session open
+        (meshSession) the edit goes through it, so its tiles follow the scene."""
         edits = list(edits)
         self._activate()
-        self.ctx.edit_spheres(edits)
+        if self._session is not None:
+            self._session.edit_spheres(edits)
+        else:
+            self.ctx.edit_spheres(edits)
         if edits:
             self._uploaded = True
 
@@ -171,6 +180,14 @@ class Scene:
         if sparse:
             return self.ctx.mesh_sparse(origin, du, dv, dw, shape, lipschitz=lipschitz, **more)
         return self.ctx.mesh(origin, du, dv, dw, shape, **more)
+
+    def meshSession(self, origin, du, dv, dw, shape, iso=0.0, lipschitz=1.0):
+        """Opens a mesh session on this scene at its own time (Context.mesh_session) and returns it: session.mesh() is
+        toMesh(sparse=True, exact=True) over the lattice, and from now on editSpheres / setSphere / insertSphere /
+        removeSphere re-sample only the tiles the edit can reach.  Loading another scene closes the session."""
+        self._activate()
+        self._session = self.ctx.mesh_session(origin, du, dv, dw, shape, iso=iso, time=self.time, lipschitz=lipschitz)
+        return self._session
 
     def info(self):
         self._activate()

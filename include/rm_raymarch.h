@@ -465,6 +465,76 @@ RM_API int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double i
                                 uint32_t *quads, int64_t cap_quads, int64_t *cells, int64_t *edges, rm_mesh_info *info,
                                 rm_sparse_info *sparse_info);
 
+/* ---- re-meshing an edited scene: only the tiles an edit can reach are sampled again ------------------------------
+ *
+ * The loop is pick -> edit -> look again.  After an edit the caller runs rm_scene_blocks_device afresh (one distance per block:
+ * cheap, and it gives the new slot / list with no rule of its own), then rm_scene_tiles_update_device instead of
+ * rm_scene_tiles_device, then rm_mesh_tiles_device as before.  The update is defined for the EXACT field E(x) = min(10, min over
+ * all objects of Primitive.sdf(x)) only ("the exact field", below): a BVH or octree scene's own field changes everywhere when
+ * an edit rebuilds the tree.  It does not read option `exact`: it IS the exact field.
+ *
+ * CONTRACT.  d_tiles afterwards holds, byte for byte, what rm_scene_tiles_device with option exact = 1 writes for the same
+ * lattice, d_list and n_kept on the ACTIVE scene, given
+ *   P1  d_prev_slot (int32[n_blocks]) and d_prev_tiles (f64[n_prev_kept][729]) are what the exact sparse path --
+ *       rm_scene_blocks_device, then rm_scene_tiles_device with exact = 1 or this entry -- wrote for the PREVIOUS scene on the
+ *       same lattice, `time` included;
+ *   P2  the balls cover every object that differs between the two scenes, in each of its versions: for every such object
+ *       version o there is a ball (c, rho) with Primitive.sdf_o(x) >= |x - c| - rho at every point x.  For a sphere: its own
+ *       binary32 centre and its radius, with equality.  For a rigidly transformed box or torus: a ball that contains it.
+ *       Objects whose index merely shifted are not changed objects: E does not depend on the order.
+ * DECISION per kept block, b = d_list[r], the same for the 256 threads of its workgroup:
+ *   1  p = d_prev_slot[b]; p outside 0 .. n_prev_kept - 1 (b outside 0 .. n_blocks - 1 counts as -1): EVALUATE.
+ *   2  c = the tile's centre point as rm_scene_tiles_device forms it under exact: the lattice point rule at index 8 b + 4 per
+ *      axis, NOT clamped to the lattice.  A non-finite component: EVALUATE.
+ *   3  M = the largest of the previous tile's values at the tile points inside the lattice (i < nu, j < nv, k < nw; the NaN
+ *      fill beyond it is skipped by index, not by value).  A NaN at a point inside the lattice: EVALUATE.
+ *   4  for each ball, binary64, one operation at a time: lo = c - half, hi = c + half per axis, half the exact tile launch's
+ *      own (4 (|du_a| + |dv_a| + |dw_a|) + slack, slack as under "bound" above); e = max(max(lo - cb, cb - hi), 0) per axis;
+ *      gap = sqrt((ex * ex + ey * ey) + ez * ez); the ball REACHES the tile iff !(gap * (1 - 2^-20) - 2^-20 - rho > M) -- a
+ *      NaN anywhere reaches.  Any ball that reaches: EVALUATE.
+ *   5  otherwise COPY the 729 doubles of d_prev_tiles[p] to d_tiles[r].
+ * EVALUATE is what rm_scene_tiles_device does for the block under exact, by the same device function.
+ * WHY COPYING IS SOUND (DESIGN.md 4 has it in full).  The box c +- half contains every tile point, so a changed object
+ * version's true lower bound at a tile point is gap - rho; the computed sdf falls below it by at most a relative 2^-23 of a
+ * length (three binary32 roundings under a hypot), which the margins cover eight times over.  Hence every changed version has
+ * sdf > M >= E_old at every tile point: no old version attains the old minimum, no new one can lower it, Math.min does not
+ * depend on the order, and E_new and E_old are the same bits.  No Lipschitz assumption: the bound is the tile's own stored
+ * values, so the rule holds for offset surfaces and deep inside large spheres.
+ *
+ * rm_scene_edit_balls: the balls of an edit list for rm_scene_edit_spheres, host-only (it works on a host-only context).  Call
+ * it BEFORE rm_scene_edit_spheres with the same list: it replays the index bookkeeping on the active sphere list and writes,
+ * in edit order, for SET the sphere before and after, for INSERT the new one, for REMOVE the old one -- at most 2 n_edits
+ * balls.  *n_balls is their number whatever `cap` is; the first min(*n_balls, cap) are written (cap 0 and null balls: it only
+ * counts).  RM_E_INVALID for null n_balls, cap < 0 or null balls with cap > 0; then it validates exactly as
+ * rm_scene_edit_spheres does, same codes in the same order (after a refused index, balls written so far mean nothing and
+ * *n_balls is 0).  It changes nothing.
+ *
+ * rm_scene_tiles_update_device: asynchronous on `stream`; one 256-thread workgroup per kept block (tiles_update_kernel<GEN>),
+ * the previous tile staged in LDS; then, when d_info is given, one small kernel that sums the flags.  d_balls: n_balls rm_ball
+ * records on the device.  d_reused int32[n_kept], optional: 1 where the tile was copied, 0 where it was evaluated.  d_info,
+ * optional: an rm_tiles_update_info.  n_balls == 0 copies every block that was kept before.  RM_E_INVALID -- ahead of
+ * RM_E_NO_DEVICE, RM_E_NO_SCENE after it -- for the lattice as the sparse entries check it, n_kept or n_prev_kept outside
+ * 0 .. n_blocks, n_balls outside 0 .. RM_TILES_UPDATE_MAX_BALLS, with n_kept > 0 a null d_list, d_tiles or d_prev_slot (and
+ * a null d_prev_tiles with n_prev_kept > 0), null d_balls with n_balls > 0, d_list / d_prev_slot / d_reused not 4-byte or
+ * d_tiles / d_prev_tiles / d_balls / d_info not 8-byte aligned, and d_tiles[0 .. n_kept) overlapping d_prev_tiles[0 ..
+ * n_prev_kept): slots shift when the kept set changes, so there is no in-place form.  RM_E_UNSUPPORTED, last, for
+ * expression-program scenes (forests, presets 5 .. 18): rm_scene_tiles_device with exact = 1 remains their route; no buffer is
+ * touched.  n_kept == 0 is RM_OK: zero info.  The knobs `filter` and `length` apply as for rm_scene_tiles_device.  Not a
+ * render entry.  rm_last_kernel: tiles_update_kernel<GEN>. */
+#define RM_TILES_UPDATE_MAX_BALLS 65536
+typedef struct rm_ball {   /* 24 bytes */
+    float   center[3];
+    int32_t reserved;    /* 0 */
+    double  radius;
+} rm_ball;
+typedef struct rm_tiles_update_info {   /* 32 bytes */
+    int64_t n_kept, n_reused, n_evaluated, reserved;
+} rm_tiles_update_info;
+RM_API int rm_scene_edit_balls(rm_ctx *ctx, const rm_sphere_edit *edits, int32_t n_edits, rm_ball *balls, int32_t cap, int32_t *n_balls);
+RM_API int rm_scene_tiles_update_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_prev_slot, const void *d_prev_tiles,
+                                        int64_t n_prev_kept, const void *d_balls, int32_t n_balls, const void *d_list, int64_t n_kept,
+                                        void *d_tiles, void *d_reused, void *d_info, void *stream);
+
 /* ---- sharp meshes: vertices from Hermite data (dual contouring's vertex rule) --------------------------------- */
 
 typedef struct rm_sharp_query {  /* 32 bytes */
