@@ -926,17 +926,9 @@ class Context:
 
     def _points(self, points, normal, object, snap, tol, iso, time, device):
         q = self._point_query(normal, snap, tol, iso, time)
-        if _is_torch(points) or device:
+        p = self._device_input("points", points, device, np.float32, (3,), "points must be a contiguous float32 CUDA tensor of [n, 3]")
+        if p is not None:
             import torch
-            if self.device < 0:
-                raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance path")
-            if _is_torch(points):
-                if not (points.is_cuda and points.dtype == torch.float32 and points.is_contiguous() and points.numel() % 3 == 0):
-                    raise ValueError("points must be a contiguous float32 CUDA tensor of [n, 3]")
-                self._same_device(dict(points=points))
-                p = points
-            else:
-                p = torch.from_numpy(np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)).to(torch.device("cuda", self.device))
             pos = torch.empty((p.numel() // 3, 3), dtype=torch.float32, device=p.device)
             return Points(pos, *self._points_device(q, p, pos, normal, object))
         p = np.ascontiguousarray(points, dtype=np.float32).reshape(-1, 3)
@@ -948,6 +940,22 @@ class Context:
         N.check(self._h, N.lib().rm_scene_points(self._h, C.byref(q), n, _ptr(p), _ptr(pos), _ptr(dist), _ptr(nrm), _ptr(obj), _ptr(steps),
                                                  _ptr(cnt)))
         return Points(pos, dist, nrm, obj, steps, cnt)
+
+    def _device_input(self, name, x, device, dtype, trailing, text):
+        """The input of a query that has a device form and a host form: a numpy array without device=True -> None, the host
+        entry is to be used; else a contiguous CUDA tensor of `dtype` (a numpy type) and whole rows of `trailing` -- the tensor
+        given, which has to be one (ValueError `text`) on the context's device, or the array uploaded as [n] + trailing."""
+        if not (_is_torch(x) or device):
+            return None
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance path")
+        if not _is_torch(x):
+            import torch
+            return torch.from_numpy(np.ascontiguousarray(x, dtype=dtype).reshape((-1,) + trailing)).to(torch.device("cuda", self.device))
+        if not (x.is_cuda and str(x.dtype) == "torch." + dtype.__name__ and x.is_contiguous() and x.numel() % (trailing[0] if trailing else 1) == 0):
+            raise ValueError(text)
+        self._same_device({name: x})
+        return x
 
     def project(self, points, steps=4, tol=1e-4, iso=0.0, time=0.0, device=False, exact=False):
         """The snap alone: `points` moved onto the surface getDistance == iso by up to `steps` steps (points(...) without
@@ -981,27 +989,55 @@ class Context:
         sharp=True moves every vertex to dual contouring's place first (`mesh_cells`, then `sharpen` with refine, rank_tol and
         reach against the ACTIVE scene at `time`): edges and corners of the solid are kept; the faces are untouched and the
         attribute pass runs on the sharpened vertices."""
-        lat = make_lattice(origin, du, dv, dw, shape)
+        lat = self._volume_lattice(origin, du, dv, dw, shape)
+        import torch
+        values, vt = self._mesh_values(values, lat.nu * lat.nv * lat.nw)
+
+        def call(info, v, n_v, q, n_q):
+            N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), v[0], n_v, q[0], n_q, info,
+                                                          _current_stream_ptr()))
+        (vertices,), (quads,) = self._counted(call, [((3,), torch.float32)], [((4,), torch.int32)])
+        cells = self._mesh_cells(lat, values, vt, iso, len(vertices)) if sharp and len(vertices) else None
+        return self._finish_mesh(lat, vertices, quads, cells, iso, time, (refine, rank_tol, reach) if sharp else None, triangles, attributes, snap,
+                                 tol, device)
+
+    def _need_volume(self, shape):
         if len(tuple(shape)) != 3:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
-        n = lat.nu * lat.nv * lat.nw
         if self.device < 0:
             raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+
+    def _volume_lattice(self, origin, du, dv, dw, shape, time=0.0):
+        """How a mesher opens: a volume's shape, a device, then the rm_lattice."""
+        self._need_volume(shape)
+        return make_lattice(origin, du, dv, dw, shape, time)
+
+    def _counted(self, call, per_vertex, per_quad=(), counts=None):
+        """The capacity protocol of the mesh entries: the counting call, one read of its totals, buffers of exactly the counted
+        sizes, the filling call when something was counted.  call(info, vertex_ptrs, n_vertices, quad_ptrs, n_quads) runs the
+        entry (a pointer is None in the counting call and for a buffer that is empty or not asked for); per_vertex / per_quad:
+        (trailing shape, dtype) per buffer, None for one not asked for.  counts: totals already known, no counting call."""
         import torch
         dev = torch.device("cuda", self.device)
-        values, vt = self._mesh_values(values, n)
         info = torch.zeros(4, dtype=torch.int64, device=dev)
-        N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), None, 0, None, 0, _ptr(info),
-                                                      _current_stream_ptr()))
-        n_vertices, n_quads = (int(x) for x in info.cpu()[:2])
-        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
-        quads = torch.empty((n_quads, 4), dtype=torch.int32, device=dev)
-        if n_vertices or n_quads:
-            N.check(self._h, N.lib().rm_mesh_field_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), _ptr(vertices) if n_vertices else None,
-                                                          n_vertices, _ptr(quads) if n_quads else None, n_quads, _ptr(info), _current_stream_ptr()))
-        if sharp and n_vertices:
-            cells = self._mesh_cells(lat, values, vt, iso, n_vertices)
-            vertices = self._sharpen_device(make_lattice(origin, du, dv, dw, shape, time), cells, iso, refine, rank_tol, reach, False, False)[0]
+        if counts is None:
+            call(_ptr(info), [None] * len(per_vertex), 0, [None] * len(per_quad), 0)
+            counts = info.cpu()[:2].tolist()
+        n_v, n_q = counts
+        vb = [None if s is None else torch.empty((n_v,) + s[0], dtype=s[1], device=dev) for s in per_vertex]
+        qb = [None if s is None else torch.empty((n_q,) + s[0], dtype=s[1], device=dev) for s in per_quad]
+        if n_v or n_q:
+            call(_ptr(info), [_ptr(b) if n_v else None for b in vb], n_v, [_ptr(b) if n_q else None for b in qb], n_q)
+        return vb, qb
+
+    def _finish_mesh(self, lat, vertices, quads, cells, iso, time, sharp, triangles, attributes, snap, tol, device):
+        """How a mesh ends, from the device tensors of a mesher: the vertices sharpened (sharp = (refine, rank_tol, reach), with
+        the cells' keys) when there are any, the winding flipped when (du, dv, dw) is left-handed, the quads split into
+        triangles, the attribute pass on the final vertices, and the download unless `device`."""
+        if sharp and len(vertices):
+            at = N.rm_lattice.from_buffer_copy(lat)  # (mesh_field's lattice has no time)
+            at.time = float(time)
+            vertices = self._sharpen_device(at, cells, iso, *sharp, False, False)[0]
         u, v, w = (np.array(list(getattr(lat, k)), np.float64) for k in ("du", "dv", "dw"))
         if float(np.dot(u, np.cross(v, w))) < 0:
             quads = quads[:, [0, 3, 2, 1]].contiguous()
@@ -1028,27 +1064,16 @@ class Context:
     def _mesh_cells(self, lat, values, vt, iso, n_vertices=None):
         """rm_mesh_cells_device on torch's current stream -> int64 CUDA tensor [V]; n_vertices None: the counting call first."""
         import torch
-        dev = torch.device("cuda", self.device)
-        info = torch.zeros(4, dtype=torch.int64, device=dev)
-        if n_vertices is None:
-            N.check(self._h, N.lib().rm_mesh_cells_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), None, 0, _ptr(info),
-                                                          _current_stream_ptr()))
-            n_vertices = int(info.cpu()[0])
-        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev)
-        if n_vertices:
-            N.check(self._h, N.lib().rm_mesh_cells_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), _ptr(cells), n_vertices, _ptr(info),
-                                                          _current_stream_ptr()))
-        return cells
+
+        def call(info, c, n_v, _, n_q):
+            N.check(self._h, N.lib().rm_mesh_cells_device(self._h, C.byref(lat), _ptr(values), vt, float(iso), c[0], n_v, info, _current_stream_ptr()))
+        return self._counted(call, [((), torch.int64)], counts=None if n_vertices is None else (n_vertices, 0))[0][0]
 
     def mesh_cells(self, values, origin, du, dv, dw, shape, iso=0.0, device=False):
         """The cell of every vertex of `mesh_field`'s mesh of the same values (rm_mesh_cells_device): int64 [V], the key
         l = (k * nv + j) * nu + i of the cell's low corner, in vertex order -- what `sharpen` takes, and what the sparse mesher
         returns as `cells`.  device=True returns a CUDA tensor."""
-        lat = make_lattice(origin, du, dv, dw, shape)
-        if len(tuple(shape)) != 3:
-            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
-        if self.device < 0:
-            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        lat = self._volume_lattice(origin, du, dv, dw, shape)
         values, vt = self._mesh_values(values, lat.nu * lat.nv * lat.nw)
         cells = self._mesh_cells(lat, values, vt, iso)
         return cells if device else cells.cpu().numpy()
@@ -1087,17 +1112,8 @@ class Context:
             raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
         lat = make_lattice(origin, du, dv, dw, shape, time)
         with self._exact(exact):
-            if _is_torch(cells) or device:
-                import torch
-                if self.device < 0:
-                    raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance path")
-                if _is_torch(cells):
-                    if not (cells.is_cuda and cells.dtype == torch.int64 and cells.is_contiguous()):
-                        raise ValueError("cells must be a contiguous int64 CUDA tensor")
-                    self._same_device(dict(cells=cells))
-                    c = cells.reshape(-1)
-                else:
-                    c = torch.from_numpy(np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)).to(torch.device("cuda", self.device))
+            c = self._device_input("cells", cells, device, np.int64, (), "cells must be a contiguous int64 CUDA tensor")
+            if c is not None:
                 return Sharp(*self._sharpen_device(lat, c, iso, refine, rank_tol, reach))
             c = np.ascontiguousarray(cells, dtype=np.int64).reshape(-1)
             n = len(c)
@@ -1113,10 +1129,7 @@ class Context:
         mesh_field returns (attributes, snap, tol: as there).  The field under a BVH or an octree is the marchers' bound, not
         always the exact distance: an offset surface (iso != 0) wants exact=True (option `exact` for this call: the volume
         and the attribute pass then come from the exact field).  sharp, refine, rank_tol, reach: as mesh_field."""
-        if len(tuple(shape)) != 3:
-            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
-        if self.device < 0:
-            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        self._need_volume(shape)  # (field and mesh_field each make the lattice)
         with self._exact(exact):
             vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True)
             return self.mesh_field(vol, origin, du, dv, dw, shape, iso=iso, device=device, triangles=triangles, attributes=attributes, snap=snap,
@@ -1129,24 +1142,24 @@ class Context:
         |d - iso| > lipschitz * R + slack proves it empty.  Returns the named tuple SparseBlocks(slot int32 [n_blocks]: the
         block's rank among the kept ones or -1, list int32 [n_kept]: the kept blocks in that order, dist float64 [n_blocks] or
         None, n_kept, dims = (nbu, nbv, nbw)); CUDA tensors."""
-        if len(tuple(shape)) != 3:
-            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
-        if self.device < 0:
-            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
         import torch
-        lat = make_lattice(origin, du, dv, dw, shape, time)
+        lat = self._volume_lattice(origin, du, dv, dw, shape, time)
+        dims, _, slot, lst = self._block_buffers(lat)
+        d = torch.empty(len(slot), dtype=torch.float64, device=slot.device) if dist else None
+        n_kept = self._sparse_blocks_into(lat, iso, lipschitz, slot, lst, d)
+        return SparseBlocks(slot, lst[:n_kept], d, n_kept, dims)
+
+    def _block_buffers(self, lat):
+        """The blocks of a lattice (rm_lattice_blocks) and the two buffers the coarse pass fills -> (dims, n_blocks, slot, list)."""
+        import torch
         dims = (C.c_int32 * 3)()
         rc = N.lib().rm_lattice_blocks(C.byref(lat), dims)
         if rc != N.RM_OK:
             raise N.RmError(rc, "rm_lattice_blocks")
         n_blocks = dims[0] * dims[1] * dims[2]
-        dev = torch.device("cuda", self.device)
         room = min(n_blocks, 1 << 24)  # (beyond that the entry refuses before it touches a buffer)
-        slot = torch.empty(room, dtype=torch.int32, device=dev)
-        lst = torch.empty(room, dtype=torch.int32, device=dev)
-        d = torch.empty(room, dtype=torch.float64, device=dev) if dist else None
-        n_kept = self._sparse_blocks_into(lat, iso, lipschitz, slot, lst, d)
-        return SparseBlocks(slot, lst[:n_kept], d, n_kept, tuple(dims))
+        slot = torch.empty(room, dtype=torch.int32, device=torch.device("cuda", self.device))
+        return tuple(dims), n_blocks, slot, torch.empty_like(slot)
 
     def _sparse_blocks_into(self, lat, iso, lipschitz, slot, lst, d=None):
         """The coarse pass into the caller's buffers -> n_kept."""
@@ -1179,33 +1192,30 @@ class Context:
         blocks = self.sparse_blocks(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, dist=False)
         import torch
         lat = make_lattice(origin, du, dv, dw, shape, time)
-        dev = torch.device("cuda", self.device)
         k = blocks.n_kept
-        tiles = torch.empty((k, 729), dtype=torch.float64, device=dev)
-        N.check(self._h, N.lib().rm_scene_tiles_device(self._h, C.byref(lat), _ptr(blocks.list) if k else None, k, _ptr(tiles) if k else None,
-                                                       _current_stream_ptr()))
+        tiles = torch.empty((k, 729), dtype=torch.float64, device=blocks.slot.device)
+        self._tiles_into(lat, blocks.list, k, tiles)
         return self._mesh_tiles(lat, blocks.slot, blocks.list, k, tiles, iso, time, order, device, triangles, attributes, snap, tol, sharp)
+
+    def _tiles_into(self, lat, lst, k, tiles):
+        """The full tile call (rm_scene_tiles_device): the k kept blocks of `lst` sampled into `tiles`."""
+        N.check(self._h, N.lib().rm_scene_tiles_device(self._h, C.byref(lat), _ptr(lst) if k else None, k, _ptr(tiles) if k else None,
+                                                       _current_stream_ptr()))
 
     def _mesh_tiles(self, lat, slot, lst, k, tiles, iso, time, order, device, triangles, attributes, snap, tol, sharp=None):
         """mesh_sparse from the tiles onward (rm_mesh_tiles_device: the counting call, an exact allocation, the filling call):
         slot int32 [n_blocks], lst and tiles hold k kept blocks at least.  What `mesh_sparse` and a MeshSession share."""
         import torch
         dev = torch.device("cuda", self.device)
-        info = torch.zeros(4, dtype=torch.int64, device=dev)
-
-        def call(v, nv_, q, nq_, c, e):
-            N.check(self._h, N.lib().rm_mesh_tiles_device(self._h, C.byref(lat), _ptr(slot), _ptr(lst) if k else None, k,
-                                                          _ptr(tiles) if k else None, float(iso), _ptr(v) if nv_ else None, nv_, _ptr(q) if nq_ else None,
-                                                          nq_, _ptr(c) if nv_ else None, _ptr(e) if nq_ else None, _ptr(info), _current_stream_ptr()))
-        call(None, 0, None, 0, None, None)
-        n_vertices, n_quads = (int(x) for x in info.cpu()[:2])
-        vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
-        quads = torch.empty((n_quads, 4), dtype=torch.int32, device=dev)
         dense = order == "dense"
-        cells = torch.empty(n_vertices, dtype=torch.int64, device=dev) if dense or sharp else None
-        edges = torch.empty(n_quads, dtype=torch.int64, device=dev) if dense else None
-        if n_vertices or n_quads:
-            call(vertices, n_vertices, quads, n_quads, cells, edges)
+
+        def call(info, v, n_v, q, n_q):
+            N.check(self._h, N.lib().rm_mesh_tiles_device(self._h, C.byref(lat), _ptr(slot), _ptr(lst) if k else None, k, _ptr(tiles) if k else None,
+                                                          float(iso), v[0], n_v, q[0], n_q, v[1], q[1], info, _current_stream_ptr()))
+        keys = ((), torch.int64)
+        (vertices, cells), (quads, edges) = self._counted(call, [((3,), torch.float32), keys if dense or sharp else None],
+                                                          [((4,), torch.int32), keys if dense else None])
+        n_vertices, n_quads = len(vertices), len(quads)
         if dense and n_vertices:
             by_cell = torch.argsort(cells)  # (the keys are distinct)
             vertices = vertices[by_cell].contiguous()
@@ -1214,16 +1224,7 @@ class Context:
             rename[by_cell] = torch.arange(n_vertices, dtype=torch.int32, device=dev)
             if n_quads:
                 quads = rename[quads[torch.argsort(edges)].long()].contiguous()
-        if sharp and n_vertices:
-            vertices = self._sharpen_device(lat, cells, iso, *sharp, False, False)[0]
-        u, v, w = (np.array(list(getattr(lat, name)), np.float64) for name in ("du", "dv", "dw"))
-        if float(np.dot(u, np.cross(v, w))) < 0:
-            quads = quads[:, [0, 3, 2, 1]].contiguous()
-        faces = quads[:, [0, 1, 2, 0, 2, 3]].reshape(-1, 3).contiguous() if triangles else quads
-        out = (vertices, faces) + (self._mesh_attributes(vertices, iso, time, snap, tol) if attributes else ())
-        if device:
-            return out
-        return (out[0].cpu().numpy(), out[1].cpu().numpy().view(np.uint32)) + tuple(t.cpu().numpy() for t in out[2:])
+        return self._finish_mesh(lat, vertices, quads, cells, iso, time, sharp, triangles, attributes, snap, tol, device)
 
     def mesh_session(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0):
         """A MeshSession over this lattice: the exact sparse mesh of the active scene whose tiles are kept on the device, so
@@ -1549,24 +1550,15 @@ class MeshSession:
     n_evaluated)."""
 
     def __init__(self, ctx, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0):
-        if len(tuple(shape)) != 3:
-            raise ValueError("a mesh needs a volume: shape is (nu, nv, nw)")
-        if ctx.device < 0:
-            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU mesher")
+        self.lattice = ctx._volume_lattice(origin, du, dv, dw, shape, time)
         import torch
         self.ctx, self.iso, self.time, self.lipschitz = ctx, float(iso), float(time), float(lipschitz)
-        self.lattice = make_lattice(origin, du, dv, dw, shape, time)
-        dims = (C.c_int32 * 3)()
-        rc = N.lib().rm_lattice_blocks(C.byref(self.lattice), dims)
-        if rc != N.RM_OK:
-            raise N.RmError(rc, "rm_lattice_blocks")
-        self.dims = tuple(dims)
-        self.n_blocks = dims[0] * dims[1] * dims[2]
         dev = torch.device("cuda", ctx.device)
-        room = min(self.n_blocks, 1 << 24)
         # [slot, list, tiles, n_kept] twice; the tiles grow with the kept set
-        self._sets = [[torch.empty(room, dtype=torch.int32, device=dev), torch.empty(room, dtype=torch.int32, device=dev),
-                       torch.empty((0, 729), dtype=torch.float64, device=dev), 0] for _ in range(2)]
+        self._sets = []
+        for _ in range(2):
+            self.dims, self.n_blocks, slot, lst = ctx._block_buffers(self.lattice)
+            self._sets.append([slot, lst, torch.empty((0, 729), dtype=torch.float64, device=dev), 0])
         self._cur = None  # index of the current set
         self._info = torch.zeros(4, dtype=torch.int64, device=dev)
         self.reused = None  # int32 [n_kept]: the last update's flags (1: the tile was copied), on the device
@@ -1604,11 +1596,9 @@ class MeshSession:
         if new[2].shape[0] < k:
             new[2] = torch.empty((k + k // 8, 729), dtype=torch.float64, device=new[0].device)
         new[3] = k
-        stream = _current_stream_ptr()
         if balls is None or self._cur is None:
             with ctx._exact(True):
-                N.check(ctx._h, N.lib().rm_scene_tiles_device(ctx._h, C.byref(lat), _ptr(new[1]) if k else None, k, _ptr(new[2]) if k else None,
-                                                              stream))
+                ctx._tiles_into(lat, new[1], k, new[2])
             self.reused = torch.zeros(k, dtype=torch.int32, device=new[0].device)
             self.stats = dict(n_kept=k, n_reused=0, n_evaluated=k)
         else:
@@ -1623,7 +1613,7 @@ class MeshSession:
             self.reused = torch.empty(k, dtype=torch.int32, device=new[0].device)
             N.check(ctx._h, N.lib().rm_scene_tiles_update_device(
                 ctx._h, C.byref(lat), _ptr(old[0]), _ptr(old[2]) if old[3] else None, old[3], _ptr(d_balls), n, _ptr(new[1]) if k else None, k,
-                _ptr(new[2]) if k else None, _ptr(self.reused) if k else None, _ptr(self._info), stream))
+                _ptr(new[2]) if k else None, _ptr(self.reused) if k else None, _ptr(self._info), _current_stream_ptr()))
             info = [int(x) for x in self._info.cpu()]
             self.stats = dict(n_kept=info[0], n_reused=info[1], n_evaluated=info[2])
         self._cur = target

@@ -1181,8 +1181,8 @@ size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // regions out in the order they are named, each 256-byte aligned, and returns their offsets; reserve() grows the scratch
 // once to hold them all (it never shrinks, and the device is synchronised before an old buffer is freed) and asks for 256
 // bytes at least, so at() is a device pointer even when every region is empty.  in / zero / out are enqueued.
-// An asynchronous entry (rm_mesh_field_device) reserves for the caller's stream and calls keep() behind its launches: whoever
-// reserves next, on whatever stream, waits on the device for them, so two users of the scratch never overlap.
+// An asynchronous entry reserves for the caller's stream and calls keep() behind its launches (scratch_call): whoever reserves
+// next, on whatever stream, waits on the device for them, so two users of the scratch never overlap.
 struct Staging {
     rm_ctx *ctx;
     size_t total = 0;
@@ -1220,6 +1220,28 @@ struct Staging {
         return hipEventRecord(ctx->scratch_busy, user);
     }
 };
+
+// An asynchronous entry that needs room in the scratch buffer, behind its checks; `bytes`: its regions in order (four at most).
+// With `work` they are reserved for the caller's stream, launch(st, o) -- o[i] the offset of region i -- enqueues the kernels and
+// returns an RM_* code, and keep() follows whatever that code is: what a launch that failed half way did enqueue reads the
+// scratch too.  Without work there is no launch: info_bytes at d_info (null: none) are zeroed on the stream.
+template <typename Launch>
+int scratch_call(rm_ctx *ctx, hipStream_t stream, bool work, void *d_info, size_t info_bytes, std::initializer_list<size_t> bytes, Launch launch) {
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    if (!work) {
+        if (d_info) RM_HIP(ctx, hipMemsetAsync(d_info, 0, info_bytes, stream));
+        return RM_OK;
+    }
+    Staging st{ctx};
+    size_t o[4] = {0, 0, 0, 0}, *next = o;
+    for (const size_t b : bytes) *next++ = st.region(b);
+    if (const int rc = st.reserve_for(stream)) return rc;
+    const int rc = launch(st, o);
+    const hipError_t kept = st.keep(stream);
+    if (rc) return rc;
+    RM_HIP(ctx, kept);
+    return RM_OK;
+}
 
 // One buffer of a call that has a device form and a host form (staged_call): the caller's pointer -- device or host by the form;
 // null: not asked for, no staging bytes and a null kernel pointer --, its bytes per element, where the kernel's argument block
@@ -1867,6 +1889,13 @@ void fill_field(const rm_ctx *ctx, const rm_lattice *lat, RmRenderParams &p, RmF
 static_assert(sizeof(rm_mesh_info) == 32 && sizeof(RmMeshInfo) == sizeof(rm_mesh_info), "rm_mesh_info layout");
 static_assert(RM_MESH_F64 == 0 && RM_MESH_F32 == 1, "rm_launch_mesh reads these values");
 
+// Where a mesh launch writes: device pointers for the kernels, the caller's host pointers in a host entry.  cells and edges are
+// the sparse mesher's keys (null: not asked for; the dense entries have none).
+struct MeshOutputs {
+    void *vertices, *quads, *cells, *edges, *info;
+    int64_t cap_vertices, cap_quads;
+};
+
 // What both mesh entries check, arguments first, each described once; *n receives the point count and *cells whether the
 // lattice has a cell (every count at least 2).  `values` null: the entry samples the scene itself (rm_scene_mesh) and needs one.
 struct MeshCall {
@@ -1875,90 +1904,109 @@ struct MeshCall {
     const void *values;
     int32_t value_type;
     double iso;
-    const void *vertices, *quads, *info;
-    int64_t cap_vertices, cap_quads;
+    MeshOutputs out;
 };
 
 bool misaligned(const void *p, uintptr_t mask) { return (reinterpret_cast<uintptr_t>(p) & mask) != 0; }
 
 // what every mesh entry, dense or sparse, checks about iso, capacities and output buffers (the sparse ones: cells and edges too)
-const char *mesh_outputs_error(double iso, const void *vertices, int64_t cap_vertices, const void *quads, int64_t cap_quads, const void *cells,
-                               const void *edges) {
+const char *mesh_outputs_error(double iso, const MeshOutputs &o) {
     if (!std::isfinite(iso)) return "non-finite iso";
-    if (cap_vertices < 0 || cap_quads < 0) return "negative capacity";
-    if ((cap_vertices > 0 && !vertices) || (cap_quads > 0 && !quads)) return "null buffer with a capacity above 0";
-    if (misaligned(vertices, 3) || misaligned(quads, 3)) return "vertices and quads must be 4-byte aligned";
-    if (misaligned(cells, 7) || misaligned(edges, 7)) return "cells and edges must be 8-byte aligned";
+    if (o.cap_vertices < 0 || o.cap_quads < 0) return "negative capacity";
+    if ((o.cap_vertices > 0 && !o.vertices) || (o.cap_quads > 0 && !o.quads)) return "null buffer with a capacity above 0";
+    if (misaligned(o.vertices, 3) || misaligned(o.quads, 3)) return "vertices and quads must be 4-byte aligned";
+    if (misaligned(o.cells, 7) || misaligned(o.edges, 7)) return "cells and edges must be 8-byte aligned";
     return nullptr;
+}
+
+// what an entry without a host path asks of the context, behind its arguments: a device (no CPU `path`), then a scene if it samples one
+int need_device(rm_ctx *ctx, const char *path, bool scene) {
+    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, std::string("host-only context: there is no CPU ") + path);
+    if (scene && !ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    return RM_OK;
 }
 
 int check_mesh(rm_ctx *ctx, const MeshCall &m, int64_t *n, bool *cells) {
     if (const char *bad = lattice_error(m.lattice, n)) return fail(ctx, RM_E_INVALID, bad);
     if (*n > (int64_t(1) << 30)) return fail(ctx, RM_E_INVALID, "more than 2^30 lattice points: the mesher does not split a volume");
     *cells = m.lattice->nu >= 2 && m.lattice->nv >= 2 && m.lattice->nw >= 2;
-    if (!m.info) return fail(ctx, RM_E_INVALID, "null info");
-    if (const char *bad = mesh_outputs_error(m.iso, m.vertices, m.cap_vertices, m.quads, m.cap_quads, nullptr, nullptr)) return fail(ctx, RM_E_INVALID, bad);
+    if (!m.out.info) return fail(ctx, RM_E_INVALID, "null info");
+    if (const char *bad = mesh_outputs_error(m.iso, m.out)) return fail(ctx, RM_E_INVALID, bad);
     if (m.own_values) {
         if (m.value_type != RM_MESH_F64 && m.value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
         if (*cells && !m.values) return fail(ctx, RM_E_INVALID, "null values");
         if (reinterpret_cast<uintptr_t>(m.values) & (m.value_type == RM_MESH_F64 ? 7 : 3)) return fail(ctx, RM_E_INVALID, "values must be aligned to their type");
-        if (reinterpret_cast<uintptr_t>(m.info) & 7) return fail(ctx, RM_E_INVALID, "info must be 8-byte aligned");
+        if (reinterpret_cast<uintptr_t>(m.out.info) & 7) return fail(ctx, RM_E_INVALID, "info must be 8-byte aligned");
     }
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
-    if (!m.own_values && !ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
-    return RM_OK;
+    return need_device(ctx, "mesher", !m.own_values);
 }
 
-// The launch both entries share: `values` laid out by the lattice, outputs and info on the device, the map and the block totals
-// at their places in the reserved scratch.
-RmMeshArgs mesh_args(const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices, void *d_quads,
-                     void *d_info, size_t o_map, size_t o_totals) {
+// the outputs and the mesher's scratch of an argument block, dense or sparse
+template <typename ARGS>
+void fill_mesh_outputs(ARGS &a, const MeshOutputs &o, uint32_t *d_map, uint32_t *d_totals) {
+    a.vertices = static_cast<float *>(o.vertices);
+    a.quads = static_cast<uint32_t *>(o.quads);
+    a.info = static_cast<RmMeshInfo *>(o.info);
+    a.map = d_map;
+    a.totals = d_totals;
+    a.cap_vertices = o.cap_vertices;
+    a.cap_quads = o.cap_quads;
+}
+
+// The launch both entries share: m.values laid out by the lattice, m.out and the values on the device, the map and the block
+// totals at their places in the reserved scratch.
+RmMeshArgs mesh_args(const Staging &st, const MeshCall &m, int64_t n, size_t o_map, size_t o_totals) {
     RmMeshArgs a;
     std::memset(&a, 0, sizeof a);
     a.lat = widen_lattice(*m.lattice);
-    a.values = d_values;
+    a.values = m.values;
     a.iso = m.iso;
-    a.vertices = static_cast<float *>(d_vertices);
-    a.quads = static_cast<uint32_t *>(d_quads);
-    a.info = static_cast<RmMeshInfo *>(d_info);
-    a.map = st.at<uint32_t>(o_map);
-    a.totals = st.at<uint32_t>(o_totals);
+    fill_mesh_outputs(a, m.out, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals));
     a.n = n;
-    a.cap_vertices = m.cap_vertices;
-    a.cap_quads = m.cap_quads;
     a.nu = static_cast<unsigned int>(m.lattice->nu);
     a.nv = static_cast<unsigned int>(m.lattice->nv);
     a.nw = static_cast<unsigned int>(m.lattice->nw);
     a.n_blocks = static_cast<unsigned int>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK);
-    a.f32 = value_type == RM_MESH_F32;
+    a.f32 = m.value_type == RM_MESH_F32;
     return a;
 }
 
-int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, const void *d_values, int32_t value_type, void *d_vertices,
-                void *d_quads, void *d_info, size_t o_map, size_t o_totals, hipStream_t stream) {
-    const RmMeshArgs a = mesh_args(st, m, n, d_values, value_type, d_vertices, d_quads, d_info, o_map, o_totals);
-    RM_HIP(ctx, rm_launch_mesh(a, stream, &ctx->last_kernel));
+int launch_mesh(rm_ctx *ctx, const Staging &st, const MeshCall &m, int64_t n, size_t o_map, size_t o_totals, hipStream_t stream) {
+    RM_HIP(ctx, rm_launch_mesh(mesh_args(st, m, n, o_map, o_totals), stream, &ctx->last_kernel));
     return RM_OK;
 }
 
 size_t mesh_blocks(int64_t n) { return static_cast<size_t>((n + RM_MESH_BLOCK - 1) / RM_MESH_BLOCK); }
 
+// The outputs of a host mesh entry in the scratch buffer, behind the entry's other regions: the info, then room for what the
+// caller's capacities hold or the lattice or the kept blocks can yield at most, whichever is less; keys only where asked for.
+struct MeshRegions {
+    size_t room_v, room_q, o_info, o_vert, o_quad, o_cells, o_edges;
+    MeshRegions(Staging &st, const MeshOutputs &host, int64_t most_v, int64_t most_q)
+        : room_v(static_cast<size_t>(std::min(host.cap_vertices, most_v))), room_q(static_cast<size_t>(std::min(host.cap_quads, most_q))),
+          o_info(st.region(sizeof(rm_mesh_info))), o_vert(st.region(12 * room_v)), o_quad(st.region(16 * room_q)),
+          o_cells(st.region(host.cells ? 8 * room_v : 0)), o_edges(st.region(host.edges ? 8 * room_q : 0)) {}
+    // the same outputs as the kernels see them, once the scratch is reserved
+    MeshOutputs on_device(const Staging &st, const MeshOutputs &host) const {
+        return {st.at<void>(o_vert), st.at<void>(o_quad), host.cells ? st.at<void>(o_cells) : nullptr, host.edges ? st.at<void>(o_edges) : nullptr,
+                st.at<void>(o_info), static_cast<int64_t>(room_v), static_cast<int64_t>(room_q)};
+    }
+};
+
 // How both host mesh entries end: the info comes back first, then of every output asked for what the mesher wrote of it --
 // min(info->n_vertices, room_v) records per vertex, min(info->n_quads, room_q) per quad.
-struct MeshOutput {
-    void *host;  // null: not asked for
-    size_t offset, bytes;
-    bool per_quad;
-};
-int read_mesh(rm_ctx *ctx, const Staging &st, rm_mesh_info *info, size_t o_info, size_t room_v, size_t room_q, std::initializer_list<MeshOutput> outputs) {
-    RM_HIP(ctx, st.out(info, o_info, sizeof *info));
+int read_mesh(rm_ctx *ctx, const Staging &st, const MeshRegions &r, const MeshOutputs &host) {
+    rm_mesh_info *info = static_cast<rm_mesh_info *>(host.info);
+    RM_HIP(ctx, st.out(info, r.o_info, sizeof *info));
     RM_HIP(ctx, st.sync());
-    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(room_v))),
-                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(room_q)));
-    for (const MeshOutput &o : outputs) {
-        const size_t got = o.per_quad ? got_q : got_v;
-        if (got && o.host) RM_HIP(ctx, st.out(o.host, o.offset, o.bytes * got));
-    }
+    const size_t got_v = static_cast<size_t>(std::min<int64_t>(info->n_vertices, static_cast<int64_t>(r.room_v))),
+                 got_q = static_cast<size_t>(std::min<int64_t>(info->n_quads, static_cast<int64_t>(r.room_q)));
+    const struct {
+        void *host;  // null: not asked for
+        size_t offset, bytes;
+    } outputs[] = {{host.vertices, r.o_vert, 12 * got_v}, {host.quads, r.o_quad, 16 * got_q}, {host.cells, r.o_cells, 8 * got_v}, {host.edges, r.o_edges, 8 * got_q}};
+    for (const auto &o : outputs)
+        if (o.bytes && o.host) RM_HIP(ctx, st.out(o.host, o.offset, o.bytes));
     RM_HIP(ctx, st.sync());
     return RM_OK;
 }
@@ -1981,6 +2029,17 @@ const char *sparse_error(const rm_lattice *l, SparseGrid *g, bool limit = true) 
     g->n_blocks = static_cast<int64_t>(g->nb[0]) * g->nb[1] * g->nb[2];
     if (limit && g->n_blocks > RM_SPARSE_MAX_BLOCKS) return "more than 2^24 blocks";
     return nullptr;
+}
+
+// What the sparse entries check about the kept blocks, in two parts because two of the three entries check other arguments in
+// between: n_kept in [0, min(n_blocks, cap)] (cap 0: none), and the list and the tiles once a block is kept.
+static_assert(RM_SPARSE_MAX_KEPT == 1 << 21, "the text of kept_range_error");
+const char *kept_range_error(const SparseGrid &g, int64_t n_kept, int64_t cap = 0) {
+    if (n_kept < 0 || n_kept > g.n_blocks || (cap && n_kept > cap)) return cap ? "n_kept must be in [0, min(n_blocks, 2^21)]" : "n_kept must be in [0, n_blocks]";
+    return nullptr;
+}
+const char *kept_buffers_error(int64_t n_kept, const void *list, const void *tiles) {
+    return n_kept > 0 && (!list || !tiles) ? "null list or tiles" : nullptr;
 }
 
 // lipschitz * R + slack of the header's rule, one binary64 operation at a time
@@ -2089,8 +2148,7 @@ struct SparseMeshCall {
     const void *slot, *list, *tiles;
     int64_t n_kept;
     double iso;
-    void *vertices, *quads, *cells, *edges, *info;
-    int64_t cap_vertices, cap_quads;
+    MeshOutputs out;
 };
 
 int launch_mesh_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const SparseMeshCall &m, uint32_t *d_map, uint32_t *d_totals,
@@ -2102,15 +2160,9 @@ int launch_mesh_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, c
     a.slot = static_cast<const int32_t *>(m.slot);
     a.list = static_cast<const int32_t *>(m.list);
     a.tiles = static_cast<const double *>(m.tiles);
-    a.vertices = static_cast<float *>(m.vertices);
-    a.quads = static_cast<uint32_t *>(m.quads);
-    a.cells = static_cast<long long *>(m.cells);
-    a.edges = static_cast<long long *>(m.edges);
-    a.info = static_cast<RmMeshInfo *>(m.info);
-    a.map = d_map;
-    a.totals = d_totals;
-    a.cap_vertices = m.cap_vertices;
-    a.cap_quads = m.cap_quads;
+    fill_mesh_outputs(a, m.out, d_map, d_totals);
+    a.cells = static_cast<long long *>(m.out.cells);
+    a.edges = static_cast<long long *>(m.out.edges);
     a.n_kept = static_cast<unsigned int>(m.n_kept);
     RM_HIP(ctx, rm_launch_mesh_tiles(a, stream, &ctx->last_kernel));
     return RM_OK;
@@ -3218,44 +3270,33 @@ int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const vo
 int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_vertices,
                          int64_t cap_vertices, void *d_quads, int64_t cap_quads, void *d_info, void *stream) {
     if (!ctx) return RM_E_INVALID;
-    const MeshCall m{lattice, true, d_values, value_type, iso, d_vertices, d_quads, d_info, cap_vertices, cap_quads};
+    const MeshCall m{lattice, true, d_values, value_type, iso, {d_vertices, d_quads, nullptr, nullptr, d_info, cap_vertices, cap_quads}};
     int64_t n = 0;
     bool cells = false;
-    int rc = check_mesh(ctx, m, &n, &cells);
-    if (rc) return rc;
+    if (const int rc = check_mesh(ctx, m, &n, &cells)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!cells) {  // no cell, no launch: the totals are zero
-        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
-        return RM_OK;
-    }
-    Staging st{ctx};
-    const size_t o_map = st.region(4 * static_cast<size_t>(n)), o_totals = st.region(12 * mesh_blocks(n));
-    if ((rc = st.reserve_for(s))) return rc;
-    rc = launch_mesh(ctx, st, m, n, d_values, value_type, d_vertices, d_quads, d_info, o_map, o_totals, s);
-    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
-    return rc;
+    // no cell, no launch: the totals are zero; else the map and the block totals
+    return scratch_call(ctx, s, cells, d_info, sizeof(rm_mesh_info), {4 * static_cast<size_t>(n), 12 * mesh_blocks(n)},
+                        [&](const Staging &st, const size_t *o) { return launch_mesh(ctx, st, m, n, o[0], o[1], s); });
 }
 
 int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *vertices, int64_t cap_vertices, uint32_t *quads,
                   int64_t cap_quads, rm_mesh_info *info) {
     if (!ctx) return RM_E_INVALID;
-    const MeshCall m{lattice, false, nullptr, RM_MESH_F64, iso, vertices, quads, info, cap_vertices, cap_quads};
+    const MeshCall m{lattice, false, nullptr, RM_MESH_F64, iso, {vertices, quads, nullptr, nullptr, info, cap_vertices, cap_quads}};
     int64_t n = 0;
     bool cells = false;
     int rc = check_mesh(ctx, m, &n, &cells);
     if (rc) return rc;
     std::memset(info, 0, sizeof *info);
     if (!cells) return RM_OK;
-    // The volume, the mesher's scratch and the outputs side by side in the scratch buffer.  The outputs are sized by the
-    // capacities -- memory the caller holds on the host anyway -- and by what the lattice can yield at most: a vertex per cell,
-    // three quads per point.
+    // The volume, the mesher's scratch and the outputs side by side in the scratch buffer; the lattice yields a vertex per cell
+    // and three quads per point at most.
     const int64_t n_cells = static_cast<int64_t>(lattice->nu - 1) * (lattice->nv - 1) * (lattice->nw - 1);
-    const size_t room_v = static_cast<size_t>(std::min(cap_vertices, n_cells)), room_q = static_cast<size_t>(std::min(cap_quads, 3 * n));
     RM_HIP(ctx, hipSetDevice(ctx->device));
     Staging st{ctx};
-    const size_t o_vol = st.region(8 * static_cast<size_t>(n)), o_map = st.region(4 * static_cast<size_t>(n)), o_totals = st.region(12 * mesh_blocks(n)),
-                 o_info = st.region(sizeof(rm_mesh_info)), o_vert = st.region(12 * room_v), o_quad = st.region(16 * room_q);
+    const size_t o_vol = st.region(8 * static_cast<size_t>(n)), o_map = st.region(4 * static_cast<size_t>(n)), o_totals = st.region(12 * mesh_blocks(n));
+    const MeshRegions r(st, m.out, n_cells, 3 * n);
     if ((rc = st.reserve())) return rc;
     RmRenderParams p;
     RmFieldArgs a;
@@ -3265,37 +3306,26 @@ int rm_scene_mesh(rm_ctx *ctx, const rm_lattice *lattice, double iso, float *ver
     a.first = 0;
     a.n = n;
     RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
-    MeshCall on_device = m;
-    on_device.cap_vertices = static_cast<int64_t>(room_v);
-    on_device.cap_quads = static_cast<int64_t>(room_q);
-    if ((rc = launch_mesh(ctx, st, on_device, n, st.at<void>(o_vol), RM_MESH_F64, st.at<void>(o_vert), st.at<void>(o_quad), st.at<void>(o_info), o_map,
-                          o_totals, ctx->stream)))
-        return rc;
-    return read_mesh(ctx, st, info, o_info, room_v, room_q, {{vertices, o_vert, 12, false}, {quads, o_quad, 16, true}});
+    const MeshCall on_device{lattice, true, st.at<void>(o_vol), RM_MESH_F64, iso, r.on_device(st, m.out)};
+    if ((rc = launch_mesh(ctx, st, on_device, n, o_map, o_totals, ctx->stream))) return rc;
+    return read_mesh(ctx, st, r, m.out);
 }
 
 int rm_mesh_cells_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_cells,
                          int64_t cap_vertices, void *d_info, void *stream) {
     if (!ctx) return RM_E_INVALID;
     if (reinterpret_cast<uintptr_t>(d_cells) & 7) return fail(ctx, RM_E_INVALID, "cells must be 8-byte aligned");
-    const MeshCall m{lattice, true, d_values, value_type, iso, d_cells, nullptr, d_info, cap_vertices, 0};
+    MeshCall m{lattice, true, d_values, value_type, iso, {d_cells, nullptr, nullptr, nullptr, d_info, cap_vertices, 0}};  // checked as the vertices are
     int64_t n = 0;
     bool cells = false;
-    int rc = check_mesh(ctx, m, &n, &cells);
-    if (rc) return rc;
+    if (const int rc = check_mesh(ctx, m, &n, &cells)) return rc;
+    m.out.vertices = nullptr;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!cells) {  // no cell, no launch: the totals are zero
-        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
+    // no cell, no launch: the totals are zero; else the block totals (no map: nothing reads one)
+    return scratch_call(ctx, s, cells, d_info, sizeof(rm_mesh_info), {12 * mesh_blocks(n)}, [&](const Staging &st, const size_t *o) -> int {
+        RM_HIP(ctx, rm_launch_mesh_cells(mesh_args(st, m, n, o[0], o[0]), static_cast<long long *>(d_cells), s, &ctx->last_kernel));
         return RM_OK;
-    }
-    Staging st{ctx};
-    const size_t o_totals = st.region(12 * mesh_blocks(n));
-    if ((rc = st.reserve_for(s))) return rc;
-    const RmMeshArgs a = mesh_args(st, m, n, d_values, value_type, nullptr, nullptr, d_info, o_totals, o_totals);  // (no map: nothing reads one)
-    RM_HIP(ctx, rm_launch_mesh_cells(a, static_cast<long long *>(d_cells), s, &ctx->last_kernel));
-    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
-    return RM_OK;
+    });
 }
 
 int rm_scene_sharpen_device(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_query *q, int64_t n, const void *d_cells, void *d_position,
@@ -3326,32 +3356,22 @@ int rm_scene_blocks_device(rm_ctx *ctx, const rm_lattice *lattice, double iso, d
     if (g.n_blocks > 0 && (!d_slot || !d_list)) return fail(ctx, RM_E_INVALID, "null slot or list");
     if (misaligned(d_slot, 3) || misaligned(d_list, 3)) return fail(ctx, RM_E_INVALID, "slot and list must be 4-byte aligned");
     if (misaligned(d_dist, 7) || misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "dist and info must be 8-byte aligned");
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (const int rc = need_device(ctx, "mesher", true)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!g.n_blocks) {  // no block, no launch
-        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_sparse_info), s));
-        return RM_OK;
-    }
-    Staging st{ctx};
-    const size_t o_totals = st.region(4 * sparse_groups(g.n_blocks));
-    int rc = st.reserve_for(s);
-    if (rc) return rc;
-    rc = launch_blocks(ctx, lattice, g, iso, lipschitz, d_slot, d_list, d_dist, d_info, st.at<uint32_t>(o_totals), s);
-    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
-    return rc;
+    // no block, no launch; else the scan's totals
+    return scratch_call(ctx, s, g.n_blocks > 0, d_info, sizeof(rm_sparse_info), {4 * sparse_groups(g.n_blocks)}, [&](const Staging &st, const size_t *o) {
+        return launch_blocks(ctx, lattice, g, iso, lipschitz, d_slot, d_list, d_dist, d_info, st.at<uint32_t>(o[0]), s);
+    });
 }
 
 int rm_scene_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_list, int64_t n_kept, void *d_tiles, void *stream) {
     if (!ctx) return RM_E_INVALID;
     SparseGrid g;
     if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
-    if (n_kept < 0 || n_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, n_blocks]");
-    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
+    if (const char *bad = kept_range_error(g, n_kept)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = kept_buffers_error(n_kept, d_list, d_tiles)) return fail(ctx, RM_E_INVALID, bad);
     if (misaligned(d_list, 3) || misaligned(d_tiles, 7)) return fail(ctx, RM_E_INVALID, "list must be 4-byte and tiles 8-byte aligned");
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (const int rc = need_device(ctx, "distance path", true)) return rc;
     if (!n_kept) return RM_OK;
     RM_HIP(ctx, hipSetDevice(ctx->device));
     return launch_tiles(ctx, lattice, g, d_list, n_kept, d_tiles, static_cast<hipStream_t>(stream));
@@ -3367,10 +3387,10 @@ int rm_scene_tiles_update_device(rm_ctx *ctx, const rm_lattice *lattice, const v
     if (!ctx) return RM_E_INVALID;
     SparseGrid g;
     if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
-    if (n_kept < 0 || n_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, n_blocks]");
+    if (const char *bad = kept_range_error(g, n_kept)) return fail(ctx, RM_E_INVALID, bad);
     if (n_prev_kept < 0 || n_prev_kept > g.n_blocks) return fail(ctx, RM_E_INVALID, "n_prev_kept must be in [0, n_blocks]");
     if (n_balls < 0 || n_balls > RM_TILES_UPDATE_MAX_BALLS) return fail(ctx, RM_E_INVALID, "n_balls must be in [0, 65536]");
-    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
+    if (const char *bad = kept_buffers_error(n_kept, d_list, d_tiles)) return fail(ctx, RM_E_INVALID, bad);
     if (n_kept > 0 && !d_prev_slot) return fail(ctx, RM_E_INVALID, "null previous slot map");
     if (n_kept > 0 && n_prev_kept > 0 && !d_prev_tiles) return fail(ctx, RM_E_INVALID, "null previous tiles");
     if (n_balls > 0 && !d_balls) return fail(ctx, RM_E_INVALID, "null balls");
@@ -3383,25 +3403,19 @@ int rm_scene_tiles_update_device(rm_ctx *ctx, const rm_lattice *lattice, const v
         const uintptr_t na = static_cast<uintptr_t>(n_kept) * 8 * RM_SPARSE_TILE, nb = static_cast<uintptr_t>(n_prev_kept) * 8 * RM_SPARSE_TILE;
         if (d_tiles && d_prev_tiles && na && nb && a < b + nb && b < a + na) return fail(ctx, RM_E_INVALID, "tiles and previous tiles overlap");
     }
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU distance path");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    if (const int rc = need_device(ctx, "distance path", true)) return rc;
     if (ctx->host.program) return fail(ctx, RM_E_UNSUPPORTED, "expression-program scenes take the full path: rm_scene_tiles_device with option exact");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!n_kept) {  // no kept block, no launch: the totals are zero
-        if (d_info) RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_tiles_update_info), s));
-        return RM_OK;
-    }
     TilesUpdateCall c{d_prev_slot, d_prev_tiles, d_balls, n_prev_kept, n_balls, d_reused, d_info};
-    if (d_reused || !d_info) return launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
-    Staging st{ctx};  // the totals without the caller's flags: the flags live in the scratch
-    const size_t o_flags = st.region(4 * static_cast<size_t>(n_kept));
-    int rc = st.reserve_for(s);
-    if (rc) return rc;
-    c.reused = st.at<void>(o_flags);
-    rc = launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
-    RM_HIP(ctx, st.keep(s));  // the kernels touch the scratch after this call returns
-    return rc;
+    if (n_kept && (d_reused || !d_info)) {  // nothing of it lives in the scratch
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        return launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
+    }
+    // no kept block, no launch: the totals are zero; else the totals without the caller's flags: the flags live in the scratch
+    return scratch_call(ctx, s, n_kept > 0, d_info, sizeof(rm_tiles_update_info), {4 * static_cast<size_t>(n_kept)}, [&](const Staging &st, const size_t *o) {
+        c.reused = st.at<void>(o[0]);
+        return launch_tiles_update(ctx, lattice, g, c, d_list, n_kept, d_tiles, s);
+    });
 }
 
 int rm_mesh_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept, const void *d_tiles, double iso,
@@ -3410,28 +3424,21 @@ int rm_mesh_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_s
     if (!ctx) return RM_E_INVALID;
     SparseGrid g;
     if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
-    if (n_kept < 0 || n_kept > g.n_blocks || n_kept > RM_SPARSE_MAX_KEPT) return fail(ctx, RM_E_INVALID, "n_kept must be in [0, min(n_blocks, 2^21)]");
+    const SparseMeshCall m{d_slot, d_list, d_tiles, n_kept, iso, {d_vertices, d_quads, d_cells, d_edges, d_info, cap_vertices, cap_quads}};
+    if (const char *bad = kept_range_error(g, n_kept, RM_SPARSE_MAX_KEPT)) return fail(ctx, RM_E_INVALID, bad);
     if (!d_info) return fail(ctx, RM_E_INVALID, "null info");
     if (g.n_blocks > 0 && !d_slot) return fail(ctx, RM_E_INVALID, "null slot");
-    if (n_kept > 0 && (!d_list || !d_tiles)) return fail(ctx, RM_E_INVALID, "null list or tiles");
-    if (const char *bad = mesh_outputs_error(iso, d_vertices, cap_vertices, d_quads, cap_quads, d_cells, d_edges)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = kept_buffers_error(n_kept, d_list, d_tiles)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = mesh_outputs_error(iso, m.out)) return fail(ctx, RM_E_INVALID, bad);
     if (misaligned(d_slot, 3) || misaligned(d_list, 3)) return fail(ctx, RM_E_INVALID, "slot and list must be 4-byte aligned");
     if (misaligned(d_tiles, 7) || misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "tiles and info must be 8-byte aligned");
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
+    if (const int rc = need_device(ctx, "mesher", false)) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    if (!n_kept) {  // no kept block, no launch: the totals are zero
-        RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_mesh_info), s));
-        return RM_OK;
-    }
-    Staging st{ctx};
-    const size_t k = static_cast<size_t>(n_kept), o_map = st.region(4 * RM_SPARSE_CELLS * k), o_totals = st.region(12 * k);
-    int rc = st.reserve_for(s);
-    if (rc) return rc;
-    const SparseMeshCall m{d_slot, d_list, d_tiles, n_kept, iso, d_vertices, d_quads, d_cells, d_edges, d_info, cap_vertices, cap_quads};
-    rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), s);
-    RM_HIP(ctx, st.keep(s));  // the kernels read the scratch after this call returns
-    return rc;
+    const size_t k = static_cast<size_t>(n_kept);
+    // no kept block, no launch: the totals are zero; else the map and the totals per kept block
+    return scratch_call(ctx, s, n_kept > 0, d_info, sizeof(rm_mesh_info), {4 * RM_SPARSE_CELLS * k, 12 * k}, [&](const Staging &st, const size_t *o) {
+        return launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o[0]), st.at<uint32_t>(o[1]), s);
+    });
 }
 
 int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, float *vertices, int64_t cap_vertices, uint32_t *quads,
@@ -3441,9 +3448,9 @@ int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, dou
     if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
     if (!info) return fail(ctx, RM_E_INVALID, "null info");
     if (!std::isfinite(lipschitz) || !(lipschitz > 0.0)) return fail(ctx, RM_E_INVALID, "lipschitz must be finite and > 0");
-    if (const char *bad = mesh_outputs_error(iso, vertices, cap_vertices, quads, cap_quads, cells, edges)) return fail(ctx, RM_E_INVALID, bad);
-    if (!ctx->has_device) return fail(ctx, RM_E_NO_DEVICE, "host-only context: there is no CPU mesher");
-    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    const MeshOutputs host{vertices, quads, cells, edges, info, cap_vertices, cap_quads};
+    if (const char *bad = mesh_outputs_error(iso, host)) return fail(ctx, RM_E_INVALID, bad);
+    if (const int nrc = need_device(ctx, "mesher", true)) return nrc;
     std::memset(info, 0, sizeof *info);
     rm_sparse_info si;
     std::memset(&si, 0, sizeof si);
@@ -3466,14 +3473,11 @@ int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, dou
     const int64_t n_kept = si.n_kept;
     if (n_kept <= 0) return RM_OK;
     if (n_kept > RM_SPARSE_MAX_KEPT) return fail(ctx, RM_E_UNSUPPORTED, "more than 2^21 kept blocks: vertex numbers are 32-bit");
-    // Steps 2 and 3 behind the same four regions: the tiles, the mesher's scratch and the outputs, sized by the capacities and by
-    // what the kept blocks can yield at most (a vertex per cell, three quads per cell).
+    // Steps 2 and 3 behind the same four regions: the tiles, the mesher's scratch and the outputs; the kept blocks yield a vertex
+    // per cell and three quads per cell at most.
     const size_t k = static_cast<size_t>(n_kept);
-    const size_t room_v = static_cast<size_t>(std::min<int64_t>(cap_vertices, RM_SPARSE_CELLS * n_kept)),
-                 room_q = static_cast<size_t>(std::min<int64_t>(cap_quads, 3 * RM_SPARSE_CELLS * n_kept));
-    const size_t o_tiles = st.region(8 * RM_SPARSE_TILE * k), o_map = st.region(4 * RM_SPARSE_CELLS * k), o_totals = st.region(12 * k),
-                 o_info = st.region(sizeof(rm_mesh_info)), o_vert = st.region(12 * room_v), o_quad = st.region(16 * room_q),
-                 o_cells = st.region(cells ? 8 * room_v : 0), o_edges = st.region(edges ? 8 * room_q : 0);
+    const size_t o_tiles = st.region(8 * RM_SPARSE_TILE * k), o_map = st.region(4 * RM_SPARSE_CELLS * k), o_totals = st.region(12 * k);
+    const MeshRegions r(st, host, RM_SPARSE_CELLS * n_kept, 3 * RM_SPARSE_CELLS * n_kept);
     if (st.total > ctx->scratch_bytes) {  // the scratch has to grow, which frees it: the map and the list go through the host
         std::vector<int32_t> slot(nb), list(k);
         RM_HIP(ctx, st.out(slot.data(), o_slot, 4 * nb));
@@ -3485,12 +3489,9 @@ int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, dou
         RM_HIP(ctx, st.sync());  // (the vectors end here)
     }
     if ((rc = launch_tiles(ctx, lattice, g, st.at<void>(o_list), n_kept, st.at<void>(o_tiles), ctx->stream))) return rc;
-    const SparseMeshCall m{st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_tiles), n_kept, iso, st.at<void>(o_vert), st.at<void>(o_quad),
-                           cells ? st.at<void>(o_cells) : nullptr, edges ? st.at<void>(o_edges) : nullptr, st.at<void>(o_info),
-                           static_cast<int64_t>(room_v), static_cast<int64_t>(room_q)};
+    const SparseMeshCall m{st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_tiles), n_kept, iso, r.on_device(st, host)};
     if ((rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), ctx->stream))) return rc;
-    return read_mesh(ctx, st, info, o_info, room_v, room_q,
-                     {{vertices, o_vert, 12, false}, {quads, o_quad, 16, true}, {cells, o_cells, 8, false}, {edges, o_edges, 8, true}});
+    return read_mesh(ctx, st, r, host);
 }
 
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {

@@ -99,14 +99,7 @@ __global__ __launch_bounds__(kBlock) void mesh_vertex_kernel(RmMeshArgs a) {
     unsigned total;
     const unsigned r = a.totals[blockIdx.x] + block_rank<1>(act, s_sums, &total);
     if (l < a.n) a.map[l] = act[0] ? r : kNone;
-    if (act[0] && static_cast<long long>(r) < a.cap_vertices) {
-        float p[3];
-        vertex_position(a, c, v, p);
-        float *out = a.vertices + 3ull * r;
-        out[0] = p[0];
-        out[1] = p[1];
-        out[2] = p[2];
-    }
+    if (act[0]) store_vertex(a, c, v, r, nullptr);
 }
 
 template <typename T>
@@ -134,14 +127,7 @@ __global__ __launch_bounds__(kBlock) void mesh_quad_kernel(RmMeshArgs a) {
 #pragma unroll
     for (int A = 0; A < 3; ++A) {
         if (!quad[A]) continue;
-        if (static_cast<long long>(q) < a.cap_quads) {  // counter-clockwise seen from +A when the point is inside
-            const bool in = c.inside & 1u;
-            uint32_t *out = a.quads + 4ull * q;
-            out[0] = ring[A][0];
-            out[1] = ring[A][in ? 1 : 3];
-            out[2] = ring[A][2];
-            out[3] = ring[A][in ? 3 : 1];
-        }
+        store_quad(a, c, ring[A], q, nullptr, 0, A);
         ++q;
     }
 }

@@ -1,6 +1,6 @@
 // rm_mesh_device.h -- what the two surface-nets meshers share on the device (rm_mesh.hip over a dense volume, rm_mesh_sparse.hip
-// over 9 x 9 x 9 tiles): the cell record, the ballot ranks, the scan of the workgroup totals and the vertex position.  The rule
-// is the contract of include/rm_raymarch.h ("meshes"); both files keep to it through these functions.
+// over 9 x 9 x 9 tiles): the cell record, the ballot ranks, the scan of the workgroup totals, the vertex position and the stores
+// of a vertex and of a quad.  The rule is the contract of include/rm_raymarch.h ("meshes"); both files keep to it through these.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -141,6 +141,40 @@ __device__ __forceinline__ void vertex_position(const ARGS &a, const Cell &c, co
                  fk = static_cast<double>(c.k) + sum[2] / count;
 #pragma unroll
     for (int n = 0; n < 3; ++n) out[n] = static_cast<float>(rm_lattice_component(a.lat, n, fi, fj, fk));
+}
+
+// the key of a cell: the linear index of its low corner in the lattice
+template <typename ARGS>
+__device__ __forceinline__ long long cell_key(const ARGS &a, const Cell &c) {
+    return (static_cast<long long>(c.k) * a.nv + c.j) * a.nu + c.i;
+}
+
+// Vertex n of the mesh, the one of the active cell c, where the capacity has room for it; `cells` (may be null): its key too.
+template <typename ARGS>
+__device__ __forceinline__ void store_vertex(const ARGS &a, const Cell &c, const double (&v)[8], unsigned n, long long *cells) {
+    if (static_cast<long long>(n) >= a.cap_vertices) return;
+    float p[3];
+    vertex_position(a, c, v, p);
+    float *out = a.vertices + 3ull * n;
+    out[0] = p[0];
+    out[1] = p[1];
+    out[2] = p[2];
+    if (cells) cells[n] = cell_key(a, c);
+}
+
+// Quad q of the mesh where the capacity has room for it: the ring of the four cells' vertices around the edge from the point
+// of cell c towards +A, counter-clockwise seen from +A when the point is inside; `edges` (may be null): its key 3 l + A too.
+// (The loop over A stays with the kernels: in here it turns the ring into a run-time indexed vector, 40 VGPRs for 26.)
+template <typename ARGS>
+__device__ __forceinline__ void store_quad(const ARGS &a, const Cell &c, const uint32_t (&ring)[4], unsigned q, long long *edges, long long l, int A) {
+    if (static_cast<long long>(q) >= a.cap_quads) return;
+    const bool in = c.inside & 1u;
+    uint32_t *out = a.quads + 4ull * q;
+    out[0] = ring[0];
+    out[1] = ring[in ? 1 : 3];
+    out[2] = ring[2];
+    out[3] = ring[in ? 3 : 1];
+    if (edges) edges[q] = 3ll * l + A;
 }
 
 }  // namespace

@@ -197,15 +197,7 @@ __global__ __launch_bounds__(kBlock) void mesh_tiles_vertex_kernel(RmSparseMeshA
         const unsigned n = first + block_rank<1>(act, s_sums[h], &total);
         first += total;
         a.map[static_cast<size_t>(r) * kCells + local] = act[0] ? n : kNone;
-        if (act[0] && static_cast<long long>(n) < a.cap_vertices) {
-            float p[3];
-            vertex_position(a, c, v, p);
-            float *out = a.vertices + 3ull * n;
-            out[0] = p[0];
-            out[1] = p[1];
-            out[2] = p[2];
-            if (a.cells) a.cells[n] = (static_cast<long long>(c.k) * a.nv + c.j) * a.nu + c.i;
-        }
+        if (act[0]) store_vertex(a, c, v, n, a.cells);
     }
 }
 
@@ -248,19 +240,11 @@ __global__ __launch_bounds__(kBlock) void mesh_tiles_quad_kernel(RmSparseMeshArg
         unsigned total;
         unsigned q = first + block_rank<3>(quad, s_sums[h], &total);
         first += total;
-        const long long l = (static_cast<long long>(c.k) * a.nv + c.j) * a.nu + c.i;
+        const long long l = cell_key(a, c);
 #pragma unroll
         for (int A = 0; A < 3; ++A) {
             if (!quad[A]) continue;
-            if (static_cast<long long>(q) < a.cap_quads) {  // counter-clockwise seen from +A when the point is inside
-                const bool in = c.inside & 1u;
-                uint32_t *out = a.quads + 4ull * q;
-                out[0] = ring[A][0];
-                out[1] = ring[A][in ? 1 : 3];
-                out[2] = ring[A][2];
-                out[3] = ring[A][in ? 3 : 1];
-                if (a.edges) a.edges[q] = 3ll * l + A;
-            }
+            store_quad(a, c, ring[A], q, a.edges, l, A);
             ++q;
         }
     }

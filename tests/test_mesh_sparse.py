@@ -630,6 +630,49 @@ def test_the_host_entry_equals_the_device_path_and_has_no_side_effects(rm, oracl
 
 
 @pytest.mark.gpu
+def test_the_host_entry_on_a_fresh_context_grows_the_scratch_between_its_steps(rm, oracle, sctx):
+    """The first mesh call of a context whose scratch is empty: the coarse pass reserves a few kilobytes, the tiles and the
+    outputs need far more, so the slot map and the list cross the host while the scratch grows.  Everything equals the three
+    device entries on the module's context, byte for byte."""
+    N = rm._native
+    lat = scene_lattice(rm, time=0.4)
+    load(rm, oracle, sctx, "smooth", "None")
+    _, lst, _, binfo, (d_slot, d_list) = run_blocks(rm, sctx, lat, 0.1, 1.0)
+    want = full_mesh(rm, sctx, lat, d_slot, d_list, len(lst), run_tiles(rm, sctx, lat, d_list, len(lst)), 0.1)
+    V, Q = int(want[4][0]), int(want[4][1])
+    assert V > 100 and Q > 100 and int(binfo[0]) == 100
+    with rm.Context(0) as fresh:
+        fresh.set_option("specialise", 0)
+        load(rm, oracle, fresh, "smooth", "None")
+        v, q = np.full((V, 3), -1, np.float32), np.full((Q, 4), 7, np.uint32)
+        cells, edges = np.full(V, -1, np.int64), np.full(Q, -1, np.int64)
+        info, sinfo = N.rm_mesh_info(-1, -1, -1, -1), N.rm_sparse_info(-1, -1)
+        N.check(fresh._h, N.lib().rm_scene_mesh_sparse(fresh._h, C.byref(lat), 0.1, 1.0, vp(v), V, vp(q), Q, vp(cells), vp(edges), C.byref(info),
+                                                       C.byref(sinfo)))
+    assert_model_mesh((v, q, cells, edges, np.frombuffer(bytes(info), np.int64)), want, "fresh context")
+    assert bytes(sinfo) == binfo.tobytes()
+
+
+@pytest.mark.gpu
+def test_every_stage_of_the_epilogue_at_once_dense_against_sparse(rm, oracle, sctx):
+    """Sharp vertices, the winding flip of a left-handed lattice, triangles and the attribute pass with a snap, all in one call:
+    `mesh` against `mesh_sparse(order="dense")`, as numpy arrays and as device tensors."""
+    load(rm, oracle, sctx, "grid", "BVH").updateTime(0.0)
+    vecs = vectors(scene_lattice(rm))
+    left, lshape = (vecs[0], vecs[2], vecs[1], vecs[3]), (vecs[5], vecs[4], vecs[6])
+    for device in (False, True):
+        more = dict(triangles=True, attributes=True, snap=2, sharp=True, device=device)
+        a, b = sctx.mesh(*left, lshape, **more), sctx.mesh_sparse(*left, lshape, order="dense", **more)
+        assert len(a) == len(b) == 4
+        if device:
+            assert all(t.is_cuda for t in a + b)
+            a, b = [t.cpu().numpy() for t in a], [t.cpu().numpy() for t in b]
+        assert len(a[0]) > 100 and a[1].shape == (len(a[1]), 3)
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and x.shape == y.shape and same_bits(x, y)
+
+
+@pytest.mark.gpu
 def test_the_python_mirror(rm, oracle, sctx):
     sc = load(rm, oracle, sctx, "grid", "BVH")
     sc.updateTime(0.0)
