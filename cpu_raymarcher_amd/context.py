@@ -29,24 +29,43 @@ def _ptr(x):
 _BPP = {"depth": 1, "normal": 3, "sdf": 2, "iters": 2, "rgba": 4}
 
 
+_MIXED = "buffers must be all on the host or all on the device"
+
+
+def _describe(name, x):
+    """The C ABI takes raw pointers: what it assumes about a buffer is read here, in one place.  A torch tensor or
+    a numpy array -> (on the device, C-contiguous, bytes per element, bytes, writable).  (A plain tuple: these checks are
+    host time on every call, and a named one costs half a microsecond per buffer.)"""
+    if _is_torch(x):
+        e = x.element_size()
+        return x.is_cuda, x.is_contiguous(), e, x.numel() * e, True
+    if isinstance(x, np.ndarray):
+        f = x.flags
+        return False, f["C_CONTIGUOUS"], x.itemsize, x.nbytes, f["WRITEABLE"]
+    raise ValueError("%s must be a numpy array or a torch tensor, not %s" % (name, type(x).__name__))
+
+
+def _bytes_on(device, x):
+    """The bytes of `x` when it is a contiguous CUDA tensor (device) or a writable contiguous numpy array (not device), else -1."""
+    try:
+        on_dev, contiguous, _, nbytes, writable = _describe("", x)
+    except ValueError:
+        return -1
+    return nbytes if on_dev == device and contiguous and writable and (device or isinstance(x, np.ndarray)) else -1
+
+
 def _check_buffers(npx, bufs, need_device=None):
-    """The C ABI takes raw pointers: everything it assumes about a buffer is checked here.  bufs: name -> buffer
-    or None.  Every buffer must be C-contiguous, of the reference's element size (depth / normal / rgba 1 byte, sdf / iters
-    2 bytes: Uint8ClampedArray / Uint16Array) and hold at least npx pixels; all of them on the host or all on one
-    device.  Returns True when they are device (torch CUDA) buffers."""
+    """bufs: name -> buffer or None.  Every buffer must be C-contiguous, of the reference's element size (depth / normal / rgba
+    1 byte, sdf / iters 2 bytes: Uint8ClampedArray / Uint16Array) and hold at least npx pixels; all of them on the host or
+    all on one device.  Returns True when they are device (torch CUDA) buffers."""
     on_dev = None
     for name, b in bufs.items():
         if b is None:
             continue
         esz = 2 if name in ("sdf", "iters") else 1
-        if _is_torch(b):
-            dev, contiguous, itemsize, nbytes = b.is_cuda, b.is_contiguous(), b.element_size(), b.numel() * b.element_size()
-        elif isinstance(b, np.ndarray):
-            dev, contiguous, itemsize, nbytes = False, b.flags["C_CONTIGUOUS"], b.itemsize, b.nbytes
-            if not b.flags["WRITEABLE"] and name != "_in":
-                raise ValueError("%s buffer is read-only" % name)
-        else:
-            raise ValueError("%s must be a numpy array or a torch tensor, not %s" % (name, type(b).__name__))
+        dev, contiguous, itemsize, nbytes, writable = _describe(name, b)
+        if not writable and name != "_in":
+            raise ValueError("%s buffer is read-only" % name)
         if not contiguous:
             raise ValueError("%s buffer must be C-contiguous" % name)
         if itemsize != esz and not (dev and itemsize == 1):  # device side: byte views into a packed gather buffer are fine
@@ -56,13 +75,27 @@ def _check_buffers(npx, bufs, need_device=None):
         if on_dev is None:
             on_dev = dev
         elif on_dev != dev:
-            raise ValueError("buffers must be all on the host or all on the device")
+            raise ValueError(_MIXED)
     if need_device is not None and on_dev is not None and on_dev != need_device:
         raise ValueError("this entry point takes %s buffers" % ("device" if need_device else "host"))
     return bool(on_dev)
 
 
-def _check_pixel_sets(npx, bufs, rgba, stats, stats_bytes):
+def _check_records(name, buf, each, n_frames, on_dev):
+    """A buffer of one record of `each` bytes per frame (rm_compare_stats 128, rm_frame_hist 2 128), on the side the pixel
+    buffers are on (on_dev None: either).  Returns its side."""
+    try:
+        dev, contiguous, _, nbytes, _ = _describe(name, buf)
+    except ValueError:
+        raise ValueError("%s must be a numpy array or a torch tensor" % name) from None
+    if not contiguous or nbytes < each * max(0, n_frames):
+        raise ValueError("%s must be a contiguous buffer of %d bytes per frame" % (name, each))
+    if on_dev is not None and on_dev != dev:
+        raise ValueError(_MIXED)
+    return dev
+
+
+def _check_pixel_sets(npx, bufs, rgba, stats, n_frames):
     """_check_buffers for compare_frames: bufs maps depth_a .. iters_b to buffers or None.  Returns True for device buffers."""
     on_dev = None
     for name, b in list(bufs.items()) + [("rgba", rgba)]:
@@ -70,34 +103,16 @@ def _check_pixel_sets(npx, bufs, rgba, stats, stats_bytes):
             continue
         d = _check_buffers(npx, {name.split("_")[0]: b})
         if on_dev is not None and on_dev != d:
-            raise ValueError("buffers must be all on the host or all on the device")
+            raise ValueError(_MIXED)
         on_dev = d
     if stats is not None:
-        d = bool(_is_torch(stats) and stats.is_cuda)
-        if not (_is_torch(stats) or isinstance(stats, np.ndarray)):
-            raise ValueError("stats must be a numpy array or a torch tensor")
-        contiguous = stats.is_contiguous() if _is_torch(stats) else stats.flags["C_CONTIGUOUS"]
-        nbytes = stats.numel() * stats.element_size() if _is_torch(stats) else stats.nbytes
-        if not contiguous or nbytes < stats_bytes:
-            raise ValueError("stats must be a contiguous buffer of 128 bytes per frame")
-        if on_dev is not None and on_dev != d:
-            raise ValueError("buffers must be all on the host or all on the device")
-        on_dev = d
+        on_dev = _check_records("stats", stats, 128, n_frames, on_dev)
     return bool(on_dev)
 
 
-def _check_records(hist, n_frames, on_dev):
-    """A buffer of one rm_frame_hist (2 128 bytes) per frame, on the side the pixel buffers are on (on_dev None: either)."""
-    if not (_is_torch(hist) or isinstance(hist, np.ndarray)):
-        raise ValueError("hist must be a numpy array or a torch tensor")
-    d = bool(_is_torch(hist) and hist.is_cuda)
-    contiguous = hist.is_contiguous() if _is_torch(hist) else hist.flags["C_CONTIGUOUS"]
-    nbytes = hist.numel() * hist.element_size() if _is_torch(hist) else hist.nbytes
-    if not contiguous or nbytes < 2128 * max(0, n_frames):
-        raise ValueError("hist must be a contiguous buffer of 2128 bytes per frame")
-    if on_dev is not None and on_dev != d:
-        raise ValueError("buffers must be all on the host or all on the device")
-    return d
+def _compare_map(map):
+    """A name of COMPARE_MAPS or an rm_compare_map value -> the value."""
+    return N.COMPARE_MAPS[map] if isinstance(map, str) else int(map)
 
 
 def percentile(record, permille):
@@ -563,24 +578,13 @@ class Context:
         for name, b in (("lit", lit), ("ao", ao)):
             if b is None:
                 continue
-            if _is_torch(b):
-                import torch
-                ok, dev, count = b.dtype == torch.float32 and b.is_contiguous(), b.is_cuda, b.numel()
-            elif isinstance(b, np.ndarray):
-                ok, dev, count = b.dtype == np.float32 and b.flags["C_CONTIGUOUS"], False, b.size
-            else:
-                raise ValueError("%s must be a numpy array or a torch tensor, not %s" % (name, type(b).__name__))
-            if not ok or count < npx:
+            dev, contiguous, _, nbytes, _ = _describe(name, b)
+            if str(b.dtype) not in ("float32", "torch.float32") or not contiguous or nbytes < 4 * npx:
                 raise ValueError("%s must be a contiguous float32 buffer of one element per pixel" % name)
             if dev != on_dev and (depth is not None or normal is not None or rgba is not None):
-                raise ValueError("buffers must be all on the host or all on the device")
+                raise ValueError(_MIXED)
         self._same_device(dict(depth=depth, normal=normal, lit=lit, ao=ao, rgba=rgba))
-        if on_dev:
-            N.check(self._h, N.lib().rm_shade_lit_device(self._h, int(width), int(rows), n, _ptr(depth), _ptr(normal), _ptr(lit), _ptr(ao),
-                                                         _ptr(rgba), _current_stream_ptr()))
-        else:
-            N.check(self._h, N.lib().rm_shade_lit(self._h, int(width), int(rows), n, _ptr(depth), _ptr(normal), _ptr(lit), _ptr(ao),
-                                                  _ptr(rgba)))
+        self._both("rm_shade_lit", on_dev, int(width), int(rows), n, _ptr(depth), _ptr(normal), _ptr(lit), _ptr(ao), _ptr(rgba))
         return rgba
 
     def scene_object(self, index):
@@ -600,7 +604,7 @@ class Context:
         receives (total_sdf, total_iters, max_sdf | min_sdf << 32, pad) of the pixels that call renders (decode_acc)."""
         if diag is None:
             return
-        if not (_is_torch(diag) and diag.is_cuda and diag.is_contiguous() and diag.numel() * diag.element_size() >= 32):
+        if _bytes_on(True, diag) < 32:
             raise ValueError("diag must be a contiguous CUDA tensor of 32 bytes")
         self._same_device(dict(diag=diag))
         N.check(self._h, N.lib().rm_render_attach_diagnostics(self._h, _ptr(diag)))
@@ -640,7 +644,7 @@ class Context:
         _check_buffers(npx * n, bufs, need_device=True)
         self._same_device(bufs)
         if diag is not None:
-            if not (_is_torch(diag) and diag.is_cuda and diag.is_contiguous() and diag.numel() * diag.element_size() >= 32 * n):
+            if _bytes_on(True, diag) < 32 * n:
                 raise ValueError("diag must be a contiguous CUDA tensor of 32 bytes per view")
             self._same_device(dict(diag=diag))
         N.check(self._h, N.lib().rm_render_frames_device(
@@ -663,22 +667,17 @@ class Context:
             if len(a) != 4 or len(b) != 4:
                 raise ValueError("a and b are (depth, normal, sdf, iters)")
             sides = [N.rm_frame_set(*[getattr(_ptr(x), "value", None) for x in side]) for side in (a, b)]
-        m = N.COMPARE_MAPS[map] if isinstance(map, str) else int(map)
+        m = _compare_map(map)
         n = int(n_frames)
         npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
         bufs = {}
         for side, tag in ((a, "_a"), (b, "_b")):
             for name, x in zip(("depth", "normal", "sdf", "iters"), side or ()):
                 bufs[name + tag] = x
-        on_dev = _check_pixel_sets(npx, bufs, rgba, stats, 128 * max(0, n))
+        on_dev = _check_pixel_sets(npx, bufs, rgba, stats, n)
         self._same_device(dict(bufs, rgba=rgba, stats=stats))
         refs = [None if x is None else C.byref(x) for x in sides]
-        if on_dev:
-            N.check(self._h, N.lib().rm_compare_frames_device(self._h, int(width), int(rows), n, refs[0], refs[1], m, int(gain),
-                                                              _ptr(rgba), _ptr(stats), _current_stream_ptr()))
-        else:
-            N.check(self._h, N.lib().rm_compare_frames(self._h, int(width), int(rows), n, refs[0], refs[1], m, int(gain),
-                                                       _ptr(rgba), _ptr(stats)))
+        self._both("rm_compare_frames", on_dev, int(width), int(rows), n, refs[0], refs[1], m, int(gain), _ptr(rgba), _ptr(stats))
 
     @staticmethod
     def decode_compare_stats(buf):
@@ -716,7 +715,7 @@ class Context:
                 self.render_frames(job, views, *g, rgba=img, shader=shader or 0)
             sets.append(g)
             shaded.append(img)
-        m = N.COMPARE_MAPS[map] if isinstance(map, str) else int(map)
+        m = _compare_map(map)
         rgba = None if m < 0 else torch.empty(4 * total, dtype=torch.uint8, device=dev)
         stats = torch.empty(128 * n, dtype=torch.uint8, device=dev)
         self.compare_frames(sets[0], sets[1], rgba=rgba, map=m, gain=gain, stats=stats, width=W, rows=rows, n_frames=n)
@@ -738,25 +737,20 @@ class Context:
         npx = max(0, int(width)) * max(0, int(rows)) * max(0, n)
         bufs = dict(sdf=sdf, iters=iters, normal=normal)
         on_dev = _check_buffers(npx, bufs)
-        some = next((b for b in bufs.values() if b is not None), None)
-        if some is None:
-            on_dev = None if hist is None else bool(_is_torch(hist) and hist.is_cuda)
+        if sdf is None and iters is None and normal is None:
+            on_dev = None  # (no pixel buffer: the records decide the side)
         if hist is None:
             if on_dev:
                 import torch
+                some = next(b for b in bufs.values() if b is not None)
                 hist = torch.empty(2128 * max(0, n), dtype=torch.uint8, device=some.device)
             else:
                 hist = np.zeros(2128 * max(0, n), np.uint8)
                 on_dev = False
-        on_dev = _check_records(hist, n, on_dev)
+        on_dev = _check_records("hist", hist, 2128, n, on_dev)
         self._same_device(dict(bufs, hist=hist))
         lo, hi = (int(x) for x in percentiles)
-        if on_dev:
-            N.check(self._h, N.lib().rm_counter_hist_device(self._h, int(width), int(rows), n, _ptr(sdf), _ptr(iters), _ptr(normal), m,
-                                                            int(bin_shift), lo, hi, _ptr(hist), _current_stream_ptr()))
-        else:
-            N.check(self._h, N.lib().rm_counter_hist(self._h, int(width), int(rows), n, _ptr(sdf), _ptr(iters), _ptr(normal), m,
-                                                     int(bin_shift), lo, hi, _ptr(hist)))
+        self._both("rm_counter_hist", on_dev, int(width), int(rows), n, _ptr(sdf), _ptr(iters), _ptr(normal), m, int(bin_shift), lo, hi, _ptr(hist))
         return hist
 
     @staticmethod
@@ -789,14 +783,9 @@ class Context:
         bufs = dict(sdf=values, rgba=rgba)
         on_dev = _check_buffers(npx, bufs)
         if hist is not None:
-            _check_records(hist, n, on_dev if (values is not None or rgba is not None) else None)
+            _check_records("hist", hist, 2128, n, on_dev if (values is not None or rgba is not None) else None)
         self._same_device(dict(bufs, hist=hist))
-        if on_dev:
-            N.check(self._h, N.lib().rm_shade_ranged_device(self._h, c, int(width), int(rows), n, _ptr(values), _ptr(hist), int(lo), int(hi),
-                                                            _ptr(rgba), _current_stream_ptr()))
-        else:
-            N.check(self._h, N.lib().rm_shade_ranged(self._h, c, int(width), int(rows), n, _ptr(values), _ptr(hist), int(lo), int(hi),
-                                                     _ptr(rgba)))
+        self._both("rm_shade_ranged", on_dev, c, int(width), int(rows), n, _ptr(values), _ptr(hist), int(lo), int(hi), _ptr(rgba))
         return rgba
 
     # ---- field queries: distance slices and volumes sampled on the device ------------------
@@ -865,25 +854,24 @@ class Context:
         sh.map, sh.reserved = m, 0
         sh.range, sh.band, sh.line = float(range), float(band), float(line)
         sh.lo, sh.hi = int(lo), int(hi)
-        if _is_torch(values):
+        on_dev = _is_torch(values)
+        if on_dev:
             import torch
             want = (torch.float64,) if m == 0 else (torch.int32, torch.uint32)
-            if not (values.is_cuda and values.is_contiguous() and values.dtype in want):
+            if _bytes_on(True, values) < 0 or values.dtype not in want:
                 raise ValueError("values must be a contiguous CUDA tensor of %s" % ("float64" if m == 0 else "int32 / uint32"))
             n = values.numel()
             if rgba is None:
                 rgba = torch.empty(tuple(values.shape) + (4,), dtype=torch.uint8, device=values.device)
-            if not (_is_torch(rgba) and rgba.is_cuda and rgba.is_contiguous() and rgba.numel() * rgba.element_size() >= 4 * n):
-                raise ValueError("rgba must be a contiguous CUDA tensor of 4 bytes per value")
-            self._same_device(dict(values=values, rgba=rgba))
-            N.check(self._h, N.lib().rm_shade_field_device(self._h, C.byref(sh), n, _ptr(values), _ptr(rgba), _current_stream_ptr()))
-            return rgba
-        values = np.ascontiguousarray(values, dtype=np.float64 if m == 0 else np.uint32)
-        if rgba is None:
-            rgba = np.zeros(values.shape + (4,), np.uint8)
-        if not (isinstance(rgba, np.ndarray) and rgba.flags["C_CONTIGUOUS"] and rgba.flags["WRITEABLE"] and rgba.nbytes >= 4 * values.size):
-            raise ValueError("rgba must be a writable contiguous numpy array of 4 bytes per value")
-        N.check(self._h, N.lib().rm_shade_field(self._h, C.byref(sh), values.size, _ptr(values), _ptr(rgba)))
+        else:
+            values = np.ascontiguousarray(values, dtype=np.float64 if m == 0 else np.uint32)
+            n = values.size
+            if rgba is None:
+                rgba = np.zeros(values.shape + (4,), np.uint8)
+        if _bytes_on(on_dev, rgba) < 4 * n:
+            raise ValueError("rgba must be a %s of 4 bytes per value" % ("contiguous CUDA tensor" if on_dev else "writable contiguous numpy array"))
+        self._same_device(dict(values=values, rgba=rgba))
+        self._both("rm_shade_field", on_dev, C.byref(sh), n, _ptr(values), _ptr(rgba))
         return rgba
 
     # ---- point queries: distance, normal, object and projection onto the surface ------------
@@ -1261,6 +1249,14 @@ class Context:
             if b is not None and _is_torch(b) and b.is_cuda and b.device.index != self.device:
                 raise ValueError("%s buffer is on cuda:%s, the context on cuda:%d" % (name, b.device.index, self.device))
 
+    def _both(self, name, on_dev, *args):
+        """The two forms of an entry from one argument list: <name>_device on torch's current stream for device buffers, <name>
+        (synchronous) for host buffers."""
+        if on_dev:
+            N.check(self._h, getattr(N.lib(), name + "_device")(self._h, *args, _current_stream_ptr()))
+        else:
+            N.check(self._h, getattr(N.lib(), name)(self._h, *args))
+
     def render_stripes(self, job, stripe_rows, n_parts, part, depth, normal, sdf, iters, rgba=None, shader=0, diag=None):
         """One launch for every stripe of `part` (rm_render_stripes_device); device buffers only."""
         rows = N.lib().rm_stripe_rows(job.y_start, job.y_end, int(stripe_rows), int(n_parts), int(part))
@@ -1339,16 +1335,12 @@ class Context:
     def shade(self, shader, width, height, depth, normal, sdf, iters, rgba):
         npx = max(0, int(width)) * max(0, int(height))
         bufs = dict(depth=depth, normal=normal, sdf=sdf, iters=iters, rgba=rgba)
-        if any(b is None for b in bufs.values()):
+        if depth is None or normal is None or sdf is None or iters is None or rgba is None:
             raise ValueError("shade needs all five buffers")
-        if _check_buffers(npx, bufs):
+        on_dev = _check_buffers(npx, bufs)
+        if on_dev:
             self._same_device(bufs)
-            N.check(self._h, N.lib().rm_shade_device(self._h, int(shader), width, height, _ptr(depth),
-                                                      _ptr(normal), _ptr(sdf), _ptr(iters), _ptr(rgba),
-                                                      _current_stream_ptr()))
-        else:
-            N.check(self._h, N.lib().rm_shade(self._h, int(shader), width, height, _ptr(depth), _ptr(normal),
-                                               _ptr(sdf), _ptr(iters), _ptr(rgba)))
+        self._both("rm_shade", on_dev, int(shader), width, height, _ptr(depth), _ptr(normal), _ptr(sdf), _ptr(iters), _ptr(rgba))
 
     def _check_counters(self, sdf, iters):
         if sdf is None or iters is None:

@@ -1260,11 +1260,12 @@ constexpr int kMaxColumns = 10;
 // columns, 224 MB a pick's, 272 MB a light's, 288 MB of walk summaries, 192 MB of a point query's, 64 MB of a field's.
 constexpr int64_t kHostChunk = int64_t(1) << 22;
 
-// Both forms of a query over n > 0 elements, behind its checks.  launch(first, m, stream) enqueues the kernel for elements
+// Both forms of a query or a frame operation over n > 0 elements (rays, points, lattice points, vertices, pixels, whole frames),
+// behind its checks.  launch(first, m, stream) enqueues the kernel for elements
 // [first, first + m) with every column's pointer fed and indexed from `first`.  host false: the columns are the caller's device
 // buffers, one launch of all n on `stream`.  host true: through the scratch buffer on the context's stream in chunks of at most
 // `limit` elements, whole rows of `row` (a row at least; n is a multiple of row), synchronous; only the columns asked for are
-// staged and copied.  Nothing here depends on the query.
+// staged and copied; limit = n makes it one trip and one launch.  Nothing here depends on the caller.
 template <typename Launch>
 int staged_call(rm_ctx *ctx, bool host, hipStream_t stream, int64_t n, int64_t row, int64_t limit, const Column *cols, int n_cols, Launch launch) {
     const auto feed = [](const Column &col, const void *ptr) { std::memcpy(col.slot, &ptr, sizeof ptr); };
@@ -2364,6 +2365,166 @@ int scene_sharpen_call(rm_ctx *ctx, const rm_lattice *lattice, const rm_sharp_qu
     });
 }
 
+// Both forms of the operations on rendered frames, in the same way: the checks, the kernel's argument block, then staged_call
+// with the entry's columns -- in ONE trip (limit = n): a host form is one launch, as its device form.  The element of the four
+// per-frame entries is a frame (n = n_frames; a column's bytes are its buffer's per frame), of rm_shade and rm_shade_field a
+// pixel or a value.  host: the buffers are the caller's host memory.
+
+// A frame set's pair absent on both sides, the image with RM_CMP_MAP_NONE and absent records are null columns.  Frames of
+// several workgroups combine their partial records through the context's ring, taken ahead of the launch on the trip's stream.
+int compare_call(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b, int32_t map, int32_t gain,
+                 bool host, void *rgba, void *stats, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_compare(ctx, width, rows, n_frames, a, b, map, gain, rgba, stats);
+    if (rc || n_frames == 0) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(rows), n = static_cast<size_t>(n_frames);
+    if (npx == 0) {  // frames without a pixel: all-zero records, no image byte
+        if (stats && host) std::memset(stats, 0, sizeof(rm_compare_stats) * n);
+        else if (stats) RM_HIP(ctx, hipMemsetAsync(stats, 0, sizeof(rm_compare_stats) * n, static_cast<hipStream_t>(stream)));
+        return RM_OK;
+    }
+    RmCompareArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.npx = static_cast<int64_t>(npx);
+    args.gain = static_cast<unsigned int>(map == RM_CMP_MAP_NONE ? 1 : gain);
+    const int32_t per_frame = rm_compare_blocks_per_frame(args.npx, n_frames);
+    const size_t entries = stats && per_frame > 1 ? static_cast<size_t>(per_frame) * n : 0;
+    const Column cols[] = {{a->depth, npx, &args.depth_a, true, false},      {b->depth, npx, &args.depth_b, true, false},
+                           {a->normal, 3 * npx, &args.normal_a, true, false}, {b->normal, 3 * npx, &args.normal_b, true, false},
+                           {a->sdf, 2 * npx, &args.sdf_a, true, false},       {b->sdf, 2 * npx, &args.sdf_b, true, false},
+                           {a->iters, 2 * npx, &args.iters_a, true, false},   {b->iters, 2 * npx, &args.iters_b, true, false},
+                           {map == RM_CMP_MAP_NONE ? nullptr : rgba, 4 * npx, &args.rgba, false, true},
+                           {stats, sizeof(rm_compare_stats), &args.stats, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n_frames, 1, n_frames, cols, 10, [&](int64_t, int64_t, hipStream_t s) {
+        size_t first = 0;
+        if (entries) {
+            const hipError_t taken = ctx->compare.take(entries, &first);
+            if (taken != hipSuccess) return taken;
+            args.partials = ctx->compare.partials + first;
+            args.counters = ctx->compare.counters + first;
+        }
+        const hipError_t e = rm_launch_compare(args, map, n_frames, per_frame, s, &ctx->last_kernel);
+        if (entries) ctx->compare.launched(first, entries, s);  // (also behind a failed launch)
+        return e;
+    });
+}
+
+// Frames without a pixel still launch: one workgroup per frame writes the empty records, which carry the shift.  RM_HIST_ALL
+// passes no normal buffer.  Frames of several workgroups add into scratch entries of the context's ring.
+int hist_call(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *sdf, const void *iters, const void *normal, int32_t mask,
+              int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, bool host, void *hist, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_hist(ctx, width, rows, n_frames, sdf, iters, normal, mask, bin_shift, lo_permille, hi_permille, hist);
+    if (rc || n_frames == 0) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(rows);
+    RmHistArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.npx = static_cast<int64_t>(npx);
+    args.shift = static_cast<unsigned int>(bin_shift);
+    args.lo_permille = static_cast<unsigned int>(lo_permille);
+    args.hi_permille = static_cast<unsigned int>(hi_permille);
+    args.want_surface = mask == RM_HIST_SURFACE;
+    const int32_t per_frame = rm_compare_blocks_per_frame(args.npx, n_frames);
+    const size_t entries = per_frame > 1 ? static_cast<size_t>(n_frames) : 0;
+    const Column cols[] = {{sdf, 2 * npx, &args.sdf, true, false},
+                           {iters, 2 * npx, &args.iters, true, false},
+                           {mask == RM_HIST_ALL ? nullptr : normal, 3 * npx, &args.normal, true, false},
+                           {hist, sizeof(rm_frame_hist), &args.hist, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n_frames, 1, n_frames, cols, 4, [&](int64_t, int64_t, hipStream_t s) {
+        size_t first = 0;
+        if (entries) {
+            const hipError_t taken = ctx->hists.take(entries, &first);
+            if (taken != hipSuccess) return taken;
+            args.scratch = ctx->hists.entries + first;
+        }
+        const hipError_t e = rm_launch_hist(args, mask != RM_HIST_ALL, n_frames, per_frame, s, &ctx->last_kernel);
+        if (entries) ctx->hists.launched(first, entries, s);  // (also behind a failed launch)
+        return e;
+    });
+}
+
+// Absent records are a null column: every frame then takes lo and hi.
+int shade_ranged_call(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const void *values, const void *hist, uint32_t lo,
+                      uint32_t hi, bool host, void *rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_ranged(ctx, counter, width, rows, n_frames, values, hist, lo, hi, rgba);
+    const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(rows);
+    if (rc || n_frames == 0 || npx == 0) return rc;
+    RmShadeRangedArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.npx = static_cast<int64_t>(npx);
+    args.counter = static_cast<unsigned int>(counter);
+    args.lo = lo;
+    args.hi = hi;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{values, 2 * npx, &args.values, true, false}, {hist, sizeof(rm_frame_hist), &args.hist, true, false},
+                           {rgba, 4 * npx, &args.rgba, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n_frames, 1, n_frames, cols, 3, [&](int64_t, int64_t, hipStream_t s) {
+        return rm_launch_shade_ranged(args, n_frames, s, &ctx->last_kernel);
+    });
+}
+
+int shade_lit_call(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *depth, const void *normal, const void *lit, const void *ao,
+                   bool host, void *rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_lit(ctx, width, rows, n_frames, depth, normal, lit, ao, rgba);
+    const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(rows);
+    if (rc || n_frames == 0 || npx == 0) return rc;
+    RmShadeLitArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.npx = static_cast<int64_t>(npx);
+    for (int k = 0; k < 3; ++k) args.light[k] = ctx->light[k];
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{depth, npx, &args.depth, true, false}, {normal, 3 * npx, &args.normal, true, false}, {lit, 4 * npx, &args.lit, true, false},
+                           {ao, 4 * npx, &args.ao, true, false},   {rgba, 4 * npx, &args.rgba, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n_frames, 1, n_frames, cols, 5, [&](int64_t, int64_t, hipStream_t s) {
+        return rm_launch_shade_lit(args, n_frames, s, &ctx->last_kernel);
+    });
+}
+
+// The device check comes first here, and the entry leaves rm_last_kernel alone.
+int shade_call(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, const void *depth, const void *normal, const void *sdf, const void *iters,
+               bool host, void *rgba, void *stream) {
+    RM_NEED_DEVICE(ctx, "host-only context");
+    if (width < 0 || height < 0) return fail(ctx, RM_E_INVALID, "negative size");
+    if (!depth || !normal || !sdf || !iters || !rgba) return fail(ctx, RM_E_INVALID, "null buffer");
+    const int64_t npx = static_cast<int64_t>(width) * height;
+    if (!npx) return RM_OK;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    struct {
+        const uint8_t *depth, *normal;
+        const uint16_t *sdf, *iters;
+        uint8_t *rgba;
+    } d;
+    const Column cols[] = {{depth, 1, &d.depth, true, false}, {normal, 3, &d.normal, true, false}, {sdf, 2, &d.sdf, true, false},
+                           {iters, 2, &d.iters, true, false}, {rgba, 4, &d.rgba, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), npx, 1, npx, cols, 5, [&](int64_t, int64_t m, hipStream_t s) {
+        return rm_launch_shade(norm_shader(shader), m, d.depth, d.normal, d.sdf, d.iters, d.rgba, ctx->light, s);
+    });
+}
+
+int shade_field_call(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *values, bool host, void *rgba, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    const int rc = check_shade_field(ctx, shade, n, values, rgba);
+    if (rc || !n) return rc;
+    RmShadeFieldArgs args;
+    std::memset(&args, 0, sizeof args);
+    args.n = n;
+    args.range = shade->range;
+    args.band = shade->band;
+    args.line = shade->line;
+    args.lo = shade->lo;
+    args.hi = shade->hi;
+    args.map = shade->map;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    const Column cols[] = {{values, shade->map == RM_FIELD_MAP_DISTANCE ? 8u : 4u, &args.values, true, false}, {rgba, 4, &args.rgba, false, true}};
+    return staged_call(ctx, host, static_cast<hipStream_t>(stream), n, 1, n, cols, 2, [&](int64_t, int64_t, hipStream_t s) {
+        return rm_launch_shade_field(args, s, &ctx->last_kernel);
+    });
+}
+
 
 // What rm_scene_edit_spheres and rm_scene_edit_balls share: the checks of an edit list in their order -- the list, each edit
 // without the scene, the scene, each index at its turn -- and the edits applied to the active scene's object list `d`.
@@ -2733,224 +2894,43 @@ int rm_render_frames_device(rm_ctx *ctx, const rm_job *job, int32_t shader, cons
 
 int rm_compare_frames_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b,
                              int32_t map, int32_t gain, void *d_rgba, void *d_stats, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_compare(ctx, width, rows, n_frames, a, b, map, gain, d_rgba, d_stats);
-    if (rc || n_frames == 0) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    const int64_t npx = static_cast<int64_t>(width) * rows;
-    if (npx == 0) {  // frames without a pixel: all-zero records, no image byte
-        if (d_stats) RM_HIP(ctx, hipMemsetAsync(d_stats, 0, sizeof(rm_compare_stats) * static_cast<size_t>(n_frames), hs));
-        return RM_OK;
-    }
-    RmCompareArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.depth_a = static_cast<const uint8_t *>(a->depth);
-    args.depth_b = static_cast<const uint8_t *>(b->depth);
-    args.normal_a = static_cast<const uint8_t *>(a->normal);
-    args.normal_b = static_cast<const uint8_t *>(b->normal);
-    args.sdf_a = static_cast<const uint16_t *>(a->sdf);
-    args.sdf_b = static_cast<const uint16_t *>(b->sdf);
-    args.iters_a = static_cast<const uint16_t *>(a->iters);
-    args.iters_b = static_cast<const uint16_t *>(b->iters);
-    args.rgba = map == RM_CMP_MAP_NONE ? nullptr : static_cast<uint8_t *>(d_rgba);
-    args.stats = static_cast<RmCompareStats *>(d_stats);
-    args.npx = npx;
-    args.gain = static_cast<unsigned int>(map == RM_CMP_MAP_NONE ? 1 : gain);
-    const int32_t per_frame = rm_compare_blocks_per_frame(npx, n_frames);
-    // frames of several workgroups combine their partial records through the context's ring
-    const size_t entries = d_stats && per_frame > 1 ? static_cast<size_t>(per_frame) * static_cast<size_t>(n_frames) : 0;
-    size_t first = 0;
-    if (entries) {
-        RM_HIP(ctx, ctx->compare.take(entries, &first));
-        args.partials = ctx->compare.partials + first;
-        args.counters = ctx->compare.counters + first;
-    }
-    const hipError_t e = rm_launch_compare(args, map, n_frames, per_frame, hs, &ctx->last_kernel);
-    if (entries) ctx->compare.launched(first, entries, hs);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_compare_frames_device");
-    return RM_OK;
+    return compare_call(ctx, width, rows, n_frames, a, b, map, gain, false, d_rgba, d_stats, stream);
 }
 
 int rm_compare_frames(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const rm_frame_set *a, const rm_frame_set *b, int32_t map,
                       int32_t gain, uint8_t *rgba, rm_compare_stats *stats) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_compare(ctx, width, rows, n_frames, a, b, map, gain, rgba, stats);
-    if (rc) return rc;
-    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
-    if (!total) {
-        if (stats && n) std::memset(stats, 0, sizeof(rm_compare_stats) * n);
-        return RM_OK;
-    }
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const void *host[2][4] = {{a->depth, a->normal, a->sdf, a->iters}, {b->depth, b->normal, b->sdf, b->iters}};
-    const size_t bpp[4] = {1, 3, 2, 2};
-    size_t at[2][4];
-    for (int side = 0; side < 2; ++side)
-        for (int k = 0; k < 4; ++k) at[side][k] = st.region(host[side][k] ? bpp[k] * total : 0);
-    const bool image = map != RM_CMP_MAP_NONE;
-    const size_t o_rgba = st.region(image ? 4 * total : 0), o_stats = st.region(stats ? sizeof(rm_compare_stats) * n : 0);
-    if ((rc = st.reserve())) return rc;
-    rm_frame_set dev[2];
-    for (int side = 0; side < 2; ++side) {
-        const void *d[4];
-        for (int k = 0; k < 4; ++k) {
-            d[k] = host[side][k] ? st.at<void>(at[side][k]) : nullptr;
-            if (host[side][k]) RM_HIP(ctx, st.in(at[side][k], host[side][k], bpp[k] * total));
-        }
-        dev[side] = rm_frame_set{d[0], d[1], d[2], d[3]};
-    }
-    rc = rm_compare_frames_device(ctx, width, rows, n_frames, &dev[0], &dev[1], map, gain, image ? st.at<void>(o_rgba) : nullptr,
-                                  stats ? st.at<void>(o_stats) : nullptr, ctx->stream);
-    if (rc) return rc;
-    if (image) RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
-    if (stats) RM_HIP(ctx, st.out(stats, o_stats, sizeof(rm_compare_stats) * n));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return compare_call(ctx, width, rows, n_frames, a, b, map, gain, true, rgba, stats, nullptr);
 }
 
 int rm_counter_hist_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *d_sdf, const void *d_iters,
                            const void *d_normal, int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, void *d_hist,
                            void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_hist(ctx, width, rows, n_frames, d_sdf, d_iters, d_normal, mask, bin_shift, lo_permille, hi_permille, d_hist);
-    if (rc || n_frames == 0) return rc;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    hipStream_t hs = static_cast<hipStream_t>(stream);
-    RmHistArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.sdf = static_cast<const uint16_t *>(d_sdf);
-    args.iters = static_cast<const uint16_t *>(d_iters);
-    args.normal = mask == RM_HIST_ALL ? nullptr : static_cast<const uint8_t *>(d_normal);
-    args.hist = static_cast<RmFrameHist *>(d_hist);
-    args.npx = static_cast<int64_t>(width) * rows;  // (0: one workgroup per frame writes the empty records)
-    args.shift = static_cast<unsigned int>(bin_shift);
-    args.lo_permille = static_cast<unsigned int>(lo_permille);
-    args.hi_permille = static_cast<unsigned int>(hi_permille);
-    args.want_surface = mask == RM_HIST_SURFACE;
-    const int32_t per_frame = rm_compare_blocks_per_frame(args.npx, n_frames);
-    // frames of several workgroups add into scratch entries of the context's ring
-    const size_t entries = per_frame > 1 ? static_cast<size_t>(n_frames) : 0;
-    size_t first = 0;
-    if (entries) {
-        RM_HIP(ctx, ctx->hists.take(entries, &first));
-        args.scratch = ctx->hists.entries + first;
-    }
-    const hipError_t e = rm_launch_hist(args, mask != RM_HIST_ALL, n_frames, per_frame, hs, &ctx->last_kernel);
-    if (entries) ctx->hists.launched(first, entries, hs);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_counter_hist_device");
-    return RM_OK;
+    return hist_call(ctx, width, rows, n_frames, d_sdf, d_iters, d_normal, mask, bin_shift, lo_permille, hi_permille, false, d_hist, stream);
 }
 
 int rm_counter_hist(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint16_t *sdf, const uint16_t *iters,
                     const uint8_t *normal, int32_t mask, int32_t bin_shift, int32_t lo_permille, int32_t hi_permille, rm_frame_hist *hist) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_hist(ctx, width, rows, n_frames, sdf, iters, normal, mask, bin_shift, lo_permille, hi_permille, hist);
-    if (rc || n_frames == 0) return rc;
-    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const bool masked = mask != RM_HIST_ALL;
-    const size_t o_sdf = st.region(sdf ? 2 * total : 0), o_iters = st.region(iters ? 2 * total : 0), o_normal = st.region(masked ? 3 * total : 0),
-                 o_hist = st.region(sizeof(rm_frame_hist) * n);
-    if ((rc = st.reserve())) return rc;
-    if (sdf && total) RM_HIP(ctx, st.in(o_sdf, sdf, 2 * total));
-    if (iters && total) RM_HIP(ctx, st.in(o_iters, iters, 2 * total));
-    if (masked && total) RM_HIP(ctx, st.in(o_normal, normal, 3 * total));
-    rc = rm_counter_hist_device(ctx, width, rows, n_frames, sdf ? st.at<void>(o_sdf) : nullptr, iters ? st.at<void>(o_iters) : nullptr,
-                                masked ? st.at<void>(o_normal) : nullptr, mask, bin_shift, lo_permille, hi_permille, st.at<void>(o_hist), ctx->stream);
-    if (rc) return rc;
-    RM_HIP(ctx, st.out(hist, o_hist, sizeof(rm_frame_hist) * n));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return hist_call(ctx, width, rows, n_frames, sdf, iters, normal, mask, bin_shift, lo_permille, hi_permille, true, hist, nullptr);
 }
 
 int rm_shade_ranged_device(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const void *d_counter,
                            const void *d_hist, uint32_t lo, uint32_t hi, void *d_rgba, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_shade_ranged(ctx, counter, width, rows, n_frames, d_counter, d_hist, lo, hi, d_rgba);
-    if (rc) return rc;
-    RmShadeRangedArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.values = static_cast<const uint16_t *>(d_counter);
-    args.hist = static_cast<const RmFrameHist *>(d_hist);
-    args.rgba = static_cast<uint8_t *>(d_rgba);
-    args.npx = static_cast<int64_t>(width) * rows;
-    args.counter = static_cast<unsigned int>(counter);
-    args.lo = lo;
-    args.hi = hi;
-    if (n_frames == 0 || args.npx == 0) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    const hipError_t e = rm_launch_shade_ranged(args, n_frames, static_cast<hipStream_t>(stream), &ctx->last_kernel);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_ranged_device");
-    return RM_OK;
+    return shade_ranged_call(ctx, counter, width, rows, n_frames, d_counter, d_hist, lo, hi, false, d_rgba, stream);
 }
 
 int rm_shade_ranged(rm_ctx *ctx, int32_t counter, int32_t width, int32_t rows, int32_t n_frames, const uint16_t *values,
                     const rm_frame_hist *hist, uint32_t lo, uint32_t hi, uint8_t *rgba) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_shade_ranged(ctx, counter, width, rows, n_frames, values, hist, lo, hi, rgba);
-    if (rc) return rc;
-    const size_t n = static_cast<size_t>(n_frames), total = static_cast<size_t>(width) * static_cast<size_t>(rows) * n;
-    if (!total) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const size_t o_val = st.region(2 * total), o_hist = st.region(hist ? sizeof(rm_frame_hist) * n : 0), o_rgba = st.region(4 * total);
-    if ((rc = st.reserve())) return rc;
-    RM_HIP(ctx, st.in(o_val, values, 2 * total));
-    if (hist) RM_HIP(ctx, st.in(o_hist, hist, sizeof(rm_frame_hist) * n));
-    rc = rm_shade_ranged_device(ctx, counter, width, rows, n_frames, st.at<void>(o_val), hist ? st.at<void>(o_hist) : nullptr, lo, hi,
-                                st.at<void>(o_rgba), ctx->stream);
-    if (rc) return rc;
-    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return shade_ranged_call(ctx, counter, width, rows, n_frames, values, hist, lo, hi, true, rgba, nullptr);
 }
 
 int rm_shade_lit_device(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const void *d_depth, const void *d_normal, const void *d_lit,
                         const void *d_ao, void *d_rgba, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_shade_lit(ctx, width, rows, n_frames, d_depth, d_normal, d_lit, d_ao, d_rgba);
-    if (rc) return rc;
-    RmShadeLitArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.depth = static_cast<const uint8_t *>(d_depth);
-    args.normal = static_cast<const uint8_t *>(d_normal);
-    args.lit = static_cast<const float *>(d_lit);
-    args.ao = static_cast<const float *>(d_ao);
-    args.rgba = static_cast<uint8_t *>(d_rgba);
-    args.npx = static_cast<int64_t>(width) * rows;
-    for (int k = 0; k < 3; ++k) args.light[k] = ctx->light[k];
-    if (n_frames == 0 || args.npx == 0) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    const hipError_t e = rm_launch_shade_lit(args, n_frames, static_cast<hipStream_t>(stream), &ctx->last_kernel);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_lit_device");
-    return RM_OK;
+    return shade_lit_call(ctx, width, rows, n_frames, d_depth, d_normal, d_lit, d_ao, false, d_rgba, stream);
 }
 
 int rm_shade_lit(rm_ctx *ctx, int32_t width, int32_t rows, int32_t n_frames, const uint8_t *depth, const uint8_t *normal, const float *lit,
                  const float *ao, uint8_t *rgba) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_shade_lit(ctx, width, rows, n_frames, depth, normal, lit, ao, rgba);
-    if (rc) return rc;
-    const size_t total = static_cast<size_t>(width) * static_cast<size_t>(rows) * static_cast<size_t>(n_frames);
-    if (!total) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const size_t o_depth = st.region(total), o_normal = st.region(3 * total), o_lit = st.region(4 * total), o_ao = st.region(4 * total),
-                 o_rgba = st.region(4 * total);
-    if ((rc = st.reserve())) return rc;
-    RM_HIP(ctx, st.in(o_depth, depth, total));
-    RM_HIP(ctx, st.in(o_normal, normal, 3 * total));
-    RM_HIP(ctx, st.in(o_lit, lit, 4 * total));
-    RM_HIP(ctx, st.in(o_ao, ao, 4 * total));
-    rc = rm_shade_lit_device(ctx, width, rows, n_frames, st.at<void>(o_depth), st.at<void>(o_normal), st.at<void>(o_lit), st.at<void>(o_ao),
-                             st.at<void>(o_rgba), ctx->stream);
-    if (rc) return rc;
-    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return shade_lit_call(ctx, width, rows, n_frames, depth, normal, lit, ao, true, rgba, nullptr);
 }
 
 int rm_sweep_views(double pitch, double yaw, double d_pitch, double d_yaw, double time0, double d_time, int32_t n, rm_view *views) {
@@ -3087,40 +3067,12 @@ int rm_render_tile(rm_ctx *ctx, const rm_job *job, uint8_t *depth, uint8_t *norm
 
 int rm_shade_device(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, const void *d_depth,
                     const void *d_normal, const void *d_sdf, const void *d_iters, void *d_rgba, void *stream) {
-    RM_NEED_DEVICE(ctx, "host-only context");
-    if (width < 0 || height < 0) return fail(ctx, RM_E_INVALID, "negative size");
-    if (!d_depth || !d_normal || !d_sdf || !d_iters || !d_rgba) return fail(ctx, RM_E_INVALID, "null buffer");
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    RM_HIP(ctx, rm_launch_shade(norm_shader(shader), static_cast<int64_t>(width) * height,
-                                static_cast<const uint8_t *>(d_depth), static_cast<const uint8_t *>(d_normal),
-                                static_cast<const uint16_t *>(d_sdf), static_cast<const uint16_t *>(d_iters),
-                                static_cast<uint8_t *>(d_rgba), ctx->light, static_cast<hipStream_t>(stream)));
-    return RM_OK;
+    return shade_call(ctx, shader, width, height, d_depth, d_normal, d_sdf, d_iters, false, d_rgba, stream);
 }
 
 int rm_shade(rm_ctx *ctx, int32_t shader, int32_t width, int32_t height, const uint8_t *depth, const uint8_t *normal,
              const uint16_t *sdf, const uint16_t *iters, uint8_t *rgba) {
-    RM_NEED_DEVICE(ctx, "host-only context");
-    if (width < 0 || height < 0) return fail(ctx, RM_E_INVALID, "negative size");
-    if (!depth || !normal || !sdf || !iters || !rgba) return fail(ctx, RM_E_INVALID, "null buffer");
-    const size_t npx = static_cast<size_t>(width) * static_cast<size_t>(height);
-    if (!npx) return RM_OK;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const size_t o_depth = st.region(npx), o_normal = st.region(3 * npx), o_sdf = st.region(2 * npx), o_iters = st.region(2 * npx),
-                 o_rgba = st.region(4 * npx);
-    int rc = st.reserve();
-    if (rc) return rc;
-    RM_HIP(ctx, st.in(o_depth, depth, npx));
-    RM_HIP(ctx, st.in(o_normal, normal, 3 * npx));
-    RM_HIP(ctx, st.in(o_sdf, sdf, 2 * npx));
-    RM_HIP(ctx, st.in(o_iters, iters, 2 * npx));
-    rc = rm_shade_device(ctx, shader, width, height, st.at<void>(o_depth), st.at<void>(o_normal), st.at<void>(o_sdf), st.at<void>(o_iters),
-                         st.at<void>(o_rgba), ctx->stream);
-    if (rc) return rc;
-    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * npx));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return shade_call(ctx, shader, width, height, depth, normal, sdf, iters, true, rgba, nullptr);
 }
 
 int rm_reduce_counters_enqueue(rm_ctx *ctx, const void *d_sdf, const void *d_iters, int64_t n, void *d_acc,
@@ -3230,41 +3182,11 @@ int rm_scene_points(rm_ctx *ctx, const rm_point_query *q, int64_t n, const float
 }
 
 int rm_shade_field_device(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *d_values, void *d_rgba, void *stream) {
-    if (!ctx) return RM_E_INVALID;
-    const int rc = check_shade_field(ctx, shade, n, d_values, d_rgba);
-    if (rc || !n) return rc;
-    RmShadeFieldArgs args;
-    std::memset(&args, 0, sizeof args);
-    args.values = d_values;
-    args.rgba = static_cast<uint8_t *>(d_rgba);
-    args.n = n;
-    args.range = shade->range;
-    args.band = shade->band;
-    args.line = shade->line;
-    args.lo = shade->lo;
-    args.hi = shade->hi;
-    args.map = shade->map;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    const hipError_t e = rm_launch_shade_field(args, static_cast<hipStream_t>(stream), &ctx->last_kernel);
-    if (e != hipSuccess) return hip_fail(ctx, e, "rm_shade_field_device");
-    return RM_OK;
+    return shade_field_call(ctx, shade, n, d_values, false, d_rgba, stream);
 }
 
 int rm_shade_field(rm_ctx *ctx, const rm_field_shade *shade, int64_t n, const void *values, uint8_t *rgba) {
-    if (!ctx) return RM_E_INVALID;
-    int rc = check_shade_field(ctx, shade, n, values, rgba);
-    if (rc || !n) return rc;
-    const size_t total = static_cast<size_t>(n), each = shade->map == RM_FIELD_MAP_DISTANCE ? 8 : 4;
-    RM_HIP(ctx, hipSetDevice(ctx->device));
-    Staging st{ctx};
-    const size_t o_val = st.region(each * total), o_rgba = st.region(4 * total);
-    if ((rc = st.reserve())) return rc;
-    RM_HIP(ctx, st.in(o_val, values, each * total));
-    rc = rm_shade_field_device(ctx, shade, n, st.at<void>(o_val), st.at<void>(o_rgba), ctx->stream);
-    if (rc) return rc;
-    RM_HIP(ctx, st.out(rgba, o_rgba, 4 * total));
-    RM_HIP(ctx, st.sync());
-    return RM_OK;
+    return shade_field_call(ctx, shade, n, values, true, rgba, nullptr);
 }
 
 int rm_mesh_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_vertices,
