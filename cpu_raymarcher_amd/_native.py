@@ -113,6 +113,17 @@ class rm_sparse_info(C.Structure):  # include/rm_raymarch.h: struct rm_sparse_in
 RM_SPARSE_BLOCK = 8
 
 
+class rm_measure(C.Structure):  # include/rm_raymarch.h: struct rm_measure
+    _fields_ = [("n_points", C.c_int64), ("n_inside", C.c_int64), ("n_nonfinite", C.c_int64), ("sum1", C.c_int64 * 3), ("sum2", C.c_int64 * 6),
+                ("crossings", C.c_int64 * 3), ("lo", C.c_int32 * 3), ("hi", C.c_int32 * 3), ("n_blocks", C.c_int64), ("n_kept", C.c_int64),
+                ("n_blocks_inside", C.c_int64), ("reserved", C.c_int64)]
+
+
+class rm_measure_world(C.Structure):  # include/rm_raymarch.h: struct rm_measure_world
+    _fields_ = [("cell_volume", C.c_double), ("volume", C.c_double), ("centroid", C.c_double * 3), ("second", C.c_double * 6),
+                ("projected_area", C.c_double * 3), ("area_estimate", C.c_double)]
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -245,6 +256,10 @@ SIGNATURES = {
                                        _VP, _VP]),
     "rm_scene_mesh_sparse": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, _VP, C.c_int64, _VP, C.c_int64, _VP, _VP,
                                        C.POINTER(rm_mesh_info), C.POINTER(rm_sparse_info)]),
+    "rm_measure_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, _VP, _VP]),
+    "rm_measure_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
+    "rm_scene_measure": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, C.POINTER(rm_measure), C.POINTER(rm_sparse_info)]),
+    "rm_measure_world": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(rm_measure), C.POINTER(rm_measure_world)]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

@@ -11,6 +11,20 @@ from . import _native as N
 Points = collections.namedtuple("Points", "position dist normal object steps count")
 SparseBlocks = collections.namedtuple("SparseBlocks", "slot list dist n_kept dims")
 Sharp = collections.namedtuple("Sharp", "position feature count")
+MeasureWorld = collections.namedtuple("MeasureWorld", "cell_volume volume centroid second projected_area area_estimate")
+
+
+class Measure(collections.namedtuple("Measure", "n_points n_inside n_nonfinite sum1 sum2 crossings lo hi n_blocks n_kept n_blocks_inside")):
+    """rm_measure (include/rm_raymarch.h, "measures") as Python ints -- sum1, sum2, crossings, lo and hi as tuples --, what
+    Context.measure_field, Context.measure and MeshSession.measure return.  Two measures compare equal when these integer
+    fields are.  `world`: the MeasureWorld rm_measure_world makes of it on the measured lattice."""
+    world = None
+
+    def inertia(self):
+        """The inertia tensor of the solid about its centroid at unit density, trace(second) * I - second, float64 [3, 3]."""
+        xx, yy, zz, xy, yz, zx = self.world.second
+        second = np.array([[xx, xy, zx], [xy, yy, yz], [zx, yz, zz]], np.float64)
+        return np.trace(second) * np.eye(3) - second
 
 
 def _is_torch(x):
@@ -1226,6 +1240,74 @@ class Context:
         and `margin` beyond it on every side (None: two cells and max(iso, 0), so the surface closes inside the lattice).
         `box` = (lo, hi) replaces the root box: a scene without a structure reports none.  sparse=True: `mesh_sparse` with
         `lipschitz` over the same lattice (order "dense": the same mesh).  exact, sharp, refine, rank_tol, reach: as `mesh`."""
+        lattice = self._box_lattice(cells, margin, iso, box)
+        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact, sharp=sharp,
+                    refine=refine, rank_tol=rank_tol, reach=reach)
+        if sparse:
+            more["lipschitz"] = lipschitz
+        return (self.mesh_sparse if sparse else self.mesh)(*lattice, **more)
+
+    # ---- measures: how much there is of the solid ---------------------------------------------
+    def _read_measure(self, lat, record):
+        """The rm_measure a device entry wrote into the int64 CUDA tensor `record` (one read) -> Measure."""
+        raw = N.rm_measure.from_buffer_copy(record.cpu().numpy().tobytes())
+        return measure_from_record(lat, raw)
+
+    def _measure_values(self, lat, values, vt, iso):
+        """rm_measure_field_device on torch's current stream over the CUDA tensor `values` -> Measure."""
+        import torch
+        record = torch.empty(22, dtype=torch.int64, device=torch.device("cuda", self.device))
+        N.check(self._h, N.lib().rm_measure_field_device(self._h, C.byref(lat), _ptr(values) if values.numel() else None, vt, float(iso), _ptr(record),
+                                                         _current_stream_ptr()))
+        return self._read_measure(lat, record)
+
+    def _measure_tiles(self, lat, slot, lst, k, dist, tiles, iso):
+        """rm_measure_tiles_device on torch's current stream over what the coarse pass and a tile pass left -> Measure."""
+        import torch
+        record = torch.empty(22, dtype=torch.int64, device=torch.device("cuda", self.device))
+        N.check(self._h, N.lib().rm_measure_tiles_device(self._h, C.byref(lat), _ptr(slot), _ptr(lst) if k else None, k, _ptr(dist),
+                                                         _ptr(tiles) if k else None, float(iso), _ptr(record), _current_stream_ptr()))
+        return self._read_measure(lat, record)
+
+    def measure_field(self, values, origin, du, dv, dw, shape, iso=0.0):
+        """How much of a volume the caller already holds lies inside (rm_measure_field_device; the rule is in
+        include/rm_raymarch.h, "measures"): `values` is a torch CUDA tensor, or a numpy array that is uploaded, of nu * nv * nw
+        float64 or float32 values in the lattice's order; a point is inside where value < iso.  shape = (nu, nv) measures a
+        slice.  Returns a Measure: the integer fields of rm_measure as Python ints (n_points, n_inside, n_nonfinite, sum1,
+        sum2, crossings, lo, hi, n_blocks, n_kept, n_blocks_inside), `.world` (rm_measure_world: cell_volume, volume, centroid,
+        second, projected_area, area_estimate) and `.inertia()`.  On torch's current stream; one read of 176 bytes."""
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU measure")
+        lat = make_lattice(origin, du, dv, dw, shape)
+        values, vt = self._mesh_values(values, lat.nu * lat.nv * lat.nw)
+        return self._measure_values(lat, values, vt, iso)
+
+    def measure(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, lipschitz=1.0, sparse=True, exact=True):
+        """How much there is of the active scene over a lattice -> Measure (`measure_field`).  sparse=True: `sparse_blocks` with
+        its distances, the tiles of the kept blocks under the EXACT field (always: the coarse pass decides by it) and
+        rm_measure_tiles_device, on torch's current stream -- work and memory follow the surface; equal to the dense measure
+        of the exact field whenever that field is `lipschitz`-Lipschitz.  sparse=False: `field` samples the volume (float64,
+        honouring `exact` as `field` does) and `measure_field` measures it."""
+        if not sparse:
+            vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True, exact=exact)
+            return self.measure_field(vol, origin, du, dv, dw, shape, iso=iso)
+        import torch
+        blocks = self.sparse_blocks(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, dist=True)
+        lat = make_lattice(origin, du, dv, dw, shape, time)
+        k = blocks.n_kept
+        tiles = torch.empty((k, 729), dtype=torch.float64, device=blocks.slot.device)
+        with self._exact(True):
+            self._tiles_into(lat, blocks.list, k, tiles)
+        return self._measure_tiles(lat, blocks.slot, blocks.list, k, blocks.dist, tiles, iso)
+
+    def measure_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, box=None, lipschitz=1.0, sparse=True, exact=True):
+        """`measure` over `mesh_box`'s lattice: cells[0] x cells[1] x cells[2] cells that cover scene_info()'s root box (or
+        `box` = (lo, hi)) and `margin` beyond it on every side."""
+        origin, du, dv, dw, shape = self._box_lattice(cells, margin, iso, box)
+        return self.measure(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, sparse=sparse, exact=exact)
+
+    def _box_lattice(self, cells, margin, iso, box):
+        """The lattice `mesh_box` meshes over -> (origin, du, dv, dw, shape)."""
         if box is None:
             info = self.scene_info()
             box = (info["root_min"], info["root_max"])
@@ -1237,12 +1319,7 @@ class Context:
             raise ValueError("at least 5 cells per axis")
         m = np.full(3, float(margin)) if margin is not None else max(float(iso), 0.0) * (1 + 4 / (c - 4)) + 2 * (hi - lo) / (c - 4)
         step = (hi - lo + 2 * m) / c
-        more = dict(iso=iso, time=time, device=device, triangles=triangles, attributes=attributes, snap=snap, tol=tol, exact=exact, sharp=sharp,
-                    refine=refine, rank_tol=rank_tol, reach=reach)
-        if sparse:
-            more["lipschitz"] = lipschitz
-        return (self.mesh_sparse if sparse else self.mesh)(lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c),
-                                                           **more)
+        return lo - m, (step[0], 0, 0), (0, step[1], 0), (0, 0, step[2]), tuple(int(x) + 1 for x in c)
 
     def _same_device(self, bufs):
         for name, b in bufs.items():
@@ -1435,6 +1512,24 @@ def make_lattice(origin, du, dv, dw=None, shape=(1, 1), time=0.0):
     return lat
 
 
+def measure_world(lat, record):
+    """rm_measure_world (host-only, no context): the N.rm_measure `record` in the world units of the rm_lattice `lat` ->
+    MeasureWorld(cell_volume, volume, centroid[3], second[6] as xx yy zz xy yz zx, projected_area[3], area_estimate)."""
+    out = N.rm_measure_world()
+    rc = N.lib().rm_measure_world(C.byref(lat), C.byref(record), C.byref(out))
+    if rc != N.RM_OK:
+        raise N.RmError(rc, "rm_measure_world")
+    return MeasureWorld(out.cell_volume, out.volume, tuple(out.centroid), tuple(out.second), tuple(out.projected_area), out.area_estimate)
+
+
+def measure_from_record(lat, record):
+    """An N.rm_measure over the rm_lattice `lat` -> Measure, its `world` filled in."""
+    m = Measure(record.n_points, record.n_inside, record.n_nonfinite, tuple(record.sum1), tuple(record.sum2), tuple(record.crossings),
+                tuple(record.lo), tuple(record.hi), record.n_blocks, record.n_kept, record.n_blocks_inside)
+    m.world = measure_world(lat, record)
+    return m
+
+
 def slice_lattice(axis="z", offset=0.0, half_extent=5.0, size=(256, 256)):
     """The lattice of the axis-aligned plane axis = offset, [-half_extent, half_extent] in both other axes, sampled at the
     centres of size = (nu, nv) texels -> (origin, du, dv, (nu, nv)), float32 vectors, what Context.field takes.  i runs along
@@ -1546,11 +1641,11 @@ class MeshSession:
         import torch
         self.ctx, self.iso, self.time, self.lipschitz = ctx, float(iso), float(time), float(lipschitz)
         dev = torch.device("cuda", ctx.device)
-        # [slot, list, tiles, n_kept] twice; the tiles grow with the kept set
+        # [slot, list, tiles, n_kept, dist] twice; the tiles grow with the kept set
         self._sets = []
         for _ in range(2):
             self.dims, self.n_blocks, slot, lst = ctx._block_buffers(self.lattice)
-            self._sets.append([slot, lst, torch.empty((0, 729), dtype=torch.float64, device=dev), 0])
+            self._sets.append([slot, lst, torch.empty((0, 729), dtype=torch.float64, device=dev), 0, torch.empty(len(slot), dtype=torch.float64, device=dev)])
         self._cur = None  # index of the current set
         self._info = torch.zeros(4, dtype=torch.int64, device=dev)
         self.reused = None  # int32 [n_kept]: the last update's flags (1: the tile was copied), on the device
@@ -1584,7 +1679,7 @@ class MeshSession:
         ctx, lat = self.ctx, self.lattice
         target = 1 - self._cur if self._cur is not None else 0
         new = self._sets[target]
-        k = ctx._sparse_blocks_into(lat, self.iso, self.lipschitz, new[0], new[1])
+        k = ctx._sparse_blocks_into(lat, self.iso, self.lipschitz, new[0], new[1], new[4])
         if new[2].shape[0] < k:
             new[2] = torch.empty((k + k // 8, 729), dtype=torch.float64, device=new[0].device)
         new[3] = k
@@ -1626,3 +1721,9 @@ class MeshSession:
             raise ValueError("order is 'dense' or 'tile'")
         s = self._sets[self._cur]
         return self.ctx._mesh_tiles(self.lattice, s[0], s[1], s[3], s[2], self.iso, self.time, order, device, triangles, False, 0, 1e-4)
+
+    def measure(self):
+        """The Measure of the current tiles (rm_measure_tiles_device): what Context.measure(sparse=True) returns for the active
+        scene over the session's lattice, without its coarse pass and its tile pass."""
+        s = self._sets[self._cur]
+        return self.ctx._measure_tiles(self.lattice, s[0], s[1], s[3], s[4], s[2], self.iso)

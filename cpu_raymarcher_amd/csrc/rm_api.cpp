@@ -2108,10 +2108,12 @@ RmTilesArgs tiles_args(const rm_lattice *lat, const SparseGrid &g, const void *d
     return a;
 }
 
-int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream) {
+// exact: the exact field whatever option `exact` says (rm_scene_measure)
+int launch_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const void *d_list, int64_t n_kept, void *d_tiles, hipStream_t stream,
+                 bool exact = false) {
     RmRenderParams p;
     fill_scene_query(ctx, lat->time, p);
-    if (const int erc = apply_exact(ctx, p)) return erc;
+    if (const int erc = exact ? use_exact(ctx, p) : apply_exact(ctx, p)) return erc;
     const RmTilesArgs a = tiles_args(lat, g, d_list, n_kept, d_tiles);
     RM_HIP(ctx, (ctx->opt_length ? rm_launch_tiles_sqrt : rm_launch_tiles)(p, a, stream, &ctx->last_kernel));
     return RM_OK;
@@ -2167,6 +2169,74 @@ int launch_mesh_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, c
     a.n_kept = static_cast<unsigned int>(m.n_kept);
     RM_HIP(ctx, rm_launch_mesh_tiles(a, stream, &ctx->last_kernel));
     return RM_OK;
+}
+
+// ---- measures: integer sums over the inside points of a lattice (rm_measure.hip)
+
+static_assert(sizeof(rm_measure) == 176 && sizeof(RmMeasure) == sizeof(rm_measure) && offsetof(rm_measure, lo) == 120 &&
+                  offsetof(rm_measure, n_blocks) == 144 && offsetof(RmMeasure, n_blocks) == 144,
+              "rm_measure layout");
+static_assert(sizeof(struct rm_measure_world) == 120 && sizeof(RmMeasurePartial) == 144, "rm_measure_world and partial layout");
+
+// every sum of a measure fits an int64: n * (max(nu, nv, nw) - 1)^2 stays below 2^63 (formed without overflow)
+bool measure_fits(const rm_lattice &l, int64_t n) {
+    const int64_t m = std::max(std::max(l.nu, l.nv), l.nw) - 1;
+    return m <= 0 || n <= std::numeric_limits<int64_t>::max() / (m * m);
+}
+const char *const kMeasureOverflow = "the sums of this lattice do not fit 64 bits: n_points * (max count - 1)^2 reaches 2^63";
+
+// The dense launch: the values and the record on the device, the partials at their place in the reserved scratch.
+int launch_measure_field(rm_ctx *ctx, const rm_lattice *lat, int64_t n, const void *d_values, int32_t value_type, double iso, void *d_partials,
+                         unsigned int n_groups, void *d_measure, hipStream_t stream) {
+    RmMeasureFieldArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.values = d_values;
+    a.iso = iso;
+    a.partials = static_cast<RmMeasurePartial *>(d_partials);
+    a.out = static_cast<RmMeasure *>(d_measure);
+    a.n = n;
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.f32 = value_type == RM_MESH_F32;
+    RM_HIP(ctx, rm_launch_measure_field(a, n_groups, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+struct SparseMeasureCall {
+    const void *slot, *list, *dist, *tiles;
+    int64_t n_kept;
+    double iso;
+    void *measure;
+};
+
+int launch_measure_tiles(rm_ctx *ctx, const rm_lattice *lat, const SparseGrid &g, const SparseMeasureCall &m, void *d_partials, unsigned int n_groups,
+                         hipStream_t stream) {
+    RmMeasureTilesArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.iso = m.iso;
+    a.slot = static_cast<const int32_t *>(m.slot);
+    a.list = static_cast<const int32_t *>(m.list);
+    a.dist = static_cast<const double *>(m.dist);
+    a.tiles = static_cast<const double *>(m.tiles);
+    a.partials = static_cast<RmMeasurePartial *>(d_partials);
+    a.out = static_cast<RmMeasure *>(m.measure);
+    a.n = g.n;
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.nbu = static_cast<unsigned int>(g.nb[0]);
+    a.nbv = static_cast<unsigned int>(g.nb[1]);
+    a.nbw = static_cast<unsigned int>(g.nb[2]);
+    a.n_blocks = static_cast<unsigned int>(g.n_blocks);
+    a.n_kept = static_cast<unsigned int>(m.n_kept);
+    RM_HIP(ctx, rm_launch_measure_tiles(a, n_groups, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+// what the sparse measure entries ask of the lattice beyond sparse_error: blocks on every axis
+const char *measure_blocks_error(const rm_lattice *l) {
+    return l->nu < 2 || l->nv < 2 || l->nw < 2 ? "every lattice count must be at least 2: a slice goes through rm_measure_field_device" : nullptr;
 }
 
 int check_shade_field(rm_ctx *ctx, const rm_field_shade *sh, int64_t n, const void *values, const void *rgba) {
@@ -3414,6 +3484,153 @@ int rm_scene_mesh_sparse(rm_ctx *ctx, const rm_lattice *lattice, double iso, dou
     const SparseMeshCall m{st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_tiles), n_kept, iso, r.on_device(st, host)};
     if ((rc = launch_mesh_tiles(ctx, lattice, g, m, st.at<uint32_t>(o_map), st.at<uint32_t>(o_totals), ctx->stream))) return rc;
     return read_mesh(ctx, st, r, host);
+}
+
+int rm_measure_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, void *d_measure, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = lattice_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (n > (int64_t(1) << 30)) return fail(ctx, RM_E_INVALID, "more than 2^30 lattice points: the measure does not split a volume");
+    if (n > 0 && !d_values) return fail(ctx, RM_E_INVALID, "null values");
+    if (!d_measure) return fail(ctx, RM_E_INVALID, "null measure");
+    if (!std::isfinite(iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (value_type != RM_MESH_F64 && value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
+    if (misaligned(d_values, value_type == RM_MESH_F64 ? 7 : 3)) return fail(ctx, RM_E_INVALID, "values must be aligned to their type");
+    if (misaligned(d_measure, 7)) return fail(ctx, RM_E_INVALID, "measure must be 8-byte aligned");
+    if (!measure_fits(*lattice, n)) return fail(ctx, RM_E_UNSUPPORTED, kMeasureOverflow);
+    if (const int rc = need_device(ctx, "measure", false)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    RM_HIP(ctx, hipSetDevice(ctx->device));  // the grid is sized by what this device holds
+    const unsigned int groups = rm_measure_field_groups(n, static_cast<unsigned int>(lattice->nv), static_cast<unsigned int>(lattice->nw), ctx->num_cus);
+    // one partial per workgroup; without a point the last kernel alone writes the empty record
+    return scratch_call(ctx, s, true, d_measure, sizeof(rm_measure), {sizeof(RmMeasurePartial) * groups}, [&](const Staging &st, const size_t *o) {
+        return launch_measure_field(ctx, lattice, n, d_values, value_type, iso, st.at<void>(o[0]), groups, d_measure, s);
+    });
+}
+
+int rm_measure_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept, const void *d_dist,
+                            const void *d_tiles, double iso, void *d_measure, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = measure_blocks_error(lattice)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = kept_range_error(g, n_kept)) return fail(ctx, RM_E_INVALID, bad);
+    if (!d_measure) return fail(ctx, RM_E_INVALID, "null measure");
+    if (!d_slot) return fail(ctx, RM_E_INVALID, "null slot");
+    if (!d_dist) return fail(ctx, RM_E_INVALID, "null dist");
+    if (const char *bad = kept_buffers_error(n_kept, d_list, d_tiles)) return fail(ctx, RM_E_INVALID, bad);
+    if (!std::isfinite(iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (misaligned(d_slot, 3) || misaligned(d_list, 3)) return fail(ctx, RM_E_INVALID, "slot and list must be 4-byte aligned");
+    if (misaligned(d_dist, 7) || misaligned(d_tiles, 7) || misaligned(d_measure, 7)) return fail(ctx, RM_E_INVALID, "dist, tiles and measure must be 8-byte aligned");
+    if (!measure_fits(*lattice, g.n)) return fail(ctx, RM_E_UNSUPPORTED, kMeasureOverflow);
+    if (const int rc = need_device(ctx, "measure", false)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const unsigned int groups = rm_measure_block_groups(static_cast<unsigned int>(g.n_blocks), ctx->num_cus);
+    const SparseMeasureCall m{d_slot, d_list, d_dist, d_tiles, n_kept, iso, d_measure};
+    // one partial per kept block and per workgroup of the closed forms
+    return scratch_call(ctx, s, true, d_measure, sizeof(rm_measure), {sizeof(RmMeasurePartial) * (static_cast<size_t>(n_kept) + groups)},
+                        [&](const Staging &st, const size_t *o) { return launch_measure_tiles(ctx, lattice, g, m, st.at<void>(o[0]), groups, s); });
+}
+
+int rm_scene_measure(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, rm_measure *out, rm_sparse_info *sparse_info) {
+    if (!ctx) return RM_E_INVALID;
+    SparseGrid g;
+    if (const char *bad = sparse_error(lattice, &g)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = measure_blocks_error(lattice)) return fail(ctx, RM_E_INVALID, bad);
+    if (!out) return fail(ctx, RM_E_INVALID, "null measure");
+    if (!std::isfinite(iso)) return fail(ctx, RM_E_INVALID, "non-finite iso");
+    if (!std::isfinite(lipschitz) || !(lipschitz > 0.0)) return fail(ctx, RM_E_INVALID, "lipschitz must be finite and > 0");
+    if (!measure_fits(*lattice, g.n)) return fail(ctx, RM_E_UNSUPPORTED, kMeasureOverflow);
+    if (const int nrc = need_device(ctx, "measure", true)) return nrc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // Step 1 in the scratch buffer: the slot map, the list, the distances, the info and the scan's totals.
+    const size_t nb = static_cast<size_t>(g.n_blocks);
+    Staging st{ctx};
+    const size_t o_slot = st.region(4 * nb), o_list = st.region(4 * nb), o_dist = st.region(8 * nb), o_sinfo = st.region(sizeof(rm_sparse_info)),
+                 o_groups = st.region(4 * sparse_groups(g.n_blocks));
+    int rc = st.reserve();
+    if (rc) return rc;
+    if ((rc = launch_blocks(ctx, lattice, g, iso, lipschitz, st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_dist), st.at<void>(o_sinfo),
+                            st.at<uint32_t>(o_groups), ctx->stream)))
+        return rc;
+    rm_sparse_info si;
+    RM_HIP(ctx, st.out(&si, o_sinfo, sizeof si));
+    RM_HIP(ctx, st.sync());
+    if (sparse_info) *sparse_info = si;
+    const int64_t n_kept = si.n_kept;
+    if (n_kept < 0 || n_kept > g.n_blocks) return fail(ctx, RM_E_HIP, "the coarse pass reported an impossible n_kept");
+    // Steps 2 and 3 behind the same regions: the tiles, the partials and the record.
+    const size_t k = static_cast<size_t>(n_kept);
+    const unsigned int groups = rm_measure_block_groups(static_cast<unsigned int>(g.n_blocks), ctx->num_cus);
+    const size_t o_tiles = st.region(8 * RM_SPARSE_TILE * k), o_partials = st.region(sizeof(RmMeasurePartial) * (k + groups)),
+                 o_measure = st.region(sizeof(rm_measure));
+    if (st.total > ctx->scratch_bytes) {  // the scratch has to grow, which frees it: step 1's results go through the host
+        std::vector<int32_t> slot(nb), list(k);
+        std::vector<double> dist(nb);
+        RM_HIP(ctx, st.out(slot.data(), o_slot, 4 * nb));
+        if (k) RM_HIP(ctx, st.out(list.data(), o_list, 4 * k));
+        RM_HIP(ctx, st.out(dist.data(), o_dist, 8 * nb));
+        RM_HIP(ctx, st.sync());
+        if ((rc = st.reserve())) return rc;
+        RM_HIP(ctx, st.in(o_slot, slot.data(), 4 * nb));
+        if (k) RM_HIP(ctx, st.in(o_list, list.data(), 4 * k));
+        RM_HIP(ctx, st.in(o_dist, dist.data(), 8 * nb));
+        RM_HIP(ctx, st.sync());  // (the vectors end here)
+    }
+    if (k && (rc = launch_tiles(ctx, lattice, g, st.at<void>(o_list), n_kept, st.at<void>(o_tiles), ctx->stream, true))) return rc;
+    const SparseMeasureCall m{st.at<void>(o_slot), st.at<void>(o_list), st.at<void>(o_dist), st.at<void>(o_tiles), n_kept, iso, st.at<void>(o_measure)};
+    if ((rc = launch_measure_tiles(ctx, lattice, g, m, st.at<void>(o_partials), groups, ctx->stream))) return rc;
+    RM_HIP(ctx, st.out(out, o_measure, sizeof *out));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_measure_world(const rm_lattice *lattice, const rm_measure *measure, struct rm_measure_world *out) {
+    int64_t n = 0;
+    if (!measure || !out || lattice_error(lattice, &n)) return RM_E_INVALID;
+    // binary64, one operation at a time (-ffp-contract=off), in the header's order
+    double M[3][3];  // M[p][a]: component p of step a
+    for (int p = 0; p < 3; ++p) {
+        M[p][0] = static_cast<double>(lattice->du[p]);
+        M[p][1] = static_cast<double>(lattice->dv[p]);
+        M[p][2] = static_cast<double>(lattice->dw[p]);
+    }
+    const double u0 = M[0][0], u1 = M[1][0], u2 = M[2][0], v0 = M[0][1], v1 = M[1][1], v2 = M[2][1], w0 = M[0][2], w1 = M[1][2], w2 = M[2][2];
+    const double cv = std::fabs((u0 * (v1 * w2 - v2 * w1) - u1 * (v0 * w2 - v2 * w0)) + u2 * (v0 * w1 - v1 * w0));
+    const double N = static_cast<double>(measure->n_inside);
+    out->cell_volume = cv;
+    out->volume = N * cv;
+    const double S[3] = {static_cast<double>(measure->sum1[0]), static_cast<double>(measure->sum1[1]), static_cast<double>(measure->sum1[2])};
+    const double none = std::numeric_limits<double>::quiet_NaN();  // the mean index of no point
+    const bool any = measure->n_inside != 0;
+    const double m[3] = {any ? S[0] / N : none, any ? S[1] / N : none, any ? S[2] / N : none};
+    for (int c = 0; c < 3; ++c) out->centroid[c] = ((static_cast<double>(lattice->origin[c]) + m[0] * M[c][0]) + m[1] * M[c][1]) + m[2] * M[c][2];
+    static const int kPair[6][2] = {{0, 0}, {1, 1}, {2, 2}, {0, 1}, {1, 2}, {2, 0}};  // sum2's order, and second's
+    double C[3][3];
+    for (int e = 0; e < 6; ++e) {
+        const int a = kPair[e][0], b = kPair[e][1];
+        C[a][b] = C[b][a] = static_cast<double>(measure->sum2[e]) - (S[a] * S[b]) / N;
+    }
+    for (int e = 0; e < 6; ++e) {
+        const int p = kPair[e][0], q = kPair[e][1];
+        if (measure->n_inside == 0) {
+            out->second[e] = 0.0;
+            continue;
+        }
+        double t[3];
+        for (int a = 0; a < 3; ++a) t[a] = (C[a][0] * M[q][0] + C[a][1] * M[q][1]) + C[a][2] * M[q][2];
+        const double pushed = (M[p][0] * t[0] + M[p][1] * t[1]) + M[p][2] * t[2];
+        const double own = (M[p][0] * M[q][0] + M[p][1] * M[q][1]) + M[p][2] * M[q][2];
+        out->second[e] = pushed * cv + ((N * cv) / 12.0) * own;
+    }
+    for (int A = 0; A < 3; ++A) {
+        const int B = A == 2 ? 0 : A + 1, Cx = A == 0 ? 2 : A - 1;
+        const double x = M[1][B] * M[2][Cx] - M[2][B] * M[1][Cx], y = M[2][B] * M[0][Cx] - M[0][B] * M[2][Cx],
+                     z = M[0][B] * M[1][Cx] - M[1][B] * M[0][Cx];
+        out->projected_area[A] = static_cast<double>(measure->crossings[A]) * std::sqrt((x * x + y * y) + z * z);
+    }
+    out->area_estimate = (2.0 / 3.0) * ((out->projected_area[0] + out->projected_area[1]) + out->projected_area[2]);
+    return RM_OK;
 }
 
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {

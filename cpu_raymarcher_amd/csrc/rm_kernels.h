@@ -350,6 +350,36 @@ struct RmSparseMeshArgs {
     long long cap_vertices, cap_quads;
     unsigned int nu, nv, nw, nbu, nbv, nbw, n_kept, pad;
 };
+// rm_measure_field_device / rm_measure_tiles_device (rm_measure.hip): integer sums over the inside points of a lattice.
+#define RM_MEASURE_SUMS 15
+struct RmMeasure {  // rm_measure (176 bytes)
+    long long n_points, n_inside, n_nonfinite, sum1[3], sum2[6], crossings[3];
+    int lo[3], hi[3];
+    long long n_blocks, n_kept, n_blocks_inside, reserved;
+};
+// what one workgroup found: n_inside, n_nonfinite, sum1, sum2, crossings, n_blocks_inside in that order, and its box
+struct RmMeasurePartial {  // 144 bytes
+    long long sum[RM_MEASURE_SUMS];
+    int lo[3], hi[3];
+};
+struct RmMeasureFieldArgs {
+    const void *values;  // n binary64 values, or binary32 ones with f32
+    double iso;
+    RmMeasurePartial *partials;  // one per workgroup of the launch
+    RmMeasure *out;
+    long long n;
+    unsigned int nu, nv, nw;
+    int f32;
+};
+struct RmMeasureTilesArgs {
+    double iso;
+    const int32_t *slot, *list;
+    const double *dist, *tiles;
+    RmMeasurePartial *partials;  // n_kept, then one per workgroup of measure_blocks_kernel
+    RmMeasure *out;
+    long long n;
+    unsigned int nu, nv, nw, nbu, nbv, nbw, n_blocks, n_kept;
+};
 // The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
 // A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
 // its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
@@ -547,6 +577,15 @@ hipError_t rm_launch_mesh_tiles(const RmSparseMeshArgs &a, hipStream_t stream, c
 hipError_t rm_launch_tiles_update(const RmRenderParams &p, const RmTilesArgs &a, const RmTilesUpdateArgs &u, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_tiles_update_sqrt(const RmRenderParams &p, const RmTilesArgs &a, const RmTilesUpdateArgs &u, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_tiles_update_totals(const int32_t *reused, unsigned int n_kept, RmTilesUpdateInfo *info, hipStream_t stream);
+// The measures (rm_measure.hip).  rm_launch_measure_field: measure_field_kernel<T> over n_groups workgroups, then
+// measure_final_kernel; 0 <= a.n <= 2^30, and n_groups = rm_measure_field_groups(...) partials (0 without a point: the final
+// kernel alone writes the empty record).  rm_launch_measure_tiles: measure_tiles_kernel over a.n_kept workgroups (none: not
+// launched), measure_blocks_kernel over n_groups = rm_measure_block_groups(...) workgroups, measure_final_kernel;
+// a.partials holds a.n_kept + n_groups records.  The grids are persistent: num_cus bounds them.
+unsigned int rm_measure_field_groups(long long n, unsigned int nv, unsigned int nw, int num_cus);
+unsigned int rm_measure_block_groups(unsigned int n_blocks, int num_cus);
+hipError_t rm_launch_measure_field(const RmMeasureFieldArgs &a, unsigned int n_groups, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_measure_tiles(const RmMeasureTilesArgs &a, unsigned int n_groups, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

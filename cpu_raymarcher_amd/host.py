@@ -181,6 +181,19 @@ class Scene:
             return self.ctx.mesh_sparse(origin, du, dv, dw, shape, lipschitz=lipschitz, **more)
         return self.ctx.mesh(origin, du, dv, dw, shape, **more)
 
+    def measure(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, lipschitz=1.0, sparse=True,
+                exact=True):
+        """How much there is of the solid getDistance < iso at this scene's own time -> a Measure (Context.measure): the
+        integer record (n_inside, sum1, sum2, crossings, the index box, ...), `.world` (volume, centroid, second moments,
+        projected areas, an area estimate) and `.inertia()`.  Over the lattice origin + i * du + j * dv + k * dw of `shape`
+        points, or, without one, over the root box in `cells` cells (Context.measure_box).  sparse, lipschitz, exact: as
+        Context.measure."""
+        self._activate()
+        more = dict(iso=iso, time=self.time, lipschitz=lipschitz, sparse=sparse, exact=exact)
+        if origin is None:
+            return self.ctx.measure_box(cells, margin=margin, **more)
+        return self.ctx.measure(origin, du, dv, dw, shape, **more)
+
     def meshSession(self, origin, du, dv, dw, shape, iso=0.0, lipschitz=1.0):
         """Opens a mesh session on this scene at its own time (Context.mesh_session) and returns it: session.mesh() is
         toMesh(sparse=True, exact=True) over the lattice, and from now on editSpheres / setSphere / insertSphere /

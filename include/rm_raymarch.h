@@ -535,6 +535,109 @@ RM_API int rm_scene_tiles_update_device(rm_ctx *ctx, const rm_lattice *lattice, 
                                         int64_t n_prev_kept, const void *d_balls, int32_t n_balls, const void *d_list, int64_t n_kept,
                                         void *d_tiles, void *d_reused, void *d_info, void *stream);
 
+/* ---- measures: how much there is of the solid -- volume, centroid, second moments, crossings, index box ---------- */
+
+typedef struct rm_measure {   /* 176 bytes, 8-byte aligned; every field is written */
+    int64_t n_points;         /* nu * nv * nw */
+    int64_t n_inside;         /* inside points */
+    int64_t n_nonfinite;      /* points whose value is not finite (the sparse path: of kept blocks only) */
+    int64_t sum1[3];          /* sum of i, of j, of k over the inside points */
+    int64_t sum2[6];          /* sum of i i, j j, k k, i j, j k, k i over the inside points */
+    int64_t crossings[3];     /* axis A: lattice edges p -> p + e_A, both ends in the lattice, whose ends differ in `inside` */
+    int32_t lo[3], hi[3];     /* the index box of the inside points; n_inside == 0: lo = INT32_MAX, hi = -1 */
+    int64_t n_blocks, n_kept; /* the sparse path only, else 0 */
+    int64_t n_blocks_inside;  /* the sparse path only, else 0: dropped blocks with d - iso < 0 */
+    int64_t reserved;         /* written 0 */
+} rm_measure;
+
+struct rm_measure_world {   /* 120 bytes: rm_measure in the lattice's world units.  A tag without a typedef: the entry that
+                             * fills it has the same name, so it is spelled `struct rm_measure_world` in C and C++ alike */
+    double cell_volume;         /* |det(du, dv, dw)| */
+    double volume;              /* n_inside * cell_volume */
+    double centroid[3];         /* the lattice's point formula at the mean index, unrounded binary64; NaN when n_inside == 0 */
+    double second[6];           /* integral of (x - c)(x - c)^T dV over the inside cells: xx, yy, zz, xy, yz, zx; 0 when n_inside == 0 */
+    double projected_area[3];   /* crossings[A] * |step_B x step_C|: the surface projected along index axis A, with multiplicity */
+    double area_estimate;       /* 2/3 of the sum of the three: an isotropic estimate, NOT a bound */
+};
+
+/* The meshers say where the surface is; these entries say how much it encloses.  Everything measured is an INTEGER -- counts of
+ * inside lattice points, sums of their indices and index products, counts of sign-changing lattice edges --, so the result does
+ * not depend on the order of summation and is compared bit for bit with a numpy restatement (tests/measure_model.py), the
+ * standard the meshers are held to.  The rule:
+ *   inside    point (i, j, k) is inside iff value < iso, the mesher's rule unchanged: NaN is outside, equality is outside.
+ *   record    rm_measure above.  A point stands for its cell-sized box around it: volume = n_inside cells, and so on.
+ *   overflow  both device entries (and rm_scene_measure) return RM_E_UNSUPPORTED -- behind their RM_E_INVALID checks, ahead of
+ *             RM_E_NO_DEVICE -- when n_points * (max(nu, nv, nw) - 1)^2 does not fit below 2^63; every sum then fits an int64.
+ *             (A dense volume of at most 2^30 points always fits.)
+ *
+ * rm_measure_field_device: d_values binary64 or binary32 (value_type: RM_MESH_F64 / RM_MESH_F32) laid out by the lattice
+ * (lattice->time is not used), d_measure an rm_measure on the device; asynchronous on `stream`; it needs no scene.  A persistent
+ * grid sized from the device's compute units; a wave takes whole lattice rows, a lane the points i = lane, lane + 64, ..., each
+ * with its +i, +j and +k neighbours; one partial record per workgroup in the context's scratch buffer (ordered as
+ * rm_mesh_field_device's use of it), then one workgroup adds the partials: no atomics, nothing to initialise, re-entrant.
+ * RM_E_INVALID -- ahead of RM_E_NO_DEVICE, in this order -- for everything rm_scene_field refuses about a lattice, more than
+ * 2^30 points, null d_values when the lattice has points, null d_measure, a non-finite iso, a value_type outside the enum,
+ * d_measure or binary64 values not 8-byte aligned (binary32 values: 4).  Counts of 1 on an axis are fine: a slice has no edges
+ * along that axis, and its cross-section is n_inside.  A lattice with a zero count is RM_OK: zero sums and the empty box are
+ * written.  rm_last_kernel: measure_field_kernel<double> or <float> (measure_final_kernel for a lattice without points).
+ *
+ * rm_measure_tiles_device: the same record from what rm_scene_blocks_device (with d_dist) and the tile entries leave.
+ *   ownership  block (bx, by, bz) owns the lattice points 8 bx .. 8 bx + 7 per axis; the last block of an axis also owns point
+ *              8 nb when that index is <= n - 1.  Every lattice point is owned by exactly one block; an edge belongs to the
+ *              owner of its low end; every owned point and owned edge of a block lies inside that block's 9 x 9 x 9 tile.
+ *   kept       a kept block's owned points and edges are counted from its tile values; tile points beyond the lattice are
+ *              skipped by index, not by value.
+ *   dropped    d_slot[b] < 0.  If d_dist[b] - iso < 0 all owned points are inside: n_inside, sum1, sum2 and the box take the
+ *              closed-form sums over the owned index ranges and no edge crosses; otherwise the block contributes nothing.  A
+ *              dropped block never contributes to n_nonfinite.
+ *   GUARANTEE  whenever the exact field is `lipschitz`-Lipschitz and the tiles hold that same field (option `exact`), no point
+ *              of a dropped block's tile lies on the other side of iso than its centre (the coarse pass's bound covers the
+ *              tile), so the record equals rm_measure_field_device's over the dense volume of that field, field by field --
+ *              the block fields apart, and n_nonfinite counts kept blocks only.
+ * One 256-thread workgroup per kept block, the tile staged in LDS, up to three owned points per lane, local sums in 32 bits and
+ * the block's base indices joined once per workgroup; one lane per block for the closed forms; the partials and the last
+ * workgroup as above.  RM_E_INVALID for the lattice as the sparse entries check it, any count below 2 (the lattice must have
+ * blocks on every axis: a slice goes through the dense entry), n_kept outside 0 .. n_blocks, null d_measure, d_slot or d_dist,
+ * null d_list or d_tiles with n_kept > 0, a non-finite iso, d_slot / d_list not 4-byte or d_dist / d_tiles / d_measure not
+ * 8-byte aligned; then the overflow refusal; RM_E_NO_DEVICE.  It needs no scene.  rm_last_kernel: measure_tiles_kernel
+ * (measure_blocks_kernel when nothing is kept).
+ *
+ * rm_scene_measure: host-side and synchronous -- the coarse pass with distances, the tile pass UNDER THE EXACT FIELD whatever
+ * option `exact` says (the coarse pass decides by the exact field, so the tiles must hold it too), then the measure, all in the
+ * context's scratch buffer as rm_scene_mesh_sparse uses it; n_kept is read back once.  sparse_info may be NULL.  The checks of
+ * the entries for its own arguments (no alignment is asked of `out`), the overflow refusal, RM_E_NO_DEVICE; RM_E_NO_SCENE last.
+ * None of these is a render entry: they neither consume nor fire rm_render_attach_diagnostics and leave rm_scene_set_time's
+ * value alone.
+ *
+ * rm_measure_world: host-only, no ctx; RM_E_INVALID for a null argument or a lattice rm_scene_field refuses.  binary64, one
+ * operation at a time, no contraction, in this order (u, v, w: du, dv, dw widened; N = (double)n_inside; S = (double)sum1,
+ * Q = (double)sum2):
+ *   cell_volume     fabs((u0 * (v1 * w2 - v2 * w1) - u1 * (v0 * w2 - v2 * w0)) + u2 * (v0 * w1 - v1 * w0))
+ *   volume          N * cell_volume
+ *   centroid[c]     m[a] = S[a] / N (the quiet NaN 0x7FF8000000000000 when n_inside == 0);
+ *                   (((double)origin[c] + m[0] * u[c]) + m[1] * v[c]) + m[2] * w[c]
+ *   second          the index covariance C[a][b] = Q[ab] - (S[a] * S[b]) / N (symmetric; ab as in sum2), pushed through
+ *                   M = (u v w), M[p][a] the component p of step a: for (p, q) = xx, yy, zz, xy, yz, zx
+ *                     t[a] = (C[a][0] * M[q][0] + C[a][1] * M[q][1]) + C[a][2] * M[q][2]
+ *                     (((M[p][0] * t[0] + M[p][1] * t[1]) + M[p][2] * t[2]) * cell_volume)
+ *                       + ((N * cell_volume) / 12.0) * ((M[p][0] * M[q][0] + M[p][1] * M[q][1]) + M[p][2] * M[q][2])
+ *                   -- the second term is each cell's own box, u u^T + v v^T + w w^T over 12.  All 0.0 when n_inside == 0.
+ *   projected_area  (double)crossings[A] * sqrt((x * x + y * y) + z * z), (x, y, z) = step_B x step_C =
+ *                   (b1 * c2 - b2 * c1, b2 * c0 - b0 * c2, b0 * c1 - b1 * c0), (B, C) the other two axes in cyclic order.
+ *                   It equals the integral of |n . a| dS over the staircase surface, with multiplicity.
+ *   area_estimate   (2.0 / 3.0) * ((p[0] + p[1]) + p[2]).  An isotropic (Cauchy-Crofton) estimate, not a bound: exact in the
+ *                   limit for a sphere, and off by factors between 2/3 and 2/sqrt(3) for flat faces (2/3 for an axis-aligned
+ *                   one).  For a true area sum the mesh's quads.
+ * For a slice (nw = 1) pass a unit dw orthogonal to du and dv to read `volume` as an area.
+ * Out of scope: fractional (sub-cell) coverage, a true surface-area integral, and the N-API addon. */
+RM_API int rm_measure_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso,
+                                   void *d_measure, void *stream);
+RM_API int rm_measure_tiles_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_slot, const void *d_list, int64_t n_kept,
+                                   const void *d_dist, const void *d_tiles, double iso, void *d_measure, void *stream);
+RM_API int rm_scene_measure(rm_ctx *ctx, const rm_lattice *lattice, double iso, double lipschitz, rm_measure *out,
+                            rm_sparse_info *sparse_info);
+RM_API int rm_measure_world(const rm_lattice *lattice, const rm_measure *measure, struct rm_measure_world *out);
+
 /* ---- sharp meshes: vertices from Hermite data (dual contouring's vertex rule) --------------------------------- */
 
 typedef struct rm_sharp_query {  /* 32 bytes */
