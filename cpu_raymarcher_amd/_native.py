@@ -124,6 +124,13 @@ class rm_measure_world(C.Structure):  # include/rm_raymarch.h: struct rm_measure
                 ("projected_area", C.c_double * 3), ("area_estimate", C.c_double)]
 
 
+class rm_parts_info(C.Structure):  # include/rm_raymarch.h: struct rm_parts_info
+    _fields_ = [("n_points", C.c_int64), ("n_set", C.c_int64), ("n_parts", C.c_int64), ("gave_up", C.c_int64)]
+
+
+RM_PARTS_INSIDE, RM_PARTS_OUTSIDE = 0, 1
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -260,6 +267,9 @@ SIGNATURES = {
     "rm_measure_tiles_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, _VP, C.c_int64, _VP, _VP, C.c_double, _VP, _VP]),
     "rm_scene_measure": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_double, C.POINTER(rm_measure), C.POINTER(rm_sparse_info)]),
     "rm_measure_world": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(rm_measure), C.POINTER(rm_measure_world)]),
+    "rm_label_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, C.c_int32, _VP, _VP, _VP]),
+    "rm_measure_labels_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int64, _VP, _VP]),
+    "rm_scene_parts": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_int32, _VP, C.c_int64, _VP, C.POINTER(rm_parts_info)]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

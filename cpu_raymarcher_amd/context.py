@@ -27,6 +27,47 @@ class Measure(collections.namedtuple("Measure", "n_points n_inside n_nonfinite s
         return np.trace(second) * np.eye(3) - second
 
 
+class Parts:
+    """What Context.label_field, Context.parts and Scene.parts return (include/rm_raymarch.h, "parts"): `labels` int32
+    [nw, nv, nu] -- a numpy array, or a CUDA tensor with device=True --, the part's number at every point of the set and -1
+    elsewhere; `n_points`, `n_set`, `n_parts`; `measures`: the Measure of each of the first min(n_parts, records) parts, each
+    with `.world` and `.inertia()`; `iso` and `side` as they were asked."""
+
+    def __init__(self, labels, n_points, n_set, n_parts, measures, iso=0.0, side="inside"):
+        self.labels, self.n_points, self.n_set, self.n_parts, self.measures = labels, int(n_points), int(n_set), int(n_parts), list(measures)
+        self.iso, self.side = float(iso), side
+
+    def by_size(self):
+        """The numbers of the parts that have a Measure, the largest (most points) first, ties by number."""
+        return sorted(range(len(self.measures)), key=lambda p: (-self.measures[p].n_inside, p))
+
+    def touches_border(self, p):
+        """Whether part p has a point on the lattice's border: its index box reaches it.  (An enclosed void is an outside
+        part that does not.)"""
+        nw, nv, nu = (int(x) for x in self.labels.shape)
+        m = self.measures[p]
+        return any(lo == 0 or hi == n - 1 for lo, hi, n in zip(m.lo, m.hi, (nu, nv, nw)))
+
+    def select(self, values, keep):
+        """A copy of `values` (numpy or torch, shaped or flat, the volume that was labelled) in which every point of the set
+        whose part is not in `keep` is mirrored to the other side of iso: 2 * iso - value in the values' own type, so a value
+        equal to iso stays iso (and NaN stays NaN: both only occur in an outside set).  `mesh_field` of the result meshes the kept parts only: two
+        parts are never adjacent, so every lattice edge that crosses at a kept part keeps both its values, and no kept part's
+        vertices or quads change.  torch plumbing, not a kernel."""
+        import torch
+        if _is_torch(values):
+            v = values
+            lab = self.labels if _is_torch(self.labels) else torch.from_numpy(np.ascontiguousarray(self.labels))
+            lab = lab.to(v.device).reshape(v.shape)
+            kept = torch.isin(lab, torch.as_tensor(sorted(int(p) for p in keep), dtype=lab.dtype, device=v.device))
+            drop = (lab >= 0) & ~kept
+            return torch.where(drop, 2 * self.iso - v, v)
+        v = np.asarray(values)
+        lab = (self.labels.cpu().numpy() if _is_torch(self.labels) else np.asarray(self.labels)).reshape(v.shape)
+        drop = (lab >= 0) & ~np.isin(lab, sorted(int(p) for p in keep))
+        return np.where(drop, (2 * self.iso - v).astype(v.dtype, copy=False), v)
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -1305,6 +1346,63 @@ class Context:
         `box` = (lo, hi)) and `margin` beyond it on every side."""
         origin, du, dv, dw, shape = self._box_lattice(cells, margin, iso, box)
         return self.measure(origin, du, dv, dw, shape, iso=iso, time=time, lipschitz=lipschitz, sparse=sparse, exact=exact)
+
+    # ---- parts: the connected pieces of the solid, numbered, with a measure each ----------------
+    def label_field(self, values, origin, du, dv, dw, shape, iso=0.0, side="inside", records=64, device=False):
+        """The connected parts of a volume the caller already holds (rm_label_field_device, then rm_measure_labels_device;
+        the rule is in include/rm_raymarch.h, "parts") -> Parts.  `values` as `measure_field` takes them.  side="inside": the
+        set is value < iso; "outside": its complement, NaN included; both are 6-connected.  Parts are numbered by their
+        smallest linear index.  `records`: how many parts get a Measure (the first ones); None reads n_parts first and sizes
+        the records exactly (2^20 at most), a second read.  device=True leaves `.labels` a CUDA tensor.  On torch's current stream; the info
+        and the records come back in one read.  A non-zero gave_up raises RmError."""
+        if side not in ("inside", "outside"):
+            raise ValueError("side is 'inside' or 'outside'")
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU labelling")
+        import torch
+        lat = make_lattice(origin, du, dv, dw, shape)
+        n = lat.nu * lat.nv * lat.nw
+        values, vt = self._mesh_values(values, n)
+        dev = torch.device("cuda", self.device)
+        labels = torch.empty((lat.nw, lat.nv, lat.nu), dtype=torch.int32, device=dev)
+        words = C.sizeof(N.rm_measure) // 8
+        info = torch.empty(4, dtype=torch.int64, device=dev)
+
+        def measure(k):
+            """The info and k records behind it in one int64 tensor, on the host."""
+            out = torch.empty(4 + words * k, dtype=torch.int64, device=dev)
+            out[:4].copy_(info)
+            N.check(self._h, N.lib().rm_measure_labels_device(self._h, C.byref(lat), _ptr(labels) if n else None, k, _ptr(out[4:]) if k else None,
+                                                              _current_stream_ptr()))
+            return out.cpu().numpy()
+
+        N.check(self._h, N.lib().rm_label_field_device(self._h, C.byref(lat), _ptr(values) if n else None, vt, float(iso),
+                                                       N.RM_PARTS_OUTSIDE if side == "outside" else N.RM_PARTS_INSIDE, _ptr(labels) if n else None,
+                                                       _ptr(info), _current_stream_ptr()))
+        if records is None:
+            head = info.cpu().numpy()
+            if head[3]:
+                raise N.RmError(N.RM_E_HIP, "the labelling gave up: a thread ran out of its hop budget")
+            records = min(int(head[2]), 1 << 20)  # what rm_measure_labels_device takes at most
+        raw = measure(int(records))
+        if raw[3]:
+            raise N.RmError(N.RM_E_HIP, "the labelling gave up: a thread ran out of its hop budget")
+        n_parts = int(raw[2])
+        recs = [N.rm_measure.from_buffer_copy(raw[4 + words * p:4 + words * (p + 1)].tobytes()) for p in range(min(n_parts, int(records)))]
+        return Parts(labels if device else labels.cpu().numpy(), int(raw[0]), int(raw[1]), n_parts, [measure_from_record(lat, r) for r in recs], float(iso),
+                     side)
+
+    def parts(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, side="inside", records=64, device=False, exact=True):
+        """The connected parts of the active scene's solid over a lattice -> Parts (`label_field`): `field` samples the volume
+        on the device (float64, honouring `exact` as `field` does) and `label_field` labels and measures it."""
+        vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True, exact=exact)
+        return self.label_field(vol, origin, du, dv, dw, shape, iso=iso, side=side, records=records, device=device)
+
+    def parts_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, box=None, side="inside", records=64, device=False, exact=True):
+        """`parts` over `mesh_box`'s lattice: cells[0] x cells[1] x cells[2] cells that cover scene_info()'s root box (or
+        `box` = (lo, hi)) and `margin` beyond it on every side."""
+        origin, du, dv, dw, shape = self._box_lattice(cells, margin, iso, box)
+        return self.parts(origin, du, dv, dw, shape, iso=iso, time=time, side=side, records=records, device=device, exact=exact)
 
     def _box_lattice(self, cells, margin, iso, box):
         """The lattice `mesh_box` meshes over -> (origin, du, dv, dw, shape)."""

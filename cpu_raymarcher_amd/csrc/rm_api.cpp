@@ -3633,6 +3633,143 @@ int rm_measure_world(const rm_lattice *lattice, const rm_measure *measure, struc
     return RM_OK;
 }
 
+// ---- parts: the connected components of one side of iso, and a record each (rm_parts.hip)
+
+static_assert(sizeof(rm_parts_info) == 32 && sizeof(RmPartsInfo) == sizeof(rm_parts_info), "rm_parts_info layout");
+
+namespace {
+
+// what the parts entries check about a lattice of at most 2^30 points, iso and the side; *n receives the point count
+const char *parts_error(const rm_lattice *lattice, int64_t *n) {
+    if (const char *bad = lattice_error(lattice, n)) return bad;
+    return *n > (int64_t(1) << 30) ? "more than 2^30 lattice points: the labelling does not split a volume" : nullptr;
+}
+const char *parts_side_error(double iso, int32_t side) {
+    if (!std::isfinite(iso)) return "non-finite iso";
+    return side != RM_PARTS_INSIDE && side != RM_PARTS_OUTSIDE ? "side must be RM_PARTS_INSIDE or RM_PARTS_OUTSIDE" : nullptr;
+}
+const char *parts_records_error(int64_t n_records, const void *records) {
+    if (n_records < 0 || n_records > RM_PARTS_MAX_RECORDS) return "n_records must be in [0, 2^20]";
+    return n_records > 0 && !records ? "null records with n_records above 0" : nullptr;
+}
+
+// The label launch, n > 0: everything on the device, the info zeroed first -- gave_up is only ever raised.
+int launch_label_field(rm_ctx *ctx, const rm_lattice *lat, int64_t n, const void *d_values, int32_t value_type, double iso, int32_t side, void *d_labels,
+                       void *d_map, void *d_totals, void *d_info, hipStream_t stream) {
+    RmPartsArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.values = d_values;
+    a.iso = iso;
+    a.labels = static_cast<int32_t *>(d_labels);
+    a.map = static_cast<uint32_t *>(d_map);
+    a.totals = static_cast<uint32_t *>(d_totals);
+    a.info = static_cast<RmPartsInfo *>(d_info);
+    a.n = n;
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.n_blocks = static_cast<unsigned int>(mesh_blocks(n));
+    a.f32 = value_type == RM_MESH_F32;
+    a.outside = side == RM_PARTS_OUTSIDE;
+    RM_HIP(ctx, hipMemsetAsync(d_info, 0, sizeof(rm_parts_info), stream));
+    RM_HIP(ctx, rm_launch_label_field(a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+int launch_measure_labels(rm_ctx *ctx, const rm_lattice *lat, int64_t n, const void *d_labels, int64_t n_records, void *d_records, hipStream_t stream) {
+    RmPartsMeasureArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.labels = static_cast<const int32_t *>(d_labels);
+    a.records = static_cast<RmMeasure *>(d_records);
+    a.n = n;
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.n_records = static_cast<unsigned int>(n_records);
+    RM_HIP(ctx, rm_launch_measure_labels(a, ctx->num_cus, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_label_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, int32_t side, void *d_labels,
+                          void *d_info, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = parts_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (n > 0 && !d_values) return fail(ctx, RM_E_INVALID, "null values");
+    if (const char *bad = parts_side_error(iso, side)) return fail(ctx, RM_E_INVALID, bad);
+    if (value_type != RM_MESH_F64 && value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
+    if (misaligned(d_values, value_type == RM_MESH_F64 ? 7 : 3)) return fail(ctx, RM_E_INVALID, "values must be aligned to their type");
+    if (n > 0 && !d_labels) return fail(ctx, RM_E_INVALID, "null labels");
+    if (!d_info) return fail(ctx, RM_E_INVALID, "null info");
+    if (misaligned(d_labels, 3)) return fail(ctx, RM_E_INVALID, "labels must be 4-byte aligned");
+    if (misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "info must be 8-byte aligned");
+    if (const int rc = need_device(ctx, "labelling", false)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    // no point, no launch: the info is zero; else the map and the block totals, the mesher's layout
+    return scratch_call(ctx, s, n > 0, d_info, sizeof(rm_parts_info), {4 * static_cast<size_t>(n), 12 * mesh_blocks(n)},
+                        [&](const Staging &st, const size_t *o) {
+                            return launch_label_field(ctx, lattice, n, d_values, value_type, iso, side, d_labels, st.at<void>(o[0]), st.at<void>(o[1]), d_info, s);
+                        });
+}
+
+int rm_measure_labels_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_labels, int64_t n_records, void *d_records, void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = parts_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (n > 0 && !d_labels) return fail(ctx, RM_E_INVALID, "null labels");
+    if (const char *bad = parts_records_error(n_records, d_records)) return fail(ctx, RM_E_INVALID, bad);
+    if (misaligned(d_labels, 3)) return fail(ctx, RM_E_INVALID, "labels must be 4-byte aligned");
+    if (misaligned(d_records, 7)) return fail(ctx, RM_E_INVALID, "records must be 8-byte aligned");
+    if (!measure_fits(*lattice, n)) return fail(ctx, RM_E_UNSUPPORTED, kMeasureOverflow);
+    if (const int rc = need_device(ctx, "measure", false)) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // the records are the caller's and nothing else is written: no scratch
+    return launch_measure_labels(ctx, lattice, n, d_labels, n_records, d_records, static_cast<hipStream_t>(stream));
+}
+
+int rm_scene_parts(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t side, int32_t *labels_out, int64_t n_records, rm_measure *records_out,
+                   rm_parts_info *info_out) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = parts_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = parts_side_error(iso, side)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = parts_records_error(n_records, records_out)) return fail(ctx, RM_E_INVALID, bad);
+    if (!info_out) return fail(ctx, RM_E_INVALID, "null info");
+    if (!measure_fits(*lattice, n)) return fail(ctx, RM_E_UNSUPPORTED, kMeasureOverflow);
+    int rc = need_device(ctx, "labelling", true);
+    if (rc) return rc;
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // The volume, the labels, the labelling's scratch, the info and the records side by side in the scratch buffer.
+    const size_t points = static_cast<size_t>(n), records = static_cast<size_t>(n_records);
+    Staging st{ctx};
+    const size_t o_vol = st.region(8 * points), o_labels = st.region(4 * points), o_map = st.region(4 * points), o_totals = st.region(12 * mesh_blocks(n)),
+                 o_info = st.region(sizeof(rm_parts_info)), o_records = st.region(sizeof(rm_measure) * records);
+    if ((rc = st.reserve())) return rc;
+    if (n > 0) {
+        RmRenderParams p;
+        RmFieldArgs a;
+        fill_field(ctx, lattice, p, a);  // the field entries' own launch, at the lattice's time
+        if (const int erc = use_exact(ctx, p)) return erc;
+        a.dist = st.at<double>(o_vol);
+        a.first = 0;
+        a.n = n;
+        RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
+        if ((rc = launch_label_field(ctx, lattice, n, st.at<void>(o_vol), RM_MESH_F64, iso, side, st.at<void>(o_labels), st.at<void>(o_map),
+                                     st.at<void>(o_totals), st.at<void>(o_info), ctx->stream)))
+            return rc;
+    } else {
+        RM_HIP(ctx, st.zero(o_info, sizeof(rm_parts_info)));
+    }
+    if ((rc = launch_measure_labels(ctx, lattice, n, st.at<void>(o_labels), n_records, st.at<void>(o_records), ctx->stream))) return rc;
+    if (labels_out && n > 0) RM_HIP(ctx, st.out(labels_out, o_labels, 4 * points));
+    if (records) RM_HIP(ctx, st.out(records_out, o_records, sizeof(rm_measure) * records));
+    RM_HIP(ctx, st.out(info_out, o_info, sizeof *info_out));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
     RmRenderParams p;
     const auto supported = [&] {

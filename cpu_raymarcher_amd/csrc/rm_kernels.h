@@ -380,6 +380,28 @@ struct RmMeasureTilesArgs {
     long long n;
     unsigned int nu, nv, nw, nbu, nbv, nbw, n_blocks, n_kept;
 };
+// rm_label_field_device / rm_measure_labels_device (rm_parts.hip): the connected parts of the points on one side of iso.
+#define RM_PARTS_MAX_RECORDS (1 << 20)
+struct RmPartsInfo {  // rm_parts_info (32 bytes)
+    long long n_points, n_set, n_parts, gave_up;
+};
+struct RmPartsArgs {
+    const void *values;  // n binary64 values, or binary32 ones with f32
+    double iso;
+    int32_t *labels;     // n words: the union-find's parent array, then the part numbers
+    uint32_t *map;       // n words: a root's part number
+    uint32_t *totals;    // 2 x n_blocks words: roots (they become offsets) and points of the set per workgroup
+    RmPartsInfo *info;   // zeroed ahead of the launch
+    long long n;
+    unsigned int nu, nv, nw, n_blocks;  // n_blocks = ceil(n / RM_MESH_BLOCK)
+    int f32, outside;
+};
+struct RmPartsMeasureArgs {
+    const int32_t *labels;
+    RmMeasure *records;  // n_records of them
+    long long n;
+    unsigned int nu, nv, nw, n_records;
+};
 // The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
 // A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
 // its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
@@ -586,6 +608,12 @@ unsigned int rm_measure_field_groups(long long n, unsigned int nv, unsigned int 
 unsigned int rm_measure_block_groups(unsigned int n_blocks, int num_cus);
 hipError_t rm_launch_measure_field(const RmMeasureFieldArgs &a, unsigned int n_groups, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_measure_tiles(const RmMeasureTilesArgs &a, unsigned int n_groups, hipStream_t stream, const char **kernel_name);
+// The parts (rm_parts.hip).  rm_launch_label_field: parts_init_kernel<T>, parts_merge_kernel, parts_flatten_kernel, parts_scan_kernel,
+// parts_number_kernel and parts_relabel_kernel over a.n_blocks workgroups each (the scan: one); 0 < a.n <= 2^30 and *a.info zeroed
+// on the stream beforehand.  rm_launch_measure_labels: parts_records_kernel over the a.n_records records (none: not launched),
+// then parts_measure_kernel over a persistent grid that num_cus bounds (no point: not launched); 0 <= a.n <= 2^30.
+hipError_t rm_launch_label_field(const RmPartsArgs &a, hipStream_t stream, const char **kernel_name);
+hipError_t rm_launch_measure_labels(const RmPartsMeasureArgs &a, int num_cus, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

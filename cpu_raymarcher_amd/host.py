@@ -194,6 +194,18 @@ class Scene:
             return self.ctx.measure_box(cells, margin=margin, **more)
         return self.ctx.measure(origin, du, dv, dw, shape, **more)
 
+    def parts(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, side="inside", records=64,
+              device=False, exact=True):
+        """The connected pieces of the solid getDistance < iso (side="outside": of what surrounds it) at this scene's own
+        time -> Parts (Context.parts): `.labels`, `.n_parts`, `.n_set`, `.measures` (a Measure per part), `.by_size()`,
+        `.touches_border(p)`, `.select(values, keep)`.  Over the lattice origin + i * du + j * dv + k * dw of `shape` points,
+        or, without one, over the root box in `cells` cells (Context.parts_box)."""
+        self._activate()
+        more = dict(iso=iso, time=self.time, side=side, records=records, device=device, exact=exact)
+        if origin is None:
+            return self.ctx.parts_box(cells, margin=margin, **more)
+        return self.ctx.parts(origin, du, dv, dw, shape, **more)
+
     def meshSession(self, origin, du, dv, dw, shape, iso=0.0, lipschitz=1.0):
         """Opens a mesh session on this scene at its own time (Context.mesh_session) and returns it: session.mesh() is
         toMesh(sparse=True, exact=True) over the lattice, and from now on editSpheres / setSphere / insertSphere /

@@ -638,6 +638,74 @@ RM_API int rm_scene_measure(rm_ctx *ctx, const rm_lattice *lattice, double iso, 
                             rm_sparse_info *sparse_info);
 RM_API int rm_measure_world(const rm_lattice *lattice, const rm_measure *measure, struct rm_measure_world *out);
 
+/* ---- parts: the connected pieces of the solid (or of what surrounds it), numbered, with a measure each --------------- */
+
+enum { RM_PARTS_INSIDE = 0, RM_PARTS_OUTSIDE = 1 };
+
+typedef struct rm_parts_info {   /* 32 bytes, 8-byte aligned; every field is written */
+    int64_t n_points;            /* nu * nv * nw */
+    int64_t n_set;               /* points of the set S */
+    int64_t n_parts;             /* connected components of S */
+    int64_t gave_up;             /* non-zero: a thread ran out of its hop budget (below); labels and counts are then unspecified */
+} rm_parts_info;
+
+/* The measures are sums over the whole inside set; these entries split the set into its pieces.  Everything is an integer with
+ * one right answer and is compared bit for bit with a numpy restatement (tests/parts_model.py).  The rule:
+ *   set S      side = RM_PARTS_INSIDE: point (i, j, k) is in S iff value < iso -- the meshers' and the measures' rule unchanged:
+ *              NaN is outside, equality is outside.  side = RM_PARTS_OUTSIDE: S is the complement, !(value < iso), NaN included.
+ *   adjacency  two points of S are adjacent iff a lattice edge joins them (the 6-neighbourhood; the edges `crossings` counts).
+ *              BOTH sides use this rule: the outside is 6-connected too, which is not the topologically dual choice (with a
+ *              6-connected inside the dual outside would be 26-connected), so two outside pockets that touch across a diagonal
+ *              count as two.
+ *   part       a connected component of S.
+ *   numbering  parts are numbered 0 .. n_parts - 1 in ascending order of their smallest linear index l = i + nu * (j + nv * k)
+ *              (the numbering of scipy.ndimage.label(...)[0] - 1 on the [nw, nv, nu] array).
+ *   labels     int32[n_points] in the lattice's order: the part's number, or -1 where the point is not in S.
+ *   info       rm_parts_info above.
+ *   records    part p < n_records gets an rm_measure, the struct unchanged: n_points is the lattice's; n_inside, sum1, sum2, lo
+ *              and hi are taken over the part's points; crossings[A] counts the lattice edges along A with exactly one end in
+ *              S, for the part of the end that is in S (two different parts are never adjacent, so every such edge belongs to
+ *              one part); n_nonfinite, the block fields and reserved are 0.  Records p >= n_parts are the empty record (zero
+ *              sums, lo = INT32_MAX, hi = -1); parts numbered >= n_records are skipped.  Hence, with side = RM_PARTS_INSIDE and
+ *              n_records >= n_parts, the records summed field by field (the boxes united) equal rm_measure_field_device's
+ *              record of the same values in n_inside, sum1, sum2, crossings, lo and hi.  A part touches the lattice's border
+ *              iff its box does: an enclosed void is an outside part whose box does not, and needs no field of its own.
+ *
+ * rm_label_field_device: d_values as rm_measure_field_device takes them (it needs no scene; lattice->time is not used),
+ * d_labels n_points int32 and d_info an rm_parts_info on the device; asynchronous on `stream`, re-entrant, nothing to
+ * initialise.  d_labels is the parent array of a lock-free union-find: every point of S first points at the start of its run
+ * along i within its wave and row (one ballot), unions with the -j and -k neighbours (and -i where a wave cut a run) link the
+ * larger root below the smaller by atomicMin, so a part's root is its smallest index in whatever order the atomics arrive; the
+ * roots are counted per workgroup, scanned, numbered by ballot rank into a map in the context's scratch buffer (ordered as
+ * rm_mesh_field_device's use of it) and the labels rewritten through the map.  No thread waits for another; every loop lowers
+ * an index at every step and has a budget of n_points steps, after which the thread stops and sets gave_up -- which no
+ * well-formed run does.  RM_E_INVALID -- ahead of RM_E_NO_DEVICE -- for everything rm_measure_field_device refuses about the
+ * lattice, the values, iso and value_type (more than 2^30 points among it), a `side` outside the enum, null d_labels when the
+ * lattice has points, null d_info, d_labels not 4-byte or d_info not 8-byte aligned.  Counts of 1 on an axis are fine.  A lattice
+ * with a zero count is RM_OK: info {0, 0, 0, 0}.  rm_last_kernel: parts_relabel_kernel (unchanged for a lattice without points).
+ *
+ * rm_measure_labels_device: the records from labels of that form alone -- the values are not needed; labels outside
+ * -1 .. n_records - 1 are skipped.  d_records: n_records rm_measure on the device, all of them initialised by the entry.  A
+ * persistent grid of waves over contiguous spans of the lattice; where a wave sees one label it keeps the sums in registers and
+ * adds them to the record once, else once per run of a label along i; 64-bit integer atomicAdd and 32-bit atomicMin / atomicMax,
+ * so the record does not depend on the order.  It uses no scratch.  RM_E_INVALID for the lattice, more than 2^30 points, null
+ * d_labels when the lattice has points, n_records < 0 or > 2^20, null d_records with n_records > 0, d_labels not 4-byte or
+ * d_records not 8-byte aligned; then the measures' overflow refusal RM_E_UNSUPPORTED; RM_E_NO_DEVICE.  rm_last_kernel:
+ * parts_measure_kernel (parts_records_kernel for a lattice without points; unchanged with n_records = 0).
+ *
+ * rm_scene_parts: host-side and synchronous -- the dense volume of the active scene UNDER THE EXACT FIELD whatever option
+ * `exact` says (as rm_scene_measure), the labels and the records, all in the context's scratch buffer, then one copy back.
+ * labels_out may be NULL.  The checks of the two entries for its own arguments (no alignment is asked of host buffers), the
+ * overflow refusal, RM_E_NO_DEVICE; RM_E_NO_SCENE last.  Not a render entry: it neither consumes nor fires
+ * rm_render_attach_diagnostics and leaves rm_scene_set_time's value alone.
+ * Out of scope: a sparse (tile) path -- dropped inside blocks would need a labelling rule of their own --, and the N-API addon. */
+RM_API int rm_label_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso,
+                                 int32_t side, void *d_labels, void *d_info, void *stream);
+RM_API int rm_measure_labels_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_labels, int64_t n_records, void *d_records,
+                                    void *stream);
+RM_API int rm_scene_parts(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t side, int32_t *labels_out, int64_t n_records,
+                          rm_measure *records_out, rm_parts_info *info_out);
+
 /* ---- sharp meshes: vertices from Hermite data (dual contouring's vertex rule) --------------------------------- */
 
 typedef struct rm_sharp_query {  /* 32 bytes */
