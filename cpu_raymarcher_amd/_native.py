@@ -326,6 +326,8 @@ SIGNATURES = {
     "rm_debug_overlap_fill": (C.c_int, [_VP, C.c_int32, C.c_int64, C.POINTER(C.c_int32)]),
     "rm_debug_step_box": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "rm_debug_cell_tab": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "rm_debug_runner_up": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
+    "rm_debug_scan_keys": (C.c_int, [_VP, C.c_int64, C.c_float, C.POINTER(C.c_uint32), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "rm_debug_exact_tree": (C.c_int, [_VP, C.POINTER(C.c_int32)]),
     "rm_debug_rect_cull": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
     "rm_debug_leaf_rects": (C.c_int, [_VP, _VP, _VP, C.c_int32, C.c_int32, _VP, _VP, C.c_int64, C.POINTER(C.c_int64)]),

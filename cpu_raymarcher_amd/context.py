@@ -292,6 +292,27 @@ class Context:
         return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2], list_cap=out[3], list_cap_without=out[4], table_bytes=out[5],
                     per_cu=out[6], scene_bytes=out[7], scene_bytes_without=out[8], cells=out[9], records=out[10], leaf_sets=out[11])
 
+    def runner_up(self):
+        """Section M's runner-up test (rm_debug_runner_up; no device needed but for `last`): dict(last = the last v2 launch
+        bounded the runner-up sphere of an in-round step by its own distance, planned = a launch of the active scene would
+        under the options as they stand, reason = why not (0 it would, 1 option `runner_up` is 0, 2 the launch does not
+        take the cell table, 3 the spheres do not share one radius))."""
+        out = (C.c_int32 * 4)()
+        N.check(self._h, N.lib().rm_debug_runner_up(self._h, out))
+        return dict(last=bool(out[0]), planned=bool(out[1]), reason=out[2])
+
+    @staticmethod
+    def scan_keys(keys, rf=0.5):
+        """The three-key update of the one-radius scan over a list of uint32 keys, from the kernel's own text on the host
+        (rm_debug_scan_keys; no context state, no device): (the three smallest keys in order, 0xFFFFFFFF where there are
+        fewer; the third key's lower bound for radius rf, +inf when fewer than three keys came; that bound as section M
+        reads it, after its trip through the upper half of a word)."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32).reshape(-1)
+        out = (C.c_uint32 * 3)()
+        lb3, carried = C.c_float(0.0), C.c_float(0.0)
+        N.check(None, N.lib().rm_debug_scan_keys(_ptr(k) if k.size else None, int(k.size), float(rf), out, C.byref(lb3), C.byref(carried)))
+        return [int(out[0]), int(out[1]), int(out[2])], lb3.value, carried.value
+
     def rect_cull(self, rot, origin, width, height):
         """The leaf rectangles of the v2 bundle cull for a camera (rot[9], origin[3]: rm_camera_from_angles) and a full
         frame (rm_debug_rect_cull; no device needed but for `last`): dict(last = the last v2 launch culled by rectangles,

@@ -438,15 +438,18 @@ struct rm_ctx {
     // that is really there.  0: the floor alone.
     int64_t opt_overlap_fill = 1;
     int hw_queues = 4;  // GPU_MAX_HW_QUEUES as rm_create found it (read_hw_queues); the library never sets it
-    uint32_t last_v2_shape[6] = {0, 0, 0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
+    uint32_t last_v2_shape[7] = {0, 0, 0, 0, 0, 0, 0};  // the last v2 launch: workgroups, threads per workgroup, dynamic LDS bytes (rm_debug_last_launch); whether section M
                                                   // tested its steps against the step-box table (rm_debug_step_box); whether its cull went by leaf rectangles (rm_debug_rect_cull);
-                                                  // whether section B read its candidates from the cell table (rm_debug_cell_tab)
+                                                  // whether section B read its candidates from the cell table (rm_debug_cell_tab); whether section M bounded the
+                                                  // runner-up by its own distance (rm_debug_runner_up)
     int64_t opt_item_wide = 0;  // v2: the 64-pixel batches of an item side by side (1) or one above the other (0)
     int64_t opt_multi_step = 1;  // v2 BVH: in-round march steps (rm_render_v2.hip, section M)
     int64_t opt_step_box = 1;    // ... test their leaf sets against the bracket of the round's point in the scene's threshold tables (rm_scene_host.cpp
                                  // build_step_box) where the scene has them and they fit the launch's LDS; 0: the exact test against the leaf lists
     int64_t opt_cell_tab = 1;    // v2 BVH: section B reads a point's candidate spheres, and section M its step box, from the scene's table of threshold cells
                                  // (rm_scene_host.cpp build_cell_tab) where the launch takes the step-box table and the cell table fits the LDS the point-query grid frees
+    int64_t opt_runner_up = 1;   // v2 BVH, one-radius launches with the cell table: section M bounds the runner-up sphere by its own distance at the new point and
+                                 // the candidates behind it by the third scan key's bound (round 12: fewer runs end, fewer rounds begin); 0: all of them by lb2 - dd
     int64_t opt_lds_kb = 0;         // v2: LDS budget per workgroup the launcher trims the hit lists to (0: as many workgroups per CU as the kernel's registers allow; 32: five per CU, 40: four)
     int64_t opt_refill = 64;
     int64_t opt_recs = 1;  // octree leaves read leaf-ordered sphere records
@@ -1425,6 +1428,7 @@ int fill_params(rm_ctx *ctx, const rm_job *job, RmRenderParams &p) {
     p.ct_words = static_cast<int32_t>(ctx->host.cell_tab.size());
     for (int k = 0; k < 3; ++k) p.ct_dim[k] = ctx->host.ct_dim[k];
     p.cell_on = (ctx->opt_cell_tab && p.step_box && !ctx->host.cell_tab.empty() && (ctx->dev.cell_tab || !ctx->has_device)) ? 1 : 0;
+    p.runner_up = (ctx->opt_runner_up && p.cell_on) ? 1 : 0;  // (and a one-radius scene: the launcher's to see, rm_v2_plan)
     p.uniform_radius = 0;
     if (ctx->opt_uniform && !ctx->host.general && ctx->host.spheres.size() >= 2 &&
         ctx->host.spheres.size() <= 256) {  // one radius, bit for bit; at most 256 spheres: the scan keys carry the id in eight bits
@@ -4149,6 +4153,50 @@ int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]) {
     return RM_OK;
 }
 
+// Section M's runner-up test (option `runner_up`), without a device: out[0] whether the last v2 launch bounded the runner-up by
+// its own distance (0 before the first), out[1] whether a launch of the active scene under the options as they stand would
+// (rm_v2_plan), out[2] why not -- 0 it would, 1 option `runner_up` is 0, 2 the launch does not take the cell table
+// (rm_debug_cell_tab says why), 3 the scene's spheres do not share one radius (or option `uniform` is 0).
+int rm_debug_runner_up(rm_ctx *ctx, int32_t out[4]) {
+    if (!ctx || !out) return RM_E_INVALID;
+    for (int k = 0; k < 4; ++k) out[k] = 0;
+    out[0] = static_cast<int32_t>(ctx->last_v2_shape[6]);
+    if (!ctx->have_scene) return fail(ctx, RM_E_NO_SCENE, "no scene set");
+    rm_job job;
+    std::memset(&job, 0, sizeof job);
+    job.width = job.height = job.y_end = 64;
+    job.algorithm = RM_ALG_SPHERE_TRACER;
+    job.scene_preset_index = ctx->scene_is_uploaded ? RM_SCENE_UPLOADED : ctx->scene_preset;
+    job.acceleration_structure = ctx->host.accel;
+    job.overshoot_factor = job.step_size = std::nan("");
+    const double scene_time = ctx->time;
+    RmRenderParams p;
+    const int rc = fill_params(ctx, &job, p);
+    ctx->time = scene_time;  // (a debug read leaves the scene's time alone)
+    if (rc) return rc;
+    const RmV2Plan plan = rm_v2_plan(p);
+    const bool v2 = p.variant == 2 && p.algorithm == 0 && p.accel == 2;
+    out[1] = v2 && plan.runner_up ? 1 : 0;
+    out[2] = out[1] ? 0 : (!ctx->opt_runner_up ? 1 : (!(v2 && plan.cell_on) ? 2 : 3));
+    return RM_OK;
+}
+
+// The three-key update of the one-radius scan (rm_kernels.h rm_scan_keys_update, the text the wave loop runs) over a caller's
+// list of n keys, without a device: out3[0 .. 2] the three smallest in order (all ones where there are fewer), *lb3 the third
+// key's bound for radius rf (rm_scan_key_bound: +inf exactly when fewer than three keys came), *lb3_carried that bound as section
+// M reads it after its trip through the upper half of a word (rm_runner_up_pack_bound / _unpack_bound).  `keys` may be null when n is 0.
+int rm_debug_scan_keys(const uint32_t *keys, int64_t n, float rf, uint32_t out3[3], float *lb3, float *lb3_carried) {
+    if (n < 0 || (n > 0 && !keys) || !out3 || !lb3 || !lb3_carried) return RM_E_INVALID;
+    RmScanKeys k = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
+    for (int64_t i = 0; i < n; ++i) rm_scan_keys_update(k, keys[i]);
+    out3[0] = k.best;
+    out3[1] = k.second;
+    out3[2] = k.third;
+    *lb3 = rm_scan_key_bound(k.third, rf);
+    *lb3_carried = rm_runner_up_unpack_bound(rm_runner_up_pack_bound(*lb3));
+    return RM_OK;
+}
+
 // What the next exact query (option `exact`) of the active scene walks, without a device: out[0] the mode (0 every object, 1 the
 // scene's BVH, 2 an own tree), out[1 .. 3] the nodes, leaves and depth of that tree (zeros in mode 0).  Builds the own tree if
 // it is due, whatever the option says.
@@ -4256,6 +4304,7 @@ static const OptionRow kOptions[] = {
     {"multi_step", &rm_ctx::opt_multi_step, kSwitch, {}, nullptr},
     {"step_box", &rm_ctx::opt_step_box, kSwitch, {}, nullptr},
     {"cell_tab", &rm_ctx::opt_cell_tab, kSwitch, {}, nullptr},
+    {"runner_up", &rm_ctx::opt_runner_up, kSwitch, {}, nullptr},
     {"item_wide", &rm_ctx::opt_item_wide, kSwitch, {}, nullptr},
     {"prune", &rm_ctx::opt_prune, kSwitch, {}, nullptr},
     {"rtc_spheres", &rm_ctx::opt_rtc_spheres, kRange, {0, 33}, "rtc_spheres must be 0..33"},

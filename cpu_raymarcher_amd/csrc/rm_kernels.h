@@ -82,6 +82,51 @@ inline __host__ __device__ RmLeafRect rm_leaf_rect(const float lo[3], const floa
     return r;
 }
 
+// The order keys of the one-radius scan (rm_render_v2.hip scan_sphere<true>: a sphere's squared centre distance, its id in the
+// low byte) and the three smallest of them: one text for the wave loop and for rm_debug_scan_keys, which needs no device.
+// All three start at all ones ("no sphere").  After any number of updates best <= second <= third are the three smallest keys
+// fed so far, equal keys counted as often as they came -- five integer min / max, no compare and no select:
+//   lo = min(best, key), hi = max(best, key): the new best, and whichever of the two is displaced;
+//   mid = max(second, hi): whichever of those two is displaced in turn (taken before second changes);
+//   second = min(second, hi);  third = min(third, mid).
+// Section M's runner-up test (option `runner_up`) reads the second key's id and the third key's distance.
+struct RmScanKeys {
+    uint32_t best, second, third;
+};
+inline __host__ __device__ void rm_scan_keys_update(RmScanKeys &k, uint32_t key) {
+    const uint32_t lo = key < k.best ? key : k.best, hi = key < k.best ? k.best : key;
+    const uint32_t mid = hi < k.second ? k.second : hi;
+    k.best = lo;
+    k.second = hi < k.second ? hi : k.second;
+    k.third = mid < k.third ? mid : k.third;
+}
+// the key of a squared distance s2 >= 0 (its bit pattern, which orders like the value) and a sphere id below 256
+inline __host__ __device__ uint32_t rm_scan_key(uint32_t s2_bits, uint32_t id) { return (s2_bits & 0xFFFFFF00u) | (id & 0xFFu); }
+// A key's conservative binary32 lower bound of that sphere's distance (radius rf), by the formula and margin of
+// scan_finish_uniform (rm_render_v2.hip); +inf for the all-ones key: there is no such sphere.  Clearing the id byte only lowers
+// s2, and the bound is monotone in s2 up to what the margin absorbs, so it bounds every sphere whose key is no smaller.
+inline __host__ __device__ float rm_scan_key_bound(uint32_t key, float rf) {
+    const float s2 = __builtin_bit_cast(float, key & 0xFFFFFF00u);
+#ifdef __HIP_DEVICE_COMPILE__
+    const float len = __builtin_amdgcn_sqrtf(s2);
+#else
+    const float len = __builtin_sqrtf(s2);
+#endif
+    const float lb = (len - rf) - (len + __builtin_fabsf(rf) + 1.0f) * 4e-6f;
+    return key != 0xFFFFFFFFu && s2 < __builtin_inff() ? lb : __builtin_inff();
+}
+// That bound on its way from section B to section M, in the upper half of a word (NormalAux::k1, rm_render_v2.hip).  The upper
+// half of a binary32 number is the number with its mantissa cut to seven bits: the cut moves a value towards zero by less than
+// 2^-7 of its magnitude, so the value is lowered by 2^-6 of its magnitude first and what is unpacked never exceeds what was
+// packed, and is at least 0.97 of a positive one.  +inf stays +inf, a NaN a NaN; only a negative denormal can come out raised,
+// by less than 2^-126.
+inline __host__ __device__ uint32_t rm_runner_up_pack_bound(float lb3) {
+    const float mag = __builtin_fabsf(lb3);
+    const float low = lb3 - (mag < 3.0e38f ? mag : 3.0e38f) * 0.015625f;
+    return __builtin_bit_cast(uint32_t, low) & 0xFFFF0000u;
+}
+inline __host__ __device__ float rm_runner_up_unpack_bound(uint32_t word) { return __builtin_bit_cast(float, word & 0xFFFF0000u); }
+
 // rm_compare_frames_device (rm_frame_ops.hip, compare_kernel).  The maps are rm_compare_map's values.
 enum { RM_CMP_NONE = -1, RM_CMP_SDF = 0, RM_CMP_ITERS = 1, RM_CMP_DEPTH = 2, RM_CMP_NORMAL = 3, RM_CMP_SURFACE = 4 };
 struct RmCompareStats {  // rm_compare_stats: sums = sum_sdf_a .. a_cheaper in the order of the header
@@ -508,6 +553,7 @@ inline bool rm_rect_cull_camera_ok(const float rot[9], const float origin[3]) {
 struct RmV2Plan {
     bool lds, rel;
     int list_cap, step_box, tier, refused, cell_on, cell_refused;
+    int runner_up;  // section M bounds the runner-up by its own distance (asked for through RmRenderParams::runner_up; granted to a one-radius launch that took the cell table)
     int per_cu;  // workgroups of the launch that a CU's LDS holds (at most RM_V2_WAVES: the registers')
     size_t scene_bytes, list_bytes;
 };

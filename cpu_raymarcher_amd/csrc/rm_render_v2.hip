@@ -51,7 +51,11 @@ __shared__ unsigned int rm_cnt_s[32];
 // why an in-round run of march steps (section M) ends: 0 the leaf set changed, 1 the point left the root box or met a crowded
 // cell, 2 the end of the BVH interval, 3 the runner-up came too close.  Executions at slot i, lanes at i + 4; added to
 // P.stamps[40 .. 47] (the first words of the wave-time block, which an RM_COUNTS build does not otherwise write).
-__shared__ unsigned int rm_cnt_e[8];
+// Round 12, option `runner_up`, a second group of the same shape in P.stamps[48 .. 55]: 8 trips that the runner-up's own
+// distance accepted and lb2 - dd would have refused (RM_CNT_END counts an event of section M there, not an end), 9 runs that end
+// for the runner-up although that test was made.  The sixteen event slots of rm_cnt_s are all taken and the first group's eight
+// words are too, so the array grew by a group; the block behind it is the wave-time block, unused in this build.
+__shared__ unsigned int rm_cnt_e[16];
 #define RM_CNT_END(i)                                                                              \
     {                                                                                              \
         const unsigned int n_ = static_cast<unsigned int>(__popcll(__ballot(1)));                  \
@@ -360,7 +364,7 @@ __device__ double bvh_distance_wave_seq(const RmRenderParams &P, const SceneView
 struct BestScan {
     int k1;
     float hi1, lb1, lb2;
-    uint32_t kbest, ksecond;  // UR: order keys (see scan_sphere)
+    RmScanKeys keys;  // UR: the three smallest order keys (see scan_sphere; rm_kernels.h)
 };
 // UR (every sphere of the scene has the same radius): distance order = order of the squared centre distances, so
 // the scan ranks by s2 = |p - c|^2 (hi1 holds the smallest, lb2 the smallest of the others) and the square root,
@@ -368,7 +372,8 @@ struct BestScan {
 // UR keys: s2 >= 0, so its bit pattern orders like the value; the low eight mantissa bits give way to the sphere id (UR
 // kernels run scenes of at most 256 spheres), which makes "smallest and its id, and the smallest of the others" three
 // integer min / max instructions with no compare and no select:  lo = min(best, key), hi = max(best, key), second =
-// min(second, hi).  Clearing mantissa bits only lowers a key, so the runner-up's bound stays a lower bound; two spheres
+// min(second, hi) -- and, since round 12, two more for the third smallest key (rm_kernels.h rm_scan_keys_update), whose bound
+// covers every candidate behind the runner-up.  Clearing mantissa bits only lowers a key, so the runner-up's bound stays a lower bound; two spheres
 // closer than 2^-15 (relative, in s2) may be ranked the wrong way round, which the near-tie test after the exact
 // evaluation catches like any other near tie (the wrongly ranked one's lower bound cannot exceed the exact value).
 template <bool UR>
@@ -376,10 +381,7 @@ __device__ __forceinline__ void scan_sphere(BestScan &b, const RmSphere &s, int 
     if (UR) {
         const float dx = p.x - s.cx, dy = p.y - s.cy, dz = p.z - s.cz;
         const float s2 = dx * dx + dy * dy + dz * dz;
-        const uint32_t key = (__float_as_uint(s2) & 0xFFFFFF00u) | static_cast<uint32_t>(id);
-        const uint32_t lo = min(key, b.kbest), hi = max(key, b.kbest);
-        b.kbest = lo;
-        b.ksecond = min(hi, b.ksecond);
+        rm_scan_keys_update(b.keys, rm_scan_key(__float_as_uint(s2), static_cast<uint32_t>(id)));
         return;
     }
     float err;
@@ -408,8 +410,16 @@ __device__ __forceinline__ void scan_finish_uniform(BestScan &b, float rf) {
 // What the fused normal evaluation (render_kernel_v2, section N) needs to know about the evaluation at the hit point:
 // which sphere gave the value, how far every other candidate is at least (binary32 lower bound), how many primitives
 // were counted, and whether the set of leaves that contain the point is the same for every point within NRM_DELTA of it.
+// Runner-up rule (option `runner_up`): lb3, the lower bound at q of every candidate other than k1 and k2 (+inf: there is none),
+// travels from section B to section M in the upper half of NormalAux::k1 -- the kernels hold 80 VGPRs with none to spare, and a
+// word of its own spilled two 64-bit values of the one-radius instantiations.  The upper half of a binary32 number is that
+// number with its mantissa cut to seven bits: cutting moves a value towards zero by less than 2^-7 of its magnitude, so the
+// value is first lowered by 2^-6 of its magnitude and what is unpacked is at most lb3 (+inf stays +inf, a NaN a NaN).  The
+// bound of the third-nearest sphere is far above the distances it is compared with; 1.6 % of it decides next to no step.
+// (rm_kernels.h rm_runner_up_pack_bound / rm_runner_up_unpack_bound: one text for the kernel and for rm_debug_scan_keys, which tests it)
 struct NormalAux {
-    int k1;
+    int k1;          // with the runner-up rule (CellTabView::ru) the low byte; the runner-up's id k2 in the byte above it (k1 again where there is
+                     // none), and lb3 in the upper half (rm_runner_up_pack_bound)
     float lb2;
     uint32_t found;  // low half: primitives counted (all its users add it to the upper, wrapping half of `counters`); high half: how many of the
                      // cell's listed leaves contain q (at most 254), or 0xFFFF when the leaves did not come from the cell's list (tree walk);
@@ -443,6 +453,7 @@ struct CellTabView {
     const uint32_t *tab;   // the cell table
     const uint32_t *step;  // the step-box thresholds its indices refer to
     bool on;               // wave-uniform
+    bool ru;               // option `runner_up` in a one-radius launch that took the table (wave-uniform): section M wants k2 and lb3
 };
 // index of the threshold cell of x on axis k: the look-up byte of x's bin and the walk up (see section M), kept inside the axis
 __device__ __forceinline__ int cell_axis_index(const RmRenderParams &P, const uint32_t *step, int k, float x) {
@@ -473,7 +484,7 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
     BestScan bs;
     bs.k1 = -1;
     bs.hi1 = bs.lb1 = bs.lb2 = __builtin_inff();
-    bs.kbest = bs.ksecond = 0xFFFFFFFFu;
+    bs.keys.best = bs.keys.second = bs.keys.third = 0xFFFFFFFFu;
     auto scan_leaf = [&](const RmBvhNode &node) {
         const int first = node.leaf >> 8, cnt = node.leaf & 0xFF;
         for (int k = 0; k < cnt; ++k) {
@@ -621,20 +632,26 @@ __device__ double bvh_distance_wave(const RmRenderParams &P, const SceneView &S,
     }
     // the one exact evaluation of this call
     bool redo = false;
-    if (UR && bs.kbest != 0xFFFFFFFFu) {  // decode the keys: best id, and the runner-up's squared distance (rounded down)
-        bs.k1 = static_cast<int>(bs.kbest & 0xFFu);
-        bs.lb2 = bs.ksecond == 0xFFFFFFFFu ? __builtin_inff() : __uint_as_float(bs.ksecond & 0xFFFFFF00u);
+    if (UR && bs.keys.best != 0xFFFFFFFFu) {  // decode the keys: best id, and the runner-up's squared distance (rounded down)
+        bs.k1 = static_cast<int>(bs.keys.best & 0xFFu);
+        bs.lb2 = bs.keys.second == 0xFFFFFFFFu ? __builtin_inff() : __uint_as_float(bs.keys.second & 0xFFFFFF00u);
     }
+    float lb3 = __builtin_inff();
     if (bs.k1 >= 0) {
         RM_CNT(10)
         const RmSphere s1 = S.spheres[bs.k1];
         if (UR) scan_finish_uniform(bs, s1.rf);
+        if (UR && CT.ru) lb3 = rm_scan_key_bound(bs.keys.third, s1.rf);  // the third key bounds every sphere behind the runner-up
         closest = sphere_sdf_fast(s1, S.radii[bs.k1], q);
         if (closest > RM_MAX_DIST) closest = RM_MAX_DIST;  // Math.min(sdf, closestDistance = 10)
         redo = bs.lb2 <= f32_upper_bound(closest);
     }
     {   // the value came from sphere k1 alone, every other candidate of the leaf set (the same within rho) is at least lb2 away
         aux->k1 = bs.k1;
+        if (UR && CT.ru) {  // (one-radius kernels run at most 256 spheres; without a runner-up lb2 is +inf and section M never asks for k2)
+            const uint32_t k2 = bs.keys.second == 0xFFFFFFFFu ? bs.keys.best : bs.keys.second;
+            aux->k1 = static_cast<int>((bs.keys.best & 0xFFu) | ((k2 & 0xFFu) << 8) | rm_runner_up_pack_bound(lb3));
+        }
         aux->lb2 = bs.lb2;
         aux->found = (found & 0xFFFFu) | nleaf16;
         aux->rho = rho;
@@ -1238,7 +1255,7 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
 #endif
 #ifdef RM_COUNTS
     if (threadIdx.x < 32) rm_cnt_s[threadIdx.x] = 0;
-    if (threadIdx.x < 8) rm_cnt_e[threadIdx.x] = 0;
+    if (threadIdx.x < 16) rm_cnt_e[threadIdx.x] = 0;
     __syncthreads();
 #endif
     for (;;) {
@@ -1516,11 +1533,15 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
         aux.rho_cell = 0.f;
         // option `cell_tab` (wave-uniform): the candidates from the cell table, with the thresholds its indices name
         const bool cell_on = ACCEL == 2 && CB.cell_on != 0;
+        // option `runner_up` (wave-uniform; one-radius launches that took the cell table): section B hands section M the runner-up's
+        // id and the bound of the candidates behind it; aux.k1 then carries two ids
+        const bool ru = UR && cell_on && CB.runner_up != 0;
         if (ACCEL == 2) {
             CellTabView CT;  // (the pointers are formed whether or not the table is there: their address space is then a compile-time fact)
             CT.tab = LDS ? reinterpret_cast<const uint32_t *>(smem + CB.lds_off[11]) : CB.cell_tab;
             CT.step = LDS ? reinterpret_cast<const uint32_t *>(smem + CB.lds_off[10]) : CB.step_tab;
             CT.on = cell_on;
+            CT.ru = ru;
 #ifdef RM_STAMPS
             unsigned long long fbc = 0;
             dist = bvh_distance_wave<UR>(CB, SB, need, q, evaluated, lane_b, coop, filter, use_grid, &fbc, &aux, CT);
@@ -1593,8 +1614,9 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                 if (go) {
                     const RmRenderParams CM = cold_params();
                     const SceneView SM = scene_view<ACCEL, LDS, REL>(CM, smem);
-                    const RmSphere s1 = SM.spheres[aux.k1];
-                    const double r1 = SM.radii[aux.k1];
+                    const int k1 = ru ? aux.k1 & 0xFF : aux.k1;
+                    const RmSphere s1 = SM.spheres[k1];
+                    const double r1 = SM.radii[k1];
                     // Option `step_box` (round 9): the leaf-set test of a trip as six compares against a box found once per run.
                     // box_margin(lo, hi, p) >= 0 holds exactly when lo[k] <= p[k] <= hi[k] on the three axes (the sign of a
                     // binary32 difference is exact; denormals are kept), so which leaves contain a point, and whether the root
@@ -1698,9 +1720,28 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
                         const float ex = p2.x - q.x, ey = p2.y - q.y, ez = p2.z - q.z;
                         const float dd = __builtin_amdgcn_sqrtf(ex * ex + ey * ey + ez * ez) * 1.00001f + 1e-7f;  // >= |p2 - q|
                         const double e = sphere_sdf_fast(s1, r1, p2);
-                        if (!(aux.lb2 - dd > f32_upper_bound(e))) {
-                            RM_CNT_END(3)
-                            break;
+                        const float e_up = f32_upper_bound(e);
+                        if (!(aux.lb2 - dd > e_up)) {
+                            // Option `runner_up` (round 12).  lb2 - dd bounds every other candidate by the NEAREST of them and
+                            // lets that bound decay by the whole step whichever way the ray moves.  The nearest of them is one
+                            // known sphere, k2: its own distance at p2, as a conservative binary32 lower bound (the estimate
+                            // less its error term, rm_device.h), replaces the decayed bound, and only the candidates behind it
+                            // -- at least lb3 away at q, the third key's bound, and 1-Lipschitz -- keep the decay.  The
+                            // candidates at p2 are the round's (p2 is in the run's box), every one of them other than k1 is
+                            // then farther than e_up >= e, and Math.min over them is e with the same `found`: the step the
+                            // ordinary path would take.  No take-over: when k2 is the nearer one the run ends as before.
+                            bool farther = false;
+                            if (ru) {
+                                float err2;
+                                const float a2 = sphere_sdf_estimate(SM.spheres[(aux.k1 >> 8) & 0xFF], p2, err2);
+                                farther = __builtin_fminf(a2 - err2, rm_runner_up_unpack_bound(static_cast<uint32_t>(aux.k1)) - dd) > e_up;
+                            }
+                            if (!farther) {
+                                RM_CNT_END(3)
+                                if (ru) RM_CNT_END(9)
+                                break;
+                            }
+                            RM_CNT_END(8)
                         }
                         RM_CNT(15)
                         st += 1 << ST_TRIP_SHIFT;
@@ -1742,8 +1783,9 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
             }
             if (fuse && stable) {
                 const SceneView SN = scene_view<ACCEL, LDS, REL>(cold_params(), smem);
-                const RmSphere s1 = SN.spheres[aux.k1];
-                const double r1 = SN.radii[aux.k1];
+                const int k1 = ru ? aux.k1 & 0xFF : aux.k1;
+                const RmSphere s1 = SN.spheres[k1];
+                const double r1 = SN.radii[k1];
                 Vec3f qx = q, qy = q, qz = q;
                 qx.x = to_f32(static_cast<double>(q.x) - 0.01);
                 qy.y = to_f32(static_cast<double>(q.y) - 0.01);
@@ -1785,7 +1827,7 @@ __device__ __forceinline__ void render_v2_body(const RmRenderParams &P) {
 #ifdef RM_COUNTS
     __syncthreads();
     if (threadIdx.x < 32 && P.stamps) atomicAdd(&P.stamps[8 + threadIdx.x], static_cast<unsigned long long>(rm_cnt_s[threadIdx.x]));
-    if (threadIdx.x < 8 && P.stamps) atomicAdd(&P.stamps[40 + threadIdx.x], static_cast<unsigned long long>(rm_cnt_e[threadIdx.x]));
+    if (threadIdx.x < 16 && P.stamps) atomicAdd(&P.stamps[40 + threadIdx.x], static_cast<unsigned long long>(rm_cnt_e[threadIdx.x]));
 #endif
 }
 
@@ -1813,7 +1855,7 @@ __global__ __launch_bounds__(256) void wave_distance_kernel(const RmRenderParams
     const SceneView S = scene_view<2, false, false>(P, nullptr);
     uint32_t c = 0;
     NormalAux aux;
-    const CellTabView CT = {P.cell_tab, P.step_tab, P.cell_on != 0};  // (option `cell_tab`: the same switch as the wave loop's, the tables in global memory)
+    const CellTabView CT = {P.cell_tab, P.step_tab, P.cell_on != 0, false};  // (option `cell_tab`: the same switch as the wave loop's, the tables in global memory)
     const double d = bvh_distance_wave<UR>(P, S, need, q, c, static_cast<int>(threadIdx.x & 63), P.coop != 0, P.filter != 0, P.use_grid != 0, nullptr, &aux, CT);
     if (need) {
         dist[i] = d;
@@ -1868,6 +1910,7 @@ RmV2Plan rm_v2_plan(const RmRenderParams &p_in) {
         r.step_box = c.step_box;
         r.cell_on = c.cell_on;
         r.cell_refused = 0;
+        r.runner_up = c.cell_on && c.runner_up != 0 && c.uniform_radius != 0 ? 1 : 0;  // (a launch with the cell table stages its scene: the one-radius instantiation)
         r.list_cap = c.list_cap;
         r.list_bytes = c.accel == 2 ? static_cast<size_t>(4) * c.list_cap * 128 : 0;
         r.scene_bytes = scene_lds_bytes(c);
@@ -2048,6 +2091,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
     p.list_cap = plan.list_cap;
     p.step_box = plan.step_box;
     p.cell_on = plan.cell_on;
+    p.runner_up = plan.runner_up;
     // the leaf rectangles need the cull they serve, a slot for the table and a leaf count the slot holds
     if (p.accel != 2 || !p.leaf_rects || !p.bvh_leaves || p.bvh_leaf_count <= 0 || p.bvh_leaf_count > RM_RECT_CULL_MAX_LEAVES ||
         p.width > 65536 || p.height > 65536)
@@ -2082,6 +2126,7 @@ hipError_t RM_LEN_VARIANT(rm_launch_render_v2)(const RmRenderParams &p_in, hipSt
         shape[3] = p.step_box ? 1u : 0u;
         shape[4] = p.rect_cull ? 1u : 0u;
         shape[5] = p.cell_on ? 1u : 0u;
+        shape[6] = p.runner_up ? 1u : 0u;
     }
     // the tile-queue heads are zero: a launch's last wave leaves them so (rm_diag.h).  Without an accumulator block
     // (a caller below the API layer) they are cleared here.

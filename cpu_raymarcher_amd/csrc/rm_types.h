@@ -290,4 +290,8 @@ struct RmRenderParams {
     int32_t ct_dim[3];
     int32_t ct_rec_off, ct_list_off, ct_words;
     int32_t cell_on;
+    // v2 BVH, section M: the runner-up sphere is bounded by its own distance at the new point and only the candidates behind it
+    // by the round's bound less the distance travelled.  What fill_params asks for (option `runner_up`) and, from the launcher
+    // on, what the launch does: a one-radius launch that took the cell table (rm_v2_plan grants it); 0: every other candidate by lb2 - dd.
+    int32_t runner_up;
 };

@@ -15,7 +15,7 @@
     X(refill_threshold) X(hw_xcd) X(item_px) X(rel_boxes) X(lpt_stride) X(prim_filter) X(n0_batch) X(use_nn) X(tile_w_log2)     \
     X(tile_h_log2) X(tiles_x) X(item_wide) X(item_w_log2) X(sub_dx) X(sub_dy) X(tiles_x_magic) X(leaf_order) X(algorithm)       \
     X(general) X(uniform_radius) X(multi_step) X(use_ext) X(step_box) X(sb_bins) X(sb_stride) X(rect_cull) \
-    X(ct_rec_off) X(ct_list_off) X(ct_words) X(cell_on)
+    X(ct_rec_off) X(ct_list_off) X(ct_words) X(cell_on) X(runner_up)
 
 // The scene's counts.  As literals they are loop bounds too: worth another 2 - 3 % on the 125-sphere grid, but on a nine-sphere
 // scene the optimiser unrolls the node and leaf loops completely and the instantiation that held 80 VGPRs spills 53 -- such a

@@ -1436,6 +1436,19 @@ RM_API int rm_debug_step_box(rm_ctx *ctx, int32_t out[6]);
  * size in bytes (0: none); out[6]: the workgroups of that launch a CU holds; out[7], out[8]: the bytes of scene tables the
  * launch stages in LDS, and would with cell_tab 0; out[9..11]: the table's cells, records and distinct leaf sets. */
 RM_API int rm_debug_cell_tab(rm_ctx *ctx, int32_t out[12]);
+/* Option runner_up (below), for tests and evidence; works on a host-only context except for out[0].  out[0]: whether the last
+ * launch of the v2 wave loop bounded the runner-up sphere of an in-round march step by its own distance (0 before the first such
+ * launch); out[1]: whether a launch of the active scene would, with the options as they stand; out[2]: why not (0: it would;
+ * 1: option runner_up is 0; 2: the launch does not take the cell table -- rm_debug_cell_tab says why; 3: the scene's spheres do
+ * not share one radius, or option uniform is 0); out[3]: 0. */
+RM_API int rm_debug_runner_up(rm_ctx *ctx, int32_t out[4]);
+/* The key update of the one-radius scan, the text the wave loop runs, over a caller's n keys (a squared distance's bit pattern,
+ * the sphere id in its low byte); needs no context and no device.  out3: the three smallest keys in order, equal keys counted as
+ * often as they came, 0xFFFFFFFF where there are fewer; *lb3: the lower bound the third key gives the spheres behind the
+ * runner-up for radius rf, +infinity exactly when fewer than three keys came; *lb3_carried: that bound as the in-round march steps
+ * read it, cut to the upper half of a word on its way (never above *lb3, at least 0.97 of a positive one).  keys may be null when
+ * n is 0. */
+RM_API int rm_debug_scan_keys(const uint32_t *keys, int64_t n, float rf, uint32_t out3[3], float *lb3, float *lb3_carried);
 /* Option exact (below), for tests and evidence; works on a host-only context.  What the next exact query of the active scene
  * walks -- out[0]: 0 every object, 1 the scene's BVH, 2 an exact tree of its own -- and that tree's nodes (out[1]), leaves
  * (out[2]) and depth (out[3]); zeros in mode 0.  It builds the exact tree if it is due (and, with a device, copies it up),
@@ -1500,6 +1513,12 @@ RM_API int rm_debug_read_batch_log(rm_ctx *ctx, uint32_t *out196608);
  *                 instead of from box tests against the leaf grid's lists; the launch then stages the table in the leaf
  *                 grid's place (default 1; 0, a scene without the table, or a launch it does not fit: as before; same bytes
  *                 either way; rm_debug_cell_tab)
+ *   runner_up 0|1 v2 BVH, those steps, in a launch that took the cell table of a scene whose spheres share one radius: a step
+ *                 that the bound of all other candidates (the runner-up's bound at the round's point less the distance
+ *                 travelled) does not admit is admitted when the runner-up sphere's own distance at the new point, and the
+ *                 third-nearest candidate's bound less the distance travelled, both exceed the winner's exact distance; fewer
+ *                 runs end, fewer rounds begin (default 1; 0, or any other launch: the one bound; same bytes either way;
+ *                 rm_debug_runner_up)
  *   lds_fill 0|1  v2: pad the LDS request so that exactly blocks_per_cu workgroups fit a CU (default 0; measurement knob)
  *   min_fill 0|1  v2: a persistent launch brings max(blocks_per_cu, ceil(6 / Q)) workgroups per CU, Q = GPU_MAX_HW_QUEUES as
  *                 rm_create found it (unset or not a positive integer: 4, HIP's default; never set by the library).  Launches

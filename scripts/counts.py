@@ -42,6 +42,11 @@ for i, n in enumerate(names):
     print("%-32s %12d %14d %5.1f%% %10.2f" % (n, w, l, 100.0 * l / (64.0 * w) if w else 0.0, l / float(W * H)))
 # why an in-round run of march steps ends (RM_CNT_END of rm_render_v2.hip: the first eight words of the wave-time block)
 N.lib().rm_debug_read_wave_times(ctx._h, ends.ctypes.data_as(C.c_void_p))
-for i, n in enumerate(["M run ends: leaf set changed", "M run ends: root box / crowded", "M run ends: BVH interval", "M run ends: runner-up"]):
+# ... and, in a second group of the same shape, option `runner_up`: trips that the runner-up's own distance accepted where the
+# one bound would have ended the run, and runs that end for the runner-up although that test was made (zeros in a build from
+# before round 12, which writes no second group)
+for i, n in [(0, "M run ends: leaf set changed"), (1, "M run ends: root box / crowded"), (2, "M run ends: BVH interval"), (3, "M run ends: runner-up"),
+             (8, "M trip kept by runner-up rule"), (9, "M run ends: runner-up, rule on")]:
     w, l = int(ends[i]), int(ends[i + 4])
     print("%-32s %12d %14d %5.1f%% %10.2f" % (n, w, l, 100.0 * l / (64.0 * w) if w else 0.0, l / float(W * H)))
+print("runner_up:", ctx.runner_up() if hasattr(N.lib(), "rm_debug_runner_up") else "(a build without the option)")

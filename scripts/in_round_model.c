@@ -12,7 +12,13 @@
  * trips in its r-th round the maximum over its lanes' r-th rounds.  Every sixth batch in both directions over the whole
  * frame: 3 600 batches.  Refill, the deferred normals (0.30 rounds per pixel) and the binary32 lower bound of the
  * runner-up (the exact runner-up is used) are not modelled.  "today" is the rule before round 8 (a ball around the
- * round's point); its three figures are to be held against scripts/counts.py on a -DRM_COUNTS build. */
+ * round's point); its three figures are to be held against scripts/counts.py on a -DRM_COUNTS build.
+ *
+ * Round 12, test (3): the last two rows bound the runner-up by its own (exact) distance at the new point and everything behind it
+ * by the third-nearest distance less dd (option `runner_up`), and then let the run follow the runner-up when it becomes the nearer
+ * one (the take-over: 0.14 fewer wave rounds per batch for 7.5 lane events that each need a second exact evaluation by the whole
+ * wave -- not built).  Every accepted step's value is asserted to be the oracle's distance.  The play is per lane, as above: a
+ * lockstep play of the wave (trips in which no lane commits) is not modelled. */
 #include <stdio.h>
 
 #include "../oracle/rm_oracle.c"
@@ -23,10 +29,10 @@
 #define MAXSTEP 100
 
 typedef struct {
-    double t, d, second, enter, exit_;
+    double t, d, second, third, enter, exit_; /* second, third: the exact distances of the runner-up and of the nearest candidate behind it */
     float p[3];
     unsigned long long set; /* leaves whose box contains p */
-    int k1;
+    int k1, k2;
 } Step;
 
 static BBox leaf_box[MAXL];
@@ -101,22 +107,24 @@ static int trace(const ro_scene *s, const float *o, const float *dir, Scratch *s
         e->enter = sc->intervals[as.curIdx].tEnter;
         e->exit_ = sc->intervals[as.curIdx].tExit;
         e->set = 0;
-        e->k1 = -1;
-        double best = 1e300, second = 1e300;
+        e->k1 = e->k2 = -1;
+        double best = 1e300, second = 1e300, third = 1e300;
         for (int l = 0; l < n_leaf; l++)
             if (margin(&leaf_box[l], p) >= 0.f) {
                 e->set |= 1ull << l;
                 for (int j = 0; j < leaf_node[l]->nprims; j++) {
                     int id = leaf_node[l]->prims[j];
                     double v = prim_sdf(&s->prims[id], p);
-                    if (v < best) { second = best; best = v; e->k1 = id; }
-                    else if (v < second) second = v;
+                    if (v < best) { third = second; second = best; e->k2 = e->k1; best = v; e->k1 = id; }
+                    else if (v < second) { third = second; second = v; e->k2 = id; }
+                    else if (v < third) third = v;
                 }
             }
         uint32_t cnt = 0;
         double dist = scene_get_distance(s, p, &cnt, sc);
         e->d = dist;
         e->second = second;
+        e->third = third;
         total += dist;
         if (dist < EPSILON) break;
         if (total > MAX_DIST) break;
@@ -272,12 +280,16 @@ typedef struct {
                      * 4: the merged box of q's threshold cell */
     double grow;    /* ball: how far the cell lists are grown */
     double confine; /* exact: p2 stays within q's cell grown by this; < 0: anywhere in the root box */
+    int runner;     /* test (3), round 12 -- 0: every other candidate by second - dd; 1: the runner-up by its own distance at p2, the rest by
+                     * third - dd (option `runner_up`); 2: ... and the run follows the runner-up when it becomes the nearer one (not built) */
 } Rule;
 
 enum { END_SET, END_CELL, END_INTERVAL, END_RUNNER, N_END };
 
-/* may step j be taken in the round whose point is step h?  returns -1, or the reason it may not */
-static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e) {
+static long takeovers, kept_by_runner;
+/* may step j be taken in the round whose point is step h?  returns -1, or the reason it may not.  *win: the sphere the run follows
+ * (h->k1 at its start; rule 2 may change it) */
+static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e, int *win) {
     if (e->t < h->enter || e->t > h->exit_) return END_INTERVAL;
     float ex = e->p[0] - h->p[0], ey = e->p[1] - h->p[1], ez = e->p[2] - h->p[2];
     float dd = sqrtf(ex * ex + ey * ey + ez * ez) * 1.00001f + 1e-7f;
@@ -311,8 +323,22 @@ static int refuse(const ro_scene *s, const Rule *r, const Step *h, const Step *e
             }
         if (margin(&root_box, e->p) < 0.f || e->set != h->set) return END_SET;
     }
-    double v = prim_sdf(&s->prims[h->k1], e->p);
-    if (!((float)h->second - dd > (float)(v * (1 + 1e-6)))) return END_RUNNER;
+    double v = prim_sdf(&s->prims[*win], e->p);
+    if (!((float)h->second - dd > (float)(v * (1 + 1e-6)))) {
+        if (!r->runner || h->k2 < 0) return END_RUNNER;
+        /* the other of the round's two nearest spheres by its own distance, everything behind them by third - dd */
+        int other = *win == h->k1 ? h->k2 : h->k1;
+        double w = prim_sdf(&s->prims[other], e->p);
+        float rest = (float)h->third - dd;
+        if ((float)(w * (1 - 1e-6)) > (float)(v * (1 + 1e-6)) && rest > (float)(v * (1 + 1e-6))) kept_by_runner += r->runner == 1;
+        else if (r->runner == 2 && (float)(v * (1 - 1e-6)) > (float)(w * (1 + 1e-6)) && rest > (float)(w * (1 + 1e-6))) {
+            *win = other; /* a second exact evaluation, by the whole wave, for this lane */
+            v = w;
+            takeovers += 1;
+        } else return END_RUNNER;
+    }
+    /* the claim of test (3), on every accepted step: the value is the oracle's distance */
+    if ((v < MAX_DIST ? v : MAX_DIST) != e->d) { fprintf(stderr, "rule '%s' accepted a step whose value is not the oracle's\n", r->name); exit(3); }
     return -1;
 }
 
@@ -341,6 +367,8 @@ int main(void) {
         {"half-open threshold cells (round 9)", 2, 0, 0},
         {"open threshold cells", 3, 0, 0},
         {"merged threshold-cell boxes (round 11)", 4, 0, 0},
+        {"... runner-up by its own distance (r12)", 4, 0, 0, 1},
+        {"... and the run follows a take-over", 4, 0, 0, 2},
     };
     enum { NR = sizeof rules / sizeof rules[0] };
     double lane_rounds[NR] = {0}, lane_steps[NR] = {0}, wave_rounds[NR] = {0}, wave_trips[NR] = {0}, ends[NR][N_END] = {{0}};
@@ -370,7 +398,7 @@ int main(void) {
                 int n = trace(s, org, dir, &sc, st);
                 pixels++;
                 for (int r = 0; r < NR; r++) {
-                    int nr = 0, h = 0;
+                    int nr = 0, h = 0, win = -1;
                     for (int j = 0; j < n; j++) {
                         int in_round = 0;
                         if (j > 0) {
@@ -378,7 +406,7 @@ int main(void) {
                             /* aux.ok: leaves found, a winner, and no near tie with the runner-up */
                             int ok = q->set != 0 && q->k1 >= 0 && (float)q->second > (float)(q->d * (1 + 1e-6));
                             if (ok) {
-                                int why = refuse(s, &rules[r], q, &st[j]);
+                                int why = refuse(s, &rules[r], q, &st[j], &win);
                                 if (why < 0) in_round = 1;
                                 else ends[r][why] += 1;
                             }
@@ -388,6 +416,7 @@ int main(void) {
                             lane_steps[r] += 1;
                         } else {
                             h = j;
+                            win = st[j].k1;
                             trips[r][l][nr++] = 0;
                             lane_rounds[r] += 1;
                         }
@@ -414,6 +443,8 @@ int main(void) {
         printf("%-38s %12.2f %12.2f %12.2f %12.2f   %.2f / %.2f / %.2f / %.2f\n", rules[r].name, lane_rounds[r] / pixels, lane_steps[r] / pixels,
                wave_rounds[r] / batches, wave_trips[r] / batches, ends[r][END_SET] / pixels, ends[r][END_CELL] / pixels,
                ends[r][END_INTERVAL] / pixels, ends[r][END_RUNNER] / pixels);
+    printf("runner-up by its own distance: %.2f lane steps per batch kept that second - dd refuses; take-over: %.2f lane take-overs per batch\n",
+           (double)kept_by_runner / batches, (double)takeovers / batches);
     ro_scene_free(s);
     return 0;
 }
