@@ -10,8 +10,8 @@ from ._native import STEP_DTYPE, WALK_DTYPE, WALK_ENDS  # the records Context.wa
 
 _native.lib()  # raise now, not at first render, when the HIP library is missing
 
-from .context import (Context, Measure, MeasureWorld, MeshSession, camera_from_angles, camera_rays, make_lattice, make_transform,  # noqa: E402
-                      measure_world, Parts, partition_rows, percentile, phong_light, scale_transform, slice_lattice, sweep_views)
+from .context import (Context, Edt, Measure, MeasureWorld, MeshSession, camera_from_angles, camera_rays, lattice_cubic, make_lattice,  # noqa: E402
+                      make_transform, measure_world, Parts, partition_rows, percentile, phong_light, scale_transform, slice_lattice, sweep_views)
 from .host import (ALGORITHMS, SHADERS, AdaptiveStep, AdaptiveStepV2, AdaptiveStepV3, Camera, FixedStep,  # noqa: E402
                    IterationHeatmap, Job, NormalModel, PhongModel, RangedIterationHeatmap, RangedSDFHeatmap, Raymarcher,
                    RaymarchWorker, Result, Scene,

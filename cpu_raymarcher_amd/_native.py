@@ -131,6 +131,13 @@ class rm_parts_info(C.Structure):  # include/rm_raymarch.h: struct rm_parts_info
 RM_PARTS_INSIDE, RM_PARTS_OUTSIDE = 0, 1
 
 
+class rm_edt_info(C.Structure):  # include/rm_raymarch.h: struct rm_edt_info
+    _fields_ = [("n_points", C.c_int64), ("n_set", C.c_int64), ("max_d2", C.c_int64), ("argmax", C.c_int64)]
+
+
+RM_EDT_FAR = 2 ** 31 - 1
+
+
 class rm_view(C.Structure):  # include/rm_raymarch.h: struct rm_view
     _fields_ = [("camera_pitch", C.c_double), ("camera_yaw", C.c_double), ("time", C.c_double)]
 
@@ -270,6 +277,9 @@ SIGNATURES = {
     "rm_label_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, C.c_int32, _VP, _VP, _VP]),
     "rm_measure_labels_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int64, _VP, _VP]),
     "rm_scene_parts": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_int32, _VP, C.c_int64, _VP, C.POINTER(rm_parts_info)]),
+    "rm_edt_field_device": (C.c_int, [_VP, C.POINTER(rm_lattice), _VP, C.c_int32, C.c_double, C.c_int32, _VP, _VP, _VP]),
+    "rm_scene_edt": (C.c_int, [_VP, C.POINTER(rm_lattice), C.c_double, C.c_int32, _VP, C.POINTER(rm_edt_info)]),
+    "rm_lattice_cubic": (C.c_int, [C.POINTER(rm_lattice), C.POINTER(C.c_double)]),
     "rm_ray_march": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_ray_march_device": (C.c_int, [_VP, C.POINTER(rm_ray_query), C.c_int64, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "rm_camera_rays": (C.c_int, [C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, C.c_int32, _VP, _VP]),

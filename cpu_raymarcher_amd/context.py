@@ -68,6 +68,69 @@ class Parts:
         return np.where(drop, (2 * self.iso - v).astype(v.dtype, copy=False), v)
 
 
+class Edt:
+    """What Context.edt_field, Context.edt and Scene.edt return (include/rm_raymarch.h, "distances"): `d2` int32 [nw, nv, nu]
+    -- a numpy array, or a CUDA tensor with device=True --, the squared index distance of every point of the set to the
+    nearest lattice point that is not in it, 0 outside the set, RM_EDT_FAR everywhere when nothing is outside it; `n_points`,
+    `n_set`, `max_d2`, `argmax` (linear index, -1 for an empty set) and `at`, the same as (i, j, k) or None; `side` as it was
+    asked; `step`: what an index step is worth in the world where the lattice is cubic (rm_lattice_cubic), else None."""
+
+    def __init__(self, d2, n_points, n_set, max_d2, argmax, side="inside", step=None):
+        self.d2, self.n_points, self.n_set, self.max_d2, self.argmax = d2, int(n_points), int(n_set), int(max_d2), int(argmax)
+        self.side, self.step = side, (None if step is None else float(step))
+        nw, nv, nu = (int(x) for x in d2.shape)
+        self.at = None if self.argmax < 0 else (self.argmax % nu, self.argmax // nu % nv, self.argmax // (nu * nv))
+
+    def _cubic_step(self):
+        if self.step is None:
+            raise ValueError("the lattice is not cubic (rm_lattice_cubic): index distances are not world distances")
+        return self.step
+
+    def distance(self):
+        """sqrt(d2) * step in float64, in `d2`'s container; inf where d2 is RM_EDT_FAR.  Raises on a lattice that is not cubic."""
+        step = self._cubic_step()
+        if _is_torch(self.d2):
+            import torch
+            d = torch.sqrt(self.d2.to(torch.float64)) * step
+            return torch.where(self.d2 == N.RM_EDT_FAR, torch.full_like(d, float("inf")), d)
+        return np.where(self.d2 == N.RM_EDT_FAR, np.inf, np.sqrt(self.d2.astype(np.float64)) * step)
+
+    @property
+    def inradius(self):
+        """The radius of the largest ball about a lattice point of the set that holds no lattice point outside it: sqrt(max_d2) * step
+        (inf when nothing is outside the set)."""
+        step = self._cubic_step()
+        return float("inf") if self.max_d2 == N.RM_EDT_FAR else float(np.sqrt(np.float64(self.max_d2)) * step)
+
+    def eroded(self, r2):
+        """The set eroded by the squared index radius r2 as a volume of `d2`'s container and shape: -1.0 where the point is in
+        the set and d2 >= r2, +1.0 elsewhere (float64) -- ready for label_field, mesh_field, measure_field or edt_field at iso = 0."""
+        if _is_torch(self.d2):
+            import torch
+            keep = (self.d2 > 0) & (self.d2 >= int(r2))
+            return torch.where(keep, -1.0, 1.0).to(torch.float64)
+        return np.where((self.d2 > 0) & (self.d2 >= int(r2)), -1.0, 1.0)
+
+    def max_by_part(self, parts):
+        """The largest d2 of each part of `parts` (a Parts of the same lattice and set): int64 [n_parts], in the container of
+        `d2` -- torch scatter_reduce on the device, numpy on the host."""
+        labels = parts.labels
+        if _is_torch(self.d2):
+            import torch
+            lab = labels if _is_torch(labels) else torch.from_numpy(np.ascontiguousarray(labels))
+            lab = lab.to(self.d2.device).reshape(-1).to(torch.int64)
+            d = self.d2.reshape(-1).to(torch.int64)
+            sel = lab >= 0
+            out = torch.zeros(parts.n_parts, dtype=torch.int64, device=self.d2.device)
+            return out.scatter_reduce(0, lab[sel], d[sel], reduce="amax", include_self=True)
+        lab = (labels.cpu().numpy() if _is_torch(labels) else np.asarray(labels)).reshape(-1)
+        d = self.d2.reshape(-1).astype(np.int64)
+        out = np.zeros(parts.n_parts, np.int64)
+        sel = lab >= 0
+        np.maximum.at(out, lab[sel], d[sel])
+        return out
+
+
 def _is_torch(x):
     return type(x).__module__.startswith("torch")
 
@@ -1425,6 +1488,56 @@ class Context:
         origin, du, dv, dw, shape = self._box_lattice(cells, margin, iso, box)
         return self.parts(origin, du, dv, dw, shape, iso=iso, time=time, side=side, records=records, device=device, exact=exact)
 
+    # ---- distances: how far inside the solid every lattice point lies, exactly ------------------
+    def edt_field(self, values, origin, du, dv, dw, shape, iso=0.0, side="inside", device=False):
+        """The exact Euclidean distance transform of a volume the caller already holds (rm_edt_field_device; the rule is in
+        include/rm_raymarch.h, "distances") -> Edt.  `values` as `label_field` takes them.  side="inside": the set is
+        value < iso; "outside": its complement, NaN included.  `.d2` is the squared index distance to the nearest lattice
+        point on the other side -- points beyond the lattice do not exist, so leave a margin around a solid whose thickness is
+        asked.  device=True leaves `.d2` a CUDA tensor.  On torch's current stream; the info comes back in one read."""
+        if side not in ("inside", "outside"):
+            raise ValueError("side is 'inside' or 'outside'")
+        if self.device < 0:
+            raise N.RmError(N.RM_E_NO_DEVICE, "host-only context: there is no CPU distance transform")
+        import torch
+        lat = make_lattice(origin, du, dv, dw, shape)
+        n = lat.nu * lat.nv * lat.nw
+        values, vt = self._mesh_values(values, n)
+        dev = torch.device("cuda", self.device)
+        d2 = torch.empty((lat.nw, lat.nv, lat.nu), dtype=torch.int32, device=dev)
+        info = torch.empty(4, dtype=torch.int64, device=dev)
+        N.check(self._h, N.lib().rm_edt_field_device(self._h, C.byref(lat), _ptr(values) if n else None, vt, float(iso),
+                                                     N.RM_PARTS_OUTSIDE if side == "outside" else N.RM_PARTS_INSIDE, _ptr(d2) if n else None, _ptr(info),
+                                                     _current_stream_ptr()))
+        head = info.cpu().numpy()
+        return Edt(d2 if device else d2.cpu().numpy(), head[0], head[1], head[2], head[3], side, lattice_cubic(lat))
+
+    def edt(self, origin, du, dv, dw, shape, iso=0.0, time=0.0, side="inside", device=False, exact=True):
+        """The distance transform of the active scene's solid over a lattice -> Edt (`edt_field`): `field` samples the volume
+        on the device (float64, honouring `exact` as `field` does) and `edt_field` transforms it."""
+        vol, _ = self.field(origin, du, dv, dw, shape=shape, time=time, count=False, device=True, exact=exact)
+        return self.edt_field(vol, origin, du, dv, dw, shape, iso=iso, side=side, device=device)
+
+    def edt_box(self, cells=(64, 64, 64), margin=None, iso=0.0, time=0.0, box=None, side="inside", device=False, exact=True):
+        """`edt` over `mesh_box`'s lattice: cells[0] x cells[1] x cells[2] cells that cover scene_info()'s root box (or
+        `box` = (lo, hi)) and `margin` beyond it on every side -- the margin keeps the solid off the lattice's border, where the
+        transform would not see its surface.  The lattice is cubic (`.step`, `.distance()`, `.inradius`) when the cells are."""
+        origin, du, dv, dw, shape = self._box_lattice(cells, margin, iso, box)
+        return self.edt(origin, du, dv, dw, shape, iso=iso, time=time, side=side, device=device, exact=exact)
+
+    def open_field(self, values, origin, du, dv, dw, shape, r2, iso=0.0, device=False):
+        """The morphological opening of the solid value < iso by the squared index radius r2 -> a volume of -1.0 (in the
+        result) and +1.0, float64 [nw, nv, nu], a numpy array or a CUDA tensor with device=True.  Two transforms: the set is
+        eroded (`Edt.eroded(r2)`: d2 >= r2 stays), then dilated by the same radius -- a point is in the result iff it is in the
+        eroded set or its squared distance to the eroded set is below r2.  Crumbs and whiskers thinner than the radius go, the
+        rest does not move; the result is always a subset of the solid."""
+        import torch
+        first = self.edt_field(values, origin, du, dv, dw, shape, iso=iso, side="inside", device=True)
+        eroded = first.eroded(r2)
+        second = self.edt_field(eroded, origin, du, dv, dw, shape, iso=0.0, side="outside", device=True)
+        opened = torch.where((eroded < 0) | (second.d2 < int(r2)), -1.0, 1.0).to(torch.float64)
+        return opened if device else opened.cpu().numpy()
+
     def _box_lattice(self, cells, margin, iso, box):
         """The lattice `mesh_box` meshes over -> (origin, du, dv, dw, shape)."""
         if box is None:
@@ -1639,6 +1752,18 @@ def measure_world(lat, record):
     if rc != N.RM_OK:
         raise N.RmError(rc, "rm_measure_world")
     return MeasureWorld(out.cell_volume, out.volume, tuple(out.centroid), tuple(out.second), tuple(out.projected_area), out.area_estimate)
+
+
+def lattice_cubic(lat):
+    """rm_lattice_cubic of an rm_lattice: the length of its steps where they are equal and orthogonal to 1e-5 (axes of one
+    point aside), so that index distances are world distances up to this factor; else None."""
+    step = C.c_double(0.0)
+    rc = N.lib().rm_lattice_cubic(C.byref(lat), C.byref(step))
+    if rc == N.RM_E_UNSUPPORTED:
+        return None
+    if rc != N.RM_OK:
+        raise N.RmError(rc, "rm_lattice_cubic refused the lattice")
+    return step.value
 
 
 def measure_from_record(lat, record):

@@ -3774,6 +3774,134 @@ int rm_scene_parts(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t s
     return RM_OK;
 }
 
+// ---- distances: the exact Euclidean distance transform of one side of iso (rm_edt.hip)
+
+static_assert(sizeof(rm_edt_info) == 32 && sizeof(RmEdtInfo) == sizeof(rm_edt_info), "rm_edt_info layout");
+static_assert(RM_EDT_FAR == INT32_MAX, "rm_edt.hip marks an absent parabola with INT_MAX");
+
+namespace {
+
+// every finite squared index distance of the lattice is below RM_EDT_FAR
+bool edt_fits(const rm_lattice &l) {
+    int64_t sum = 0;
+    for (const int64_t count : {int64_t(l.nu), int64_t(l.nv), int64_t(l.nw)}) sum += count > 0 ? (count - 1) * (count - 1) : 0;
+    return sum <= int64_t(INT32_MAX) - 1;
+}
+const char *const kEdtRange = "(nu-1)^2 + (nv-1)^2 + (nw-1)^2 exceeds INT32_MAX - 1: a squared index distance would not fit 32 bits";
+const rm_edt_info kEdtEmpty = {0, 0, 0, -1};  // of a lattice without points
+
+// The transform's launch, n > 0: everything on the device; every field of the info is written by the last kernel.
+int launch_edt_field(rm_ctx *ctx, const rm_lattice *lat, int64_t n, const void *d_values, int32_t value_type, double iso, int32_t side, void *d_d2,
+                     void *d_stack, void *d_partials, void *d_info, hipStream_t stream) {
+    RmEdtArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.values = d_values;
+    a.iso = iso;
+    a.d2 = static_cast<int32_t *>(d_d2);
+    a.stack = static_cast<unsigned long long *>(d_stack);
+    a.partials = d_partials;
+    a.info = static_cast<RmEdtInfo *>(d_info);
+    a.n = n;
+    a.nu = static_cast<unsigned int>(lat->nu);
+    a.nv = static_cast<unsigned int>(lat->nv);
+    a.nw = static_cast<unsigned int>(lat->nw);
+    a.f32 = value_type == RM_MESH_F32;
+    a.outside = side == RM_PARTS_OUTSIDE;
+    RM_HIP(ctx, rm_launch_edt_field(a, stream, &ctx->last_kernel));
+    return RM_OK;
+}
+
+}  // namespace
+
+int rm_edt_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso, int32_t side, void *d_d2, void *d_info,
+                        void *stream) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = parts_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (n > 0 && !d_values) return fail(ctx, RM_E_INVALID, "null values");
+    if (const char *bad = parts_side_error(iso, side)) return fail(ctx, RM_E_INVALID, bad);
+    if (value_type != RM_MESH_F64 && value_type != RM_MESH_F32) return fail(ctx, RM_E_INVALID, "value_type must be RM_MESH_F64 or RM_MESH_F32");
+    if (misaligned(d_values, value_type == RM_MESH_F64 ? 7 : 3)) return fail(ctx, RM_E_INVALID, "values must be aligned to their type");
+    if (n > 0 && !d_d2) return fail(ctx, RM_E_INVALID, "null d2");
+    if (!d_info) return fail(ctx, RM_E_INVALID, "null info");
+    if (misaligned(d_d2, 3)) return fail(ctx, RM_E_INVALID, "d2 must be 4-byte aligned");
+    if (misaligned(d_info, 7)) return fail(ctx, RM_E_INVALID, "info must be 8-byte aligned");
+    if (!edt_fits(*lattice)) return fail(ctx, RM_E_UNSUPPORTED, kEdtRange);
+    if (const int rc = need_device(ctx, "distance transform", false)) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n == 0) {  // no point, no launch: the info of the empty lattice, which is not all zero
+        RM_HIP(ctx, hipSetDevice(ctx->device));
+        RM_HIP(ctx, hipMemsetAsync(d_info, 0, offsetof(rm_edt_info, argmax), s));
+        RM_HIP(ctx, hipMemsetAsync(static_cast<char *>(d_info) + offsetof(rm_edt_info, argmax), 0xFF, sizeof(int64_t), s));
+        return RM_OK;
+    }
+    // the lines' stacks, laid out as the volume, and the reduction's partials
+    return scratch_call(ctx, s, true, d_info, sizeof(rm_edt_info), {8 * static_cast<size_t>(n), RM_EDT_PARTIAL_BYTES}, [&](const Staging &st, const size_t *o) {
+        return launch_edt_field(ctx, lattice, n, d_values, value_type, iso, side, d_d2, st.at<void>(o[0]), st.at<void>(o[1]), d_info, s);
+    });
+}
+
+int rm_scene_edt(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t side, int32_t *d2_out, rm_edt_info *info_out) {
+    if (!ctx) return RM_E_INVALID;
+    int64_t n = 0;
+    if (const char *bad = parts_error(lattice, &n)) return fail(ctx, RM_E_INVALID, bad);
+    if (const char *bad = parts_side_error(iso, side)) return fail(ctx, RM_E_INVALID, bad);
+    if (!info_out) return fail(ctx, RM_E_INVALID, "null info");
+    if (!edt_fits(*lattice)) return fail(ctx, RM_E_UNSUPPORTED, kEdtRange);
+    int rc = need_device(ctx, "distance transform", true);
+    if (rc) return rc;
+    if (n == 0) {
+        *info_out = kEdtEmpty;
+        return RM_OK;
+    }
+    RM_HIP(ctx, hipSetDevice(ctx->device));
+    // The volume, the transform, its stacks and partials and the info side by side in the scratch buffer.
+    const size_t points = static_cast<size_t>(n);
+    Staging st{ctx};
+    const size_t o_vol = st.region(8 * points), o_d2 = st.region(4 * points), o_stack = st.region(8 * points), o_partials = st.region(RM_EDT_PARTIAL_BYTES),
+                 o_info = st.region(sizeof(rm_edt_info));
+    if ((rc = st.reserve())) return rc;
+    RmRenderParams p;
+    RmFieldArgs a;
+    fill_field(ctx, lattice, p, a);  // the field entries' own launch, at the lattice's time
+    if (const int erc = use_exact(ctx, p)) return erc;
+    a.dist = st.at<double>(o_vol);
+    a.first = 0;
+    a.n = n;
+    RM_HIP(ctx, (ctx->opt_length ? rm_launch_field_sqrt : rm_launch_field)(p, a, ctx->stream, &ctx->last_kernel));
+    if ((rc = launch_edt_field(ctx, lattice, n, st.at<void>(o_vol), RM_MESH_F64, iso, side, st.at<void>(o_d2), st.at<void>(o_stack), st.at<void>(o_partials),
+                               st.at<void>(o_info), ctx->stream)))
+        return rc;
+    if (d2_out) RM_HIP(ctx, st.out(d2_out, o_d2, 4 * points));
+    RM_HIP(ctx, st.out(info_out, o_info, sizeof *info_out));
+    RM_HIP(ctx, st.sync());
+    return RM_OK;
+}
+
+int rm_lattice_cubic(const rm_lattice *lattice, double *step) {
+    int64_t n = 0;
+    if (!step || lattice_error(lattice, &n)) return RM_E_INVALID;
+    // binary64 of the widened components, one operation at a time (-ffp-contract=off)
+    const float *const steps[3] = {lattice->du, lattice->dv, lattice->dw};
+    const int32_t counts[3] = {lattice->nu, lattice->nv, lattice->nw};
+    double v[3][3], first = 1.0;
+    int m = 0;  // the axes that take part: those with more than one point
+    for (int A = 0; A < 3; ++A) {
+        if (counts[A] <= 1) continue;
+        for (int c = 0; c < 3; ++c) v[m][c] = static_cast<double>(steps[A][c]);
+        ++m;
+    }
+    const auto dot = [&](int p, int q) { return (v[p][0] * v[q][0] + v[p][1] * v[q][1]) + v[p][2] * v[q][2]; };
+    if (m > 0) first = std::sqrt(dot(0, 0));
+    for (int p = 1; p < m; ++p)
+        if (!(std::fabs(std::sqrt(dot(p, p)) - first) <= 1e-5 * first)) return RM_E_UNSUPPORTED;
+    for (int p = 0; p < m; ++p)
+        for (int q = p + 1; q < m; ++q)
+            if (!(std::fabs(dot(p, q)) <= 1e-5 * (first * first))) return RM_E_UNSUPPORTED;
+    *step = first;
+    return RM_OK;
+}
+
 int rm_debug_wave_distance(rm_ctx *ctx, const float *points_xyz, int64_t n, double *dist, uint32_t *count) {
     RmRenderParams p;
     const auto supported = [&] {

@@ -447,6 +447,22 @@ struct RmPartsMeasureArgs {
     long long n;
     unsigned int nu, nv, nw, n_records;
 };
+// rm_edt_field_device (rm_edt.hip): the squared index distance of every point on one side of iso to the nearest point on the other.
+#define RM_EDT_PARTIAL_BYTES (16 * 1024)  // edt_reduce_kernel's partials: 1024 workgroups at most, 16 bytes each
+struct RmEdtInfo {  // rm_edt_info (32 bytes)
+    long long n_points, n_set, max_d2, argmax;
+};
+struct RmEdtArgs {
+    const void *values;         // n binary64 values, or binary32 ones with f32
+    double iso;
+    int32_t *d2;                // n words: the result, every pass in place
+    unsigned long long *stack;  // n entries: a line's envelope, entry q where the line's q-th point is in the volume
+    void *partials;             // RM_EDT_PARTIAL_BYTES
+    RmEdtInfo *info;
+    long long n;
+    unsigned int nu, nv, nw;
+    int f32, outside;
+};
 // The device scene builder (rm_scene_build.hip): the pair loops of rm_scene_host.h's PairLoops.
 // A candidate grid: cell (x, y, z) is the box org + (x - 0.03) * w .. org + (x + 1.03) * w per axis (the host's cell with
 // its 3 % slack; org and w are the host's own binary64 values), its spheres the n entries from `first` on of the launch's
@@ -660,6 +676,10 @@ hipError_t rm_launch_measure_tiles(const RmMeasureTilesArgs &a, unsigned int n_g
 // then parts_measure_kernel over a persistent grid that num_cus bounds (no point: not launched); 0 <= a.n <= 2^30.
 hipError_t rm_launch_label_field(const RmPartsArgs &a, hipStream_t stream, const char **kernel_name);
 hipError_t rm_launch_measure_labels(const RmPartsMeasureArgs &a, int num_cus, hipStream_t stream, const char **kernel_name);
+// The distance transform (rm_edt.hip): edt_rows_kernel<T> over ceil(a.n / RM_MESH_BLOCK) workgroups, edt_axis_kernel along j and
+// along k over a lane per line (an axis of one point: not launched), edt_reduce_kernel and edt_info_kernel; 0 < a.n <= 2^30 and
+// (nu-1)^2 + (nv-1)^2 + (nw-1)^2 <= INT32_MAX - 1.  *kernel_name: edt_axis_kernel, or edt_rows_kernel where no axis pass ran.
+hipError_t rm_launch_edt_field(const RmEdtArgs &a, hipStream_t stream, const char **kernel_name);
 
 // rm_render_frames_device: frame k of n_views is rows [y_start, y_end) of p with views[k] (device table) for p's rot, origin,
 // origin_d and time, its pixels at element k * width * local_rows of every buffer p names (x3 normal, x4 rgba), its diagnostics

@@ -206,6 +206,18 @@ class Scene:
             return self.ctx.parts_box(cells, margin=margin, **more)
         return self.ctx.parts(origin, du, dv, dw, shape, **more)
 
+    def edt(self, origin=None, du=None, dv=None, dw=None, shape=None, iso=0.0, cells=(64, 64, 64), margin=None, side="inside", device=False,
+            exact=True):
+        """How far inside the solid getDistance < iso (side="outside": outside it) every lattice point lies, at this scene's
+        own time -> Edt (Context.edt): `.d2` (squared index distances, exact), `.max_d2`, `.at`, `.inradius`, `.distance()`,
+        `.eroded(r2)`, `.max_by_part(parts)`.  Over the lattice origin + i * du + j * dv + k * dw of `shape` points, or,
+        without one, over the root box in `cells` cells (Context.edt_box)."""
+        self._activate()
+        more = dict(iso=iso, time=self.time, side=side, device=device, exact=exact)
+        if origin is None:
+            return self.ctx.edt_box(cells, margin=margin, **more)
+        return self.ctx.edt(origin, du, dv, dw, shape, **more)
+
     def meshSession(self, origin, du, dv, dw, shape, iso=0.0, lipschitz=1.0):
         """Opens a mesh session on this scene at its own time (Context.mesh_session) and returns it: session.mesh() is
         toMesh(sparse=True, exact=True) over the lattice, and from now on editSpheres / setSphere / insertSphere /

@@ -706,6 +706,72 @@ RM_API int rm_measure_labels_device(rm_ctx *ctx, const rm_lattice *lattice, cons
 RM_API int rm_scene_parts(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t side, int32_t *labels_out, int64_t n_records,
                           rm_measure *records_out, rm_parts_info *info_out);
 
+/* ---- distances: how far inside the solid (or outside it) every lattice point lies, exactly ------------------------------ */
+
+#define RM_EDT_FAR INT32_MAX
+typedef struct rm_edt_info {   /* 32 bytes, 8-byte aligned; every field is written */
+    int64_t n_points;          /* nu * nv * nw */
+    int64_t n_set;             /* points of the set S */
+    int64_t max_d2;            /* the largest d2 over S; 0 when S is empty */
+    int64_t argmax;            /* the smallest linear index of a point of S that attains it; -1 when S is empty */
+} rm_edt_info;
+
+/* The meshers, the measures and the parts ask on which side of iso a point lies; these entries say how far from the other
+ * side it is.  The scene's own fields cannot: the exact field, a minimum over primitives, is exact outside a union and too
+ * small inside it, the operator scenes hold bounds, and a caller's volume holds any values.  The answer here is the exact
+ * Euclidean distance transform of the set on the lattice itself, in integers with one right answer, compared bit for bit with
+ * a numpy restatement (tests/edt_model.py) and, as sqrt(d2), with scipy.ndimage.distance_transform_edt.  The rule:
+ *   set S   exactly the parts' rule with the parts' `side` enum: RM_PARTS_INSIDE is value < iso (NaN is outside, equality is
+ *           outside), RM_PARTS_OUTSIDE the complement, NaN included.  T is the complement of S WITHIN THE LATTICE: points
+ *           beyond the lattice do not exist, they are neither S nor T (scipy's convention).  A solid that touches the border
+ *           is therefore not cut there -- its points at the border are as deep as the nearest lattice point of T says --, so
+ *           a lattice meant to measure thickness leaves a margin around the solid (Context.edt_box does).
+ *   d2      int32[n_points] in the lattice's order: 0 where the point is not in S; where it is, the minimum over the points
+ *           (i', j', k') of T of (i-i')^2 + (j-j')^2 + (k-k')^2.  Where T is empty d2 is RM_EDT_FAR at every point, and
+ *           max_d2 is then RM_EDT_FAR (argmax 0).  These are INDEX units: the entries never read the lattice's steps;
+ *           rm_lattice_cubic says whether, and by which factor, sqrt(d2) is a world distance.
+ *   range   RM_E_UNSUPPORTED when (nu-1)^2 + (nv-1)^2 + (nw-1)^2 > INT32_MAX - 1, so every finite d2 lies below
+ *           RM_EDT_FAR: a cube of 2^30 points is far inside the limit, a row of 46 341 points is the longest line allowed.
+ *   info    rm_edt_info above.
+ *
+ * rm_edt_field_device: d_values as rm_label_field_device takes them (it needs no scene; lattice->time is not used), d_d2
+ * n_points int32 and d_info an rm_edt_info on the device; asynchronous on `stream`, re-entrant, nothing to initialise.  The
+ * squared distance separates by axis, so there are three passes over the resident volume, all in 32-bit integers.  Along i,
+ * membership is one wave ballot and the nearest point of T on either side comes from bit scans of it (a row longer than a
+ * wave walks on through the row's further 64-point segments).  Along j and then along k, one lane per line -- adjacent lanes
+ * adjacent in i -- builds the lower envelope of the line's parabolas by Meijster's two scans, in place; the break point of two
+ * parabolas is a floor division, RM_EDT_FAR marks an absent parabola and is never an addend, and no intermediate exceeds 32
+ * bits.  An axis with one point has no pass: a slice gets the 2-D transform.  A line's envelope is a stack of (position, break
+ * point, value) entries in the context's scratch buffer, laid out like the volume: 8 bytes per lattice point, plus 16 KiB of
+ * partial maxima; max_d2, argmax and n_set are reduced per workgroup and then by one workgroup, without atomics, so nothing
+ * depends on an order.  No thread waits for another and every loop is bounded by the length of its row or line: there is no
+ * give-up flag.  RM_E_INVALID -- ahead of everything else -- for everything rm_label_field_device refuses about the lattice,
+ * the values, value_type, iso and side (more than 2^30 points among it), null d_d2 when the lattice has points, null d_info,
+ * d_d2 not 4-byte or d_info not 8-byte aligned; then the range refusal RM_E_UNSUPPORTED; then RM_E_NO_DEVICE.  Counts of 1 on
+ * an axis are fine.  A lattice with a zero count is RM_OK: info {0, 0, 0, -1}.  rm_last_kernel: edt_axis_kernel (edt_rows_kernel
+ * for a lattice that is a single row, which has no axis pass; unchanged for a lattice without points).
+ *
+ * rm_scene_edt: host-side and synchronous -- the dense volume of the active scene UNDER THE EXACT FIELD whatever option
+ * `exact` says (as rm_scene_parts), the transform and its scratch, all in the context's scratch buffer, then one copy back.
+ * d2_out may be NULL.  The same checks for its own arguments (no alignment is asked of host buffers), the range refusal,
+ * RM_E_NO_DEVICE; RM_E_NO_SCENE last.  Not a render entry: it neither consumes nor fires rm_render_attach_diagnostics and
+ * leaves rm_scene_set_time's value alone.
+ *
+ * rm_lattice_cubic: host-only, no ctx -- whether index distances are world distances up to one factor, and the factor.  All
+ * arithmetic is binary64 of the widened components, one operation at a time; the length of a step is
+ * sqrt((x*x + y*y) + z*z).  Only axes whose count exceeds 1 take part.  *step is the length of the first such axis's step (1.0
+ * when there is none).  RM_OK when every other participating length differs from *step by at most 1e-5 * step and every
+ * pairwise dot product of participating steps is at most 1e-5 * step^2 in magnitude; else RM_E_UNSUPPORTED with *step
+ * untouched.  RM_E_INVALID for a null argument or a lattice rm_scene_field refuses.  Why 1e-5: the binary32 rounding of a
+ * rotated cubic lattice's steps perturbs lengths and dot products by a few 1e-7 relative; 1e-5 leaves an order of magnitude
+ * above that and still bounds the error of a world distance far below the half-cell quantisation of the transform itself.
+ * Out of scope: the nearest point itself (a feature transform), world-metric transforms on non-cubic lattices, a sparse
+ * (tile) path, sub-cell (fractional) distances, local thickness in the Hildebrand-Ruegsegger sense, and the N-API addon. */
+RM_API int rm_edt_field_device(rm_ctx *ctx, const rm_lattice *lattice, const void *d_values, int32_t value_type, double iso,
+                               int32_t side, void *d_d2, void *d_info, void *stream);
+RM_API int rm_scene_edt(rm_ctx *ctx, const rm_lattice *lattice, double iso, int32_t side, int32_t *d2_out, rm_edt_info *info_out);
+RM_API int rm_lattice_cubic(const rm_lattice *lattice, double *step);
+
 /* ---- sharp meshes: vertices from Hermite data (dual contouring's vertex rule) --------------------------------- */
 
 typedef struct rm_sharp_query {  /* 32 bytes */
